@@ -1,20 +1,25 @@
 #!/usr/bin/env python3
 """bench.py -- EM iterations/s of the HIP abundance core on BASELINE.json's headline workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3] [--scale 1.0]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [--config cfg3] [--scale 1.0]
 
 A "step" is one EM pass (E-step + M-step) over one synthetic read->transcript compatibility matrix that is
 already resident in HBM.  N=1: BASELINE config 3 (50M reads x 200k transcripts, mean 5 alignments, -k 100).
 N>1 (torchrun, one rank per GPU): the -M multi-sample path -- every rank solves its OWN independent sample
 of the same shape (different seed), no data-path collective; weak scaling.  The only torch.distributed use
-is the barrier and the max-over-ranks of the timed region.
+is the barrier and the max-over-ranks of the timed region; a one-GPU run does not import torch.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel of the TILED layout, k_pass_tiled_unit
-(+ the small k_update that shares the pass): algorithmic bytes per pass /
-mean device time per pass measured with HIP events on the library's own stream (`frac_actual`: the same with the HBM bytes the PMC
-counters saw, profiles/traffic.json).  After the timed passes: `solve_to_convergence` (the same matrix solved to --solve) and
-`fpkm_delta_vs_oracle` (a down-scaled config 3 solved by both).  `cpu_baseline` times the CPU oracle's OpenMP EM pass on the same
-matrix on this box's host cores (rank 0, N=1 only).
+Prints ONE JSON line (rank 0).  A plain run generates the matrix, uploads it, warms up, times exactly K steps and prints
+`value` (steps/s) and `ms_per_step`.  `roofline` is for the dominant kernel of the TILED layout, k_pass_tiled_unit
+(+ the small k_update that shares the pass): HBM bytes per pass from the committed PMC measurement (profiles/traffic.json) /
+mean device time per pass measured with HIP events on the library's own stream.  --dump-outputs DIR writes theta after the
+last timed step (what a caller of the pass receives) as DIR/theta.npy, float64; the inputs are seeded, so two builds can be
+compared output for output.
+
+--full adds everything else, as separate measurements after the timed steps: the pass kernel's HBM traffic observed by
+rocprofv3 child processes, `solve_to_convergence` (the same matrix solved to --solve), the other row laws and the collapsed
+form of the matrix, `cpu_baseline` (the CPU oracle's OpenMP EM pass on the same matrix, this box's host cores),
+`fpkm_delta_vs_oracle` (a down-scaled config 3 solved by both) and `time_to_mle` (rank 0, N=1 only).
 """
 import argparse
 import json
@@ -39,6 +44,90 @@ def _cfg(args, rank, structure):
         cfg["n_tx"] = max(500, int(cfg["n_tx"] * args.scale))
     cfg["structure"] = structure
     return cfg
+
+
+def _host_threads():
+    # host threads of the CPU-side work: EMSAR_CPU_THREADS (default 16, a one-GPU share of a multi-GPU host), never more than this
+    # process may run on, whatever os.cpu_count() says about the whole machine
+    return min(os.cpu_count() or 1, len(os.sched_getaffinity(0)), int(os.environ.get("EMSAR_CPU_THREADS", "16")))
+
+
+def make_workload(cfg):
+    """synth.make_matrix(**cfg); the family law (the headline) through family_matrix_threaded, which returns the same arrays."""
+    from emsar_amd import synth
+    if cfg["structure"] != "family":
+        return synth.make_matrix(**cfg)
+    c = dict(cfg)
+    del c["structure"]
+    return family_matrix_threaded(**c)
+
+
+def family_matrix_threaded(n_tx, n_reads, law="human", xfam=0.02, seed=1, block=2_000_000, geo_p=None, threads=None):
+    """synth.make_matrix(..., structure="family"), array for array (tests/test_bench_cpu.py), in a fraction of its time: the random
+    stream is drawn on this thread in synth's order, block after block; the tid lookup and the bitmask -> CSR expansion of a
+    block, which draw nothing, run on threads (numpy releases the GIL in them).  One thread needs ~20 s for config 3."""
+    from collections import deque
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    from emsar_amd import synth
+    threads = threads or _host_threads()
+    if geo_p is None and law == "human":
+        geo_p = 0.076                                           # synth._make_matrix_family's default for this law
+    theta, length = synth.make_abundance(n_tx, seed)
+    fam_start, fam_of = synth.make_families(n_tx, seed)
+    cdf = np.cumsum(theta * length)
+    cdf /= cdf[-1]
+    rng = np.random.default_rng(seed + 1000)
+    lens = np.empty(n_reads, dtype=np.int32)
+    cols = [None] * ((n_reads + block - 1) // block)
+
+    def lookup(u):
+        return np.searchsorted(cdf, u, side="right").astype(np.int32)
+
+    def expand(b, n, S, fs, x, extra):
+        bits = np.unpackbits(S.view(np.uint8).reshape(n, 8), axis=1, bitorder="little")
+        row, bit = np.nonzero(bits)                       # row-major: CSR order, members ascending inside a row
+        del bits
+        kk = np.bincount(row, minlength=n).astype(np.int32)
+        tot = kk + x.astype(np.int32)
+        lens[b * block:b * block + n] = tot
+        rp = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(tot, out=rp[1:])
+        rp_main = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(kk, out=rp_main[1:])
+        c = np.empty(int(rp[-1]), dtype=np.int32)
+        c[rp[row] + (np.arange(len(row), dtype=np.int64) - rp_main[row])] = fs[row] + bit.astype(np.int32)
+        c[rp[1:][x] - 1] = extra                          # the extra cross-family hit sits in the last slot of its row
+        cols[b] = c
+
+    with ThreadPoolExecutor(threads) as lookups, ThreadPoolExecutor(threads) as expanders:
+        pending = deque()
+        for b in range(len(cols)):
+            n = min(block, n_reads - b * block)
+            t0 = np.concatenate(list(lookups.map(lookup, np.array_split(rng.random(n), threads))))
+            np.minimum(t0, n_tx - 1, out=t0)
+            k = synth._draw_k(rng, n, law, geo_p)
+            S, fs = synth._family_subsets(rng, t0, k, fam_start, fam_of)
+            x = (rng.random(n) < xfam) if xfam > 0 else np.zeros(n, dtype=bool)
+            extra = rng.integers(0, n_tx, int(x.sum()), dtype=np.int32)
+            pending.append(expanders.submit(expand, b, n, S, fs, x, extra))
+            while len(pending) > threads:                 # bounds the host memory of the blocks in flight
+                pending.popleft().result()
+        while pending:
+            pending.popleft().result()
+    col_idx = np.concatenate(cols) if len(cols) > 1 else cols[0]
+    del cols
+    row_ptr = np.zeros(n_reads + 1, dtype=np.uint64)
+    np.cumsum(lens, out=row_ptr[1:], dtype=np.uint64)
+    return {"n_tx": n_tx, "n_reads": n_reads, "row_ptr": row_ptr, "col_idx": col_idx, "den": length / 1e3 * (n_reads / 1e6),
+            "theta_true": theta, "fam_start": fam_start}
+
+
+def dump_outputs(out_dir, theta):
+    """--dump-outputs: what the timed path computed in its last step (theta after pass W + K, float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "theta.npy"), np.ascontiguousarray(theta, dtype=np.float64))
 
 
 def _traffic(args, structure, layout_name):
@@ -230,32 +319,45 @@ def main():
     ap.add_argument("--solve-floor", type=float, default=1e-2,
                     help="abs_floor of the stopping rule max|dtheta|/(theta+floor) in FPKM; boundary components decay like 1/k, "
                          "so a floor at the print quantum (1e-6) is only reachable on small problems")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write theta after the last one to DIR/theta.npy (float64; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline: observed HBM traffic (rocprofv3 child processes), the solve to "
+                         "--solve, the other row laws and the collapsed form, the CPU baseline, the FPKM delta against the oracle and "
+                         "time to MLE (the --no-* options and --solve 0 leave parts of them out)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
-    import torch
-    from emsar_amd import EmsarHip, synth
+    from emsar_amd import EmsarHip, EmsarHipError
     from emsar_amd import dist as D
     from emsar_amd.hip import LAYOUT_AUTO, LAYOUT_CSR
 
     rank, world, local_rank = D.env_rank()
-    if not torch.cuda.is_available():
-        sys.exit("bench.py needs a GPU (the HIP path has no CPU fallback)")
     # rehearsal knobs (one-GPU box): EMSAR_BENCH_BACKEND=gloo EMSAR_BENCH_DEVICE=0 lets several ranks share a card
     backend = os.environ.get("EMSAR_BENCH_BACKEND", "nccl")
     if "EMSAR_BENCH_DEVICE" in os.environ:
         local_rank = int(os.environ["EMSAR_BENCH_DEVICE"])
-    torch.cuda.set_device(local_rank)
-    # RCCL (backend "nccl"); used for the barrier and the max-over-ranks of the timed region only
-    group = D.Group(backend, torch.device("cuda", local_rank) if backend == "nccl" else None)
+    torch = None
+    if world > 1:
+        import torch
+        if not torch.cuda.is_available():
+            sys.exit("bench.py needs a GPU (the HIP path has no CPU fallback)")
+        torch.cuda.set_device(local_rank)
+    # RCCL (backend "nccl"); used for the barrier and the max-over-ranks of the timed region only (one process: no group)
+    group = D.Group(backend, torch.device("cuda", local_rank) if torch is not None and backend == "nccl" else None)
 
     # ---- workload: one independent sample per rank ------------------------------------------------------
     t0 = time.time()
-    s = synth.make_matrix(**_cfg(args, rank, args.structure))
+    s = make_workload(_cfg(args, rank, args.structure))
     t_gen = time.time() - t0
     nnz = int(len(s["col_idx"]))
     layout = {"auto": LAYOUT_AUTO, "csr": LAYOUT_CSR, "tiled": 3}[args.layout]
-    dev = EmsarHip(local_rank)
+    try:
+        dev = EmsarHip(local_rank)
+    except EmsarHipError as e:
+        sys.exit("bench.py needs a GPU (the HIP path has no CPU fallback): %s" % e)
     t0 = time.time()
     collapsed_main = None
     if args.collapsed:
@@ -270,10 +372,11 @@ def main():
     t_up = time.time() - t0
     info = dev.info()
 
-    def barrier():
-        torch.cuda.synchronize()
-        group.barrier()
-        torch.cuda.synchronize()
+    def barrier():                            # one process: run_passes has already synchronised the library's stream
+        if torch is not None:
+            torch.cuda.synchronize()
+            group.barrier()
+            torch.cuda.synchronize()
 
     # ---- spin-up (clocks), warmup, then exactly K timed steps --------------------------------------------------
     t_spin = time.perf_counter()
@@ -293,9 +396,12 @@ def main():
     th = dev.get_theta()
     mass = float((th * s["den"]).sum())
     ok = bool(np.isfinite(th).all() and abs(mass - s["n_reads"]) <= 1e-8 * s["n_reads"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, th)
 
+    # ---- --full: what the headline does not need, each measured on its own after the timed steps --------------------------
     solve = None
-    if args.solve > 0:
+    if args.full and args.solve > 0:
         # the whole solve of the benchmarked matrix: SQUAREM-accelerated EM from the uniform start until the plain EM step moves no
         # component by more than tol relative to (theta + abs_floor); streaming passes (a read-level matrix is one connected set)
         t0 = time.perf_counter()
@@ -306,9 +412,9 @@ def main():
                  "mass_conserved": bool(abs(float((th_s * s["den"]).sum()) - s["n_reads"]) <= 1e-8 * s["n_reads"])}
     live, live_why = None, "not requested"
     under_profiler = any(k.startswith("ROCPROF") for k in os.environ)          # this process is itself being profiled (tools/prof_round.sh)
-    if nnz > 1.5e9 and not args.no_live_pmc:
+    if args.full and nnz > 1.5e9 and not args.no_live_pmc:
         live_why = "skipped above 1.5e9 nonzeros (the matrix would be written out and uploaded twice more)"
-    elif rank == 0 and world == 1 and not args.no_live_pmc and info["layout"] != 1 and not under_profiler:
+    elif args.full and rank == 0 and world == 1 and not args.no_live_pmc and info["layout"] != 1 and not under_profiler:
         t0 = time.time()
         if args.collapsed:
             live, live_why = live_traffic(local_rank, s["n_tx"], rp_c, ci_c, s["den"], layout, wgt=w_c)
@@ -340,10 +446,10 @@ def main():
             out["config"]["collapsed"] = collapsed_main
         if solve is not None:
             out["solve_to_convergence"] = solve
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(s, nnz)
     # ---- the other forms of the same config (rank 0, N = 1): the other row laws, and the collapsed (segment-level) form -----------
-    if rank == 0 and world == 1 and not args.no_variants and not args.collapsed and not args.merge_rows:
+    if args.full and rank == 0 and world == 1 and not args.no_variants and not args.collapsed and not args.merge_rows:
         variants = {args.structure: {"ms_per_pass": kernel_ms / args.steps, "nnz": nnz, **_variant_stats(info),
                                      "roofline_frac": out["roofline"]["frac"], "hbm_traffic_bytes": out["roofline"]["traffic"],
                                      "traffic_observed_in_this_run": live is not None}}
@@ -354,12 +460,12 @@ def main():
             if st_name == "family_shuffled" and args.structure == "family":
                 v = shuffled_copy(s)                      # the same matrix, transcripts numbered at random
             else:
-                v = synth.make_matrix(**_cfg(args, rank, st_name))
+                v = make_workload(_cfg(args, rank, st_name))
             variants[st_name] = time_variant(args, dev, v, st_name)
             del v
         out["workload_variants"] = variants
     dev.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["fpkm_delta_vs_oracle"] = fpkm_delta_vs_oracle(local_rank, args.config, args.structure)
         out["time_to_mle"] = time_to_mle(local_rank)
     group.close()
@@ -433,9 +539,7 @@ def cpu_baseline(s, nnz):
     """The CPU oracle's EM pass (oracle/em_oracle.c, OpenMP) on the same matrix, bounded to ~10-30 s."""
     import numpy as np
     import oracle as O
-    # a one-GPU box owns a 16-core share of its host (the pool's rule for worker counts); never more threads
-    # than that, whatever os.cpu_count() says about the whole machine
-    cores = min(os.cpu_count() or 1, len(os.sched_getaffinity(0)), int(os.environ.get("EMSAR_CPU_THREADS", "16")))
+    cores = _host_threads()
     m = O.Csr(s["n_tx"], s["row_ptr"], s["col_idx"])
     th = np.ones(s["n_tx"])
     th, _ = m.em_step(th, s["den"], n_threads=cores)     # untimed warm pass
@@ -459,7 +563,7 @@ def fpkm_delta_vs_oracle(device, config, structure="family"):
     scale = {"cfg2": 0.02, "cfg3": 0.004, "cfg4": 0.01, "cfg5": 0.0005}.get(config, 0.004)
     s = synth.make_config(config, scale, structure)
     m = O.Csr(s["n_tx"], s["row_ptr"], s["col_idx"])
-    cores = min(os.cpu_count() or 1, len(os.sched_getaffinity(0)), int(os.environ.get("EMSAR_CPU_THREADS", "16")))
+    cores = _host_threads()
     th_o, st_o = m.em_solve(max_iter=200000, accel=1, tol=1e-9, n_threads=cores)
     with EmsarHip(device) as dev:
         dev.upload_structure(s["n_tx"], s["row_ptr"], s["col_idx"])
@@ -489,7 +593,7 @@ def time_to_mle(device):
     # counts drawn from the model itself: theta* ~ LogNormal(0, 2) with 30 % zeros, R_c ~ Poisson(E_c * sum theta*)
     theta_true = np.where(rng.random(n_tx) < 0.3, 0.0, rng.lognormal(0.0, 2.0, size=n_tx))
     R = rng.poisson(E * np.add.reduceat(theta_true[ci], rp[:-1].astype(np.int64))).astype(np.int32)
-    cores = min(os.cpu_count() or 1, len(os.sched_getaffinity(0)), int(os.environ.get("EMSAR_CPU_THREADS", "16")))
+    cores = _host_threads()
     m = O.Csr(n_tx, rp, ci, R=R, E=E, L=E)
     n_sets, cs, ts, _ = m.components()
     t0 = time.perf_counter()
