@@ -15,6 +15,7 @@
 //   kernels_vector.hpp    k_update, k_update_p2/p3, k_sq_extrap_ll (SQUAREM extrapolation / acceptance on the device),
 //                         k_normalise, k_adj_euma, small reductions
 //   kernels_sets.hpp      k_solve_sets                           one workgroup solves one connected set out of LDS
+//   kernels_boot.hpp      k_boot_draw, k_boot_accum, ...         the Poisson bootstrap (draws: boot_rng.hpp; sets: k_solve_sets_boot)
 //   collapse.hip          read-level rows -> weighted segments (own translation unit)
 #include <hip/hip_runtime.h>
 
@@ -31,6 +32,7 @@
 #include "layout.hpp"
 #include "layout_tiled.hpp"
 #include "sets.hpp"
+#include "boot_rng.hpp"
 #include "internal.hpp"
 
 #include "kernels_common.hpp"
@@ -39,6 +41,7 @@
 #include "kernels_vector.hpp"
 #include "kernels_sets.hpp"
 #include "kernels_cluster.hpp"
+#include "kernels_boot.hpp"
 
 // ==================================================================================================
 // context
@@ -119,6 +122,11 @@ struct emsar_hip_ctx {
     double sets_build_ms = 0.0;
     // compute_adjEUMA on the device
     int32_t *d_euma_t = nullptr; int32_t nfl = 0; double *d_wf = nullptr, *d_adj = nullptr;
+    // bootstrap (emsar_hip_bootstrap): the sample's row weights in caller order and the draw map of the set solver, built on first use
+    int32_t *d_boot_R = nullptr;
+    int64_t *d_boot_slot = nullptr;   // caller row -> index into one replicate's [row_w | usum] block, -1 = none
+    int64_t boot_n_rw = 0;            // row_w entries of the resident sets (usum follows them)
+    bool boot_slot_ready = false;
 };
 
 namespace {
@@ -173,6 +181,8 @@ void free_sets(emsar_hip_ctx *ctx) {
     ctx->d_cdesc = nullptr; ctx->d_cblk = ctx->d_crp = ctx->d_ccp = ctx->d_cpart = nullptr; ctx->d_cent = ctx->d_ccrow = nullptr;
     ctx->d_cg_tid = nullptr; ctx->d_cg_u = ctx->d_crow_w = ctx->d_cscratch = nullptr; ctx->d_cbar = nullptr; ctx->d_cstat = nullptr; ctx->n_cstat = 0;
     ctx->RS = emsar::ResidentSets(); ctx->sets_ready = false; ctx->n_sstat = 0;
+    dfree(ctx->d_boot_R); dfree(ctx->d_boot_slot); ctx->d_boot_R = nullptr; ctx->d_boot_slot = nullptr;
+    ctx->boot_n_rw = 0; ctx->boot_slot_ready = false;
 }
 
 void free_structure(emsar_hip_ctx *ctx) {
@@ -337,6 +347,61 @@ struct CycleGraph {
         if (graph) (void)hipGraphDestroy(graph);
     }
 };
+
+// The streaming layout's row weights from per-row weights x(r) (caller order, 0 = outside the likelihood): TILED -- the slots (a merged
+// slot sums its member rows), the leftover rows and the per-transcript count of the folded single-transcript rows; CSR -- the rows as
+// they are.  w / wl are filled only when `weighted`.  With row_E, llc += sum x log E over the rows with x > 0.  Used by upload_sample
+// and by the bootstrap, which swaps a replicate's weights in.  ERR_ARG if a merged slot's sum exceeds INT32_MAX.
+struct LayoutWeights { std::vector<int32_t> w, wl; std::vector<double> u; };
+template <class WeightOf>
+int layout_weights(const emsar_hip_ctx *ctx, const WeightOf &weight_of, const double *row_E, bool weighted, LayoutWeights &out, double &llc) {
+    if (ctx->layout != EMSAR_LAYOUT_TILED) {
+        if (!weighted) return EMSAR_HIP_OK;
+        out.w.assign(std::max<size_t>((size_t)ctx->n_rows, 1), 0);
+        for (int64_t r = 0; r < ctx->n_rows; r++) {
+            const int32_t x = weight_of(r);
+            out.w[(size_t)r] = x;
+            if (x > 0 && row_E) llc += (double)x * std::log(row_E[r]);
+        }
+        return EMSAR_HIP_OK;
+    }
+    const auto &L = ctx->TL;
+    out.u.assign((size_t)ctx->n_tx, 0.0);
+    for (size_t i = 0; i < L.single_row.size(); i++) {
+        int32_t x = weight_of(L.single_row[i]);
+        out.u[(size_t)L.single_tid[i]] += (double)x;
+        if (x > 0 && row_E) llc += (double)x * std::log(row_E[L.single_row[i]]);
+    }
+    if (!weighted) return EMSAR_HIP_OK;
+    out.w.assign((size_t)std::max<int64_t>(ctx->n_slots, 1), 0);
+    out.wl.assign((size_t)std::max<int64_t>(ctx->n_left, 1), 0);
+    for (int64_t i = 0; i < ctx->n_slots; i++) {
+        int64_t r = L.slot_row[(size_t)i];
+        if (r < 0) continue;
+        if (L.merged) {                                   // a slot stands for all rows with this tid multiset
+            int64_t sum = 0;
+            for (uint64_t q = L.mem_ptr[(size_t)r]; q < L.mem_ptr[(size_t)r + 1]; q++) {
+                int64_t o = L.mem_row[(size_t)q];
+                int32_t x = weight_of(o);
+                sum += x;
+                if (x > 0 && row_E) llc += (double)x * std::log(row_E[o]);
+            }
+            if (sum > INT32_MAX) return EMSAR_HIP_ERR_ARG;
+            out.w[(size_t)i] = (int32_t)sum;
+            continue;
+        }
+        int32_t x = weight_of(r);
+        out.w[(size_t)i] = x;
+        if (x > 0 && row_E) llc += (double)x * std::log(row_E[r]);
+    }
+    for (int64_t i = 0; i < ctx->n_left; i++) {
+        int64_t r = L.left_row[(size_t)i];
+        int32_t x = weight_of(r);
+        out.wl[(size_t)i] = x;
+        if (x > 0 && row_E) llc += (double)x * std::log(row_E[r]);
+    }
+    return EMSAR_HIP_OK;
+}
 
 // scatter a per-row value (original row order, host) to its columns: out[t] = sum_c m_ct val[c]
 int scatter_rows(emsar_hip_ctx *ctx, const double *val_host, double *d_out) {
@@ -745,58 +810,25 @@ int emsar_hip_upload_sample(emsar_hip_ctx *ctx, const int32_t *row_weight, const
         ctx->fx_mass = std::ldexp(1.0, 61 - e_mass);
         ctx->fx_ll = std::ldexp(1.0, 61 - e_ll);
     } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    if (ctx->layout == EMSAR_LAYOUT_TILED) {
-        const auto &L = ctx->TL;
-        dfree(ctx->d_left_wgt); ctx->d_left_wgt = nullptr;
-        std::vector<double> u((size_t)ctx->n_tx, 0.0);
-        for (size_t i = 0; i < L.single_row.size(); i++) {
-            int32_t x = weight_of(L.single_row[i]);
-            u[(size_t)L.single_tid[i]] += (double)x;
-            if (x > 0 && row_E) ctx->loglik_const += (double)x * std::log(row_E[L.single_row[i]]);
-        }
-        HIPCHK(hipMemcpy(ctx->d_u, u.data(), u.size() * 8, hipMemcpyHostToDevice));
-        if (ctx->weighted) {
-            std::vector<int32_t> w((size_t)std::max<int64_t>(ctx->n_slots, 1), 0), wl((size_t)std::max<int64_t>(ctx->n_left, 1), 0);
-            for (int64_t i = 0; i < ctx->n_slots; i++) {
-                int64_t r = L.slot_row[(size_t)i];
-                if (r < 0) continue;
-                if (L.merged) {                                   // a slot stands for all rows with this tid multiset
-                    int64_t sum = 0;
-                    for (uint64_t q = L.mem_ptr[(size_t)r]; q < L.mem_ptr[(size_t)r + 1]; q++) {
-                        int64_t o = L.mem_row[(size_t)q];
-                        int32_t x = weight_of(o);
-                        sum += x;
-                        if (x > 0 && row_E) ctx->loglik_const += (double)x * std::log(row_E[o]);
-                    }
-                    if (sum > INT32_MAX) return EMSAR_HIP_ERR_ARG;
-                    w[(size_t)i] = (int32_t)sum;
-                    continue;
-                }
-                int32_t x = weight_of(r);
-                w[(size_t)i] = x;
-                if (x > 0 && row_E) ctx->loglik_const += (double)x * std::log(row_E[r]);
+    {
+        LayoutWeights LW;
+        try {
+            const int rc = layout_weights(ctx, weight_of, row_E, ctx->weighted, LW, ctx->loglik_const);
+            if (rc) return rc;
+        } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+        if (ctx->layout == EMSAR_LAYOUT_TILED) {
+            dfree(ctx->d_left_wgt); ctx->d_left_wgt = nullptr;
+            HIPCHK(hipMemcpy(ctx->d_u, LW.u.data(), LW.u.size() * 8, hipMemcpyHostToDevice));
+            if (ctx->weighted) {
+                HIPCHK(hipMalloc(&ctx->d_wgt, LW.w.size() * 4));
+                HIPCHK(hipMemcpy(ctx->d_wgt, LW.w.data(), LW.w.size() * 4, hipMemcpyHostToDevice));
+                HIPCHK(hipMalloc(&ctx->d_left_wgt, LW.wl.size() * 4));
+                HIPCHK(hipMemcpy(ctx->d_left_wgt, LW.wl.data(), LW.wl.size() * 4, hipMemcpyHostToDevice));
             }
-            for (int64_t i = 0; i < ctx->n_left; i++) {
-                int64_t r = L.left_row[(size_t)i];
-                int32_t x = weight_of(r);
-                wl[(size_t)i] = x;
-                if (x > 0 && row_E) ctx->loglik_const += (double)x * std::log(row_E[r]);
-            }
-            HIPCHK(hipMalloc(&ctx->d_wgt, w.size() * 4));
-            HIPCHK(hipMemcpy(ctx->d_wgt, w.data(), w.size() * 4, hipMemcpyHostToDevice));
-            HIPCHK(hipMalloc(&ctx->d_left_wgt, wl.size() * 4));
-            HIPCHK(hipMemcpy(ctx->d_left_wgt, wl.data(), wl.size() * 4, hipMemcpyHostToDevice));
+        } else if (ctx->weighted) {
+            HIPCHK(hipMalloc(&ctx->d_wgt, LW.w.size() * 4));
+            HIPCHK(hipMemcpy(ctx->d_wgt, LW.w.data(), LW.w.size() * 4, hipMemcpyHostToDevice));
         }
-    } else if (ctx->weighted) {
-        std::vector<int32_t> w(std::max<size_t>((size_t)n_rows, 1), 0);
-        for (int64_t r = 0; r < n_rows; r++) {
-            int32_t x = row_weight ? row_weight[r] : 1;
-            if (row_E && row_E[r] == 0.0) x = 0;
-            w[(size_t)r] = x;
-            if (x > 0 && row_E) ctx->loglik_const += (double)x * std::log(row_E[r]);
-        }
-        HIPCHK(hipMalloc(&ctx->d_wgt, w.size() * 4));
-        HIPCHK(hipMemcpy(ctx->d_wgt, w.data(), w.size() * 4, hipMemcpyHostToDevice));
     }
     if (den) {
         std::vector<double> tmp;
@@ -869,6 +901,24 @@ int emsar_hip_run_passes(emsar_hip_ctx *ctx, int32_t n_passes, float *elapsed_ms
 }
 
 static int solve_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpkm_out, emsar_em_stats *stats);
+// the caller's parameters with the defaults filled in
+static emsar_em_params solve_params(const emsar_em_params *pp) {
+    emsar_em_params p = pp ? *pp : emsar_em_params{0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (p.max_iter <= 0) p.max_iter = 100000;
+    if (p.tol <= 0) p.tol = 1e-10;
+    if (p.abs_floor <= 0) p.abs_floor = 1e-6;
+    if (p.check_every <= 0) p.check_every = 8;
+    return p;
+}
+// what the resident sets get of them
+static SetSolveParams set_params(const emsar_em_params &p) {
+    // zero_cut / abs_step exist because a boundary optimum is approached like 1/k by the EM; the sets that get Newton steps reach it
+    // in a few steps and are held to the strict rule (same pass counts with and without the two rules on every problem measured,
+    // and then nothing is printed differently); the rules stay in force for the streamed part and with newton_after < 0
+    const bool strict_sets = p.newton_after >= 0;
+    return SetSolveParams{p.tol, p.abs_floor, p.count_floor, (!strict_sets && p.zero_cut > 0.0) ? p.zero_cut : 0.0,
+                          (!strict_sets && p.abs_step > 0.0) ? p.abs_step : 0.0, p.max_iter, p.accel, p.newton_after == 0 ? 60 : p.newton_after};
+}
 int emsar_hip_solve(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpkm_out, emsar_em_stats *stats) {
     if (!ctx || !fpkm_out) return EMSAR_HIP_ERR_ARG;
     if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
@@ -877,11 +927,7 @@ int emsar_hip_solve(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpkm_
     return rc;
 }
 static int solve_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpkm_out, emsar_em_stats *stats) {
-    emsar_em_params p = pp ? *pp : emsar_em_params{0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (p.max_iter <= 0) p.max_iter = 100000;
-    if (p.tol <= 0) p.tol = 1e-10;
-    if (p.abs_floor <= 0) p.abs_floor = 1e-6;
-    if (p.check_every <= 0) p.check_every = 8;
+    emsar_em_params p = solve_params(pp);
     if (!(p.count_floor >= 0.0)) return EMSAR_HIP_ERR_ARG;
     if (p.set_mode != 0 && p.set_mode != 1) return EMSAR_HIP_ERR_ARG;
     ctx->count_floor = p.count_floor;
@@ -942,12 +988,7 @@ static int solve_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpk
     ctx->delta_mask = nullptr;
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     if (use_sets) {
-        // zero_cut / abs_step exist because a boundary optimum is approached like 1/k by the EM; the sets that get Newton steps reach it
-        // in a few steps and are held to the strict rule (same pass counts with and without the two rules on every problem measured,
-        // and then nothing is printed differently); the rules stay in force for the streamed part and with newton_after < 0
-        const bool strict_sets = p.newton_after >= 0;
-        SetSolveParams P{p.tol, p.abs_floor, p.count_floor, (!strict_sets && p.zero_cut > 0.0) ? p.zero_cut : 0.0,
-                         (!strict_sets && p.abs_step > 0.0) ? p.abs_step : 0.0, p.max_iter, p.accel, p.newton_after == 0 ? 60 : p.newton_after};
+        const SetSolveParams P = set_params(p);
         // the cluster solver has no Newton step: its sets keep the two print-quantum rules whatever newton_after says (with the strict rule
         // alone a boundary optimum keeps a cluster going for 10^5 passes at ~32 us each)
         SetSolveParams Pc = P;
@@ -1023,6 +1064,307 @@ static int solve_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpk
             if (ctx->n_cstat > 0) { float mc = 0; HIPCHK(hipEventElapsedTime(&mc, ctx->ev_c0, ctx->ev_c1)); stats->cluster_kernel_ms = mc; }
         }
     }
+    return EMSAR_HIP_OK;
+}
+
+// ---- bootstrap --------------------------------------------------------------------------------------------------------------
+// The sample's row weights in caller order on the device (the draws' R) and, for the set solver, the draw map: build_sets run again
+// on the same weights with the map asked for -- the same code that filled row_w / usum, so the same sets, merged rows and slots.
+static int boot_prepare(emsar_hip_ctx *ctx, bool want_slot) {
+    const size_t n = (size_t)std::max<int64_t>(ctx->n_rows, 1);
+    if (!ctx->d_boot_R) {
+        HIPCHK(hipMalloc(&ctx->d_boot_R, n * 4));
+        if (ctx->n_rows) HIPCHK(hipMemcpy(ctx->d_boot_R, ctx->h_wgt.data(), (size_t)ctx->n_rows * 4, hipMemcpyHostToDevice));
+    }
+    if (!want_slot || ctx->boot_slot_ready) return EMSAR_HIP_OK;
+    try {
+        emsar::ResidentSets S;
+        std::vector<int64_t> slot;
+        emsar::build_sets(ctx->n_rows, ctx->n_tx, ctx->h_row_ptr.data(), ctx->h_col.data(), ctx->h_wgt.data(), S, &slot);
+        const int64_t n_rw = (int64_t)S.row_w.size();
+        // the resident records on the device are those of ensure_sets: same input, same builder
+        size_t rw_dev = 0;
+        for (int c = 0; c < emsar::kSetClasses; c++) for (const auto &d : S.desc[c]) rw_dev += d.n_r;
+        if (rw_dev != (size_t)n_rw || S.n_resident() != ctx->RS.n_resident()) { ctx->err = "bootstrap: draw map does not match the sets"; return EMSAR_HIP_ERR_HIP; }
+        const auto &m = tid_map(ctx);
+        const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !m.empty();
+        for (auto &v : slot)
+            if (v <= -2) { const int64_t t = -2 - v; v = n_rw + (remap ? m[(size_t)t] : t); }   // usum entry, library numbering
+        HIPCHK(hipMalloc(&ctx->d_boot_slot, n * 8));
+        if (ctx->n_rows) HIPCHK(hipMemcpy(ctx->d_boot_slot, slot.data(), (size_t)ctx->n_rows * 8, hipMemcpyHostToDevice));
+        ctx->boot_n_rw = n_rw;
+    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+    ctx->boot_slot_ready = true;
+    return EMSAR_HIP_OK;
+}
+
+// Swap per-row weights x (caller order) into the streaming layout, as upload_sample would place them (den and E unchanged), with the
+// deterministic mode's fixed-point scales taken from their own total.  x = the sample's own weights (h_wgt) restores the sample.
+static int boot_stream_weights(emsar_hip_ctx *ctx, const int32_t *x) {
+    LayoutWeights LW;
+    double llc = 0.0;
+    int64_t total = 0;
+    try {
+        const int rc = layout_weights(ctx, [&](int64_t r) { return x[r]; }, nullptr, true, LW, llc);
+        if (rc) return rc;
+    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+    for (int64_t r = 0; r < ctx->n_rows; r++) total += x[r];
+    int e_mass = 0, e_ll = 0;
+    (void)std::frexp((double)total + 1.0, &e_mass);
+    (void)std::frexp(((double)total + 1.0) * 1024.0, &e_ll);
+    ctx->fx_mass = std::ldexp(1.0, 61 - e_mass);
+    ctx->fx_ll = std::ldexp(1.0, 61 - e_ll);
+    if (!ctx->d_wgt) HIPCHK(hipMalloc(&ctx->d_wgt, LW.w.size() * 4));
+    HIPCHK(hipMemcpy(ctx->d_wgt, LW.w.data(), LW.w.size() * 4, hipMemcpyHostToDevice));
+    if (ctx->layout == EMSAR_LAYOUT_TILED) {
+        if (!ctx->d_left_wgt) HIPCHK(hipMalloc(&ctx->d_left_wgt, LW.wl.size() * 4));
+        HIPCHK(hipMemcpy(ctx->d_left_wgt, LW.wl.data(), LW.wl.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ctx->d_u, LW.u.data(), LW.u.size() * 8, hipMemcpyHostToDevice));
+    }
+    ctx->weighted = true;
+    return EMSAR_HIP_OK;
+}
+
+// what a bootstrap call changes in the context, put back whatever the exit
+struct BootRestore {
+    emsar_hip_ctx *ctx;
+    bool weighted, swapped = false;
+    double fx_mass, fx_ll;
+    double *d_th0 = nullptr;               // the current point before the call
+    std::vector<void *> bufs;              // device buffers of the call
+    int rc = EMSAR_HIP_OK;
+    explicit BootRestore(emsar_hip_ctx *c) : ctx(c), weighted(c->weighted), fx_mass(c->fx_mass), fx_ll(c->fx_ll) {}
+    ~BootRestore() {
+        (void)hipStreamSynchronize(ctx->stream);
+        if (swapped) {
+            rc = boot_stream_weights(ctx, ctx->h_wgt.data());
+            if (!weighted) {
+                dfree(ctx->d_wgt); ctx->d_wgt = nullptr;
+                if (ctx->layout == EMSAR_LAYOUT_TILED) { dfree(ctx->d_left_wgt); ctx->d_left_wgt = nullptr; }
+            }
+            ctx->weighted = weighted;
+        }
+        ctx->fx_mass = fx_mass; ctx->fx_ll = fx_ll;
+        ctx->count_floor = 0.0; ctx->zero_cut = 0.0; ctx->delta_mask = nullptr;
+        if (d_th0) {
+            (void)hipMemcpy(ctx->d_th[0], d_th0, (size_t)ctx->n_tx * 8, hipMemcpyDeviceToDevice);
+            dfree(d_th0);
+        }
+        for (void *p : bufs) dfree(p);
+    }
+    hipError_t alloc(void **p, size_t bytes) {
+        hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
+        if (e == hipSuccess) bufs.push_back(*p);
+        return e;
+    }
+};
+
+static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_t seed, int32_t first, int32_t n_rep, double *fpkm_mean,
+                          double *fpkm_sd, double *tpm_sd, double *replicates, emsar_boot_stats *stats) {
+    const auto tw0 = std::chrono::steady_clock::now();
+    emsar_em_params p = solve_params(pp);
+    if (!(p.count_floor >= 0.0) || (p.set_mode != 0 && p.set_mode != 1)) return EMSAR_HIP_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    int rc;
+    bool use_sets = p.set_mode == 0;
+    if (use_sets && (rc = ensure_sets(ctx))) return rc;
+    if (use_sets && ctx->RS.giant) use_sets = false;
+    // the streaming passes solve what the set solver does not cover: everything, the streamed sets, the cluster sets
+    const bool need_stream = !use_sets || ctx->RS.n_streamed_sets > 0 || ctx->n_cstat > 0;
+    if ((rc = boot_prepare(ctx, use_sets))) return rc;
+    const int n = ctx->n_tx;
+    const int64_t n_rows = ctx->n_rows;
+    const int64_t n_rw = use_sets ? ctx->boot_n_rw : 0, slot_stride = n_rw + n;
+    const auto &S = ctx->RS;
+    const int64_t n_sets = use_sets ? S.n_resident() : 0;
+    int64_t n_gu = 0;
+    if (use_sets) for (int c = 0; c < emsar::kSetClasses; c++) for (const auto &d : S.desc[c]) n_gu += d.n_t;
+    // replicates per batch: what fits a quarter of the free device memory (at most 2 GiB), EMSAR_HIP_BOOT_BATCH overrides
+    const int64_t per_rep = 8 * (slot_stride + n_gu + n + 1) + (need_stream ? 4 * n_rows : 0) + (int64_t)sizeof(SetStat) * n_sets;
+    size_t mfree = 0, mtotal = 0;
+    if (hipMemGetInfo(&mfree, &mtotal) != hipSuccess) mfree = (size_t)1 << 30;
+    const int64_t budget = std::min<int64_t>((int64_t)(mfree / 4), (int64_t)2 << 30);
+    int64_t batch = std::max<int64_t>(1, budget / std::max<int64_t>(per_rep, 1));
+    if (const char *e = getenv("EMSAR_HIP_BOOT_BATCH")) { if (atoi(e) >= 1) batch = atoi(e); }
+    batch = std::min<int64_t>(std::min<int64_t>(batch, n_rep), 65535);
+    BootRestore guard(ctx);
+    double *d_slots = nullptr, *d_gu = nullptr, *d_thb = nullptr, *d_sums = nullptr, *d_acc4 = nullptr;
+    int32_t *d_wb = nullptr;
+    SetStat *d_bstat = nullptr;
+    HIPCHK(guard.alloc((void **)&d_slots, (size_t)(batch * slot_stride) * 8));
+    HIPCHK(guard.alloc((void **)&d_gu, (size_t)(batch * n_gu) * 8));
+    HIPCHK(guard.alloc((void **)&d_thb, (size_t)(batch * n) * 8));
+    HIPCHK(guard.alloc((void **)&d_sums, (size_t)batch * 8));
+    HIPCHK(guard.alloc((void **)&d_acc4, (size_t)4 * n * 8));
+    if (need_stream) HIPCHK(guard.alloc((void **)&d_wb, (size_t)(batch * n_rows) * 4));
+    if (n_sets) HIPCHK(guard.alloc((void **)&d_bstat, (size_t)(batch * n_sets) * sizeof(SetStat)));
+    HIPCHK(hipMalloc(&guard.d_th0, std::max<size_t>((size_t)n, 1) * 8));
+    HIPCHK(hipMemcpyAsync(guard.d_th0, ctx->d_th[0], (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(d_acc4, 0, (size_t)4 * n * 8, ctx->stream));
+    hipEvent_t e[2] = {nullptr, nullptr};
+    struct EvFree { hipEvent_t *e; ~EvFree() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evfree{e};
+    HIPCHK(hipEventCreate(&e[0])); HIPCHK(hipEventCreate(&e[1]));
+    auto lap = [&](double &acc) -> int { float ms = 0; HIPCHK(hipEventRecord(e[1], ctx->stream)); HIPCHK(hipEventSynchronize(e[1]));
+                                         HIPCHK(hipEventElapsedTime(&ms, e[0], e[1])); acc += ms; return EMSAR_HIP_OK; };
+    double draw_ms = 0, sets_ms = 0, stream_ms = 0, reduce_ms = 0;
+    int32_t unconverged = 0, passes_max = 0;
+    const SetSolveParams P = set_params(p);
+    if (n_sets) {
+        HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets_boot<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[0]));
+        HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets_boot<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[1]));
+        HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets_boot<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[2]));
+    }
+    std::vector<int32_t> h_wb(need_stream ? (size_t)(batch * n_rows) : 0);
+    std::vector<double> h_th((size_t)std::max(n, 1));
+    std::vector<SetStat> h_bstat((size_t)(batch * n_sets));
+    const unsigned gn = (unsigned)grid_for(n, 256);
+    for (int64_t done = 0; done < n_rep; ) {
+        const int64_t nb = std::min<int64_t>(batch, n_rep - done);
+        std::vector<char> unconv((size_t)nb, 0);      // replicates of the batch with a part that hit max_iter
+        // ---- draws ----
+        HIPCHK(hipEventRecord(e[0], ctx->stream));
+        if (use_sets) HIPCHK(hipMemsetAsync(d_slots, 0, (size_t)(nb * slot_stride) * 8, ctx->stream));
+        if (n_rows > 0)
+            hipLaunchKernelGGL(k_boot_draw, dim3((unsigned)((n_rows + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, n_rows, seed,
+                               (int64_t)first + done, ctx->d_boot_R, use_sets ? ctx->d_boot_slot : nullptr, need_stream ? d_wb : nullptr, d_slots,
+                               slot_stride);
+        HIPCHK(hipGetLastError());
+        if ((rc = lap(draw_ms))) return rc;
+        // ---- closed form + resident sets, all replicates of the batch in one launch per class ----
+        if (use_sets) {
+            HIPCHK(hipEventRecord(e[0], ctx->stream));
+            if (n_gu > 0)
+                hipLaunchKernelGGL(k_boot_gather_u, dim3((unsigned)((n_gu + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, n_gu, ctx->d_g_tid,
+                                   d_slots, slot_stride, n_rw, d_gu);
+            hipLaunchKernelGGL(k_boot_closed, dim3(gn, (unsigned)nb), dim3(256), 0, ctx->stream, n, ctx->d_kind, d_slots, slot_stride, n_rw,
+                               ctx->d_den, d_thb);
+            const size_t off[3] = {0, S.desc[0].size(), S.desc[0].size() + S.desc[1].size()};
+            HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
+            for (int i = 0; i < 2; i++) HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0));
+#define LAUNCH_SB(C, TH, ST)                                                                                                           \
+            if (!S.desc[C].empty())                                                                                                    \
+                hipLaunchKernelGGL(k_solve_sets_boot<TH>, dim3((unsigned)S.desc[C].size(), (unsigned)nb), dim3(TH), S.max_lds[C], ST,   \
+                                   ctx->d_sdesc[C], ctx->d_g_tid, d_gu, d_slots, ctx->d_srp, ctx->d_sent, ctx->d_scp, ctx->d_scrow,       \
+                                   ctx->d_den, d_thb, d_bstat + off[C], P, n_gu, slot_stride, (int64_t)n, n_sets);
+            LAUNCH_SB(2, 512, ctx->side[1])
+            LAUNCH_SB(1, 256, ctx->side[0])
+            LAUNCH_SB(0, 64, ctx->stream)
+#undef LAUNCH_SB
+            for (int i = 0; i < 2; i++) {
+                HIPCHK(hipEventRecord(ctx->ev_join[i], ctx->side[i]));
+                HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
+            }
+            HIPCHK(hipGetLastError());
+            if (n_sets) HIPCHK(hipMemcpyAsync(h_bstat.data(), d_bstat, (size_t)(nb * n_sets) * sizeof(SetStat), hipMemcpyDeviceToHost, ctx->stream));
+            if ((rc = lap(sets_ms))) return rc;
+            for (int64_t i = 0; i < nb * n_sets; i++) {
+                const SetStat &q = h_bstat[(size_t)i];
+                if (!std::isfinite(q.delta)) { ctx->err = "non-finite theta in a connected set of a bootstrap replicate"; return EMSAR_HIP_ERR_NUMERIC; }
+                passes_max = std::max(passes_max, q.passes);
+                if (!q.converged) unconv[(size_t)(i / n_sets)] = 1;
+            }
+        }
+        // ---- the rest: one streaming solve per replicate with its weights swapped into the layout ----
+        if (need_stream) {
+            HIPCHK(hipMemcpyAsync(h_wb.data(), d_wb, (size_t)(nb * n_rows) * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            emsar_em_params ps = p;
+            ps.set_mode = 1;
+            for (int64_t y = 0; y < nb; y++) {
+                guard.swapped = true;
+                if ((rc = boot_stream_weights(ctx, h_wb.data() + y * n_rows))) return rc;
+                emsar_em_stats st;
+                rc = solve_impl(ctx, &ps, h_th.data(), &st);
+                ctx->count_floor = 0.0; ctx->zero_cut = 0.0; ctx->delta_mask = nullptr;
+                if (rc) return rc;
+                stream_ms += st.kernel_ms;
+                if (!st.converged) unconv[(size_t)y] = 1;
+                hipLaunchKernelGGL(k_boot_take_streamed, dim3(gn), dim3(256), 0, ctx->stream, n, use_sets ? ctx->d_kind : nullptr, ctx->d_th[0],
+                                   d_thb + y * n);
+                HIPCHK(hipGetLastError());
+            }
+        }
+        // ---- reduction over the replicates, in replicate order ----
+        HIPCHK(hipEventRecord(e[0], ctx->stream));
+        hipLaunchKernelGGL(k_boot_sums, dim3((unsigned)nb), dim3(1024), 0, ctx->stream, n, d_thb, d_sums);
+        hipLaunchKernelGGL(k_boot_accum, dim3(gn), dim3(256), 0, ctx->stream, n, (int)nb, done, d_thb, d_sums, d_acc4);
+        HIPCHK(hipGetLastError());
+        if ((rc = lap(reduce_ms))) return rc;
+        if (replicates) {
+            HIPCHK(hipMemcpy(replicates + done * n, d_thb, (size_t)(nb * n) * 8, hipMemcpyDeviceToHost));
+            try { for (int64_t y = 0; y < nb; y++) from_lib(ctx, replicates + (done + y) * n); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+        }
+        for (char c : unconv) unconverged += c;
+        done += nb;
+    }
+    std::vector<double> acc((size_t)4 * n);
+    HIPCHK(hipMemcpyAsync(acc.data(), d_acc4, acc.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int t = 0; t < n; t++) {
+        if (!std::isfinite(acc[(size_t)t]) || !std::isfinite(acc[(size_t)n + t])) { ctx->err = "non-finite theta in a bootstrap replicate"; return EMSAR_HIP_ERR_NUMERIC; }
+        fpkm_mean[t] = acc[(size_t)t];
+        fpkm_sd[t] = n_rep > 1 ? std::sqrt(acc[(size_t)n + t] / (double)(n_rep - 1)) : 0.0;
+        tpm_sd[t] = n_rep > 1 ? std::sqrt(acc[(size_t)3 * n + t] / (double)(n_rep - 1)) : 0.0;
+    }
+    try { from_lib(ctx, fpkm_mean); from_lib(ctx, fpkm_sd); from_lib(ctx, tpm_sd); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+    if (stats) {
+        memset(stats, 0, sizeof(*stats));
+        stats->n_replicates = n_rep; stats->batch = (int32_t)batch; stats->replicates_unconverged = unconverged; stats->set_passes_max = passes_max;
+        int64_t pos = 0;
+        for (int64_t r = 0; r < n_rows; r++) pos += ctx->h_wgt[(size_t)r] > 0;
+        stats->draws = pos * n_rep;
+        stats->draw_ms = draw_ms; stats->sets_ms = sets_ms; stats->stream_ms = stream_ms; stats->reduce_ms = reduce_ms;
+    }
+    // the sample's own weights back before the call returns (the guard does it too, but a failure there must be reported)
+    if (guard.swapped) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        guard.swapped = false;
+        if ((rc = boot_stream_weights(ctx, ctx->h_wgt.data()))) return rc;
+        if (!guard.weighted) {
+            dfree(ctx->d_wgt); ctx->d_wgt = nullptr;
+            if (ctx->layout == EMSAR_LAYOUT_TILED) { dfree(ctx->d_left_wgt); ctx->d_left_wgt = nullptr; }
+        }
+        ctx->weighted = guard.weighted;
+    }
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
+    return EMSAR_HIP_OK;
+}
+
+int emsar_hip_bootstrap(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t first_replicate, int32_t n_replicates,
+                        double *fpkm_mean, double *fpkm_sd, double *tpm_sd, double *replicates, emsar_boot_stats *stats) {
+    if (!ctx) return EMSAR_HIP_ERR_ARG;
+    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
+    if (!fpkm_mean || !fpkm_sd || !tpm_sd || n_replicates < 1 || first_replicate < 0 ||
+        (int64_t)first_replicate + (int64_t)n_replicates > (int64_t)INT32_MAX + 1)
+        return EMSAR_HIP_ERR_ARG;
+    try {
+        return bootstrap_impl(ctx, p, seed, first_replicate, n_replicates, fpkm_mean, fpkm_sd, tpm_sd, replicates, stats);
+    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+}
+
+int emsar_hip_bootstrap_weights(emsar_hip_ctx *ctx, uint64_t seed, int32_t replicate, int32_t *w_out) {
+    if (!ctx || !w_out || replicate < 0) return EMSAR_HIP_ERR_ARG;
+    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
+    HIPCHK(hipSetDevice(ctx->device));
+    int rc;
+    try { if ((rc = boot_prepare(ctx, false))) return rc; } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+    if (ctx->n_rows == 0) return EMSAR_HIP_OK;
+    int32_t *d_w = nullptr;
+    HIPCHK(hipMalloc(&d_w, (size_t)ctx->n_rows * 4));
+    hipLaunchKernelGGL(k_boot_draw, dim3((unsigned)((ctx->n_rows + 255) / 256), 1), dim3(256), 0, ctx->stream, ctx->n_rows, seed, (int64_t)replicate,
+                       ctx->d_boot_R, (const int64_t *)nullptr, d_w, (double *)nullptr, (int64_t)0);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(w_out, d_w, (size_t)ctx->n_rows * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    dfree(d_w);
+    HIPCHK(e);
+    return EMSAR_HIP_OK;
+}
+
+int emsar_hip_bootstrap_draw_host(uint64_t seed, int32_t replicate, int64_t n_rows, const int32_t *row_weight, int32_t *w_out) {
+    if (replicate < 0 || n_rows < 0 || (n_rows > 0 && !w_out)) return EMSAR_HIP_ERR_ARG;
+    if (row_weight) for (int64_t r = 0; r < n_rows; r++) if (row_weight[r] < 0) return EMSAR_HIP_ERR_ARG;
+    for (int64_t r = 0; r < n_rows; r++) w_out[r] = emsar::boot_poisson(seed, (uint64_t)replicate, (uint64_t)r, row_weight ? row_weight[r] : 1);
     return EMSAR_HIP_OK;
 }
 

@@ -14,7 +14,9 @@
  *
  * Outputs: <outdir>/<prefix>.<i>.fpkm, .fraglength_effect and, with -g, .segments -- i = 0-based index of the
  * alignment file (emsar_main.c:459-469).  Column 3 (sd.of.FPKM) is 0: the EM is deterministic, the reference's
- * spread comes from its random restarts (documented deviation).
+ * spread comes from its random restarts (documented deviation).  For an uncertainty measure,
+ * --bootstrap B writes <prefix>.<i>.bootstrap: mean and sd of FPKM and sd of TPM over B Poisson bootstrap replicates
+ * (emsar_hip_bootstrap; seed --bootstrap-seed + i).  .fpkm, .fraglength_effect and .segments do not change with it.
  *
  * -M: samples are independent (emsar_main.c:380-488 resets every count per file), so sample i runs on GPU
  * i mod G with one host thread per GPU; no collective.  The only cross-sample state of the reference, EUMAcut
@@ -42,6 +44,7 @@ typedef struct {
     double tol, count_floor, zero_cut, abs_step; int max_iter;
     const char *stats_json;
     const char *rsh_cache;      /* NULL = off, "" = <rsh>.bin, else the path */
+    int boot_n; uint64_t boot_seed;   /* --bootstrap B (0 = off), --bootstrap-seed: sample i uses seed + i */
 } config;
 
 typedef struct {
@@ -51,6 +54,7 @@ typedef struct {
     pthread_mutex_t *mu; pthread_cond_t *cv; int *next_model; double *eumacut;
     int *status;          /* per sample */
     emsar_em_stats *stats; /* per sample */
+    emsar_boot_stats *bstats; /* per sample (--bootstrap) */
     double *parse_s;
     double *model_s, *host_s;   /* per sample: model preparation, and all host work of run_sample outside the library calls */
     int *go;              /* start gate: the workers wait until main() knows how many of them exist */
@@ -189,6 +193,19 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         if ((rc = emsar_write_segments(path, r, cnt, m, mean))) { fprintf(stderr, "can't write %s\n", path); goto done; }
     }
     w->host_s[i] += now_s() - t_host;
+    /* ---- Poisson bootstrap (--bootstrap B): its own file; .fpkm keeps the reference's column 3 ---- */
+    if (cfg->boot_n > 0) {
+        double *bm = (double *)malloc(T * 8), *bs = (double *)malloc(T * 8), *bt = (double *)malloc(T * 8);
+        if (!bm || !bs || !bt) rc = EMSAR_HOST_ERR_OOM;
+        else if ((rc = emsar_hip_bootstrap(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, bm, bs, bt, NULL, &w->bstats[i])))
+            fprintf(stderr, "alnfile[%d]: bootstrap: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+        else {
+            snprintf(path, sizeof path, "%s/%s.%d.bootstrap", cfg->outdir, cfg->prefix, i);
+            if ((rc = emsar_write_bootstrap(path, r, mean, bm, bs, tpm, bt))) fprintf(stderr, "can't write %s\n", path);
+        }
+        free(bm); free(bs); free(bt);
+        if (rc) goto done;
+    }
     if (cfg->verbose > 0)
         fprintf(stdout, "Complete: %s/%s.%d.fpkm  (EM passes %d, converged %d, solve %.1f ms, logL %.6f)\n", cfg->outdir, cfg->prefix, i,
                 w->stats[i].iters, w->stats[i].converged, w->stats[i].solve_ms, w->stats[i].loglik);
@@ -266,6 +283,9 @@ static void usage(const char *a0) {
             "                            the fixed-point sums that make two runs of the same input print the same bytes\n"
             "      --device-collapse     reads with two or more transcripts are merged into weighted segments on the GPU\n"
             "                            (emsar_hip_collapse_rows) instead of one index lookup per read on the host; same counts\n"
+            "      --bootstrap <B>       also write <outdir>/<prefix>.<i>.bootstrap: mean and sd of FPKM and sd of TPM over B Poisson\n"
+            "                            bootstrap replicates of the sample (default 0 = off; .fpkm is the same either way)\n"
+            "      --bootstrap-seed <n>  seed of the replicates' draws (default 1; sample i of -M uses n + i)\n"
             "      --gpus <n> / --devices <a,b,..> (-M: one worker per entry, ids may repeat) / --device <d> / --plain /\n"
             "      --stats-json <file> / -q / -v\n", a0);
 }
@@ -275,6 +295,7 @@ int main(int argc, char **argv) {
     cfg.ao.max_repeat = 100; cfg.n_round = 4; cfg.verbose = 1; cfg.accel = 1; cfg.tol = 1e-10; cfg.max_iter = 200000;
     cfg.zero_cut = 2.5e-7;      /* a quarter of the "%lf" print quantum of the .fpkm file */
     cfg.abs_step = 1e-13;       /* see emsar_em_params.abs_step */
+    cfg.boot_seed = 1;
     const char *strand = "ns"; int multisample = 0, gpus = 0, device = 0;
     int dev_map[64], n_dev_map = 0;
     static struct option lo[] = {
@@ -285,6 +306,7 @@ int main(int argc, char **argv) {
         {"verbose", no_argument, 0, 'v'}, {"no_verbose", no_argument, 0, 'q'}, {"gpus", required_argument, 0, 1000},
         {"device", required_argument, 0, 1001}, {"plain", no_argument, 0, 1002}, {"stats-json", required_argument, 0, 1003},
         {"count-floor", required_argument, 0, 1004}, {"streaming-only", no_argument, 0, 1005}, {"rsh-cache", optional_argument, 0, 1006}, {"zero-cut", required_argument, 0, 1007}, {"abs-step", required_argument, 0, 1008}, {"devices", required_argument, 0, 1009}, {"device-collapse", no_argument, 0, 1010}, {"no-deterministic", no_argument, 0, 1011},
+        {"bootstrap", required_argument, 0, 1012}, {"bootstrap-seed", required_argument, 0, 1013},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
@@ -316,6 +338,20 @@ int main(int argc, char **argv) {
             case 1008: cfg.abs_step = atof(optarg); break;
             case 1010: cfg.device_collapse = 1; break;
             case 1011: cfg.no_deterministic = 1; break;
+            case 1012: {
+                char *end; errno = 0;
+                long v = strtol(optarg, &end, 10);
+                if (end == optarg || *end || errno || v < 0 || v > 1000000) { fprintf(stderr, "--bootstrap wants a number of replicates (0 .. 1000000).\n"); return 1; }
+                cfg.boot_n = (int)v;
+                break;
+            }
+            case 1013: {
+                char *end; errno = 0;
+                unsigned long long v = strtoull(optarg, &end, 10);
+                if (end == optarg || *end || errno || optarg[0] == '-') { fprintf(stderr, "--bootstrap-seed wants a non-negative integer.\n"); return 1; }
+                cfg.boot_seed = (uint64_t)v;
+                break;
+            }
             case 1009: {
                 const char *q = optarg;
                 while (*q && n_dev_map < 64) {
@@ -412,17 +448,18 @@ int main(int argc, char **argv) {
     int next_model = 0; double eumacut = 0.0;
     int *status = (int *)calloc((size_t)n_list, sizeof(int));
     emsar_em_stats *stats = (emsar_em_stats *)calloc((size_t)n_list, sizeof(emsar_em_stats));
+    emsar_boot_stats *bstats = (emsar_boot_stats *)calloc((size_t)n_list, sizeof(emsar_boot_stats));
     double *parse_s = (double *)calloc((size_t)n_list, sizeof(double));
     double *model_s = (double *)calloc((size_t)n_list, sizeof(double)), *host_s = (double *)calloc((size_t)n_list, sizeof(double));
     worker_arg *wa = (worker_arg *)calloc((size_t)n_workers, sizeof(worker_arg));
     pthread_t *th = (pthread_t *)calloc((size_t)n_workers, sizeof(pthread_t));
-    if (!status || !stats || !parse_s || !model_s || !host_s || !wa || !th) { fprintf(stderr, "out of memory\n"); return 1; }
+    if (!status || !stats || !bstats || !parse_s || !model_s || !host_s || !wa || !th) { fprintf(stderr, "out of memory\n"); return 1; }
     t0 = now_s();
     /* Workers wait at a gate until their number is final: a thread that cannot be started must not leave the others
      * waiting for samples nobody will take (the EUMAcut hand-over is in sample order). */
     int go = 0, n_started = 1;
     for (int g = 0; g < n_workers; g++)
-        wa[g] = (worker_arg){&cfg, rsh, multisample ? dev_map[g] : device, n_workers, g, &mu, &cv, &next_model, &eumacut, status, stats, parse_s,
+        wa[g] = (worker_arg){&cfg, rsh, multisample ? dev_map[g] : device, n_workers, g, &mu, &cv, &next_model, &eumacut, status, stats, bstats, parse_s,
                              model_s, host_s, &go, cfg.ao, {NULL, PTHREAD_MUTEX_INITIALIZER}};
     for (int g = 1; g < n_workers; g++) {
         if (pthread_create(&th[g], NULL, worker_main, &wa[g]) != 0) { fprintf(stderr, "warning: worker %d could not be started, using %d\n", g, g); break; }
@@ -450,18 +487,27 @@ int main(int argc, char **argv) {
         FILE *f = fopen(cfg.stats_json, "w");
         if (f) {
             fprintf(f, "{\"samples\": %d, \"gpus\": %d, \"wall_s\": %.6f, \"failed\": %d, \"per_sample\": [", n_list, n_workers, wall, bad);
-            for (int i = 0; i < n_list; i++)
+            for (int i = 0; i < n_list; i++) {
                 fprintf(f, "%s{\"status\": %d, \"parse_s\": %.6f, \"model_s\": %.6f, \"host_s\": %.6f, \"em_passes\": %d, \"converged\": %d, \"solve_ms\": %.4f, \"kernel_ms\": %.4f, \"loglik\": %.9g, \"bytes_per_pass\": %lld, "
-                           "\"sets_resident\": %d, \"sets_streamed\": %d, \"set_passes_max\": %d, \"set_passes_sum\": %lld, \"sets_build_ms\": %.4f, \"sets_kernel_ms\": %.4f}",
+                           "\"sets_resident\": %d, \"sets_streamed\": %d, \"set_passes_max\": %d, \"set_passes_sum\": %lld, \"sets_build_ms\": %.4f, \"sets_kernel_ms\": %.4f",
                         i ? ", " : "", status[i], parse_s[i], model_s[i], host_s[i], stats[i].iters, stats[i].converged, stats[i].solve_ms, stats[i].kernel_ms, stats[i].loglik,
                         (long long)stats[i].bytes_per_pass, stats[i].sets_resident, stats[i].sets_streamed, stats[i].set_passes_max,
                         (long long)stats[i].set_passes_sum, stats[i].sets_build_ms, stats[i].sets_kernel_ms);
+                if (cfg.boot_n > 0) {
+                    const emsar_boot_stats *b = &bstats[i];
+                    fprintf(f, ", \"boot_replicates\": %d, \"boot_batch\": %d, \"boot_replicates_unconverged\": %d, \"boot_set_passes_max\": %d, "
+                               "\"boot_draws\": %lld, \"boot_draw_ms\": %.4f, \"boot_sets_ms\": %.4f, \"boot_stream_ms\": %.4f, \"boot_reduce_ms\": %.4f, \"boot_total_ms\": %.4f",
+                            b->n_replicates, b->batch, b->replicates_unconverged, b->set_passes_max, (long long)b->draws, b->draw_ms, b->sets_ms,
+                            b->stream_ms, b->reduce_ms, b->total_ms);
+                }
+                fprintf(f, "}");
+            }
             fprintf(f, "]}\n");
             fclose(f);
         }
     }
     emsar_rsh_free(rsh);
     for (int i = 0; i < n_list; i++) free(list[i]);
-    free(list); free(status); free(stats); free(parse_s); free(model_s); free(host_s); free(wa); free(th);
+    free(list); free(status); free(stats); free(bstats); free(parse_s); free(model_s); free(host_s); free(wa); free(th);
     return bad ? 1 : 0;
 }

@@ -134,6 +134,9 @@ void emsar_mean_sd(int32_t n_tx, int32_t n_round, const double *rounds, double *
 
 int emsar_write_fpkm(const char *path, const emsar_rsh *r, const double *mean, const double *sd, const double *ieuma,
                      const double *ireadcount, const int32_t *ireadcount_int, const double *tpm, int64_t *total_ireadcount);
+/* .bootstrap (emsar-hip --bootstrap): transcriptID FPKM boot.mean.FPKM boot.sd.FPKM TPM boot.sd.TPM, "%lf" like .fpkm */
+int emsar_write_bootstrap(const char *path, const emsar_rsh *r, const double *fpkm, const double *boot_mean, const double *boot_sd,
+                          const double *tpm, const double *boot_tpm_sd);
 int emsar_write_fraglength(const char *path, const emsar_rsh *r, const emsar_counts *c, const emsar_model *m);
 int emsar_write_segments(const char *path, const emsar_rsh *r, const emsar_counts *c, const emsar_model *m,
                          const double *mean_fpkm);

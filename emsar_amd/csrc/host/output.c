@@ -2,6 +2,8 @@
  *   .fpkm               print_FPKMfinal      emsar_functions.c:3184,3207   "%s\t%lf\t%lf\t%lf\t%lf\t%d\t%lf\n"
  *   .fraglength_effect  print_FraglengthDist emsar_functions.c:2489-2490   "%d\t%d\t%lg\n"
  *   .segments           print_aEUMA_3        emsar_functions.c:2274-2297
+ * and the bootstrap's own file (no counterpart in the reference):
+ *   .bootstrap          "%s\t%lf\t%lf\t%lf\t%lf\t%lf\n"  FPKM and TPM as in .fpkm, then the Poisson bootstrap's mean / sd
  * Column order of .fpkm is a contract: the reference's Perl utilities read columns 0,1,4,6 (util/FPKM2gFPKM.pl:19).
  */
 #include "emsar_host.h"
@@ -20,6 +22,16 @@ int emsar_write_fpkm(const char *path, const emsar_rsh *r, const double *mean, c
                 ireadcount_int[t], tpm[t]);
     }
     if (total_ir) *total_ir = tot;
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+int emsar_write_bootstrap(const char *path, const emsar_rsh *r, const double *fpkm, const double *boot_mean, const double *boot_sd,
+                          const double *tpm, const double *boot_tpm_sd) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "transcriptID\tFPKM\tboot.mean.FPKM\tboot.sd.FPKM\tTPM\tboot.sd.TPM\n");
+    for (int32_t t = 0; t < r->n_tx; t++)
+        fprintf(f, "%s\t%lf\t%lf\t%lf\t%lf\t%lf\n", r->names[t], fpkm[t], boot_mean[t], boot_sd[t], tpm[t], boot_tpm_sd[t]);
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
 

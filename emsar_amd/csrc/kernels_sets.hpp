@@ -284,15 +284,15 @@ __device__ __forceinline__ bool set_newton_step(const SetLds &L, double *x, doub
     return false;
 }
 
+// the solve of one set by the whole workgroup (k_solve_sets; k_solve_sets_boot runs it on a bootstrap replicate's weights)
 template <int THREADS>
-__global__ __launch_bounds__(THREADS) void k_solve_sets(const emsar::SetDesc *__restrict__ desc, const int32_t *__restrict__ g_tid,
-                                                        const double *__restrict__ g_u, const double *__restrict__ row_w,
-                                                        const uint16_t *__restrict__ rp_g, const uint16_t *__restrict__ ent_g,
-                                                        const uint16_t *__restrict__ cp_g, const uint16_t *__restrict__ crow_g,
-                                                        const double *__restrict__ den_g, double *__restrict__ theta_g,
-                                                        SetStat *__restrict__ stat, SetSolveParams P) {
+__device__ __forceinline__ void solve_one_set(const emsar::SetDesc d, const int32_t *__restrict__ g_tid,
+                                              const double *__restrict__ g_u, const double *__restrict__ row_w,
+                                              const uint16_t *__restrict__ rp_g, const uint16_t *__restrict__ ent_g,
+                                              const uint16_t *__restrict__ cp_g, const uint16_t *__restrict__ crow_g,
+                                              const double *__restrict__ den_g, double *__restrict__ theta_g,
+                                              SetStat *__restrict__ st, SetSolveParams P) {
     extern __shared__ double smem[];
-    const emsar::SetDesc d = desc[blockIdx.x];
     const int nt = (int)d.n_t, nr = (int)d.n_r, nnz = (int)d.nnz;
     double *A = smem, *B = A + nt, *Cc = B + nt;
     SetLds L;
@@ -401,7 +401,33 @@ __global__ __launch_bounds__(THREADS) void k_solve_sets(const emsar::SetDesc *__
         }
     }
     for (int i = threadIdx.x; i < nt; i += THREADS) theta_g[g_tid[d.tid_off + i]] = res[i];
-    if (threadIdx.x == 0) { stat[blockIdx.x].passes = passes; stat[blockIdx.x].converged = converged; stat[blockIdx.x].delta = delta; }
+    if (threadIdx.x == 0) { st->passes = passes; st->converged = converged; st->delta = delta; }
+}
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_solve_sets(const emsar::SetDesc *__restrict__ desc, const int32_t *__restrict__ g_tid,
+                                                        const double *__restrict__ g_u, const double *__restrict__ row_w,
+                                                        const uint16_t *__restrict__ rp_g, const uint16_t *__restrict__ ent_g,
+                                                        const uint16_t *__restrict__ cp_g, const uint16_t *__restrict__ crow_g,
+                                                        const double *__restrict__ den_g, double *__restrict__ theta_g,
+                                                        SetStat *__restrict__ stat, SetSolveParams P) {
+    solve_one_set<THREADS>(desc[blockIdx.x], g_tid, g_u, row_w, rp_g, ent_g, cp_g, crow_g, den_g, theta_g, stat + blockIdx.x, P);
+}
+
+// Bootstrap replicates (emsar_hip_bootstrap): workgroup (x, y) solves set x on replicate y of the batch.  The replicates share the
+// set records (descriptors, indices, den); their row weights, folded single-row counts, results and statistics lie at a fixed
+// stride per replicate.  Same code as k_solve_sets: a replicate's result does not depend on where it sits in the batch.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_solve_sets_boot(const emsar::SetDesc *__restrict__ desc, const int32_t *__restrict__ g_tid,
+                                                             const double *__restrict__ g_u, const double *__restrict__ row_w,
+                                                             const uint16_t *__restrict__ rp_g, const uint16_t *__restrict__ ent_g,
+                                                             const uint16_t *__restrict__ cp_g, const uint16_t *__restrict__ crow_g,
+                                                             const double *__restrict__ den_g, double *__restrict__ theta_g,
+                                                             SetStat *__restrict__ stat, SetSolveParams P,
+                                                             int64_t gu_stride, int64_t rw_stride, int64_t th_stride, int64_t stat_stride) {
+    const int64_t y = blockIdx.y;
+    solve_one_set<THREADS>(desc[blockIdx.x], g_tid, g_u + y * gu_stride, row_w + y * rw_stride, rp_g, ent_g, cp_g, crow_g, den_g,
+                           theta_g + y * th_stride, stat + y * stat_stride + blockIdx.x, P);
 }
 
 }  // namespace

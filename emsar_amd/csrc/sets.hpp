@@ -180,10 +180,14 @@ inline bool pack_cluster(ResidentSets &out, const int32_t *tids, size_t nt, cons
 }  // namespace detail
 
 // wgt[r] >= 0: weight of row r inside the likelihood (0 = the row does not couple anything).
+// row_slot (optional, the bootstrap's draw map): [n_rows] where the weight of row r went -- j >= 0: row_w[j] of a resident set (after
+// the merge of identical rows), -2 - t: usum[t] (a single-transcript row; t in the caller's numbering), -1: nowhere (weight 0, empty
+// row, a row of a streamed or cluster set, or everything when the problem is one giant component).
 // Returns 0; the CSR is assumed validated (validate_csr).
 inline int build_sets(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr, const int32_t *col_idx, const int32_t *wgt,
-                      ResidentSets &out) {
+                      ResidentSets &out, std::vector<int64_t> *row_slot = nullptr) {
     out = ResidentSets();
+    if (row_slot) row_slot->assign((size_t)n_rows, -1);
     // measured (tests/test_set_solver.py, 2500..9000-transcript families): 32 us per pass in a cluster against 19 us through the
     // streaming passes -- a cluster barrier is three dependent trips to memory that bypass the (non-coherent) L2s, ~2 us each.
     // Correct and bit-reproducible, but not faster: opt-in.
@@ -206,6 +210,7 @@ inline int build_sets(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr, con
             std::fill(out.kind.begin(), out.kind.end(), (uint8_t)KIND_STREAMED);
             std::fill(out.usum.begin(), out.usum.end(), 0.0);
             out.n_components = 1; out.n_streamed_sets = 1; out.n_streamed_tids = (int64_t)T;
+            if (row_slot) std::fill(row_slot->begin(), row_slot->end(), (int64_t)-1);
             return 0;
         }
         const int32_t x = wgt ? wgt[r] : 1;
@@ -214,7 +219,7 @@ inline int build_sets(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr, con
         const int32_t first = col_idx[b];
         bool single = true;
         for (uint64_t k = b + 1; k < e; k++) if (col_idx[k] != first) { single = false; break; }
-        if (single) { out.usum[(size_t)first] += (double)x; continue; }
+        if (single) { out.usum[(size_t)first] += (double)x; if (row_slot) (*row_slot)[(size_t)r] = -2 - (int64_t)first; continue; }
         multi_rows.push_back(r);
         int32_t ra = detail::uf_find(parent, first);
         for (uint64_t k = b + 1; k < e; k++) {
@@ -260,7 +265,7 @@ inline int build_sets(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr, con
     std::vector<int32_t> local(T, -1);
     const size_t cap = kSetLdsCap[kSetClasses - 1];
     std::vector<uint16_t> lst;            // local sorted tid lists of the component's rows, back to back
-    std::vector<uint32_t> lptr, order;
+    std::vector<uint32_t> lptr, order, rep_of;   // rep_of: row of the component -> its merged row (row_slot only)
     for (size_t c = 0; c < NC; c++) {
         const size_t nt = (size_t)comp_nt[c];
         const size_t nr0 = (size_t)(rptr[c + 1] - rptr[c]);
@@ -298,10 +303,12 @@ inline int build_sets(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr, con
         std::vector<uint32_t> rep;        // representative (first) row of each distinct list
         std::vector<double> repw;
         size_t nnz = 0;
+        if (row_slot) rep_of.resize(nr0);
         for (size_t j = 0; j < nr0; j++) {
             const uint32_t a = order[j];
             const double x = (double)(wgt ? wgt[rows[rptr[c] + a]] : 1);
-            if (!rep.empty() && cmp3(rep.back(), a) == 0) { repw.back() += x; continue; }
+            if (!rep.empty() && cmp3(rep.back(), a) == 0) { repw.back() += x; if (row_slot) rep_of[a] = (uint32_t)rep.size() - 1; continue; }
+            if (row_slot) rep_of[a] = (uint32_t)rep.size();
             rep.push_back(a); repw.push_back(x);
             nnz += lptr[a + 1] - lptr[a];
         }
@@ -350,6 +357,8 @@ inline int build_sets(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr, con
             out.kind[(size_t)t] = KIND_RESIDENT;
             local[(size_t)t] = -1;
         }
+        if (row_slot)
+            for (size_t j = 0; j < nr0; j++) (*row_slot)[(size_t)rows[rptr[c] + j]] = (int64_t)d.row_off + rep_of[j];
         out.desc[cls].push_back(d);
         out.max_lds[cls] = std::max(out.max_lds[cls], bytes);
         out.n_resident_tids += (int64_t)nt;

@@ -20,7 +20,7 @@ SYMBOLS = [
     "emsar_hip_reset_theta", "emsar_hip_set_theta", "emsar_hip_get_theta", "emsar_hip_run_passes",
     "emsar_hip_ieuma", "emsar_hip_normalise", "emsar_hip_get_info",
     "emsar_hip_layout_selfcheck_tiled", "emsar_hip_sets_selfcheck", "emsar_hip_upload_euma", "emsar_hip_adj_euma", "emsar_hip_collapse_rows",
-    "emsar_hip_set_deterministic",
+    "emsar_hip_set_deterministic", "emsar_hip_bootstrap", "emsar_hip_bootstrap_weights", "emsar_hip_bootstrap_draw_host",
 ]
 
 
@@ -48,6 +48,15 @@ class EmStats(C.Structure):
 class CollapseStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("total_ms", C.c_double), ("n_rows", C.c_int64), ("nnz", C.c_int64),
                 ("n_unique", C.c_int64), ("nnz_unique", C.c_int64), ("table_slots", C.c_int64), ("algorithmic_bytes", C.c_int64), ("rounds", C.c_int64)]
+
+
+class BootStats(C.Structure):
+    _fields_ = [("n_replicates", C.c_int32), ("batch", C.c_int32), ("replicates_unconverged", C.c_int32), ("set_passes_max", C.c_int32),
+                ("draws", C.c_int64), ("draw_ms", C.c_double), ("sets_ms", C.c_double), ("stream_ms", C.c_double), ("reduce_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class SetsInfo(C.Structure):
@@ -102,6 +111,9 @@ def load_library():
     L.emsar_hip_upload_euma.argtypes = [vp, i32p, C.c_int32]
     L.emsar_hip_adj_euma.argtypes = [vp, f64p, f64p]
     L.emsar_hip_sets_selfcheck.argtypes = [C.c_int64, C.c_int32, u64p, i32p, i32p, C.POINTER(SetsInfo)]
+    L.emsar_hip_bootstrap.argtypes = [vp, C.POINTER(EmParams), C.c_uint64, C.c_int32, C.c_int32, f64p, f64p, f64p, f64p, C.POINTER(BootStats)]
+    L.emsar_hip_bootstrap_weights.argtypes = [vp, C.c_uint64, C.c_int32, i32p]
+    L.emsar_hip_bootstrap_draw_host.argtypes = [C.c_uint64, C.c_int32, C.c_int64, i32p, i32p]
     _lib = L
     return L
 
@@ -135,6 +147,19 @@ def sets_selfcheck(n_tx, row_ptr, col_idx, row_weight=None):
     d["sets_resident"] = list(d["sets_resident"])
     d["max_lds_bytes"] = list(d["max_lds_bytes"])
     return d
+
+
+def bootstrap_draw_host(seed, replicate, row_weight=None, n_rows=None):
+    """Host-only: the Poisson draws of bootstrap replicate `replicate` of `seed` (no GPU needed), the same function the device
+    evaluates.  row_weight None = 1 per row (then n_rows is required)."""
+    L = load_library()
+    w = None if row_weight is None else _arr(row_weight, np.int32)
+    n = len(w) if w is not None else int(n_rows)
+    out = np.zeros(max(n, 1), dtype=np.int32)
+    rc = L.emsar_hip_bootstrap_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(replicate), n, _p(w, C.c_int32), _p(out, C.c_int32))
+    if rc != 0:
+        raise EmsarHipError(rc, "bootstrap_draw_host")
+    return out[:n]
 
 
 def layout_selfcheck_tiled(n_tx, row_ptr, col_idx, merge_rows=False):
@@ -208,6 +233,25 @@ class EmsarHip:
         out = np.zeros(self.n_tx)
         self._chk(self._L.emsar_hip_solve(self._h, C.byref(p), _p(out, C.c_double), C.byref(st)), "solve")
         return out, st
+
+    def bootstrap(self, n, seed, first=0, want_replicates=False, max_iter=100000, accel=1, tol=1e-10, abs_floor=1e-6, check_every=8,
+                  count_floor=0.0, set_mode=0, zero_cut=0.0, abs_step=0.0, newton_after=0):
+        """Poisson bootstrap of the current sample: replicates first .. first+n-1, each solved like solve() with these parameters.
+        Returns (fpkm_mean, fpkm_sd, tpm_sd, replicates [n][n_tx] or None, stats)."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        mean, sd, tsd = np.zeros(self.n_tx), np.zeros(self.n_tx), np.zeros(self.n_tx)
+        reps = np.zeros((n, self.n_tx)) if (want_replicates and n > 0) else None
+        st = BootStats()
+        self._chk(self._L.emsar_hip_bootstrap(self._h, C.byref(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(n), _p(mean, C.c_double),
+                                              _p(sd, C.c_double), _p(tsd, C.c_double), _p(reps, C.c_double), C.byref(st)), "bootstrap")
+        return mean, sd, tsd, reps, st
+
+    def bootstrap_weights(self, seed, replicate):
+        """The drawn row weights of one bootstrap replicate (caller row order), drawn on the device."""
+        out = np.zeros(max(self.n_rows, 1), dtype=np.int32)
+        self._chk(self._L.emsar_hip_bootstrap_weights(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(replicate), _p(out, C.c_int32)),
+                  "bootstrap_weights")
+        return out[:self.n_rows]
 
     def collapse_rows(self, n_tx, row_ptr, col_idx, row_weight=None, want_map=True):
         """Read -> segment collapse on the device: rows with the same multiset of ids become one weighted row.

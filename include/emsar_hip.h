@@ -197,6 +197,32 @@ int emsar_hip_collapse_rows(emsar_hip_ctx *ctx, int64_t n_rows, int32_t n_tx, co
  * tile order.  Costs a few percent of a pass.  Default: off, or EMSAR_HIP_DETERMINISTIC=1 in the environment at create time. */
 int emsar_hip_set_deterministic(emsar_hip_ctx *ctx, int on);
 
+/* ---- Poisson bootstrap of the estimates -------------------------------------------------------------------------------
+ * Replicate b re-draws every row c of the current sample: w_c ~ Poisson(R_c) (R_c = the uploaded weight, 0 for rows with E == 0; such
+ * rows keep 0), E and den unchanged, and solves it to the MLE with the caller's parameters (set_mode as in solve).  The draws are
+ * keyed by (seed, b) and by the caller's row index (Philox4x64-10, see DESIGN.md "Bootstrap"): they do not depend on the layout, the
+ * set partition, the batch or the device.  Poisson(1) per read and Poisson(R) per segment have the same distribution, so read-level
+ * and segment-level uploads give statistically equivalent bootstraps (not the same bits).
+ *   bootstrap         replicates first_replicate .. first_replicate + n_replicates - 1: per transcript the mean and the sample sd (n - 1)
+ *                     of theta (= FPKM) and the sd of TPM_b = theta_b * 1e6 / sum theta_b; replicates (may be NULL): [n_replicates][n_tx].
+ *                     Reduced in replicate order: the results are the same whatever batch size the library picks.  The context is left
+ *                     as it was (a following solve returns the same bits).  ERR_STATE before upload_sample, ERR_ARG for n_replicates < 1,
+ *                     first_replicate < 0 or a replicate index past INT32_MAX, ERR_NUMERIC as solve.
+ *   bootstrap_weights the drawn weights of one replicate, caller row order (computed on the device).
+ *   bootstrap_draw_host  the same draws on the host, no HIP call (row_weight NULL = 1 per row). */
+typedef struct {
+    int32_t n_replicates, batch, replicates_unconverged, set_passes_max;
+    int64_t draws;                                   /* rows with R > 0 x replicates */
+    double  draw_ms, sets_ms, stream_ms, reduce_ms;  /* device time per stage (HIP events) */
+    double  total_ms;                                /* wall time of the call */
+} emsar_boot_stats;
+int emsar_hip_bootstrap(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t first_replicate,
+                        int32_t n_replicates, double *fpkm_mean, double *fpkm_sd, double *tpm_sd,
+                        double *replicates /* n_replicates * n_tx, or NULL */, emsar_boot_stats *stats);
+int emsar_hip_bootstrap_weights(emsar_hip_ctx *ctx, uint64_t seed, int32_t replicate, int32_t *w_out /* n_rows */);
+int emsar_hip_bootstrap_draw_host(uint64_t seed, int32_t replicate, int64_t n_rows, const int32_t *row_weight /* NULL = 1 */,
+                                  int32_t *w_out);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 typedef struct {
     int64_t n_rows, nnz;

@@ -1,0 +1,84 @@
+"""Cost of the Poisson bootstrap (emsar_hip_bootstrap) on two workloads; prints one JSON object.
+
+    python tools/boot_bench.py [--reps 100] [--cfg3-scale 0.1] [--cfg3-reps 10] [--out FILE]
+
+  segment   bench.py's time_to_mle problem (same seeds): one solve, then B replicates in one call -- device time per stage (HIP events),
+            wall time, ms per replicate against one solve, the batch size and the slowest set's passes
+  cfg3      BASELINE config 3 at --cfg3-scale, collapsed to weighted segments on the device, B = --cfg3-reps: one giant component, so
+            every replicate is a streaming solve of its own (deterministic mode, as emsar-hip runs it)
+Kernel-level times come from a separate `rocprofv3 --kernel-trace --stats` run of this script."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def segment_problem():
+    from emsar_amd import synth
+    rng = np.random.default_rng(11)                       # bench.py time_to_mle, draw for draw
+    sizes = np.minimum(rng.zipf(1.6, size=40000), 60)
+    sizes = sizes[np.cumsum(sizes) <= 100000]
+    n_tx, rp, ci, _ = synth.family_matrix([int(x) for x in sizes], rows_per_tid=3, seed=11, dup=0.0)
+    E = rng.uniform(0.5, 2.0, size=len(rp) - 1)
+    theta_true = np.where(rng.random(n_tx) < 0.3, 0.0, rng.lognormal(0.0, 2.0, size=n_tx))
+    R = rng.poisson(E * np.add.reduceat(theta_true[ci], rp[:-1].astype(np.int64))).astype(np.int32)
+    return n_tx, rp, ci, R, E
+
+
+def run(dev, B, solve_kw, seed=1):
+    dev.solve(**solve_kw)                                 # sets found and packed, warm
+    t0 = time.perf_counter()
+    th, st = dev.solve(**solve_kw)
+    solve_s = time.perf_counter() - t0
+    dev.bootstrap(min(B, 2), seed, **solve_kw)            # first call: draw map, kernels loaded
+    t0 = time.perf_counter()
+    mean, sd, tsd, _, bs = dev.bootstrap(B, seed, **solve_kw)
+    boot_s = time.perf_counter() - t0
+    return {"solve_ms": solve_s * 1e3, "solve_kernel_ms": st.kernel_ms, "solve_set_passes_max": st.set_passes_max,
+            "sets_resident": st.sets_resident, "sets_streamed": st.sets_streamed, "replicates": B, "boot_wall_ms": boot_s * 1e3,
+            "boot_ms_per_replicate": boot_s * 1e3 / B, "replicate_over_solve": boot_s / B / solve_s, **bs.as_dict(),
+            "sd_fpkm_median_rel": float(np.median((sd / np.maximum(mean, 1e-300))[mean > 1e-3]))}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=100)
+    ap.add_argument("--cfg3-scale", type=float, default=0.1)
+    ap.add_argument("--cfg3-reps", type=int, default=10)
+    ap.add_argument("--skip-cfg3", action="store_true")
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    from emsar_amd import EmsarHip, synth
+    out = {}
+    with EmsarHip(0) as dev:
+        n_tx, rp, ci, R, E = segment_problem()
+        dev.upload_structure(n_tx, rp, ci)
+        dev.upload_sample(R, E, None)
+        out["segment"] = {"n_tx": int(n_tx), "segments": int(len(R)), **run(dev, a.reps, dict(max_iter=200000, tol=1e-10))}
+        if not a.skip_cfg3:
+            import bench
+            cfg = dict(synth.CONFIGS["cfg3"])
+            cfg["n_reads"] = max(1000, int(cfg["n_reads"] * a.cfg3_scale))
+            s = bench.family_matrix_threaded(**cfg)
+            crp, cci, cw, _, _ = dev.collapse_rows(s["n_tx"], s["row_ptr"], s["col_idx"], want_map=False)
+            dev.set_deterministic(True)
+            dev.upload_structure(s["n_tx"], crp, cci)
+            dev.upload_sample(cw, None, s["den"])
+            kw = dict(max_iter=200000, tol=1e-10, zero_cut=2.5e-7, abs_step=1e-13)
+            out["cfg3"] = {"scale": a.cfg3_scale, "reads": int(s["n_reads"]), "n_tx": int(s["n_tx"]), "segments": int(len(cw)),
+                           **run(dev, a.cfg3_reps, kw)}
+    txt = json.dumps(out, indent=1)
+    print(txt)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(txt + "\n")
+
+
+if __name__ == "__main__":
+    main()
