@@ -72,8 +72,12 @@ def test_device_draws_equal_host_draws(dev):
     assert (got[~small] == want[~small]).mean() >= 0.999
 
 
-@pytest.mark.parametrize("set_mode", [0, 1])
-def test_replicates_are_solves_of_their_draws(set_mode):
+@pytest.mark.parametrize("set_mode,tiled_multi", [(0, None), (1, None), (1, "5")], ids=["0", "1", "1-unit"])
+def test_replicates_are_solves_of_their_draws(set_mode, tiled_multi, monkeypatch):
+    """1-unit: the streaming solves with the unit kernel forced (EMSAR_HIP_TILED_MULTI=5), so that the replicates' swapped-in
+    weights go through k_pass_tiled_unit<true, MODE_EM> as well."""
+    if tiled_multi is not None:
+        monkeypatch.setenv("EMSAR_HIP_TILED_MULTI", tiled_multi)
     with EmsarHip(0) as a, EmsarHip(0) as b:
         for name, m in _problems():
             a.upload_structure(m.n_tx, m.row_ptr, m.col_idx)
