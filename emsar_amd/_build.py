@@ -5,7 +5,7 @@
 
 Outputs (git-ignored, shipped to the GPU box by gpurun):
     emsar_amd/libemsar_hip.so     kernels + C ABI (include/emsar_hip.h)
-    emsar_amd/libemsar_host.so    C host: rsh / alignment readers, model preparation, .fpkm writer
+    emsar_amd/libemsar_host.so    C host: rsh / alignment readers, model preparation, g2t reader, output writers
     emsar_amd/emsar-hip           C command-line driver linked against both
 hipcc cross-compiles without a GPU; intermediates (.s with register usage) go to build/.
 """
@@ -26,7 +26,7 @@ CLI = os.path.join(PKG, "emsar-hip")
 
 HIP_FLAGS = ["-O3", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-std=c++17", "-fPIC", "-shared",
              "-Wall", "-Wextra", "-Wno-unused-value"]
-HOST_SRC = ["rsh.c", "align.c", "model.c", "output.c", "pbgzf.c", "hostutil.c"]
+HOST_SRC = ["rsh.c", "align.c", "model.c", "output.c", "pbgzf.c", "hostutil.c", "genes.c"]
 C_FLAGS = ["-O2", "-std=c11", "-fPIC", "-Wall", "-Wextra", "-D_POSIX_C_SOURCE=200809L"]
 
 

@@ -16,6 +16,7 @@
 //                         k_normalise, k_adj_euma, small reductions
 //   kernels_sets.hpp      k_solve_sets                           one workgroup solves one connected set out of LDS
 //   kernels_boot.hpp      k_boot_draw, k_boot_accum, ...         the Poisson bootstrap (draws: boot_rng.hpp; sets: k_solve_sets_boot)
+//   kernels_genes.hpp     k_gene_sums, k_gene_finish             per-gene sums in a fixed order (gene_sums, the bootstrap's gene sd)
 //   collapse.hip          read-level rows -> weighted segments (own translation unit)
 #include <hip/hip_runtime.h>
 
@@ -42,6 +43,7 @@
 #include "kernels_sets.hpp"
 #include "kernels_cluster.hpp"
 #include "kernels_boot.hpp"
+#include "kernels_genes.hpp"
 
 // ==================================================================================================
 // context
@@ -127,6 +129,13 @@ struct emsar_hip_ctx {
     int64_t *d_boot_slot = nullptr;   // caller row -> index into one replicate's [row_w | usum] block, -1 = none
     int64_t boot_n_rw = 0;            // row_w entries of the resident sets (usum follows them)
     bool boot_slot_ready = false;
+    // gene map (emsar_hip_set_gene_map), dropped by upload_structure.  One int32 block: per gene in gene order its transcripts' library
+    // indices by ascending caller tid (gene_tx), the chunks' begin offsets into gene_tx (chunk_beg, n_gene_chunks + 1), each chunk's
+    // gene when that gene has one chunk, else -1 (chunk_out), and the genes of more than one chunk (gene_multi: gene, first chunk, end)
+    bool have_genes = false;
+    int32_t n_genes = 0;
+    int64_t n_gene_chunks = 0, n_gene_multi = 0;
+    int32_t *d_gene_blk = nullptr, *d_gene_tx = nullptr, *d_chunk_beg = nullptr, *d_chunk_out = nullptr, *d_gene_multi = nullptr;
 };
 
 namespace {
@@ -185,8 +194,15 @@ void free_sets(emsar_hip_ctx *ctx) {
     ctx->boot_n_rw = 0; ctx->boot_slot_ready = false;
 }
 
+void free_genes(emsar_hip_ctx *ctx) {
+    dfree(ctx->d_gene_blk);
+    ctx->d_gene_blk = ctx->d_gene_tx = ctx->d_chunk_beg = ctx->d_chunk_out = ctx->d_gene_multi = nullptr;
+    ctx->have_genes = false; ctx->n_genes = 0; ctx->n_gene_chunks = ctx->n_gene_multi = 0;
+}
+
 void free_structure(emsar_hip_ctx *ctx) {
     free_sets(ctx);
+    free_genes(ctx);
     dfree(ctx->d_euma_t); dfree(ctx->d_wf); dfree(ctx->d_adj); ctx->d_euma_t = nullptr; ctx->d_wf = ctx->d_adj = nullptr; ctx->nfl = 0;
     std::vector<uint64_t>().swap(ctx->h_row_ptr); std::vector<int32_t>().swap(ctx->h_col); std::vector<int32_t>().swap(ctx->h_wgt);
     dfree(ctx->d_row_ptr); dfree(ctx->d_col);
@@ -1159,8 +1175,25 @@ struct BootRestore {
     }
 };
 
+// Gene sums of ncol (<= 65535) rows x[ncol][n_tx] in library order into out[ncol][n_genes], on the context's stream; part holds
+// ncol * n_gene_chunks doubles (may be null when no gene has more than one chunk).
+static int launch_gene_sums(emsar_hip_ctx *ctx, const double *x, int64_t ncol, double *out, double *part) {
+    if (ctx->n_gene_chunks > 0)
+        hipLaunchKernelGGL(k_gene_sums, dim3((unsigned)grid_for(ctx->n_gene_chunks, 256), (unsigned)ncol), dim3(256), 0, ctx->stream,
+                           ctx->n_gene_chunks, ctx->d_chunk_beg, ctx->d_chunk_out, ctx->d_gene_tx, x, (int64_t)ctx->n_tx, out,
+                           (int64_t)ctx->n_genes, part);
+    if (ctx->n_gene_multi > 0)
+        hipLaunchKernelGGL(k_gene_finish, dim3((unsigned)grid_for(ctx->n_gene_multi, 256), (unsigned)ncol), dim3(256), 0, ctx->stream,
+                           ctx->n_gene_multi, ctx->d_gene_multi, part, ctx->n_gene_chunks, out, (int64_t)ctx->n_genes);
+    HIPCHK(hipGetLastError());
+    return EMSAR_HIP_OK;
+}
+
+// gene_* (all null = no gene outputs): per gene the bootstrap mean and sd of its FPKM sum and the sd of its TPM sum
 static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_t seed, int32_t first, int32_t n_rep, double *fpkm_mean,
-                          double *fpkm_sd, double *tpm_sd, double *replicates, emsar_boot_stats *stats) {
+                          double *fpkm_sd, double *tpm_sd, double *replicates, double *gene_mean, double *gene_sd, double *gene_tpm_sd,
+                          emsar_boot_stats *stats) {
+    const bool genes = gene_mean != nullptr;
     const auto tw0 = std::chrono::steady_clock::now();
     emsar_em_params p = solve_params(pp);
     if (!(p.count_floor >= 0.0) || (p.set_mode != 0 && p.set_mode != 1)) return EMSAR_HIP_ERR_ARG;
@@ -1180,7 +1213,8 @@ static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_
     int64_t n_gu = 0;
     if (use_sets) for (int c = 0; c < emsar::kSetClasses; c++) for (const auto &d : S.desc[c]) n_gu += d.n_t;
     // replicates per batch: what fits a quarter of the free device memory (at most 2 GiB), EMSAR_HIP_BOOT_BATCH overrides
-    const int64_t per_rep = 8 * (slot_stride + n_gu + n + 1) + (need_stream ? 4 * n_rows : 0) + (int64_t)sizeof(SetStat) * n_sets;
+    const int64_t ng = genes ? ctx->n_genes : 0, n_gchunk = genes && ctx->n_gene_multi > 0 ? ctx->n_gene_chunks : 0;
+    const int64_t per_rep = 8 * (slot_stride + n_gu + n + 1 + ng + n_gchunk) + (need_stream ? 4 * n_rows : 0) + (int64_t)sizeof(SetStat) * n_sets;
     size_t mfree = 0, mtotal = 0;
     if (hipMemGetInfo(&mfree, &mtotal) != hipSuccess) mfree = (size_t)1 << 30;
     const int64_t budget = std::min<int64_t>((int64_t)(mfree / 4), (int64_t)2 << 30);
@@ -1196,6 +1230,13 @@ static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_
     HIPCHK(guard.alloc((void **)&d_thb, (size_t)(batch * n) * 8));
     HIPCHK(guard.alloc((void **)&d_sums, (size_t)batch * 8));
     HIPCHK(guard.alloc((void **)&d_acc4, (size_t)4 * n * 8));
+    double *d_gsum = nullptr, *d_gpart = nullptr, *d_gacc4 = nullptr;       // [batch][n_genes], [batch][n_gene_chunks], [4][n_genes]
+    if (genes) {
+        HIPCHK(guard.alloc((void **)&d_gsum, (size_t)(batch * ng) * 8));
+        if (n_gchunk) HIPCHK(guard.alloc((void **)&d_gpart, (size_t)(batch * n_gchunk) * 8));
+        HIPCHK(guard.alloc((void **)&d_gacc4, (size_t)4 * ng * 8));
+        HIPCHK(hipMemsetAsync(d_gacc4, 0, (size_t)4 * ng * 8, ctx->stream));
+    }
     if (need_stream) HIPCHK(guard.alloc((void **)&d_wb, (size_t)(batch * n_rows) * 4));
     if (n_sets) HIPCHK(guard.alloc((void **)&d_bstat, (size_t)(batch * n_sets) * sizeof(SetStat)));
     HIPCHK(hipMalloc(&guard.d_th0, std::max<size_t>((size_t)n, 1) * 8));
@@ -1289,6 +1330,11 @@ static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_
         hipLaunchKernelGGL(k_boot_sums, dim3((unsigned)nb), dim3(1024), 0, ctx->stream, n, d_thb, d_sums);
         hipLaunchKernelGGL(k_boot_accum, dim3(gn), dim3(256), 0, ctx->stream, n, (int)nb, done, d_thb, d_sums, d_acc4);
         HIPCHK(hipGetLastError());
+        if (genes) {   // the replicates' gene sums, then the same Welford step on them (gene TPM_b = G_b * 1e6 / S_b)
+            if ((rc = launch_gene_sums(ctx, d_thb, nb, d_gsum, d_gpart))) return rc;
+            hipLaunchKernelGGL(k_boot_accum, dim3((unsigned)grid_for(ng, 256)), dim3(256), 0, ctx->stream, (int)ng, (int)nb, done, d_gsum, d_sums, d_gacc4);
+            HIPCHK(hipGetLastError());
+        }
         if ((rc = lap(reduce_ms))) return rc;
         if (replicates) {
             HIPCHK(hipMemcpy(replicates + done * n, d_thb, (size_t)(nb * n) * 8, hipMemcpyDeviceToHost));
@@ -1307,6 +1353,17 @@ static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_
         tpm_sd[t] = n_rep > 1 ? std::sqrt(acc[(size_t)3 * n + t] / (double)(n_rep - 1)) : 0.0;
     }
     try { from_lib(ctx, fpkm_mean); from_lib(ctx, fpkm_sd); from_lib(ctx, tpm_sd); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+    if (genes) {   // gene order is the caller's: no renumbering to undo
+        std::vector<double> gacc((size_t)4 * ng);
+        HIPCHK(hipMemcpyAsync(gacc.data(), d_gacc4, gacc.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        for (int64_t g = 0; g < ng; g++) {
+            if (!std::isfinite(gacc[(size_t)g]) || !std::isfinite(gacc[(size_t)(ng + g)])) { ctx->err = "non-finite gene sum in a bootstrap replicate"; return EMSAR_HIP_ERR_NUMERIC; }
+            gene_mean[g] = gacc[(size_t)g];
+            gene_sd[g] = n_rep > 1 ? std::sqrt(gacc[(size_t)(ng + g)] / (double)(n_rep - 1)) : 0.0;
+            gene_tpm_sd[g] = n_rep > 1 ? std::sqrt(gacc[(size_t)(3 * ng + g)] / (double)(n_rep - 1)) : 0.0;
+        }
+    }
     if (stats) {
         memset(stats, 0, sizeof(*stats));
         stats->n_replicates = n_rep; stats->batch = (int32_t)batch; stats->replicates_unconverged = unconverged; stats->set_passes_max = passes_max;
@@ -1338,8 +1395,104 @@ int emsar_hip_bootstrap(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t s
         (int64_t)first_replicate + (int64_t)n_replicates > (int64_t)INT32_MAX + 1)
         return EMSAR_HIP_ERR_ARG;
     try {
-        return bootstrap_impl(ctx, p, seed, first_replicate, n_replicates, fpkm_mean, fpkm_sd, tpm_sd, replicates, stats);
+        return bootstrap_impl(ctx, p, seed, first_replicate, n_replicates, fpkm_mean, fpkm_sd, tpm_sd, replicates, nullptr, nullptr, nullptr, stats);
     } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+}
+
+int emsar_hip_bootstrap_genes(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t first_replicate, int32_t n_replicates,
+                              double *fpkm_mean, double *fpkm_sd, double *tpm_sd, double *replicates,
+                              double *gene_fpkm_mean, double *gene_fpkm_sd, double *gene_tpm_sd, emsar_boot_stats *stats) {
+    if (!ctx) return EMSAR_HIP_ERR_ARG;
+    if (!ctx->have_sample || !ctx->have_genes) return EMSAR_HIP_ERR_STATE;
+    if (!fpkm_mean || !fpkm_sd || !tpm_sd || !gene_fpkm_mean || !gene_fpkm_sd || !gene_tpm_sd || n_replicates < 1 || first_replicate < 0 ||
+        (int64_t)first_replicate + (int64_t)n_replicates > (int64_t)INT32_MAX + 1)
+        return EMSAR_HIP_ERR_ARG;
+    try {
+        return bootstrap_impl(ctx, p, seed, first_replicate, n_replicates, fpkm_mean, fpkm_sd, tpm_sd, replicates, gene_fpkm_mean, gene_fpkm_sd,
+                              gene_tpm_sd, stats);
+    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+}
+
+// ---- gene map -----------------------------------------------------------------------------------------------------------------
+int emsar_hip_set_gene_map(emsar_hip_ctx *ctx, int32_t n_genes, const int32_t *gene_of_tx) {
+    if (!ctx) return EMSAR_HIP_ERR_ARG;
+    if (!ctx->have_structure) return EMSAR_HIP_ERR_STATE;
+    if (n_genes < 1 || (!gene_of_tx && ctx->n_tx > 0)) return EMSAR_HIP_ERR_ARG;
+    const int32_t n = ctx->n_tx;
+    for (int32_t t = 0; t < n; t++) if (gene_of_tx[t] < -1 || gene_of_tx[t] >= n_genes) return EMSAR_HIP_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    free_genes(ctx);
+    try {
+        // gene CSR in library indices, each gene's transcripts by ascending caller tid; then its chunks of kGeneChunk
+        std::vector<int64_t> gp((size_t)n_genes + 1, 0);
+        for (int32_t t = 0; t < n; t++) if (gene_of_tx[t] >= 0) gp[(size_t)gene_of_tx[t] + 1]++;
+        for (int32_t g = 0; g < n_genes; g++) gp[(size_t)g + 1] += gp[(size_t)g];
+        const int64_t m = gp[(size_t)n_genes];
+        std::vector<int32_t> tx((size_t)m), chunk_beg, chunk_out, multi;
+        std::vector<int64_t> fill(gp.begin(), gp.end() - 1);
+        const auto &map = tid_map(ctx);
+        const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !map.empty();
+        for (int32_t t = 0; t < n; t++)
+            if (gene_of_tx[t] >= 0) tx[(size_t)fill[(size_t)gene_of_tx[t]]++] = remap ? map[(size_t)t] : t;
+        for (int32_t g = 0; g < n_genes; g++) {
+            const int64_t len = gp[(size_t)g + 1] - gp[(size_t)g];
+            const int64_t nch = std::max<int64_t>(1, (len + kGeneChunk - 1) / kGeneChunk);     // an empty gene: one empty chunk, sum 0
+            if (nch > 1) { multi.push_back(g); multi.push_back((int32_t)chunk_out.size()); multi.push_back((int32_t)(chunk_out.size() + nch)); }
+            for (int64_t j = 0; j < nch; j++) {
+                chunk_beg.push_back((int32_t)(gp[(size_t)g] + j * kGeneChunk));
+                chunk_out.push_back(nch == 1 ? g : -1);
+            }
+            if (chunk_out.size() > (size_t)INT32_MAX - 1) return EMSAR_HIP_ERR_ARG;
+        }
+        chunk_beg.push_back((int32_t)m);
+        const size_t nc = chunk_out.size();
+        std::vector<int32_t> blk;
+        blk.reserve((size_t)m + 2 * nc + 1 + multi.size());
+        blk.insert(blk.end(), tx.begin(), tx.end());
+        blk.insert(blk.end(), chunk_beg.begin(), chunk_beg.end());
+        blk.insert(blk.end(), chunk_out.begin(), chunk_out.end());
+        blk.insert(blk.end(), multi.begin(), multi.end());
+        HIPCHK(hipMalloc(&ctx->d_gene_blk, blk.size() * 4));
+        hipError_t e = hipMemcpy(ctx->d_gene_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { free_genes(ctx); HIPCHK(e); }
+        ctx->d_gene_tx = ctx->d_gene_blk;
+        ctx->d_chunk_beg = ctx->d_gene_tx + m;
+        ctx->d_chunk_out = ctx->d_chunk_beg + nc + 1;
+        ctx->d_gene_multi = ctx->d_chunk_out + nc;
+        ctx->n_genes = n_genes; ctx->n_gene_chunks = (int64_t)nc; ctx->n_gene_multi = (int64_t)multi.size() / 3;
+        ctx->have_genes = true;
+    } catch (const std::bad_alloc &) { free_genes(ctx); return EMSAR_HIP_ERR_OOM; }
+    return EMSAR_HIP_OK;
+}
+
+int emsar_hip_gene_sums(emsar_hip_ctx *ctx, int32_t n_cols, const double *tx_values, double *gene_out) {
+    if (!ctx) return EMSAR_HIP_ERR_ARG;
+    if (!ctx->have_structure || !ctx->have_genes) return EMSAR_HIP_ERR_STATE;
+    if (n_cols < 1 || !tx_values || !gene_out) return EMSAR_HIP_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t n = ctx->n_tx, ng = ctx->n_genes, nc = ctx->n_gene_multi > 0 ? ctx->n_gene_chunks : 0;
+    const int64_t cb = std::min<int64_t>(n_cols, 65535);        // columns per launch (grid y)
+    double *d_x = nullptr, *d_out = nullptr, *d_part = nullptr;
+    struct Free { double **p[3]; ~Free() { for (auto q : p) dfree(*q); } } fr{{&d_x, &d_out, &d_part}};
+    HIPCHK(hipMalloc(&d_x, (size_t)std::max<int64_t>(cb * n, 1) * 8));
+    HIPCHK(hipMalloc(&d_out, (size_t)(cb * ng) * 8));
+    if (nc) HIPCHK(hipMalloc(&d_part, (size_t)(cb * nc) * 8));
+    try {
+        std::vector<double> tmp;
+        for (int64_t c0 = 0; c0 < n_cols; c0 += cb) {
+            const int64_t k = std::min<int64_t>(cb, n_cols - c0);
+            for (int64_t j = 0; j < k; j++) {
+                const double *col = to_lib(ctx, tx_values + (c0 + j) * n, tmp);
+                HIPCHK(hipMemcpy(d_x + j * n, col, (size_t)n * 8, hipMemcpyHostToDevice));
+            }
+            int rc = launch_gene_sums(ctx, d_x, k, d_out, d_part);
+            if (rc) return rc;
+            HIPCHK(hipMemcpyAsync(gene_out + c0 * ng, d_out, (size_t)(k * ng) * 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+        }
+    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+    return EMSAR_HIP_OK;
 }
 
 int emsar_hip_bootstrap_weights(emsar_hip_ctx *ctx, uint64_t seed, int32_t replicate, int32_t *w_out) {

@@ -17,6 +17,10 @@
  * spread comes from its random restarts (documented deviation).  For an uncertainty measure,
  * --bootstrap B writes <prefix>.<i>.bootstrap: mean and sd of FPKM and sd of TPM over B Poisson bootstrap replicates
  * (emsar_hip_bootstrap; seed --bootstrap-seed + i).  .fpkm, .fraglength_effect and .segments do not change with it.
+ * --g2t FILE adds the reference's gene step (util/FPKM2gFPKM.pl, run by util/post_processing.pl): <prefix>.<i>.gfpkm, the per-gene
+ * sums of FPKM, iReadcount and TPM (emsar_hip_gene_sums; the map is read once, genes.c), which merge_gTPM.pl / merge_gReadcount.pl
+ * read as they are; with --bootstrap also <prefix>.<i>.gbootstrap, the genes' bootstrap mean and sd from the same replicates
+ * (emsar_hip_bootstrap_genes).  The other files are the same bytes with and without it.
  *
  * -M: samples are independent (emsar_main.c:380-488 resets every count per file), so sample i runs on GPU
  * i mod G with one host thread per GPU; no collective.  The only cross-sample state of the reference, EUMAcut
@@ -45,6 +49,8 @@ typedef struct {
     const char *stats_json;
     const char *rsh_cache;      /* NULL = off, "" = <rsh>.bin, else the path */
     int boot_n; uint64_t boot_seed;   /* --bootstrap B (0 = off), --bootstrap-seed: sample i uses seed + i */
+    const char *g2t;                  /* --g2t FILE (NULL = off) */
+    const emsar_genes *genes;         /* its gene map, read once by main() and shared read-only by the workers */
 } config;
 
 typedef struct {
@@ -101,6 +107,7 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
     char err[512] = "", path[4096];
     emsar_counts *cnt = parsed->cnt; emsar_model *m = NULL;
     double *theta = NULL, *rounds = NULL, *mean = NULL, *sd = NULL, *ieuma = NULL, *tpm = NULL, *ir = NULL, *den = NULL; int32_t *iri = NULL;
+    double *gcols = NULL, *gsums = NULL;     /* --g2t: [3][n_tx] FPKM, iReadcount, TPM and their [3][n_genes] gene sums */
     int rc = parsed->rc;
     parsed->cnt = NULL;
     snprintf(err, sizeof err, "%s", parsed->err);
@@ -193,24 +200,46 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         if ((rc = emsar_write_segments(path, r, cnt, m, mean))) { fprintf(stderr, "can't write %s\n", path); goto done; }
     }
     w->host_s[i] += now_s() - t_host;
-    /* ---- Poisson bootstrap (--bootstrap B): its own file; .fpkm keeps the reference's column 3 ---- */
+    /* ---- gene level (--g2t): FPKM2gFPKM.pl's sums of columns FPKM, iReadcount and TPM per gene, on the device ---- */
+    const emsar_genes *G = cfg->genes;
+    const size_t NG = G ? (size_t)G->n_genes : 0;
+    if (G) {
+        gcols = (double *)malloc(T * 8 * 3); gsums = (double *)malloc(NG * 8 * 3);
+        if (!gcols || !gsums) { rc = EMSAR_HOST_ERR_OOM; goto done; }
+        memcpy(gcols, mean, T * 8); memcpy(gcols + T, ir, T * 8); memcpy(gcols + 2 * T, tpm, T * 8);
+        if ((rc = emsar_hip_gene_sums(ctx, 3, gcols, gsums))) {
+            fprintf(stderr, "alnfile[%d]: gene sums: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+            goto done;
+        }
+        snprintf(path, sizeof path, "%s/%s.%d.gfpkm", cfg->outdir, cfg->prefix, i);
+        if ((rc = emsar_write_gfpkm(path, G, gsums, gsums + NG, gsums + 2 * NG))) { fprintf(stderr, "can't write %s\n", path); goto done; }
+    }
+    /* ---- Poisson bootstrap (--bootstrap B): its own file; .fpkm keeps the reference's column 3.  With --g2t the same replicates
+     *      give the genes' sd as well (bootstrap_genes: the transcript outputs are the same bits as bootstrap's) ---- */
     if (cfg->boot_n > 0) {
         double *bm = (double *)malloc(T * 8), *bs = (double *)malloc(T * 8), *bt = (double *)malloc(T * 8);
-        if (!bm || !bs || !bt) rc = EMSAR_HOST_ERR_OOM;
-        else if ((rc = emsar_hip_bootstrap(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, bm, bs, bt, NULL, &w->bstats[i])))
+        double *gb = G ? (double *)malloc(NG * 8 * 3) : NULL;
+        if (!bm || !bs || !bt || (G && !gb)) rc = EMSAR_HOST_ERR_OOM;
+        else if ((rc = G ? emsar_hip_bootstrap_genes(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, bm, bs, bt, NULL, gb, gb + NG, gb + 2 * NG,
+                                                     &w->bstats[i])
+                         : emsar_hip_bootstrap(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, bm, bs, bt, NULL, &w->bstats[i])))
             fprintf(stderr, "alnfile[%d]: bootstrap: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
         else {
             snprintf(path, sizeof path, "%s/%s.%d.bootstrap", cfg->outdir, cfg->prefix, i);
             if ((rc = emsar_write_bootstrap(path, r, mean, bm, bs, tpm, bt))) fprintf(stderr, "can't write %s\n", path);
+            else if (G) {
+                snprintf(path, sizeof path, "%s/%s.%d.gbootstrap", cfg->outdir, cfg->prefix, i);
+                if ((rc = emsar_write_gbootstrap(path, G, gsums, gb, gb + NG, gsums + 2 * NG, gb + 2 * NG))) fprintf(stderr, "can't write %s\n", path);
+            }
         }
-        free(bm); free(bs); free(bt);
+        free(bm); free(bs); free(bt); free(gb);
         if (rc) goto done;
     }
     if (cfg->verbose > 0)
         fprintf(stdout, "Complete: %s/%s.%d.fpkm  (EM passes %d, converged %d, solve %.1f ms, logL %.6f)\n", cfg->outdir, cfg->prefix, i,
                 w->stats[i].iters, w->stats[i].converged, w->stats[i].solve_ms, w->stats[i].loglik);
 done:
-    free(theta); free(rounds); free(mean); free(sd); free(ieuma); free(tpm); free(ir); free(iri); free(den);
+    free(theta); free(rounds); free(mean); free(sd); free(ieuma); free(tpm); free(ir); free(iri); free(den); free(gcols); free(gsums);
     emsar_counts_free(cnt); emsar_model_free(m);
     return rc;
 }
@@ -237,6 +266,7 @@ static void *worker_main(void *a) {
     if (rc == 0) rc = emsar_hip_set_deterministic(ctx, !w->cfg->no_deterministic);     /* the streamed part of a solve: same bytes every run */
     if (rc == 0) rc = emsar_hip_upload_structure(ctx, w->rsh->n_rows, w->rsh->n_tx, w->rsh->row_ptr, w->rsh->col_idx, EMSAR_LAYOUT_AUTO);
     if (rc == 0) rc = emsar_hip_upload_euma(ctx, w->rsh->euma, w->rsh->nfl);     /* once per rsh: compute_adjEUMA runs on the device */
+    if (rc == 0 && w->cfg->genes) rc = emsar_hip_set_gene_map(ctx, w->cfg->genes->n_genes, w->cfg->genes->gene_of_tx);
     if (rc) fprintf(stderr, "GPU %d: %s\n", w->device, emsar_hip_strerror(rc));
     for (int i = w->worker; i < w->cfg->n_aln; i += w->n_workers) {
         parse_job *cur = &slot[c];
@@ -286,6 +316,8 @@ static void usage(const char *a0) {
             "      --bootstrap <B>       also write <outdir>/<prefix>.<i>.bootstrap: mean and sd of FPKM and sd of TPM over B Poisson\n"
             "                            bootstrap replicates of the sample (default 0 = off; .fpkm is the same either way)\n"
             "      --bootstrap-seed <n>  seed of the replicates' draws (default 1; sample i of -M uses n + i)\n"
+            "      --g2t <file>          gene map (gene<TAB>transcript per line, plain or gzipped): also write <prefix>.<i>.gfpkm, the\n"
+            "                            per-gene sums of util/FPKM2gFPKM.pl, and with --bootstrap <prefix>.<i>.gbootstrap (gene sd)\n"
             "      --gpus <n> / --devices <a,b,..> (-M: one worker per entry, ids may repeat) / --device <d> / --plain /\n"
             "      --stats-json <file> / -q / -v\n", a0);
 }
@@ -306,7 +338,7 @@ int main(int argc, char **argv) {
         {"verbose", no_argument, 0, 'v'}, {"no_verbose", no_argument, 0, 'q'}, {"gpus", required_argument, 0, 1000},
         {"device", required_argument, 0, 1001}, {"plain", no_argument, 0, 1002}, {"stats-json", required_argument, 0, 1003},
         {"count-floor", required_argument, 0, 1004}, {"streaming-only", no_argument, 0, 1005}, {"rsh-cache", optional_argument, 0, 1006}, {"zero-cut", required_argument, 0, 1007}, {"abs-step", required_argument, 0, 1008}, {"devices", required_argument, 0, 1009}, {"device-collapse", no_argument, 0, 1010}, {"no-deterministic", no_argument, 0, 1011},
-        {"bootstrap", required_argument, 0, 1012}, {"bootstrap-seed", required_argument, 0, 1013},
+        {"bootstrap", required_argument, 0, 1012}, {"bootstrap-seed", required_argument, 0, 1013}, {"g2t", required_argument, 0, 1014},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
@@ -352,6 +384,7 @@ int main(int argc, char **argv) {
                 cfg.boot_seed = (uint64_t)v;
                 break;
             }
+            case 1014: cfg.g2t = optarg; break;
             case 1009: {
                 const char *q = optarg;
                 while (*q && n_dev_map < 64) {
@@ -426,6 +459,14 @@ int main(int argc, char **argv) {
     free(cache_path);
     if (cfg.verbose > 0) fprintf(stdout, "rsh: %d transcripts, %lld segments, fragment lengths %d-%d (%.2fs)\n", rsh->n_tx,
                                  (long long)rsh->n_rows, rsh->frag_min, rsh->frag_max, now_s() - t0);
+    emsar_genes *genes = NULL;
+    if (cfg.g2t) {                             /* before any sample: a bad gene map ends the run here */
+        if (emsar_genes_read(rsh, cfg.g2t, &genes, err, sizeof err)) { fprintf(stderr, "%s\n", err); emsar_rsh_free(rsh); return 1; }
+        cfg.genes = genes;
+        if (cfg.verbose > 1)
+            fprintf(stdout, "g2t: %d genes; %lld g2t lines name a transcript not in the index (ignored); %d index transcripts in no gene%s\n",
+                    genes->n_genes, (long long)genes->n_unknown, genes->n_unmapped, genes->n_unmapped ? " (empty geneID)" : "");
+    }
 
     int n_workers = 1;
     if (multisample) {
@@ -507,6 +548,7 @@ int main(int argc, char **argv) {
         }
     }
     emsar_rsh_free(rsh);
+    emsar_genes_free(genes);
     for (int i = 0; i < n_list; i++) free(list[i]);
     free(list); free(status); free(stats); free(bstats); free(parse_s); free(model_s); free(host_s); free(wa); free(th);
     return bad ? 1 : 0;

@@ -137,6 +137,25 @@ int emsar_write_fpkm(const char *path, const emsar_rsh *r, const double *mean, c
 /* .bootstrap (emsar-hip --bootstrap): transcriptID FPKM boot.mean.FPKM boot.sd.FPKM TPM boot.sd.TPM, "%lf" like .fpkm */
 int emsar_write_bootstrap(const char *path, const emsar_rsh *r, const double *fpkm, const double *boot_mean, const double *boot_sd,
                           const double *tpm, const double *boot_tpm_sd);
+/* gene map of a g2t file (genes.c: util/FPKM2gFPKM.pl's rules, last line wins, unlisted transcripts in one gene with an empty ID;
+ * plain or gzipped).  gene_of_tx[t] in 0 .. n_genes-1 for every index transcript; genes in order of first appearance in the file,
+ * the empty-ID gene (if any transcript falls into it) last. */
+typedef struct {
+    int32_t n_genes, n_tx;
+    char **names;            /* n_genes; "" = the gene of the transcripts the g2t does not list */
+    int32_t *gene_of_tx;     /* n_tx */
+    int64_t n_unknown;       /* g2t lines whose transcript is not in the index (ignored) */
+    int32_t n_unmapped;      /* index transcripts in the empty-ID gene */
+} emsar_genes;
+int  emsar_genes_read(const emsar_rsh *r, const char *g2t_path, emsar_genes **out, char *err, size_t errlen);
+void emsar_genes_free(emsar_genes *g);
+
+/* .gfpkm (emsar-hip --g2t): FPKM2gFPKM.pl's header and columns, "%s\t%lf\t%lf\t%d\t%lf\n"; iReadcount.int is the script's half-up
+ * roundoff of the gene's iReadcount.  Per-gene arrays of n_genes. */
+int emsar_write_gfpkm(const char *path, const emsar_genes *g, const double *fpkm, const double *ireadcount, const double *tpm);
+/* .gbootstrap (emsar-hip --g2t --bootstrap): the columns of .bootstrap per gene */
+int emsar_write_gbootstrap(const char *path, const emsar_genes *g, const double *fpkm, const double *boot_mean, const double *boot_sd,
+                           const double *tpm, const double *boot_tpm_sd);
 int emsar_write_fraglength(const char *path, const emsar_rsh *r, const emsar_counts *c, const emsar_model *m);
 int emsar_write_segments(const char *path, const emsar_rsh *r, const emsar_counts *c, const emsar_model *m,
                          const double *mean_fpkm);

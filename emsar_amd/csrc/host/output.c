@@ -4,10 +4,15 @@
  *   .segments           print_aEUMA_3        emsar_functions.c:2274-2297
  * and the bootstrap's own file (no counterpart in the reference):
  *   .bootstrap          "%s\t%lf\t%lf\t%lf\t%lf\t%lf\n"  FPKM and TPM as in .fpkm, then the Poisson bootstrap's mean / sd
+ * and, with --g2t, the gene files:
+ *   .gfpkm              util/FPKM2gFPKM.pl's header byte for byte, rows "%s\t%lf\t%lf\t%d\t%lf\n" (the script prints Perl's
+ *                       default number format; merge_gTPM.pl / merge_gReadcount.pl read either)
+ *   .gbootstrap         the columns of .bootstrap per gene
  * Column order of .fpkm is a contract: the reference's Perl utilities read columns 0,1,4,6 (util/FPKM2gFPKM.pl:19).
  */
 #include "emsar_host.h"
 
+#include <math.h>
 #include <stdio.h>
 
 int emsar_write_fpkm(const char *path, const emsar_rsh *r, const double *mean, const double *sd, const double *ieuma,
@@ -32,6 +37,31 @@ int emsar_write_bootstrap(const char *path, const emsar_rsh *r, const double *fp
     fprintf(f, "transcriptID\tFPKM\tboot.mean.FPKM\tboot.sd.FPKM\tTPM\tboot.sd.TPM\n");
     for (int32_t t = 0; t < r->n_tx; t++)
         fprintf(f, "%s\t%lf\t%lf\t%lf\t%lf\t%lf\n", r->names[t], fpkm[t], boot_mean[t], boot_sd[t], tpm[t], boot_tpm_sd[t]);
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+/* FPKM2gFPKM.pl's roundoff: ($x - int($x) >= 0.5) ? int($x) + 1 : int($x), int() truncating toward zero */
+static int roundoff(double x) {
+    const double i = trunc(x);
+    return (int)i + (x - i >= 0.5 ? 1 : 0);
+}
+
+int emsar_write_gfpkm(const char *path, const emsar_genes *g, const double *fpkm, const double *ir, const double *tpm) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "geneID\tFPKM\tiReadcount\tiReadcount.int\tTPM\n");
+    for (int32_t k = 0; k < g->n_genes; k++)
+        fprintf(f, "%s\t%lf\t%lf\t%d\t%lf\n", g->names[k], fpkm[k], ir[k], roundoff(ir[k]), tpm[k]);
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+int emsar_write_gbootstrap(const char *path, const emsar_genes *g, const double *fpkm, const double *boot_mean, const double *boot_sd,
+                           const double *tpm, const double *boot_tpm_sd) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "geneID\tFPKM\tboot.mean.FPKM\tboot.sd.FPKM\tTPM\tboot.sd.TPM\n");
+    for (int32_t k = 0; k < g->n_genes; k++)
+        fprintf(f, "%s\t%lf\t%lf\t%lf\t%lf\t%lf\n", g->names[k], fpkm[k], boot_mean[k], boot_sd[k], tpm[k], boot_tpm_sd[k]);
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
 

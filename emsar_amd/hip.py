@@ -21,6 +21,7 @@ SYMBOLS = [
     "emsar_hip_ieuma", "emsar_hip_normalise", "emsar_hip_get_info",
     "emsar_hip_layout_selfcheck_tiled", "emsar_hip_sets_selfcheck", "emsar_hip_upload_euma", "emsar_hip_adj_euma", "emsar_hip_collapse_rows",
     "emsar_hip_set_deterministic", "emsar_hip_bootstrap", "emsar_hip_bootstrap_weights", "emsar_hip_bootstrap_draw_host",
+    "emsar_hip_set_gene_map", "emsar_hip_gene_sums", "emsar_hip_bootstrap_genes",
 ]
 
 
@@ -114,6 +115,10 @@ def load_library():
     L.emsar_hip_bootstrap.argtypes = [vp, C.POINTER(EmParams), C.c_uint64, C.c_int32, C.c_int32, f64p, f64p, f64p, f64p, C.POINTER(BootStats)]
     L.emsar_hip_bootstrap_weights.argtypes = [vp, C.c_uint64, C.c_int32, i32p]
     L.emsar_hip_bootstrap_draw_host.argtypes = [C.c_uint64, C.c_int32, C.c_int64, i32p, i32p]
+    L.emsar_hip_set_gene_map.argtypes = [vp, C.c_int32, i32p]
+    L.emsar_hip_gene_sums.argtypes = [vp, C.c_int32, f64p, f64p]
+    L.emsar_hip_bootstrap_genes.argtypes = [vp, C.POINTER(EmParams), C.c_uint64, C.c_int32, C.c_int32, f64p, f64p, f64p, f64p,
+                                            f64p, f64p, f64p, C.POINTER(BootStats)]
     _lib = L
     return L
 
@@ -189,6 +194,7 @@ class EmsarHip:
         self._h = h
         self.n_tx = 0
         self.n_rows = 0
+        self.n_genes = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -215,6 +221,7 @@ class EmsarHip:
                                                      _p(col_idx, C.c_int32), layout), "upload_structure")
         self.n_tx = int(n_tx)
         self.n_rows = len(row_ptr) - 1
+        self.n_genes = 0                                  # the library drops the gene map
 
     def upload_sample(self, row_weight=None, row_E=None, den=None):
         w, e, d = _arr(row_weight, np.int32), _arr(row_E, np.float64), _arr(den, np.float64)
@@ -245,6 +252,44 @@ class EmsarHip:
         self._chk(self._L.emsar_hip_bootstrap(self._h, C.byref(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(n), _p(mean, C.c_double),
                                               _p(sd, C.c_double), _p(tsd, C.c_double), _p(reps, C.c_double), C.byref(st)), "bootstrap")
         return mean, sd, tsd, reps, st
+
+    def set_gene_map(self, gene_of_tx, n_genes):
+        """gene_of_tx[t] = gene of transcript t (caller numbering) in 0 .. n_genes-1, -1 = no gene.  After upload_structure."""
+        g = _arr(gene_of_tx, np.int32)
+        if self.n_tx and g.shape != (self.n_tx,):          # (before upload_structure the library answers: ERR_STATE)
+            raise ValueError("gene_of_tx must have n_tx entries")
+        self._chk(self._L.emsar_hip_set_gene_map(self._h, int(n_genes), _p(g, C.c_int32)), "set_gene_map")
+        self.n_genes = int(n_genes)
+
+    def gene_sums(self, cols):
+        """Per-gene sums of transcript values in the library's fixed order (include/emsar_hip.h): cols [n_cols][n_tx] -> [n_cols][n_genes],
+        a single vector [n_tx] -> [n_genes]."""
+        x = _arr(cols, np.float64)
+        one = x.ndim == 1
+        x = np.ascontiguousarray(np.atleast_2d(x))
+        if x.shape[1] != self.n_tx:
+            raise ValueError("columns of n_tx values expected")
+        out = np.zeros((x.shape[0], max(self.n_genes, 1)))
+        self._chk(self._L.emsar_hip_gene_sums(self._h, x.shape[0], _p(x, C.c_double), _p(out, C.c_double)), "gene_sums")
+        out = out[:, :self.n_genes]
+        return out[0] if one else out
+
+    def bootstrap_genes(self, n, seed, first=0, want_replicates=False, max_iter=100000, accel=1, tol=1e-10, abs_floor=1e-6, check_every=8,
+                        count_floor=0.0, set_mode=0, zero_cut=0.0, abs_step=0.0, newton_after=0):
+        """bootstrap() plus per-gene statistics over the same replicates.  Returns a dict: fpkm_mean, fpkm_sd, tpm_sd, replicates
+        ([n][n_tx] or None), gene_fpkm_mean, gene_fpkm_sd, gene_tpm_sd, stats."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        T, G = self.n_tx, max(self.n_genes, 1)
+        mean, sd, tsd = np.zeros(T), np.zeros(T), np.zeros(T)
+        gm, gs, gt = np.zeros(G), np.zeros(G), np.zeros(G)
+        reps = np.zeros((n, T)) if (want_replicates and n > 0) else None
+        st = BootStats()
+        self._chk(self._L.emsar_hip_bootstrap_genes(self._h, C.byref(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(n), _p(mean, C.c_double),
+                                                    _p(sd, C.c_double), _p(tsd, C.c_double), _p(reps, C.c_double), _p(gm, C.c_double),
+                                                    _p(gs, C.c_double), _p(gt, C.c_double), C.byref(st)), "bootstrap_genes")
+        k = self.n_genes
+        return {"fpkm_mean": mean, "fpkm_sd": sd, "tpm_sd": tsd, "replicates": reps, "gene_fpkm_mean": gm[:k], "gene_fpkm_sd": gs[:k],
+                "gene_tpm_sd": gt[:k], "stats": st}
 
     def bootstrap_weights(self, seed, replicate):
         """The drawn row weights of one bootstrap replicate (caller row order), drawn on the device."""

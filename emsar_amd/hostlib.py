@@ -42,6 +42,11 @@ class Model(C.Structure):
                 ("CS", C.POINTER(C.c_int32)), ("TS", C.POINTER(C.c_int32)), ("n_sets", C.c_int32), ("eumacut", C.c_double)]
 
 
+class Genes(C.Structure):
+    _fields_ = [("n_genes", C.c_int32), ("n_tx", C.c_int32), ("names", C.POINTER(C.c_char_p)), ("gene_of_tx", C.POINTER(C.c_int32)),
+                ("n_unknown", C.c_int64), ("n_unmapped", C.c_int32)]
+
+
 class HostError(RuntimeError):
     pass
 
@@ -78,6 +83,11 @@ def lib():
         L.emsar_mean_sd.restype = None
         L.emsar_write_fpkm.argtypes = [C.c_char_p, C.POINTER(Rsh), f64p, f64p, f64p, f64p, i32p, f64p, C.POINTER(C.c_int64)]
         L.emsar_write_fraglength.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Counts), C.POINTER(Model)]
+        L.emsar_genes_read.argtypes = [C.POINTER(Rsh), C.c_char_p, C.POINTER(C.POINTER(Genes)), C.c_char_p, C.c_size_t]
+        L.emsar_genes_free.argtypes = [C.POINTER(Genes)]
+        L.emsar_genes_free.restype = None
+        L.emsar_write_gfpkm.argtypes = [C.c_char_p, C.POINTER(Genes), f64p, f64p, f64p]
+        L.emsar_write_gbootstrap.argtypes = [C.c_char_p, C.POINTER(Genes), f64p, f64p, f64p, f64p, f64p]
         L.emsar_write_segments.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Counts), C.POINTER(Model), f64p]
         _lib = L
     return _lib
@@ -188,6 +198,44 @@ class HostRsh:
         if rc != 0:
             raise HostError("write_fpkm rc=%d" % rc)
         return tot.value
+
+    def genes(self, g2t_path):
+        """The gene map of a g2t file (genes.c, util/FPKM2gFPKM.pl's rules): (names, gene_of_tx int32[n_tx]); genes in order of first
+        appearance, the empty-ID gene of the unlisted transcripts last.  self.g2t_counts = (g2t lines with a transcript not in the
+        index, index transcripts in the empty-ID gene)."""
+        p = C.POINTER(Genes)()
+        err = C.create_string_buffer(512)
+        rc = lib().emsar_genes_read(self._p, g2t_path.encode(), C.byref(p), err, 512)
+        if rc != 0:
+            raise HostError("genes_read rc=%d: %s" % (rc, err.value.decode()))
+        try:
+            g = p.contents
+            names = [g.names[k].decode() for k in range(g.n_genes)]
+            gene_of_tx = _np(g.gene_of_tx, g.n_tx, np.int32)
+            self.g2t_counts = (g.n_unknown, g.n_unmapped)
+        finally:
+            lib().emsar_genes_free(p)
+        return names, gene_of_tx
+
+    @staticmethod
+    def _genes_struct(names):
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        g = Genes(len(names), 0, C.cast(arr, C.POINTER(C.c_char_p)), None, 0, 0)
+        g._keep = arr
+        return g
+
+    def write_gfpkm(self, path, names, fpkm, ir, tpm):
+        """.gfpkm: per-gene arrays in the order of `names` (FPKM2gFPKM.pl's header and columns)."""
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (fpkm, ir, tpm)]
+        g = self._genes_struct(names)
+        if lib().emsar_write_gfpkm(path.encode(), C.byref(g), _dp(a[0]), _dp(a[1]), _dp(a[2])) != 0:
+            raise HostError("write_gfpkm")
+
+    def write_gbootstrap(self, path, names, fpkm, boot_mean, boot_sd, tpm, boot_tpm_sd):
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (fpkm, boot_mean, boot_sd, tpm, boot_tpm_sd)]
+        g = self._genes_struct(names)
+        if lib().emsar_write_gbootstrap(path.encode(), C.byref(g), *[_dp(x) for x in a]) != 0:
+            raise HostError("write_gbootstrap")
 
     def write_fraglength(self, path, counts, model):
         if lib().emsar_write_fraglength(path.encode(), self._p, counts._p, model._p) != 0:

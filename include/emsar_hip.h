@@ -220,6 +220,26 @@ int emsar_hip_bootstrap(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t s
                         int32_t n_replicates, double *fpkm_mean, double *fpkm_sd, double *tpm_sd,
                         double *replicates /* n_replicates * n_tx, or NULL */, emsar_boot_stats *stats);
 int emsar_hip_bootstrap_weights(emsar_hip_ctx *ctx, uint64_t seed, int32_t replicate, int32_t *w_out /* n_rows */);
+
+/* ---- gene-level sums (the reference's util/FPKM2gFPKM.pl, on the device) -----------------------------------------------------
+ *   set_gene_map      gene_of_tx[t] = gene of caller transcript t in 0 .. n_genes-1, -1 = in no gene.  After upload_structure
+ *                     (ERR_STATE before); a later upload_structure drops the map.  ERR_ARG for n_genes < 1 or an id < -1 or >= n_genes.
+ *   gene_sums         gene_out[c][g] = sum of tx_values[c][t] over the transcripts t of gene g (0 for a gene without any), for
+ *                     n_cols >= 1 columns of n_tx values in caller order.  ERR_STATE without a map.
+ *   bootstrap_genes   emsar_hip_bootstrap (same arguments, same transcript outputs bit for bit) plus, per gene, the mean and the
+ *                     sample sd (n - 1) over the replicates of G_b,g = the gene sum of theta_b, and the sd of the gene TPM
+ *                     G_b,g * 1e6 / S_b (S_b = sum_t theta_b,t; 0 when S_b = 0), reduced in replicate order like the transcripts.
+ *                     Its sd includes the covariance of a gene's isoforms, which sqrt(sum_t sd_t^2) leaves out.  Their device time is
+ *                     part of emsar_boot_stats.reduce_ms.  ERR_STATE without a map.
+ * Summation order (fixed, so that results are bit for bit the same across layouts, renumbering, batch sizes and devices): a gene's
+ * transcripts in ascending caller tid are cut into consecutive chunks of 256; each chunk is added left to right starting from its
+ * first value, then the chunk sums left to right starting from the first.  A gene of up to 256 transcripts gets the plain sequential
+ * sum; a one-transcript gene gets that transcript's value. */
+int emsar_hip_set_gene_map(emsar_hip_ctx *ctx, int32_t n_genes, const int32_t *gene_of_tx /* n_tx, caller numbering, -1 = no gene */);
+int emsar_hip_gene_sums(emsar_hip_ctx *ctx, int32_t n_cols, const double *tx_values /* n_cols * n_tx */, double *gene_out /* n_cols * n_genes */);
+int emsar_hip_bootstrap_genes(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t first_replicate, int32_t n_replicates,
+                              double *fpkm_mean, double *fpkm_sd, double *tpm_sd, double *replicates /* or NULL */,
+                              double *gene_fpkm_mean, double *gene_fpkm_sd, double *gene_tpm_sd /* n_genes each */, emsar_boot_stats *stats);
 int emsar_hip_bootstrap_draw_host(uint64_t seed, int32_t replicate, int64_t n_rows, const int32_t *row_weight /* NULL = 1 */,
                                   int32_t *w_out);
 

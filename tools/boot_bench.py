@@ -1,11 +1,14 @@
 """Cost of the Poisson bootstrap (emsar_hip_bootstrap) on two workloads; prints one JSON object.
 
-    python tools/boot_bench.py [--reps 100] [--cfg3-scale 0.1] [--cfg3-reps 10] [--out FILE]
+    python tools/boot_bench.py [--reps 100] [--cfg3-scale 0.1] [--cfg3-reps 10] [--genes] [--out FILE]
 
   segment   bench.py's time_to_mle problem (same seeds): one solve, then B replicates in one call -- device time per stage (HIP events),
             wall time, ms per replicate against one solve, the batch size and the slowest set's passes
   cfg3      BASELINE config 3 at --cfg3-scale, collapsed to weighted segments on the device, B = --cfg3-reps: one giant component, so
             every replicate is a streaming solve of its own (deterministic mode, as emsar-hip runs it)
+  --genes  instead: emsar_hip_bootstrap against emsar_hip_bootstrap_genes on both workloads, the generator's families as genes, and on
+            the segment problem also a worst-case map with 90 % of the transcripts in one gene -- reduce_ms and total_ms of each, the
+            calls alternated (two rounds) so that the solves' own spread shows
 Kernel-level times come from a separate `rocprofv3 --kernel-trace --stats` run of this script."""
 import argparse
 import json
@@ -19,6 +22,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def family_sizes(n_tx):
+    """the family sizes segment_problem() drew (same seed), which family_matrix laid out as consecutive tid blocks"""
+    rng = np.random.default_rng(11)
+    sizes = np.minimum(rng.zipf(1.6, size=40000), 60)
+    sizes = sizes[np.cumsum(sizes) <= 100000]
+    assert int(sizes.sum()) == n_tx
+    return sizes
+
+
 def segment_problem():
     from emsar_amd import synth
     rng = np.random.default_rng(11)                       # bench.py time_to_mle, draw for draw
@@ -29,6 +41,35 @@ def segment_problem():
     theta_true = np.where(rng.random(n_tx) < 0.3, 0.0, rng.lognormal(0.0, 2.0, size=n_tx))
     R = rng.poisson(E * np.add.reduceat(theta_true[ci], rp[:-1].astype(np.int64))).astype(np.int32)
     return n_tx, rp, ci, R, E
+
+
+def worst_case_map(n_tx, fam_of, seed=1):
+    """90 % of the transcripts, drawn at random, in gene 0; the rest keep their family (numbered after it)"""
+    big = np.random.default_rng(seed).random(n_tx) < 0.9
+    g = (fam_of + 1).astype(np.int32)
+    g[big] = 0
+    used, g = np.unique(g, return_inverse=True)
+    return g.astype(np.int32), len(used)
+
+
+def run_genes(dev, B, solve_kw, maps, seed=1, rounds=2):
+    """bootstrap vs bootstrap_genes with each map of `maps` ({name: (gene_of_tx, n_genes)}), alternated"""
+    dev.solve(**solve_kw)
+    dev.bootstrap(min(B, 2), seed, **solve_kw)
+    for gm, ng in maps.values():                          # first calls: kernels loaded, draw map built
+        dev.set_gene_map(gm, ng)
+        dev.bootstrap_genes(min(B, 2), seed, **solve_kw)
+    out = {"replicates": B, "none": []}
+    for name, (gm, ng) in maps.items():
+        out[name] = {"n_genes": int(ng), "largest_gene": int(np.bincount(gm).max()), "runs": []}
+    for _ in range(rounds):
+        st = dev.bootstrap(B, seed, **solve_kw)[4]
+        out["none"].append({"reduce_ms": st.reduce_ms, "total_ms": st.total_ms, "batch": st.batch})
+        for name, (gm, ng) in maps.items():
+            dev.set_gene_map(gm, ng)
+            st = dev.bootstrap_genes(B, seed, **solve_kw)["stats"]
+            out[name]["runs"].append({"reduce_ms": st.reduce_ms, "total_ms": st.total_ms, "batch": st.batch})
+    return out
 
 
 def run(dev, B, solve_kw, seed=1):
@@ -52,6 +93,7 @@ def main():
     ap.add_argument("--cfg3-scale", type=float, default=0.1)
     ap.add_argument("--cfg3-reps", type=int, default=10)
     ap.add_argument("--skip-cfg3", action="store_true")
+    ap.add_argument("--genes", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
     from emsar_amd import EmsarHip, synth
@@ -60,7 +102,14 @@ def main():
         n_tx, rp, ci, R, E = segment_problem()
         dev.upload_structure(n_tx, rp, ci)
         dev.upload_sample(R, E, None)
-        out["segment"] = {"n_tx": int(n_tx), "segments": int(len(R)), **run(dev, a.reps, dict(max_iter=200000, tol=1e-10))}
+        seg_kw = dict(max_iter=200000, tol=1e-10)
+        if a.genes:
+            sizes = family_sizes(n_tx)
+            fam = np.repeat(np.arange(len(sizes)), sizes).astype(np.int32)
+            maps = {"families": (fam, int(fam.max()) + 1), "worst_90pct": worst_case_map(n_tx, fam)}
+            out["segment"] = {"n_tx": int(n_tx), "segments": int(len(R)), **run_genes(dev, a.reps, seg_kw, maps)}
+        else:
+            out["segment"] = {"n_tx": int(n_tx), "segments": int(len(R)), **run(dev, a.reps, seg_kw)}
         if not a.skip_cfg3:
             import bench
             cfg = dict(synth.CONFIGS["cfg3"])
@@ -71,8 +120,12 @@ def main():
             dev.upload_structure(s["n_tx"], crp, cci)
             dev.upload_sample(cw, None, s["den"])
             kw = dict(max_iter=200000, tol=1e-10, zero_cut=2.5e-7, abs_step=1e-13)
-            out["cfg3"] = {"scale": a.cfg3_scale, "reads": int(s["n_reads"]), "n_tx": int(s["n_tx"]), "segments": int(len(cw)),
-                           **run(dev, a.cfg3_reps, kw)}
+            info = {"scale": a.cfg3_scale, "reads": int(s["n_reads"]), "n_tx": int(s["n_tx"]), "segments": int(len(cw))}
+            if a.genes:
+                _, fam = synth.make_families(s["n_tx"], cfg["seed"])
+                out["cfg3"] = {**info, **run_genes(dev, a.cfg3_reps, kw, {"families": (fam, int(fam.max()) + 1)})}
+            else:
+                out["cfg3"] = {**info, **run(dev, a.cfg3_reps, kw)}
     txt = json.dumps(out, indent=1)
     print(txt)
     if a.out:
