@@ -1,4 +1,5 @@
-// boot_rng.hpp -- the counter-based Poisson draws of the bootstrap (emsar_hip_bootstrap), host and device alike.
+// boot_rng.hpp -- the counter-based draws of the bootstrap (emsar_hip_bootstrap: Poisson) and of the depth subsampling
+// (emsar_hip_subsample: binomial, at the end of this comment), host and device alike.
 //
 // Replicate b of seed s gives caller row c the weight w ~ Poisson(R_c).  Every draw is a pure function of (s, b, c, R_c):
 //   * generator: Philox4x64-10 (Salmon et al., SC'11), key = (s, b), counter = (c, j, 0, 0) with j = 0, 1, ... the 4-word
@@ -11,6 +12,13 @@
 // and compares with floating contraction off: host and device give the same bits.  PTRS calls log and sqrt; sqrt is correctly
 // rounded on both sides, log may differ by an ulp between the host libm and the device library, which can flip an acceptance
 // test that lands on its edge.
+//
+// Subsampling at fraction f gives row c the weight w ~ Binomial(R_c, f), a pure function of (s, b, c, R_c, f): the same generator and
+// key with counter (c, j, 1, bits of the double f), so the draws of a fraction do not depend on the other fractions of a call and are
+// independent of the bootstrap's under the same seed.  p = min(f, 1 - f), k ~ Binomial(R, p), w = k or R - k;
+//   * R p < 10: inversion from q^R (square and multiply), one uniform, *, /, +, - and compares only: host and device give the same bits;
+//   * R p >= 10: transformed rejection with squeeze (BTRS, Hoermann 1993, "The generation of binomial random variates"), two uniforms
+//     per trial, log-factorials from boot_loggam; log as for PTRS.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -46,13 +54,14 @@ __host__ __device__ inline void philox4x64_10(uint64_t &c0, uint64_t &c1, uint64
 
 // the uniforms of one draw, in order
 struct BootUniforms {
-    uint64_t k0, k1, row, j = 0;
+    uint64_t k0, k1, row, c2, c3, j = 0;     // counter (row, j, c2, c3): c2 = c3 = 0 the bootstrap, (1, bits of f) the subsampling
     uint64_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
     int i = 4;
-    __host__ __device__ BootUniforms(uint64_t seed, uint64_t rep, uint64_t r) : k0(seed), k1(rep), row(r) {}
+    __host__ __device__ BootUniforms(uint64_t seed, uint64_t rep, uint64_t r, uint64_t c2_ = 0, uint64_t c3_ = 0)
+        : k0(seed), k1(rep), row(r), c2(c2_), c3(c3_) {}
     __host__ __device__ double next() {
         if (i == 4) {
-            w0 = row; w1 = j++; w2 = 0; w3 = 0;
+            w0 = row; w1 = j++; w2 = c2; w3 = c3;
             philox4x64_10(w0, w1, w2, w3, k0, k1);
             i = 0;
         }
@@ -111,6 +120,47 @@ __host__ __device__ inline int32_t boot_poisson(uint64_t seed, uint64_t rep, uin
         if (kd < 0.0 || (us < 0.013 && V > us)) continue;
         if ((log(V) + log(invalpha) - log(a / (us * us) + b)) <= (-lam + kd * loglam - boot_loggam(kd + 1.0)))
             return kd >= 2147483647.0 ? 2147483647 : (int32_t)kd;
+    }
+}
+
+constexpr double kSubInversionMax = 10.0;  // R * min(f, 1 - f) below this: inversion; from it on: BTRS
+
+// w ~ Binomial(R, f) for caller row `row` of replicate `rep` of seed `seed` at fraction f in (0, 1]; R <= 0 gives 0, f >= 1 gives R.
+__host__ __device__ inline int32_t boot_binomial(uint64_t seed, uint64_t rep, uint64_t row, int32_t R, double f) {
+#pragma clang fp contract(off)
+    if (R <= 0) return 0;
+    if (f >= 1.0) return R;
+    BootUniforms U(seed, rep, row, 1, __builtin_bit_cast(uint64_t, f));
+    const bool flip = f > 0.5;
+    const double p = flip ? 1.0 - f : f, q = 1.0 - p, n = (double)R;
+    if (n * p < kSubInversionMax) {
+        double pr = 1.0, sq = q;                   // q^R
+        for (uint32_t e = (uint32_t)R; e; e >>= 1) { if (e & 1u) pr = pr * sq; sq = sq * sq; }
+        const double u = U.next(), s = p / q;
+        double F = pr;
+        int32_t k = 0;
+        while (u >= F && k < R) { k++; pr = pr * s * (double)(R - k + 1) / (double)k; F = F + pr; }
+        return flip ? R - k : k;
+    }
+    const double spq = sqrt(n * p * q);
+    const double b = 1.15 + 2.53 * spq;
+    const double a = -0.0873 + 0.0248 * b + 0.01 * p;
+    const double c = n * p + 0.5;
+    const double vr = 0.92 - 4.2 / b;
+    const double alpha = (2.83 + 5.1 / b) * spq;
+    const double lpq = log(p / q);
+    const double m = floor((n + 1.0) * p);
+    const double h = boot_loggam(m + 1.0) + boot_loggam(n - m + 1.0);
+    for (;;) {
+        const double Uc = U.next() - 0.5, V = U.next();
+        const double us = 0.5 - fabs(Uc);
+        const double kd = floor((2.0 * a / us + b) * Uc + c);
+        if (!(us >= 0.07 && V <= vr)) {
+            if (kd < 0.0 || kd > n) continue;
+            if (!(log(V * alpha / (a / (us * us) + b)) <= h - boot_loggam(kd + 1.0) - boot_loggam(n - kd + 1.0) + (kd - m) * lpq)) continue;
+        }
+        const int32_t k = (int32_t)kd;
+        return flip ? R - k : k;
     }
 }
 

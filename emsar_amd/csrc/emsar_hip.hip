@@ -16,6 +16,7 @@
 //                         k_normalise, k_adj_euma, small reductions
 //   kernels_sets.hpp      k_solve_sets                           one workgroup solves one connected set out of LDS
 //   kernels_boot.hpp      k_boot_draw, k_boot_accum, ...         the Poisson bootstrap (draws: boot_rng.hpp; sets: k_solve_sets_boot)
+//                         k_sub_draw, k_sub_scale                the depth subsampling: binomial draws, every replicate to its own depth
 //   kernels_genes.hpp     k_gene_sums, k_gene_finish             per-gene sums in a fixed order (gene_sums, the bootstrap's gene sd)
 //   collapse.hip          read-level rows -> weighted segments (own translation unit)
 #include <hip/hip_runtime.h>
@@ -1189,11 +1190,25 @@ static int launch_gene_sums(emsar_hip_ctx *ctx, const double *x, int64_t ncol, d
     return EMSAR_HIP_OK;
 }
 
-// gene_* (all null = no gene outputs): per gene the bootstrap mean and sd of its FPKM sum and the sd of its TPM sum
-static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_t seed, int32_t first, int32_t n_rep, double *fpkm_mean,
-                          double *fpkm_sd, double *tpm_sd, double *replicates, double *gene_mean, double *gene_sd, double *gene_tpm_sd,
-                          emsar_boot_stats *stats) {
-    const bool genes = gene_mean != nullptr;
+// What a call draws and where its results go.  fractions null: the Poisson bootstrap, one round.  Else the depth subsampling: one round
+// per fraction f_k with w_c ~ Binomial(R_c, f_k), every replicate scaled to its own depth, the outputs of round k at [k][...].
+// Outputs that are null are not returned; gene_mean non-null asks for the gene statistics (all null = none).
+struct BootPlan {
+    const double *fractions = nullptr;
+    int32_t n_fractions = 1;
+    double *fpkm_mean = nullptr, *fpkm_sd = nullptr, *tpm_mean = nullptr, *tpm_sd = nullptr, *replicates = nullptr;
+    double *gene_mean = nullptr, *gene_sd = nullptr, *gene_tpm_mean = nullptr, *gene_tpm_sd = nullptr;
+    double *depth_mean = nullptr;        // subsampling: mean over the replicates of N_b = sum_c w_c, per fraction
+};
+struct BootTimes {
+    int32_t batch = 0, unconverged = 0, passes_max = 0;
+    int64_t draws = 0;
+    double draw_ms = 0, sets_ms = 0, stream_ms = 0, reduce_ms = 0, total_ms = 0;
+};
+
+static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_t seed, int32_t first, int32_t n_rep, const BootPlan &plan,
+                          BootTimes *stats) {
+    const bool genes = plan.gene_mean != nullptr, binomial = plan.fractions != nullptr;
     const auto tw0 = std::chrono::steady_clock::now();
     emsar_em_params p = solve_params(pp);
     if (!(p.count_floor >= 0.0) || (p.set_mode != 0 && p.set_mode != 1)) return EMSAR_HIP_ERR_ARG;
@@ -1235,13 +1250,21 @@ static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_
         HIPCHK(guard.alloc((void **)&d_gsum, (size_t)(batch * ng) * 8));
         if (n_gchunk) HIPCHK(guard.alloc((void **)&d_gpart, (size_t)(batch * n_gchunk) * 8));
         HIPCHK(guard.alloc((void **)&d_gacc4, (size_t)4 * ng * 8));
-        HIPCHK(hipMemsetAsync(d_gacc4, 0, (size_t)4 * ng * 8, ctx->stream));
+    }
+    // subsampling: the drawn total N_b of every replicate of the batch, and the total N_R of the rows that are drawn
+    long long *d_ndrawn = nullptr;
+    std::vector<long long> h_ndrawn(binomial ? (size_t)batch : 0);
+    double n_full = 0.0;
+    if (binomial) {
+        HIPCHK(guard.alloc((void **)&d_ndrawn, (size_t)batch * 8));
+        int64_t tot = 0;
+        for (int64_t r = 0; r < n_rows; r++) tot += ctx->h_wgt[(size_t)r];
+        n_full = (double)tot;
     }
     if (need_stream) HIPCHK(guard.alloc((void **)&d_wb, (size_t)(batch * n_rows) * 4));
     if (n_sets) HIPCHK(guard.alloc((void **)&d_bstat, (size_t)(batch * n_sets) * sizeof(SetStat)));
     HIPCHK(hipMalloc(&guard.d_th0, std::max<size_t>((size_t)n, 1) * 8));
     HIPCHK(hipMemcpyAsync(guard.d_th0, ctx->d_th[0], (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(hipMemsetAsync(d_acc4, 0, (size_t)4 * n * 8, ctx->stream));
     hipEvent_t e[2] = {nullptr, nullptr};
     struct EvFree { hipEvent_t *e; ~EvFree() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evfree{e};
     HIPCHK(hipEventCreate(&e[0])); HIPCHK(hipEventCreate(&e[1]));
@@ -1259,117 +1282,150 @@ static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_
     std::vector<double> h_th((size_t)std::max(n, 1));
     std::vector<SetStat> h_bstat((size_t)(batch * n_sets));
     const unsigned gn = (unsigned)grid_for(n, 256);
-    for (int64_t done = 0; done < n_rep; ) {
-        const int64_t nb = std::min<int64_t>(batch, n_rep - done);
-        std::vector<char> unconv((size_t)nb, 0);      // replicates of the batch with a part that hit max_iter
-        // ---- draws ----
-        HIPCHK(hipEventRecord(e[0], ctx->stream));
-        if (use_sets) HIPCHK(hipMemsetAsync(d_slots, 0, (size_t)(nb * slot_stride) * 8, ctx->stream));
-        if (n_rows > 0)
-            hipLaunchKernelGGL(k_boot_draw, dim3((unsigned)((n_rows + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, n_rows, seed,
-                               (int64_t)first + done, ctx->d_boot_R, use_sets ? ctx->d_boot_slot : nullptr, need_stream ? d_wb : nullptr, d_slots,
-                               slot_stride);
-        HIPCHK(hipGetLastError());
-        if ((rc = lap(draw_ms))) return rc;
-        // ---- closed form + resident sets, all replicates of the batch in one launch per class ----
-        if (use_sets) {
+    for (int32_t fk = 0; fk < plan.n_fractions; fk++) {
+        const double frac = binomial ? plan.fractions[fk] : 1.0;
+        double *const replicates = plan.replicates ? plan.replicates + (int64_t)fk * n_rep * n : nullptr;
+        long long depth_sum = 0;
+        HIPCHK(hipMemsetAsync(d_acc4, 0, (size_t)4 * n * 8, ctx->stream));
+        if (genes) HIPCHK(hipMemsetAsync(d_gacc4, 0, (size_t)4 * ng * 8, ctx->stream));
+        for (int64_t done = 0; done < n_rep; ) {
+            const int64_t nb = std::min<int64_t>(batch, n_rep - done);
+            std::vector<char> unconv((size_t)nb, 0);      // replicates of the batch with a part that hit max_iter
+            // ---- draws ----
             HIPCHK(hipEventRecord(e[0], ctx->stream));
-            if (n_gu > 0)
-                hipLaunchKernelGGL(k_boot_gather_u, dim3((unsigned)((n_gu + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, n_gu, ctx->d_g_tid,
-                                   d_slots, slot_stride, n_rw, d_gu);
-            hipLaunchKernelGGL(k_boot_closed, dim3(gn, (unsigned)nb), dim3(256), 0, ctx->stream, n, ctx->d_kind, d_slots, slot_stride, n_rw,
-                               ctx->d_den, d_thb);
-            const size_t off[3] = {0, S.desc[0].size(), S.desc[0].size() + S.desc[1].size()};
-            HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
-            for (int i = 0; i < 2; i++) HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0));
-#define LAUNCH_SB(C, TH, ST)                                                                                                           \
-            if (!S.desc[C].empty())                                                                                                    \
-                hipLaunchKernelGGL(k_solve_sets_boot<TH>, dim3((unsigned)S.desc[C].size(), (unsigned)nb), dim3(TH), S.max_lds[C], ST,   \
-                                   ctx->d_sdesc[C], ctx->d_g_tid, d_gu, d_slots, ctx->d_srp, ctx->d_sent, ctx->d_scp, ctx->d_scrow,       \
-                                   ctx->d_den, d_thb, d_bstat + off[C], P, n_gu, slot_stride, (int64_t)n, n_sets);
-            LAUNCH_SB(2, 512, ctx->side[1])
-            LAUNCH_SB(1, 256, ctx->side[0])
-            LAUNCH_SB(0, 64, ctx->stream)
-#undef LAUNCH_SB
-            for (int i = 0; i < 2; i++) {
-                HIPCHK(hipEventRecord(ctx->ev_join[i], ctx->side[i]));
-                HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
-            }
+            if (use_sets) HIPCHK(hipMemsetAsync(d_slots, 0, (size_t)(nb * slot_stride) * 8, ctx->stream));
+            if (binomial) HIPCHK(hipMemsetAsync(d_ndrawn, 0, (size_t)nb * 8, ctx->stream));
+            if (n_rows > 0 && !binomial)
+                hipLaunchKernelGGL(k_boot_draw, dim3((unsigned)((n_rows + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, n_rows, seed,
+                                   (int64_t)first + done, ctx->d_boot_R, use_sets ? ctx->d_boot_slot : nullptr, need_stream ? d_wb : nullptr, d_slots,
+                                   slot_stride);
+            if (n_rows > 0 && binomial)
+                hipLaunchKernelGGL(k_sub_draw, dim3((unsigned)((n_rows + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, n_rows, seed,
+                                   (int64_t)first + done, frac, ctx->d_boot_R, use_sets ? ctx->d_boot_slot : nullptr, need_stream ? d_wb : nullptr,
+                                   d_slots, slot_stride, d_ndrawn);
             HIPCHK(hipGetLastError());
-            if (n_sets) HIPCHK(hipMemcpyAsync(h_bstat.data(), d_bstat, (size_t)(nb * n_sets) * sizeof(SetStat), hipMemcpyDeviceToHost, ctx->stream));
-            if ((rc = lap(sets_ms))) return rc;
-            for (int64_t i = 0; i < nb * n_sets; i++) {
-                const SetStat &q = h_bstat[(size_t)i];
-                if (!std::isfinite(q.delta)) { ctx->err = "non-finite theta in a connected set of a bootstrap replicate"; return EMSAR_HIP_ERR_NUMERIC; }
-                passes_max = std::max(passes_max, q.passes);
-                if (!q.converged) unconv[(size_t)(i / n_sets)] = 1;
+            if ((rc = lap(draw_ms))) return rc;
+            // ---- closed form + resident sets, all replicates of the batch in one launch per class ----
+            if (use_sets) {
+                HIPCHK(hipEventRecord(e[0], ctx->stream));
+                if (n_gu > 0)
+                    hipLaunchKernelGGL(k_boot_gather_u, dim3((unsigned)((n_gu + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, n_gu, ctx->d_g_tid,
+                                       d_slots, slot_stride, n_rw, d_gu);
+                hipLaunchKernelGGL(k_boot_closed, dim3(gn, (unsigned)nb), dim3(256), 0, ctx->stream, n, ctx->d_kind, d_slots, slot_stride, n_rw,
+                                   ctx->d_den, d_thb);
+                const size_t off[3] = {0, S.desc[0].size(), S.desc[0].size() + S.desc[1].size()};
+                HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
+                for (int i = 0; i < 2; i++) HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0));
+#define LAUNCH_SB(C, TH, ST)                                                                                                           \
+                if (!S.desc[C].empty())                                                                                                    \
+                    hipLaunchKernelGGL(k_solve_sets_boot<TH>, dim3((unsigned)S.desc[C].size(), (unsigned)nb), dim3(TH), S.max_lds[C], ST,   \
+                                       ctx->d_sdesc[C], ctx->d_g_tid, d_gu, d_slots, ctx->d_srp, ctx->d_sent, ctx->d_scp, ctx->d_scrow,       \
+                                       ctx->d_den, d_thb, d_bstat + off[C], P, n_gu, slot_stride, (int64_t)n, n_sets);
+                LAUNCH_SB(2, 512, ctx->side[1])
+                LAUNCH_SB(1, 256, ctx->side[0])
+                LAUNCH_SB(0, 64, ctx->stream)
+#undef LAUNCH_SB
+                for (int i = 0; i < 2; i++) {
+                    HIPCHK(hipEventRecord(ctx->ev_join[i], ctx->side[i]));
+                    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
+                }
+                HIPCHK(hipGetLastError());
+                if (n_sets) HIPCHK(hipMemcpyAsync(h_bstat.data(), d_bstat, (size_t)(nb * n_sets) * sizeof(SetStat), hipMemcpyDeviceToHost, ctx->stream));
+                if ((rc = lap(sets_ms))) return rc;
+                for (int64_t i = 0; i < nb * n_sets; i++) {
+                    const SetStat &q = h_bstat[(size_t)i];
+                    if (!std::isfinite(q.delta)) { ctx->err = binomial ? "non-finite theta in a connected set of a subsampling replicate" : "non-finite theta in a connected set of a bootstrap replicate"; return EMSAR_HIP_ERR_NUMERIC; }
+                    passes_max = std::max(passes_max, q.passes);
+                    if (!q.converged) unconv[(size_t)(i / n_sets)] = 1;
+                }
             }
-        }
-        // ---- the rest: one streaming solve per replicate with its weights swapped into the layout ----
-        if (need_stream) {
-            HIPCHK(hipMemcpyAsync(h_wb.data(), d_wb, (size_t)(nb * n_rows) * 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            emsar_em_params ps = p;
-            ps.set_mode = 1;
-            for (int64_t y = 0; y < nb; y++) {
-                guard.swapped = true;
-                if ((rc = boot_stream_weights(ctx, h_wb.data() + y * n_rows))) return rc;
-                emsar_em_stats st;
-                rc = solve_impl(ctx, &ps, h_th.data(), &st);
-                ctx->count_floor = 0.0; ctx->zero_cut = 0.0; ctx->delta_mask = nullptr;
-                if (rc) return rc;
-                stream_ms += st.kernel_ms;
-                if (!st.converged) unconv[(size_t)y] = 1;
-                hipLaunchKernelGGL(k_boot_take_streamed, dim3(gn), dim3(256), 0, ctx->stream, n, use_sets ? ctx->d_kind : nullptr, ctx->d_th[0],
-                                   d_thb + y * n);
+            // ---- the rest: one streaming solve per replicate with its weights swapped into the layout ----
+            if (need_stream) {
+                HIPCHK(hipMemcpyAsync(h_wb.data(), d_wb, (size_t)(nb * n_rows) * 4, hipMemcpyDeviceToHost, ctx->stream));
+                HIPCHK(hipStreamSynchronize(ctx->stream));
+                emsar_em_params ps = p;
+                ps.set_mode = 1;
+                for (int64_t y = 0; y < nb; y++) {
+                    guard.swapped = true;
+                    if ((rc = boot_stream_weights(ctx, h_wb.data() + y * n_rows))) return rc;
+                    emsar_em_stats st;
+                    rc = solve_impl(ctx, &ps, h_th.data(), &st);
+                    ctx->count_floor = 0.0; ctx->zero_cut = 0.0; ctx->delta_mask = nullptr;
+                    if (rc) return rc;
+                    stream_ms += st.kernel_ms;
+                    if (!st.converged) unconv[(size_t)y] = 1;
+                    hipLaunchKernelGGL(k_boot_take_streamed, dim3(gn), dim3(256), 0, ctx->stream, n, use_sets ? ctx->d_kind : nullptr, ctx->d_th[0],
+                                       d_thb + y * n);
+                    HIPCHK(hipGetLastError());
+                }
+            }
+            // ---- reduction over the replicates, in replicate order ----
+            HIPCHK(hipEventRecord(e[0], ctx->stream));
+            if (binomial)     // every replicate to its own depth: theta_b * N_R / N_b
+                hipLaunchKernelGGL(k_sub_scale, dim3(gn, (unsigned)nb), dim3(256), 0, ctx->stream, n, n_full, d_ndrawn, d_thb);
+            hipLaunchKernelGGL(k_boot_sums, dim3((unsigned)nb), dim3(1024), 0, ctx->stream, n, d_thb, d_sums);
+            hipLaunchKernelGGL(k_boot_accum, dim3(gn), dim3(256), 0, ctx->stream, n, (int)nb, done, d_thb, d_sums, d_acc4);
+            HIPCHK(hipGetLastError());
+            if (genes) {   // the replicates' gene sums, then the same Welford step on them (gene TPM_b = G_b * 1e6 / S_b)
+                if ((rc = launch_gene_sums(ctx, d_thb, nb, d_gsum, d_gpart))) return rc;
+                hipLaunchKernelGGL(k_boot_accum, dim3((unsigned)grid_for(ng, 256)), dim3(256), 0, ctx->stream, (int)ng, (int)nb, done, d_gsum, d_sums, d_gacc4);
                 HIPCHK(hipGetLastError());
             }
+            // (after the launches: a copy into pageable memory makes the host wait for the stream)
+            if (binomial) HIPCHK(hipMemcpyAsync(h_ndrawn.data(), d_ndrawn, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream));
+            if ((rc = lap(reduce_ms))) return rc;
+            if (binomial) for (int64_t y = 0; y < nb; y++) depth_sum += h_ndrawn[(size_t)y];
+            if (replicates) {
+                HIPCHK(hipMemcpy(replicates + done * n, d_thb, (size_t)(nb * n) * 8, hipMemcpyDeviceToHost));
+                try { for (int64_t y = 0; y < nb; y++) from_lib(ctx, replicates + (done + y) * n); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+            }
+            for (char c : unconv) unconverged += c;
+            done += nb;
         }
-        // ---- reduction over the replicates, in replicate order ----
-        HIPCHK(hipEventRecord(e[0], ctx->stream));
-        hipLaunchKernelGGL(k_boot_sums, dim3((unsigned)nb), dim3(1024), 0, ctx->stream, n, d_thb, d_sums);
-        hipLaunchKernelGGL(k_boot_accum, dim3(gn), dim3(256), 0, ctx->stream, n, (int)nb, done, d_thb, d_sums, d_acc4);
-        HIPCHK(hipGetLastError());
-        if (genes) {   // the replicates' gene sums, then the same Welford step on them (gene TPM_b = G_b * 1e6 / S_b)
-            if ((rc = launch_gene_sums(ctx, d_thb, nb, d_gsum, d_gpart))) return rc;
-            hipLaunchKernelGGL(k_boot_accum, dim3((unsigned)grid_for(ng, 256)), dim3(256), 0, ctx->stream, (int)ng, (int)nb, done, d_gsum, d_sums, d_gacc4);
-            HIPCHK(hipGetLastError());
-        }
-        if ((rc = lap(reduce_ms))) return rc;
-        if (replicates) {
-            HIPCHK(hipMemcpy(replicates + done * n, d_thb, (size_t)(nb * n) * 8, hipMemcpyDeviceToHost));
-            try { for (int64_t y = 0; y < nb; y++) from_lib(ctx, replicates + (done + y) * n); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-        }
-        for (char c : unconv) unconverged += c;
-        done += nb;
-    }
-    std::vector<double> acc((size_t)4 * n);
-    HIPCHK(hipMemcpyAsync(acc.data(), d_acc4, acc.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int t = 0; t < n; t++) {
-        if (!std::isfinite(acc[(size_t)t]) || !std::isfinite(acc[(size_t)n + t])) { ctx->err = "non-finite theta in a bootstrap replicate"; return EMSAR_HIP_ERR_NUMERIC; }
-        fpkm_mean[t] = acc[(size_t)t];
-        fpkm_sd[t] = n_rep > 1 ? std::sqrt(acc[(size_t)n + t] / (double)(n_rep - 1)) : 0.0;
-        tpm_sd[t] = n_rep > 1 ? std::sqrt(acc[(size_t)3 * n + t] / (double)(n_rep - 1)) : 0.0;
-    }
-    try { from_lib(ctx, fpkm_mean); from_lib(ctx, fpkm_sd); from_lib(ctx, tpm_sd); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    if (genes) {   // gene order is the caller's: no renumbering to undo
-        std::vector<double> gacc((size_t)4 * ng);
-        HIPCHK(hipMemcpyAsync(gacc.data(), d_gacc4, gacc.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        std::vector<double> acc((size_t)4 * n);
+        HIPCHK(hipMemcpyAsync(acc.data(), d_acc4, acc.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        for (int64_t g = 0; g < ng; g++) {
-            if (!std::isfinite(gacc[(size_t)g]) || !std::isfinite(gacc[(size_t)(ng + g)])) { ctx->err = "non-finite gene sum in a bootstrap replicate"; return EMSAR_HIP_ERR_NUMERIC; }
-            gene_mean[g] = gacc[(size_t)g];
-            gene_sd[g] = n_rep > 1 ? std::sqrt(gacc[(size_t)(ng + g)] / (double)(n_rep - 1)) : 0.0;
-            gene_tpm_sd[g] = n_rep > 1 ? std::sqrt(gacc[(size_t)(3 * ng + g)] / (double)(n_rep - 1)) : 0.0;
+        for (int t = 0; t < n; t++)
+            if (!std::isfinite(acc[(size_t)t]) || !std::isfinite(acc[(size_t)n + t])) {
+                ctx->err = binomial ? "non-finite theta in a subsampling replicate" : "non-finite theta in a bootstrap replicate";
+                return EMSAR_HIP_ERR_NUMERIC;
+            }
+        // row r of the accumulators as it is (mean) or as the sample sd, into the caller's vector of this round, caller numbering
+        auto put = [&](double *out, int r, bool sd) {
+            if (!out) return;
+            out += (int64_t)fk * n;
+            for (int t = 0; t < n; t++) {
+                const double v = acc[(size_t)r * n + t];
+                out[t] = !sd ? v : n_rep > 1 ? std::sqrt(v / (double)(n_rep - 1)) : 0.0;
+            }
+            from_lib(ctx, out);
+        };
+        try { put(plan.fpkm_mean, 0, false); put(plan.fpkm_sd, 1, true); put(plan.tpm_mean, 2, false); put(plan.tpm_sd, 3, true); }
+        catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+        if (genes) {   // gene order is the caller's: no renumbering to undo
+            std::vector<double> gacc((size_t)4 * ng);
+            HIPCHK(hipMemcpyAsync(gacc.data(), d_gacc4, gacc.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            for (int64_t g = 0; g < ng; g++) {
+                if (!std::isfinite(gacc[(size_t)g]) || !std::isfinite(gacc[(size_t)(ng + g)])) {
+                    ctx->err = binomial ? "non-finite gene sum in a subsampling replicate" : "non-finite gene sum in a bootstrap replicate";
+                    return EMSAR_HIP_ERR_NUMERIC;
+                }
+                const int64_t o = (int64_t)fk * ng + g;
+                plan.gene_mean[o] = gacc[(size_t)g];
+                if (plan.gene_sd) plan.gene_sd[o] = n_rep > 1 ? std::sqrt(gacc[(size_t)(ng + g)] / (double)(n_rep - 1)) : 0.0;
+                if (plan.gene_tpm_mean) plan.gene_tpm_mean[o] = gacc[(size_t)(2 * ng + g)];
+                if (plan.gene_tpm_sd) plan.gene_tpm_sd[o] = n_rep > 1 ? std::sqrt(gacc[(size_t)(3 * ng + g)] / (double)(n_rep - 1)) : 0.0;
+            }
         }
+        if (plan.depth_mean) plan.depth_mean[fk] = (double)depth_sum / (double)n_rep;
     }
     if (stats) {
-        memset(stats, 0, sizeof(*stats));
-        stats->n_replicates = n_rep; stats->batch = (int32_t)batch; stats->replicates_unconverged = unconverged; stats->set_passes_max = passes_max;
+        *stats = BootTimes();
+        stats->batch = (int32_t)batch; stats->unconverged = unconverged; stats->passes_max = passes_max;
         int64_t pos = 0;
         for (int64_t r = 0; r < n_rows; r++) pos += ctx->h_wgt[(size_t)r] > 0;
-        stats->draws = pos * n_rep;
+        stats->draws = pos * n_rep * plan.n_fractions;
         stats->draw_ms = draw_ms; stats->sets_ms = sets_ms; stats->stream_ms = stream_ms; stats->reduce_ms = reduce_ms;
     }
     // the sample's own weights back before the call returns (the guard does it too, but a failure there must be reported)
@@ -1387,6 +1443,14 @@ static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_
     return EMSAR_HIP_OK;
 }
 
+static void boot_stats_out(emsar_boot_stats *out, const BootTimes &t, int32_t n_rep) {
+    if (!out) return;
+    memset(out, 0, sizeof(*out));
+    out->n_replicates = n_rep; out->batch = t.batch; out->replicates_unconverged = t.unconverged; out->set_passes_max = t.passes_max;
+    out->draws = t.draws;
+    out->draw_ms = t.draw_ms; out->sets_ms = t.sets_ms; out->stream_ms = t.stream_ms; out->reduce_ms = t.reduce_ms; out->total_ms = t.total_ms;
+}
+
 int emsar_hip_bootstrap(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t first_replicate, int32_t n_replicates,
                         double *fpkm_mean, double *fpkm_sd, double *tpm_sd, double *replicates, emsar_boot_stats *stats) {
     if (!ctx) return EMSAR_HIP_ERR_ARG;
@@ -1395,7 +1459,12 @@ int emsar_hip_bootstrap(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t s
         (int64_t)first_replicate + (int64_t)n_replicates > (int64_t)INT32_MAX + 1)
         return EMSAR_HIP_ERR_ARG;
     try {
-        return bootstrap_impl(ctx, p, seed, first_replicate, n_replicates, fpkm_mean, fpkm_sd, tpm_sd, replicates, nullptr, nullptr, nullptr, stats);
+        BootPlan plan;
+        plan.fpkm_mean = fpkm_mean; plan.fpkm_sd = fpkm_sd; plan.tpm_sd = tpm_sd; plan.replicates = replicates;
+        BootTimes t;
+        const int rc = bootstrap_impl(ctx, p, seed, first_replicate, n_replicates, plan, &t);
+        if (rc == EMSAR_HIP_OK) boot_stats_out(stats, t, n_replicates);
+        return rc;
     } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
 }
 
@@ -1408,8 +1477,13 @@ int emsar_hip_bootstrap_genes(emsar_hip_ctx *ctx, const emsar_em_params *p, uint
         (int64_t)first_replicate + (int64_t)n_replicates > (int64_t)INT32_MAX + 1)
         return EMSAR_HIP_ERR_ARG;
     try {
-        return bootstrap_impl(ctx, p, seed, first_replicate, n_replicates, fpkm_mean, fpkm_sd, tpm_sd, replicates, gene_fpkm_mean, gene_fpkm_sd,
-                              gene_tpm_sd, stats);
+        BootPlan plan;
+        plan.fpkm_mean = fpkm_mean; plan.fpkm_sd = fpkm_sd; plan.tpm_sd = tpm_sd; plan.replicates = replicates;
+        plan.gene_mean = gene_fpkm_mean; plan.gene_sd = gene_fpkm_sd; plan.gene_tpm_sd = gene_tpm_sd;
+        BootTimes t;
+        const int rc = bootstrap_impl(ctx, p, seed, first_replicate, n_replicates, plan, &t);
+        if (rc == EMSAR_HIP_OK) boot_stats_out(stats, t, n_replicates);
+        return rc;
     } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
 }
 
@@ -1518,6 +1592,69 @@ int emsar_hip_bootstrap_draw_host(uint64_t seed, int32_t replicate, int64_t n_ro
     if (replicate < 0 || n_rows < 0 || (n_rows > 0 && !w_out)) return EMSAR_HIP_ERR_ARG;
     if (row_weight) for (int64_t r = 0; r < n_rows; r++) if (row_weight[r] < 0) return EMSAR_HIP_ERR_ARG;
     for (int64_t r = 0; r < n_rows; r++) w_out[r] = emsar::boot_poisson(seed, (uint64_t)replicate, (uint64_t)r, row_weight ? row_weight[r] : 1);
+    return EMSAR_HIP_OK;
+}
+
+// ---- depth subsampling ----------------------------------------------------------------------------------------------------------
+static bool sub_fraction_ok(double f) { return std::isfinite(f) && f > 0.0 && f <= 1.0; }
+
+int emsar_hip_subsample(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t n_fractions, const double *fractions,
+                        int32_t n_replicates, double *fpkm_mean, double *fpkm_sd, double *tpm_mean, double *tpm_sd, double *depth_mean,
+                        double *replicates, double *gene_fpkm_mean, double *gene_fpkm_sd, double *gene_tpm_mean, emsar_subsample_stats *stats) {
+    if (!ctx) return EMSAR_HIP_ERR_ARG;
+    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
+    if (n_fractions < 1 || !fractions || n_replicates < 1 || !fpkm_mean || !fpkm_sd || !tpm_mean || !tpm_sd || !depth_mean) return EMSAR_HIP_ERR_ARG;
+    for (int32_t k = 0; k < n_fractions; k++) if (!sub_fraction_ok(fractions[k])) return EMSAR_HIP_ERR_ARG;
+    const int n_gene_out = (gene_fpkm_mean != nullptr) + (gene_fpkm_sd != nullptr) + (gene_tpm_mean != nullptr);
+    if (n_gene_out != 0 && n_gene_out != 3) return EMSAR_HIP_ERR_ARG;
+    if (n_gene_out && !ctx->have_genes) return EMSAR_HIP_ERR_STATE;
+    try {
+        BootPlan plan;
+        plan.fractions = fractions; plan.n_fractions = n_fractions;
+        plan.fpkm_mean = fpkm_mean; plan.fpkm_sd = fpkm_sd; plan.tpm_mean = tpm_mean; plan.tpm_sd = tpm_sd; plan.replicates = replicates;
+        plan.gene_mean = gene_fpkm_mean; plan.gene_sd = gene_fpkm_sd; plan.gene_tpm_mean = gene_tpm_mean;
+        plan.depth_mean = depth_mean;
+        BootTimes t;
+        const int rc = bootstrap_impl(ctx, p, seed, 0, n_replicates, plan, &t);
+        if (rc == EMSAR_HIP_OK && stats) {
+            memset(stats, 0, sizeof(*stats));
+            stats->n_fractions = n_fractions; stats->n_replicates = n_replicates; stats->batch = t.batch; stats->replicates_unconverged = t.unconverged;
+            stats->draws = t.draws;
+            stats->draw_ms = t.draw_ms; stats->sets_ms = t.sets_ms; stats->stream_ms = t.stream_ms; stats->reduce_ms = t.reduce_ms;
+            stats->total_ms = t.total_ms;
+        }
+        return rc;
+    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+}
+
+int emsar_hip_subsample_weights(emsar_hip_ctx *ctx, uint64_t seed, int32_t replicate, double fraction, int32_t *w_out) {
+    if (!ctx || !w_out || replicate < 0 || !sub_fraction_ok(fraction)) return EMSAR_HIP_ERR_ARG;
+    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
+    HIPCHK(hipSetDevice(ctx->device));
+    int rc;
+    try { if ((rc = boot_prepare(ctx, false))) return rc; } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+    if (ctx->n_rows == 0) return EMSAR_HIP_OK;
+    int32_t *d_w = nullptr;
+    HIPCHK(hipMalloc(&d_w, ((size_t)ctx->n_rows + 1) / 2 * 8 + 8));
+    long long *d_tot = (long long *)(d_w + (ctx->n_rows + 1) / 2 * 2);      // the draw kernel's total, 8-byte aligned behind the weights
+    hipError_t e = hipMemsetAsync(d_tot, 0, 8, ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_sub_draw, dim3((unsigned)((ctx->n_rows + 255) / 256), 1), dim3(256), 0, ctx->stream, ctx->n_rows, seed, (int64_t)replicate,
+                           fraction, ctx->d_boot_R, (const int64_t *)nullptr, d_w, (double *)nullptr, (int64_t)0, d_tot);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(w_out, d_w, (size_t)ctx->n_rows * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    dfree(d_w);
+    HIPCHK(e);
+    return EMSAR_HIP_OK;
+}
+
+int emsar_hip_subsample_draw_host(uint64_t seed, int32_t replicate, double fraction, int64_t n_rows, const int32_t *row_weight, int32_t *w_out) {
+    if (replicate < 0 || n_rows < 0 || (n_rows > 0 && !w_out) || !sub_fraction_ok(fraction)) return EMSAR_HIP_ERR_ARG;
+    if (row_weight) for (int64_t r = 0; r < n_rows; r++) if (row_weight[r] < 0) return EMSAR_HIP_ERR_ARG;
+    for (int64_t r = 0; r < n_rows; r++)
+        w_out[r] = emsar::boot_binomial(seed, (uint64_t)replicate, (uint64_t)r, row_weight ? row_weight[r] : 1, fraction);
     return EMSAR_HIP_OK;
 }
 

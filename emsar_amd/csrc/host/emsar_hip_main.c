@@ -21,6 +21,10 @@
  * sums of FPKM, iReadcount and TPM (emsar_hip_gene_sums; the map is read once, genes.c), which merge_gTPM.pl / merge_gReadcount.pl
  * read as they are; with --bootstrap also <prefix>.<i>.gbootstrap, the genes' bootstrap mean and sd from the same replicates
  * (emsar_hip_bootstrap_genes).  The other files are the same bytes with and without it.
+ * --subsample f1,f2,.. answers "was the sample sequenced deep enough": <prefix>.<i>.saturation holds, per transcript and fraction,
+ * the mean and sd of FPKM (at the thinned depth) and TPM over --subsample-reps replicates in which every read is kept with
+ * probability f (emsar_hip_subsample; seed --subsample-seed + i), with --g2t also <prefix>.<i>.gsaturation per gene.  The other
+ * files are the same bytes with and without it.
  *
  * -M: samples are independent (emsar_main.c:380-488 resets every count per file), so sample i runs on GPU
  * i mod G with one host thread per GPU; no collective.  The only cross-sample state of the reference, EUMAcut
@@ -49,6 +53,7 @@ typedef struct {
     const char *stats_json;
     const char *rsh_cache;      /* NULL = off, "" = <rsh>.bin, else the path */
     int boot_n; uint64_t boot_seed;   /* --bootstrap B (0 = off), --bootstrap-seed: sample i uses seed + i */
+    int sub_nf, sub_reps; double sub_f[64]; uint64_t sub_seed;   /* --subsample f1,.. (0 = off), --subsample-reps, --subsample-seed: sample i uses seed + i */
     const char *g2t;                  /* --g2t FILE (NULL = off) */
     const emsar_genes *genes;         /* its gene map, read once by main() and shared read-only by the workers */
 } config;
@@ -61,6 +66,7 @@ typedef struct {
     int *status;          /* per sample */
     emsar_em_stats *stats; /* per sample */
     emsar_boot_stats *bstats; /* per sample (--bootstrap) */
+    emsar_subsample_stats *sstats; /* per sample (--subsample) */
     double *parse_s;
     double *model_s, *host_s;   /* per sample: model preparation, and all host work of run_sample outside the library calls */
     int *go;              /* start gate: the workers wait until main() knows how many of them exist */
@@ -235,6 +241,31 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         free(bm); free(bs); free(bt); free(gb);
         if (rc) goto done;
     }
+    /* ---- depth subsampling (--subsample f1,f2,..): its own files ---- */
+    if (cfg->sub_nf > 0) {
+        const size_t K = (size_t)cfg->sub_nf;
+        const uint64_t seed = cfg->sub_seed + (uint64_t)i;
+        double *sv = (double *)malloc((T > 0 ? T : 1) * 8 * 4 * K), *gv = G ? (double *)malloc(NG * 8 * 3 * K) : NULL;
+        double depth[64];
+        if (!sv || (G && !gv)) rc = EMSAR_HOST_ERR_OOM;
+        else if ((rc = emsar_hip_subsample(ctx, &p, seed, cfg->sub_nf, cfg->sub_f, cfg->sub_reps, sv, sv + K * T, sv + 2 * K * T, sv + 3 * K * T, depth, NULL,
+                                           gv, gv ? gv + K * NG : NULL, gv ? gv + 2 * K * NG : NULL, &w->sstats[i])))
+            fprintf(stderr, "alnfile[%d]: subsample: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+        else {
+            snprintf(path, sizeof path, "%s/%s.%d.saturation", cfg->outdir, cfg->prefix, i);
+            if ((rc = emsar_write_saturation(path, r, mean, tpm, cfg->sub_nf, cfg->sub_f, cfg->sub_reps, seed, depth, sv, sv + K * T, sv + 2 * K * T,
+                                             sv + 3 * K * T)))
+                fprintf(stderr, "can't write %s\n", path);
+            else if (G) {
+                snprintf(path, sizeof path, "%s/%s.%d.gsaturation", cfg->outdir, cfg->prefix, i);
+                if ((rc = emsar_write_gsaturation(path, G, gsums, gsums + 2 * NG, cfg->sub_nf, cfg->sub_f, cfg->sub_reps, seed, depth, gv, gv + K * NG,
+                                                  gv + 2 * K * NG)))
+                    fprintf(stderr, "can't write %s\n", path);
+            }
+        }
+        free(sv); free(gv);
+        if (rc) goto done;
+    }
     if (cfg->verbose > 0)
         fprintf(stdout, "Complete: %s/%s.%d.fpkm  (EM passes %d, converged %d, solve %.1f ms, logL %.6f)\n", cfg->outdir, cfg->prefix, i,
                 w->stats[i].iters, w->stats[i].converged, w->stats[i].solve_ms, w->stats[i].loglik);
@@ -316,6 +347,10 @@ static void usage(const char *a0) {
             "      --bootstrap <B>       also write <outdir>/<prefix>.<i>.bootstrap: mean and sd of FPKM and sd of TPM over B Poisson\n"
             "                            bootstrap replicates of the sample (default 0 = off; .fpkm is the same either way)\n"
             "      --bootstrap-seed <n>  seed of the replicates' draws (default 1; sample i of -M uses n + i)\n"
+            "      --subsample <f1,f2,..> also write <prefix>.<i>.saturation: per fraction f in (0, 1] (at most 64) the mean and sd of FPKM and\n"
+            "                            TPM over replicates that keep every read with probability f (with --g2t also .gsaturation per gene)\n"
+            "      --subsample-reps <B>  replicates per fraction (default 10)\n"
+            "      --subsample-seed <n>  seed of their draws (default 1; sample i of -M uses n + i)\n"
             "      --g2t <file>          gene map (gene<TAB>transcript per line, plain or gzipped): also write <prefix>.<i>.gfpkm, the\n"
             "                            per-gene sums of util/FPKM2gFPKM.pl, and with --bootstrap <prefix>.<i>.gbootstrap (gene sd)\n"
             "      --gpus <n> / --devices <a,b,..> (-M: one worker per entry, ids may repeat) / --device <d> / --plain /\n"
@@ -328,6 +363,7 @@ int main(int argc, char **argv) {
     cfg.zero_cut = 2.5e-7;      /* a quarter of the "%lf" print quantum of the .fpkm file */
     cfg.abs_step = 1e-13;       /* see emsar_em_params.abs_step */
     cfg.boot_seed = 1;
+    cfg.sub_reps = 10; cfg.sub_seed = 1;
     const char *strand = "ns"; int multisample = 0, gpus = 0, device = 0;
     int dev_map[64], n_dev_map = 0;
     static struct option lo[] = {
@@ -339,6 +375,7 @@ int main(int argc, char **argv) {
         {"device", required_argument, 0, 1001}, {"plain", no_argument, 0, 1002}, {"stats-json", required_argument, 0, 1003},
         {"count-floor", required_argument, 0, 1004}, {"streaming-only", no_argument, 0, 1005}, {"rsh-cache", optional_argument, 0, 1006}, {"zero-cut", required_argument, 0, 1007}, {"abs-step", required_argument, 0, 1008}, {"devices", required_argument, 0, 1009}, {"device-collapse", no_argument, 0, 1010}, {"no-deterministic", no_argument, 0, 1011},
         {"bootstrap", required_argument, 0, 1012}, {"bootstrap-seed", required_argument, 0, 1013}, {"g2t", required_argument, 0, 1014},
+        {"subsample", required_argument, 0, 1015}, {"subsample-reps", required_argument, 0, 1016}, {"subsample-seed", required_argument, 0, 1017},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
@@ -385,6 +422,35 @@ int main(int argc, char **argv) {
                 break;
             }
             case 1014: cfg.g2t = optarg; break;
+            case 1015: {
+                const char *q = optarg;
+                cfg.sub_nf = 0;
+                for (;;) {
+                    char *end; errno = 0;
+                    const double v = strtod(q, &end);
+                    if (end == q || (*end && *end != ',') || errno || !isfinite(v) || !(v > 0.0 && v <= 1.0) || cfg.sub_nf >= 64) {
+                        fprintf(stderr, "--subsample wants a comma-separated list of 1 to 64 fractions in (0, 1].\n"); return 1;
+                    }
+                    cfg.sub_f[cfg.sub_nf++] = v;
+                    if (!*end) break;
+                    q = end + 1;
+                }
+                break;
+            }
+            case 1016: {
+                char *end; errno = 0;
+                long v = strtol(optarg, &end, 10);
+                if (end == optarg || *end || errno || v < 1 || v > 1000000) { fprintf(stderr, "--subsample-reps wants a number of replicates (1 .. 1000000).\n"); return 1; }
+                cfg.sub_reps = (int)v;
+                break;
+            }
+            case 1017: {
+                char *end; errno = 0;
+                unsigned long long v = strtoull(optarg, &end, 10);
+                if (end == optarg || *end || errno || optarg[0] == '-') { fprintf(stderr, "--subsample-seed wants a non-negative integer.\n"); return 1; }
+                cfg.sub_seed = (uint64_t)v;
+                break;
+            }
             case 1009: {
                 const char *q = optarg;
                 while (*q && n_dev_map < 64) {
@@ -490,17 +556,18 @@ int main(int argc, char **argv) {
     int *status = (int *)calloc((size_t)n_list, sizeof(int));
     emsar_em_stats *stats = (emsar_em_stats *)calloc((size_t)n_list, sizeof(emsar_em_stats));
     emsar_boot_stats *bstats = (emsar_boot_stats *)calloc((size_t)n_list, sizeof(emsar_boot_stats));
+    emsar_subsample_stats *sstats = (emsar_subsample_stats *)calloc((size_t)n_list, sizeof(emsar_subsample_stats));
     double *parse_s = (double *)calloc((size_t)n_list, sizeof(double));
     double *model_s = (double *)calloc((size_t)n_list, sizeof(double)), *host_s = (double *)calloc((size_t)n_list, sizeof(double));
     worker_arg *wa = (worker_arg *)calloc((size_t)n_workers, sizeof(worker_arg));
     pthread_t *th = (pthread_t *)calloc((size_t)n_workers, sizeof(pthread_t));
-    if (!status || !stats || !bstats || !parse_s || !model_s || !host_s || !wa || !th) { fprintf(stderr, "out of memory\n"); return 1; }
+    if (!status || !stats || !bstats || !sstats || !parse_s || !model_s || !host_s || !wa || !th) { fprintf(stderr, "out of memory\n"); return 1; }
     t0 = now_s();
     /* Workers wait at a gate until their number is final: a thread that cannot be started must not leave the others
      * waiting for samples nobody will take (the EUMAcut hand-over is in sample order). */
     int go = 0, n_started = 1;
     for (int g = 0; g < n_workers; g++)
-        wa[g] = (worker_arg){&cfg, rsh, multisample ? dev_map[g] : device, n_workers, g, &mu, &cv, &next_model, &eumacut, status, stats, bstats, parse_s,
+        wa[g] = (worker_arg){&cfg, rsh, multisample ? dev_map[g] : device, n_workers, g, &mu, &cv, &next_model, &eumacut, status, stats, bstats, sstats, parse_s,
                              model_s, host_s, &go, cfg.ao, {NULL, PTHREAD_MUTEX_INITIALIZER}};
     for (int g = 1; g < n_workers; g++) {
         if (pthread_create(&th[g], NULL, worker_main, &wa[g]) != 0) { fprintf(stderr, "warning: worker %d could not be started, using %d\n", g, g); break; }
@@ -541,6 +608,13 @@ int main(int argc, char **argv) {
                             b->n_replicates, b->batch, b->replicates_unconverged, b->set_passes_max, (long long)b->draws, b->draw_ms, b->sets_ms,
                             b->stream_ms, b->reduce_ms, b->total_ms);
                 }
+                if (cfg.sub_nf > 0) {
+                    const emsar_subsample_stats *b = &sstats[i];
+                    fprintf(f, ", \"sub_fractions\": %d, \"sub_replicates\": %d, \"sub_batch\": %d, \"sub_replicates_unconverged\": %d, "
+                               "\"sub_draws\": %lld, \"sub_draw_ms\": %.4f, \"sub_sets_ms\": %.4f, \"sub_stream_ms\": %.4f, \"sub_reduce_ms\": %.4f, \"sub_total_ms\": %.4f",
+                            b->n_fractions, b->n_replicates, b->batch, b->replicates_unconverged, (long long)b->draws, b->draw_ms, b->sets_ms,
+                            b->stream_ms, b->reduce_ms, b->total_ms);
+                }
                 fprintf(f, "}");
             }
             fprintf(f, "]}\n");
@@ -550,6 +624,6 @@ int main(int argc, char **argv) {
     emsar_rsh_free(rsh);
     emsar_genes_free(genes);
     for (int i = 0; i < n_list; i++) free(list[i]);
-    free(list); free(status); free(stats); free(bstats); free(parse_s); free(model_s); free(host_s); free(wa); free(th);
+    free(list); free(status); free(stats); free(bstats); free(sstats); free(parse_s); free(model_s); free(host_s); free(wa); free(th);
     return bad ? 1 : 0;
 }

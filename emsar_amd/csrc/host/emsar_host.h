@@ -156,6 +156,15 @@ int emsar_write_gfpkm(const char *path, const emsar_genes *g, const double *fpkm
 /* .gbootstrap (emsar-hip --g2t --bootstrap): the columns of .bootstrap per gene */
 int emsar_write_gbootstrap(const char *path, const emsar_genes *g, const double *fpkm, const double *boot_mean, const double *boot_sd,
                            const double *tpm, const double *boot_tpm_sd);
+/* .saturation (emsar-hip --subsample): a "#" line (fractions, replicates, seed, depth_mean per fraction), a header, then per
+ * transcript its name, FPKM and TPM as in .fpkm and per fraction mean_FPKM sd_FPKM mean_TPM sd_TPM ([n_fractions][n_tx] each) */
+int emsar_write_saturation(const char *path, const emsar_rsh *r, const double *fpkm, const double *tpm, int n_fractions,
+                           const double *fractions, int n_replicates, uint64_t seed, const double *depth_mean, const double *fpkm_mean,
+                           const double *fpkm_sd, const double *tpm_mean, const double *tpm_sd);
+/* .gsaturation (with --g2t): per gene FPKM and TPM as in .gfpkm and per fraction mean_FPKM sd_FPKM mean_TPM ([n_fractions][n_genes]) */
+int emsar_write_gsaturation(const char *path, const emsar_genes *g, const double *fpkm, const double *tpm, int n_fractions,
+                            const double *fractions, int n_replicates, uint64_t seed, const double *depth_mean, const double *fpkm_mean,
+                            const double *fpkm_sd, const double *tpm_mean);
 int emsar_write_fraglength(const char *path, const emsar_rsh *r, const emsar_counts *c, const emsar_model *m);
 int emsar_write_segments(const char *path, const emsar_rsh *r, const emsar_counts *c, const emsar_model *m,
                          const double *mean_fpkm);

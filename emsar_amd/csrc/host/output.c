@@ -8,6 +8,10 @@
  *   .gfpkm              util/FPKM2gFPKM.pl's header byte for byte, rows "%s\t%lf\t%lf\t%d\t%lf\n" (the script prints Perl's
  *                       default number format; merge_gTPM.pl / merge_gReadcount.pl read either)
  *   .gbootstrap         the columns of .bootstrap per gene
+ * and the depth subsampling's files (--subsample):
+ *   .saturation         "# fractions=.. replicates=.. seed=.. depth_mean=..", a header, then per transcript FPKM and TPM as in .fpkm and
+ *                       per fraction mean_FPKM sd_FPKM mean_TPM sd_TPM, all "%lf"
+ *   .gsaturation        the same per gene, per fraction mean_FPKM sd_FPKM mean_TPM
  * Column order of .fpkm is a contract: the reference's Perl utilities read columns 0,1,4,6 (util/FPKM2gFPKM.pl:19).
  */
 #include "emsar_host.h"
@@ -63,6 +67,45 @@ int emsar_write_gbootstrap(const char *path, const emsar_genes *g, const double 
     for (int32_t k = 0; k < g->n_genes; k++)
         fprintf(f, "%s\t%lf\t%lf\t%lf\t%lf\t%lf\n", g->names[k], fpkm[k], boot_mean[k], boot_sd[k], tpm[k], boot_tpm_sd[k]);
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+/* the rows of .saturation / .gsaturation: n names, per fraction ncol columns col[j] = [n_fractions][n] */
+static int write_saturation(const char *path, const char *id, char **names, int64_t n, const double *fpkm, const double *tpm, int n_fractions,
+                            const double *fractions, int n_replicates, uint64_t seed, const double *depth_mean, int ncol,
+                            const double *const *col, const char *const *colname) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "# fractions=");
+    for (int k = 0; k < n_fractions; k++) fprintf(f, "%s%.17g", k ? "," : "", fractions[k]);
+    fprintf(f, " replicates=%d seed=%llu depth_mean=", n_replicates, (unsigned long long)seed);
+    for (int k = 0; k < n_fractions; k++) fprintf(f, "%s%lf", k ? "," : "", depth_mean[k]);
+    fprintf(f, "\n%s\tFPKM\tTPM", id);
+    for (int k = 0; k < n_fractions; k++)
+        for (int j = 0; j < ncol; j++) fprintf(f, "\t%s@%.17g", colname[j], fractions[k]);
+    fprintf(f, "\n");
+    for (int64_t t = 0; t < n; t++) {
+        fprintf(f, "%s\t%lf\t%lf", names[t], fpkm[t], tpm[t]);
+        for (int k = 0; k < n_fractions; k++)
+            for (int j = 0; j < ncol; j++) fprintf(f, "\t%lf", col[j][(int64_t)k * n + t]);
+        fprintf(f, "\n");
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+int emsar_write_saturation(const char *path, const emsar_rsh *r, const double *fpkm, const double *tpm, int n_fractions,
+                           const double *fractions, int n_replicates, uint64_t seed, const double *depth_mean, const double *fpkm_mean,
+                           const double *fpkm_sd, const double *tpm_mean, const double *tpm_sd) {
+    const double *col[4] = {fpkm_mean, fpkm_sd, tpm_mean, tpm_sd};
+    const char *name[4] = {"mean_FPKM", "sd_FPKM", "mean_TPM", "sd_TPM"};
+    return write_saturation(path, "transcriptID", r->names, r->n_tx, fpkm, tpm, n_fractions, fractions, n_replicates, seed, depth_mean, 4, col, name);
+}
+
+int emsar_write_gsaturation(const char *path, const emsar_genes *g, const double *fpkm, const double *tpm, int n_fractions,
+                            const double *fractions, int n_replicates, uint64_t seed, const double *depth_mean, const double *fpkm_mean,
+                            const double *fpkm_sd, const double *tpm_mean) {
+    const double *col[3] = {fpkm_mean, fpkm_sd, tpm_mean};
+    const char *name[3] = {"mean_FPKM", "sd_FPKM", "mean_TPM"};
+    return write_saturation(path, "geneID", g->names, g->n_genes, fpkm, tpm, n_fractions, fractions, n_replicates, seed, depth_mean, 3, col, name);
 }
 
 int emsar_write_fraglength(const char *path, const emsar_rsh *r, const emsar_counts *c, const emsar_model *m) {

@@ -1,9 +1,21 @@
 // kernels_boot.hpp -- the Poisson bootstrap (emsar_hip_bootstrap): draws, the closed-form and merge steps of a batch of replicates,
 // and the per-transcript reduction over the replicates.  The batched set solver is k_solve_sets_boot (kernels_sets.hpp).
+// The depth subsampling (emsar_hip_subsample) runs the same steps on binomial draws (k_sub_draw) and scales every replicate to its
+// own depth (k_sub_scale) before the reduction.
 #pragma once
 // included by emsar_hip.hip only (one translation unit: the kernels live in its anonymous namespace)
 
 namespace {
+
+// the drawn weight w of caller row c in replicate y of the batch: into w_out and into the row's slot of the set solver
+__device__ __forceinline__ void boot_place(int64_t c, int64_t y, int32_t w, int64_t n_rows, const int64_t *__restrict__ slot,
+                                           int32_t *__restrict__ w_out, double *__restrict__ slots, int64_t slot_stride) {
+    if (w_out) w_out[y * n_rows + c] = w;
+    if (slot && w > 0) {
+        const int64_t s = slot[c];
+        if (s >= 0) atomic_add_f64(slots + y * slot_stride + s, (double)w);
+    }
+}
 
 // One lane per (caller row, replicate of the batch): w = Poisson(R_c) under key (seed, first + y), counter (c, j, 0, 0).
 //   w_out (may be null): [nb][n_rows] the drawn weights in caller order
@@ -17,11 +29,34 @@ __global__ __launch_bounds__(256) void k_boot_draw(int64_t n_rows, uint64_t seed
     if (c >= n_rows) return;
     const int64_t y = blockIdx.y;
     const int32_t w = emsar::boot_poisson(seed, (uint64_t)(first + y), (uint64_t)c, R[c]);
-    if (w_out) w_out[y * n_rows + c] = w;
-    if (slot && w > 0) {
-        const int64_t s = slot[c];
-        if (s >= 0) atomic_add_f64(slots + y * slot_stride + s, (double)w);
+    boot_place(c, y, w, n_rows, slot, w_out, slots, slot_stride);
+}
+
+// The subsampling's draw: w = Binomial(R_c, f) under key (seed, first + y), counter (c, j, 1, bits of f), placed like the bootstrap's.
+// n_drawn[y] += the replicate's total sum_c w_c: one integer atomic per wavefront (integers commute: exact, any order).
+__global__ __launch_bounds__(256) void k_sub_draw(int64_t n_rows, uint64_t seed, int64_t first, double f, const int32_t *__restrict__ R,
+                                                  const int64_t *__restrict__ slot, int32_t *__restrict__ w_out,
+                                                  double *__restrict__ slots, int64_t slot_stride, long long *__restrict__ n_drawn) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t y = blockIdx.y;
+    int32_t w = 0;
+    if (c < n_rows) {
+        w = emsar::boot_binomial(seed, (uint64_t)(first + y), (uint64_t)c, R[c], f);
+        boot_place(c, y, w, n_rows, slot, w_out, slots, slot_stride);
     }
+    long long tot = w;
+    for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
+    if ((threadIdx.x & 63) == 0 && tot > 0) __hip_atomic_fetch_add(n_drawn + y, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// theta_b -> theta_b * N_R / N_b, the FPKM of replicate b at its own depth (0 when nothing was drawn): E carries the full sample's
+// read total and the fixed point is linear in that scale.  blockIdx.y = replicate of the batch; the factor is computed once per workgroup.
+__global__ __launch_bounds__(256) void k_sub_scale(int n, double n_full, const long long *__restrict__ n_drawn, double *__restrict__ theta) {
+    __shared__ double factor;
+    if (threadIdx.x == 0) { const long long nb = n_drawn[blockIdx.y]; factor = nb > 0 ? n_full / (double)nb : 0.0; }
+    __syncthreads();
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n) theta[(int64_t)blockIdx.y * n + t] *= factor;
 }
 
 // g_u of every resident transcript from the replicate's folded single-row counts: g_u[k] = usum[g_tid[k]]

@@ -22,6 +22,7 @@ SYMBOLS = [
     "emsar_hip_layout_selfcheck_tiled", "emsar_hip_sets_selfcheck", "emsar_hip_upload_euma", "emsar_hip_adj_euma", "emsar_hip_collapse_rows",
     "emsar_hip_set_deterministic", "emsar_hip_bootstrap", "emsar_hip_bootstrap_weights", "emsar_hip_bootstrap_draw_host",
     "emsar_hip_set_gene_map", "emsar_hip_gene_sums", "emsar_hip_bootstrap_genes",
+    "emsar_hip_subsample", "emsar_hip_subsample_weights", "emsar_hip_subsample_draw_host",
 ]
 
 
@@ -53,6 +54,15 @@ class CollapseStats(C.Structure):
 
 class BootStats(C.Structure):
     _fields_ = [("n_replicates", C.c_int32), ("batch", C.c_int32), ("replicates_unconverged", C.c_int32), ("set_passes_max", C.c_int32),
+                ("draws", C.c_int64), ("draw_ms", C.c_double), ("sets_ms", C.c_double), ("stream_ms", C.c_double), ("reduce_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SubsampleStats(C.Structure):
+    _fields_ = [("n_fractions", C.c_int32), ("n_replicates", C.c_int32), ("batch", C.c_int32), ("replicates_unconverged", C.c_int32),
                 ("draws", C.c_int64), ("draw_ms", C.c_double), ("sets_ms", C.c_double), ("stream_ms", C.c_double), ("reduce_ms", C.c_double),
                 ("total_ms", C.c_double)]
 
@@ -119,6 +129,10 @@ def load_library():
     L.emsar_hip_gene_sums.argtypes = [vp, C.c_int32, f64p, f64p]
     L.emsar_hip_bootstrap_genes.argtypes = [vp, C.POINTER(EmParams), C.c_uint64, C.c_int32, C.c_int32, f64p, f64p, f64p, f64p,
                                             f64p, f64p, f64p, C.POINTER(BootStats)]
+    L.emsar_hip_subsample.argtypes = [vp, C.POINTER(EmParams), C.c_uint64, C.c_int32, f64p, C.c_int32, f64p, f64p, f64p, f64p, f64p, f64p,
+                                      f64p, f64p, f64p, C.POINTER(SubsampleStats)]
+    L.emsar_hip_subsample_weights.argtypes = [vp, C.c_uint64, C.c_int32, C.c_double, i32p]
+    L.emsar_hip_subsample_draw_host.argtypes = [C.c_uint64, C.c_int32, C.c_double, C.c_int64, i32p, i32p]
     _lib = L
     return L
 
@@ -164,6 +178,19 @@ def bootstrap_draw_host(seed, replicate, row_weight=None, n_rows=None):
     rc = L.emsar_hip_bootstrap_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(replicate), n, _p(w, C.c_int32), _p(out, C.c_int32))
     if rc != 0:
         raise EmsarHipError(rc, "bootstrap_draw_host")
+    return out[:n]
+
+
+def subsample_draw_host(seed, replicate, fraction, row_weight=None, n_rows=None):
+    """Host-only: the binomial draws w ~ Binomial(row_weight, fraction) of subsampling replicate `replicate` of `seed` (no GPU
+    needed), the same function the device evaluates.  row_weight None = 1 per row (then n_rows is required)."""
+    L = load_library()
+    w = None if row_weight is None else _arr(row_weight, np.int32)
+    n = len(w) if w is not None else int(n_rows)
+    out = np.zeros(max(n, 1), dtype=np.int32)
+    rc = L.emsar_hip_subsample_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(replicate), float(fraction), n, _p(w, C.c_int32), _p(out, C.c_int32))
+    if rc != 0:
+        raise EmsarHipError(rc, "subsample_draw_host")
     return out[:n]
 
 
@@ -296,6 +323,37 @@ class EmsarHip:
         out = np.zeros(max(self.n_rows, 1), dtype=np.int32)
         self._chk(self._L.emsar_hip_bootstrap_weights(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(replicate), _p(out, C.c_int32)),
                   "bootstrap_weights")
+        return out[:self.n_rows]
+
+    def subsample(self, fractions, n, seed, want_replicates=False, want_genes=False, max_iter=100000, accel=1, tol=1e-10, abs_floor=1e-6,
+                  check_every=8, count_floor=0.0, set_mode=0, zero_cut=0.0, abs_step=0.0, newton_after=0):
+        """Binomial depth subsampling of the current sample: for each fraction f in (0, 1], n replicates with w ~ Binomial(R, f), each
+        solved like solve() with these parameters and scaled to its own depth.  Returns a dict: fpkm_mean, fpkm_sd, tpm_mean, tpm_sd
+        ([n_fractions][n_tx]), depth_mean ([n_fractions]), replicates ([n_fractions][n][n_tx] or None), with want_genes also
+        gene_fpkm_mean, gene_fpkm_sd, gene_tpm_mean ([n_fractions][n_genes]), stats."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        fr = np.ascontiguousarray(np.atleast_1d(np.asarray(fractions, dtype=np.float64)))
+        K, T, G = len(fr), self.n_tx, max(self.n_genes, 1)
+        Ka = max(K, 1)
+        out = {k: np.zeros((Ka, T)) for k in ("fpkm_mean", "fpkm_sd", "tpm_mean", "tpm_sd")}
+        depth = np.zeros(Ka)
+        reps = np.zeros((Ka, n, T)) if (want_replicates and n > 0) else None
+        gene = {k: np.zeros((Ka, G)) for k in ("gene_fpkm_mean", "gene_fpkm_sd", "gene_tpm_mean")} if want_genes else {}
+        st = SubsampleStats()
+        self._chk(self._L.emsar_hip_subsample(self._h, C.byref(p), int(seed) & 0xFFFFFFFFFFFFFFFF, K, _p(fr, C.c_double), int(n),
+                                              _p(out["fpkm_mean"], C.c_double), _p(out["fpkm_sd"], C.c_double), _p(out["tpm_mean"], C.c_double),
+                                              _p(out["tpm_sd"], C.c_double), _p(depth, C.c_double), _p(reps, C.c_double),
+                                              _p(gene.get("gene_fpkm_mean"), C.c_double), _p(gene.get("gene_fpkm_sd"), C.c_double),
+                                              _p(gene.get("gene_tpm_mean"), C.c_double), C.byref(st)), "subsample")
+        out.update(depth_mean=depth, replicates=reps, stats=st)
+        out.update({k: v[:, :self.n_genes] for k, v in gene.items()})
+        return out
+
+    def subsample_weights(self, seed, replicate, fraction):
+        """The drawn row weights of one subsampling replicate at one fraction (caller row order), drawn on the device."""
+        out = np.zeros(max(self.n_rows, 1), dtype=np.int32)
+        self._chk(self._L.emsar_hip_subsample_weights(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(replicate), float(fraction), _p(out, C.c_int32)),
+                  "subsample_weights")
         return out[:self.n_rows]
 
     def collapse_rows(self, n_tx, row_ptr, col_idx, row_weight=None, want_map=True):

@@ -243,6 +243,41 @@ int emsar_hip_bootstrap_genes(emsar_hip_ctx *ctx, const emsar_em_params *p, uint
 int emsar_hip_bootstrap_draw_host(uint64_t seed, int32_t replicate, int64_t n_rows, const int32_t *row_weight /* NULL = 1 */,
                                   int32_t *w_out);
 
+/* ---- binomial depth subsampling: the estimates at a fraction of the reads ---------------------------------------------------
+ * "Did we sequence deep enough": keeping every read of the sample with probability f, independently (what samtools view -s does),
+ * gives row c the weight w_c ~ Binomial(R_c, f) (a read-level row has R = 1, a segment the sum of its reads: the same law).  For
+ * each fraction f_k in the caller's order, replicates b = 0 .. n_replicates-1 are drawn and solved exactly like bootstrap replicates
+ * (same kernels, set_mode 0 and 1, E and den unchanged, the context left as it was, ERR_NUMERIC as solve).
+ * Keying: Philox4x64-10 with key (seed, b) and counter (row, j, 1, bits of the double f_k), see DESIGN.md "Subsampling".  A draw is a
+ * pure function of (seed, b, row, R_c, f_k): it does not depend on where f_k stands in the list, on the layout, the set partition, the
+ * batch or the device, and it is independent of the bootstrap's draws (counter (row, j, 0, 0)) under the same seed.  f = 1 gives w = R.
+ * Normalisation: E_c carries the full sample's read total N, so the raw MLE of a thinned replicate is about f times the FPKM.  The
+ * fixed point is linear in that scale: the FPKM of replicate b at its own depth is theta_b * N_R / N_b with N_b = sum_c w_c and
+ * N_R = sum_c R_c over the rows that are drawn (E != 0); 0 when N_b = 0.  TPM_b = theta_b * 1e6 / sum theta_b does not depend on it.
+ *   subsample            per fraction and transcript the mean and the sample sd (n - 1) over the replicates of the normalised FPKM and
+ *                        of TPM_b, reduced in replicate order (the same results for any batch size); depth_mean[k] = mean of N_b.
+ *                        Gene outputs (all three NULL, or all three given after set_gene_map: ERR_STATE without a map): mean / sd of
+ *                        the gene sums of the normalised FPKM (the order of gene_sums), mean of the gene TPM.  replicates (may be
+ *                        NULL): [n_fractions][n_replicates][n_tx], the normalised FPKM.  ERR_STATE before upload_sample; ERR_ARG for
+ *                        n_fractions < 1, n_replicates < 1, a fraction that is not finite or not in (0, 1].
+ *   subsample_weights    the drawn weights of one replicate at one fraction, caller row order (computed on the device).
+ *   subsample_draw_host  the same draws on the host, no HIP call (row_weight NULL = 1 per row). */
+typedef struct {
+    int32_t n_fractions, n_replicates, batch, replicates_unconverged;
+    int64_t draws;                                   /* rows with R > 0 x replicates x fractions */
+    double  draw_ms, sets_ms, stream_ms, reduce_ms;  /* device time per stage, summed over the fractions */
+    double  total_ms;                                /* wall time of the call */
+} emsar_subsample_stats;
+int emsar_hip_subsample(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed,
+                        int32_t n_fractions, const double *fractions, int32_t n_replicates,
+                        double *fpkm_mean, double *fpkm_sd, double *tpm_mean, double *tpm_sd /* [n_fractions][n_tx] each */,
+                        double *depth_mean /* n_fractions */, double *replicates /* or NULL */,
+                        double *gene_fpkm_mean, double *gene_fpkm_sd, double *gene_tpm_mean /* [n_fractions][n_genes] or NULL */,
+                        emsar_subsample_stats *stats);
+int emsar_hip_subsample_weights(emsar_hip_ctx *ctx, uint64_t seed, int32_t replicate, double fraction, int32_t *w_out /* n_rows */);
+int emsar_hip_subsample_draw_host(uint64_t seed, int32_t replicate, double fraction, int64_t n_rows,
+                                  const int32_t *row_weight /* NULL = 1 */, int32_t *w_out);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 typedef struct {
     int64_t n_rows, nnz;

@@ -1,6 +1,6 @@
 """Cost of the Poisson bootstrap (emsar_hip_bootstrap) on two workloads; prints one JSON object.
 
-    python tools/boot_bench.py [--reps 100] [--cfg3-scale 0.1] [--cfg3-reps 10] [--genes] [--out FILE]
+    python tools/boot_bench.py [--reps 100] [--cfg3-scale 0.1] [--cfg3-reps 10] [--genes | --subsample] [--out FILE]
 
   segment   bench.py's time_to_mle problem (same seeds): one solve, then B replicates in one call -- device time per stage (HIP events),
             wall time, ms per replicate against one solve, the batch size and the slowest set's passes
@@ -9,6 +9,9 @@
   --genes  instead: emsar_hip_bootstrap against emsar_hip_bootstrap_genes on both workloads, the generator's families as genes, and on
             the segment problem also a worst-case map with 90 % of the transcripts in one gene -- reduce_ms and total_ms of each, the
             calls alternated (two rounds) so that the solves' own spread shows
+  --subsample  instead: emsar_hip_subsample (fractions 0.1, 0.25, 0.5, 0.75, 1.0, B replicates each) next to one solve and next to
+            emsar_hip_bootstrap with the same B on the same context, the calls alternated (two rounds); per fraction also a call of its
+            own, which gives the time per replicate at that fraction
 Kernel-level times come from a separate `rocprofv3 --kernel-trace --stats` run of this script."""
 import argparse
 import json
@@ -72,6 +75,36 @@ def run_genes(dev, B, solve_kw, maps, seed=1, rounds=2):
     return out
 
 
+SUB_FRACTIONS = [0.1, 0.25, 0.5, 0.75, 1.0]
+
+
+def run_subsample(dev, B, solve_kw, seed=1, rounds=2):
+    """subsample over SUB_FRACTIONS vs one solve vs bootstrap, B replicates each, alternated; then every fraction alone"""
+    dev.solve(**solve_kw)
+    dev.bootstrap(min(B, 2), seed, **solve_kw)            # first calls: draw map, kernels loaded
+    dev.subsample([0.5], min(B, 2), seed, **solve_kw)
+    out = {"replicates": B, "fractions": SUB_FRACTIONS, "solve": [], "bootstrap": [], "subsample": [], "per_fraction": []}
+    for _ in range(rounds):
+        t0 = time.perf_counter()
+        _, st = dev.solve(**solve_kw)
+        out["solve"].append({"wall_ms": (time.perf_counter() - t0) * 1e3, "kernel_ms": st.kernel_ms})
+        t0 = time.perf_counter()
+        bs = dev.bootstrap(B, seed, **solve_kw)[4]
+        out["bootstrap"].append({"wall_ms": (time.perf_counter() - t0) * 1e3, "ms_per_replicate": bs.total_ms / B, **bs.as_dict()})
+        t0 = time.perf_counter()
+        r = dev.subsample(SUB_FRACTIONS, B, seed, **solve_kw)
+        ss = r["stats"]
+        out["subsample"].append({"wall_ms": (time.perf_counter() - t0) * 1e3, "ms_per_replicate": ss.total_ms / (B * len(SUB_FRACTIONS)),
+                                 "depth_mean": [float(x) for x in r["depth_mean"]], **ss.as_dict()})
+    for f in SUB_FRACTIONS:
+        runs = []
+        for _ in range(rounds):
+            ss = dev.subsample([f], B, seed, **solve_kw)["stats"]
+            runs.append({"ms_per_replicate": ss.total_ms / B, **ss.as_dict()})
+        out["per_fraction"].append({"fraction": f, "runs": runs})
+    return out
+
+
 def run(dev, B, solve_kw, seed=1):
     dev.solve(**solve_kw)                                 # sets found and packed, warm
     t0 = time.perf_counter()
@@ -94,6 +127,7 @@ def main():
     ap.add_argument("--cfg3-reps", type=int, default=10)
     ap.add_argument("--skip-cfg3", action="store_true")
     ap.add_argument("--genes", action="store_true")
+    ap.add_argument("--subsample", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
     from emsar_amd import EmsarHip, synth
@@ -103,7 +137,9 @@ def main():
         dev.upload_structure(n_tx, rp, ci)
         dev.upload_sample(R, E, None)
         seg_kw = dict(max_iter=200000, tol=1e-10)
-        if a.genes:
+        if a.subsample:
+            out["segment"] = {"n_tx": int(n_tx), "segments": int(len(R)), **run_subsample(dev, a.reps, seg_kw)}
+        elif a.genes:
             sizes = family_sizes(n_tx)
             fam = np.repeat(np.arange(len(sizes)), sizes).astype(np.int32)
             maps = {"families": (fam, int(fam.max()) + 1), "worst_90pct": worst_case_map(n_tx, fam)}
@@ -121,7 +157,9 @@ def main():
             dev.upload_sample(cw, None, s["den"])
             kw = dict(max_iter=200000, tol=1e-10, zero_cut=2.5e-7, abs_step=1e-13)
             info = {"scale": a.cfg3_scale, "reads": int(s["n_reads"]), "n_tx": int(s["n_tx"]), "segments": int(len(cw))}
-            if a.genes:
+            if a.subsample:
+                out["cfg3"] = {**info, **run_subsample(dev, a.cfg3_reps, kw)}
+            elif a.genes:
                 _, fam = synth.make_families(s["n_tx"], cfg["seed"])
                 out["cfg3"] = {**info, **run_genes(dev, a.cfg3_reps, kw, {"families": (fam, int(fam.max()) + 1)})}
             else:
