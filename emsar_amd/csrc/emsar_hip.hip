@@ -18,9 +18,11 @@
 //   kernels_boot.hpp      k_boot_draw, k_boot_accum, ...         the Poisson bootstrap (draws: boot_rng.hpp; sets: k_solve_sets_boot)
 //                         k_sub_draw, k_sub_scale                the depth subsampling: binomial draws, every replicate to its own depth
 //   kernels_genes.hpp     k_gene_sums, k_gene_finish             per-gene sums in a fixed order (gene_sums, the bootstrap's gene sd)
+//   kernels_quant.hpp     k_boot_quantiles                       quantiles over the held replicates (bootstrap_quantiles)
 //   collapse.hip          read-level rows -> weighted segments (own translation unit)
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -45,6 +47,7 @@
 #include "kernels_cluster.hpp"
 #include "kernels_boot.hpp"
 #include "kernels_genes.hpp"
+#include "kernels_quant.hpp"
 
 // ==================================================================================================
 // context
@@ -1199,11 +1202,18 @@ struct BootPlan {
     double *fpkm_mean = nullptr, *fpkm_sd = nullptr, *tpm_mean = nullptr, *tpm_sd = nullptr, *replicates = nullptr;
     double *gene_mean = nullptr, *gene_sd = nullptr, *gene_tpm_mean = nullptr, *gene_tpm_sd = nullptr;
     double *depth_mean = nullptr;        // subsampling: mean over the replicates of N_b = sum_c w_c, per fraction
+    // quantiles (bootstrap only, n_q > 0): every replicate's theta, S_b and gene sums stay on the device for k_boot_quantiles
+    int32_t n_q = 0;
+    const double *q = nullptr;
+    double *fpkm_q = nullptr, *tpm_q = nullptr, *gene_fpkm_q = nullptr, *gene_tpm_q = nullptr;     // [n_q][n_tx], [n_q][n_genes]
+    double *replicate_sums = nullptr;    // [n_rep] S_b
 };
 struct BootTimes {
     int32_t batch = 0, unconverged = 0, passes_max = 0;
     int64_t draws = 0;
     double draw_ms = 0, sets_ms = 0, stream_ms = 0, reduce_ms = 0, total_ms = 0;
+    int64_t held_bytes = 0;
+    double quantile_ms = 0;
 };
 
 static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_t seed, int32_t first, int32_t n_rep, const BootPlan &plan,
@@ -1214,6 +1224,33 @@ static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_
     if (!(p.count_floor >= 0.0) || (p.set_mode != 0 && p.set_mode != 1)) return EMSAR_HIP_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     int rc;
+    BootRestore guard(ctx);
+    // quantiles: all n_rep replicates are held -- theta, S_b and the gene sums -- and, with the quantile stage's own buffers, must fit
+    // half of the free device memory; they are allocated here, before anything is launched
+    const bool hold = plan.n_q > 0;
+    const int64_t held_bytes = hold ? 8 * (int64_t)n_rep * ((int64_t)ctx->n_tx + 1 + (genes ? ctx->n_genes : 0)) : 0;
+    double *d_thb0 = nullptr, *d_sums0 = nullptr, *d_gsum0 = nullptr;       // [batch or n_rep][n_tx], [..], [..][n_genes]
+    double *d_q = nullptr, *d_qout = nullptr, *d_qsums = nullptr;           // [n_q], [2][n_q][n_tx] then [2][n_q][n_genes], [n_rep]
+    int32_t *d_libof = nullptr;                                             // caller tid -> library index, null = the same
+    if (hold) {
+        const int64_t T = ctx->n_tx, G = genes ? ctx->n_genes : 0, nq = plan.n_q;
+        const auto &m = tid_map(ctx);
+        const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !m.empty();
+        const int64_t need = held_bytes + 8 * (int64_t)n_rep + 8 * nq + 16 * nq * (T + G) + (remap ? 4 * T : 0);
+        size_t hfree = 0, htotal = 0;
+        if (hipMemGetInfo(&hfree, &htotal) != hipSuccess) hfree = (size_t)1 << 30;
+        if ((uint64_t)need > (uint64_t)(hfree / 2)) { ctx->err = "bootstrap quantiles: the replicates do not fit half of the free device memory"; return EMSAR_HIP_ERR_OOM; }
+        if (guard.alloc((void **)&d_thb0, (size_t)(n_rep * T) * 8) != hipSuccess || guard.alloc((void **)&d_sums0, (size_t)n_rep * 8) != hipSuccess ||
+            (genes && guard.alloc((void **)&d_gsum0, (size_t)(n_rep * G) * 8) != hipSuccess) || guard.alloc((void **)&d_q, (size_t)nq * 8) != hipSuccess ||
+            guard.alloc((void **)&d_qout, (size_t)(2 * nq * (T + G)) * 8) != hipSuccess || guard.alloc((void **)&d_qsums, (size_t)n_rep * 8) != hipSuccess ||
+            (remap && guard.alloc((void **)&d_libof, (size_t)T * 4) != hipSuccess)) {
+            (void)hipGetLastError();
+            ctx->err = "bootstrap quantiles: device allocation of the held replicates failed";
+            return EMSAR_HIP_ERR_OOM;
+        }
+        HIPCHK(hipMemcpy(d_q, plan.q, (size_t)nq * 8, hipMemcpyHostToDevice));
+        if (remap) HIPCHK(hipMemcpy(d_libof, m.data(), (size_t)T * 4, hipMemcpyHostToDevice));
+    }
     bool use_sets = p.set_mode == 0;
     if (use_sets && (rc = ensure_sets(ctx))) return rc;
     if (use_sets && ctx->RS.giant) use_sets = false;
@@ -1229,25 +1266,28 @@ static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_
     if (use_sets) for (int c = 0; c < emsar::kSetClasses; c++) for (const auto &d : S.desc[c]) n_gu += d.n_t;
     // replicates per batch: what fits a quarter of the free device memory (at most 2 GiB), EMSAR_HIP_BOOT_BATCH overrides
     const int64_t ng = genes ? ctx->n_genes : 0, n_gchunk = genes && ctx->n_gene_multi > 0 ? ctx->n_gene_chunks : 0;
-    const int64_t per_rep = 8 * (slot_stride + n_gu + n + 1 + ng + n_gchunk) + (need_stream ? 4 * n_rows : 0) + (int64_t)sizeof(SetStat) * n_sets;
+    // (a quantile call's theta, S_b and gene sums live in the held buffers, allocated above: not part of a batch, and mfree is what they left)
+    const int64_t per_rep = 8 * (slot_stride + n_gu + (hold ? 0 : n + 1 + ng) + n_gchunk) + (need_stream ? 4 * n_rows : 0) + (int64_t)sizeof(SetStat) * n_sets;
     size_t mfree = 0, mtotal = 0;
     if (hipMemGetInfo(&mfree, &mtotal) != hipSuccess) mfree = (size_t)1 << 30;
     const int64_t budget = std::min<int64_t>((int64_t)(mfree / 4), (int64_t)2 << 30);
     int64_t batch = std::max<int64_t>(1, budget / std::max<int64_t>(per_rep, 1));
     if (const char *e = getenv("EMSAR_HIP_BOOT_BATCH")) { if (atoi(e) >= 1) batch = atoi(e); }
     batch = std::min<int64_t>(std::min<int64_t>(batch, n_rep), 65535);
-    BootRestore guard(ctx);
-    double *d_slots = nullptr, *d_gu = nullptr, *d_thb = nullptr, *d_sums = nullptr, *d_acc4 = nullptr;
+    double *d_slots = nullptr, *d_gu = nullptr, *d_acc4 = nullptr;
     int32_t *d_wb = nullptr;
     SetStat *d_bstat = nullptr;
     HIPCHK(guard.alloc((void **)&d_slots, (size_t)(batch * slot_stride) * 8));
     HIPCHK(guard.alloc((void **)&d_gu, (size_t)(batch * n_gu) * 8));
-    HIPCHK(guard.alloc((void **)&d_thb, (size_t)(batch * n) * 8));
-    HIPCHK(guard.alloc((void **)&d_sums, (size_t)batch * 8));
+    // (a quantile call keeps all n_rep replicates: a batch then writes its rows of the held buffers instead of a buffer of its own)
+    if (!hold) {
+        HIPCHK(guard.alloc((void **)&d_thb0, (size_t)(batch * n) * 8));
+        HIPCHK(guard.alloc((void **)&d_sums0, (size_t)batch * 8));
+    }
     HIPCHK(guard.alloc((void **)&d_acc4, (size_t)4 * n * 8));
-    double *d_gsum = nullptr, *d_gpart = nullptr, *d_gacc4 = nullptr;       // [batch][n_genes], [batch][n_gene_chunks], [4][n_genes]
+    double *d_gpart = nullptr, *d_gacc4 = nullptr;                          // [batch][n_gene_chunks], [4][n_genes]
     if (genes) {
-        HIPCHK(guard.alloc((void **)&d_gsum, (size_t)(batch * ng) * 8));
+        if (!hold) HIPCHK(guard.alloc((void **)&d_gsum0, (size_t)(batch * ng) * 8));
         if (n_gchunk) HIPCHK(guard.alloc((void **)&d_gpart, (size_t)(batch * n_gchunk) * 8));
         HIPCHK(guard.alloc((void **)&d_gacc4, (size_t)4 * ng * 8));
     }
@@ -1270,7 +1310,7 @@ static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_
     HIPCHK(hipEventCreate(&e[0])); HIPCHK(hipEventCreate(&e[1]));
     auto lap = [&](double &acc) -> int { float ms = 0; HIPCHK(hipEventRecord(e[1], ctx->stream)); HIPCHK(hipEventSynchronize(e[1]));
                                          HIPCHK(hipEventElapsedTime(&ms, e[0], e[1])); acc += ms; return EMSAR_HIP_OK; };
-    double draw_ms = 0, sets_ms = 0, stream_ms = 0, reduce_ms = 0;
+    double draw_ms = 0, sets_ms = 0, stream_ms = 0, reduce_ms = 0, quantile_ms = 0;
     int32_t unconverged = 0, passes_max = 0;
     const SetSolveParams P = set_params(p);
     if (n_sets) {
@@ -1291,6 +1331,9 @@ static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_
         for (int64_t done = 0; done < n_rep; ) {
             const int64_t nb = std::min<int64_t>(batch, n_rep - done);
             std::vector<char> unconv((size_t)nb, 0);      // replicates of the batch with a part that hit max_iter
+            // the batch's theta, S_b and gene sums: the batch buffers, or the batch's rows of the held ones
+            double *const d_thb = d_thb0 + (hold ? done * n : 0), *const d_sums = d_sums0 + (hold ? done : 0);
+            double *const d_gsum = genes ? d_gsum0 + (hold ? done * ng : 0) : nullptr;
             // ---- draws ----
             HIPCHK(hipEventRecord(e[0], ctx->stream));
             if (use_sets) HIPCHK(hipMemsetAsync(d_slots, 0, (size_t)(nb * slot_stride) * 8, ctx->stream));
@@ -1419,6 +1462,34 @@ static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_
             }
         }
         if (plan.depth_mean) plan.depth_mean[fk] = (double)depth_sum / (double)n_rep;
+        if (hold) {   // ---- quantiles over the held replicates: transcripts, then genes ----
+            const int64_t nq = plan.n_q;
+            int Bp = 1;
+            while (Bp < n_rep) Bp <<= 1;
+            const int cs = emsar::quant_tile_shift(Bp);
+            const size_t lds = ((size_t)Bp << cs) * 8;
+            double *const d_gq = d_qout + 2 * nq * n;
+            HIPCHK(hipEventRecord(e[0], ctx->stream));
+            // S_b added in the caller's order: the TPM quantiles do not depend on the library's numbering (kernels_quant.hpp)
+            hipLaunchKernelGGL(k_quant_sums, dim3((unsigned)n_rep), dim3(1024), 0, ctx->stream, n, d_libof, d_thb0, d_qsums);
+            if (n > 0)
+                hipLaunchKernelGGL(k_boot_quantiles, dim3((unsigned)(((int64_t)n + (1 << cs) - 1) >> cs)), dim3(256), lds, ctx->stream, (int64_t)n,
+                                   (int)n_rep, Bp, cs, d_thb0, d_qsums, (int)nq, d_q, d_qout, d_qout + nq * n);
+            if (genes && ng > 0)
+                hipLaunchKernelGGL(k_boot_quantiles, dim3((unsigned)((ng + (1 << cs) - 1) >> cs)), dim3(256), lds, ctx->stream, ng, (int)n_rep, Bp, cs,
+                                   d_gsum0, d_qsums, (int)nq, d_q, d_gq, d_gq + nq * ng);
+            HIPCHK(hipGetLastError());
+            if ((rc = lap(quantile_ms))) return rc;
+            HIPCHK(hipMemcpy(plan.fpkm_q, d_qout, (size_t)(nq * n) * 8, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(plan.tpm_q, d_qout + nq * n, (size_t)(nq * n) * 8, hipMemcpyDeviceToHost));
+            try { for (int64_t k = 0; k < nq; k++) { from_lib(ctx, plan.fpkm_q + k * n); from_lib(ctx, plan.tpm_q + k * n); } }
+            catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+            if (genes) {
+                HIPCHK(hipMemcpy(plan.gene_fpkm_q, d_gq, (size_t)(nq * ng) * 8, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(plan.gene_tpm_q, d_gq + nq * ng, (size_t)(nq * ng) * 8, hipMemcpyDeviceToHost));
+            }
+            if (plan.replicate_sums) HIPCHK(hipMemcpy(plan.replicate_sums, d_qsums, (size_t)n_rep * 8, hipMemcpyDeviceToHost));
+        }
     }
     if (stats) {
         *stats = BootTimes();
@@ -1427,6 +1498,7 @@ static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_
         for (int64_t r = 0; r < n_rows; r++) pos += ctx->h_wgt[(size_t)r] > 0;
         stats->draws = pos * n_rep * plan.n_fractions;
         stats->draw_ms = draw_ms; stats->sets_ms = sets_ms; stats->stream_ms = stream_ms; stats->reduce_ms = reduce_ms;
+        stats->held_bytes = held_bytes; stats->quantile_ms = quantile_ms;
     }
     // the sample's own weights back before the call returns (the guard does it too, but a failure there must be reported)
     if (guard.swapped) {
@@ -1485,6 +1557,55 @@ int emsar_hip_bootstrap_genes(emsar_hip_ctx *ctx, const emsar_em_params *p, uint
         if (rc == EMSAR_HIP_OK) boot_stats_out(stats, t, n_replicates);
         return rc;
     } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+}
+
+// ---- bootstrap quantiles ------------------------------------------------------------------------------------------------------
+static bool quantile_args_ok(int32_t n_q, const double *q) {
+    if (n_q < 1 || !q) return false;
+    for (int32_t k = 0; k < n_q; k++) if (!std::isfinite(q[k]) || q[k] < 0.0 || q[k] > 1.0) return false;
+    return true;
+}
+
+int emsar_hip_bootstrap_quantiles(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t first_replicate, int32_t n_replicates,
+                                  int32_t n_q, const double *q, double *fpkm_mean, double *fpkm_sd, double *tpm_sd, double *replicates,
+                                  double *replicate_sums, double *fpkm_q, double *tpm_q, double *gene_fpkm_mean, double *gene_fpkm_sd,
+                                  double *gene_tpm_sd, double *gene_fpkm_q, double *gene_tpm_q, emsar_boot_stats *stats,
+                                  emsar_quantile_stats *qstats) {
+    if (!ctx) return EMSAR_HIP_ERR_ARG;
+    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
+    const int n_gene_out = (gene_fpkm_mean != nullptr) + (gene_fpkm_sd != nullptr) + (gene_tpm_sd != nullptr) + (gene_fpkm_q != nullptr) +
+                           (gene_tpm_q != nullptr);
+    if (!fpkm_mean || !fpkm_sd || !tpm_sd || !fpkm_q || !tpm_q || n_replicates < 1 || n_replicates > emsar::kQuantMaxRep || first_replicate < 0 ||
+        (int64_t)first_replicate + (int64_t)n_replicates > (int64_t)INT32_MAX + 1 || !quantile_args_ok(n_q, q) || (n_gene_out != 0 && n_gene_out != 5))
+        return EMSAR_HIP_ERR_ARG;
+    if (n_gene_out && !ctx->have_genes) return EMSAR_HIP_ERR_STATE;
+    try {
+        BootPlan plan;
+        plan.fpkm_mean = fpkm_mean; plan.fpkm_sd = fpkm_sd; plan.tpm_sd = tpm_sd; plan.replicates = replicates;
+        plan.gene_mean = gene_fpkm_mean; plan.gene_sd = gene_fpkm_sd; plan.gene_tpm_sd = gene_tpm_sd;
+        plan.n_q = n_q; plan.q = q; plan.fpkm_q = fpkm_q; plan.tpm_q = tpm_q; plan.gene_fpkm_q = gene_fpkm_q; plan.gene_tpm_q = gene_tpm_q;
+        plan.replicate_sums = replicate_sums;
+        BootTimes t;
+        const int rc = bootstrap_impl(ctx, p, seed, first_replicate, n_replicates, plan, &t);
+        if (rc == EMSAR_HIP_OK) {
+            boot_stats_out(stats, t, n_replicates);
+            if (qstats) { memset(qstats, 0, sizeof(*qstats)); qstats->n_quantiles = n_q; qstats->held_bytes = t.held_bytes; qstats->quantile_ms = t.quantile_ms; }
+        }
+        return rc;
+    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+}
+
+int emsar_hip_quantiles_host(int32_t n_rep, int64_t n, const double *values, int32_t n_q, const double *q, double *out) {
+    if (n_rep < 1 || n < 0 || (n > 0 && (!values || !out)) || !quantile_args_ok(n_q, q)) return EMSAR_HIP_ERR_ARG;
+    try {
+        std::vector<double> col((size_t)n_rep);
+        for (int64_t t = 0; t < n; t++) {
+            for (int32_t b = 0; b < n_rep; b++) col[(size_t)b] = values[(int64_t)b * n + t];
+            std::sort(col.begin(), col.end(), [](double a, double b) { return a < b || (b != b && a == a); });   // NaN last: a strict weak order
+            for (int32_t k = 0; k < n_q; k++) out[(int64_t)k * n + t] = emsar::quantile_sorted(col.data(), 1, n_rep, q[k]);
+        }
+    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+    return EMSAR_HIP_OK;
 }
 
 // ---- gene map -----------------------------------------------------------------------------------------------------------------

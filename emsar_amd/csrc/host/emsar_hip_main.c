@@ -21,6 +21,9 @@
  * sums of FPKM, iReadcount and TPM (emsar_hip_gene_sums; the map is read once, genes.c), which merge_gTPM.pl / merge_gReadcount.pl
  * read as they are; with --bootstrap also <prefix>.<i>.gbootstrap, the genes' bootstrap mean and sd from the same replicates
  * (emsar_hip_bootstrap_genes).  The other files are the same bytes with and without it.
+ * --bootstrap-quantiles q1,q2,.. (needs --bootstrap B, B <= 4096) adds percentile intervals: <prefix>.<i>.bootq holds, per transcript, the
+ * q-quantiles of FPKM and then of TPM over the same B replicates (emsar_hip_bootstrap_quantiles: q = 0.025,0.5,0.975 gives the 95 %
+ * percentile interval and the median), with --g2t also <prefix>.<i>.gbootq per gene.  The other files are the same bytes with and without it.
  * --subsample f1,f2,.. answers "was the sample sequenced deep enough": <prefix>.<i>.saturation holds, per transcript and fraction,
  * the mean and sd of FPKM (at the thinned depth) and TPM over --subsample-reps replicates in which every read is kept with
  * probability f (emsar_hip_subsample; seed --subsample-seed + i), with --g2t also <prefix>.<i>.gsaturation per gene.  The other
@@ -53,6 +56,7 @@ typedef struct {
     const char *stats_json;
     const char *rsh_cache;      /* NULL = off, "" = <rsh>.bin, else the path */
     int boot_n; uint64_t boot_seed;   /* --bootstrap B (0 = off), --bootstrap-seed: sample i uses seed + i */
+    int bq_n; double bq[64];          /* --bootstrap-quantiles q1,.. (0 = off) */
     int sub_nf, sub_reps; double sub_f[64]; uint64_t sub_seed;   /* --subsample f1,.. (0 = off), --subsample-reps, --subsample-seed: sample i uses seed + i */
     const char *g2t;                  /* --g2t FILE (NULL = off) */
     const emsar_genes *genes;         /* its gene map, read once by main() and shared read-only by the workers */
@@ -67,6 +71,7 @@ typedef struct {
     emsar_em_stats *stats; /* per sample */
     emsar_boot_stats *bstats; /* per sample (--bootstrap) */
     emsar_subsample_stats *sstats; /* per sample (--subsample) */
+    emsar_quantile_stats *qstats; /* per sample (--bootstrap-quantiles) */
     double *parse_s;
     double *model_s, *host_s;   /* per sample: model preparation, and all host work of run_sample outside the library calls */
     int *go;              /* start gate: the workers wait until main() knows how many of them exist */
@@ -225,8 +230,14 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
     if (cfg->boot_n > 0) {
         double *bm = (double *)malloc(T * 8), *bs = (double *)malloc(T * 8), *bt = (double *)malloc(T * 8);
         double *gb = G ? (double *)malloc(NG * 8 * 3) : NULL;
-        if (!bm || !bs || !bt || (G && !gb)) rc = EMSAR_HOST_ERR_OOM;
-        else if ((rc = G ? emsar_hip_bootstrap_genes(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, bm, bs, bt, NULL, gb, gb + NG, gb + 2 * NG,
+        /* --bootstrap-quantiles: [2][n_q][n_tx] FPKM then TPM quantiles, with --g2t also [2][n_q][n_genes] */
+        const size_t NQ = (size_t)cfg->bq_n;
+        double *bq = NQ ? (double *)malloc((T > 0 ? T : 1) * 8 * 2 * NQ) : NULL, *gq = NQ && G ? (double *)malloc((NG > 0 ? NG : 1) * 8 * 2 * NQ) : NULL;
+        if (!bm || !bs || !bt || (G && !gb) || (NQ && !bq) || (NQ && G && !gq)) rc = EMSAR_HOST_ERR_OOM;
+        else if ((rc = NQ ? emsar_hip_bootstrap_quantiles(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, cfg->bq_n, cfg->bq, bm, bs, bt, NULL, NULL,
+                                                          bq, bq + NQ * T, gb, G ? gb + NG : NULL, G ? gb + 2 * NG : NULL, gq, G ? gq + NQ * NG : NULL,
+                                                          &w->bstats[i], &w->qstats[i])
+                         : G ? emsar_hip_bootstrap_genes(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, bm, bs, bt, NULL, gb, gb + NG, gb + 2 * NG,
                                                      &w->bstats[i])
                          : emsar_hip_bootstrap(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, bm, bs, bt, NULL, &w->bstats[i])))
             fprintf(stderr, "alnfile[%d]: bootstrap: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
@@ -237,8 +248,16 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
                 snprintf(path, sizeof path, "%s/%s.%d.gbootstrap", cfg->outdir, cfg->prefix, i);
                 if ((rc = emsar_write_gbootstrap(path, G, gsums, gb, gb + NG, gsums + 2 * NG, gb + 2 * NG))) fprintf(stderr, "can't write %s\n", path);
             }
+            if (!rc && NQ) {
+                snprintf(path, sizeof path, "%s/%s.%d.bootq", cfg->outdir, cfg->prefix, i);
+                if ((rc = emsar_write_bootq(path, r, cfg->bq_n, cfg->bq, bq, bq + NQ * T))) fprintf(stderr, "can't write %s\n", path);
+                else if (G) {
+                    snprintf(path, sizeof path, "%s/%s.%d.gbootq", cfg->outdir, cfg->prefix, i);
+                    if ((rc = emsar_write_gbootq(path, G, cfg->bq_n, cfg->bq, gq, gq + NQ * NG))) fprintf(stderr, "can't write %s\n", path);
+                }
+            }
         }
-        free(bm); free(bs); free(bt); free(gb);
+        free(bm); free(bs); free(bt); free(gb); free(bq); free(gq);
         if (rc) goto done;
     }
     /* ---- depth subsampling (--subsample f1,f2,..): its own files ---- */
@@ -347,6 +366,9 @@ static void usage(const char *a0) {
             "      --bootstrap <B>       also write <outdir>/<prefix>.<i>.bootstrap: mean and sd of FPKM and sd of TPM over B Poisson\n"
             "                            bootstrap replicates of the sample (default 0 = off; .fpkm is the same either way)\n"
             "      --bootstrap-seed <n>  seed of the replicates' draws (default 1; sample i of -M uses n + i)\n"
+            "      --bootstrap-quantiles <q1,q2,..> with --bootstrap B (B <= 4096): also write <prefix>.<i>.bootq, per transcript the quantiles of\n"
+            "                            FPKM and of TPM over the replicates at each probability q in [0, 1] (at most 64; 0.025,0.5,0.975 = the\n"
+            "                            95 %% percentile interval and the median), and with --g2t <prefix>.<i>.gbootq per gene\n"
             "      --subsample <f1,f2,..> also write <prefix>.<i>.saturation: per fraction f in (0, 1] (at most 64) the mean and sd of FPKM and\n"
             "                            TPM over replicates that keep every read with probability f (with --g2t also .gsaturation per gene)\n"
             "      --subsample-reps <B>  replicates per fraction (default 10)\n"
@@ -376,6 +398,7 @@ int main(int argc, char **argv) {
         {"count-floor", required_argument, 0, 1004}, {"streaming-only", no_argument, 0, 1005}, {"rsh-cache", optional_argument, 0, 1006}, {"zero-cut", required_argument, 0, 1007}, {"abs-step", required_argument, 0, 1008}, {"devices", required_argument, 0, 1009}, {"device-collapse", no_argument, 0, 1010}, {"no-deterministic", no_argument, 0, 1011},
         {"bootstrap", required_argument, 0, 1012}, {"bootstrap-seed", required_argument, 0, 1013}, {"g2t", required_argument, 0, 1014},
         {"subsample", required_argument, 0, 1015}, {"subsample-reps", required_argument, 0, 1016}, {"subsample-seed", required_argument, 0, 1017},
+        {"bootstrap-quantiles", required_argument, 0, 1018},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
@@ -451,6 +474,21 @@ int main(int argc, char **argv) {
                 cfg.sub_seed = (uint64_t)v;
                 break;
             }
+            case 1018: {
+                const char *q = optarg;
+                cfg.bq_n = 0;
+                for (;;) {
+                    char *end; errno = 0;
+                    const double v = strtod(q, &end);
+                    if (end == q || (*end && *end != ',') || errno || !isfinite(v) || !(v >= 0.0 && v <= 1.0) || cfg.bq_n >= 64) {
+                        fprintf(stderr, "--bootstrap-quantiles wants a comma-separated list of 1 to 64 probabilities in [0, 1].\n"); return 1;
+                    }
+                    cfg.bq[cfg.bq_n++] = v;
+                    if (!*end) break;
+                    q = end + 1;
+                }
+                break;
+            }
             case 1009: {
                 const char *q = optarg;
                 while (*q && n_dev_map < 64) {
@@ -465,6 +503,9 @@ int main(int argc, char **argv) {
             }
             default: usage(argv[0]); return 1;
         }
+    }
+    if (cfg.bq_n > 0 && (cfg.boot_n < 1 || cfg.boot_n > 4096)) {
+        fprintf(stderr, "--bootstrap-quantiles needs --bootstrap B with 1 <= B <= 4096 replicates.\n"); return 1;
     }
     if (!cfg.rsh_path || optind + 2 >= argc) { usage(argv[0]); return 1; }
     if (emsar_set_strand(strand, cfg.ao.pe, &cfg.ao.strand)) { fprintf(stderr, "error: invalid strand type.\n"); return 1; }
@@ -557,17 +598,18 @@ int main(int argc, char **argv) {
     emsar_em_stats *stats = (emsar_em_stats *)calloc((size_t)n_list, sizeof(emsar_em_stats));
     emsar_boot_stats *bstats = (emsar_boot_stats *)calloc((size_t)n_list, sizeof(emsar_boot_stats));
     emsar_subsample_stats *sstats = (emsar_subsample_stats *)calloc((size_t)n_list, sizeof(emsar_subsample_stats));
+    emsar_quantile_stats *qstats = (emsar_quantile_stats *)calloc((size_t)n_list, sizeof(emsar_quantile_stats));
     double *parse_s = (double *)calloc((size_t)n_list, sizeof(double));
     double *model_s = (double *)calloc((size_t)n_list, sizeof(double)), *host_s = (double *)calloc((size_t)n_list, sizeof(double));
     worker_arg *wa = (worker_arg *)calloc((size_t)n_workers, sizeof(worker_arg));
     pthread_t *th = (pthread_t *)calloc((size_t)n_workers, sizeof(pthread_t));
-    if (!status || !stats || !bstats || !sstats || !parse_s || !model_s || !host_s || !wa || !th) { fprintf(stderr, "out of memory\n"); return 1; }
+    if (!status || !stats || !bstats || !sstats || !qstats || !parse_s || !model_s || !host_s || !wa || !th) { fprintf(stderr, "out of memory\n"); return 1; }
     t0 = now_s();
     /* Workers wait at a gate until their number is final: a thread that cannot be started must not leave the others
      * waiting for samples nobody will take (the EUMAcut hand-over is in sample order). */
     int go = 0, n_started = 1;
     for (int g = 0; g < n_workers; g++)
-        wa[g] = (worker_arg){&cfg, rsh, multisample ? dev_map[g] : device, n_workers, g, &mu, &cv, &next_model, &eumacut, status, stats, bstats, sstats, parse_s,
+        wa[g] = (worker_arg){&cfg, rsh, multisample ? dev_map[g] : device, n_workers, g, &mu, &cv, &next_model, &eumacut, status, stats, bstats, sstats, qstats, parse_s,
                              model_s, host_s, &go, cfg.ao, {NULL, PTHREAD_MUTEX_INITIALIZER}};
     for (int g = 1; g < n_workers; g++) {
         if (pthread_create(&th[g], NULL, worker_main, &wa[g]) != 0) { fprintf(stderr, "warning: worker %d could not be started, using %d\n", g, g); break; }
@@ -608,6 +650,9 @@ int main(int argc, char **argv) {
                             b->n_replicates, b->batch, b->replicates_unconverged, b->set_passes_max, (long long)b->draws, b->draw_ms, b->sets_ms,
                             b->stream_ms, b->reduce_ms, b->total_ms);
                 }
+                if (cfg.boot_n > 0 && cfg.bq_n > 0)
+                    fprintf(f, ", \"bootq_quantiles\": %d, \"bootq_held_bytes\": %lld, \"bootq_ms\": %.4f", qstats[i].n_quantiles,
+                            (long long)qstats[i].held_bytes, qstats[i].quantile_ms);
                 if (cfg.sub_nf > 0) {
                     const emsar_subsample_stats *b = &sstats[i];
                     fprintf(f, ", \"sub_fractions\": %d, \"sub_replicates\": %d, \"sub_batch\": %d, \"sub_replicates_unconverged\": %d, "
@@ -624,6 +669,6 @@ int main(int argc, char **argv) {
     emsar_rsh_free(rsh);
     emsar_genes_free(genes);
     for (int i = 0; i < n_list; i++) free(list[i]);
-    free(list); free(status); free(stats); free(bstats); free(sstats); free(parse_s); free(model_s); free(host_s); free(wa); free(th);
+    free(list); free(status); free(stats); free(bstats); free(sstats); free(qstats); free(parse_s); free(model_s); free(host_s); free(wa); free(th);
     return bad ? 1 : 0;
 }

@@ -156,6 +156,10 @@ int emsar_write_gfpkm(const char *path, const emsar_genes *g, const double *fpkm
 /* .gbootstrap (emsar-hip --g2t --bootstrap): the columns of .bootstrap per gene */
 int emsar_write_gbootstrap(const char *path, const emsar_genes *g, const double *fpkm, const double *boot_mean, const double *boot_sd,
                            const double *tpm, const double *boot_tpm_sd);
+/* .bootq / .gbootq (emsar-hip --bootstrap B --bootstrap-quantiles q1,..): name, then the quantiles of FPKM at each q, then of TPM at each
+ * q over the bootstrap replicates ([n_q][n_tx] / [n_q][n_genes] each), "%lf"; the header names the probabilities */
+int emsar_write_bootq(const char *path, const emsar_rsh *r, int n_q, const double *q, const double *fpkm_q, const double *tpm_q);
+int emsar_write_gbootq(const char *path, const emsar_genes *g, int n_q, const double *q, const double *fpkm_q, const double *tpm_q);
 /* .saturation (emsar-hip --subsample): a "#" line (fractions, replicates, seed, depth_mean per fraction), a header, then per
  * transcript its name, FPKM and TPM as in .fpkm and per fraction mean_FPKM sd_FPKM mean_TPM sd_TPM ([n_fractions][n_tx] each) */
 int emsar_write_saturation(const char *path, const emsar_rsh *r, const double *fpkm, const double *tpm, int n_fractions,

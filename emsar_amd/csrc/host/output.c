@@ -8,6 +8,10 @@
  *   .gfpkm              util/FPKM2gFPKM.pl's header byte for byte, rows "%s\t%lf\t%lf\t%d\t%lf\n" (the script prints Perl's
  *                       default number format; merge_gTPM.pl / merge_gReadcount.pl read either)
  *   .gbootstrap         the columns of .bootstrap per gene
+ * and the bootstrap quantiles' files (--bootstrap-quantiles):
+ *   .bootq              a header naming the probabilities (FPKM@q.. then TPM@q.., q as "%.17g"), then per transcript the quantiles of
+ *                       FPKM at each q and of TPM at each q over the bootstrap replicates, all "%lf"
+ *   .gbootq             the same per gene, in the order of .gfpkm
  * and the depth subsampling's files (--subsample):
  *   .saturation         "# fractions=.. replicates=.. seed=.. depth_mean=..", a header, then per transcript FPKM and TPM as in .fpkm and
  *                       per fraction mean_FPKM sd_FPKM mean_TPM sd_TPM, all "%lf"
@@ -67,6 +71,31 @@ int emsar_write_gbootstrap(const char *path, const emsar_genes *g, const double 
     for (int32_t k = 0; k < g->n_genes; k++)
         fprintf(f, "%s\t%lf\t%lf\t%lf\t%lf\t%lf\n", g->names[k], fpkm[k], boot_mean[k], boot_sd[k], tpm[k], boot_tpm_sd[k]);
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+/* the rows of .bootq / .gbootq: n names, fpkm_q and tpm_q = [n_q][n] */
+static int write_bootq(const char *path, const char *id, char **names, int64_t n, int n_q, const double *q, const double *fpkm_q, const double *tpm_q) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "%s", id);
+    for (int k = 0; k < n_q; k++) fprintf(f, "\tFPKM@%.17g", q[k]);
+    for (int k = 0; k < n_q; k++) fprintf(f, "\tTPM@%.17g", q[k]);
+    fprintf(f, "\n");
+    for (int64_t t = 0; t < n; t++) {
+        fprintf(f, "%s", names[t]);
+        for (int k = 0; k < n_q; k++) fprintf(f, "\t%lf", fpkm_q[(int64_t)k * n + t]);
+        for (int k = 0; k < n_q; k++) fprintf(f, "\t%lf", tpm_q[(int64_t)k * n + t]);
+        fprintf(f, "\n");
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+int emsar_write_bootq(const char *path, const emsar_rsh *r, int n_q, const double *q, const double *fpkm_q, const double *tpm_q) {
+    return write_bootq(path, "transcriptID", r->names, r->n_tx, n_q, q, fpkm_q, tpm_q);
+}
+
+int emsar_write_gbootq(const char *path, const emsar_genes *g, int n_q, const double *q, const double *fpkm_q, const double *tpm_q) {
+    return write_bootq(path, "geneID", g->names, g->n_genes, n_q, q, fpkm_q, tpm_q);
 }
 
 /* the rows of .saturation / .gsaturation: n names, per fraction ncol columns col[j] = [n_fractions][n] */

@@ -23,6 +23,7 @@ SYMBOLS = [
     "emsar_hip_set_deterministic", "emsar_hip_bootstrap", "emsar_hip_bootstrap_weights", "emsar_hip_bootstrap_draw_host",
     "emsar_hip_set_gene_map", "emsar_hip_gene_sums", "emsar_hip_bootstrap_genes",
     "emsar_hip_subsample", "emsar_hip_subsample_weights", "emsar_hip_subsample_draw_host",
+    "emsar_hip_bootstrap_quantiles", "emsar_hip_quantiles_host",
 ]
 
 
@@ -65,6 +66,13 @@ class SubsampleStats(C.Structure):
     _fields_ = [("n_fractions", C.c_int32), ("n_replicates", C.c_int32), ("batch", C.c_int32), ("replicates_unconverged", C.c_int32),
                 ("draws", C.c_int64), ("draw_ms", C.c_double), ("sets_ms", C.c_double), ("stream_ms", C.c_double), ("reduce_ms", C.c_double),
                 ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class QuantileStats(C.Structure):
+    _fields_ = [("n_quantiles", C.c_int32), ("reserved0", C.c_int32), ("held_bytes", C.c_int64), ("quantile_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -133,6 +141,9 @@ def load_library():
                                       f64p, f64p, f64p, C.POINTER(SubsampleStats)]
     L.emsar_hip_subsample_weights.argtypes = [vp, C.c_uint64, C.c_int32, C.c_double, i32p]
     L.emsar_hip_subsample_draw_host.argtypes = [C.c_uint64, C.c_int32, C.c_double, C.c_int64, i32p, i32p]
+    L.emsar_hip_bootstrap_quantiles.argtypes = [vp, C.POINTER(EmParams), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, f64p] + [f64p] * 12 + [
+        C.POINTER(BootStats), C.POINTER(QuantileStats)]
+    L.emsar_hip_quantiles_host.argtypes = [C.c_int32, C.c_int64, f64p, C.c_int32, f64p, f64p]
     _lib = L
     return L
 
@@ -192,6 +203,21 @@ def subsample_draw_host(seed, replicate, fraction, row_weight=None, n_rows=None)
     if rc != 0:
         raise EmsarHipError(rc, "subsample_draw_host")
     return out[:n]
+
+
+def quantiles_host(values, q):
+    """Host-only: the library's quantile definition (include/emsar_hip.h "bootstrap quantiles") over axis 0 of values [n_rep][n] (or
+    [n_rep]) for the probabilities q -> [n_q][n] (or [n_q]); no GPU needed, the same function the device evaluates."""
+    L = load_library()
+    v = _arr(values, np.float64)
+    one = v.ndim == 1
+    v = np.ascontiguousarray(v.reshape(v.shape[0], -1))
+    qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+    out = np.zeros((max(len(qa), 1), v.shape[1]))
+    rc = L.emsar_hip_quantiles_host(v.shape[0], v.shape[1], _p(v, C.c_double), len(qa), _p(qa, C.c_double), _p(out, C.c_double))
+    if rc != 0:
+        raise EmsarHipError(rc, "quantiles_host")
+    return out[:, 0] if one else out
 
 
 def layout_selfcheck_tiled(n_tx, row_ptr, col_idx, merge_rows=False):
@@ -317,6 +343,34 @@ class EmsarHip:
         k = self.n_genes
         return {"fpkm_mean": mean, "fpkm_sd": sd, "tpm_sd": tsd, "replicates": reps, "gene_fpkm_mean": gm[:k], "gene_fpkm_sd": gs[:k],
                 "gene_tpm_sd": gt[:k], "stats": st}
+
+    def bootstrap_quantiles(self, n, q, seed, first=0, want_replicates=False, want_genes=False, max_iter=100000, accel=1, tol=1e-10,
+                            abs_floor=1e-6, check_every=8, count_floor=0.0, set_mode=0, zero_cut=0.0, abs_step=0.0, newton_after=0):
+        """bootstrap() / bootstrap_genes() plus, per transcript (with want_genes: and per gene), the q-quantiles of FPKM and TPM over the
+        same replicates (definition: include/emsar_hip.h; n <= 4096).  Returns a dict: fpkm_mean, fpkm_sd, tpm_sd, replicates ([n][n_tx]
+        or None), replicate_sums ([n], the TPM denominators), fpkm_q, tpm_q ([n_q][n_tx]), with want_genes also gene_fpkm_mean,
+        gene_fpkm_sd, gene_tpm_sd ([n_genes]), gene_fpkm_q, gene_tpm_q ([n_q][n_genes]), stats, qstats."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        K, T, G = len(qa), self.n_tx, max(self.n_genes, 1)
+        Ka, na = max(K, 1), max(int(n), 1)
+        out = {k: np.zeros(T) for k in ("fpkm_mean", "fpkm_sd", "tpm_sd")}
+        out.update(fpkm_q=np.zeros((Ka, T)), tpm_q=np.zeros((Ka, T)), replicate_sums=np.zeros(na))
+        reps = np.zeros((n, T)) if (want_replicates and n > 0) else None
+        gene = {k: np.zeros(G) for k in ("gene_fpkm_mean", "gene_fpkm_sd", "gene_tpm_sd")} if want_genes else {}
+        if want_genes:
+            gene.update(gene_fpkm_q=np.zeros((Ka, G)), gene_tpm_q=np.zeros((Ka, G)))
+        st, qs = BootStats(), QuantileStats()
+        d = lambda a: _p(a, C.c_double)
+        self._chk(self._L.emsar_hip_bootstrap_quantiles(
+            self._h, C.byref(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(n), K, d(qa), d(out["fpkm_mean"]), d(out["fpkm_sd"]),
+            d(out["tpm_sd"]), d(reps), d(out["replicate_sums"]), d(out["fpkm_q"]), d(out["tpm_q"]), d(gene.get("gene_fpkm_mean")),
+            d(gene.get("gene_fpkm_sd")), d(gene.get("gene_tpm_sd")), d(gene.get("gene_fpkm_q")), d(gene.get("gene_tpm_q")),
+            C.byref(st), C.byref(qs)), "bootstrap_quantiles")
+        k = self.n_genes
+        out.update({key: (v[:, :k] if v.ndim == 2 else v[:k]) for key, v in gene.items()})
+        out.update(replicates=reps, stats=st, qstats=qs)
+        return out
 
     def bootstrap_weights(self, seed, replicate):
         """The drawn row weights of one bootstrap replicate (caller row order), drawn on the device."""

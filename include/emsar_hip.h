@@ -243,6 +243,44 @@ int emsar_hip_bootstrap_genes(emsar_hip_ctx *ctx, const emsar_em_params *p, uint
 int emsar_hip_bootstrap_draw_host(uint64_t seed, int32_t replicate, int64_t n_rows, const int32_t *row_weight /* NULL = 1 */,
                                   int32_t *w_out);
 
+/* ---- bootstrap quantiles: percentile intervals and medians over the replicates ---------------------------------------------------
+ * Definition (fixed, so that host and device agree bit for bit): for the order statistics x_(0) <= ... <= x_(B-1) of one transcript's
+ * (or gene's) B replicate values and a probability q in [0, 1],
+ *     h = q * (double)(B - 1),  i = (int64)floor(h),  g = h - (double)i,
+ *     result = x_(i) when g == 0 or i == B - 1, else x_(i) + g * (x_(i+1) - x_(i)),
+ * subtract, multiply and add rounded separately (no fused multiply-add) -- numpy's default "linear" method up to rounding.  Sorting
+ * does not round, so the result does not depend on the batch size, the layout, the numbering or the device; q = 0 is the minimum,
+ * q = 1 the maximum, q = 0.5 with odd B the middle value, and B = 1 gives the single value for every q.
+ *   bootstrap_quantiles  emsar_hip_bootstrap / emsar_hip_bootstrap_genes (same arguments, the same mean, sd and replicates bit for bit)
+ *                        that also keeps every replicate on the device -- theta_b, S_b = sum_t theta_b,t and, with gene outputs, the
+ *                        gene sums G_b -- and returns per transcript the q-quantiles of FPKM (theta_b) and of TPM_b = S_b > 0 ?
+ *                        theta_b * 1e6 / S_b : 0, [n_q][n_tx] each in the order of q, per gene those of G_b and of the gene TPM,
+ *                        [n_q][n_genes].  S_b of the quantiles is added up in the caller's transcript order (same reduction tree as the sd's
+ *                        S_b, which is added in the library's order: the two are the same bits unless the library numbered the
+ *                        transcripts itself), so no quantile depends on the library's numbering.  replicate_sums (may be NULL): that
+ *                        S_b, n_replicates values.  Gene outputs: all five NULL, or
+ *                        all five given after set_gene_map.
+ *                        Limits: 1 <= n_replicates <= 4096 (a column is sorted in a workgroup's LDS: 32 KiB of doubles), ERR_ARG
+ *                        above; the held replicates, 8 * n_replicates * (n_tx + 1 + n_genes) bytes (held_bytes), plus the quantile stage's
+ *                        own buffers (16 * n_q * (n_tx + n_genes) bytes and a few vectors) must fit half of the free device memory and
+ *                        are allocated first, else ERR_OOM before any replicate is drawn.
+ *                        ERR_ARG for n_q < 1, a q that is not finite or outside [0, 1], a gene output group only partly given, and
+ *                        as bootstrap; ERR_STATE before upload_sample and for gene outputs without a map; ERR_NUMERIC as solve.  The
+ *                        context is left as it was.  quantile_ms: device time of the quantile stage (HIP events).
+ *   quantiles_host       the same definition on the host, no HIP call: values [n_rep][n] -> out [n_q][n].  ERR_ARG for n_rep < 1,
+ *                        n_q < 1 or a q that is not finite or outside [0, 1]. */
+typedef struct { int32_t n_quantiles, reserved0; int64_t held_bytes; double quantile_ms; } emsar_quantile_stats;
+int emsar_hip_bootstrap_quantiles(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t first_replicate, int32_t n_replicates,
+                                  int32_t n_q, const double *q,
+                                  double *fpkm_mean, double *fpkm_sd, double *tpm_sd, double *replicates /* or NULL */,
+                                  double *replicate_sums /* n_replicates, or NULL: S_b as used for TPM */,
+                                  double *fpkm_q, double *tpm_q /* [n_q][n_tx] */,
+                                  double *gene_fpkm_mean, double *gene_fpkm_sd, double *gene_tpm_sd,
+                                  double *gene_fpkm_q, double *gene_tpm_q /* all five NULL, or all five given after set_gene_map */,
+                                  emsar_boot_stats *stats, emsar_quantile_stats *qstats);
+int emsar_hip_quantiles_host(int32_t n_rep, int64_t n, const double *values /* [n_rep][n] */,
+                             int32_t n_q, const double *q, double *out /* [n_q][n] */);
+
 /* ---- binomial depth subsampling: the estimates at a fraction of the reads ---------------------------------------------------
  * "Did we sequence deep enough": keeping every read of the sample with probability f, independently (what samtools view -s does),
  * gives row c the weight w_c ~ Binomial(R_c, f) (a read-level row has R = 1, a segment the sum of its reads: the same law).  For

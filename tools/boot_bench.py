@@ -1,6 +1,6 @@
 """Cost of the Poisson bootstrap (emsar_hip_bootstrap) on two workloads; prints one JSON object.
 
-    python tools/boot_bench.py [--reps 100] [--cfg3-scale 0.1] [--cfg3-reps 10] [--genes | --subsample] [--out FILE]
+    python tools/boot_bench.py [--reps 100] [--cfg3-scale 0.1] [--cfg3-reps 10] [--genes | --subsample | --quantiles] [--out FILE]
 
   segment   bench.py's time_to_mle problem (same seeds): one solve, then B replicates in one call -- device time per stage (HIP events),
             wall time, ms per replicate against one solve, the batch size and the slowest set's passes
@@ -12,6 +12,9 @@
   --subsample  instead: emsar_hip_subsample (fractions 0.1, 0.25, 0.5, 0.75, 1.0, B replicates each) next to one solve and next to
             emsar_hip_bootstrap with the same B on the same context, the calls alternated (two rounds); per fraction also a call of its
             own, which gives the time per replicate at that fraction
+  --quantiles  instead: emsar_hip_bootstrap_genes against emsar_hip_bootstrap_quantiles (q = 0.025, 0.5, 0.975, gene outputs included) on both
+            workloads, the generator's families as genes, same context and B, the calls alternated (two rounds) -- total_ms of both,
+            quantile_ms (device time of the quantile stage) and held_bytes
 Kernel-level times come from a separate `rocprofv3 --kernel-trace --stats` run of this script."""
 import argparse
 import json
@@ -75,6 +78,26 @@ def run_genes(dev, B, solve_kw, maps, seed=1, rounds=2):
     return out
 
 
+QUANTILES = [0.025, 0.5, 0.975]
+
+
+def run_quantiles(dev, B, solve_kw, gene_of_tx, n_genes, seed=1, rounds=2):
+    """bootstrap_genes vs bootstrap_quantiles over QUANTILES, the same B, alternated"""
+    dev.set_gene_map(gene_of_tx, n_genes)
+    dev.solve(**solve_kw)
+    dev.bootstrap_genes(min(B, 2), seed, **solve_kw)      # first calls: draw map, kernels loaded
+    dev.bootstrap_quantiles(min(B, 2), QUANTILES, seed, want_genes=True, **solve_kw)
+    out = {"replicates": B, "n_genes": int(n_genes), "q": QUANTILES, "bootstrap_genes": [], "bootstrap_quantiles": []}
+    for _ in range(rounds):
+        st = dev.bootstrap_genes(B, seed, **solve_kw)["stats"]
+        out["bootstrap_genes"].append({"total_ms": st.total_ms, "reduce_ms": st.reduce_ms, "batch": st.batch})
+        r = dev.bootstrap_quantiles(B, QUANTILES, seed, want_genes=True, **solve_kw)
+        st, qs = r["stats"], r["qstats"]
+        out["bootstrap_quantiles"].append({"total_ms": st.total_ms, "reduce_ms": st.reduce_ms, "batch": st.batch, "quantile_ms": qs.quantile_ms,
+                                           "held_bytes": qs.held_bytes})
+    return out
+
+
 SUB_FRACTIONS = [0.1, 0.25, 0.5, 0.75, 1.0]
 
 
@@ -128,6 +151,7 @@ def main():
     ap.add_argument("--skip-cfg3", action="store_true")
     ap.add_argument("--genes", action="store_true")
     ap.add_argument("--subsample", action="store_true")
+    ap.add_argument("--quantiles", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
     from emsar_amd import EmsarHip, synth
@@ -139,6 +163,10 @@ def main():
         seg_kw = dict(max_iter=200000, tol=1e-10)
         if a.subsample:
             out["segment"] = {"n_tx": int(n_tx), "segments": int(len(R)), **run_subsample(dev, a.reps, seg_kw)}
+        elif a.quantiles:
+            sizes = family_sizes(n_tx)
+            fam = np.repeat(np.arange(len(sizes)), sizes).astype(np.int32)
+            out["segment"] = {"n_tx": int(n_tx), "segments": int(len(R)), **run_quantiles(dev, a.reps, seg_kw, fam, int(fam.max()) + 1)}
         elif a.genes:
             sizes = family_sizes(n_tx)
             fam = np.repeat(np.arange(len(sizes)), sizes).astype(np.int32)
@@ -159,6 +187,9 @@ def main():
             info = {"scale": a.cfg3_scale, "reads": int(s["n_reads"]), "n_tx": int(s["n_tx"]), "segments": int(len(cw))}
             if a.subsample:
                 out["cfg3"] = {**info, **run_subsample(dev, a.cfg3_reps, kw)}
+            elif a.quantiles:
+                _, fam = synth.make_families(s["n_tx"], cfg["seed"])
+                out["cfg3"] = {**info, **run_quantiles(dev, a.cfg3_reps, kw, fam, int(fam.max()) + 1)}
             elif a.genes:
                 _, fam = synth.make_families(s["n_tx"], cfg["seed"])
                 out["cfg3"] = {**info, **run_genes(dev, a.cfg3_reps, kw, {"families": (fam, int(fam.max()) + 1)})}
