@@ -7,7 +7,8 @@
 // and compute_iEUMA / the TPM + iReadcount arithmetic of print_FPKMfinal (emsar_functions.c:3176-3232).
 //
 // One pass is HBM-bound integer streaming plus FP64 adds: ~2 flop per nonzero -- no MFMA.
-// This file: the context, the launch logic (launch_pass, enqueue_cycles, the set solver's driver) and the C ABI.
+// This file: the context, the launch logic (launch_pass, enqueue_cycles, the set solver's driver) and the C ABI of uploads and solves.
+// resample.hpp (same translation unit, included at the end): the resampling driver and its C ABI -- bootstrap, quantiles, subsampling, genes.
 // Kernels (one translation unit, included below):
 //   kernels_tiled.hpp     k_pass_tiled / k_pass_tiled_multi<2>   the hot ones: one workgroup per tile (or pair of tiles) of the
 //                         TILED layout, dictionary of theta/acc in LDS, 10-bit ids, per-slice transposed index
@@ -29,6 +30,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <numeric>
 #include <string>
 #include <vector>
 
@@ -156,6 +158,24 @@ namespace {
 inline void dfree(void *p) { if (p) (void)hipFree(p); }
 
 inline int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
+
+// a new device buffer (16 bytes at least) filled from the host
+inline hipError_t upload_new(void **dp, const void *src, size_t bytes) {
+    hipError_t e = hipMalloc(dp, std::max<size_t>(bytes, 16));
+    if (e == hipSuccess && bytes) e = hipMemcpy(*dp, src, bytes, hipMemcpyHostToDevice);
+    return e;
+}
+// per-solve state, cleared whatever the exit of a solve
+inline void clear_solve_state(emsar_hip_ctx *ctx) { ctx->count_floor = 0.0; ctx->zero_cut = 0.0; ctx->delta_mask = nullptr; }
+inline void free_row_weights(emsar_hip_ctx *ctx) { dfree(ctx->d_wgt); dfree(ctx->d_left_wgt); ctx->d_wgt = ctx->d_left_wgt = nullptr; }
+// deterministic mode's scales for a sample of `total` reads: no transcript is assigned more reads than the sample holds, |sum R log S| <= N * 745
+inline void set_fx_scales(emsar_hip_ctx *ctx, int64_t total) {
+    int e_mass = 0, e_ll = 0;
+    (void)std::frexp((double)total + 1.0, &e_mass);
+    (void)std::frexp(((double)total + 1.0) * 1024.0, &e_ll);
+    ctx->fx_mass = std::ldexp(1.0, 61 - e_mass);
+    ctx->fx_ll = std::ldexp(1.0, 61 - e_ll);
+}
 
 // The TILED layout may number the transcripts itself (renumber.hpp); every T-sized device vector is then in the LIBRARY's numbering and
 // the ABI maps: lib[new_of_old[t]] = caller[t].  Empty map = the caller's numbering.
@@ -423,6 +443,19 @@ int layout_weights(const emsar_hip_ctx *ctx, const WeightOf &weight_of, const do
     return EMSAR_HIP_OK;
 }
 
+// a LayoutWeights on the device: d_u of TILED, and for weighted rows d_wgt / d_left_wgt, allocated when absent
+int upload_layout_weights(emsar_hip_ctx *ctx, const LayoutWeights &LW, bool weighted) {
+    const bool tiled = ctx->layout == EMSAR_LAYOUT_TILED;
+    if (weighted) {
+        if (!ctx->d_wgt) HIPCHK(hipMalloc(&ctx->d_wgt, LW.w.size() * 4));
+        HIPCHK(hipMemcpy(ctx->d_wgt, LW.w.data(), LW.w.size() * 4, hipMemcpyHostToDevice));
+        if (tiled && !ctx->d_left_wgt) HIPCHK(hipMalloc(&ctx->d_left_wgt, LW.wl.size() * 4));
+        if (tiled) HIPCHK(hipMemcpy(ctx->d_left_wgt, LW.wl.data(), LW.wl.size() * 4, hipMemcpyHostToDevice));
+    }
+    if (tiled) HIPCHK(hipMemcpy(ctx->d_u, LW.u.data(), LW.u.size() * 8, hipMemcpyHostToDevice));
+    return EMSAR_HIP_OK;
+}
+
 // scatter a per-row value (original row order, host) to its columns: out[t] = sum_c m_ct val[c]
 int scatter_rows(emsar_hip_ctx *ctx, const double *val_host, double *d_out) {
     try {
@@ -487,24 +520,19 @@ int ensure_sets_impl(emsar_hip_ctx *ctx) {
         for (int32_t &t : S.g_tid) t = m[(size_t)t];
         for (int32_t &t : S.CL.g_tid) t = m[(size_t)t];
     }
-    auto up = [&](void **dp, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dp, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess && bytes) e = hipMemcpy(*dp, src, bytes, hipMemcpyHostToDevice);
-        return e;
-    };
-    HIPCHK(up((void **)&ctx->d_kind, S.kind.data(), S.kind.size()));
-    HIPCHK(up((void **)&ctx->d_usum, S.usum.data(), S.usum.size() * 8));
+    HIPCHK(upload_new((void **)&ctx->d_kind, S.kind.data(), S.kind.size()));
+    HIPCHK(upload_new((void **)&ctx->d_usum, S.usum.data(), S.usum.size() * 8));
     const int64_t n = S.n_resident();
     if (n > 0) {
-        HIPCHK(up((void **)&ctx->d_g_tid, S.g_tid.data(), S.g_tid.size() * 4));
-        HIPCHK(up((void **)&ctx->d_g_u, S.g_u.data(), S.g_u.size() * 8));
-        HIPCHK(up((void **)&ctx->d_row_w, S.row_w.data(), S.row_w.size() * 8));
-        HIPCHK(up((void **)&ctx->d_srp, S.rp.data(), S.rp.size() * 2));
-        HIPCHK(up((void **)&ctx->d_sent, S.ent.data(), S.ent.size() * 2));
-        HIPCHK(up((void **)&ctx->d_scp, S.cp.data(), S.cp.size() * 2));
-        HIPCHK(up((void **)&ctx->d_scrow, S.crow.data(), S.crow.size() * 2));
+        HIPCHK(upload_new((void **)&ctx->d_g_tid, S.g_tid.data(), S.g_tid.size() * 4));
+        HIPCHK(upload_new((void **)&ctx->d_g_u, S.g_u.data(), S.g_u.size() * 8));
+        HIPCHK(upload_new((void **)&ctx->d_row_w, S.row_w.data(), S.row_w.size() * 8));
+        HIPCHK(upload_new((void **)&ctx->d_srp, S.rp.data(), S.rp.size() * 2));
+        HIPCHK(upload_new((void **)&ctx->d_sent, S.ent.data(), S.ent.size() * 2));
+        HIPCHK(upload_new((void **)&ctx->d_scp, S.cp.data(), S.cp.size() * 2));
+        HIPCHK(upload_new((void **)&ctx->d_scrow, S.crow.data(), S.crow.size() * 2));
         for (int c = 0; c < emsar::kSetClasses; c++)
-            if (!S.desc[c].empty()) HIPCHK(up((void **)&ctx->d_sdesc[c], S.desc[c].data(), S.desc[c].size() * sizeof(emsar::SetDesc)));
+            if (!S.desc[c].empty()) HIPCHK(upload_new((void **)&ctx->d_sdesc[c], S.desc[c].data(), S.desc[c].size() * sizeof(emsar::SetDesc)));
         HIPCHK(hipMalloc(&ctx->d_sstat, (size_t)n * sizeof(SetStat)));
         HIPCHK(hipHostMalloc((void **)&ctx->h_sstat, (size_t)n * sizeof(SetStat), hipHostMallocDefault));
         ctx->n_sstat = n;
@@ -515,16 +543,16 @@ int ensure_sets_impl(emsar_hip_ctx *ctx) {
     const int64_t nc = S.n_cluster_sets();
     if (nc > 0) {
         auto &CL = S.CL;
-        HIPCHK(up((void **)&ctx->d_cdesc, CL.desc.data(), CL.desc.size() * sizeof(emsar::ClusterDesc)));
-        HIPCHK(up((void **)&ctx->d_cblk, CL.blk_set.data(), CL.blk_set.size() * 4));
-        HIPCHK(up((void **)&ctx->d_crp, CL.rp.data(), CL.rp.size() * 4));
-        HIPCHK(up((void **)&ctx->d_ccp, CL.cp.data(), CL.cp.size() * 4));
-        HIPCHK(up((void **)&ctx->d_cpart, CL.part.data(), CL.part.size() * 4));
-        HIPCHK(up((void **)&ctx->d_cent, CL.ent.data(), CL.ent.size() * 2));
-        HIPCHK(up((void **)&ctx->d_ccrow, CL.crow.data(), CL.crow.size() * 2));
-        HIPCHK(up((void **)&ctx->d_cg_tid, CL.g_tid.data(), CL.g_tid.size() * 4));
-        HIPCHK(up((void **)&ctx->d_cg_u, CL.g_u.data(), CL.g_u.size() * 8));
-        HIPCHK(up((void **)&ctx->d_crow_w, CL.row_w.data(), CL.row_w.size() * 8));
+        HIPCHK(upload_new((void **)&ctx->d_cdesc, CL.desc.data(), CL.desc.size() * sizeof(emsar::ClusterDesc)));
+        HIPCHK(upload_new((void **)&ctx->d_cblk, CL.blk_set.data(), CL.blk_set.size() * 4));
+        HIPCHK(upload_new((void **)&ctx->d_crp, CL.rp.data(), CL.rp.size() * 4));
+        HIPCHK(upload_new((void **)&ctx->d_ccp, CL.cp.data(), CL.cp.size() * 4));
+        HIPCHK(upload_new((void **)&ctx->d_cpart, CL.part.data(), CL.part.size() * 4));
+        HIPCHK(upload_new((void **)&ctx->d_cent, CL.ent.data(), CL.ent.size() * 2));
+        HIPCHK(upload_new((void **)&ctx->d_ccrow, CL.crow.data(), CL.crow.size() * 2));
+        HIPCHK(upload_new((void **)&ctx->d_cg_tid, CL.g_tid.data(), CL.g_tid.size() * 4));
+        HIPCHK(upload_new((void **)&ctx->d_cg_u, CL.g_u.data(), CL.g_u.size() * 8));
+        HIPCHK(upload_new((void **)&ctx->d_crow_w, CL.row_w.data(), CL.row_w.size() * 8));
         HIPCHK(hipMalloc(&ctx->d_cscratch, std::max<size_t>((size_t)CL.scratch_doubles, 2) * 8));
         HIPCHK(hipMalloc(&ctx->d_cbar, (size_t)nc * 2 * sizeof(unsigned)));
         HIPCHK(hipMalloc(&ctx->d_cstat, (size_t)nc * sizeof(ClusterStat)));
@@ -544,21 +572,33 @@ int ensure_sets_impl(emsar_hip_ctx *ctx) {
     return EMSAR_HIP_OK;
 }
 
+// The three size classes of the set solver are independent (disjoint sets, disjoint theta entries): the larger two run on side streams next to
+// the 64-thread class.  fork_side_streams: the first n_side side streams wait for ctx->stream; launch_set_classes: launch(class, threads,
+// stream) for every class that has sets, the big ones first (the fewest, the longest per pass), then ctx->stream waits for those side streams.
+int fork_side_streams(emsar_hip_ctx *ctx, int n_side) {
+    HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
+    for (int i = 0; i < n_side; i++) HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0));
+    return EMSAR_HIP_OK;
+}
+template <class Launch>
+int launch_set_classes(emsar_hip_ctx *ctx, int n_side, const Launch &launch) {
+    const hipStream_t st[emsar::kSetClasses] = {ctx->stream, ctx->side[0], ctx->side[1]};
+    for (int c = emsar::kSetClasses - 1; c >= 0; c--) if (!ctx->RS.desc[c].empty()) launch(c, emsar::kSetThreads[c], st[c]);
+    for (int i = 0; i < n_side; i++) {
+        HIPCHK(hipEventRecord(ctx->ev_join[i], ctx->side[i]));
+        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
+    }
+    HIPCHK(hipGetLastError());
+    return EMSAR_HIP_OK;
+}
+
 // closed-form transcripts and every LDS-resident set, written into theta (the streamed sets' entries are left alone)
 int solve_resident_sets(emsar_hip_ctx *ctx, const SetSolveParams &P, const SetSolveParams &Pcluster, double *theta) {
     const auto &S = ctx->RS;
     hipLaunchKernelGGL(k_closed_form, dim3(grid_for(ctx->n_tx, 256)), dim3(256), 0, ctx->stream, ctx->n_tx, ctx->d_kind, ctx->d_usum,
                        ctx->d_den, theta);
-    // The three size classes are independent (disjoint sets, disjoint theta entries): the larger two run on side streams
-    // next to the 64-thread class, so the solve lasts as long as the slowest class, not as long as their sum.
-    HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
     const size_t off[3] = {0, S.desc[0].size(), S.desc[0].size() + S.desc[1].size()};      // per-set results in class order
-#define LAUNCH_S(C, TH, ST)                                                                                                \
-    if (!S.desc[C].empty())                                                                                                \
-        hipLaunchKernelGGL(k_solve_sets<TH>, dim3((unsigned)S.desc[C].size()), dim3(TH), S.max_lds[C], ST,                   \
-                           ctx->d_sdesc[C], ctx->d_g_tid, ctx->d_g_u, ctx->d_row_w, ctx->d_srp, ctx->d_sent, ctx->d_scp,     \
-                           ctx->d_scrow, ctx->d_den, theta, ctx->d_sstat + off[C], P);
-    for (int i = 0; i < 3; i++) HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0));
+    if (const int rc = fork_side_streams(ctx, 3)) return rc;
     if (ctx->n_cstat > 0) {
         // The clusters, on a stream of their own.  Every workgroup of a launch must be resident at once (they wait for each other at
         // the cluster barriers): at most one workgroup per CU per launch -- each asks for most of a CU's LDS --, whole sets only.
@@ -582,16 +622,11 @@ int solve_resident_sets(emsar_hip_ctx *ctx, const SetSolveParams &P, const SetSo
         HIPCHK(hipStreamWaitEvent(ctx->side[1], ctx->ev_c1, 0));
         HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_c1, 0));
     }
-    LAUNCH_S(2, 512, ctx->side[1])      // the big ones first: they are the fewest and the longest per pass
-    LAUNCH_S(1, 256, ctx->side[0])
-    LAUNCH_S(0, 64, ctx->stream)
-#undef LAUNCH_S
-    for (int i = 0; i < 3; i++) {
-        HIPCHK(hipEventRecord(ctx->ev_join[i], ctx->side[i]));
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
-    }
-    HIPCHK(hipGetLastError());
-    return EMSAR_HIP_OK;
+    return launch_set_classes(ctx, 3, [&](int c, int threads, hipStream_t st) {
+        hipLaunchKernelGGL((c == 2 ? k_solve_sets<512> : c == 1 ? k_solve_sets<256> : k_solve_sets<64>), dim3((unsigned)S.desc[c].size()), dim3(threads),
+                           S.max_lds[c], st, ctx->d_sdesc[c], ctx->d_g_tid, ctx->d_g_u, ctx->d_row_w, ctx->d_srp, ctx->d_sent, ctx->d_scp,
+                           ctx->d_scrow, ctx->d_den, theta, ctx->d_sstat + off[c], P);
+    });
 }
 
 }  // namespace
@@ -645,7 +680,6 @@ int emsar_hip_create(emsar_hip_ctx **out, int device_id) {
     if (hipMalloc(&ctx->d_sqpart, 4 * kSqPart * sizeof(double)) != hipSuccess) return fail(EMSAR_HIP_ERR_OOM);
     if (hipMemset(ctx->d_sqpart, 0, 4 * kSqPart * sizeof(double)) != hipSuccess) return fail(EMSAR_HIP_ERR_HIP);
     if (hipHostMalloc((void **)&ctx->h_scal, sizeof(Scal), hipHostMallocDefault) != hipSuccess) return fail(EMSAR_HIP_ERR_OOM);
-    // both pass kernels may need more than the default dynamic-LDS limit
     *out = ctx;
     return EMSAR_HIP_OK;
 }
@@ -718,25 +752,20 @@ int emsar_hip_upload_structure(emsar_hip_ctx *ctx, int64_t n_rows, int32_t n_tx,
             if (brc != 0) { ctx->err = "TILED layout builder: code " + std::to_string(brc); return EMSAR_HIP_ERR_ARG; }
             if (dbg) fprintf(stderr, "upload_structure: layout built after %.0f ms\n", since(tu0));
             ctx->n_tiles = (int64_t)L.tiles.size(); ctx->n_slots = L.n_slots(); ctx->n_left = (int64_t)L.left_row.size();
-            auto up = [&](void **dp, const void *src, size_t bytes) -> hipError_t {
-                hipError_t e = hipMalloc(dp, std::max<size_t>(bytes, 16));
-                if (e == hipSuccess && bytes) e = hipMemcpy(*dp, src, bytes, hipMemcpyHostToDevice);
-                return e;
-            };
-            HIPCHK(up((void **)&ctx->d_tiles, L.tiles.data(), L.tiles.size() * sizeof(Tile)));
-            HIPCHK(up((void **)&ctx->d_units, L.unit_first.data(), L.unit_first.size() * 4));
+            HIPCHK(upload_new((void **)&ctx->d_tiles, L.tiles.data(), L.tiles.size() * sizeof(Tile)));
+            HIPCHK(upload_new((void **)&ctx->d_units, L.unit_first.data(), L.unit_first.size() * 4));
             ctx->n_units = L.unit_first.empty() ? 0 : (int64_t)L.unit_first.size() - 1;
             {
                 emsar::UnitTables U;
                 emsar::build_unit_tables(L, U);
                 ctx->unit_stride = U.stride;
-                HIPCHK(up((void **)&ctx->d_utiles, U.utiles.data(), U.utiles.size() * sizeof(Tile)));
+                HIPCHK(upload_new((void **)&ctx->d_utiles, U.utiles.data(), U.utiles.size() * sizeof(Tile)));
             }
-            HIPCHK(up((void **)&ctx->d_fwd, L.fwd.data(), L.fwd.size() * 4));
-            HIPCHK(up((void **)&ctx->d_bwd, L.bwd.data(), L.bwd.size() * 4));
-            HIPCHK(up((void **)&ctx->d_far, L.far_tid.data(), L.far_tid.size() * 4));
-            HIPCHK(up((void **)&ctx->d_left_ptr, L.left_ptr.data(), L.left_ptr.size() * 8));
-            HIPCHK(up((void **)&ctx->d_left_col, L.left_col.data(), L.left_col.size() * 4));
+            HIPCHK(upload_new((void **)&ctx->d_fwd, L.fwd.data(), L.fwd.size() * 4));
+            HIPCHK(upload_new((void **)&ctx->d_bwd, L.bwd.data(), L.bwd.size() * 4));
+            HIPCHK(upload_new((void **)&ctx->d_far, L.far_tid.data(), L.far_tid.size() * 4));
+            HIPCHK(upload_new((void **)&ctx->d_left_ptr, L.left_ptr.data(), L.left_ptr.size() * 8));
+            HIPCHK(upload_new((void **)&ctx->d_left_col, L.left_col.data(), L.left_col.size() * 4));
             HIPCHK(hipMalloc(&ctx->d_u, T * 8));
             HIPCHK(hipMemset(ctx->d_u, 0, T * 8));
             ctx->bytes_stored = (int64_t)L.fwd.size() * 4 + (int64_t)L.bwd.size() * 4 + (int64_t)L.far_tid.size() * 4 +
@@ -812,7 +841,7 @@ int emsar_hip_upload_sample(emsar_hip_ctx *ctx, const int32_t *row_weight, const
     // a row counts w = R (or 1) when it is inside the likelihood (E != 0), else 0
     ctx->weighted = (row_weight != nullptr) || (row_E != nullptr) || (ctx->layout == EMSAR_LAYOUT_TILED && ctx->TL.merged);
     ctx->loglik_const = 0.0;
-    dfree(ctx->d_wgt); ctx->d_wgt = nullptr;
+    free_row_weights(ctx);
     auto weight_of = [&](int64_t r) -> int32_t {
         int32_t x = row_weight ? row_weight[r] : 1;
         if (row_E && row_E[r] == 0.0) x = 0;
@@ -823,32 +852,14 @@ int emsar_hip_upload_sample(emsar_hip_ctx *ctx, const int32_t *row_weight, const
         ctx->h_wgt.resize((size_t)n_rows);
         int64_t total_w = 0;
         for (int64_t r = 0; r < n_rows; r++) { const int32_t x = weight_of(r); ctx->h_wgt[(size_t)r] = x; total_w += x; }
-        // deterministic mode: no transcript is assigned more reads than the sample holds, |sum R log S| <= N * 745
-        int e_mass = 0, e_ll = 0;
-        (void)std::frexp((double)total_w + 1.0, &e_mass);
-        (void)std::frexp(((double)total_w + 1.0) * 1024.0, &e_ll);
-        ctx->fx_mass = std::ldexp(1.0, 61 - e_mass);
-        ctx->fx_ll = std::ldexp(1.0, 61 - e_ll);
+        set_fx_scales(ctx, total_w);
     } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
     {
         LayoutWeights LW;
         try {
-            const int rc = layout_weights(ctx, weight_of, row_E, ctx->weighted, LW, ctx->loglik_const);
-            if (rc) return rc;
+            int rc = layout_weights(ctx, weight_of, row_E, ctx->weighted, LW, ctx->loglik_const);
+            if (rc || (rc = upload_layout_weights(ctx, LW, ctx->weighted))) return rc;
         } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-        if (ctx->layout == EMSAR_LAYOUT_TILED) {
-            dfree(ctx->d_left_wgt); ctx->d_left_wgt = nullptr;
-            HIPCHK(hipMemcpy(ctx->d_u, LW.u.data(), LW.u.size() * 8, hipMemcpyHostToDevice));
-            if (ctx->weighted) {
-                HIPCHK(hipMalloc(&ctx->d_wgt, LW.w.size() * 4));
-                HIPCHK(hipMemcpy(ctx->d_wgt, LW.w.data(), LW.w.size() * 4, hipMemcpyHostToDevice));
-                HIPCHK(hipMalloc(&ctx->d_left_wgt, LW.wl.size() * 4));
-                HIPCHK(hipMemcpy(ctx->d_left_wgt, LW.wl.data(), LW.wl.size() * 4, hipMemcpyHostToDevice));
-            }
-        } else if (ctx->weighted) {
-            HIPCHK(hipMalloc(&ctx->d_wgt, LW.w.size() * 4));
-            HIPCHK(hipMemcpy(ctx->d_wgt, LW.w.data(), LW.w.size() * 4, hipMemcpyHostToDevice));
-        }
     }
     if (den) {
         std::vector<double> tmp;
@@ -943,7 +954,7 @@ int emsar_hip_solve(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpkm_
     if (!ctx || !fpkm_out) return EMSAR_HIP_ERR_ARG;
     if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
     const int rc = solve_impl(ctx, pp, fpkm_out, stats);
-    ctx->count_floor = 0.0; ctx->zero_cut = 0.0; ctx->delta_mask = nullptr;      // per-solve state, whatever the exit
+    clear_solve_state(ctx);
     return rc;
 }
 static int solve_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpkm_out, emsar_em_stats *stats) {
@@ -1084,698 +1095,6 @@ static int solve_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpk
             if (ctx->n_cstat > 0) { float mc = 0; HIPCHK(hipEventElapsedTime(&mc, ctx->ev_c0, ctx->ev_c1)); stats->cluster_kernel_ms = mc; }
         }
     }
-    return EMSAR_HIP_OK;
-}
-
-// ---- bootstrap --------------------------------------------------------------------------------------------------------------
-// The sample's row weights in caller order on the device (the draws' R) and, for the set solver, the draw map: build_sets run again
-// on the same weights with the map asked for -- the same code that filled row_w / usum, so the same sets, merged rows and slots.
-static int boot_prepare(emsar_hip_ctx *ctx, bool want_slot) {
-    const size_t n = (size_t)std::max<int64_t>(ctx->n_rows, 1);
-    if (!ctx->d_boot_R) {
-        HIPCHK(hipMalloc(&ctx->d_boot_R, n * 4));
-        if (ctx->n_rows) HIPCHK(hipMemcpy(ctx->d_boot_R, ctx->h_wgt.data(), (size_t)ctx->n_rows * 4, hipMemcpyHostToDevice));
-    }
-    if (!want_slot || ctx->boot_slot_ready) return EMSAR_HIP_OK;
-    try {
-        emsar::ResidentSets S;
-        std::vector<int64_t> slot;
-        emsar::build_sets(ctx->n_rows, ctx->n_tx, ctx->h_row_ptr.data(), ctx->h_col.data(), ctx->h_wgt.data(), S, &slot);
-        const int64_t n_rw = (int64_t)S.row_w.size();
-        // the resident records on the device are those of ensure_sets: same input, same builder
-        size_t rw_dev = 0;
-        for (int c = 0; c < emsar::kSetClasses; c++) for (const auto &d : S.desc[c]) rw_dev += d.n_r;
-        if (rw_dev != (size_t)n_rw || S.n_resident() != ctx->RS.n_resident()) { ctx->err = "bootstrap: draw map does not match the sets"; return EMSAR_HIP_ERR_HIP; }
-        const auto &m = tid_map(ctx);
-        const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !m.empty();
-        for (auto &v : slot)
-            if (v <= -2) { const int64_t t = -2 - v; v = n_rw + (remap ? m[(size_t)t] : t); }   // usum entry, library numbering
-        HIPCHK(hipMalloc(&ctx->d_boot_slot, n * 8));
-        if (ctx->n_rows) HIPCHK(hipMemcpy(ctx->d_boot_slot, slot.data(), (size_t)ctx->n_rows * 8, hipMemcpyHostToDevice));
-        ctx->boot_n_rw = n_rw;
-    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    ctx->boot_slot_ready = true;
-    return EMSAR_HIP_OK;
-}
-
-// Swap per-row weights x (caller order) into the streaming layout, as upload_sample would place them (den and E unchanged), with the
-// deterministic mode's fixed-point scales taken from their own total.  x = the sample's own weights (h_wgt) restores the sample.
-static int boot_stream_weights(emsar_hip_ctx *ctx, const int32_t *x) {
-    LayoutWeights LW;
-    double llc = 0.0;
-    int64_t total = 0;
-    try {
-        const int rc = layout_weights(ctx, [&](int64_t r) { return x[r]; }, nullptr, true, LW, llc);
-        if (rc) return rc;
-    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    for (int64_t r = 0; r < ctx->n_rows; r++) total += x[r];
-    int e_mass = 0, e_ll = 0;
-    (void)std::frexp((double)total + 1.0, &e_mass);
-    (void)std::frexp(((double)total + 1.0) * 1024.0, &e_ll);
-    ctx->fx_mass = std::ldexp(1.0, 61 - e_mass);
-    ctx->fx_ll = std::ldexp(1.0, 61 - e_ll);
-    if (!ctx->d_wgt) HIPCHK(hipMalloc(&ctx->d_wgt, LW.w.size() * 4));
-    HIPCHK(hipMemcpy(ctx->d_wgt, LW.w.data(), LW.w.size() * 4, hipMemcpyHostToDevice));
-    if (ctx->layout == EMSAR_LAYOUT_TILED) {
-        if (!ctx->d_left_wgt) HIPCHK(hipMalloc(&ctx->d_left_wgt, LW.wl.size() * 4));
-        HIPCHK(hipMemcpy(ctx->d_left_wgt, LW.wl.data(), LW.wl.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(ctx->d_u, LW.u.data(), LW.u.size() * 8, hipMemcpyHostToDevice));
-    }
-    ctx->weighted = true;
-    return EMSAR_HIP_OK;
-}
-
-// what a bootstrap call changes in the context, put back whatever the exit
-struct BootRestore {
-    emsar_hip_ctx *ctx;
-    bool weighted, swapped = false;
-    double fx_mass, fx_ll;
-    double *d_th0 = nullptr;               // the current point before the call
-    std::vector<void *> bufs;              // device buffers of the call
-    int rc = EMSAR_HIP_OK;
-    explicit BootRestore(emsar_hip_ctx *c) : ctx(c), weighted(c->weighted), fx_mass(c->fx_mass), fx_ll(c->fx_ll) {}
-    ~BootRestore() {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (swapped) {
-            rc = boot_stream_weights(ctx, ctx->h_wgt.data());
-            if (!weighted) {
-                dfree(ctx->d_wgt); ctx->d_wgt = nullptr;
-                if (ctx->layout == EMSAR_LAYOUT_TILED) { dfree(ctx->d_left_wgt); ctx->d_left_wgt = nullptr; }
-            }
-            ctx->weighted = weighted;
-        }
-        ctx->fx_mass = fx_mass; ctx->fx_ll = fx_ll;
-        ctx->count_floor = 0.0; ctx->zero_cut = 0.0; ctx->delta_mask = nullptr;
-        if (d_th0) {
-            (void)hipMemcpy(ctx->d_th[0], d_th0, (size_t)ctx->n_tx * 8, hipMemcpyDeviceToDevice);
-            dfree(d_th0);
-        }
-        for (void *p : bufs) dfree(p);
-    }
-    hipError_t alloc(void **p, size_t bytes) {
-        hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess) bufs.push_back(*p);
-        return e;
-    }
-};
-
-// Gene sums of ncol (<= 65535) rows x[ncol][n_tx] in library order into out[ncol][n_genes], on the context's stream; part holds
-// ncol * n_gene_chunks doubles (may be null when no gene has more than one chunk).
-static int launch_gene_sums(emsar_hip_ctx *ctx, const double *x, int64_t ncol, double *out, double *part) {
-    if (ctx->n_gene_chunks > 0)
-        hipLaunchKernelGGL(k_gene_sums, dim3((unsigned)grid_for(ctx->n_gene_chunks, 256), (unsigned)ncol), dim3(256), 0, ctx->stream,
-                           ctx->n_gene_chunks, ctx->d_chunk_beg, ctx->d_chunk_out, ctx->d_gene_tx, x, (int64_t)ctx->n_tx, out,
-                           (int64_t)ctx->n_genes, part);
-    if (ctx->n_gene_multi > 0)
-        hipLaunchKernelGGL(k_gene_finish, dim3((unsigned)grid_for(ctx->n_gene_multi, 256), (unsigned)ncol), dim3(256), 0, ctx->stream,
-                           ctx->n_gene_multi, ctx->d_gene_multi, part, ctx->n_gene_chunks, out, (int64_t)ctx->n_genes);
-    HIPCHK(hipGetLastError());
-    return EMSAR_HIP_OK;
-}
-
-// What a call draws and where its results go.  fractions null: the Poisson bootstrap, one round.  Else the depth subsampling: one round
-// per fraction f_k with w_c ~ Binomial(R_c, f_k), every replicate scaled to its own depth, the outputs of round k at [k][...].
-// Outputs that are null are not returned; gene_mean non-null asks for the gene statistics (all null = none).
-struct BootPlan {
-    const double *fractions = nullptr;
-    int32_t n_fractions = 1;
-    double *fpkm_mean = nullptr, *fpkm_sd = nullptr, *tpm_mean = nullptr, *tpm_sd = nullptr, *replicates = nullptr;
-    double *gene_mean = nullptr, *gene_sd = nullptr, *gene_tpm_mean = nullptr, *gene_tpm_sd = nullptr;
-    double *depth_mean = nullptr;        // subsampling: mean over the replicates of N_b = sum_c w_c, per fraction
-    // quantiles (bootstrap only, n_q > 0): every replicate's theta, S_b and gene sums stay on the device for k_boot_quantiles
-    int32_t n_q = 0;
-    const double *q = nullptr;
-    double *fpkm_q = nullptr, *tpm_q = nullptr, *gene_fpkm_q = nullptr, *gene_tpm_q = nullptr;     // [n_q][n_tx], [n_q][n_genes]
-    double *replicate_sums = nullptr;    // [n_rep] S_b
-};
-struct BootTimes {
-    int32_t batch = 0, unconverged = 0, passes_max = 0;
-    int64_t draws = 0;
-    double draw_ms = 0, sets_ms = 0, stream_ms = 0, reduce_ms = 0, total_ms = 0;
-    int64_t held_bytes = 0;
-    double quantile_ms = 0;
-};
-
-static int bootstrap_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_t seed, int32_t first, int32_t n_rep, const BootPlan &plan,
-                          BootTimes *stats) {
-    const bool genes = plan.gene_mean != nullptr, binomial = plan.fractions != nullptr;
-    const auto tw0 = std::chrono::steady_clock::now();
-    emsar_em_params p = solve_params(pp);
-    if (!(p.count_floor >= 0.0) || (p.set_mode != 0 && p.set_mode != 1)) return EMSAR_HIP_ERR_ARG;
-    HIPCHK(hipSetDevice(ctx->device));
-    int rc;
-    BootRestore guard(ctx);
-    // quantiles: all n_rep replicates are held -- theta, S_b and the gene sums -- and, with the quantile stage's own buffers, must fit
-    // half of the free device memory; they are allocated here, before anything is launched
-    const bool hold = plan.n_q > 0;
-    const int64_t held_bytes = hold ? 8 * (int64_t)n_rep * ((int64_t)ctx->n_tx + 1 + (genes ? ctx->n_genes : 0)) : 0;
-    double *d_thb0 = nullptr, *d_sums0 = nullptr, *d_gsum0 = nullptr;       // [batch or n_rep][n_tx], [..], [..][n_genes]
-    double *d_q = nullptr, *d_qout = nullptr, *d_qsums = nullptr;           // [n_q], [2][n_q][n_tx] then [2][n_q][n_genes], [n_rep]
-    int32_t *d_libof = nullptr;                                             // caller tid -> library index, null = the same
-    if (hold) {
-        const int64_t T = ctx->n_tx, G = genes ? ctx->n_genes : 0, nq = plan.n_q;
-        const auto &m = tid_map(ctx);
-        const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !m.empty();
-        const int64_t need = held_bytes + 8 * (int64_t)n_rep + 8 * nq + 16 * nq * (T + G) + (remap ? 4 * T : 0);
-        size_t hfree = 0, htotal = 0;
-        if (hipMemGetInfo(&hfree, &htotal) != hipSuccess) hfree = (size_t)1 << 30;
-        if ((uint64_t)need > (uint64_t)(hfree / 2)) { ctx->err = "bootstrap quantiles: the replicates do not fit half of the free device memory"; return EMSAR_HIP_ERR_OOM; }
-        if (guard.alloc((void **)&d_thb0, (size_t)(n_rep * T) * 8) != hipSuccess || guard.alloc((void **)&d_sums0, (size_t)n_rep * 8) != hipSuccess ||
-            (genes && guard.alloc((void **)&d_gsum0, (size_t)(n_rep * G) * 8) != hipSuccess) || guard.alloc((void **)&d_q, (size_t)nq * 8) != hipSuccess ||
-            guard.alloc((void **)&d_qout, (size_t)(2 * nq * (T + G)) * 8) != hipSuccess || guard.alloc((void **)&d_qsums, (size_t)n_rep * 8) != hipSuccess ||
-            (remap && guard.alloc((void **)&d_libof, (size_t)T * 4) != hipSuccess)) {
-            (void)hipGetLastError();
-            ctx->err = "bootstrap quantiles: device allocation of the held replicates failed";
-            return EMSAR_HIP_ERR_OOM;
-        }
-        HIPCHK(hipMemcpy(d_q, plan.q, (size_t)nq * 8, hipMemcpyHostToDevice));
-        if (remap) HIPCHK(hipMemcpy(d_libof, m.data(), (size_t)T * 4, hipMemcpyHostToDevice));
-    }
-    bool use_sets = p.set_mode == 0;
-    if (use_sets && (rc = ensure_sets(ctx))) return rc;
-    if (use_sets && ctx->RS.giant) use_sets = false;
-    // the streaming passes solve what the set solver does not cover: everything, the streamed sets, the cluster sets
-    const bool need_stream = !use_sets || ctx->RS.n_streamed_sets > 0 || ctx->n_cstat > 0;
-    if ((rc = boot_prepare(ctx, use_sets))) return rc;
-    const int n = ctx->n_tx;
-    const int64_t n_rows = ctx->n_rows;
-    const int64_t n_rw = use_sets ? ctx->boot_n_rw : 0, slot_stride = n_rw + n;
-    const auto &S = ctx->RS;
-    const int64_t n_sets = use_sets ? S.n_resident() : 0;
-    int64_t n_gu = 0;
-    if (use_sets) for (int c = 0; c < emsar::kSetClasses; c++) for (const auto &d : S.desc[c]) n_gu += d.n_t;
-    // replicates per batch: what fits a quarter of the free device memory (at most 2 GiB), EMSAR_HIP_BOOT_BATCH overrides
-    const int64_t ng = genes ? ctx->n_genes : 0, n_gchunk = genes && ctx->n_gene_multi > 0 ? ctx->n_gene_chunks : 0;
-    // (a quantile call's theta, S_b and gene sums live in the held buffers, allocated above: not part of a batch, and mfree is what they left)
-    const int64_t per_rep = 8 * (slot_stride + n_gu + (hold ? 0 : n + 1 + ng) + n_gchunk) + (need_stream ? 4 * n_rows : 0) + (int64_t)sizeof(SetStat) * n_sets;
-    size_t mfree = 0, mtotal = 0;
-    if (hipMemGetInfo(&mfree, &mtotal) != hipSuccess) mfree = (size_t)1 << 30;
-    const int64_t budget = std::min<int64_t>((int64_t)(mfree / 4), (int64_t)2 << 30);
-    int64_t batch = std::max<int64_t>(1, budget / std::max<int64_t>(per_rep, 1));
-    if (const char *e = getenv("EMSAR_HIP_BOOT_BATCH")) { if (atoi(e) >= 1) batch = atoi(e); }
-    batch = std::min<int64_t>(std::min<int64_t>(batch, n_rep), 65535);
-    double *d_slots = nullptr, *d_gu = nullptr, *d_acc4 = nullptr;
-    int32_t *d_wb = nullptr;
-    SetStat *d_bstat = nullptr;
-    HIPCHK(guard.alloc((void **)&d_slots, (size_t)(batch * slot_stride) * 8));
-    HIPCHK(guard.alloc((void **)&d_gu, (size_t)(batch * n_gu) * 8));
-    // (a quantile call keeps all n_rep replicates: a batch then writes its rows of the held buffers instead of a buffer of its own)
-    if (!hold) {
-        HIPCHK(guard.alloc((void **)&d_thb0, (size_t)(batch * n) * 8));
-        HIPCHK(guard.alloc((void **)&d_sums0, (size_t)batch * 8));
-    }
-    HIPCHK(guard.alloc((void **)&d_acc4, (size_t)4 * n * 8));
-    double *d_gpart = nullptr, *d_gacc4 = nullptr;                          // [batch][n_gene_chunks], [4][n_genes]
-    if (genes) {
-        if (!hold) HIPCHK(guard.alloc((void **)&d_gsum0, (size_t)(batch * ng) * 8));
-        if (n_gchunk) HIPCHK(guard.alloc((void **)&d_gpart, (size_t)(batch * n_gchunk) * 8));
-        HIPCHK(guard.alloc((void **)&d_gacc4, (size_t)4 * ng * 8));
-    }
-    // subsampling: the drawn total N_b of every replicate of the batch, and the total N_R of the rows that are drawn
-    long long *d_ndrawn = nullptr;
-    std::vector<long long> h_ndrawn(binomial ? (size_t)batch : 0);
-    double n_full = 0.0;
-    if (binomial) {
-        HIPCHK(guard.alloc((void **)&d_ndrawn, (size_t)batch * 8));
-        int64_t tot = 0;
-        for (int64_t r = 0; r < n_rows; r++) tot += ctx->h_wgt[(size_t)r];
-        n_full = (double)tot;
-    }
-    if (need_stream) HIPCHK(guard.alloc((void **)&d_wb, (size_t)(batch * n_rows) * 4));
-    if (n_sets) HIPCHK(guard.alloc((void **)&d_bstat, (size_t)(batch * n_sets) * sizeof(SetStat)));
-    HIPCHK(hipMalloc(&guard.d_th0, std::max<size_t>((size_t)n, 1) * 8));
-    HIPCHK(hipMemcpyAsync(guard.d_th0, ctx->d_th[0], (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    hipEvent_t e[2] = {nullptr, nullptr};
-    struct EvFree { hipEvent_t *e; ~EvFree() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evfree{e};
-    HIPCHK(hipEventCreate(&e[0])); HIPCHK(hipEventCreate(&e[1]));
-    auto lap = [&](double &acc) -> int { float ms = 0; HIPCHK(hipEventRecord(e[1], ctx->stream)); HIPCHK(hipEventSynchronize(e[1]));
-                                         HIPCHK(hipEventElapsedTime(&ms, e[0], e[1])); acc += ms; return EMSAR_HIP_OK; };
-    double draw_ms = 0, sets_ms = 0, stream_ms = 0, reduce_ms = 0, quantile_ms = 0;
-    int32_t unconverged = 0, passes_max = 0;
-    const SetSolveParams P = set_params(p);
-    if (n_sets) {
-        HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets_boot<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[0]));
-        HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets_boot<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[1]));
-        HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets_boot<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[2]));
-    }
-    std::vector<int32_t> h_wb(need_stream ? (size_t)(batch * n_rows) : 0);
-    std::vector<double> h_th((size_t)std::max(n, 1));
-    std::vector<SetStat> h_bstat((size_t)(batch * n_sets));
-    const unsigned gn = (unsigned)grid_for(n, 256);
-    for (int32_t fk = 0; fk < plan.n_fractions; fk++) {
-        const double frac = binomial ? plan.fractions[fk] : 1.0;
-        double *const replicates = plan.replicates ? plan.replicates + (int64_t)fk * n_rep * n : nullptr;
-        long long depth_sum = 0;
-        HIPCHK(hipMemsetAsync(d_acc4, 0, (size_t)4 * n * 8, ctx->stream));
-        if (genes) HIPCHK(hipMemsetAsync(d_gacc4, 0, (size_t)4 * ng * 8, ctx->stream));
-        for (int64_t done = 0; done < n_rep; ) {
-            const int64_t nb = std::min<int64_t>(batch, n_rep - done);
-            std::vector<char> unconv((size_t)nb, 0);      // replicates of the batch with a part that hit max_iter
-            // the batch's theta, S_b and gene sums: the batch buffers, or the batch's rows of the held ones
-            double *const d_thb = d_thb0 + (hold ? done * n : 0), *const d_sums = d_sums0 + (hold ? done : 0);
-            double *const d_gsum = genes ? d_gsum0 + (hold ? done * ng : 0) : nullptr;
-            // ---- draws ----
-            HIPCHK(hipEventRecord(e[0], ctx->stream));
-            if (use_sets) HIPCHK(hipMemsetAsync(d_slots, 0, (size_t)(nb * slot_stride) * 8, ctx->stream));
-            if (binomial) HIPCHK(hipMemsetAsync(d_ndrawn, 0, (size_t)nb * 8, ctx->stream));
-            if (n_rows > 0 && !binomial)
-                hipLaunchKernelGGL(k_boot_draw, dim3((unsigned)((n_rows + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, n_rows, seed,
-                                   (int64_t)first + done, ctx->d_boot_R, use_sets ? ctx->d_boot_slot : nullptr, need_stream ? d_wb : nullptr, d_slots,
-                                   slot_stride);
-            if (n_rows > 0 && binomial)
-                hipLaunchKernelGGL(k_sub_draw, dim3((unsigned)((n_rows + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, n_rows, seed,
-                                   (int64_t)first + done, frac, ctx->d_boot_R, use_sets ? ctx->d_boot_slot : nullptr, need_stream ? d_wb : nullptr,
-                                   d_slots, slot_stride, d_ndrawn);
-            HIPCHK(hipGetLastError());
-            if ((rc = lap(draw_ms))) return rc;
-            // ---- closed form + resident sets, all replicates of the batch in one launch per class ----
-            if (use_sets) {
-                HIPCHK(hipEventRecord(e[0], ctx->stream));
-                if (n_gu > 0)
-                    hipLaunchKernelGGL(k_boot_gather_u, dim3((unsigned)((n_gu + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, n_gu, ctx->d_g_tid,
-                                       d_slots, slot_stride, n_rw, d_gu);
-                hipLaunchKernelGGL(k_boot_closed, dim3(gn, (unsigned)nb), dim3(256), 0, ctx->stream, n, ctx->d_kind, d_slots, slot_stride, n_rw,
-                                   ctx->d_den, d_thb);
-                const size_t off[3] = {0, S.desc[0].size(), S.desc[0].size() + S.desc[1].size()};
-                HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
-                for (int i = 0; i < 2; i++) HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0));
-#define LAUNCH_SB(C, TH, ST)                                                                                                           \
-                if (!S.desc[C].empty())                                                                                                    \
-                    hipLaunchKernelGGL(k_solve_sets_boot<TH>, dim3((unsigned)S.desc[C].size(), (unsigned)nb), dim3(TH), S.max_lds[C], ST,   \
-                                       ctx->d_sdesc[C], ctx->d_g_tid, d_gu, d_slots, ctx->d_srp, ctx->d_sent, ctx->d_scp, ctx->d_scrow,       \
-                                       ctx->d_den, d_thb, d_bstat + off[C], P, n_gu, slot_stride, (int64_t)n, n_sets);
-                LAUNCH_SB(2, 512, ctx->side[1])
-                LAUNCH_SB(1, 256, ctx->side[0])
-                LAUNCH_SB(0, 64, ctx->stream)
-#undef LAUNCH_SB
-                for (int i = 0; i < 2; i++) {
-                    HIPCHK(hipEventRecord(ctx->ev_join[i], ctx->side[i]));
-                    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
-                }
-                HIPCHK(hipGetLastError());
-                if (n_sets) HIPCHK(hipMemcpyAsync(h_bstat.data(), d_bstat, (size_t)(nb * n_sets) * sizeof(SetStat), hipMemcpyDeviceToHost, ctx->stream));
-                if ((rc = lap(sets_ms))) return rc;
-                for (int64_t i = 0; i < nb * n_sets; i++) {
-                    const SetStat &q = h_bstat[(size_t)i];
-                    if (!std::isfinite(q.delta)) { ctx->err = binomial ? "non-finite theta in a connected set of a subsampling replicate" : "non-finite theta in a connected set of a bootstrap replicate"; return EMSAR_HIP_ERR_NUMERIC; }
-                    passes_max = std::max(passes_max, q.passes);
-                    if (!q.converged) unconv[(size_t)(i / n_sets)] = 1;
-                }
-            }
-            // ---- the rest: one streaming solve per replicate with its weights swapped into the layout ----
-            if (need_stream) {
-                HIPCHK(hipMemcpyAsync(h_wb.data(), d_wb, (size_t)(nb * n_rows) * 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(hipStreamSynchronize(ctx->stream));
-                emsar_em_params ps = p;
-                ps.set_mode = 1;
-                for (int64_t y = 0; y < nb; y++) {
-                    guard.swapped = true;
-                    if ((rc = boot_stream_weights(ctx, h_wb.data() + y * n_rows))) return rc;
-                    emsar_em_stats st;
-                    rc = solve_impl(ctx, &ps, h_th.data(), &st);
-                    ctx->count_floor = 0.0; ctx->zero_cut = 0.0; ctx->delta_mask = nullptr;
-                    if (rc) return rc;
-                    stream_ms += st.kernel_ms;
-                    if (!st.converged) unconv[(size_t)y] = 1;
-                    hipLaunchKernelGGL(k_boot_take_streamed, dim3(gn), dim3(256), 0, ctx->stream, n, use_sets ? ctx->d_kind : nullptr, ctx->d_th[0],
-                                       d_thb + y * n);
-                    HIPCHK(hipGetLastError());
-                }
-            }
-            // ---- reduction over the replicates, in replicate order ----
-            HIPCHK(hipEventRecord(e[0], ctx->stream));
-            if (binomial)     // every replicate to its own depth: theta_b * N_R / N_b
-                hipLaunchKernelGGL(k_sub_scale, dim3(gn, (unsigned)nb), dim3(256), 0, ctx->stream, n, n_full, d_ndrawn, d_thb);
-            hipLaunchKernelGGL(k_boot_sums, dim3((unsigned)nb), dim3(1024), 0, ctx->stream, n, d_thb, d_sums);
-            hipLaunchKernelGGL(k_boot_accum, dim3(gn), dim3(256), 0, ctx->stream, n, (int)nb, done, d_thb, d_sums, d_acc4);
-            HIPCHK(hipGetLastError());
-            if (genes) {   // the replicates' gene sums, then the same Welford step on them (gene TPM_b = G_b * 1e6 / S_b)
-                if ((rc = launch_gene_sums(ctx, d_thb, nb, d_gsum, d_gpart))) return rc;
-                hipLaunchKernelGGL(k_boot_accum, dim3((unsigned)grid_for(ng, 256)), dim3(256), 0, ctx->stream, (int)ng, (int)nb, done, d_gsum, d_sums, d_gacc4);
-                HIPCHK(hipGetLastError());
-            }
-            // (after the launches: a copy into pageable memory makes the host wait for the stream)
-            if (binomial) HIPCHK(hipMemcpyAsync(h_ndrawn.data(), d_ndrawn, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream));
-            if ((rc = lap(reduce_ms))) return rc;
-            if (binomial) for (int64_t y = 0; y < nb; y++) depth_sum += h_ndrawn[(size_t)y];
-            if (replicates) {
-                HIPCHK(hipMemcpy(replicates + done * n, d_thb, (size_t)(nb * n) * 8, hipMemcpyDeviceToHost));
-                try { for (int64_t y = 0; y < nb; y++) from_lib(ctx, replicates + (done + y) * n); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-            }
-            for (char c : unconv) unconverged += c;
-            done += nb;
-        }
-        std::vector<double> acc((size_t)4 * n);
-        HIPCHK(hipMemcpyAsync(acc.data(), d_acc4, acc.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        for (int t = 0; t < n; t++)
-            if (!std::isfinite(acc[(size_t)t]) || !std::isfinite(acc[(size_t)n + t])) {
-                ctx->err = binomial ? "non-finite theta in a subsampling replicate" : "non-finite theta in a bootstrap replicate";
-                return EMSAR_HIP_ERR_NUMERIC;
-            }
-        // row r of the accumulators as it is (mean) or as the sample sd, into the caller's vector of this round, caller numbering
-        auto put = [&](double *out, int r, bool sd) {
-            if (!out) return;
-            out += (int64_t)fk * n;
-            for (int t = 0; t < n; t++) {
-                const double v = acc[(size_t)r * n + t];
-                out[t] = !sd ? v : n_rep > 1 ? std::sqrt(v / (double)(n_rep - 1)) : 0.0;
-            }
-            from_lib(ctx, out);
-        };
-        try { put(plan.fpkm_mean, 0, false); put(plan.fpkm_sd, 1, true); put(plan.tpm_mean, 2, false); put(plan.tpm_sd, 3, true); }
-        catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-        if (genes) {   // gene order is the caller's: no renumbering to undo
-            std::vector<double> gacc((size_t)4 * ng);
-            HIPCHK(hipMemcpyAsync(gacc.data(), d_gacc4, gacc.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            for (int64_t g = 0; g < ng; g++) {
-                if (!std::isfinite(gacc[(size_t)g]) || !std::isfinite(gacc[(size_t)(ng + g)])) {
-                    ctx->err = binomial ? "non-finite gene sum in a subsampling replicate" : "non-finite gene sum in a bootstrap replicate";
-                    return EMSAR_HIP_ERR_NUMERIC;
-                }
-                const int64_t o = (int64_t)fk * ng + g;
-                plan.gene_mean[o] = gacc[(size_t)g];
-                if (plan.gene_sd) plan.gene_sd[o] = n_rep > 1 ? std::sqrt(gacc[(size_t)(ng + g)] / (double)(n_rep - 1)) : 0.0;
-                if (plan.gene_tpm_mean) plan.gene_tpm_mean[o] = gacc[(size_t)(2 * ng + g)];
-                if (plan.gene_tpm_sd) plan.gene_tpm_sd[o] = n_rep > 1 ? std::sqrt(gacc[(size_t)(3 * ng + g)] / (double)(n_rep - 1)) : 0.0;
-            }
-        }
-        if (plan.depth_mean) plan.depth_mean[fk] = (double)depth_sum / (double)n_rep;
-        if (hold) {   // ---- quantiles over the held replicates: transcripts, then genes ----
-            const int64_t nq = plan.n_q;
-            int Bp = 1;
-            while (Bp < n_rep) Bp <<= 1;
-            const int cs = emsar::quant_tile_shift(Bp);
-            const size_t lds = ((size_t)Bp << cs) * 8;
-            double *const d_gq = d_qout + 2 * nq * n;
-            HIPCHK(hipEventRecord(e[0], ctx->stream));
-            // S_b added in the caller's order: the TPM quantiles do not depend on the library's numbering (kernels_quant.hpp)
-            hipLaunchKernelGGL(k_quant_sums, dim3((unsigned)n_rep), dim3(1024), 0, ctx->stream, n, d_libof, d_thb0, d_qsums);
-            if (n > 0)
-                hipLaunchKernelGGL(k_boot_quantiles, dim3((unsigned)(((int64_t)n + (1 << cs) - 1) >> cs)), dim3(256), lds, ctx->stream, (int64_t)n,
-                                   (int)n_rep, Bp, cs, d_thb0, d_qsums, (int)nq, d_q, d_qout, d_qout + nq * n);
-            if (genes && ng > 0)
-                hipLaunchKernelGGL(k_boot_quantiles, dim3((unsigned)((ng + (1 << cs) - 1) >> cs)), dim3(256), lds, ctx->stream, ng, (int)n_rep, Bp, cs,
-                                   d_gsum0, d_qsums, (int)nq, d_q, d_gq, d_gq + nq * ng);
-            HIPCHK(hipGetLastError());
-            if ((rc = lap(quantile_ms))) return rc;
-            HIPCHK(hipMemcpy(plan.fpkm_q, d_qout, (size_t)(nq * n) * 8, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(plan.tpm_q, d_qout + nq * n, (size_t)(nq * n) * 8, hipMemcpyDeviceToHost));
-            try { for (int64_t k = 0; k < nq; k++) { from_lib(ctx, plan.fpkm_q + k * n); from_lib(ctx, plan.tpm_q + k * n); } }
-            catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-            if (genes) {
-                HIPCHK(hipMemcpy(plan.gene_fpkm_q, d_gq, (size_t)(nq * ng) * 8, hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(plan.gene_tpm_q, d_gq + nq * ng, (size_t)(nq * ng) * 8, hipMemcpyDeviceToHost));
-            }
-            if (plan.replicate_sums) HIPCHK(hipMemcpy(plan.replicate_sums, d_qsums, (size_t)n_rep * 8, hipMemcpyDeviceToHost));
-        }
-    }
-    if (stats) {
-        *stats = BootTimes();
-        stats->batch = (int32_t)batch; stats->unconverged = unconverged; stats->passes_max = passes_max;
-        int64_t pos = 0;
-        for (int64_t r = 0; r < n_rows; r++) pos += ctx->h_wgt[(size_t)r] > 0;
-        stats->draws = pos * n_rep * plan.n_fractions;
-        stats->draw_ms = draw_ms; stats->sets_ms = sets_ms; stats->stream_ms = stream_ms; stats->reduce_ms = reduce_ms;
-        stats->held_bytes = held_bytes; stats->quantile_ms = quantile_ms;
-    }
-    // the sample's own weights back before the call returns (the guard does it too, but a failure there must be reported)
-    if (guard.swapped) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        guard.swapped = false;
-        if ((rc = boot_stream_weights(ctx, ctx->h_wgt.data()))) return rc;
-        if (!guard.weighted) {
-            dfree(ctx->d_wgt); ctx->d_wgt = nullptr;
-            if (ctx->layout == EMSAR_LAYOUT_TILED) { dfree(ctx->d_left_wgt); ctx->d_left_wgt = nullptr; }
-        }
-        ctx->weighted = guard.weighted;
-    }
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
-    return EMSAR_HIP_OK;
-}
-
-static void boot_stats_out(emsar_boot_stats *out, const BootTimes &t, int32_t n_rep) {
-    if (!out) return;
-    memset(out, 0, sizeof(*out));
-    out->n_replicates = n_rep; out->batch = t.batch; out->replicates_unconverged = t.unconverged; out->set_passes_max = t.passes_max;
-    out->draws = t.draws;
-    out->draw_ms = t.draw_ms; out->sets_ms = t.sets_ms; out->stream_ms = t.stream_ms; out->reduce_ms = t.reduce_ms; out->total_ms = t.total_ms;
-}
-
-int emsar_hip_bootstrap(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t first_replicate, int32_t n_replicates,
-                        double *fpkm_mean, double *fpkm_sd, double *tpm_sd, double *replicates, emsar_boot_stats *stats) {
-    if (!ctx) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
-    if (!fpkm_mean || !fpkm_sd || !tpm_sd || n_replicates < 1 || first_replicate < 0 ||
-        (int64_t)first_replicate + (int64_t)n_replicates > (int64_t)INT32_MAX + 1)
-        return EMSAR_HIP_ERR_ARG;
-    try {
-        BootPlan plan;
-        plan.fpkm_mean = fpkm_mean; plan.fpkm_sd = fpkm_sd; plan.tpm_sd = tpm_sd; plan.replicates = replicates;
-        BootTimes t;
-        const int rc = bootstrap_impl(ctx, p, seed, first_replicate, n_replicates, plan, &t);
-        if (rc == EMSAR_HIP_OK) boot_stats_out(stats, t, n_replicates);
-        return rc;
-    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-}
-
-int emsar_hip_bootstrap_genes(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t first_replicate, int32_t n_replicates,
-                              double *fpkm_mean, double *fpkm_sd, double *tpm_sd, double *replicates,
-                              double *gene_fpkm_mean, double *gene_fpkm_sd, double *gene_tpm_sd, emsar_boot_stats *stats) {
-    if (!ctx) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_sample || !ctx->have_genes) return EMSAR_HIP_ERR_STATE;
-    if (!fpkm_mean || !fpkm_sd || !tpm_sd || !gene_fpkm_mean || !gene_fpkm_sd || !gene_tpm_sd || n_replicates < 1 || first_replicate < 0 ||
-        (int64_t)first_replicate + (int64_t)n_replicates > (int64_t)INT32_MAX + 1)
-        return EMSAR_HIP_ERR_ARG;
-    try {
-        BootPlan plan;
-        plan.fpkm_mean = fpkm_mean; plan.fpkm_sd = fpkm_sd; plan.tpm_sd = tpm_sd; plan.replicates = replicates;
-        plan.gene_mean = gene_fpkm_mean; plan.gene_sd = gene_fpkm_sd; plan.gene_tpm_sd = gene_tpm_sd;
-        BootTimes t;
-        const int rc = bootstrap_impl(ctx, p, seed, first_replicate, n_replicates, plan, &t);
-        if (rc == EMSAR_HIP_OK) boot_stats_out(stats, t, n_replicates);
-        return rc;
-    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-}
-
-// ---- bootstrap quantiles ------------------------------------------------------------------------------------------------------
-static bool quantile_args_ok(int32_t n_q, const double *q) {
-    if (n_q < 1 || !q) return false;
-    for (int32_t k = 0; k < n_q; k++) if (!std::isfinite(q[k]) || q[k] < 0.0 || q[k] > 1.0) return false;
-    return true;
-}
-
-int emsar_hip_bootstrap_quantiles(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t first_replicate, int32_t n_replicates,
-                                  int32_t n_q, const double *q, double *fpkm_mean, double *fpkm_sd, double *tpm_sd, double *replicates,
-                                  double *replicate_sums, double *fpkm_q, double *tpm_q, double *gene_fpkm_mean, double *gene_fpkm_sd,
-                                  double *gene_tpm_sd, double *gene_fpkm_q, double *gene_tpm_q, emsar_boot_stats *stats,
-                                  emsar_quantile_stats *qstats) {
-    if (!ctx) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
-    const int n_gene_out = (gene_fpkm_mean != nullptr) + (gene_fpkm_sd != nullptr) + (gene_tpm_sd != nullptr) + (gene_fpkm_q != nullptr) +
-                           (gene_tpm_q != nullptr);
-    if (!fpkm_mean || !fpkm_sd || !tpm_sd || !fpkm_q || !tpm_q || n_replicates < 1 || n_replicates > emsar::kQuantMaxRep || first_replicate < 0 ||
-        (int64_t)first_replicate + (int64_t)n_replicates > (int64_t)INT32_MAX + 1 || !quantile_args_ok(n_q, q) || (n_gene_out != 0 && n_gene_out != 5))
-        return EMSAR_HIP_ERR_ARG;
-    if (n_gene_out && !ctx->have_genes) return EMSAR_HIP_ERR_STATE;
-    try {
-        BootPlan plan;
-        plan.fpkm_mean = fpkm_mean; plan.fpkm_sd = fpkm_sd; plan.tpm_sd = tpm_sd; plan.replicates = replicates;
-        plan.gene_mean = gene_fpkm_mean; plan.gene_sd = gene_fpkm_sd; plan.gene_tpm_sd = gene_tpm_sd;
-        plan.n_q = n_q; plan.q = q; plan.fpkm_q = fpkm_q; plan.tpm_q = tpm_q; plan.gene_fpkm_q = gene_fpkm_q; plan.gene_tpm_q = gene_tpm_q;
-        plan.replicate_sums = replicate_sums;
-        BootTimes t;
-        const int rc = bootstrap_impl(ctx, p, seed, first_replicate, n_replicates, plan, &t);
-        if (rc == EMSAR_HIP_OK) {
-            boot_stats_out(stats, t, n_replicates);
-            if (qstats) { memset(qstats, 0, sizeof(*qstats)); qstats->n_quantiles = n_q; qstats->held_bytes = t.held_bytes; qstats->quantile_ms = t.quantile_ms; }
-        }
-        return rc;
-    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-}
-
-int emsar_hip_quantiles_host(int32_t n_rep, int64_t n, const double *values, int32_t n_q, const double *q, double *out) {
-    if (n_rep < 1 || n < 0 || (n > 0 && (!values || !out)) || !quantile_args_ok(n_q, q)) return EMSAR_HIP_ERR_ARG;
-    try {
-        std::vector<double> col((size_t)n_rep);
-        for (int64_t t = 0; t < n; t++) {
-            for (int32_t b = 0; b < n_rep; b++) col[(size_t)b] = values[(int64_t)b * n + t];
-            std::sort(col.begin(), col.end(), [](double a, double b) { return a < b || (b != b && a == a); });   // NaN last: a strict weak order
-            for (int32_t k = 0; k < n_q; k++) out[(int64_t)k * n + t] = emsar::quantile_sorted(col.data(), 1, n_rep, q[k]);
-        }
-    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    return EMSAR_HIP_OK;
-}
-
-// ---- gene map -----------------------------------------------------------------------------------------------------------------
-int emsar_hip_set_gene_map(emsar_hip_ctx *ctx, int32_t n_genes, const int32_t *gene_of_tx) {
-    if (!ctx) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_structure) return EMSAR_HIP_ERR_STATE;
-    if (n_genes < 1 || (!gene_of_tx && ctx->n_tx > 0)) return EMSAR_HIP_ERR_ARG;
-    const int32_t n = ctx->n_tx;
-    for (int32_t t = 0; t < n; t++) if (gene_of_tx[t] < -1 || gene_of_tx[t] >= n_genes) return EMSAR_HIP_ERR_ARG;
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    free_genes(ctx);
-    try {
-        // gene CSR in library indices, each gene's transcripts by ascending caller tid; then its chunks of kGeneChunk
-        std::vector<int64_t> gp((size_t)n_genes + 1, 0);
-        for (int32_t t = 0; t < n; t++) if (gene_of_tx[t] >= 0) gp[(size_t)gene_of_tx[t] + 1]++;
-        for (int32_t g = 0; g < n_genes; g++) gp[(size_t)g + 1] += gp[(size_t)g];
-        const int64_t m = gp[(size_t)n_genes];
-        std::vector<int32_t> tx((size_t)m), chunk_beg, chunk_out, multi;
-        std::vector<int64_t> fill(gp.begin(), gp.end() - 1);
-        const auto &map = tid_map(ctx);
-        const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !map.empty();
-        for (int32_t t = 0; t < n; t++)
-            if (gene_of_tx[t] >= 0) tx[(size_t)fill[(size_t)gene_of_tx[t]]++] = remap ? map[(size_t)t] : t;
-        for (int32_t g = 0; g < n_genes; g++) {
-            const int64_t len = gp[(size_t)g + 1] - gp[(size_t)g];
-            const int64_t nch = std::max<int64_t>(1, (len + kGeneChunk - 1) / kGeneChunk);     // an empty gene: one empty chunk, sum 0
-            if (nch > 1) { multi.push_back(g); multi.push_back((int32_t)chunk_out.size()); multi.push_back((int32_t)(chunk_out.size() + nch)); }
-            for (int64_t j = 0; j < nch; j++) {
-                chunk_beg.push_back((int32_t)(gp[(size_t)g] + j * kGeneChunk));
-                chunk_out.push_back(nch == 1 ? g : -1);
-            }
-            if (chunk_out.size() > (size_t)INT32_MAX - 1) return EMSAR_HIP_ERR_ARG;
-        }
-        chunk_beg.push_back((int32_t)m);
-        const size_t nc = chunk_out.size();
-        std::vector<int32_t> blk;
-        blk.reserve((size_t)m + 2 * nc + 1 + multi.size());
-        blk.insert(blk.end(), tx.begin(), tx.end());
-        blk.insert(blk.end(), chunk_beg.begin(), chunk_beg.end());
-        blk.insert(blk.end(), chunk_out.begin(), chunk_out.end());
-        blk.insert(blk.end(), multi.begin(), multi.end());
-        HIPCHK(hipMalloc(&ctx->d_gene_blk, blk.size() * 4));
-        hipError_t e = hipMemcpy(ctx->d_gene_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { free_genes(ctx); HIPCHK(e); }
-        ctx->d_gene_tx = ctx->d_gene_blk;
-        ctx->d_chunk_beg = ctx->d_gene_tx + m;
-        ctx->d_chunk_out = ctx->d_chunk_beg + nc + 1;
-        ctx->d_gene_multi = ctx->d_chunk_out + nc;
-        ctx->n_genes = n_genes; ctx->n_gene_chunks = (int64_t)nc; ctx->n_gene_multi = (int64_t)multi.size() / 3;
-        ctx->have_genes = true;
-    } catch (const std::bad_alloc &) { free_genes(ctx); return EMSAR_HIP_ERR_OOM; }
-    return EMSAR_HIP_OK;
-}
-
-int emsar_hip_gene_sums(emsar_hip_ctx *ctx, int32_t n_cols, const double *tx_values, double *gene_out) {
-    if (!ctx) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_structure || !ctx->have_genes) return EMSAR_HIP_ERR_STATE;
-    if (n_cols < 1 || !tx_values || !gene_out) return EMSAR_HIP_ERR_ARG;
-    HIPCHK(hipSetDevice(ctx->device));
-    const int64_t n = ctx->n_tx, ng = ctx->n_genes, nc = ctx->n_gene_multi > 0 ? ctx->n_gene_chunks : 0;
-    const int64_t cb = std::min<int64_t>(n_cols, 65535);        // columns per launch (grid y)
-    double *d_x = nullptr, *d_out = nullptr, *d_part = nullptr;
-    struct Free { double **p[3]; ~Free() { for (auto q : p) dfree(*q); } } fr{{&d_x, &d_out, &d_part}};
-    HIPCHK(hipMalloc(&d_x, (size_t)std::max<int64_t>(cb * n, 1) * 8));
-    HIPCHK(hipMalloc(&d_out, (size_t)(cb * ng) * 8));
-    if (nc) HIPCHK(hipMalloc(&d_part, (size_t)(cb * nc) * 8));
-    try {
-        std::vector<double> tmp;
-        for (int64_t c0 = 0; c0 < n_cols; c0 += cb) {
-            const int64_t k = std::min<int64_t>(cb, n_cols - c0);
-            for (int64_t j = 0; j < k; j++) {
-                const double *col = to_lib(ctx, tx_values + (c0 + j) * n, tmp);
-                HIPCHK(hipMemcpy(d_x + j * n, col, (size_t)n * 8, hipMemcpyHostToDevice));
-            }
-            int rc = launch_gene_sums(ctx, d_x, k, d_out, d_part);
-            if (rc) return rc;
-            HIPCHK(hipMemcpyAsync(gene_out + c0 * ng, d_out, (size_t)(k * ng) * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-        }
-    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    return EMSAR_HIP_OK;
-}
-
-int emsar_hip_bootstrap_weights(emsar_hip_ctx *ctx, uint64_t seed, int32_t replicate, int32_t *w_out) {
-    if (!ctx || !w_out || replicate < 0) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
-    HIPCHK(hipSetDevice(ctx->device));
-    int rc;
-    try { if ((rc = boot_prepare(ctx, false))) return rc; } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    if (ctx->n_rows == 0) return EMSAR_HIP_OK;
-    int32_t *d_w = nullptr;
-    HIPCHK(hipMalloc(&d_w, (size_t)ctx->n_rows * 4));
-    hipLaunchKernelGGL(k_boot_draw, dim3((unsigned)((ctx->n_rows + 255) / 256), 1), dim3(256), 0, ctx->stream, ctx->n_rows, seed, (int64_t)replicate,
-                       ctx->d_boot_R, (const int64_t *)nullptr, d_w, (double *)nullptr, (int64_t)0);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(w_out, d_w, (size_t)ctx->n_rows * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    dfree(d_w);
-    HIPCHK(e);
-    return EMSAR_HIP_OK;
-}
-
-int emsar_hip_bootstrap_draw_host(uint64_t seed, int32_t replicate, int64_t n_rows, const int32_t *row_weight, int32_t *w_out) {
-    if (replicate < 0 || n_rows < 0 || (n_rows > 0 && !w_out)) return EMSAR_HIP_ERR_ARG;
-    if (row_weight) for (int64_t r = 0; r < n_rows; r++) if (row_weight[r] < 0) return EMSAR_HIP_ERR_ARG;
-    for (int64_t r = 0; r < n_rows; r++) w_out[r] = emsar::boot_poisson(seed, (uint64_t)replicate, (uint64_t)r, row_weight ? row_weight[r] : 1);
-    return EMSAR_HIP_OK;
-}
-
-// ---- depth subsampling ----------------------------------------------------------------------------------------------------------
-static bool sub_fraction_ok(double f) { return std::isfinite(f) && f > 0.0 && f <= 1.0; }
-
-int emsar_hip_subsample(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t n_fractions, const double *fractions,
-                        int32_t n_replicates, double *fpkm_mean, double *fpkm_sd, double *tpm_mean, double *tpm_sd, double *depth_mean,
-                        double *replicates, double *gene_fpkm_mean, double *gene_fpkm_sd, double *gene_tpm_mean, emsar_subsample_stats *stats) {
-    if (!ctx) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
-    if (n_fractions < 1 || !fractions || n_replicates < 1 || !fpkm_mean || !fpkm_sd || !tpm_mean || !tpm_sd || !depth_mean) return EMSAR_HIP_ERR_ARG;
-    for (int32_t k = 0; k < n_fractions; k++) if (!sub_fraction_ok(fractions[k])) return EMSAR_HIP_ERR_ARG;
-    const int n_gene_out = (gene_fpkm_mean != nullptr) + (gene_fpkm_sd != nullptr) + (gene_tpm_mean != nullptr);
-    if (n_gene_out != 0 && n_gene_out != 3) return EMSAR_HIP_ERR_ARG;
-    if (n_gene_out && !ctx->have_genes) return EMSAR_HIP_ERR_STATE;
-    try {
-        BootPlan plan;
-        plan.fractions = fractions; plan.n_fractions = n_fractions;
-        plan.fpkm_mean = fpkm_mean; plan.fpkm_sd = fpkm_sd; plan.tpm_mean = tpm_mean; plan.tpm_sd = tpm_sd; plan.replicates = replicates;
-        plan.gene_mean = gene_fpkm_mean; plan.gene_sd = gene_fpkm_sd; plan.gene_tpm_mean = gene_tpm_mean;
-        plan.depth_mean = depth_mean;
-        BootTimes t;
-        const int rc = bootstrap_impl(ctx, p, seed, 0, n_replicates, plan, &t);
-        if (rc == EMSAR_HIP_OK && stats) {
-            memset(stats, 0, sizeof(*stats));
-            stats->n_fractions = n_fractions; stats->n_replicates = n_replicates; stats->batch = t.batch; stats->replicates_unconverged = t.unconverged;
-            stats->draws = t.draws;
-            stats->draw_ms = t.draw_ms; stats->sets_ms = t.sets_ms; stats->stream_ms = t.stream_ms; stats->reduce_ms = t.reduce_ms;
-            stats->total_ms = t.total_ms;
-        }
-        return rc;
-    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-}
-
-int emsar_hip_subsample_weights(emsar_hip_ctx *ctx, uint64_t seed, int32_t replicate, double fraction, int32_t *w_out) {
-    if (!ctx || !w_out || replicate < 0 || !sub_fraction_ok(fraction)) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
-    HIPCHK(hipSetDevice(ctx->device));
-    int rc;
-    try { if ((rc = boot_prepare(ctx, false))) return rc; } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    if (ctx->n_rows == 0) return EMSAR_HIP_OK;
-    int32_t *d_w = nullptr;
-    HIPCHK(hipMalloc(&d_w, ((size_t)ctx->n_rows + 1) / 2 * 8 + 8));
-    long long *d_tot = (long long *)(d_w + (ctx->n_rows + 1) / 2 * 2);      // the draw kernel's total, 8-byte aligned behind the weights
-    hipError_t e = hipMemsetAsync(d_tot, 0, 8, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_sub_draw, dim3((unsigned)((ctx->n_rows + 255) / 256), 1), dim3(256), 0, ctx->stream, ctx->n_rows, seed, (int64_t)replicate,
-                           fraction, ctx->d_boot_R, (const int64_t *)nullptr, d_w, (double *)nullptr, (int64_t)0, d_tot);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(w_out, d_w, (size_t)ctx->n_rows * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    dfree(d_w);
-    HIPCHK(e);
-    return EMSAR_HIP_OK;
-}
-
-int emsar_hip_subsample_draw_host(uint64_t seed, int32_t replicate, double fraction, int64_t n_rows, const int32_t *row_weight, int32_t *w_out) {
-    if (replicate < 0 || n_rows < 0 || (n_rows > 0 && !w_out) || !sub_fraction_ok(fraction)) return EMSAR_HIP_ERR_ARG;
-    if (row_weight) for (int64_t r = 0; r < n_rows; r++) if (row_weight[r] < 0) return EMSAR_HIP_ERR_ARG;
-    for (int64_t r = 0; r < n_rows; r++)
-        w_out[r] = emsar::boot_binomial(seed, (uint64_t)replicate, (uint64_t)r, row_weight ? row_weight[r] : 1, fraction);
     return EMSAR_HIP_OK;
 }
 
@@ -1977,3 +1296,5 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 }
 
 }  // extern "C"
+
+#include "resample.hpp"   // the resampling driver and its entry points: bootstrap, genes, quantiles, subsampling

@@ -141,6 +141,29 @@ def test_reproducible_and_no_side_effects(dev):
     assert np.array_equal(s0, s1)
 
 
+@pytest.mark.parametrize("layout", [hip.LAYOUT_CSR, hip.LAYOUT_TILED], ids=["csr", "tiled"])
+def test_unweighted_sample_is_restored(layout):
+    """A sample uploaded without weights has no weight arrays on the device: the streamed replicates allocate them, and the call frees
+    them again and leaves the sample unweighted (stored_bytes_per_pass counts 4 bytes per row only while it is weighted)."""
+    m = _family()
+    with EmsarHip(0) as d:
+        d.set_deterministic(True)
+        d.upload_structure(m.n_tx, m.row_ptr, m.col_idx, layout=layout)
+        d.upload_sample(np.ones(m.n_rows, dtype=np.int32), None, None)
+        weighted_bytes = d.info()["stored_bytes_per_pass"]
+        d.upload_sample(None, None, None)
+        info = d.info()
+        assert info["stored_bytes_per_pass"] < weighted_bytes      # the sample really starts without weight arrays (no merged rows)
+        th0, st0 = d.solve(set_mode=1, **SOLVE)
+        d.bootstrap(3, 1, set_mode=1, **SOLVE)
+        d.subsample([0.5], 2, 1, set_mode=1, **SOLVE)
+        th1, st1 = d.solve(set_mode=1, **SOLVE)
+        assert np.array_equal(th0, th1)
+        assert st1.stored_bytes_per_pass == st0.stored_bytes_per_pass
+        assert d.info() == info
+        d.run_passes(2)
+
+
 def test_closed_form(dev):
     n_tx = 50
     rng = np.random.default_rng(1)
