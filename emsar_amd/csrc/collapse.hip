@@ -46,6 +46,7 @@
 
 #include "../../include/emsar_hip.h"
 #include "internal.hpp"
+#include "devmem.hpp"
 #include <cstdlib>
 #include <new>
 
@@ -429,12 +430,7 @@ struct Events {
     hipEvent_t a = nullptr, b = nullptr;
     ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
 };
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <class T> T *as() { return reinterpret_cast<T *>(p); }
-};
+using emsar::DevBuf;
 
 }  // namespace
 
@@ -467,24 +463,31 @@ extern "C" int emsar_hip_collapse_rows(emsar_hip_ctx *ctx, int64_t n_rows, int32
     // rounds carry part of the call.  Clamped to [16, 2^20]; the partition count below is always between 1 and 2^24, never 0.
     int64_t part_rows = kPartRows;
     if (const char *e = getenv("EMSAR_HIP_COLLAPSE_PART_ROWS")) { const long long v = atoll(e); if (v >= 16 && v <= (1 << 20)) part_rows = (int64_t)v; }
-    DevBuf d_rp, d_ci, d_w, d_seg, d_claimed, d_over0, d_over1, d_long, d_cnt, d_first, d_cntd, d_first1, d_cnt1, d_uid1, d_uidd, d_sseg, d_sfirst, d_ulen, d_uoff,
-        d_orp, d_oci, d_ow, d_map, d_tmp, d_rec0, d_rec1, d_bounds, d_pid0, d_pid1, d_idx0, d_idx1;
-    CCHK(d_rp.alloc((size_t)(n_rows + 1) * 8)); CCHK(d_ci.alloc((size_t)nnz * 4));
-    if (row_weight) CCHK(d_w.alloc((size_t)n_rows * 4));
-    if (row_map_out) { CCHK(d_seg.alloc((size_t)n_rows * 4)); CCHK(d_map.alloc((size_t)n_rows * 4)); }
-    CCHK(d_claimed.alloc((size_t)n_rows * 4));
-    CCHK(d_over0.alloc((size_t)n_rows * 4)); CCHK(d_over1.alloc((size_t)n_rows * 4)); CCHK(d_long.alloc((size_t)n_rows * 4)); CCHK(d_cnt.alloc(sizeof(Counters)));
+    DevBuf<uint64_t> d_rp, d_ulen, d_uoff, d_orp;
+    DevBuf<int32_t> d_ci, d_w, d_oci, d_map;
+    DevBuf<uint32_t> d_seg, d_claimed, d_over0, d_over1, d_long, d_first, d_first1, d_uid1, d_uidd, d_sseg, d_sfirst, d_pid0, d_pid1, d_idx0, d_idx1;
+    DevBuf<unsigned long long> d_cntd, d_cnt1;
+    DevBuf<long long> d_ow;
+    DevBuf<Counters> d_cnt;
+    DevBuf<Rec> d_rec0, d_rec1;
+    DevBuf<unsigned> d_bounds;
+    DevBuf<void> d_tmp;
+    CCHK(d_rp.alloc((size_t)(n_rows + 1))); CCHK(d_ci.alloc((size_t)nnz));
+    if (row_weight) CCHK(d_w.alloc((size_t)n_rows));
+    if (row_map_out) { CCHK(d_seg.alloc((size_t)n_rows)); CCHK(d_map.alloc((size_t)n_rows)); }
+    CCHK(d_claimed.alloc((size_t)n_rows));
+    CCHK(d_over0.alloc((size_t)n_rows)); CCHK(d_over1.alloc((size_t)n_rows)); CCHK(d_long.alloc((size_t)n_rows)); CCHK(d_cnt.alloc(1));
     // everything the numbering and the emit need, at worst-case size (every row unique), so that nothing is allocated between the kernels
-    CCHK(d_first.alloc((size_t)n_rows * 4)); CCHK(d_cntd.alloc((size_t)n_rows * 8)); CCHK(d_uidd.alloc((size_t)n_rows * 4));
-    CCHK(d_first1.alloc((size_t)std::max(n_tx, 1) * 4)); CCHK(d_cnt1.alloc((size_t)std::max(n_tx, 1) * 8)); CCHK(d_uid1.alloc((size_t)std::max(n_tx, 1) * 4));
-    CCHK(d_sseg.alloc((size_t)n_rows * 4)); CCHK(d_sfirst.alloc((size_t)n_rows * 4)); CCHK(d_ulen.alloc((size_t)n_rows * 8)); CCHK(d_uoff.alloc((size_t)n_rows * 8));
-    CCHK(d_orp.alloc((size_t)(n_rows + 1) * 8)); CCHK(d_ow.alloc((size_t)n_rows * 8)); CCHK(d_oci.alloc((size_t)nnz * 4));
-    CCHK(d_rec0.alloc((size_t)n_rows * sizeof(Rec))); CCHK(d_rec1.alloc((size_t)n_rows * sizeof(Rec)));
-    CCHK(d_pid0.alloc((size_t)n_rows * 4)); CCHK(d_pid1.alloc((size_t)n_rows * 4)); CCHK(d_idx0.alloc((size_t)n_rows * 4)); CCHK(d_idx1.alloc((size_t)n_rows * 4));
+    CCHK(d_first.alloc((size_t)n_rows)); CCHK(d_cntd.alloc((size_t)n_rows)); CCHK(d_uidd.alloc((size_t)n_rows));
+    CCHK(d_first1.alloc((size_t)std::max(n_tx, 1))); CCHK(d_cnt1.alloc((size_t)std::max(n_tx, 1))); CCHK(d_uid1.alloc((size_t)std::max(n_tx, 1)));
+    CCHK(d_sseg.alloc((size_t)n_rows)); CCHK(d_sfirst.alloc((size_t)n_rows)); CCHK(d_ulen.alloc((size_t)n_rows)); CCHK(d_uoff.alloc((size_t)n_rows));
+    CCHK(d_orp.alloc((size_t)(n_rows + 1))); CCHK(d_ow.alloc((size_t)n_rows)); CCHK(d_oci.alloc((size_t)nnz));
+    CCHK(d_rec0.alloc((size_t)n_rows)); CCHK(d_rec1.alloc((size_t)n_rows));
+    CCHK(d_pid0.alloc((size_t)n_rows)); CCHK(d_pid1.alloc((size_t)n_rows)); CCHK(d_idx0.alloc((size_t)n_rows)); CCHK(d_idx1.alloc((size_t)n_rows));
     {
         int bits_max = 0;                                          // partition bounds at the largest partition count any round can have
         while (bits_max < 24 && ((int64_t)1 << bits_max) * part_rows < n_rows) bits_max++;
-        CCHK(d_bounds.alloc((((size_t)1 << bits_max) + 1) * 4));
+        CCHK(d_bounds.alloc(((size_t)1 << bits_max) + 1));
     }
     int end_bit = 1;
     while (end_bit < 32 && ((uint64_t)1 << end_bit) < (uint64_t)n_rows) end_bit++;
@@ -493,39 +496,39 @@ extern "C" int emsar_hip_collapse_rows(emsar_hip_ctx *ctx, int64_t n_rows, int32
     CCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, (uint64_t *)nullptr, (uint64_t *)nullptr, (int)n_rows, st));
     const size_t tmp_bytes = std::max(tb1, tb2) + ((size_t)1 << 20);
     CCHK(d_tmp.alloc(tmp_bytes));
-    CCHK(hipMemcpyAsync(d_rp.p, row_ptr, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, st));
-    if (nnz) CCHK(hipMemcpyAsync(d_ci.p, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-    if (row_weight) CCHK(hipMemcpyAsync(d_w.p, row_weight, (size_t)n_rows * 4, hipMemcpyHostToDevice, st));
+    CCHK(hipMemcpyAsync(d_rp, row_ptr, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, st));
+    if (nnz) CCHK(hipMemcpyAsync(d_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+    if (row_weight) CCHK(hipMemcpyAsync(d_w, row_weight, (size_t)n_rows * 4, hipMemcpyHostToDevice, st));
     Events ev;
     CCHK(hipEventCreate(&ev.a)); CCHK(hipEventCreate(&ev.b));
     CCHK(hipEventRecord(ev.a, st));
     const char *weak_env = getenv("EMSAR_HIP_COLLAPSE_WEAK_HASH");      // tests: every row of one length collides in round 0 and is told apart by comparison
     const int weak_hash = weak_env && atoi(weak_env) != 0;
-    const int32_t *dw = row_weight ? d_w.as<int32_t>() : nullptr;
-    uint32_t *seg_of = row_map_out ? d_seg.as<uint32_t>() : nullptr;
-    uint32_t *over[2] = {d_over0.as<uint32_t>(), d_over1.as<uint32_t>()};
+    const int32_t *dw = row_weight ? d_w.get() : nullptr;
+    uint32_t *seg_of = row_map_out ? d_seg.get() : nullptr;
+    uint32_t *over[2] = {d_over0, d_over1};
     Counters hc{0, {0, 0}, 0, 0};
-    CCHK(hipMemsetAsync(d_cnt.p, 0, sizeof(Counters), st));
-    CCHK(hipMemsetAsync(d_first1.p, 0x7F, (size_t)n_tx * 4, st));       // 0x7F7F7F7F: larger than any row number
-    CCHK(hipMemsetAsync(d_cnt1.p, 0, (size_t)n_tx * 8, st));
+    CCHK(hipMemsetAsync(d_cnt, 0, sizeof(Counters), st));
+    CCHK(hipMemsetAsync(d_first1, 0x7F, (size_t)n_tx * 4, st));       // 0x7F7F7F7F: larger than any row number
+    CCHK(hipMemsetAsync(d_cnt1, 0, (size_t)n_tx * 8, st));
     int64_t n_cur = n_rows, max_parts = 0;
     const uint32_t *list = nullptr;
     int rounds = 0;
     for (uint64_t seed = 0; n_cur > 0; seed++) {
         const int o = (int)(seed & 1);
-        CCHK(hipMemsetAsync(&d_cnt.as<Counters>()->n_long, 0, sizeof(unsigned), st));
-        CCHK(hipMemsetAsync(&d_cnt.as<Counters>()->n_rec, 0, sizeof(unsigned), st));
-        CCHK(hipMemsetAsync(&d_cnt.as<Counters>()->n_over[o], 0, sizeof(unsigned), st));
+        CCHK(hipMemsetAsync(&d_cnt->n_long, 0, sizeof(unsigned), st));
+        CCHK(hipMemsetAsync(&d_cnt->n_rec, 0, sizeof(unsigned), st));
+        CCHK(hipMemsetAsync(&d_cnt->n_over[o], 0, sizeof(unsigned), st));
         const int64_t rows_per_wg = (int64_t)kHashThreads * kHashSteps;
-        hipLaunchKernelGGL(k_row_hash, dim3((unsigned)((n_cur + rows_per_wg - 1) / rows_per_wg)), dim3(kHashThreads), 0, st, n_cur, list, d_rp.as<uint64_t>(),
-                           d_ci.as<int32_t>(), dw, seg_of, d_rec0.as<Rec>(), d_long.as<uint32_t>(), d_first1.as<uint32_t>(),
-                           d_cnt1.as<unsigned long long>(), d_cnt.as<Counters>(), seed, weak_hash);
+        hipLaunchKernelGGL(k_row_hash, dim3((unsigned)((n_cur + rows_per_wg - 1) / rows_per_wg)), dim3(kHashThreads), 0, st, n_cur, list, d_rp,
+                           d_ci, dw, seg_of, d_rec0, d_long, d_first1,
+                           d_cnt1, d_cnt, seed, weak_hash);
         STAGE("k_row_hash");
-        hipLaunchKernelGGL(k_long_hash, dim3((unsigned)((n_cur + 255) / 256)), dim3(256), 0, st, d_long.as<uint32_t>(), d_rp.as<uint64_t>(), d_ci.as<int32_t>(),
-                           d_rec0.as<Rec>(), d_cnt.as<Counters>(), seed, weak_hash);
+        hipLaunchKernelGGL(k_long_hash, dim3((unsigned)((n_cur + 255) / 256)), dim3(256), 0, st, d_long, d_rp, d_ci,
+                           d_rec0, d_cnt, seed, weak_hash);
         STAGE("k_long_hash");
         CCHK(hipGetLastError());
-        CCHK(hipMemcpyAsync(&hc, d_cnt.p, sizeof(Counters), hipMemcpyDeviceToHost, st));
+        CCHK(hipMemcpyAsync(&hc, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, st));
         CCHK(hipStreamSynchronize(st));
         const int64_t n_rec = (int64_t)hc.n_rec + (int64_t)hc.n_long;          // short rows' records, then one per long row
         if (n_rec > n_cur) CFAIL("more records than rows");
@@ -535,26 +538,26 @@ extern "C" int emsar_hip_collapse_rows(emsar_hip_ctx *ctx, int64_t n_rows, int32
             while (bits < 24 && ((int64_t)1 << bits) * part_rows < n_rec) bits++;
             const unsigned P = 1u << bits;
             max_parts = std::max<int64_t>(max_parts, (int64_t)P);
-            const Rec *srec = d_rec0.as<Rec>();
+            const Rec *srec = d_rec0;
             if (bits > 0) {
                 const dim3 gr((unsigned)((n_rec + 255) / 256)), br(256);
-                hipLaunchKernelGGL(k_part_ids, gr, br, 0, st, (unsigned)n_rec, d_rec0.as<Rec>(), bits, d_pid0.as<uint32_t>(), d_idx0.as<uint32_t>());
+                hipLaunchKernelGGL(k_part_ids, gr, br, 0, st, (unsigned)n_rec, d_rec0, bits, d_pid0, d_idx0);
                 size_t t1 = 0;                                    // this call's own temporary storage size (rocPRIM picks its algorithm by the item count)
-                CCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, d_pid0.as<uint32_t>(), d_pid1.as<uint32_t>(), d_idx0.as<uint32_t>(), d_idx1.as<uint32_t>(), (int)n_rec, 0, bits, st));
+                CCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, d_pid0.get(), d_pid1.get(), d_idx0.get(), d_idx1.get(), (int)n_rec, 0, bits, st));
                 if (t1 > tmp_bytes) CFAIL("temporary storage of the partition sort exceeds the worst case");
-                CCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, t1, d_pid0.as<uint32_t>(), d_pid1.as<uint32_t>(), d_idx0.as<uint32_t>(), d_idx1.as<uint32_t>(), (int)n_rec, 0, bits, st));
-                hipLaunchKernelGGL(k_part_gather, gr, br, 0, st, (unsigned)n_rec, d_idx1.as<uint32_t>(), d_rec0.as<Rec>(), d_rec1.as<Rec>());
-                srec = d_rec1.as<Rec>();
+                CCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp, t1, d_pid0.get(), d_pid1.get(), d_idx0.get(), d_idx1.get(), (int)n_rec, 0, bits, st));
+                hipLaunchKernelGGL(k_part_gather, gr, br, 0, st, (unsigned)n_rec, d_idx1, d_rec0, d_rec1);
+                srec = d_rec1;
                 STAGE("partition sort");
             }
             if (dbg) fprintf(stderr, "collapse: round %d, %lld rows, %lld records, %u partitions\n", rounds, (long long)n_cur, (long long)n_rec, P);
-            hipLaunchKernelGGL(k_part_bounds, dim3((P + 1 + 255) / 256), dim3(256), 0, st, d_pid1.as<uint32_t>(), (unsigned)n_rec, bits, P, d_bounds.as<unsigned>());
+            hipLaunchKernelGGL(k_part_bounds, dim3((P + 1 + 255) / 256), dim3(256), 0, st, d_pid1, (unsigned)n_rec, bits, P, d_bounds);
             STAGE("k_part_bounds");
-            hipLaunchKernelGGL(k_part_count, dim3(P), dim3(kPartThreads), 0, st, d_bounds.as<unsigned>(), srec, d_rp.as<uint64_t>(), d_ci.as<int32_t>(), dw, seg_of,
-                               d_first.as<uint32_t>(), d_cntd.as<unsigned long long>(), over[o], &d_cnt.as<Counters>()->n_over[o], (unsigned)n_rec, d_cnt.as<Counters>());
+            hipLaunchKernelGGL(k_part_count, dim3(P), dim3(kPartThreads), 0, st, d_bounds, srec, d_rp, d_ci, dw, seg_of,
+                               d_first, d_cntd, over[o], &d_cnt->n_over[o], (unsigned)n_rec, d_cnt);
             STAGE("k_part_count");
             CCHK(hipGetLastError());
-            CCHK(hipMemcpyAsync(&hc, d_cnt.p, sizeof(Counters), hipMemcpyDeviceToHost, st));
+            CCHK(hipMemcpyAsync(&hc, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, st));
             CCHK(hipStreamSynchronize(st));
         }
         if ((int64_t)hc.n_over[o] > n_rec || (int64_t)hc.n_claimed > n_rows) CFAIL("overflow list or segment count out of range");
@@ -563,12 +566,12 @@ extern "C" int emsar_hip_collapse_rows(emsar_hip_ctx *ctx, int64_t n_rows, int32
         if (++rounds > 64) CFAIL("hash rounds do not terminate");
     }
     const unsigned n_multi = hc.n_claimed;
-    if (n_multi) hipLaunchKernelGGL(k_multi_claim, dim3((n_multi + 255) / 256), dim3(256), 0, st, n_multi, d_claimed.as<uint32_t>());
+    if (n_multi) hipLaunchKernelGGL(k_multi_claim, dim3((n_multi + 255) / 256), dim3(256), 0, st, n_multi, d_claimed);
     if (n_tx > 0)
-        hipLaunchKernelGGL(k_single_claim, dim3((unsigned)((n_tx + 255) / 256)), dim3(256), 0, st, n_tx, d_first1.as<uint32_t>(), d_cnt1.as<unsigned long long>(),
-                           d_claimed.as<uint32_t>(), d_first.as<uint32_t>(), d_cnt.as<Counters>());
+        hipLaunchKernelGGL(k_single_claim, dim3((unsigned)((n_tx + 255) / 256)), dim3(256), 0, st, n_tx, d_first1, d_cnt1,
+                           d_claimed, d_first, d_cnt);
     CCHK(hipGetLastError());
-    CCHK(hipMemcpyAsync(&hc, d_cnt.p, sizeof(Counters), hipMemcpyDeviceToHost, st));
+    CCHK(hipMemcpyAsync(&hc, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, st));
     CCHK(hipStreamSynchronize(st));
     const int64_t nu = (int64_t)hc.n_claimed;
     // every unique row has a member row, and every id of a unique row is an id of the input: anything else means the bookkeeping on the
@@ -579,37 +582,37 @@ extern "C" int emsar_hip_collapse_rows(emsar_hip_ctx *ctx, int64_t n_rows, int32
         // the segments in order of their first occurrence
         const dim3 gu((unsigned)((nu + 255) / 256)), bu(256);
         size_t t1 = 0, t2 = 0;
-        CCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, d_first.as<uint32_t>(), d_sfirst.as<uint32_t>(), d_claimed.as<uint32_t>(), d_sseg.as<uint32_t>(), (int)nu, 0, end_bit, st));
-        CCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, d_ulen.as<uint64_t>(), d_uoff.as<uint64_t>(), (int)nu, st));
+        CCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, d_first.get(), d_sfirst.get(), d_claimed.get(), d_sseg.get(), (int)nu, 0, end_bit, st));
+        CCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, d_ulen.get(), d_uoff.get(), (int)nu, st));
         if (t1 > tmp_bytes || t2 > tmp_bytes) CFAIL("temporary storage of the numbering exceeds the worst case");
-        CCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, t1, d_first.as<uint32_t>(), d_sfirst.as<uint32_t>(), d_claimed.as<uint32_t>(), d_sseg.as<uint32_t>(), (int)nu, 0, end_bit, st));
+        CCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp, t1, d_first.get(), d_sfirst.get(), d_claimed.get(), d_sseg.get(), (int)nu, 0, end_bit, st));
         STAGE("sort by first occurrence");
-        hipLaunchKernelGGL(k_seg_len, gu, bu, 0, st, nu, d_sseg.as<uint32_t>(), d_sfirst.as<uint32_t>(), d_rp.as<uint64_t>(), d_ulen.as<uint64_t>());
-        CCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, t2, d_ulen.as<uint64_t>(), d_uoff.as<uint64_t>(), (int)nu, st));
+        hipLaunchKernelGGL(k_seg_len, gu, bu, 0, st, nu, d_sseg, d_sfirst, d_rp, d_ulen);
+        CCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp, t2, d_ulen.get(), d_uoff.get(), (int)nu, st));
         // the size of the output is known, and checked, before anything is written into it
         uint64_t last_off = 0, last_len = 0;
-        CCHK(hipMemcpyAsync(&last_off, d_uoff.as<uint64_t>() + (nu - 1), 8, hipMemcpyDeviceToHost, st));
-        CCHK(hipMemcpyAsync(&last_len, d_ulen.as<uint64_t>() + (nu - 1), 8, hipMemcpyDeviceToHost, st));
+        CCHK(hipMemcpyAsync(&last_off, d_uoff + (nu - 1), 8, hipMemcpyDeviceToHost, st));
+        CCHK(hipMemcpyAsync(&last_len, d_ulen + (nu - 1), 8, hipMemcpyDeviceToHost, st));
         CCHK(hipStreamSynchronize(st));
         nnz_u = last_off + last_len;
         if (nnz_u > nnz) CFAIL("unique rows hold more ids than the input");
-        hipLaunchKernelGGL(k_row_emit, gu, bu, 0, st, nu, nnz_u, d_sseg.as<uint32_t>(), d_sfirst.as<uint32_t>(), d_rp.as<uint64_t>(), d_ci.as<int32_t>(), d_cntd.as<unsigned long long>(),
-                           d_cnt1.as<unsigned long long>(), d_uid1.as<uint32_t>(), d_uidd.as<uint32_t>(), d_uoff.as<uint64_t>(), d_orp.as<uint64_t>(), d_oci.as<int32_t>(),
-                           d_ow.as<long long>());
+        hipLaunchKernelGGL(k_row_emit, gu, bu, 0, st, nu, nnz_u, d_sseg, d_sfirst, d_rp, d_ci, d_cntd,
+                           d_cnt1, d_uid1, d_uidd, d_uoff, d_orp, d_oci,
+                           d_ow);
     }
     if (row_map_out)
-        hipLaunchKernelGGL(k_row_map, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, n_rows, d_seg.as<uint32_t>(), d_uid1.as<uint32_t>(), d_uidd.as<uint32_t>(), d_map.as<int32_t>());
+        hipLaunchKernelGGL(k_row_map, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, n_rows, d_seg, d_uid1, d_uidd, d_map);
     STAGE("emit + map");
     CCHK(hipGetLastError());
     CCHK(hipEventRecord(ev.b, st));
     std::vector<long long> w64;
     try { w64.resize((size_t)nu); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
     if (nu) {
-        CCHK(hipMemcpyAsync(row_ptr_out, d_orp.p, (size_t)nu * 8, hipMemcpyDeviceToHost, st));
-        CCHK(hipMemcpyAsync(w64.data(), d_ow.p, (size_t)nu * 8, hipMemcpyDeviceToHost, st));
-        if (nnz_u) CCHK(hipMemcpyAsync(col_idx_out, d_oci.p, (size_t)nnz_u * 4, hipMemcpyDeviceToHost, st));
+        CCHK(hipMemcpyAsync(row_ptr_out, d_orp, (size_t)nu * 8, hipMemcpyDeviceToHost, st));
+        CCHK(hipMemcpyAsync(w64.data(), d_ow, (size_t)nu * 8, hipMemcpyDeviceToHost, st));
+        if (nnz_u) CCHK(hipMemcpyAsync(col_idx_out, d_oci, (size_t)nnz_u * 4, hipMemcpyDeviceToHost, st));
     }
-    if (row_map_out) CCHK(hipMemcpyAsync(row_map_out, d_map.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
+    if (row_map_out) CCHK(hipMemcpyAsync(row_map_out, d_map, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
     CCHK(hipStreamSynchronize(st));
     row_ptr_out[nu] = nnz_u;
     for (int64_t i = 0; i < nu; i++) {

@@ -8,6 +8,10 @@
 //
 // One pass is HBM-bound integer streaming plus FP64 adds: ~2 flop per nonzero -- no MFMA.
 // This file: the context, the launch logic (launch_pass, enqueue_cycles, the set solver's driver) and the C ABI of uploads and solves.
+//   context      its device and pinned memory lives in DevBuf / PinBuf owners (devmem.hpp), grouped by lifetime: LayoutDev, TxVectors, GeneMap
+//                and AdjEuma go with the structure, RowWeights and SetsDev with the sample; a group is dropped by assigning an empty one
+//   launch_pass  choose_pass_kernel says which TILED kernel runs (a pure function of weighted, mode, tile count and the two knobs;
+//                emsar_hip_debug_pass_kernel shows it to the tests), one launcher per kernel family launches it
 // resample.hpp (same translation unit, included at the end): the resampling driver and its C ABI -- bootstrap, quantiles, subsampling, genes.
 // Kernels (one translation unit, included below):
 //   kernels_tiled.hpp     k_pass_tiled / k_pass_tiled_multi<2>   the hot ones: one workgroup per tile (or pair of tiles) of the
@@ -40,6 +44,7 @@
 #include "sets.hpp"
 #include "boot_rng.hpp"
 #include "internal.hpp"
+#include "devmem.hpp"
 
 #include "kernels_common.hpp"
 #include "kernels_csr.hpp"
@@ -54,7 +59,77 @@
 // ==================================================================================================
 // context
 // ==================================================================================================
-constexpr int64_t kPairMinTiles = 2048;   // 256 CUs x 4 resident workgroups x 2 tiles
+using emsar::DevBuf;
+using emsar::PinBuf;
+
+// The device memory of the context, grouped by lifetime: each group is dropped by assigning a default-constructed one (devmem.hpp).
+
+// What a sample's connected sets put on the device (ensure_sets), dropped by upload_sample
+struct SetsDev {
+    bool sets_ready = false;
+    emsar::ResidentSets RS;      // index vectors are freed after the upload, counters stay
+    DevBuf<emsar::SetDesc> d_sdesc[emsar::kSetClasses];
+    DevBuf<SetStat> d_sstat; PinBuf<SetStat> h_sstat; int64_t n_sstat = 0;
+    DevBuf<int32_t> d_g_tid; DevBuf<double> d_g_u, d_row_w, d_usum;
+    DevBuf<uint16_t> d_srp, d_sent, d_scp, d_scrow;
+    DevBuf<uint8_t> d_kind;
+    // workgroup-cluster sets (kernels_cluster.hpp)
+    DevBuf<emsar::ClusterDesc> d_cdesc; DevBuf<uint32_t> d_cblk, d_crp, d_ccp, d_cpart;
+    DevBuf<uint16_t> d_cent, d_ccrow; DevBuf<int32_t> d_cg_tid; DevBuf<double> d_cg_u, d_crow_w, d_cscratch;
+    DevBuf<unsigned> d_cbar;             // [2 n]: barrier words, then abort words
+    DevBuf<ClusterStat> d_cstat; PinBuf<ClusterStat> h_cstat;
+    int64_t n_cstat = 0;
+    // bootstrap (emsar_hip_bootstrap): the sample's row weights in caller order and the draw map of the set solver, built on first use
+    DevBuf<int32_t> d_boot_R;
+    DevBuf<int64_t> d_boot_slot;      // caller row -> index into one replicate's [row_w | usum] block, -1 = none
+    int64_t boot_n_rw = 0;            // row_w entries of the resident sets (usum follows them)
+    bool boot_slot_ready = false;
+};
+
+// gene map (emsar_hip_set_gene_map), dropped by upload_structure.  One int32 block: per gene in gene order its transcripts' library
+// indices by ascending caller tid (gene_tx), the chunks' begin offsets into gene_tx (chunk_beg, n_gene_chunks + 1), each chunk's
+// gene when that gene has one chunk, else -1 (chunk_out), and the genes of more than one chunk (gene_multi: gene, first chunk, end)
+struct GeneMap {
+    bool have_genes = false;
+    int32_t n_genes = 0;
+    int64_t n_gene_chunks = 0, n_gene_multi = 0;
+    DevBuf<int32_t> d_gene_blk;
+    int32_t *d_gene_tx = nullptr, *d_chunk_beg = nullptr, *d_chunk_out = nullptr, *d_gene_multi = nullptr;   // views into d_gene_blk
+};
+
+// compute_adjEUMA on the device (emsar_hip_upload_euma), dropped by upload_structure
+struct AdjEuma {
+    DevBuf<int32_t> d_euma_t; int32_t nfl = 0; DevBuf<double> d_wf, d_adj;
+};
+
+// row weights in layout order (0 = row outside F), dropped by upload_sample; an unweighted sample has none
+struct RowWeights { DevBuf<int32_t> d_wgt, d_left_wgt; };
+
+// the matrix in the chosen layout, dropped by upload_structure
+struct LayoutDev {
+    // CSR layout
+    DevBuf<void> d_row_ptr;      // uint32 or uint64
+    DevBuf<int32_t> d_col;
+    // TILED layout
+    emsar::TiledLayout TL;       // host copy keeps slot_row / single_* / left_row (index arrays freed after upload)
+    DevBuf<Tile> d_tiles;
+    DevBuf<Tile> d_utiles; int unit_stride = 1;   // emsar::UnitTables
+    DevBuf<uint32_t> d_units; int64_t n_units = 0;     // units of one or two tiles that share a dictionary (k_pass_tiled_unit)
+    DevBuf<uint32_t> d_fwd, d_bwd;
+    DevBuf<int32_t> d_far;
+    DevBuf<uint64_t> d_left_ptr; DevBuf<int32_t> d_left_col; DevBuf<double> d_left_val;
+    int64_t n_left = 0, n_tiles = 0, n_slots = 0;
+    DevBuf<double> d_u;          // folded single-tid rows: per-transcript weight sum
+    DevBuf<double> d_rowval;     // scratch for scatter passes (den, iEUMA)
+};
+
+// vectors [n_tx], dropped by upload_structure
+struct TxVectors {
+    DevBuf<double> d_den, d_acc;
+    DevBuf<double> d_th[5];      // th0 th1 th2 thx thn
+    DevBuf<double> d_tmp[3];
+    DevBuf<int32_t> d_itmp;
+};
 
 struct emsar_hip_ctx {
     int device = 0;
@@ -63,6 +138,7 @@ struct emsar_hip_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     hipStream_t side[3] = {nullptr, nullptr, nullptr};     // the 256- and 512-thread classes of the set solver and the clusters run next to the 64-thread class
     hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;   // around the cluster launches (stats)
     std::string err;
     // structure
     bool have_structure = false, have_sample = false;
@@ -70,31 +146,17 @@ struct emsar_hip_ctx {
     int64_t n_rows = 0, nnz = 0;
     int32_t n_tx = 0;
     bool ptr64 = false;
-    // CSR layout (device)
-    void *d_row_ptr = nullptr;   // uint32 or uint64
-    int32_t *d_col = nullptr;
-    // TILED layout
-    emsar::TiledLayout TL;       // host copy keeps slot_row / single_* / left_row (index arrays freed after upload)
-    Tile *d_tiles = nullptr;
-    Tile *d_utiles = nullptr; int unit_stride = 1;   // emsar::UnitTables
-    uint32_t *d_units = nullptr; int64_t n_units = 0;     // units of one or two tiles that share a dictionary (k_pass_tiled_unit)
-    uint32_t *d_fwd = nullptr, *d_bwd = nullptr;
-    int32_t *d_far = nullptr;
-    uint64_t *d_left_ptr = nullptr; int32_t *d_left_col = nullptr; int32_t *d_left_wgt = nullptr; double *d_left_val = nullptr;
-    int64_t n_left = 0, n_tiles = 0, n_slots = 0;
-    double *d_u = nullptr;       // folded single-tid rows: per-transcript weight sum
+    LayoutDev lay;
+    TxVectors vec;
+    GeneMap genes;
+    AdjEuma euma;
     // sample
     bool weighted = false;
-    int32_t *d_wgt = nullptr;    // row weights in layout order (0 = row outside F)
-    double *d_rowval = nullptr;  // scratch for scatter passes (den, iEUMA)
+    RowWeights rw;
+    SetsDev sets;
     double loglik_const = 0.0;   // sum_c R_c log E_c over rows inside F
-    // vectors [n_tx]
-    double *d_den = nullptr, *d_acc = nullptr;
-    double *d_th[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // th0 th1 th2 thx thn
-    double *d_tmp[3] = {nullptr, nullptr, nullptr};
-    int32_t *d_itmp = nullptr;
-    Scal *d_scal = nullptr;
-    Scal *h_scal = nullptr;      // pinned
+    DevBuf<Scal> d_scal;
+    PinBuf<Scal> h_scal;
     int64_t bytes_formula = 0, bytes_stored = 0;
     int64_t tl_fwd_slots = 0, tl_n_fslices = 0;
     double count_floor = 0.0;    // stopping-rule floor in reads for the current solve (emsar_em_params.count_floor)
@@ -103,45 +165,17 @@ struct emsar_hip_ctx {
     int64_t graph_launches = 0;  // of the last solve (debug: EMSAR_HIP_DEBUG)
     bool det = false;            // deterministic mode (emsar_hip_set_deterministic / EMSAR_HIP_DETERMINISTIC): fixed-point sums, kernels_common.hpp
     double fx_mass = 0.0, fx_ll = 0.0;   // its scales for the current sample (upload_sample)
-    double *d_sqpart = nullptr;  // per-workgroup partial sums of the SQUAREM vector kernels [4][kSqPart]
+    DevBuf<double> d_sqpart;     // per-workgroup partial sums of the SQUAREM vector kernels [4][kSqPart]
     int update_grid = 1024;       // workgroups of k_update (EMSAR_HIP_UPDATE_GRID)
     int sq_grid = 256;           // workgroups of the SQUAREM vector kernels (EMSAR_HIP_SQ_GRID)
     int weighted_unit = 1;       // EMSAR_HIP_WEIGHTED_UNIT: weighted rows on k_pass_tiled_unit -- 1: the plain EM pass, 2: the likelihood passes too, 0: never
     int tiled_multi = 1;         // EMSAR_HIP_TILED_MULTI 1: two tiles per workgroup (k_pass_tiled_multi) above kPairMinTiles tiles, else one
                                  // (k_pass_tiled); 2: always two; 0: always one
-    const uint8_t *delta_mask = nullptr;   // d_kind while the streaming solve runs next to resident sets
+    const uint8_t *delta_mask = nullptr;   // sets.d_kind while the streaming solve runs next to resident sets
     // set-resident solver (sets.hpp): host copy of the CSR and of the sample's row weights, built lazily by solve
     std::vector<uint64_t> h_row_ptr;
     std::vector<int32_t> h_col, h_wgt;
-    bool sets_ready = false;
-    emsar::ResidentSets RS;      // index vectors are freed after the upload, counters stay
-    emsar::SetDesc *d_sdesc[emsar::kSetClasses] = {nullptr, nullptr, nullptr};
-    SetStat *d_sstat = nullptr; SetStat *h_sstat = nullptr; int64_t n_sstat = 0;
-    // workgroup-cluster sets (kernels_cluster.hpp)
-    emsar::ClusterDesc *d_cdesc = nullptr; uint32_t *d_cblk = nullptr, *d_crp = nullptr, *d_ccp = nullptr, *d_cpart = nullptr;
-    uint16_t *d_cent = nullptr, *d_ccrow = nullptr; int32_t *d_cg_tid = nullptr; double *d_cg_u = nullptr, *d_crow_w = nullptr, *d_cscratch = nullptr;
-    unsigned *d_cbar = nullptr;          // [2 n]: barrier words, then abort words
-    ClusterStat *d_cstat = nullptr, *h_cstat = nullptr;
-    int64_t n_cstat = 0;
-    hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;   // around the cluster launches (stats)
-    int32_t *d_g_tid = nullptr; double *d_g_u = nullptr, *d_row_w = nullptr, *d_usum = nullptr;
-    uint16_t *d_srp = nullptr, *d_sent = nullptr, *d_scp = nullptr, *d_scrow = nullptr;
-    uint8_t *d_kind = nullptr;
     double sets_build_ms = 0.0;
-    // compute_adjEUMA on the device
-    int32_t *d_euma_t = nullptr; int32_t nfl = 0; double *d_wf = nullptr, *d_adj = nullptr;
-    // bootstrap (emsar_hip_bootstrap): the sample's row weights in caller order and the draw map of the set solver, built on first use
-    int32_t *d_boot_R = nullptr;
-    int64_t *d_boot_slot = nullptr;   // caller row -> index into one replicate's [row_w | usum] block, -1 = none
-    int64_t boot_n_rw = 0;            // row_w entries of the resident sets (usum follows them)
-    bool boot_slot_ready = false;
-    // gene map (emsar_hip_set_gene_map), dropped by upload_structure.  One int32 block: per gene in gene order its transcripts' library
-    // indices by ascending caller tid (gene_tx), the chunks' begin offsets into gene_tx (chunk_beg, n_gene_chunks + 1), each chunk's
-    // gene when that gene has one chunk, else -1 (chunk_out), and the genes of more than one chunk (gene_multi: gene, first chunk, end)
-    bool have_genes = false;
-    int32_t n_genes = 0;
-    int64_t n_gene_chunks = 0, n_gene_multi = 0;
-    int32_t *d_gene_blk = nullptr, *d_gene_tx = nullptr, *d_chunk_beg = nullptr, *d_chunk_out = nullptr, *d_gene_multi = nullptr;
 };
 
 namespace {
@@ -155,19 +189,10 @@ namespace {
         }                                                                                              \
     } while (0)
 
-inline void dfree(void *p) { if (p) (void)hipFree(p); }
-
 inline int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
 
-// a new device buffer (16 bytes at least) filled from the host
-inline hipError_t upload_new(void **dp, const void *src, size_t bytes) {
-    hipError_t e = hipMalloc(dp, std::max<size_t>(bytes, 16));
-    if (e == hipSuccess && bytes) e = hipMemcpy(*dp, src, bytes, hipMemcpyHostToDevice);
-    return e;
-}
 // per-solve state, cleared whatever the exit of a solve
 inline void clear_solve_state(emsar_hip_ctx *ctx) { ctx->count_floor = 0.0; ctx->zero_cut = 0.0; ctx->delta_mask = nullptr; }
-inline void free_row_weights(emsar_hip_ctx *ctx) { dfree(ctx->d_wgt); dfree(ctx->d_left_wgt); ctx->d_wgt = ctx->d_left_wgt = nullptr; }
 // deterministic mode's scales for a sample of `total` reads: no transcript is assigned more reads than the sample holds, |sum R log S| <= N * 745
 inline void set_fx_scales(emsar_hip_ctx *ctx, int64_t total) {
     int e_mass = 0, e_ll = 0;
@@ -179,7 +204,7 @@ inline void set_fx_scales(emsar_hip_ctx *ctx, int64_t total) {
 
 // The TILED layout may number the transcripts itself (renumber.hpp); every T-sized device vector is then in the LIBRARY's numbering and
 // the ABI maps: lib[new_of_old[t]] = caller[t].  Empty map = the caller's numbering.
-inline const std::vector<int32_t> &tid_map(const emsar_hip_ctx *ctx) { return ctx->TL.new_of_old; }
+inline const std::vector<int32_t> &tid_map(const emsar_hip_ctx *ctx) { return ctx->lay.TL.new_of_old; }
 inline const double *to_lib(const emsar_hip_ctx *ctx, const double *caller, std::vector<double> &tmp) {
     const auto &m = tid_map(ctx);
     if (m.empty() || ctx->layout != EMSAR_LAYOUT_TILED) return caller;
@@ -196,137 +221,140 @@ inline void from_lib(const emsar_hip_ctx *ctx, double *v /* in place: library or
 
 // bytes one pass actually streams in the chosen layout: index arrays + row weights + the T-sized vectors
 inline int64_t stored_bytes(const emsar_hip_ctx *ctx) {
-    int64_t rows = ctx->layout == EMSAR_LAYOUT_TILED ? ctx->n_slots + ctx->n_left : ctx->n_rows;
+    int64_t rows = ctx->layout == EMSAR_LAYOUT_TILED ? ctx->lay.n_slots + ctx->lay.n_left : ctx->n_rows;
     return ctx->bytes_stored + (ctx->weighted ? 4 * rows : 0) + (ctx->layout == EMSAR_LAYOUT_TILED ? 40 : 32) * (int64_t)ctx->n_tx;
 }
 
-void free_sets(emsar_hip_ctx *ctx) {
-    for (auto &p : ctx->d_sdesc) { dfree(p); p = nullptr; }
-    dfree(ctx->d_sstat); ctx->d_sstat = nullptr;
-    if (ctx->h_sstat) { (void)hipHostFree(ctx->h_sstat); ctx->h_sstat = nullptr; }
-    dfree(ctx->d_g_tid); dfree(ctx->d_g_u); dfree(ctx->d_row_w); dfree(ctx->d_usum);
-    dfree(ctx->d_srp); dfree(ctx->d_sent); dfree(ctx->d_scp); dfree(ctx->d_scrow); dfree(ctx->d_kind);
-    ctx->d_g_tid = nullptr; ctx->d_g_u = ctx->d_row_w = ctx->d_usum = nullptr;
-    ctx->d_srp = ctx->d_sent = ctx->d_scp = ctx->d_scrow = nullptr; ctx->d_kind = nullptr;
-    dfree(ctx->d_cdesc); dfree(ctx->d_cblk); dfree(ctx->d_crp); dfree(ctx->d_ccp); dfree(ctx->d_cpart); dfree(ctx->d_cent); dfree(ctx->d_ccrow);
-    dfree(ctx->d_cg_tid); dfree(ctx->d_cg_u); dfree(ctx->d_crow_w); dfree(ctx->d_cscratch); dfree(ctx->d_cbar); dfree(ctx->d_cstat);
-    if (ctx->h_cstat) { (void)hipHostFree(ctx->h_cstat); ctx->h_cstat = nullptr; }
-    ctx->d_cdesc = nullptr; ctx->d_cblk = ctx->d_crp = ctx->d_ccp = ctx->d_cpart = nullptr; ctx->d_cent = ctx->d_ccrow = nullptr;
-    ctx->d_cg_tid = nullptr; ctx->d_cg_u = ctx->d_crow_w = ctx->d_cscratch = nullptr; ctx->d_cbar = nullptr; ctx->d_cstat = nullptr; ctx->n_cstat = 0;
-    ctx->RS = emsar::ResidentSets(); ctx->sets_ready = false; ctx->n_sstat = 0;
-    dfree(ctx->d_boot_R); dfree(ctx->d_boot_slot); ctx->d_boot_R = nullptr; ctx->d_boot_slot = nullptr;
-    ctx->boot_n_rw = 0; ctx->boot_slot_ready = false;
-}
-
-void free_genes(emsar_hip_ctx *ctx) {
-    dfree(ctx->d_gene_blk);
-    ctx->d_gene_blk = ctx->d_gene_tx = ctx->d_chunk_beg = ctx->d_chunk_out = ctx->d_gene_multi = nullptr;
-    ctx->have_genes = false; ctx->n_genes = 0; ctx->n_gene_chunks = ctx->n_gene_multi = 0;
-}
-
+// the structure and all that hangs on it: the sample, its sets, the gene map, the adjEUMA arrays
 void free_structure(emsar_hip_ctx *ctx) {
-    free_sets(ctx);
-    free_genes(ctx);
-    dfree(ctx->d_euma_t); dfree(ctx->d_wf); dfree(ctx->d_adj); ctx->d_euma_t = nullptr; ctx->d_wf = ctx->d_adj = nullptr; ctx->nfl = 0;
+    ctx->sets = SetsDev(); ctx->rw = RowWeights();
+    ctx->genes = GeneMap(); ctx->euma = AdjEuma();
+    ctx->lay = LayoutDev(); ctx->vec = TxVectors();
     std::vector<uint64_t>().swap(ctx->h_row_ptr); std::vector<int32_t>().swap(ctx->h_col); std::vector<int32_t>().swap(ctx->h_wgt);
-    dfree(ctx->d_row_ptr); dfree(ctx->d_col);
-    ctx->d_row_ptr = nullptr; ctx->d_col = nullptr;
-    dfree(ctx->d_wgt); dfree(ctx->d_rowval); ctx->d_wgt = nullptr; ctx->d_rowval = nullptr;
-    dfree(ctx->d_units); ctx->d_units = nullptr; ctx->n_units = 0;
-    dfree(ctx->d_utiles); ctx->d_utiles = nullptr;
-    dfree(ctx->d_tiles); dfree(ctx->d_fwd); dfree(ctx->d_bwd); dfree(ctx->d_far);
-    dfree(ctx->d_left_ptr); dfree(ctx->d_left_col); dfree(ctx->d_left_wgt); dfree(ctx->d_left_val); dfree(ctx->d_u);
-    ctx->d_tiles = nullptr; ctx->d_fwd = ctx->d_bwd = nullptr; ctx->d_far = nullptr;
-    ctx->d_left_ptr = nullptr; ctx->d_left_col = nullptr; ctx->d_left_wgt = nullptr; ctx->d_left_val = nullptr; ctx->d_u = nullptr;
-    ctx->TL = emsar::TiledLayout(); ctx->n_left = ctx->n_tiles = ctx->n_slots = 0;
-    dfree(ctx->d_den); dfree(ctx->d_acc); ctx->d_den = nullptr; ctx->d_acc = nullptr;
-    for (auto &p : ctx->d_th) { dfree(p); p = nullptr; }
-    for (auto &p : ctx->d_tmp) { dfree(p); p = nullptr; }
-    dfree(ctx->d_itmp); ctx->d_itmp = nullptr;
     ctx->have_structure = ctx->have_sample = false;
 }
 
 // the fixed-point scales the EM kernels get (zeros = plain FP64 atomics; scatter passes always)
 inline Fx fx_of(const emsar_hip_ctx *ctx, int mode = MODE_EM) { return (ctx->det && mode != MODE_SCATTER) ? Fx{ctx->fx_mass, ctx->fx_ll} : Fx{0.0, 0.0}; }
 
+// ---- which TILED pass kernel runs: a pure function of the sample, the mode, the size and the two knobs ----
+constexpr int64_t kPairMinTiles = 2048;   // 256 CUs x 4 resident workgroups x 2 tiles
+enum PassFamily { FAMILY_TILE, FAMILY_MULTI, FAMILY_UNIT };      // k_pass_tiled, k_pass_tiled_multi, k_pass_tiled_unit
+struct PassKernel { PassFamily family; bool weighted; int mode; int n_multi; /* tiles per workgroup, FAMILY_MULTI only */ };
+
+PassKernel choose_pass_kernel(bool weighted, int mode, int64_t n_tiles, int tiled_multi, int weighted_unit) {
+    if (mode == MODE_SCATTER) return {FAMILY_TILE, false, MODE_SCATTER, 0};
+    const bool above = tiled_multi == 1 && n_tiles > kPairMinTiles;
+    if (!weighted && (tiled_multi >= 2 || above)) {
+        // more than one tile per workgroup.  Unweighted rows only: with the row weights in registers as well the body does not
+        // fit 128 VGPRs (round 1, two tiles: 0.218 vs 0.179 ms; round 2, the unit kernel on merged rows, 72-92 B of scratch:
+        // 0.124 vs 0.103 ms with one tile per workgroup; with the weights kept as integers its EM variant fits without
+        // scratch and runs config 3's merged rows in 0.0959 ms against 0.0956 ms for one tile per workgroup: no gain,
+        // and the likelihood variant -- twelve logs -- still spills).
+        // Only when the tiles outnumber the chip's workgroup slots: below that a pass is one workgroup's latency, and
+        // a pair takes twice as long as a tile (40 k reads: 47 -> 26 us per pass with one tile per workgroup)
+        if (tiled_multi == 1 || tiled_multi == 5) return {FAMILY_UNIT, false, mode, 0};      // units: one dictionary for up to two tiles
+        return {FAMILY_MULTI, false, mode, tiled_multi == 3 ? 3 : tiled_multi == 4 ? 4 : 2};
+    }
+    if (weighted && (weighted_unit == 2 || (weighted_unit == 1 && mode == MODE_EM)) && (tiled_multi == 5 || above)) {
+        // weighted rows (segments with read counts, merged rows) on the unit kernel: the weights are loaded as integers after the
+        // forward batch is consumed; both variants fit 128 VGPRs without scratch (round 3).  Measured on the collapsed form of
+        // config 3 (14.0 M segments of the family law / 5.4 M of the window law): plain pass 0.1273 -> 0.1221 / 0.0964 -> 0.0962 ms;
+        // the likelihood variant takes its twelve logs per lane in one rolled loop (tile_e_step) and is SLOWER than the one-tile
+        // kernel's unrolled logs (solve 0.161 against 0.150 ms per pass), so by default (1) only the plain EM pass of a SQUAREM
+        // cycle runs here and the two likelihood passes stay with k_pass_tiled; 2 = both, 0 = neither (EMSAR_HIP_WEIGHTED_UNIT)
+        return {FAMILY_UNIT, true, mode, 0};
+    }
+    return {FAMILY_TILE, weighted, mode, 0};
+}
+
+// ---- launchers: one per kernel family, the template arguments as tag values ----
+template <bool B> using BoolC = std::integral_constant<bool, B>;
+template <int M> using ModeC = std::integral_constant<int, M>;
+// f(mode tag) / f(weighted tag, mode tag) for a pass of the E- and M-step, with or without the likelihood
+template <class F> void with_em_mode(int mode, const F &f) { if (mode == MODE_EM_LL) f(ModeC<MODE_EM_LL>()); else f(ModeC<MODE_EM>()); }
+template <class F> void with_em_variant(bool weighted, int mode, const F &f) {
+    if (weighted) with_em_mode(mode, [&](auto md) { f(BoolC<true>(), md); });
+    else with_em_mode(mode, [&](auto md) { f(BoolC<false>(), md); });
+}
+
+constexpr size_t kTiledLds = (size_t)kTiledLdsDoubles * sizeof(double);
+struct PassArgs { const double *theta; double *acc, *ll_out; Fx fx; };
+
+template <bool WT, int MD> void launch_tile(BoolC<WT>, ModeC<MD>, emsar_hip_ctx *ctx, const PassArgs &a) {
+    const LayoutDev &L = ctx->lay;
+    hipLaunchKernelGGL((k_pass_tiled<WT, MD>), dim3((unsigned)L.n_tiles), dim3(kTiledThreads), kTiledLds, ctx->stream, L.d_tiles, L.d_fwd, L.d_bwd,
+                       L.d_far, ctx->rw.d_wgt, L.d_rowval, a.theta, a.acc, a.ll_out, a.fx);
+}
+template <bool WT, int MD, int N> void launch_multi(BoolC<WT>, ModeC<MD>, std::integral_constant<int, N>, emsar_hip_ctx *ctx, const PassArgs &a) {
+    const LayoutDev &L = ctx->lay;
+    hipLaunchKernelGGL((k_pass_tiled_multi<WT, MD, N>), dim3((unsigned)((L.n_tiles + N - 1) / N)), dim3(kTiledThreads), kTiledLds, ctx->stream, L.d_tiles,
+                       (int)L.n_tiles, L.d_fwd, L.d_bwd, L.d_far, ctx->rw.d_wgt, a.theta, a.acc, a.ll_out, a.fx);
+}
+template <bool WT, int MD> void launch_unit(BoolC<WT>, ModeC<MD>, emsar_hip_ctx *ctx, const PassArgs &a) {
+    const LayoutDev &L = ctx->lay;
+    hipLaunchKernelGGL((k_pass_tiled_unit<WT, MD>), dim3((unsigned)L.n_units), dim3(kTiledThreads), kTiledLds, ctx->stream, L.d_utiles, L.unit_stride,
+                       L.d_far, L.d_fwd, L.d_bwd, ctx->rw.d_wgt, a.theta, a.acc, a.ll_out, a.fx);
+}
+// the CSR kernel: the caller's rows (32- or 64-bit row_ptr), or the leftover rows of TILED
+template <class PT, bool WT, int MD>
+void launch_csr_rows(emsar_hip_ctx *ctx, unsigned max_grid, int64_t n_rows, const PT *row_ptr, const int32_t *col, const int32_t *wgt, const double *val, const PassArgs &a) {
+    hipLaunchKernelGGL((k_pass_csr<PT, WT, MD>), dim3((unsigned)std::min<int64_t>((n_rows + 255) / 256, max_grid)), dim3(256), 0, ctx->stream, n_rows, row_ptr,
+                       col, wgt, val, a.theta, a.acc, a.ll_out, a.fx);
+}
+template <bool WT, int MD> void launch_left(BoolC<WT>, ModeC<MD>, emsar_hip_ctx *ctx, const PassArgs &a) {
+    const LayoutDev &L = ctx->lay;
+    launch_csr_rows<uint64_t, WT, MD>(ctx, 8192, L.n_left, L.d_left_ptr, L.d_left_col, ctx->rw.d_left_wgt, L.d_left_val, a);
+}
+template <bool WT, int MD> void launch_csr(BoolC<WT>, ModeC<MD>, emsar_hip_ctx *ctx, const PassArgs &a) {
+    const LayoutDev &L = ctx->lay;
+    if (ctx->ptr64) launch_csr_rows<uint64_t, WT, MD>(ctx, 256 * 32, ctx->n_rows, (const uint64_t *)L.d_row_ptr.get(), L.d_col, ctx->rw.d_wgt, L.d_rowval, a);
+    else launch_csr_rows<uint32_t, WT, MD>(ctx, 256 * 32, ctx->n_rows, (const uint32_t *)L.d_row_ptr.get(), L.d_col, ctx->rw.d_wgt, L.d_rowval, a);
+}
+
+// the dynamic LDS of the TILED kernels, for every instantiation choose_pass_kernel can return (once per upload_structure)
+hipError_t set_tiled_lds_attributes() {
+    hipError_t e = hipSuccess;
+    auto set = [&](auto *kernel) { if (e == hipSuccess) e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTiledLds); };
+    set(k_pass_tiled<false, MODE_SCATTER>);
+    for (const bool weighted : {false, true})
+        for (const int mode : {MODE_EM, MODE_EM_LL})
+            with_em_variant(weighted, mode, [&](auto wt, auto md) { set(k_pass_tiled<wt(), md()>); set(k_pass_tiled_unit<wt(), md()>); });
+    for (const int mode : {MODE_EM, MODE_EM_LL})
+        with_em_mode(mode, [&](auto md) { set(k_pass_tiled_multi<false, md(), 2>); set(k_pass_tiled_multi<false, md(), 3>); set(k_pass_tiled_multi<false, md(), 4>); });
+    return e;
+}
+
 // one pass of the chosen layout.  mode: MODE_EM / MODE_EM_LL / MODE_SCATTER
 int launch_pass(emsar_hip_ctx *ctx, int mode, const double *theta, double *acc, double *ll_out, bool rows_only = false /* the folded rows' likelihood terms are added by the caller */) {
+    const PassArgs a{theta, acc, ll_out, fx_of(ctx, mode)};
+    const bool scatter = mode == MODE_SCATTER;
     if (ctx->layout == EMSAR_LAYOUT_TILED) {
-        const size_t lds = (size_t)kTiledLdsDoubles * sizeof(double);
-        if (ctx->n_tiles > 0) {
-            dim3 grid((unsigned)ctx->n_tiles), block(kTiledThreads);
-#define LAUNCH_T(WT, MD)                                                                                          \
-    hipLaunchKernelGGL((k_pass_tiled<WT, MD>), grid, block, lds, ctx->stream, ctx->d_tiles, ctx->d_fwd, ctx->d_bwd,   \
-                       ctx->d_far, ctx->d_wgt, ctx->d_rowval, theta, acc, ll_out, fx_of(ctx, mode))
-#define LAUNCH_PN(WT, MD, NN)                                                                                     \
-    hipLaunchKernelGGL((k_pass_tiled_multi<WT, MD, NN>), dim3((unsigned)((ctx->n_tiles + NN - 1) / NN)), block, lds, ctx->stream, ctx->d_tiles,  \
-                       (int)ctx->n_tiles, ctx->d_fwd, ctx->d_bwd, ctx->d_far, ctx->d_wgt, theta, acc, ll_out, fx_of(ctx, mode))
-#define LAUNCH_P(WT, MD) LAUNCH_PN(WT, MD, 2)
-            if (mode == MODE_SCATTER) LAUNCH_T(false, MODE_SCATTER);
-            else if (!ctx->weighted && (ctx->tiled_multi >= 2 || (ctx->tiled_multi == 1 && ctx->n_tiles > kPairMinTiles))) {
-                // more than one tile per workgroup.  Unweighted rows only: with the row weights in registers as well the body does not
-                // fit 128 VGPRs (round 1, two tiles: 0.218 vs 0.179 ms; round 2, the unit kernel on merged rows, 72-92 B of scratch:
-                // 0.124 vs 0.103 ms with one tile per workgroup; with the weights kept as integers its EM variant fits without
-                // scratch and runs config 3's merged rows in 0.0959 ms against 0.0956 ms for one tile per workgroup: no gain,
-                // and the likelihood variant -- twelve logs -- still spills).
-                // Only when the tiles outnumber the chip's workgroup slots: below that a pass is one workgroup's latency, and
-                // a pair takes twice as long as a tile (40 k reads: 47 -> 26 us per pass with one tile per workgroup)
-                if (ctx->tiled_multi == 1 || ctx->tiled_multi == 5) {         // units: one dictionary for up to two tiles
-#define LAUNCH_U(WT, MD) hipLaunchKernelGGL((k_pass_tiled_unit<WT, MD>), dim3((unsigned)ctx->n_units), block, lds, ctx->stream, ctx->d_utiles, ctx->unit_stride, \
-                                           ctx->d_far, ctx->d_fwd, ctx->d_bwd, ctx->d_wgt, theta, acc, ll_out, fx_of(ctx, mode))
-                    if (mode == MODE_EM_LL) LAUNCH_U(false, MODE_EM_LL); else LAUNCH_U(false, MODE_EM);
-#undef LAUNCH_U
-                }
-                else if (ctx->tiled_multi == 3) { if (mode == MODE_EM_LL) LAUNCH_PN(false, MODE_EM_LL, 3); else LAUNCH_PN(false, MODE_EM, 3); }
-                else if (ctx->tiled_multi == 4) { if (mode == MODE_EM_LL) LAUNCH_PN(false, MODE_EM_LL, 4); else LAUNCH_PN(false, MODE_EM, 4); }
-                else if (mode == MODE_EM_LL) LAUNCH_P(false, MODE_EM_LL); else LAUNCH_P(false, MODE_EM);
-            }
-            else if (ctx->weighted && (ctx->weighted_unit == 2 || (ctx->weighted_unit == 1 && mode == MODE_EM)) &&
-                     (ctx->tiled_multi == 5 || (ctx->tiled_multi == 1 && ctx->n_tiles > kPairMinTiles))) {
-                // weighted rows (segments with read counts, merged rows) on the unit kernel: the weights are loaded as integers after the
-                // forward batch is consumed; both variants fit 128 VGPRs without scratch (round 3).  Measured on the collapsed form of
-                // config 3 (14.0 M segments of the family law / 5.4 M of the window law): plain pass 0.1273 -> 0.1221 / 0.0964 -> 0.0962 ms;
-                // the likelihood variant takes its twelve logs per lane in one rolled loop (tile_e_step) and is SLOWER than the one-tile
-                // kernel's unrolled logs (solve 0.161 against 0.150 ms per pass), so by default (1) only the plain EM pass of a SQUAREM
-                // cycle runs here and the two likelihood passes stay with k_pass_tiled; 2 = both, 0 = neither (EMSAR_HIP_WEIGHTED_UNIT)
-                hipLaunchKernelGGL((mode == MODE_EM_LL ? k_pass_tiled_unit<true, MODE_EM_LL> : k_pass_tiled_unit<true, MODE_EM>), dim3((unsigned)ctx->n_units), block, lds,
-                                   ctx->stream, ctx->d_utiles, ctx->unit_stride, ctx->d_far, ctx->d_fwd, ctx->d_bwd, ctx->d_wgt, theta, acc, ll_out,
-                                   fx_of(ctx, mode), (unsigned long long *)nullptr);
-            }
-            else if (ctx->weighted) { if (mode == MODE_EM_LL) LAUNCH_T(true, MODE_EM_LL); else LAUNCH_T(true, MODE_EM); }
-            else { if (mode == MODE_EM_LL) LAUNCH_T(false, MODE_EM_LL); else LAUNCH_T(false, MODE_EM); }
-#undef LAUNCH_P
-#undef LAUNCH_PN
-#undef LAUNCH_T
+        if (ctx->lay.n_tiles > 0) {
+            const PassKernel k = choose_pass_kernel(ctx->weighted, mode, ctx->lay.n_tiles, ctx->tiled_multi, ctx->weighted_unit);
+            if (scatter) launch_tile(BoolC<false>(), ModeC<MODE_SCATTER>(), ctx, a);
+            else if (k.family == FAMILY_TILE) with_em_variant(k.weighted, k.mode, [&](auto wt, auto md) { launch_tile(wt, md, ctx, a); });
+            else if (k.family == FAMILY_UNIT) with_em_variant(k.weighted, k.mode, [&](auto wt, auto md) { launch_unit(wt, md, ctx, a); });
+            else with_em_mode(k.mode, [&](auto md) {
+                using std::integral_constant;
+                if (k.n_multi == 3) launch_multi(BoolC<false>(), md, integral_constant<int, 3>(), ctx, a);
+                else if (k.n_multi == 4) launch_multi(BoolC<false>(), md, integral_constant<int, 4>(), ctx, a);
+                else launch_multi(BoolC<false>(), md, integral_constant<int, 2>(), ctx, a);
+            });
         }
-        if (ctx->n_left > 0) {   // rows too long for a tile: generic CSR kernel on the leftover
-            dim3 grid((unsigned)std::min<int64_t>((ctx->n_left + 255) / 256, 8192)), block(256);
-#define LAUNCH_L(WT, MD)                                                                                          \
-    hipLaunchKernelGGL((k_pass_csr<uint64_t, WT, MD>), grid, block, 0, ctx->stream, ctx->n_left, ctx->d_left_ptr,     \
-                       ctx->d_left_col, ctx->d_left_wgt, ctx->d_left_val, theta, acc, ll_out, fx_of(ctx, mode))
-            if (mode == MODE_SCATTER) LAUNCH_L(false, MODE_SCATTER);
-            else if (ctx->weighted) { if (mode == MODE_EM_LL) LAUNCH_L(true, MODE_EM_LL); else LAUNCH_L(true, MODE_EM); }
-            else { if (mode == MODE_EM_LL) LAUNCH_L(false, MODE_EM_LL); else LAUNCH_L(false, MODE_EM); }
-#undef LAUNCH_L
+        if (ctx->lay.n_left > 0) {   // rows too long for a tile: generic CSR kernel on the leftover
+            if (scatter) launch_left(BoolC<false>(), ModeC<MODE_SCATTER>(), ctx, a);
+            else with_em_variant(ctx->weighted, mode, [&](auto wt, auto md) { launch_left(wt, md, ctx, a); });
         }
         if (mode == MODE_EM_LL && !rows_only)
             hipLaunchKernelGGL(k_single_ll, dim3(std::min(grid_for(ctx->n_tx, 256), 256)), dim3(256), 0, ctx->stream, ctx->n_tx,
-                               ctx->d_u, theta, ll_out, fx_of(ctx).ll);
+                               ctx->lay.d_u, theta, ll_out, fx_of(ctx).ll);
         HIPCHK(hipGetLastError());
         return EMSAR_HIP_OK;
     }
     if (ctx->n_rows == 0) return EMSAR_HIP_OK;
-    int64_t blocks = (ctx->n_rows + 255) / 256;
-    dim3 grid((unsigned)std::min<int64_t>(blocks, 256 * 32)), block(256);
-#define LAUNCH_C(PT, WT, MD)                                                                                     \
-    hipLaunchKernelGGL((k_pass_csr<PT, WT, MD>), grid, block, 0, ctx->stream, ctx->n_rows, (const PT *)ctx->d_row_ptr, \
-                       ctx->d_col, ctx->d_wgt, ctx->d_rowval, theta, acc, ll_out, fx_of(ctx, mode))
-#define LAUNCH_CP(WT, MD) do { if (ctx->ptr64) LAUNCH_C(uint64_t, WT, MD); else LAUNCH_C(uint32_t, WT, MD); } while (0)
-    if (mode == MODE_SCATTER) LAUNCH_CP(false, MODE_SCATTER);
-    else if (ctx->weighted) { if (mode == MODE_EM_LL) LAUNCH_CP(true, MODE_EM_LL); else LAUNCH_CP(true, MODE_EM); }
-    else { if (mode == MODE_EM_LL) LAUNCH_CP(false, MODE_EM_LL); else LAUNCH_CP(false, MODE_EM); }
-#undef LAUNCH_CP
-#undef LAUNCH_C
+    if (scatter) launch_csr(BoolC<false>(), ModeC<MODE_SCATTER>(), ctx, a);
+    else with_em_variant(ctx->weighted, mode, [&](auto wt, auto md) { launch_csr(wt, md, ctx, a); });
     HIPCHK(hipGetLastError());
     return EMSAR_HIP_OK;
 }
@@ -342,10 +370,10 @@ inline double host_ll(const emsar_hip_ctx *ctx, int i) {
 
 // th_out = EM(th_in); ll slot receives sum R log S at th_in when want_ll
 int em_pass(emsar_hip_ctx *ctx, const double *th_in, double *th_out, bool want_ll, int ll_slot, double abs_floor, int to_delta1 = 0) {
-    int rc = launch_pass(ctx, want_ll ? MODE_EM_LL : MODE_EM, th_in, ctx->d_acc, &ctx->d_scal->ll[ll_slot].s[0].v);
+    int rc = launch_pass(ctx, want_ll ? MODE_EM_LL : MODE_EM, th_in, ctx->vec.d_acc, &ctx->d_scal->ll[ll_slot].s[0].v);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_update, dim3(std::min(grid_for(ctx->n_tx, 256), ctx->update_grid)), dim3(256), 0, ctx->stream, ctx->n_tx, th_in, ctx->d_acc,
-                       ctx->d_den, ctx->layout == EMSAR_LAYOUT_TILED ? ctx->d_u : nullptr, th_out, abs_floor, ctx->count_floor, ctx->zero_cut, ctx->d_scal,
+    hipLaunchKernelGGL(k_update, dim3(std::min(grid_for(ctx->n_tx, 256), ctx->update_grid)), dim3(256), 0, ctx->stream, ctx->n_tx, th_in, ctx->vec.d_acc,
+                       ctx->vec.d_den, ctx->layout == EMSAR_LAYOUT_TILED ? ctx->lay.d_u.get() : nullptr, th_out, abs_floor, ctx->count_floor, ctx->zero_cut, ctx->d_scal,
                        ctx->delta_mask, to_delta1, fx_of(ctx).mass);
     HIPCHK(hipGetLastError());
     return EMSAR_HIP_OK;
@@ -353,10 +381,10 @@ int em_pass(emsar_hip_ctx *ctx, const double *th_in, double *th_out, bool want_l
 
 // `cycles` cycles of the streaming solve on ctx->stream -- launched, or recorded when the stream is capturing.
 // One cycle = one plain EM pass, or one SQUAREM cycle of three passes (8 launches, see k_update_p2).  The current point is
-// ctx->d_th[0] before and after (plain EM swaps d_th[0]/d_th[1] on the host: record an even count).
+// ctx->vec.d_th[0] before and after (plain EM swaps d_th[0]/d_th[1] on the host: record an even count).
 int enqueue_cycles(emsar_hip_ctx *ctx, const emsar_em_params &p, double abs_step_base, int cycles) {
     const int n = ctx->n_tx, g = grid_for(n, 256);
-    double **th = ctx->d_th;
+    DevBuf<double> *th = ctx->vec.d_th;     // handles: plain EM swaps two of them
     int rc;
     for (int c = 0; c < cycles; c++) {
         hipLaunchKernelGGL(k_cycle_begin, dim3(1), dim3(kLlSlots), 0, ctx->stream, ctx->d_scal, abs_step_base, p.accel ? 3 : 1);
@@ -366,14 +394,14 @@ int enqueue_cycles(emsar_hip_ctx *ctx, const emsar_em_params &p, double abs_step
             continue;
         }
         // the stopping rule is measured on the first (plain) step of the cycle only (delta1_bits)
-        const double *u = ctx->layout == EMSAR_LAYOUT_TILED ? ctx->d_u : nullptr;
+        const double *u = ctx->layout == EMSAR_LAYOUT_TILED ? ctx->lay.d_u.get() : nullptr;
         const dim3 gv((unsigned)std::min(std::min(g, ctx->sq_grid), kSqPart)), bv(256);
         if ((rc = em_pass(ctx, th[0], th[1], false, 0, p.abs_floor, 1))) return rc;
-        if ((rc = launch_pass(ctx, MODE_EM_LL, th[1], ctx->d_acc, &ctx->d_scal->ll[1].s[0].v, true))) return rc;
-        hipLaunchKernelGGL(k_update_p2, gv, bv, 0, ctx->stream, n, th[0], th[1], ctx->d_acc, ctx->d_den, u, th[2], ctx->d_scal, ctx->d_sqpart, fx_of(ctx));
-        hipLaunchKernelGGL(k_sq_extrap_ll, gv, bv, 0, ctx->stream, n, th[0], th[1], th[2], ctx->d_den, u, th[3], ctx->d_scal, ctx->d_sqpart, (int)gv.x, fx_of(ctx));
-        if ((rc = launch_pass(ctx, MODE_EM_LL, th[3], ctx->d_acc, &ctx->d_scal->ll[2].s[0].v, true))) return rc;
-        hipLaunchKernelGGL(k_update_p3, gv, bv, 0, ctx->stream, n, th[3], th[2], ctx->d_acc, ctx->d_den, u, th[0], ctx->d_scal, ctx->d_sqpart, (int)gv.x, fx_of(ctx));
+        if ((rc = launch_pass(ctx, MODE_EM_LL, th[1], ctx->vec.d_acc, &ctx->d_scal->ll[1].s[0].v, true))) return rc;
+        hipLaunchKernelGGL(k_update_p2, gv, bv, 0, ctx->stream, n, th[0], th[1], ctx->vec.d_acc, ctx->vec.d_den, u, th[2], ctx->d_scal, ctx->d_sqpart, fx_of(ctx));
+        hipLaunchKernelGGL(k_sq_extrap_ll, gv, bv, 0, ctx->stream, n, th[0], th[1], th[2], ctx->vec.d_den, u, th[3], ctx->d_scal, ctx->d_sqpart, (int)gv.x, fx_of(ctx));
+        if ((rc = launch_pass(ctx, MODE_EM_LL, th[3], ctx->vec.d_acc, &ctx->d_scal->ll[2].s[0].v, true))) return rc;
+        hipLaunchKernelGGL(k_update_p3, gv, bv, 0, ctx->stream, n, th[3], th[2], ctx->vec.d_acc, ctx->vec.d_den, u, th[0], ctx->d_scal, ctx->d_sqpart, (int)gv.x, fx_of(ctx));
         HIPCHK(hipGetLastError());
     }
     return EMSAR_HIP_OK;
@@ -405,7 +433,7 @@ int layout_weights(const emsar_hip_ctx *ctx, const WeightOf &weight_of, const do
         }
         return EMSAR_HIP_OK;
     }
-    const auto &L = ctx->TL;
+    const auto &L = ctx->lay.TL;
     out.u.assign((size_t)ctx->n_tx, 0.0);
     for (size_t i = 0; i < L.single_row.size(); i++) {
         int32_t x = weight_of(L.single_row[i]);
@@ -413,9 +441,9 @@ int layout_weights(const emsar_hip_ctx *ctx, const WeightOf &weight_of, const do
         if (x > 0 && row_E) llc += (double)x * std::log(row_E[L.single_row[i]]);
     }
     if (!weighted) return EMSAR_HIP_OK;
-    out.w.assign((size_t)std::max<int64_t>(ctx->n_slots, 1), 0);
-    out.wl.assign((size_t)std::max<int64_t>(ctx->n_left, 1), 0);
-    for (int64_t i = 0; i < ctx->n_slots; i++) {
+    out.w.assign((size_t)std::max<int64_t>(ctx->lay.n_slots, 1), 0);
+    out.wl.assign((size_t)std::max<int64_t>(ctx->lay.n_left, 1), 0);
+    for (int64_t i = 0; i < ctx->lay.n_slots; i++) {
         int64_t r = L.slot_row[(size_t)i];
         if (r < 0) continue;
         if (L.merged) {                                   // a slot stands for all rows with this tid multiset
@@ -434,7 +462,7 @@ int layout_weights(const emsar_hip_ctx *ctx, const WeightOf &weight_of, const do
         out.w[(size_t)i] = x;
         if (x > 0 && row_E) llc += (double)x * std::log(row_E[r]);
     }
-    for (int64_t i = 0; i < ctx->n_left; i++) {
+    for (int64_t i = 0; i < ctx->lay.n_left; i++) {
         int64_t r = L.left_row[(size_t)i];
         int32_t x = weight_of(r);
         out.wl[(size_t)i] = x;
@@ -447,12 +475,12 @@ int layout_weights(const emsar_hip_ctx *ctx, const WeightOf &weight_of, const do
 int upload_layout_weights(emsar_hip_ctx *ctx, const LayoutWeights &LW, bool weighted) {
     const bool tiled = ctx->layout == EMSAR_LAYOUT_TILED;
     if (weighted) {
-        if (!ctx->d_wgt) HIPCHK(hipMalloc(&ctx->d_wgt, LW.w.size() * 4));
-        HIPCHK(hipMemcpy(ctx->d_wgt, LW.w.data(), LW.w.size() * 4, hipMemcpyHostToDevice));
-        if (tiled && !ctx->d_left_wgt) HIPCHK(hipMalloc(&ctx->d_left_wgt, LW.wl.size() * 4));
-        if (tiled) HIPCHK(hipMemcpy(ctx->d_left_wgt, LW.wl.data(), LW.wl.size() * 4, hipMemcpyHostToDevice));
+        if (!ctx->rw.d_wgt) HIPCHK(ctx->rw.d_wgt.alloc(LW.w.size()));
+        HIPCHK(hipMemcpy(ctx->rw.d_wgt, LW.w.data(), LW.w.size() * 4, hipMemcpyHostToDevice));
+        if (tiled && !ctx->rw.d_left_wgt) HIPCHK(ctx->rw.d_left_wgt.alloc(LW.wl.size()));
+        if (tiled) HIPCHK(hipMemcpy(ctx->rw.d_left_wgt, LW.wl.data(), LW.wl.size() * 4, hipMemcpyHostToDevice));
     }
-    if (tiled) HIPCHK(hipMemcpy(ctx->d_u, LW.u.data(), LW.u.size() * 8, hipMemcpyHostToDevice));
+    if (tiled) HIPCHK(hipMemcpy(ctx->lay.d_u, LW.u.data(), LW.u.size() * 8, hipMemcpyHostToDevice));
     return EMSAR_HIP_OK;
 }
 
@@ -460,21 +488,21 @@ int upload_layout_weights(emsar_hip_ctx *ctx, const LayoutWeights &LW, bool weig
 int scatter_rows(emsar_hip_ctx *ctx, const double *val_host, double *d_out) {
     try {
         if (ctx->layout == EMSAR_LAYOUT_TILED) {
-            const auto &L = ctx->TL;
-            std::vector<double> slot((size_t)std::max<int64_t>(ctx->n_slots, 1), 0.0), left((size_t)std::max<int64_t>(ctx->n_left, 1), 0.0);
+            const auto &L = ctx->lay.TL;
+            std::vector<double> slot((size_t)std::max<int64_t>(ctx->lay.n_slots, 1), 0.0), left((size_t)std::max<int64_t>(ctx->lay.n_left, 1), 0.0);
             std::vector<double> base((size_t)ctx->n_tx, 0.0);
-            for (int64_t i = 0; i < ctx->n_slots; i++) {
+            for (int64_t i = 0; i < ctx->lay.n_slots; i++) {
                 int64_t r = L.slot_row[(size_t)i];
                 if (r < 0) continue;
                 if (L.merged) { double v = 0; for (uint64_t q = L.mem_ptr[(size_t)r]; q < L.mem_ptr[(size_t)r + 1]; q++) v += val_host[L.mem_row[(size_t)q]]; slot[(size_t)i] = v; }
                 else slot[(size_t)i] = val_host[r];
             }
-            for (int64_t i = 0; i < ctx->n_left; i++) left[(size_t)i] = val_host[L.left_row[(size_t)i]];
+            for (int64_t i = 0; i < ctx->lay.n_left; i++) left[(size_t)i] = val_host[L.left_row[(size_t)i]];
             for (size_t i = 0; i < L.single_row.size(); i++) base[(size_t)L.single_tid[i]] += val_host[L.single_row[i]];
-            if (!ctx->d_rowval) HIPCHK(hipMalloc(&ctx->d_rowval, slot.size() * sizeof(double)));
-            if (!ctx->d_left_val) HIPCHK(hipMalloc(&ctx->d_left_val, left.size() * sizeof(double)));
-            HIPCHK(hipMemcpyAsync(ctx->d_rowval, slot.data(), slot.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(hipMemcpyAsync(ctx->d_left_val, left.data(), left.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            if (!ctx->lay.d_rowval) HIPCHK(ctx->lay.d_rowval.alloc(slot.size()));
+            if (!ctx->lay.d_left_val) HIPCHK(ctx->lay.d_left_val.alloc(left.size()));
+            HIPCHK(hipMemcpyAsync(ctx->lay.d_rowval, slot.data(), slot.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(hipMemcpyAsync(ctx->lay.d_left_val, left.data(), left.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
             HIPCHK(hipMemcpyAsync(d_out, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
             int rc = launch_pass(ctx, MODE_SCATTER, nullptr, d_out, nullptr);
             if (rc) return rc;
@@ -484,8 +512,8 @@ int scatter_rows(emsar_hip_ctx *ctx, const double *val_host, double *d_out) {
         const double *src = val_host;
         size_t n = (size_t)ctx->n_rows;
         if (n == 0) return EMSAR_HIP_OK;
-        if (!ctx->d_rowval) HIPCHK(hipMalloc(&ctx->d_rowval, std::max<size_t>(n, 1) * sizeof(double)));
-        HIPCHK(hipMemcpyAsync(ctx->d_rowval, src, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        if (!ctx->lay.d_rowval) HIPCHK(ctx->lay.d_rowval.alloc(n));
+        HIPCHK(hipMemcpyAsync(ctx->lay.d_rowval, src, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemsetAsync(d_out, 0, (size_t)ctx->n_tx * sizeof(double), ctx->stream));
         int rc = launch_pass(ctx, MODE_SCATTER, nullptr, d_out, nullptr);
         if (rc) return rc;
@@ -497,14 +525,14 @@ int scatter_rows(emsar_hip_ctx *ctx, const double *val_host, double *d_out) {
 // find and pack the connected sets of the current sample (sets.hpp) and move the records to the device
 int ensure_sets_impl(emsar_hip_ctx *ctx);
 int ensure_sets(emsar_hip_ctx *ctx) {
-    if (ctx->sets_ready) return EMSAR_HIP_OK;
+    if (ctx->sets.sets_ready) return EMSAR_HIP_OK;
     const int rc = ensure_sets_impl(ctx);
-    if (rc != EMSAR_HIP_OK) free_sets(ctx);       // a half-uploaded record set is freed, the next solve starts over
+    if (rc != EMSAR_HIP_OK) ctx->sets = SetsDev();       // a half-uploaded record set is freed, the next solve starts over
     return rc;
 }
 int ensure_sets_impl(emsar_hip_ctx *ctx) {
     auto t0 = std::chrono::steady_clock::now();
-    auto &S = ctx->RS;
+    auto &S = ctx->sets.RS;
     try {
         emsar::build_sets(ctx->n_rows, ctx->n_tx, ctx->h_row_ptr.data(), ctx->h_col.data(), ctx->h_wgt.data(), S);
     } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
@@ -520,22 +548,22 @@ int ensure_sets_impl(emsar_hip_ctx *ctx) {
         for (int32_t &t : S.g_tid) t = m[(size_t)t];
         for (int32_t &t : S.CL.g_tid) t = m[(size_t)t];
     }
-    HIPCHK(upload_new((void **)&ctx->d_kind, S.kind.data(), S.kind.size()));
-    HIPCHK(upload_new((void **)&ctx->d_usum, S.usum.data(), S.usum.size() * 8));
+    HIPCHK(ctx->sets.d_kind.upload(S.kind.data(), S.kind.size()));
+    HIPCHK(ctx->sets.d_usum.upload(S.usum.data(), S.usum.size()));
     const int64_t n = S.n_resident();
     if (n > 0) {
-        HIPCHK(upload_new((void **)&ctx->d_g_tid, S.g_tid.data(), S.g_tid.size() * 4));
-        HIPCHK(upload_new((void **)&ctx->d_g_u, S.g_u.data(), S.g_u.size() * 8));
-        HIPCHK(upload_new((void **)&ctx->d_row_w, S.row_w.data(), S.row_w.size() * 8));
-        HIPCHK(upload_new((void **)&ctx->d_srp, S.rp.data(), S.rp.size() * 2));
-        HIPCHK(upload_new((void **)&ctx->d_sent, S.ent.data(), S.ent.size() * 2));
-        HIPCHK(upload_new((void **)&ctx->d_scp, S.cp.data(), S.cp.size() * 2));
-        HIPCHK(upload_new((void **)&ctx->d_scrow, S.crow.data(), S.crow.size() * 2));
+        HIPCHK(ctx->sets.d_g_tid.upload(S.g_tid.data(), S.g_tid.size()));
+        HIPCHK(ctx->sets.d_g_u.upload(S.g_u.data(), S.g_u.size()));
+        HIPCHK(ctx->sets.d_row_w.upload(S.row_w.data(), S.row_w.size()));
+        HIPCHK(ctx->sets.d_srp.upload(S.rp.data(), S.rp.size()));
+        HIPCHK(ctx->sets.d_sent.upload(S.ent.data(), S.ent.size()));
+        HIPCHK(ctx->sets.d_scp.upload(S.cp.data(), S.cp.size()));
+        HIPCHK(ctx->sets.d_scrow.upload(S.crow.data(), S.crow.size()));
         for (int c = 0; c < emsar::kSetClasses; c++)
-            if (!S.desc[c].empty()) HIPCHK(upload_new((void **)&ctx->d_sdesc[c], S.desc[c].data(), S.desc[c].size() * sizeof(emsar::SetDesc)));
-        HIPCHK(hipMalloc(&ctx->d_sstat, (size_t)n * sizeof(SetStat)));
-        HIPCHK(hipHostMalloc((void **)&ctx->h_sstat, (size_t)n * sizeof(SetStat), hipHostMallocDefault));
-        ctx->n_sstat = n;
+            if (!S.desc[c].empty()) HIPCHK(ctx->sets.d_sdesc[c].upload(S.desc[c].data(), S.desc[c].size()));
+        HIPCHK(ctx->sets.d_sstat.alloc((size_t)n));
+        HIPCHK(ctx->sets.h_sstat.alloc((size_t)n));
+        ctx->sets.n_sstat = n;
         HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[0]));
         HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[1]));
         HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[2]));
@@ -543,21 +571,21 @@ int ensure_sets_impl(emsar_hip_ctx *ctx) {
     const int64_t nc = S.n_cluster_sets();
     if (nc > 0) {
         auto &CL = S.CL;
-        HIPCHK(upload_new((void **)&ctx->d_cdesc, CL.desc.data(), CL.desc.size() * sizeof(emsar::ClusterDesc)));
-        HIPCHK(upload_new((void **)&ctx->d_cblk, CL.blk_set.data(), CL.blk_set.size() * 4));
-        HIPCHK(upload_new((void **)&ctx->d_crp, CL.rp.data(), CL.rp.size() * 4));
-        HIPCHK(upload_new((void **)&ctx->d_ccp, CL.cp.data(), CL.cp.size() * 4));
-        HIPCHK(upload_new((void **)&ctx->d_cpart, CL.part.data(), CL.part.size() * 4));
-        HIPCHK(upload_new((void **)&ctx->d_cent, CL.ent.data(), CL.ent.size() * 2));
-        HIPCHK(upload_new((void **)&ctx->d_ccrow, CL.crow.data(), CL.crow.size() * 2));
-        HIPCHK(upload_new((void **)&ctx->d_cg_tid, CL.g_tid.data(), CL.g_tid.size() * 4));
-        HIPCHK(upload_new((void **)&ctx->d_cg_u, CL.g_u.data(), CL.g_u.size() * 8));
-        HIPCHK(upload_new((void **)&ctx->d_crow_w, CL.row_w.data(), CL.row_w.size() * 8));
-        HIPCHK(hipMalloc(&ctx->d_cscratch, std::max<size_t>((size_t)CL.scratch_doubles, 2) * 8));
-        HIPCHK(hipMalloc(&ctx->d_cbar, (size_t)nc * 2 * sizeof(unsigned)));
-        HIPCHK(hipMalloc(&ctx->d_cstat, (size_t)nc * sizeof(ClusterStat)));
-        HIPCHK(hipHostMalloc((void **)&ctx->h_cstat, (size_t)nc * sizeof(ClusterStat), hipHostMallocDefault));
-        ctx->n_cstat = nc;
+        HIPCHK(ctx->sets.d_cdesc.upload(CL.desc.data(), CL.desc.size()));
+        HIPCHK(ctx->sets.d_cblk.upload(CL.blk_set.data(), CL.blk_set.size()));
+        HIPCHK(ctx->sets.d_crp.upload(CL.rp.data(), CL.rp.size()));
+        HIPCHK(ctx->sets.d_ccp.upload(CL.cp.data(), CL.cp.size()));
+        HIPCHK(ctx->sets.d_cpart.upload(CL.part.data(), CL.part.size()));
+        HIPCHK(ctx->sets.d_cent.upload(CL.ent.data(), CL.ent.size()));
+        HIPCHK(ctx->sets.d_ccrow.upload(CL.crow.data(), CL.crow.size()));
+        HIPCHK(ctx->sets.d_cg_tid.upload(CL.g_tid.data(), CL.g_tid.size()));
+        HIPCHK(ctx->sets.d_cg_u.upload(CL.g_u.data(), CL.g_u.size()));
+        HIPCHK(ctx->sets.d_crow_w.upload(CL.row_w.data(), CL.row_w.size()));
+        HIPCHK(ctx->sets.d_cscratch.alloc((size_t)CL.scratch_doubles));
+        HIPCHK(ctx->sets.d_cbar.alloc((size_t)nc * 2));
+        HIPCHK(ctx->sets.d_cstat.alloc((size_t)nc));
+        HIPCHK(ctx->sets.h_cstat.alloc((size_t)nc));
+        ctx->sets.n_cstat = nc;
         HIPCHK(hipFuncSetAttribute((const void *)k_solve_cluster, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kClusterLdsCap));
         // only the sizes are needed from here on
         std::vector<uint32_t>().swap(CL.rp); std::vector<uint32_t>().swap(CL.cp); std::vector<uint16_t>().swap(CL.ent); std::vector<uint16_t>().swap(CL.crow);
@@ -568,7 +596,7 @@ int ensure_sets_impl(emsar_hip_ctx *ctx) {
     std::vector<uint16_t>().swap(S.rp); std::vector<uint16_t>().swap(S.ent); std::vector<uint16_t>().swap(S.cp); std::vector<uint16_t>().swap(S.crow);
     std::vector<double>().swap(S.usum);
     ctx->sets_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    ctx->sets_ready = true;
+    ctx->sets.sets_ready = true;
     return EMSAR_HIP_OK;
 }
 
@@ -583,7 +611,7 @@ int fork_side_streams(emsar_hip_ctx *ctx, int n_side) {
 template <class Launch>
 int launch_set_classes(emsar_hip_ctx *ctx, int n_side, const Launch &launch) {
     const hipStream_t st[emsar::kSetClasses] = {ctx->stream, ctx->side[0], ctx->side[1]};
-    for (int c = emsar::kSetClasses - 1; c >= 0; c--) if (!ctx->RS.desc[c].empty()) launch(c, emsar::kSetThreads[c], st[c]);
+    for (int c = emsar::kSetClasses - 1; c >= 0; c--) if (!ctx->sets.RS.desc[c].empty()) launch(c, emsar::kSetThreads[c], st[c]);
     for (int i = 0; i < n_side; i++) {
         HIPCHK(hipEventRecord(ctx->ev_join[i], ctx->side[i]));
         HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
@@ -594,25 +622,25 @@ int launch_set_classes(emsar_hip_ctx *ctx, int n_side, const Launch &launch) {
 
 // closed-form transcripts and every LDS-resident set, written into theta (the streamed sets' entries are left alone)
 int solve_resident_sets(emsar_hip_ctx *ctx, const SetSolveParams &P, const SetSolveParams &Pcluster, double *theta) {
-    const auto &S = ctx->RS;
-    hipLaunchKernelGGL(k_closed_form, dim3(grid_for(ctx->n_tx, 256)), dim3(256), 0, ctx->stream, ctx->n_tx, ctx->d_kind, ctx->d_usum,
-                       ctx->d_den, theta);
+    const auto &S = ctx->sets.RS;
+    hipLaunchKernelGGL(k_closed_form, dim3(grid_for(ctx->n_tx, 256)), dim3(256), 0, ctx->stream, ctx->n_tx, ctx->sets.d_kind, ctx->sets.d_usum,
+                       ctx->vec.d_den, theta);
     const size_t off[3] = {0, S.desc[0].size(), S.desc[0].size() + S.desc[1].size()};      // per-set results in class order
     if (const int rc = fork_side_streams(ctx, 3)) return rc;
-    if (ctx->n_cstat > 0) {
+    if (ctx->sets.n_cstat > 0) {
         // The clusters, on a stream of their own.  Every workgroup of a launch must be resident at once (they wait for each other at
         // the cluster barriers): at most one workgroup per CU per launch -- each asks for most of a CU's LDS --, whole sets only.
         const int n_cu = ctx->n_cu;
-        HIPCHK(hipMemsetAsync(ctx->d_cbar, 0, (size_t)ctx->n_cstat * 2 * sizeof(unsigned), ctx->side[2]));
+        HIPCHK(hipMemsetAsync(ctx->sets.d_cbar, 0, (size_t)ctx->sets.n_cstat * 2 * sizeof(unsigned), ctx->side[2]));
         HIPCHK(hipEventRecord(ctx->ev_c0, ctx->side[2]));
         const auto &D = S.CL.desc;
         size_t first = 0;
         while (first < D.size()) {
             size_t last = first, wgs = 0;
             while (last < D.size() && (wgs == 0 || wgs + D[last].g <= (size_t)n_cu)) wgs += D[last++].g;
-            hipLaunchKernelGGL(k_solve_cluster, dim3((unsigned)wgs), dim3(emsar::kClusterThreads), S.CL.max_lds, ctx->side[2], ctx->d_cdesc, ctx->d_cblk,
-                               D[first].blk0, ctx->d_cg_tid, ctx->d_cg_u, ctx->d_crow_w, ctx->d_crp, ctx->d_cent, ctx->d_ccp, ctx->d_ccrow, ctx->d_cpart,
-                               ctx->d_cscratch, ctx->d_cbar, ctx->d_cbar + ctx->n_cstat, ctx->d_den, theta, ctx->d_cstat, Pcluster);
+            hipLaunchKernelGGL(k_solve_cluster, dim3((unsigned)wgs), dim3(emsar::kClusterThreads), S.CL.max_lds, ctx->side[2], ctx->sets.d_cdesc, ctx->sets.d_cblk,
+                               D[first].blk0, ctx->sets.d_cg_tid, ctx->sets.d_cg_u, ctx->sets.d_crow_w, ctx->sets.d_crp, ctx->sets.d_cent, ctx->sets.d_ccp, ctx->sets.d_ccrow, ctx->sets.d_cpart,
+                               ctx->sets.d_cscratch, ctx->sets.d_cbar, ctx->sets.d_cbar + ctx->sets.n_cstat, ctx->vec.d_den, theta, ctx->sets.d_cstat, Pcluster);
             first = last;
         }
         HIPCHK(hipEventRecord(ctx->ev_c1, ctx->side[2]));
@@ -624,8 +652,8 @@ int solve_resident_sets(emsar_hip_ctx *ctx, const SetSolveParams &P, const SetSo
     }
     return launch_set_classes(ctx, 3, [&](int c, int threads, hipStream_t st) {
         hipLaunchKernelGGL((c == 2 ? k_solve_sets<512> : c == 1 ? k_solve_sets<256> : k_solve_sets<64>), dim3((unsigned)S.desc[c].size()), dim3(threads),
-                           S.max_lds[c], st, ctx->d_sdesc[c], ctx->d_g_tid, ctx->d_g_u, ctx->d_row_w, ctx->d_srp, ctx->d_sent, ctx->d_scp,
-                           ctx->d_scrow, ctx->d_den, theta, ctx->d_sstat + off[c], P);
+                           S.max_lds[c], st, ctx->sets.d_sdesc[c], ctx->sets.d_g_tid, ctx->sets.d_g_u, ctx->sets.d_row_w, ctx->sets.d_srp, ctx->sets.d_sent, ctx->sets.d_scp,
+                           ctx->sets.d_scrow, ctx->vec.d_den, theta, ctx->sets.d_sstat + off[c], P);
     });
 }
 
@@ -676,10 +704,10 @@ int emsar_hip_create(emsar_hip_ctx **out, int device_id) {
         if (hipStreamCreateWithFlags(&ctx->side[i], hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming) != hipSuccess) return fail(EMSAR_HIP_ERR_HIP);
     if (hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess) return fail(EMSAR_HIP_ERR_HIP);
-    if (hipMalloc(&ctx->d_scal, sizeof(Scal)) != hipSuccess) return fail(EMSAR_HIP_ERR_OOM);
-    if (hipMalloc(&ctx->d_sqpart, 4 * kSqPart * sizeof(double)) != hipSuccess) return fail(EMSAR_HIP_ERR_OOM);
+    if (ctx->d_scal.alloc(1) != hipSuccess) return fail(EMSAR_HIP_ERR_OOM);
+    if (ctx->d_sqpart.alloc(4 * kSqPart) != hipSuccess) return fail(EMSAR_HIP_ERR_OOM);
     if (hipMemset(ctx->d_sqpart, 0, 4 * kSqPart * sizeof(double)) != hipSuccess) return fail(EMSAR_HIP_ERR_HIP);
-    if (hipHostMalloc((void **)&ctx->h_scal, sizeof(Scal), hipHostMallocDefault) != hipSuccess) return fail(EMSAR_HIP_ERR_OOM);
+    if (ctx->h_scal.alloc(1) != hipSuccess) return fail(EMSAR_HIP_ERR_OOM);
     *out = ctx;
     return EMSAR_HIP_OK;
 }
@@ -695,8 +723,6 @@ void emsar_hip_destroy(emsar_hip_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     free_structure(ctx);
-    dfree(ctx->d_scal); dfree(ctx->d_sqpart);
-    if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
@@ -708,7 +734,7 @@ void emsar_hip_destroy(emsar_hip_ctx *ctx) {
         if (ctx->ev_join[i]) (void)hipEventDestroy(ctx->ev_join[i]);
     }
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;     // its buffers of the context's own lifetime go with it
 }
 
 int emsar_hip_upload_structure(emsar_hip_ctx *ctx, int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr,
@@ -747,59 +773,46 @@ int emsar_hip_upload_structure(emsar_hip_ctx *ctx, int64_t n_rows, int32_t n_tx,
     struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{csr_copy};
     try {
         if (layout == EMSAR_LAYOUT_TILED) {
-            auto &L = ctx->TL;
+            auto &L = ctx->lay.TL;
             const int brc = emsar::build_tiled(n_rows, n_tx, row_ptr, col_idx, L, merge_rows);
             if (brc != 0) { ctx->err = "TILED layout builder: code " + std::to_string(brc); return EMSAR_HIP_ERR_ARG; }
             if (dbg) fprintf(stderr, "upload_structure: layout built after %.0f ms\n", since(tu0));
-            ctx->n_tiles = (int64_t)L.tiles.size(); ctx->n_slots = L.n_slots(); ctx->n_left = (int64_t)L.left_row.size();
-            HIPCHK(upload_new((void **)&ctx->d_tiles, L.tiles.data(), L.tiles.size() * sizeof(Tile)));
-            HIPCHK(upload_new((void **)&ctx->d_units, L.unit_first.data(), L.unit_first.size() * 4));
-            ctx->n_units = L.unit_first.empty() ? 0 : (int64_t)L.unit_first.size() - 1;
+            ctx->lay.n_tiles = (int64_t)L.tiles.size(); ctx->lay.n_slots = L.n_slots(); ctx->lay.n_left = (int64_t)L.left_row.size();
+            HIPCHK(ctx->lay.d_tiles.upload(L.tiles.data(), L.tiles.size()));
+            HIPCHK(ctx->lay.d_units.upload(L.unit_first.data(), L.unit_first.size()));
+            ctx->lay.n_units = L.unit_first.empty() ? 0 : (int64_t)L.unit_first.size() - 1;
             {
                 emsar::UnitTables U;
                 emsar::build_unit_tables(L, U);
-                ctx->unit_stride = U.stride;
-                HIPCHK(upload_new((void **)&ctx->d_utiles, U.utiles.data(), U.utiles.size() * sizeof(Tile)));
+                ctx->lay.unit_stride = U.stride;
+                HIPCHK(ctx->lay.d_utiles.upload(U.utiles.data(), U.utiles.size()));
             }
-            HIPCHK(upload_new((void **)&ctx->d_fwd, L.fwd.data(), L.fwd.size() * 4));
-            HIPCHK(upload_new((void **)&ctx->d_bwd, L.bwd.data(), L.bwd.size() * 4));
-            HIPCHK(upload_new((void **)&ctx->d_far, L.far_tid.data(), L.far_tid.size() * 4));
-            HIPCHK(upload_new((void **)&ctx->d_left_ptr, L.left_ptr.data(), L.left_ptr.size() * 8));
-            HIPCHK(upload_new((void **)&ctx->d_left_col, L.left_col.data(), L.left_col.size() * 4));
-            HIPCHK(hipMalloc(&ctx->d_u, T * 8));
-            HIPCHK(hipMemset(ctx->d_u, 0, T * 8));
+            HIPCHK(ctx->lay.d_fwd.upload(L.fwd.data(), L.fwd.size()));
+            HIPCHK(ctx->lay.d_bwd.upload(L.bwd.data(), L.bwd.size()));
+            HIPCHK(ctx->lay.d_far.upload(L.far_tid.data(), L.far_tid.size()));
+            HIPCHK(ctx->lay.d_left_ptr.upload(L.left_ptr.data(), L.left_ptr.size()));
+            HIPCHK(ctx->lay.d_left_col.upload(L.left_col.data(), L.left_col.size()));
+            HIPCHK(ctx->lay.d_u.alloc(T));
+            HIPCHK(hipMemset(ctx->lay.d_u, 0, T * 8));
             ctx->bytes_stored = (int64_t)L.fwd.size() * 4 + (int64_t)L.bwd.size() * 4 + (int64_t)L.far_tid.size() * 4 +
                                 (int64_t)L.tiles.size() * 64 + (int64_t)L.left_col.size() * 4 + (int64_t)L.left_ptr.size() * 8;
             ctx->tl_fwd_slots = L.padded_slots; ctx->tl_n_fslices = L.n_fslices;
             emsar::u32_vec().swap(L.fwd); emsar::u32_vec().swap(L.bwd);
             std::vector<int32_t>().swap(L.left_col);
-            const size_t lds = (size_t)kTiledLdsDoubles * sizeof(double);
-#define SETLDS_T(WT, MD) HIPCHK(hipFuncSetAttribute((const void *)k_pass_tiled<WT, MD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-            SETLDS_T(false, MODE_EM); SETLDS_T(false, MODE_EM_LL); SETLDS_T(true, MODE_EM); SETLDS_T(true, MODE_EM_LL); SETLDS_T(false, MODE_SCATTER);
-#undef SETLDS_T
-#define SETLDS_P(WT, MD, NN) HIPCHK(hipFuncSetAttribute((const void *)k_pass_tiled_multi<WT, MD, NN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-            SETLDS_P(false, MODE_EM, 2); SETLDS_P(false, MODE_EM_LL, 2);
-#define SETLDS_U(WT, MD) HIPCHK(hipFuncSetAttribute((const void *)k_pass_tiled_unit<WT, MD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-            SETLDS_U(false, MODE_EM); SETLDS_U(false, MODE_EM_LL); SETLDS_U(true, MODE_EM); SETLDS_U(true, MODE_EM_LL);
+            HIPCHK(set_tiled_lds_attributes());
             { const char *pe = getenv("EMSAR_HIP_WEIGHTED_UNIT"); ctx->weighted_unit = pe ? atoi(pe) : 1; }
-#undef SETLDS_U
-            SETLDS_P(false, MODE_EM, 3); SETLDS_P(false, MODE_EM_LL, 3); SETLDS_P(false, MODE_EM, 4); SETLDS_P(false, MODE_EM_LL, 4);
-#undef SETLDS_P
             { const char *pe = getenv("EMSAR_HIP_TILED_MULTI"); ctx->tiled_multi = pe ? atoi(pe) : 1; }
             { const char *pe = getenv("EMSAR_HIP_UPDATE_GRID"); if (pe && atoi(pe) >= 1) ctx->update_grid = atoi(pe); }
             { const char *pe = getenv("EMSAR_HIP_SQ_GRID"); if (pe && atoi(pe) >= 1) ctx->sq_grid = atoi(pe); }
         } else {
             if (ctx->ptr64) {
-                HIPCHK(hipMalloc(&ctx->d_row_ptr, ((size_t)n_rows + 1) * 8));
-                HIPCHK(hipMemcpy(ctx->d_row_ptr, row_ptr, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice));
+                HIPCHK(ctx->lay.d_row_ptr.upload(row_ptr, ((size_t)n_rows + 1) * 8));
             } else {
                 std::vector<uint32_t> rp((size_t)n_rows + 1);
                 for (int64_t r = 0; r <= n_rows; r++) rp[(size_t)r] = (uint32_t)row_ptr[r];
-                HIPCHK(hipMalloc(&ctx->d_row_ptr, rp.size() * 4));
-                HIPCHK(hipMemcpy(ctx->d_row_ptr, rp.data(), rp.size() * 4, hipMemcpyHostToDevice));
+                HIPCHK(ctx->lay.d_row_ptr.upload(rp.data(), rp.size() * 4));
             }
-            HIPCHK(hipMalloc(&ctx->d_col, std::max<size_t>((size_t)ctx->nnz, 1) * 4));
-            HIPCHK(hipMemcpy(ctx->d_col, col_idx, (size_t)ctx->nnz * 4, hipMemcpyHostToDevice));
+            HIPCHK(ctx->lay.d_col.upload(col_idx, (size_t)ctx->nnz));
             ctx->bytes_stored = ctx->nnz * 4 + (n_rows + 1) * (ctx->ptr64 ? 8 : 4);
         }
     } catch (const std::bad_alloc &) {
@@ -811,12 +824,12 @@ int emsar_hip_upload_structure(emsar_hip_ctx *ctx, int64_t n_rows, int32_t n_tx,
     csr_copy.join();
     if (copy_failed) { free_structure(ctx); return EMSAR_HIP_ERR_OOM; }
     if (dbg) fprintf(stderr, "upload_structure: host CSR copy joined after %.0f ms\n", since(tu0));
-    HIPCHK(hipMalloc(&ctx->d_den, T * 8));
-    HIPCHK(hipMalloc(&ctx->d_acc, T * 8));
-    for (auto &p : ctx->d_th) HIPCHK(hipMalloc(&p, T * 8));
-    for (auto &p : ctx->d_tmp) HIPCHK(hipMalloc(&p, T * 8));
-    HIPCHK(hipMalloc(&ctx->d_itmp, T * 4));
-    HIPCHK(hipMemset(ctx->d_acc, 0, T * 8));
+    HIPCHK(ctx->vec.d_den.alloc(T));
+    HIPCHK(ctx->vec.d_acc.alloc(T));
+    for (auto &p : ctx->vec.d_th) HIPCHK(p.alloc(T));
+    for (auto &p : ctx->vec.d_tmp) HIPCHK(p.alloc(T));
+    HIPCHK(ctx->vec.d_itmp.alloc(T));
+    HIPCHK(hipMemset(ctx->vec.d_acc, 0, T * 8));
     ctx->have_structure = true;
     return EMSAR_HIP_OK;
 }
@@ -839,15 +852,15 @@ int emsar_hip_upload_sample(emsar_hip_ctx *ctx, const int32_t *row_weight, const
     // context that still says have_sample with its weight arrays freed (run_passes would launch kernels on null pointers)
     ctx->have_sample = false;
     // a row counts w = R (or 1) when it is inside the likelihood (E != 0), else 0
-    ctx->weighted = (row_weight != nullptr) || (row_E != nullptr) || (ctx->layout == EMSAR_LAYOUT_TILED && ctx->TL.merged);
+    ctx->weighted = (row_weight != nullptr) || (row_E != nullptr) || (ctx->layout == EMSAR_LAYOUT_TILED && ctx->lay.TL.merged);
     ctx->loglik_const = 0.0;
-    free_row_weights(ctx);
+    ctx->rw = RowWeights();
     auto weight_of = [&](int64_t r) -> int32_t {
         int32_t x = row_weight ? row_weight[r] : 1;
         if (row_E && row_E[r] == 0.0) x = 0;
         return x;
     };
-    free_sets(ctx);
+    ctx->sets = SetsDev();
     try {
         ctx->h_wgt.resize((size_t)n_rows);
         int64_t total_w = 0;
@@ -864,12 +877,12 @@ int emsar_hip_upload_sample(emsar_hip_ctx *ctx, const int32_t *row_weight, const
     if (den) {
         std::vector<double> tmp;
         try { den = to_lib(ctx, den, tmp); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-        HIPCHK(hipMemcpy(ctx->d_den, den, (size_t)ctx->n_tx * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ctx->vec.d_den, den, (size_t)ctx->n_tx * 8, hipMemcpyHostToDevice));
     } else {
         std::vector<double> ones;
         const double *e = row_E;
         if (!e) { ones.assign((size_t)std::max<int64_t>(n_rows, 1), 1.0); e = ones.data(); }
-        int rc = scatter_rows(ctx, e, ctx->d_den);
+        int rc = scatter_rows(ctx, e, ctx->vec.d_den);
         if (rc) return rc;
     }
     ctx->bytes_formula = 4 * ctx->nnz + (ctx->ptr64 ? 8 : 4) * (ctx->n_rows + 1) + (row_weight ? 4 : 0) * ctx->n_rows + 32 * (int64_t)ctx->n_tx;
@@ -881,7 +894,7 @@ int emsar_hip_reset_theta(emsar_hip_ctx *ctx) {
     if (!ctx) return EMSAR_HIP_ERR_ARG;
     if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
     HIPCHK(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_fill_start, dim3(grid_for(ctx->n_tx, 256)), dim3(256), 0, ctx->stream, ctx->n_tx, ctx->d_den, ctx->d_th[0]);
+    hipLaunchKernelGGL(k_fill_start, dim3(grid_for(ctx->n_tx, 256)), dim3(256), 0, ctx->stream, ctx->n_tx, ctx->vec.d_den, ctx->vec.d_th[0]);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return EMSAR_HIP_OK;
@@ -893,7 +906,7 @@ int emsar_hip_set_theta(emsar_hip_ctx *ctx, const double *theta) {
     HIPCHK(hipSetDevice(ctx->device));
     std::vector<double> tmp;
     try { theta = to_lib(ctx, theta, tmp); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    HIPCHK(hipMemcpyAsync(ctx->d_th[0], theta, (size_t)ctx->n_tx * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->vec.d_th[0], theta, (size_t)ctx->n_tx * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return EMSAR_HIP_OK;
 }
@@ -902,7 +915,7 @@ int emsar_hip_get_theta(emsar_hip_ctx *ctx, double *theta) {
     if (!ctx || !theta) return EMSAR_HIP_ERR_ARG;
     if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMemcpyAsync(theta, ctx->d_th[0], (size_t)ctx->n_tx * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(theta, ctx->vec.d_th[0], (size_t)ctx->n_tx * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     try { from_lib(ctx, theta); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
     return EMSAR_HIP_OK;
@@ -918,12 +931,12 @@ int emsar_hip_run_passes(emsar_hip_ctx *ctx, int32_t n_passes, float *elapsed_ms
     int cur = 0;  // th[cur] holds the current point, th[cur^1] receives the next
     for (int i = 0; i < n_passes; i++) {
         bool ll = last_ll && i == n_passes - 1;
-        int rc = em_pass(ctx, ctx->d_th[cur], ctx->d_th[cur ^ 1], ll, 0, 1e-6);
+        int rc = em_pass(ctx, ctx->vec.d_th[cur], ctx->vec.d_th[cur ^ 1], ll, 0, 1e-6);
         if (rc) return rc;
         cur ^= 1;
     }
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
-    if (cur == 1) HIPCHK(hipMemcpyAsync(ctx->d_th[0], ctx->d_th[1], (size_t)ctx->n_tx * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    if (cur == 1) HIPCHK(hipMemcpyAsync(ctx->vec.d_th[0], ctx->vec.d_th[1], (size_t)ctx->n_tx * 8, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->h_scal, ctx->d_scal, sizeof(Scal), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (elapsed_ms) HIPCHK(hipEventElapsedTime(elapsed_ms, ctx->ev0, ctx->ev1));
@@ -969,16 +982,16 @@ static int solve_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpk
     int rc;
     bool use_sets = p.set_mode == 0;
     if (use_sets && (rc = ensure_sets(ctx))) return rc;
-    if (use_sets && ctx->RS.giant) use_sets = false;      // one component holds most transcripts: plain streaming solve
+    if (use_sets && ctx->sets.RS.giant) use_sets = false;      // one component holds most transcripts: plain streaming solve
     // the streaming passes run when asked for, or for the sets that do not fit a workgroup
-    const bool need_stream = !use_sets || ctx->RS.n_streamed_sets > 0;
-    if (use_sets && need_stream) ctx->delta_mask = ctx->d_kind;
+    const bool need_stream = !use_sets || ctx->sets.RS.n_streamed_sets > 0;
+    if (use_sets && need_stream) ctx->delta_mask = ctx->sets.d_kind;
     auto t0 = std::chrono::steady_clock::now();
     if ((rc = emsar_hip_reset_theta(ctx))) return rc;
     hipLaunchKernelGGL(k_scal_init, dim3(1), dim3(1), 0, ctx->stream, ctx->d_scal);
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     const int n = ctx->n_tx, g = grid_for(n, 256);
-    double **th = ctx->d_th;  // 0:th0 1:th1 2:th2 3:thx 4:thn (enqueue_cycles leaves the current point in th[0])
+    DevBuf<double> *th = ctx->vec.d_th;  // 0:th0 1:th1 2:th2 3:thx 4:thn (enqueue_cycles leaves the current point in th[0])
     int iters = 0, converged = need_stream ? 0 : 1, cycles = 0;
     double delta = need_stream ? INFINITY : 0.0;
     // The first 4 x check_every cycles are launched kernel by kernel (a quick solve never pays for a graph); after that
@@ -1026,17 +1039,17 @@ static int solve_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpk
         Pc.zero_cut = p.zero_cut > 0.0 ? p.zero_cut : 0.0;
         Pc.abs_step = p.abs_step > 0.0 ? p.abs_step : 0.0;
         if ((rc = solve_resident_sets(ctx, P, Pc, th[0]))) return rc;
-        if (ctx->n_sstat > 0)
-            HIPCHK(hipMemcpyAsync(ctx->h_sstat, ctx->d_sstat, (size_t)ctx->n_sstat * sizeof(SetStat), hipMemcpyDeviceToHost, ctx->stream));
-        if (ctx->n_cstat > 0)
-            HIPCHK(hipMemcpyAsync(ctx->h_cstat, ctx->d_cstat, (size_t)ctx->n_cstat * sizeof(ClusterStat), hipMemcpyDeviceToHost, ctx->stream));
+        if (ctx->sets.n_sstat > 0)
+            HIPCHK(hipMemcpyAsync(ctx->sets.h_sstat, ctx->sets.d_sstat, (size_t)ctx->sets.n_sstat * sizeof(SetStat), hipMemcpyDeviceToHost, ctx->stream));
+        if (ctx->sets.n_cstat > 0)
+            HIPCHK(hipMemcpyAsync(ctx->sets.h_cstat, ctx->sets.d_cstat, (size_t)ctx->sets.n_cstat * sizeof(ClusterStat), hipMemcpyDeviceToHost, ctx->stream));
     }
     HIPCHK(hipEventRecord(ctx->ev2, ctx->stream));
     // F at the returned point: one likelihood-only pass (not counted in iters)
     hipLaunchKernelGGL(k_cycle_begin, dim3(1), dim3(kLlSlots), 0, ctx->stream, ctx->d_scal, 0.0, 0);
-    if ((rc = launch_pass(ctx, MODE_EM_LL, th[0], ctx->d_acc, &ctx->d_scal->ll[0].s[0].v))) return rc;
-    HIPCHK(hipMemsetAsync(ctx->d_acc, 0, (size_t)n * 8, ctx->stream));
-    hipLaunchKernelGGL(k_dot, dim3(1), dim3(1024), 0, ctx->stream, n, th[0], ctx->d_den, &ctx->d_scal->ll[3].s[0].v);
+    if ((rc = launch_pass(ctx, MODE_EM_LL, th[0], ctx->vec.d_acc, &ctx->d_scal->ll[0].s[0].v))) return rc;
+    HIPCHK(hipMemsetAsync(ctx->vec.d_acc, 0, (size_t)n * 8, ctx->stream));
+    hipLaunchKernelGGL(k_dot, dim3(1), dim3(1024), 0, ctx->stream, n, th[0], ctx->vec.d_den, &ctx->d_scal->ll[3].s[0].v);
     HIPCHK(hipMemcpyAsync(ctx->h_scal, ctx->d_scal, sizeof(Scal), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(fpkm_out, th[0], (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1049,8 +1062,8 @@ static int solve_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpk
     int32_t set_max = 0, set_unconv = 0;
     int64_t set_sum = 0;
     if (use_sets)
-        for (int64_t i = 0; i < ctx->n_sstat; i++) {
-            const SetStat &q = ctx->h_sstat[i];
+        for (int64_t i = 0; i < ctx->sets.n_sstat; i++) {
+            const SetStat &q = ctx->sets.h_sstat[i];
             set_max = std::max(set_max, q.passes); set_sum += q.passes;
             if (!q.converged) set_unconv++;
             if (!std::isfinite(q.delta)) { ctx->err = "non-finite theta in a connected set"; return EMSAR_HIP_ERR_NUMERIC; }
@@ -1058,8 +1071,8 @@ static int solve_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpk
         }
     int32_t cl_max = 0;
     if (use_sets)
-        for (int64_t i = 0; i < ctx->n_cstat; i++) {
-            const ClusterStat &q = ctx->h_cstat[i];
+        for (int64_t i = 0; i < ctx->sets.n_cstat; i++) {
+            const ClusterStat &q = ctx->sets.h_cstat[i];
             if (q.aborted) { ctx->err = "a workgroup cluster gave up waiting at its barrier"; return EMSAR_HIP_ERR_HIP; }
             cl_max = std::max(cl_max, q.passes); set_sum += q.passes;
             if (!q.converged) set_unconv++;
@@ -1081,18 +1094,18 @@ static int solve_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpk
         stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         stats->bytes_per_pass = ctx->bytes_formula;
         stats->stored_bytes_per_pass = stored_bytes(ctx);
-        if (p.set_mode == 0 && ctx->RS.giant) { stats->sets_streamed = 1; stats->sets_build_ms = ctx->sets_build_ms; }
+        if (p.set_mode == 0 && ctx->sets.RS.giant) { stats->sets_streamed = 1; stats->sets_build_ms = ctx->sets_build_ms; }
         if (use_sets) {
-            stats->sets_resident = (int32_t)ctx->RS.n_resident();
-            stats->sets_streamed = (int32_t)ctx->RS.n_streamed_sets;
+            stats->sets_resident = (int32_t)ctx->sets.RS.n_resident();
+            stats->sets_streamed = (int32_t)ctx->sets.RS.n_streamed_sets;
             stats->set_passes_max = set_max;
             stats->sets_unconverged = set_unconv;
             stats->set_passes_sum = set_sum;
             stats->sets_build_ms = ctx->sets_build_ms;
             stats->sets_kernel_ms = ms_sets;
-            stats->sets_cluster = (int32_t)ctx->n_cstat;
+            stats->sets_cluster = (int32_t)ctx->sets.n_cstat;
             stats->cluster_passes_max = cl_max;
-            if (ctx->n_cstat > 0) { float mc = 0; HIPCHK(hipEventElapsedTime(&mc, ctx->ev_c0, ctx->ev_c1)); stats->cluster_kernel_ms = mc; }
+            if (ctx->sets.n_cstat > 0) { float mc = 0; HIPCHK(hipEventElapsedTime(&mc, ctx->ev_c0, ctx->ev_c1)); stats->cluster_kernel_ms = mc; }
         }
     }
     return EMSAR_HIP_OK;
@@ -1102,9 +1115,9 @@ int emsar_hip_ieuma(emsar_hip_ctx *ctx, const double *row_L, double *ieuma_out) 
     if (!ctx || !row_L || !ieuma_out) return EMSAR_HIP_ERR_ARG;
     if (!ctx->have_structure) return EMSAR_HIP_ERR_STATE;
     HIPCHK(hipSetDevice(ctx->device));
-    int rc = scatter_rows(ctx, row_L, ctx->d_tmp[0]);
+    int rc = scatter_rows(ctx, row_L, ctx->vec.d_tmp[0]);
     if (rc) return rc;
-    HIPCHK(hipMemcpy(ieuma_out, ctx->d_tmp[0], (size_t)ctx->n_tx * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ieuma_out, ctx->vec.d_tmp[0], (size_t)ctx->n_tx * 8, hipMemcpyDeviceToHost));
     try { from_lib(ctx, ieuma_out); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
     return EMSAR_HIP_OK;
 }
@@ -1116,18 +1129,18 @@ int emsar_hip_normalise(emsar_hip_ctx *ctx, const double *mean_fpkm, const doubl
     HIPCHK(hipSetDevice(ctx->device));
     const int n = ctx->n_tx, g = grid_for(n, 256);
     const size_t B = (size_t)n * 8;
-    HIPCHK(hipMemcpyAsync(ctx->d_tmp[0], mean_fpkm, B, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->d_tmp[1], ieuma, B, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->vec.d_tmp[0], mean_fpkm, B, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->vec.d_tmp[1], ieuma, B, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemsetAsync(&ctx->d_scal->sum_b, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, ctx->stream, n, ctx->d_tmp[0], &ctx->d_scal->sum_b);
+    hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, ctx->stream, n, ctx->vec.d_tmp[0], &ctx->d_scal->sum_b);
     // tmp[2] <- tpm, acc <- iReadcount (acc is zero between passes and is cleared again below)
-    hipLaunchKernelGGL(k_normalise, dim3(g), dim3(256), 0, ctx->stream, n, ctx->d_tmp[0], ctx->d_tmp[1],
-                       (double)total_read_count / 1E6, &ctx->d_scal->sum_b, ctx->d_tmp[2], ctx->d_acc, ctx->d_itmp);
+    hipLaunchKernelGGL(k_normalise, dim3(g), dim3(256), 0, ctx->stream, n, ctx->vec.d_tmp[0], ctx->vec.d_tmp[1],
+                       (double)total_read_count / 1E6, &ctx->d_scal->sum_b, ctx->vec.d_tmp[2], ctx->vec.d_acc, ctx->vec.d_itmp);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(tpm_out, ctx->d_tmp[2], B, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ir_out, ctx->d_acc, B, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(iri_out, ctx->d_itmp, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_acc, 0, B, ctx->stream));
+    HIPCHK(hipMemcpyAsync(tpm_out, ctx->vec.d_tmp[2], B, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ir_out, ctx->vec.d_acc, B, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(iri_out, ctx->vec.d_itmp, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->vec.d_acc, 0, B, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return EMSAR_HIP_OK;
 }
@@ -1136,38 +1149,36 @@ int emsar_hip_upload_euma(emsar_hip_ctx *ctx, const int32_t *euma, int32_t nfl) 
     if (!ctx || !euma || nfl <= 0) return EMSAR_HIP_ERR_ARG;
     if (!ctx->have_structure) return EMSAR_HIP_ERR_STATE;
     HIPCHK(hipSetDevice(ctx->device));
-    dfree(ctx->d_euma_t); dfree(ctx->d_wf); dfree(ctx->d_adj); ctx->d_euma_t = nullptr; ctx->d_wf = ctx->d_adj = nullptr; ctx->nfl = 0;
+    ctx->euma = AdjEuma();
     const size_t n = (size_t)ctx->n_rows * (size_t)nfl;
-    int32_t *tmp = nullptr;
-    HIPCHK(hipMalloc(&ctx->d_euma_t, std::max<size_t>(n, 1) * 4));
-    HIPCHK(hipMalloc(&ctx->d_wf, (size_t)nfl * 8));
-    HIPCHK(hipMalloc(&ctx->d_adj, std::max<size_t>((size_t)ctx->n_rows, 1) * 8));
+    AdjEuma A;                   // moved into the context when it is complete
+    HIPCHK(A.d_euma_t.alloc(n));
+    HIPCHK(A.d_wf.alloc((size_t)nfl));
+    HIPCHK(A.d_adj.alloc((size_t)ctx->n_rows));
     if (n) {
-        HIPCHK(hipMalloc(&tmp, n * 4));
-        hipError_t e = hipMemcpyAsync(tmp, euma, n * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            dim3 grid((unsigned)((ctx->n_rows + 63) / 64), (unsigned)((nfl + 63) / 64));
-            hipLaunchKernelGGL(k_transpose_i32, grid, dim3(256), 0, ctx->stream, ctx->n_rows, (int)nfl, tmp, ctx->d_euma_t);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(tmp);
-        HIPCHK(e);
+        DevBuf<int32_t> tmp;
+        HIPCHK(tmp.alloc(n));
+        HIPCHK(hipMemcpyAsync(tmp, euma, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        dim3 grid((unsigned)((ctx->n_rows + 63) / 64), (unsigned)((nfl + 63) / 64));
+        hipLaunchKernelGGL(k_transpose_i32, grid, dim3(256), 0, ctx->stream, ctx->n_rows, (int)nfl, tmp, A.d_euma_t);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(ctx->stream));
     }
-    ctx->nfl = nfl;
+    A.nfl = nfl;
+    ctx->euma = std::move(A);
     return EMSAR_HIP_OK;
 }
 
 int emsar_hip_adj_euma(emsar_hip_ctx *ctx, const double *wf, double *out) {
     if (!ctx || !wf || !out) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_structure || ctx->nfl <= 0) return EMSAR_HIP_ERR_STATE;
+    if (!ctx->have_structure || ctx->euma.nfl <= 0) return EMSAR_HIP_ERR_STATE;
     HIPCHK(hipSetDevice(ctx->device));
     if (ctx->n_rows == 0) return EMSAR_HIP_OK;
-    HIPCHK(hipMemcpyAsync(ctx->d_wf, wf, (size_t)ctx->nfl * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_adj_euma, dim3((unsigned)((ctx->n_rows + 255) / 256)), dim3(256), 0, ctx->stream, ctx->n_rows, (int)ctx->nfl,
-                       ctx->d_euma_t, ctx->d_wf, ctx->d_adj);
+    HIPCHK(hipMemcpyAsync(ctx->euma.d_wf, wf, (size_t)ctx->euma.nfl * 8, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_adj_euma, dim3((unsigned)((ctx->n_rows + 255) / 256)), dim3(256), 0, ctx->stream, ctx->n_rows, (int)ctx->euma.nfl,
+                       ctx->euma.d_euma_t, ctx->euma.d_wf, ctx->euma.d_adj);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, ctx->d_adj, (size_t)ctx->n_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, ctx->euma.d_adj, (size_t)ctx->n_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return EMSAR_HIP_OK;
 }
@@ -1177,12 +1188,12 @@ int emsar_hip_get_info(const emsar_hip_ctx *ctx, emsar_hip_info *o) {
     if (!ctx->have_structure) return EMSAR_HIP_ERR_STATE;
     memset(o, 0, sizeof(*o));
     o->n_rows = ctx->n_rows; o->nnz = ctx->nnz; o->n_tx = ctx->n_tx; o->device_id = ctx->device;
-    o->layout = ctx->layout | ((ctx->layout == EMSAR_LAYOUT_TILED && ctx->TL.merged) ? EMSAR_LAYOUT_FLAG_MERGE_ROWS : 0);
+    o->layout = ctx->layout | ((ctx->layout == EMSAR_LAYOUT_TILED && ctx->lay.TL.merged) ? EMSAR_LAYOUT_FLAG_MERGE_ROWS : 0);
     if (ctx->layout == EMSAR_LAYOUT_TILED) {
-        o->n_chunks = ctx->n_tiles; o->n_slices = ctx->tl_n_fslices; o->padded_entries = ctx->tl_fwd_slots;
-        o->far_entries = ctx->TL.far_entries; o->window = emsar::kTileDict;
-        o->tiled_entries = ctx->TL.tiled_entries; o->tiled_ids = ctx->TL.tiled_ids; o->renumbered = ctx->TL.renum.applied ? 1 : 0;
-        o->n_units = ctx->n_units;
+        o->n_chunks = ctx->lay.n_tiles; o->n_slices = ctx->tl_n_fslices; o->padded_entries = ctx->tl_fwd_slots;
+        o->far_entries = ctx->lay.TL.far_entries; o->window = emsar::kTileDict;
+        o->tiled_entries = ctx->lay.TL.tiled_entries; o->tiled_ids = ctx->lay.TL.tiled_ids; o->renumbered = ctx->lay.TL.renum.applied ? 1 : 0;
+        o->n_units = ctx->lay.n_units;
     }
     o->bytes_per_pass = ctx->bytes_formula;
     o->stored_bytes_per_pass = stored_bytes(ctx);
@@ -1193,58 +1204,66 @@ int emsar_hip_get_info(const emsar_hip_ctx *ctx, emsar_hip_info *o) {
 // out[0..6] = mean cycles per wave spent in: loads issued + dictionary, barrier, E-step, barrier, M-step, barrier, flush;
 // out[7] = tiles.  The result vector theta is left untouched (acc is cleared again).
 int emsar_hip_debug_tiled_stamps(emsar_hip_ctx *ctx, double *out) {
-    if (!ctx || !out || ctx->layout != EMSAR_LAYOUT_TILED || !ctx->have_sample || ctx->weighted || ctx->n_tiles == 0) return EMSAR_HIP_ERR_STATE;
+    if (!ctx || !out || ctx->layout != EMSAR_LAYOUT_TILED || !ctx->have_sample || ctx->weighted || ctx->lay.n_tiles == 0) return EMSAR_HIP_ERR_STATE;
     HIPCHK(hipSetDevice(ctx->device));
-    unsigned long long *d = nullptr;
-    const size_t nw = (size_t)ctx->n_tiles * (kTiledThreads / 64), bytes = nw * 8 * sizeof(unsigned long long);
-    HIPCHK(hipMalloc(&d, bytes));
+    const size_t nw = (size_t)ctx->lay.n_tiles * (kTiledThreads / 64), bytes = nw * 8 * sizeof(unsigned long long), lds = kTiledLds;
+    DevBuf<unsigned long long> d;
+    HIPCHK(d.alloc(nw * 8));
     HIPCHK(hipMemsetAsync(d, 0, bytes, ctx->stream));
-    const size_t lds = (size_t)kTiledLdsDoubles * sizeof(double);
     HIPCHK(hipFuncSetAttribute((const void *)k_pass_tiled<false, MODE_EM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_pass_tiled<false, MODE_EM, true>), dim3((unsigned)ctx->n_tiles), dim3(kTiledThreads), lds, ctx->stream, ctx->d_tiles,
-                       ctx->d_fwd, ctx->d_bwd, ctx->d_far, ctx->d_wgt, ctx->d_rowval, ctx->d_th[0], ctx->d_acc, &ctx->d_scal->ll[3].s[0].v, Fx{0.0, 0.0}, d);
+    hipLaunchKernelGGL((k_pass_tiled<false, MODE_EM, true>), dim3((unsigned)ctx->lay.n_tiles), dim3(kTiledThreads), lds, ctx->stream, ctx->lay.d_tiles,
+                       ctx->lay.d_fwd, ctx->lay.d_bwd, ctx->lay.d_far, ctx->rw.d_wgt, ctx->lay.d_rowval, ctx->vec.d_th[0], ctx->vec.d_acc, &ctx->d_scal->ll[3].s[0].v, Fx{0.0, 0.0}, d);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(ctx->d_acc, 0, (size_t)ctx->n_tx * 8, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->vec.d_acc, 0, (size_t)ctx->n_tx * 8, ctx->stream));
     std::vector<unsigned long long> h(nw * 8);
     HIPCHK(hipMemcpyAsync(h.data(), d, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    dfree(d);
     for (int i = 0; i < 7; i++) {
         double sum = 0;
         for (size_t w = 0; w < nw; w++) sum += (double)h[w * 8 + (size_t)i];
         out[i] = sum / (double)nw;   // mean cycles per wave
     }
-    out[7] = (double)ctx->n_tiles;
+    out[7] = (double)ctx->lay.n_tiles;
     return EMSAR_HIP_OK;
 }
 
 // The same for the unit kernel (the one config 3 runs): out[0..5] = mean cycles per wave in: descriptor + dictionary + first loads,
 // barrier, E-steps, M-steps, barrier, flush; out[6] = tiles per unit; out[7] = units.
 int emsar_hip_debug_unit_stamps(emsar_hip_ctx *ctx, double *out, unsigned long long *timeline /* NULL or 4 words per unit: start, end (100 MHz ticks), place, tiles */) {
-    if (!ctx || !out || ctx->layout != EMSAR_LAYOUT_TILED || !ctx->have_sample || ctx->weighted || ctx->n_units == 0) return EMSAR_HIP_ERR_STATE;
+    if (!ctx || !out || ctx->layout != EMSAR_LAYOUT_TILED || !ctx->have_sample || ctx->weighted || ctx->lay.n_units == 0) return EMSAR_HIP_ERR_STATE;
     HIPCHK(hipSetDevice(ctx->device));
-    unsigned long long *d = nullptr;
-    const size_t nw = (size_t)ctx->n_units * (kTiledThreads / 64), bytes = (nw * 8 + (size_t)ctx->n_units * 4) * sizeof(unsigned long long);
-    HIPCHK(hipMalloc(&d, bytes));
+    const size_t nw = (size_t)ctx->lay.n_units * (kTiledThreads / 64), words = nw * 8 + (size_t)ctx->lay.n_units * 4, bytes = words * sizeof(unsigned long long), lds = kTiledLds;
+    DevBuf<unsigned long long> d;
+    HIPCHK(d.alloc(words));
     HIPCHK(hipMemsetAsync(d, 0, bytes, ctx->stream));
-    const size_t lds = (size_t)kTiledLdsDoubles * sizeof(double);
     HIPCHK(hipFuncSetAttribute((const void *)k_pass_tiled_unit<false, MODE_EM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_pass_tiled_unit<false, MODE_EM, true>), dim3((unsigned)ctx->n_units), dim3(kTiledThreads), lds, ctx->stream, ctx->d_utiles, ctx->unit_stride,
-                       ctx->d_far, ctx->d_fwd, ctx->d_bwd, ctx->d_wgt, ctx->d_th[0], ctx->d_acc, &ctx->d_scal->ll[3].s[0].v, Fx{0.0, 0.0}, d);
+    hipLaunchKernelGGL((k_pass_tiled_unit<false, MODE_EM, true>), dim3((unsigned)ctx->lay.n_units), dim3(kTiledThreads), lds, ctx->stream, ctx->lay.d_utiles, ctx->lay.unit_stride,
+                       ctx->lay.d_far, ctx->lay.d_fwd, ctx->lay.d_bwd, ctx->rw.d_wgt, ctx->vec.d_th[0], ctx->vec.d_acc, &ctx->d_scal->ll[3].s[0].v, Fx{0.0, 0.0}, d);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(ctx->d_acc, 0, (size_t)ctx->n_tx * 8, ctx->stream));
-    std::vector<unsigned long long> h(nw * 8 + (size_t)ctx->n_units * 4);
+    HIPCHK(hipMemsetAsync(ctx->vec.d_acc, 0, (size_t)ctx->n_tx * 8, ctx->stream));
+    std::vector<unsigned long long> h(words);
     HIPCHK(hipMemcpyAsync(h.data(), d, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    dfree(d);
     if (timeline) std::copy(h.begin() + (std::ptrdiff_t)(nw * 8), h.end(), timeline);
     for (int i = 0; i < 7; i++) {
         double sum = 0;
         for (size_t w = 0; w < nw; w++) sum += (double)h[w * 8 + (size_t)i];
         out[i] = sum / (double)nw;
     }
-    out[7] = (double)ctx->n_units;
+    out[7] = (double)ctx->lay.n_units;
     return EMSAR_HIP_OK;
+}
+
+// Diagnostic only (not declared in the public header; needs no device): the name of the TILED pass kernel launch_pass picks for a sample
+// (weighted or not), a mode (0: EM, 1: EM with the likelihood, 2: scatter), a tile count and the two knobs' values.
+int emsar_hip_debug_pass_kernel(int weighted, int mode, int64_t n_tiles, int tiled_multi, int weighted_unit, char *out, size_t cap) {
+    if (!out || mode < MODE_EM || mode > MODE_SCATTER) return EMSAR_HIP_ERR_ARG;
+    const PassKernel k = choose_pass_kernel(weighted != 0, mode, n_tiles, tiled_multi, weighted_unit);
+    const char *const wt = k.weighted ? "true" : "false";
+    const int len = k.family == FAMILY_MULTI  ? snprintf(out, cap, "k_pass_tiled_multi<%s, %d, %d>", wt, k.mode, k.n_multi)
+                    : k.family == FAMILY_UNIT ? snprintf(out, cap, "k_pass_tiled_unit<%s, %d>", wt, k.mode)
+                                              : snprintf(out, cap, "k_pass_tiled<%s, %d>", wt, k.mode);
+    return len >= 0 && (size_t)len < cap ? EMSAR_HIP_OK : EMSAR_HIP_ERR_ARG;
 }
 
 int emsar_hip_layout_selfcheck_tiled(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr, const int32_t *col_idx,

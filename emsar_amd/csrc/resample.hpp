@@ -12,8 +12,8 @@ namespace {
 // The sample's row weights in caller order on the device (the draws' R) and, for the set solver, the draw map: build_sets run again
 // on the same weights with the map asked for -- the same code that filled row_w / usum, so the same sets, merged rows and slots.
 int boot_prepare(emsar_hip_ctx *ctx, bool want_slot) {
-    if (!ctx->d_boot_R) HIPCHK(upload_new((void **)&ctx->d_boot_R, ctx->h_wgt.data(), (size_t)ctx->n_rows * 4));
-    if (!want_slot || ctx->boot_slot_ready) return EMSAR_HIP_OK;
+    if (!ctx->sets.d_boot_R) HIPCHK(ctx->sets.d_boot_R.upload(ctx->h_wgt.data(), (size_t)ctx->n_rows));
+    if (!want_slot || ctx->sets.boot_slot_ready) return EMSAR_HIP_OK;
     try {
         emsar::ResidentSets S;
         std::vector<int64_t> slot;
@@ -22,15 +22,15 @@ int boot_prepare(emsar_hip_ctx *ctx, bool want_slot) {
         // the resident records on the device are those of ensure_sets: same input, same builder
         size_t rw_dev = 0;
         for (int c = 0; c < emsar::kSetClasses; c++) for (const auto &d : S.desc[c]) rw_dev += d.n_r;
-        if (rw_dev != (size_t)n_rw || S.n_resident() != ctx->RS.n_resident()) { ctx->err = "bootstrap: draw map does not match the sets"; return EMSAR_HIP_ERR_HIP; }
+        if (rw_dev != (size_t)n_rw || S.n_resident() != ctx->sets.RS.n_resident()) { ctx->err = "bootstrap: draw map does not match the sets"; return EMSAR_HIP_ERR_HIP; }
         const auto &m = tid_map(ctx);
         const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !m.empty();
         for (auto &v : slot)
             if (v <= -2) { const int64_t t = -2 - v; v = n_rw + (remap ? m[(size_t)t] : t); }   // usum entry, library numbering
-        HIPCHK(upload_new((void **)&ctx->d_boot_slot, slot.data(), (size_t)ctx->n_rows * 8));
-        ctx->boot_n_rw = n_rw;
+        HIPCHK(ctx->sets.d_boot_slot.upload(slot.data(), (size_t)ctx->n_rows));
+        ctx->sets.boot_n_rw = n_rw;
     } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    ctx->boot_slot_ready = true;
+    ctx->sets.boot_slot_ready = true;
     return EMSAR_HIP_OK;
 }
 
@@ -49,13 +49,12 @@ int boot_stream_weights(emsar_hip_ctx *ctx, const int32_t *x) {
 }
 
 // What a resampling call changes in the context, put back whatever the exit: finish() on the successful exit, which reports its status,
-// else the destructor.  Owns the call's device buffers.
+// else the destructor.
 struct BootRestore {
     emsar_hip_ctx *ctx;
     bool weighted, swapped = false, finished = false;
     double fx_mass, fx_ll;
-    double *d_th0 = nullptr;               // the current point before the call (one of bufs)
-    std::vector<void *> bufs;              // device buffers of the call
+    DevBuf<double> d_th0;                  // the current point before the call
     explicit BootRestore(emsar_hip_ctx *c) : ctx(c), weighted(c->weighted), fx_mass(c->fx_mass), fx_ll(c->fx_ll) {}
     int finish() {
         if (finished) return EMSAR_HIP_OK;
@@ -64,32 +63,27 @@ struct BootRestore {
         (void)hipStreamSynchronize(ctx->stream);
         if (swapped) {                     // the sample's own weights back; an unweighted sample has no weight arrays
             rc = boot_stream_weights(ctx, ctx->h_wgt.data());
-            if (!weighted) free_row_weights(ctx);
+            if (!weighted) ctx->rw = RowWeights();
             ctx->weighted = weighted;
         }
         ctx->fx_mass = fx_mass; ctx->fx_ll = fx_ll;
         clear_solve_state(ctx);
-        if (d_th0) (void)hipMemcpy(ctx->d_th[0], d_th0, (size_t)ctx->n_tx * 8, hipMemcpyDeviceToDevice);
+        if (d_th0) (void)hipMemcpy(ctx->vec.d_th[0], d_th0, (size_t)ctx->n_tx * 8, hipMemcpyDeviceToDevice);
         return rc;
     }
-    ~BootRestore() { (void)finish(); for (void *p : bufs) dfree(p); }
-    hipError_t alloc(void **p, size_t bytes) {
-        hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess) bufs.push_back(*p);
-        return e;
-    }
+    ~BootRestore() { (void)finish(); }
 };
 
 // Gene sums of ncol (<= 65535) rows x[ncol][n_tx] in library order into out[ncol][n_genes], on the context's stream; part holds
 // ncol * n_gene_chunks doubles (may be null when no gene has more than one chunk).
 int launch_gene_sums(emsar_hip_ctx *ctx, const double *x, int64_t ncol, double *out, double *part) {
-    if (ctx->n_gene_chunks > 0)
-        hipLaunchKernelGGL(k_gene_sums, dim3((unsigned)grid_for(ctx->n_gene_chunks, 256), (unsigned)ncol), dim3(256), 0, ctx->stream,
-                           ctx->n_gene_chunks, ctx->d_chunk_beg, ctx->d_chunk_out, ctx->d_gene_tx, x, (int64_t)ctx->n_tx, out,
-                           (int64_t)ctx->n_genes, part);
-    if (ctx->n_gene_multi > 0)
-        hipLaunchKernelGGL(k_gene_finish, dim3((unsigned)grid_for(ctx->n_gene_multi, 256), (unsigned)ncol), dim3(256), 0, ctx->stream,
-                           ctx->n_gene_multi, ctx->d_gene_multi, part, ctx->n_gene_chunks, out, (int64_t)ctx->n_genes);
+    if (ctx->genes.n_gene_chunks > 0)
+        hipLaunchKernelGGL(k_gene_sums, dim3((unsigned)grid_for(ctx->genes.n_gene_chunks, 256), (unsigned)ncol), dim3(256), 0, ctx->stream,
+                           ctx->genes.n_gene_chunks, ctx->genes.d_chunk_beg, ctx->genes.d_chunk_out, ctx->genes.d_gene_tx, x, (int64_t)ctx->n_tx, out,
+                           (int64_t)ctx->genes.n_genes, part);
+    if (ctx->genes.n_gene_multi > 0)
+        hipLaunchKernelGGL(k_gene_finish, dim3((unsigned)grid_for(ctx->genes.n_gene_multi, 256), (unsigned)ncol), dim3(256), 0, ctx->stream,
+                           ctx->genes.n_gene_multi, ctx->genes.d_gene_multi, part, ctx->genes.n_gene_chunks, out, (int64_t)ctx->genes.n_genes);
     HIPCHK(hipGetLastError());
     return EMSAR_HIP_OK;
 }
@@ -125,7 +119,6 @@ struct BootRun {
     const uint64_t seed;
     const int32_t first, n_rep;
     const BootPlan &plan;
-    BootRestore guard;
     // switches
     const bool genes, binomial, hold;    // gene statistics; binomial draws (subsampling); all replicates held on the device (quantiles)
     bool use_sets = false;               // the closed form and the resident sets, all replicates of a batch in one launch per class
@@ -138,17 +131,17 @@ struct BootRun {
     int64_t n_sets = 0, n_gu = 0;        // resident sets; their transcripts, all sets together
     int64_t n_gchunk = 0, batch = 1;     // gene chunks when some gene has more than one, else 0; replicates per batch
     double n_full = 0.0;                 // subsampling: N_R, the total of the rows that are drawn
-    // device buffers (freed by the guard); rows = batch, or n_rep when the replicates are held
-    double *d_thb = nullptr, *d_sums = nullptr, *d_gsum = nullptr;      // [rows][n] theta, [rows] S_b, [rows][ng] gene sums of the replicates
-    double *d_slots = nullptr, *d_gu = nullptr;     // [batch][slot_stride] drawn row_w | usum of the sets, [batch][n_gu] their g_u gathered from it
-    int32_t *d_wb = nullptr;                        // [batch][n_rows] drawn weights in caller row order (streaming solves)
-    SetStat *d_bstat = nullptr;                     // [batch][n_sets]
-    long long *d_ndrawn = nullptr;                  // [batch] subsampling: N_b = sum_c w_c
-    double *d_acc4 = nullptr, *d_gacc4 = nullptr;   // [4][n], [4][ng] Welford accumulators of transcripts and genes: FPKM mean, M2, TPM mean, M2
-    double *d_gpart = nullptr;                      // [batch][n_gchunk] chunk sums of the genes of more than one chunk
-    double *d_q = nullptr, *d_qsums = nullptr;      // quantiles: [n_q] the probabilities, [n_rep] S_b added in the caller's order
-    double *d_qout = nullptr;                       // [2][n_q][n] then [2][n_q][ng]: FPKM and TPM quantiles of transcripts, then of genes
-    int32_t *d_libof = nullptr;                     // [n] caller tid -> library index, null = the same
+    // device buffers of the call; rows = batch, or n_rep when the replicates are held
+    DevBuf<double> d_thb, d_sums, d_gsum;           // [rows][n] theta, [rows] S_b, [rows][ng] gene sums of the replicates
+    DevBuf<double> d_slots, d_gu;                   // [batch][slot_stride] drawn row_w | usum of the sets, [batch][n_gu] their g_u gathered from it
+    DevBuf<int32_t> d_wb;                           // [batch][n_rows] drawn weights in caller row order (streaming solves)
+    DevBuf<SetStat> d_bstat;                        // [batch][n_sets]
+    DevBuf<long long> d_ndrawn;                     // [batch] subsampling: N_b = sum_c w_c
+    DevBuf<double> d_acc4, d_gacc4;                 // [4][n], [4][ng] Welford accumulators of transcripts and genes: FPKM mean, M2, TPM mean, M2
+    DevBuf<double> d_gpart;                         // [batch][n_gchunk] chunk sums of the genes of more than one chunk
+    DevBuf<double> d_q, d_qsums;                    // quantiles: [n_q] the probabilities, [n_rep] S_b added in the caller's order
+    DevBuf<double> d_qout;                          // [2][n_q][n] then [2][n_q][ng]: FPKM and TPM quantiles of transcripts, then of genes
+    DevBuf<int32_t> d_libof;                        // [n] caller tid -> library index, null = the same
     std::vector<int32_t> h_wb;           // host staging: [batch][n_rows]
     std::vector<double> h_th;            // [n] a streaming solve's result
     std::vector<SetStat> h_bstat;        // [batch][n_sets]
@@ -159,18 +152,18 @@ struct BootRun {
     long long depth_sum = 0;             // its sum of N_b
     hipEvent_t e[2] = {nullptr, nullptr};
     BootTimes t;                         // the five stage timers, unconverged, passes_max, held_bytes
+    BootRestore guard;                   // last: the context is put back before the buffers above are freed
 
     BootRun(emsar_hip_ctx *c, const emsar_em_params &par, uint64_t seed_, int32_t first_, int32_t n_rep_, const BootPlan &plan_)
-        : ctx(c), p(par), seed(seed_), first(first_), n_rep(n_rep_), plan(plan_), guard(c),
+        : ctx(c), p(par), seed(seed_), first(first_), n_rep(n_rep_), plan(plan_),
           genes(plan_.gene_mean != nullptr), binomial(plan_.fractions != nullptr), hold(plan_.n_q > 0), n(c->n_tx), n_rows(c->n_rows),
-          ng(genes ? c->n_genes : 0), gn((unsigned)grid_for(c->n_tx, 256)) {}
+          ng(genes ? c->genes.n_genes : 0), gn((unsigned)grid_for(c->n_tx, 256)), guard(c) {}
     ~BootRun() { for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev); }
 
     // the batch's theta, S_b and gene sums: the batch buffers, or the batch's rows of the held ones
     double *th_rows(int64_t done) const { return d_thb + (hold ? done * n : 0); }
     double *sum_rows(int64_t done) const { return d_sums + (hold ? done : 0); }
     double *gene_rows(int64_t done) const { return genes ? d_gsum + (hold ? done * ng : 0) : nullptr; }
-    template <class T> hipError_t dev(T *&ptr, int64_t count) { return guard.alloc((void **)&ptr, (size_t)count * sizeof(T)); }
     int numeric(const char *sub, const char *boot) { ctx->err = binomial ? sub : boot; return EMSAR_HIP_ERR_NUMERIC; }
     // device time since e[0] was recorded, added to acc (the host waits for the stream)
     int lap(double &acc) {
@@ -188,8 +181,8 @@ struct BootRun {
         const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !m.empty();
         const int64_t need = t.held_bytes + 8 * (int64_t)n_rep + 8 * nq + 16 * nq * (T + G) + (remap ? 4 * T : 0);
         if ((uint64_t)need > (uint64_t)(free_device_bytes() / 2)) { ctx->err = "bootstrap quantiles: the replicates do not fit half of the free device memory"; return EMSAR_HIP_ERR_OOM; }
-        if (dev(d_thb, n_rep * T) != hipSuccess || dev(d_sums, n_rep) != hipSuccess || (genes && dev(d_gsum, n_rep * G) != hipSuccess) || dev(d_q, nq) != hipSuccess ||
-            dev(d_qout, 2 * nq * (T + G)) != hipSuccess || dev(d_qsums, n_rep) != hipSuccess || (remap && dev(d_libof, T) != hipSuccess)) {
+        if (d_thb.alloc((size_t)(n_rep * T)) != hipSuccess || d_sums.alloc((size_t)n_rep) != hipSuccess || (genes && d_gsum.alloc((size_t)(n_rep * G)) != hipSuccess) || d_q.alloc((size_t)nq) != hipSuccess ||
+            d_qout.alloc((size_t)(2 * nq * (T + G))) != hipSuccess || d_qsums.alloc((size_t)n_rep) != hipSuccess || (remap && d_libof.alloc((size_t)T) != hipSuccess)) {
             (void)hipGetLastError();
             ctx->err = "bootstrap quantiles: device allocation of the held replicates failed";
             return EMSAR_HIP_ERR_OOM;
@@ -204,15 +197,15 @@ struct BootRun {
         int rc;
         use_sets = p.set_mode == 0;
         if (use_sets && (rc = ensure_sets(ctx))) return rc;
-        if (use_sets && ctx->RS.giant) use_sets = false;
+        if (use_sets && ctx->sets.RS.giant) use_sets = false;
         // the streaming passes solve what the set solver does not cover: everything, the streamed sets, the cluster sets
-        need_stream = !use_sets || ctx->RS.n_streamed_sets > 0 || ctx->n_cstat > 0;
+        need_stream = !use_sets || ctx->sets.RS.n_streamed_sets > 0 || ctx->sets.n_cstat > 0;
         if ((rc = boot_prepare(ctx, use_sets))) return rc;
-        n_rw = use_sets ? ctx->boot_n_rw : 0;
+        n_rw = use_sets ? ctx->sets.boot_n_rw : 0;
         slot_stride = n_rw + n;
-        n_sets = use_sets ? ctx->RS.n_resident() : 0;
-        if (use_sets) for (int c = 0; c < emsar::kSetClasses; c++) for (const auto &d : ctx->RS.desc[c]) n_gu += d.n_t;
-        n_gchunk = genes && ctx->n_gene_multi > 0 ? ctx->n_gene_chunks : 0;
+        n_sets = use_sets ? ctx->sets.RS.n_resident() : 0;
+        if (use_sets) for (int c = 0; c < emsar::kSetClasses; c++) for (const auto &d : ctx->sets.RS.desc[c]) n_gu += d.n_t;
+        n_gchunk = genes && ctx->genes.n_gene_multi > 0 ? ctx->genes.n_gene_chunks : 0;
         // (a quantile call's theta, S_b and gene sums live in the held buffers, allocated before: not part of a batch, and what is free is what they left)
         const int64_t per_rep = 8 * (slot_stride + n_gu + (hold ? 0 : n + 1 + ng) + n_gchunk) + (need_stream ? 4 * n_rows : 0) + (int64_t)sizeof(SetStat) * n_sets;
         const int64_t budget = std::min<int64_t>((int64_t)(free_device_bytes() / 4), (int64_t)2 << 30);
@@ -224,21 +217,21 @@ struct BootRun {
     // the batch's device buffers (a quantile call keeps all n_rep replicates: a batch then writes its rows of the held buffers instead
     // of buffers of its own), the copy of the current point, the events, the host staging
     int allocate() {
-        HIPCHK(dev(d_slots, batch * slot_stride)); HIPCHK(dev(d_gu, batch * n_gu));
-        if (!hold) { HIPCHK(dev(d_thb, batch * n)); HIPCHK(dev(d_sums, batch)); }
-        HIPCHK(dev(d_acc4, 4 * (int64_t)n));
-        if (genes && !hold) HIPCHK(dev(d_gsum, batch * ng));
-        if (n_gchunk) HIPCHK(dev(d_gpart, batch * n_gchunk));
-        if (genes) HIPCHK(dev(d_gacc4, 4 * ng));
+        HIPCHK(d_slots.alloc((size_t)(batch * slot_stride))); HIPCHK(d_gu.alloc((size_t)(batch * n_gu)));
+        if (!hold) { HIPCHK(d_thb.alloc((size_t)(batch * n))); HIPCHK(d_sums.alloc((size_t)batch)); }
+        HIPCHK(d_acc4.alloc((size_t)(4 * (int64_t)n)));
+        if (genes && !hold) HIPCHK(d_gsum.alloc((size_t)(batch * ng)));
+        if (n_gchunk) HIPCHK(d_gpart.alloc((size_t)(batch * n_gchunk)));
+        if (genes) HIPCHK(d_gacc4.alloc((size_t)(4 * ng)));
         if (binomial) {
-            HIPCHK(dev(d_ndrawn, batch));
+            HIPCHK(d_ndrawn.alloc((size_t)batch));
             h_ndrawn.resize((size_t)batch);
             n_full = (double)std::accumulate(ctx->h_wgt.begin(), ctx->h_wgt.end(), (int64_t)0);
         }
-        if (need_stream) HIPCHK(dev(d_wb, batch * n_rows));
-        if (n_sets) HIPCHK(dev(d_bstat, batch * n_sets));
-        HIPCHK(dev(guard.d_th0, n));
-        HIPCHK(hipMemcpyAsync(guard.d_th0, ctx->d_th[0], (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        if (need_stream) HIPCHK(d_wb.alloc((size_t)(batch * n_rows)));
+        if (n_sets) HIPCHK(d_bstat.alloc((size_t)(batch * n_sets)));
+        HIPCHK(guard.d_th0.alloc((size_t)n));
+        HIPCHK(hipMemcpyAsync(guard.d_th0, ctx->vec.d_th[0], (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream));
         HIPCHK(hipEventCreate(&e[0])); HIPCHK(hipEventCreate(&e[1]));
         if (n_sets) {
             HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets_boot<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[0]));
@@ -257,31 +250,31 @@ struct BootRun {
         if (use_sets) HIPCHK(hipMemsetAsync(d_slots, 0, (size_t)(nb * slot_stride) * 8, ctx->stream));
         if (binomial) HIPCHK(hipMemsetAsync(d_ndrawn, 0, (size_t)nb * 8, ctx->stream));
         if (n_rows > 0 && !binomial)
-            hipLaunchKernelGGL(k_boot_draw, grid, dim3(256), 0, ctx->stream, n_rows, seed, (int64_t)first + done, ctx->d_boot_R,
-                               use_sets ? ctx->d_boot_slot : nullptr, need_stream ? d_wb : nullptr, d_slots, slot_stride);
+            hipLaunchKernelGGL(k_boot_draw, grid, dim3(256), 0, ctx->stream, n_rows, seed, (int64_t)first + done, ctx->sets.d_boot_R,
+                               use_sets ? ctx->sets.d_boot_slot.get() : nullptr, need_stream ? d_wb.get() : nullptr, d_slots, slot_stride);
         if (n_rows > 0 && binomial)
-            hipLaunchKernelGGL(k_sub_draw, grid, dim3(256), 0, ctx->stream, n_rows, seed, (int64_t)first + done, frac, ctx->d_boot_R,
-                               use_sets ? ctx->d_boot_slot : nullptr, need_stream ? d_wb : nullptr, d_slots, slot_stride, d_ndrawn);
+            hipLaunchKernelGGL(k_sub_draw, grid, dim3(256), 0, ctx->stream, n_rows, seed, (int64_t)first + done, frac, ctx->sets.d_boot_R,
+                               use_sets ? ctx->sets.d_boot_slot.get() : nullptr, need_stream ? d_wb.get() : nullptr, d_slots, slot_stride, d_ndrawn);
         HIPCHK(hipGetLastError());
         return lap(t.draw_ms);
     }
     // closed form + resident sets, all replicates of the batch in one launch per class
     int solve_sets(int64_t done, int64_t nb) {
-        const auto &S = ctx->RS;
+        const auto &S = ctx->sets.RS;
         double *const thb = th_rows(done);
         int rc;
         HIPCHK(hipEventRecord(e[0], ctx->stream));
         if (n_gu > 0)
-            hipLaunchKernelGGL(k_boot_gather_u, dim3((unsigned)((n_gu + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, n_gu, ctx->d_g_tid,
+            hipLaunchKernelGGL(k_boot_gather_u, dim3((unsigned)((n_gu + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, n_gu, ctx->sets.d_g_tid,
                                d_slots, slot_stride, n_rw, d_gu);
-        hipLaunchKernelGGL(k_boot_closed, dim3(gn, (unsigned)nb), dim3(256), 0, ctx->stream, n, ctx->d_kind, d_slots, slot_stride, n_rw,
-                           ctx->d_den, thb);
+        hipLaunchKernelGGL(k_boot_closed, dim3(gn, (unsigned)nb), dim3(256), 0, ctx->stream, n, ctx->sets.d_kind, d_slots, slot_stride, n_rw,
+                           ctx->vec.d_den, thb);
         const size_t off[3] = {0, S.desc[0].size(), S.desc[0].size() + S.desc[1].size()};
         if ((rc = fork_side_streams(ctx, 2))) return rc;
         rc = launch_set_classes(ctx, 2, [&](int c, int threads, hipStream_t st) {
             hipLaunchKernelGGL((c == 2 ? k_solve_sets_boot<512> : c == 1 ? k_solve_sets_boot<256> : k_solve_sets_boot<64>),
-                               dim3((unsigned)S.desc[c].size(), (unsigned)nb), dim3(threads), S.max_lds[c], st, ctx->d_sdesc[c], ctx->d_g_tid, d_gu,
-                               d_slots, ctx->d_srp, ctx->d_sent, ctx->d_scp, ctx->d_scrow, ctx->d_den, thb, d_bstat + off[c], set_params(p), n_gu, slot_stride,
+                               dim3((unsigned)S.desc[c].size(), (unsigned)nb), dim3(threads), S.max_lds[c], st, ctx->sets.d_sdesc[c], ctx->sets.d_g_tid, d_gu,
+                               d_slots, ctx->sets.d_srp, ctx->sets.d_sent, ctx->sets.d_scp, ctx->sets.d_scrow, ctx->vec.d_den, thb, d_bstat + off[c], set_params(p), n_gu, slot_stride,
                                (int64_t)n, n_sets);
         });
         if (rc) return rc;
@@ -311,7 +304,7 @@ struct BootRun {
             if (rc) return rc;
             t.stream_ms += st.kernel_ms;
             if (!st.converged) unconv[(size_t)y] = 1;
-            hipLaunchKernelGGL(k_boot_take_streamed, dim3(gn), dim3(256), 0, ctx->stream, n, use_sets ? ctx->d_kind : nullptr, ctx->d_th[0],
+            hipLaunchKernelGGL(k_boot_take_streamed, dim3(gn), dim3(256), 0, ctx->stream, n, use_sets ? ctx->sets.d_kind.get() : nullptr, ctx->vec.d_th[0],
                                th_rows(done) + y * n);
             HIPCHK(hipGetLastError());
         }
@@ -471,21 +464,21 @@ int draw_one(emsar_hip_ctx *ctx, uint64_t seed, int32_t replicate, const double 
     if (const int rc = boot_prepare(ctx, false)) return rc;
     if (ctx->n_rows == 0) return EMSAR_HIP_OK;
     const dim3 grid((unsigned)((ctx->n_rows + 255) / 256), 1);
-    int32_t *d_w = nullptr;
-    HIPCHK(hipMalloc(&d_w, fraction ? ((size_t)ctx->n_rows + 1) / 2 * 8 + 8 : (size_t)ctx->n_rows * 4));
-    long long *d_tot = (long long *)(d_w + (ctx->n_rows + 1) / 2 * 2);      // the binomial draw kernel's total, 8-byte aligned behind the weights
-    hipError_t e = hipSuccess;
+    const size_t n_w = ((size_t)ctx->n_rows + 1) / 2 * 2;      // the binomial draw kernel's total, 8-byte aligned behind the weights
+    DevBuf<int32_t> d_w;
+    HIPCHK(d_w.alloc(fraction ? n_w + 2 : (size_t)ctx->n_rows));
+    long long *d_tot = (long long *)(d_w + n_w);
     if (!fraction)
-        hipLaunchKernelGGL(k_boot_draw, grid, dim3(256), 0, ctx->stream, ctx->n_rows, seed, (int64_t)replicate, ctx->d_boot_R, (const int64_t *)nullptr,
+        hipLaunchKernelGGL(k_boot_draw, grid, dim3(256), 0, ctx->stream, ctx->n_rows, seed, (int64_t)replicate, ctx->sets.d_boot_R, (const int64_t *)nullptr,
                            d_w, (double *)nullptr, (int64_t)0);
-    else if ((e = hipMemsetAsync(d_tot, 0, 8, ctx->stream)) == hipSuccess)
-        hipLaunchKernelGGL(k_sub_draw, grid, dim3(256), 0, ctx->stream, ctx->n_rows, seed, (int64_t)replicate, *fraction, ctx->d_boot_R,
+    else {
+        HIPCHK(hipMemsetAsync(d_tot, 0, 8, ctx->stream));
+        hipLaunchKernelGGL(k_sub_draw, grid, dim3(256), 0, ctx->stream, ctx->n_rows, seed, (int64_t)replicate, *fraction, ctx->sets.d_boot_R,
                            (const int64_t *)nullptr, d_w, (double *)nullptr, (int64_t)0, d_tot);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(w_out, d_w, (size_t)ctx->n_rows * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    dfree(d_w);
-    HIPCHK(e);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(w_out, d_w, (size_t)ctx->n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return EMSAR_HIP_OK;
 }
 
@@ -508,7 +501,7 @@ int emsar_hip_bootstrap_genes(emsar_hip_ctx *ctx, const emsar_em_params *p, uint
                               double *fpkm_mean, double *fpkm_sd, double *tpm_sd, double *replicates,
                               double *gene_fpkm_mean, double *gene_fpkm_sd, double *gene_tpm_sd, emsar_boot_stats *stats) {
     if (!ctx) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_sample || !ctx->have_genes) return EMSAR_HIP_ERR_STATE;
+    if (!ctx->have_sample || !ctx->genes.have_genes) return EMSAR_HIP_ERR_STATE;
     if (!fpkm_mean || !fpkm_sd || !tpm_sd || !gene_fpkm_mean || !gene_fpkm_sd || !gene_tpm_sd || !replicate_range_ok(first_replicate, n_replicates)) return EMSAR_HIP_ERR_ARG;
     BootPlan plan;
     plan.fpkm_mean = fpkm_mean; plan.fpkm_sd = fpkm_sd; plan.tpm_sd = tpm_sd; plan.replicates = replicates;
@@ -529,7 +522,7 @@ int emsar_hip_bootstrap_quantiles(emsar_hip_ctx *ctx, const emsar_em_params *p, 
     if (!fpkm_mean || !fpkm_sd || !tpm_sd || !fpkm_q || !tpm_q || n_replicates > emsar::kQuantMaxRep || !replicate_range_ok(first_replicate, n_replicates) ||
         !quantile_args_ok(n_q, q) || (n_gene_out != 0 && n_gene_out != 5))
         return EMSAR_HIP_ERR_ARG;
-    if (n_gene_out && !ctx->have_genes) return EMSAR_HIP_ERR_STATE;
+    if (n_gene_out && !ctx->genes.have_genes) return EMSAR_HIP_ERR_STATE;
     BootPlan plan;
     plan.fpkm_mean = fpkm_mean; plan.fpkm_sd = fpkm_sd; plan.tpm_sd = tpm_sd; plan.replicates = replicates;
     plan.gene_mean = gene_fpkm_mean; plan.gene_sd = gene_fpkm_sd; plan.gene_tpm_sd = gene_tpm_sd;
@@ -562,7 +555,7 @@ int emsar_hip_set_gene_map(emsar_hip_ctx *ctx, int32_t n_genes, const int32_t *g
     for (int32_t t = 0; t < n; t++) if (gene_of_tx[t] < -1 || gene_of_tx[t] >= n_genes) return EMSAR_HIP_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    free_genes(ctx);
+    ctx->genes = GeneMap();
     try {
         // gene CSR in library indices, each gene's transcripts by ascending caller tid; then its chunks of kGeneChunk
         std::vector<int64_t> gp((size_t)n_genes + 1, 0);
@@ -593,31 +586,30 @@ int emsar_hip_set_gene_map(emsar_hip_ctx *ctx, int32_t n_genes, const int32_t *g
         blk.insert(blk.end(), chunk_beg.begin(), chunk_beg.end());
         blk.insert(blk.end(), chunk_out.begin(), chunk_out.end());
         blk.insert(blk.end(), multi.begin(), multi.end());
-        HIPCHK(hipMalloc(&ctx->d_gene_blk, blk.size() * 4));
-        hipError_t e = hipMemcpy(ctx->d_gene_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { free_genes(ctx); HIPCHK(e); }
-        ctx->d_gene_tx = ctx->d_gene_blk;
-        ctx->d_chunk_beg = ctx->d_gene_tx + m;
-        ctx->d_chunk_out = ctx->d_chunk_beg + nc + 1;
-        ctx->d_gene_multi = ctx->d_chunk_out + nc;
-        ctx->n_genes = n_genes; ctx->n_gene_chunks = (int64_t)nc; ctx->n_gene_multi = (int64_t)multi.size() / 3;
-        ctx->have_genes = true;
-    } catch (const std::bad_alloc &) { free_genes(ctx); return EMSAR_HIP_ERR_OOM; }
+        GeneMap G;                   // moved into the context when it is complete
+        HIPCHK(G.d_gene_blk.upload(blk.data(), blk.size()));
+        G.d_gene_tx = G.d_gene_blk;
+        G.d_chunk_beg = G.d_gene_tx + m;
+        G.d_chunk_out = G.d_chunk_beg + nc + 1;
+        G.d_gene_multi = G.d_chunk_out + nc;
+        G.n_genes = n_genes; G.n_gene_chunks = (int64_t)nc; G.n_gene_multi = (int64_t)multi.size() / 3;
+        G.have_genes = true;
+        ctx->genes = std::move(G);
+    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
     return EMSAR_HIP_OK;
 }
 
 int emsar_hip_gene_sums(emsar_hip_ctx *ctx, int32_t n_cols, const double *tx_values, double *gene_out) {
     if (!ctx) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_structure || !ctx->have_genes) return EMSAR_HIP_ERR_STATE;
+    if (!ctx->have_structure || !ctx->genes.have_genes) return EMSAR_HIP_ERR_STATE;
     if (n_cols < 1 || !tx_values || !gene_out) return EMSAR_HIP_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
-    const int64_t n = ctx->n_tx, ng = ctx->n_genes, nc = ctx->n_gene_multi > 0 ? ctx->n_gene_chunks : 0;
+    const int64_t n = ctx->n_tx, ng = ctx->genes.n_genes, nc = ctx->genes.n_gene_multi > 0 ? ctx->genes.n_gene_chunks : 0;
     const int64_t cb = std::min<int64_t>(n_cols, 65535);        // columns per launch (grid y)
-    double *d_x = nullptr, *d_out = nullptr, *d_part = nullptr;
-    struct Free { double **p[3]; ~Free() { for (auto q : p) dfree(*q); } } fr{{&d_x, &d_out, &d_part}};
-    HIPCHK(hipMalloc(&d_x, (size_t)std::max<int64_t>(cb * n, 1) * 8));
-    HIPCHK(hipMalloc(&d_out, (size_t)(cb * ng) * 8));
-    if (nc) HIPCHK(hipMalloc(&d_part, (size_t)(cb * nc) * 8));
+    DevBuf<double> d_x, d_out, d_part;
+    HIPCHK(d_x.alloc((size_t)(cb * n)));
+    HIPCHK(d_out.alloc((size_t)(cb * ng)));
+    if (nc) HIPCHK(d_part.alloc((size_t)(cb * nc)));
     try {
         std::vector<double> tmp;
         for (int64_t c0 = 0; c0 < n_cols; c0 += cb) {
@@ -653,7 +645,7 @@ int emsar_hip_subsample(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t s
     for (int32_t k = 0; k < n_fractions; k++) if (!sub_fraction_ok(fractions[k])) return EMSAR_HIP_ERR_ARG;
     const int n_gene_out = (gene_fpkm_mean != nullptr) + (gene_fpkm_sd != nullptr) + (gene_tpm_mean != nullptr);
     if (n_gene_out != 0 && n_gene_out != 3) return EMSAR_HIP_ERR_ARG;
-    if (n_gene_out && !ctx->have_genes) return EMSAR_HIP_ERR_STATE;
+    if (n_gene_out && !ctx->genes.have_genes) return EMSAR_HIP_ERR_STATE;
     BootPlan plan;
     plan.fractions = fractions; plan.n_fractions = n_fractions;
     plan.fpkm_mean = fpkm_mean; plan.fpkm_sd = fpkm_sd; plan.tpm_mean = tpm_mean; plan.tpm_sd = tpm_sd; plan.replicates = replicates;

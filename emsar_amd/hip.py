@@ -234,6 +234,18 @@ def layout_selfcheck_tiled(n_tx, row_ptr, col_idx, merge_rows=False):
     return d
 
 
+def debug_pass_kernel(weighted, mode, n_tiles, tiled_multi=1, weighted_unit=1):
+    """Host-only diagnostic: the name of the TILED pass kernel launch_pass picks for a weighted or unweighted sample, a mode (0: EM,
+    1: EM with the likelihood, 2: scatter), a tile count and the values of EMSAR_HIP_TILED_MULTI and EMSAR_HIP_WEIGHTED_UNIT (no GPU needed)."""
+    f = load_library().emsar_hip_debug_pass_kernel          # not declared in the header: bound here, not in load_library
+    f.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+    buf = C.create_string_buffer(64)
+    rc = f(int(bool(weighted)), int(mode), int(n_tiles), int(tiled_multi), int(weighted_unit), buf, len(buf))
+    if rc != 0:
+        raise EmsarHipError(rc, "debug_pass_kernel")
+    return buf.value.decode()
+
+
 class EmsarHip:
     """One context = one GPU.  Mirrors the call sequence of the reference's per-sample loop
     (emsar_main.c:380-488): upload_structure once per rsh, upload_sample + solve per alignment file."""

@@ -9,6 +9,26 @@ KMAXROWLEN = 4 * 60 - 3                # layout_tiled.hpp kMaxRowLen: longer row
 LAYOUT_KNOBS = ("TILED_MULTI", "WEIGHTED_UNIT", "TILE_BLOCK", "SHORT_ECNT", "SHORT_BLOCK", "TILE_ROWS", "UNIT_TILES", "UNIT_TILES_MAX",
                 "UNIT_FAR_SOFT", "UNIT_SORT", "UNIT_LPT", "TILE_CUT", "TILE_ANCHOR", "TILE_DENSE", "TAIL_SPLIT")
 
+# The TILED branch of launch_pass as data: variant -> knobs -> which of R / E the sample carries, merged rows -> the kernel of a
+# plain pass and of a likelihood pass (MODE_EM = 0, MODE_EM_LL = 1).  Below 2048 tiles (every matrix here) TILED_MULTI = 1, the
+# default, picks what 0 picks; above, what 5 picks (test_pass_kernels_gpu.py: test_production_dispatch_above_the_pair_threshold).
+# test_pass_dispatch_cpu.py holds the last two columns against the library's own chooser.
+VARIANTS = {
+    "tiled":        (dict(TILED_MULTI="0"), "", False, "k_pass_tiled<false, 0>", "k_pass_tiled<false, 1>"),
+    "multi2":       (dict(TILED_MULTI="2"), "", False, "k_pass_tiled_multi<false, 0, 2>", "k_pass_tiled_multi<false, 1, 2>"),
+    "multi3":       (dict(TILED_MULTI="3"), "", False, "k_pass_tiled_multi<false, 0, 3>", "k_pass_tiled_multi<false, 1, 3>"),
+    "multi4":       (dict(TILED_MULTI="4"), "", False, "k_pass_tiled_multi<false, 0, 4>", "k_pass_tiled_multi<false, 1, 4>"),
+    "unit":         (dict(TILED_MULTI="5"), "", False, "k_pass_tiled_unit<false, 0>", "k_pass_tiled_unit<false, 1>"),
+    "tiled_R":      (dict(TILED_MULTI="0"), "R", False, "k_pass_tiled<true, 0>", "k_pass_tiled<true, 1>"),
+    "tiled_E":      (dict(TILED_MULTI="0"), "E", False, "k_pass_tiled<true, 0>", "k_pass_tiled<true, 1>"),
+    "tiled_RE":     (dict(TILED_MULTI="0"), "RE", False, "k_pass_tiled<true, 0>", "k_pass_tiled<true, 1>"),
+    "unit_wu0":     (dict(TILED_MULTI="5", WEIGHTED_UNIT="0"), "RE", False, "k_pass_tiled<true, 0>", "k_pass_tiled<true, 1>"),
+    "unit_wu1":     (dict(TILED_MULTI="5", WEIGHTED_UNIT="1"), "RE", False, "k_pass_tiled_unit<true, 0>", "k_pass_tiled<true, 1>"),
+    "unit_wu2":     (dict(TILED_MULTI="5", WEIGHTED_UNIT="2"), "RE", False, "k_pass_tiled_unit<true, 0>", "k_pass_tiled_unit<true, 1>"),
+    "merged_tiled": (dict(TILED_MULTI="0"), "RE", True, "k_pass_tiled<true, 0>", "k_pass_tiled<true, 1>"),
+    "merged_unit":  (dict(TILED_MULTI="5"), "RE", True, "k_pass_tiled_unit<true, 0>", "k_pass_tiled<true, 1>"),
+}
+
 
 class Problem:
     """A CSR with a sample: R (int32 counts), E (row lengths, 0 = outside the likelihood), den (None = the E-scatter)."""

@@ -414,3 +414,52 @@ def test_csr_with_64bit_row_pointers(monkeypatch):
         assert info["bytes_per_pass"] == 4 * len(s["col_idx"]) + 8 * (s["n_reads"] + 1) + 32 * s["n_tx"]      # P = 8
     finally:
         ctx.close()
+
+
+def test_one_context_through_every_free_path_repeats_bit_for_bit():
+    """One context, deterministic mode: a weighted TILED model with a gene map, adjEUMA arrays, resident sets and a bootstrap; then an
+    unweighted CSR problem (upload_structure drops all of that); then the first model again, and a second upload_sample on the same
+    structure (drops the sample's sets and row weights).  Every output equals the first visit's, and a fresh context's, bit for bit."""
+    from tests import pass_problems as P
+    from tests.conftest import get_fixture
+    m = get_fixture("syn300_se").model
+    p = P.problem("segments")
+    gene_of_tx = np.arange(m.n_tx, dtype=np.int32) // 2         # the fixture has no gene map: two transcripts per gene
+    n_genes = int(gene_of_tx.max()) + 1
+    rng = np.random.default_rng(3)
+    euma = rng.integers(0, 5000, size=(m.n_rows, 5)).astype(np.int32)
+    wf = rng.random(5)
+
+    def solve_out(ctx):
+        th, st = ctx.solve(set_mode=0)
+        return [th, np.array([st.loglik, st.iters, st.converged])]
+
+    def visit(ctx):
+        """Steps 1 to 3: structure and sample, gene map, adjEUMA, set solve, bootstrap of 4 replicates."""
+        ctx.upload_structure(m.n_tx, m.row_ptr, m.col_idx, LAYOUT_TILED)
+        ctx.upload_sample(m.R, m.E, None)
+        ctx.set_gene_map(gene_of_tx, n_genes)
+        ctx.upload_euma(euma)
+        out = [ctx.adj_euma(wf)] + solve_out(ctx)
+        out.append(ctx.gene_sums(out[1]))
+        mean, sd, tsd, reps, _ = ctx.bootstrap(4, seed=7, want_replicates=True)
+        return out + [mean, sd, tsd, reps]
+
+    def same(got, want, what):
+        assert len(got) == len(want)
+        for i, (a, b) in enumerate(zip(got, want)):
+            np.testing.assert_array_equal(a, b, err_msg="%s, output %d" % (what, i))
+
+    with EmsarHip(0) as ctx, EmsarHip(0) as fresh:
+        ctx.set_deterministic(True)
+        fresh.set_deterministic(True)
+        first = visit(ctx)
+        assert np.isfinite(first[1]).all() and first[1].sum() > 0 and first[2][2] == 1
+        ctx.upload_structure(p.n_tx, p.rp, p.ci, LAYOUT_CSR)
+        ctx.upload_sample(None, None, None)
+        th, st = ctx.solve(set_mode=1, max_iter=300)
+        assert np.isfinite(th).all() and th.sum() > 0
+        same(visit(ctx), first, "second visit")
+        ctx.upload_sample(m.R, m.E, None)
+        same(solve_out(ctx), first[1:3], "after a second upload_sample")
+        same(visit(fresh), first, "fresh context")

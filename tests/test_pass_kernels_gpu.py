@@ -15,29 +15,12 @@ import oracle as O
 from emsar_amd import EmsarHip, EmsarHipError
 from emsar_amd.hip import LAYOUT_TILED
 from tests import pass_problems as P
+from tests.pass_problems import VARIANTS
 
 pytestmark = pytest.mark.gpu
 INT32_MAX = 2 ** 31 - 1
 ERR_ARG = -1
 
-# The TILED branch of launch_pass as data: variant -> knobs -> which of R / E the sample carries, merged rows -> the kernel of a
-# plain pass and of a likelihood pass (MODE_EM = 0, MODE_EM_LL = 1).  Below 2048 tiles (every matrix here) TILED_MULTI = 1, the
-# default, picks what 0 picks; above, what 5 picks (test_production_dispatch_above_the_pair_threshold).
-VARIANTS = {
-    "tiled":        (dict(TILED_MULTI="0"), "", False, "k_pass_tiled<false, 0>", "k_pass_tiled<false, 1>"),
-    "multi2":       (dict(TILED_MULTI="2"), "", False, "k_pass_tiled_multi<false, 0, 2>", "k_pass_tiled_multi<false, 1, 2>"),
-    "multi3":       (dict(TILED_MULTI="3"), "", False, "k_pass_tiled_multi<false, 0, 3>", "k_pass_tiled_multi<false, 1, 3>"),
-    "multi4":       (dict(TILED_MULTI="4"), "", False, "k_pass_tiled_multi<false, 0, 4>", "k_pass_tiled_multi<false, 1, 4>"),
-    "unit":         (dict(TILED_MULTI="5"), "", False, "k_pass_tiled_unit<false, 0>", "k_pass_tiled_unit<false, 1>"),
-    "tiled_R":      (dict(TILED_MULTI="0"), "R", False, "k_pass_tiled<true, 0>", "k_pass_tiled<true, 1>"),
-    "tiled_E":      (dict(TILED_MULTI="0"), "E", False, "k_pass_tiled<true, 0>", "k_pass_tiled<true, 1>"),
-    "tiled_RE":     (dict(TILED_MULTI="0"), "RE", False, "k_pass_tiled<true, 0>", "k_pass_tiled<true, 1>"),
-    "unit_wu0":     (dict(TILED_MULTI="5", WEIGHTED_UNIT="0"), "RE", False, "k_pass_tiled<true, 0>", "k_pass_tiled<true, 1>"),
-    "unit_wu1":     (dict(TILED_MULTI="5", WEIGHTED_UNIT="1"), "RE", False, "k_pass_tiled_unit<true, 0>", "k_pass_tiled<true, 1>"),
-    "unit_wu2":     (dict(TILED_MULTI="5", WEIGHTED_UNIT="2"), "RE", False, "k_pass_tiled_unit<true, 0>", "k_pass_tiled_unit<true, 1>"),
-    "merged_tiled": (dict(TILED_MULTI="0"), "RE", True, "k_pass_tiled<true, 0>", "k_pass_tiled<true, 1>"),
-    "merged_unit":  (dict(TILED_MULTI="5"), "RE", True, "k_pass_tiled_unit<true, 0>", "k_pass_tiled<true, 1>"),
-}
 MATRICES = ["segments", "cfg5_reads", "cfg5_segments", "ugly"]
 
 
