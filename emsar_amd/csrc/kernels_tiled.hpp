@@ -147,7 +147,9 @@ struct DTile {
 };
 struct TileWords { uint32_t w[16]; };
 static_assert(sizeof(TileWords) == sizeof(Tile), "tile_load reads a Tile as 16 dwords");
-static_assert(offsetof(Tile, row_base) == 16 && offsetof(Tile, lo) == 28 && offsetof(Tile, near_n) == 32 && offsetof(Tile, n_slices) == 36 && offsetof(Tile, follows) == 38 &&
+static_assert(offsetof(Tile, fwd_off) == 0 && offsetof(Tile, bwd_off) == 8 && offsetof(Tile, row_base) == 16 && offsetof(Tile, far_off) == 20 &&
+              offsetof(Tile, coo_off) == 24 && offsetof(Tile, lo) == 28 && offsetof(Tile, near_n) == 32 && offsetof(Tile, far_n) == 34 &&
+              offsetof(Tile, n_slices) == 36 && offsetof(Tile, follows) == 38 &&
               offsetof(Tile, wave_of) == 39 && offsetof(Tile, k) == 40 && offsetof(Tile, m) == 48 && offsetof(Tile, coo_n) == 56, "tile_load's field positions");
 __device__ __forceinline__ DTile tile_load(const Tile *p /* wave-uniform */) {
     const TileWords r = *reinterpret_cast<const TileWords *>(p);

@@ -101,26 +101,38 @@ constexpr int kDenseMin = 1;           // columns with fewer entries in a slice 
                                        // a load, an LDS read and an LDS atomic per entry -- costs more than a mostly empty segment: 4 / 2 / 1 -> 0.139 / 0.133 / 0.127 ms)
 // the entries (block * 8 + mask) of one row from its dictionary slots (any order; a slot that occurs twice -- an internal repeat
 // of the transcript -- opens a second entry of the same block: a subset holds a transcript once)
+// The entry rule, fed the (block, bit) of a row's slots or tids in sorted order: a slot joins the open entry unless it lies in
+// another block or the open subset holds its bit already; then it opens the next entry.
+struct EntryRun {
+    int cur_b = -1;                      // block of the open entry (-1: none)
+    uint32_t cur_m = 0;                  // its subset so far
+    // true when the slot opens an entry; the entry that it ends, if any, is appended to `closed`
+    bool opens(int b, uint32_t bit, std::vector<uint32_t> *closed = nullptr) {
+        if (b == cur_b && !(cur_m & bit)) { cur_m |= bit; return false; }
+        if (closed) close(*closed);
+        cur_b = b; cur_m = bit;
+        return true;
+    }
+    // the open entry's code appended to `ent`, if there is one; none is open afterwards
+    void close(std::vector<uint32_t> &ent) {
+        if (cur_b >= 0) ent.push_back(entry_code((uint32_t)cur_b, cur_m));
+        cur_b = -1; cur_m = 0;
+    }
+};
 inline void slots_to_entries(std::vector<uint32_t> &slots, std::vector<uint32_t> &ent, uint32_t near_n) {
     std::sort(slots.begin(), slots.end());
     ent.clear();
-    int cur_b = -1;
-    uint32_t cur_m = 0;
+    EntryRun run;
     const uint32_t far_base = (uint32_t)kBlkEntries * (uint32_t)near_blocks((int)near_n);
     for (uint32_t sl : slots) {
         if (sl >= near_n) {                       // a far transcript: its own entry (slots are sorted: the far ones come last)
-            if (cur_b >= 0) { ent.push_back(entry_code((uint32_t)cur_b, cur_m)); cur_b = -1; cur_m = 0; }
+            run.close(ent);
             ent.push_back(far_base + (sl - near_n));
             continue;
         }
-        const int b = (int)(sl / (uint32_t)kBlk);
-        const uint32_t bit = 1u << (sl % (uint32_t)kBlk);
-        if (b != cur_b || (cur_m & bit)) {
-            if (cur_b >= 0) ent.push_back(entry_code((uint32_t)cur_b, cur_m));
-            cur_b = b; cur_m = bit;
-        } else cur_m |= bit;
+        run.opens((int)(sl / (uint32_t)kBlk), 1u << (sl % (uint32_t)kBlk), &ent);
     }
-    if (cur_b >= 0) ent.push_back(entry_code((uint32_t)cur_b, cur_m));
+    run.close(ent);
 }
 constexpr int64_t kTileEntries = 65536;
 
@@ -279,170 +291,29 @@ inline int check_tiled_extents(const TiledLayout &L) {
     return 0;
 }
 
-// With merge_rows, rows with the same tid multiset (2..kMaxRowLen tids) are stored once and weighted by the sum of
-// their members' weights -- what the reference's update_ReadCounts does when it counts reads per segment
-// (emsar_functions.c:838-943).  Every quantity the library computes is a sum over rows of a function of the row's tid
-// set times a per-row weight, so the merge is exact up to summation order.
-inline int build_tiled(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr_in, const int32_t *col_idx_in, TiledLayout &out,
-                       bool merge_rows = false, bool renumber = true) {
-    if (n_rows >= (int64_t)1 << 32) return -1;
-    out = TiledLayout();
-    const uint64_t *row_ptr = row_ptr_in;
-    const int32_t *col_idx = col_idx_in;
-    if (renumber) cooccurrence_order(n_rows, n_tx, row_ptr_in, col_idx_in, kMaxRowLen, kBlk, out.new_of_old, out.renum);
-    // the id under which entry k of the caller's col_idx is stored
-    const int32_t *tid_map = out.new_of_old.empty() ? nullptr : out.new_of_old.data();
-    auto tid_at = [&](uint64_t k) -> int32_t { return tid_map ? tid_map[col_idx[k]] : col_idx[k]; };
-    // merged view of the matrix (only built when asked for): unique rows with sorted tids
-    std::vector<uint64_t> m_ptr;
-    std::vector<int32_t> m_col;
-    std::vector<uint32_t> orig_of_merged;   // first member, for rows that are not merged (singles, long rows)
-    if (merge_rows) {
-        const int64_t nnz_in = (int64_t)row_ptr_in[n_rows];
-        std::vector<int32_t> scol((size_t)nnz_in);
-        std::vector<uint64_t> hash((size_t)n_rows, 0);
-        for (int64_t r = 0; r < n_rows; r++) {
-            uint64_t b = row_ptr_in[r], e = row_ptr_in[r + 1];
-            for (uint64_t k = b; k < e; k++) scol[(size_t)k] = tid_at(k);
-            std::sort(scol.begin() + (int64_t)b, scol.begin() + (int64_t)e);
-            uint64_t h = 1469598103934665603ull ^ (e - b);
-            for (uint64_t k = b; k < e; k++) { h ^= (uint64_t)(uint32_t)scol[(size_t)k]; h *= 1099511628211ull; }
-            hash[(size_t)r] = h;
-        }
-        uint64_t cap = 16;
-        while (cap < (uint64_t)n_rows * 2 + 2) cap <<= 1;
-        std::vector<int64_t> table((size_t)cap, -1);       // -> merged id
-        std::vector<int64_t> merged_of((size_t)n_rows, -1);
-        std::vector<uint32_t> cnt;                          // members per merged row
-        m_ptr.push_back(0);
-        for (int64_t r = 0; r < n_rows; r++) {
-            uint64_t b = row_ptr_in[r], e = row_ptr_in[r + 1], len = e - b;
-            bool mergeable = len >= 2 && len <= (uint64_t)kMaxRowLen;
-            int64_t id = -1;
-            if (mergeable) {
-                uint64_t h = hash[(size_t)r] & (cap - 1);
-                while (table[(size_t)h] >= 0) {
-                    int64_t o = table[(size_t)h];
-                    uint64_t ob = m_ptr[(size_t)o], oe = m_ptr[(size_t)o + 1];
-                    if (oe - ob == len && std::memcmp(m_col.data() + ob, scol.data() + b, len * 4) == 0) { id = o; break; }
-                    h = (h + 1) & (cap - 1);
-                }
-                if (id < 0) table[(size_t)h] = (int64_t)cnt.size();
-            }
-            if (id < 0) {
-                id = (int64_t)cnt.size();
-                m_col.insert(m_col.end(), scol.begin() + (int64_t)b, scol.begin() + (int64_t)e);
-                m_ptr.push_back((uint64_t)m_col.size());
-                cnt.push_back(0);
-                orig_of_merged.push_back((uint32_t)r);
-            }
-            merged_of[(size_t)r] = id;
-            cnt[(size_t)id]++;
-        }
-        const int64_t n_m = (int64_t)cnt.size();
-        out.mem_ptr.assign((size_t)n_m + 1, 0);
-        for (int64_t i = 0; i < n_m; i++) out.mem_ptr[(size_t)i + 1] = out.mem_ptr[(size_t)i] + cnt[(size_t)i];
-        out.mem_row.resize((size_t)n_rows);
-        std::vector<uint64_t> fillp(out.mem_ptr.begin(), out.mem_ptr.end() - 1);
-        for (int64_t r = 0; r < n_rows; r++) out.mem_row[(size_t)fillp[(size_t)merged_of[(size_t)r]]++] = (uint32_t)r;
-        out.merged = true;
-        row_ptr = m_ptr.data();
-        col_idx = m_col.data();
-        tid_map = nullptr;                      // the merged view is in the library's numbering already
-        const int64_t n_rows_orig = n_rows;
-        n_rows = n_m;
-        out.n_rows = n_rows_orig; out.n_tx = n_tx; out.nnz = nnz_in;
-    }
-    if (!merge_rows) { out.n_rows = n_rows; out.n_tx = n_tx; out.nnz = (int64_t)row_ptr[n_rows]; }
-    out.left_ptr.push_back(0);
+// ---- the builder ----
+// build_tiled (at the end of this section) reads as the algorithm; every stage is a function or a small struct of its own:
+//   read_tiled_knobs -> (merge_identical_rows) -> classify_rows -> sort_rows -> FragmentTiler::run per fragment ->
+//   concat_fragments -> order_units -> (print_layout_stats) -> check_tiled_extents.
+// The layout is a function of the matrix and the knobs alone (not of the thread count, the machine or the standard library):
+// tests/test_layout_fuzz.py pins it, byte for byte, by the digests of tests/golden/layout_digests.txt.
 
-    const bool dbg_t = getenv("EMSAR_HIP_DEBUG") != nullptr;
-    auto t_now = [] { return std::chrono::steady_clock::now(); };
-    auto t_ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto tp0 = t_now();
-    // ---- classify rows; keys of the tiled ones ----
-    // host threads of the builder (fragments below use the same rule); every parallel step gives the result of the
-    // sequential one, so the layout does not depend on the number of threads
-    int n_host = 1;
-    int64_t min_chunk = (int64_t)1 << 16;                 // rows per thread at least
-    {
-        unsigned hw = std::thread::hardware_concurrency();
-        n_host = (int)(hw ? std::min(hw, 16u) : 1u);
-        if (n_rows < (int64_t)1 << 16) n_host = 1;
-        if (const char *e = getenv("EMSAR_HOST_THREADS")) { int v = atoi(e); if (v >= 1) { n_host = std::min(v, 64); min_chunk = 16; } }   // tests: threads on small inputs
-    }
-    auto par_ranges = [&](int64_t n, const std::function<void(int, int64_t, int64_t)> &fn) {
-        const int nt = (int)std::min<int64_t>(n_host, std::max<int64_t>(1, n / min_chunk));
-        run_on_threads(nt, [&](int t) { fn(t, n * t / nt, n * (t + 1) / nt); });
-        return nt;
-    };
-    std::vector<int32_t> mintid((size_t)n_rows, -1);      // the anchor tid of every tiled row (see below)
-    std::vector<uint16_t> ecnt((size_t)n_rows, 0);        // its number of block entries (dictionaries start at multiples of kBlk, so
-                                                          // a near tid t lies in block t / kBlk whatever the tile): the sort's length
-    bool anchor_median = true;
-    if (const char *e = getenv("EMSAR_HIP_TILE_ANCHOR")) anchor_median = atoi(e) != 0;
-    // the row's anchor in tid space decides which tile it joins: the MEDIAN id, not the smallest -- a read that also
-    // hits one transcript of another family stays with its own family, and only that one entry is far from the
-    // tile's window (anchored at the minimum, half of such rows landed in the other family's tile with ALL their
-    // in-family ids far: 6.5 M far entries on config 3 instead of 1.6 M)
-    par_ranges(n_rows, [&](int, int64_t lo, int64_t hi) {
-        std::vector<int32_t> tmp;
-        for (int64_t r = lo; r < hi; r++) {
-            const uint64_t b = row_ptr[r], e = row_ptr[r + 1], len = e - b;
-            if (len < 2 || len > (uint64_t)kMaxRowLen) continue;
-            tmp.resize((size_t)len);
-            for (uint64_t k = b; k < e; k++) tmp[(size_t)(k - b)] = tid_at(k);
-            std::sort(tmp.begin(), tmp.end());
-            mintid[(size_t)r] = anchor_median ? tmp[(size_t)(len / 2)] : tmp[0];
-            int n_ent = 0, cur_b = -1;
-            uint32_t cur_m = 0;
-            for (int32_t t : tmp) {                        // the rule of slots_to_entries, on tids
-                const int bb = t / kBlk;
-                const uint32_t bit = 1u << (t % kBlk);
-                if (bb != cur_b || (cur_m & bit)) { n_ent++; cur_b = bb; cur_m = bit; } else cur_m |= bit;
-            }
-            ecnt[(size_t)r] = (uint16_t)n_ent;
-        }
-    });
-    std::vector<uint32_t> act;                             // the tiled rows, ascending
-    {
-        // every thread classifies a contiguous range of rows into lists of its own; the lists are joined in range order
-        struct Part { std::vector<uint32_t> single_row, left_row, act; std::vector<int32_t> single_tid, left_col; std::vector<uint64_t> left_len; };
-        std::vector<Part> part((size_t)std::max(1, n_host));
-        const int np = par_ranges(n_rows, [&](int t, int64_t lo, int64_t hi) {
-            Part &P = part[(size_t)t];
-            for (int64_t r = lo; r < hi; r++) {
-                const uint64_t b = row_ptr[r], e = row_ptr[r + 1], len = e - b;
-                if (len == 0) continue;
-                const uint32_t r_orig = merge_rows ? orig_of_merged[(size_t)r] : (uint32_t)r;   // singles / long rows are never merged
-                if (len == 1) { P.single_row.push_back(r_orig); P.single_tid.push_back(tid_at(b)); continue; }
-                if (len > (uint64_t)kMaxRowLen) {
-                    P.left_row.push_back(r_orig);
-                    for (uint64_t k = b; k < e; k++) P.left_col.push_back(tid_at(k));
-                    P.left_len.push_back(len);
-                    continue;
-                }
-                P.act.push_back((uint32_t)r);
-            }
-        });
-        size_t ns = 0, nl = 0, nlc = 0, na = 0;
-        for (int t = 0; t < np; t++) { ns += part[(size_t)t].single_row.size(); nl += part[(size_t)t].left_row.size(); nlc += part[(size_t)t].left_col.size(); na += part[(size_t)t].act.size(); }
-        out.single_row.reserve(ns); out.single_tid.reserve(ns); out.left_row.reserve(nl); out.left_col.reserve(nlc); out.left_ptr.reserve(nl + 1); act.reserve(na);
-        for (int t = 0; t < np; t++) {
-            Part &P = part[(size_t)t];
-            out.single_row.insert(out.single_row.end(), P.single_row.begin(), P.single_row.end());
-            out.single_tid.insert(out.single_tid.end(), P.single_tid.begin(), P.single_tid.end());
-            out.left_row.insert(out.left_row.end(), P.left_row.begin(), P.left_row.end());
-            out.left_col.insert(out.left_col.end(), P.left_col.begin(), P.left_col.end());
-            for (uint64_t len : P.left_len) out.left_ptr.push_back(out.left_ptr.back() + len);
-            act.insert(act.end(), P.act.begin(), P.act.end());
-            P = Part();
-        }
-    }
-    const int64_t n_act = (int64_t)act.size();
+// an integer knob from the environment: kept only when it lies in [lo, hi]
+template <class T>
+inline void env_int(const char *name, int lo, int hi, T &value) {
+    if (const char *e = getenv(name)) { const int v = atoi(e); if (v >= lo && v <= hi) value = (T)v; }
+}
+inline void env_flag(const char *name, bool &value) { if (const char *e = getenv(name)) value = atoi(e) != 0; }
+
+// Every knob of the builder (EMSAR_HIP_<NAME>), with the measurements that set its default: the lab record.
+struct TiledKnobs {
+    bool anchor_median = true;  // TILE_ANCHOR.  The row's anchor in tid space decides which tile it joins: the MEDIAN id, not the smallest -- a read that also
+                                // hits one transcript of another family stays with its own family, and only that one entry is far from the
+                                // tile's window (anchored at the minimum, half of such rows landed in the other family's tile with ALL their
+                                // in-family ids far: 6.5 M far entries on config 3 instead of 1.6 M)
     // Sort granularity in tid space.  A tile's dictionary must hold a block's tid range plus the rows' reach, so
     // blocks stay small; wide blocks keep the (block, length) buckets large, i.e. the slices uniform.
-    int32_t block = 32;        // with 4-slot blocks (kBlk): 24 / 32 / 48 / 64 / 96 -> family law 0.1063 / 0.1060 / 0.1071 / 0.1089 / 0.1146, window law 0.0967 /
+    int32_t block = 32;        // TILE_BLOCK.  With 4-slot blocks (kBlk): 24 / 32 / 48 / 64 / 96 -> family law 0.1063 / 0.1060 / 0.1071 / 0.1089 / 0.1146, window law 0.0967 /
                                // 0.0969 / 0.0980 / 0.1030 / 0.1014, config 5 x 0.25 - / 0.2195 / 0.2204 / 0.2192 / 0.2216 ms (gpurun_out/sweep_blk4).
                                // With 3-slot blocks: 16 / 24 / 32 / 48 / 64 / 96 / 128 -> family law 0.1122 / 0.1126 / 0.1128 / 0.1141 / 0.1152 / 0.1205 / 0.1236,
                                // window law 0.1017 / 0.1012 / 0.1015 / 0.1015 / 0.1024 / 0.1042 / 0.1059, config 5 x 0.25 - / - / 0.2469 / 0.2376 / 0.2439 /
@@ -453,462 +324,659 @@ inline int build_tiled(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr_in,
                                // config 3, rows sorted by entry count inside a block: 96 / 128 / 160 / 192 tids -> 0.1178 / 0.1169 / 0.1187 / 0.124 ms per pass
                                // end of round 2 (spill-free unit kernel): 96 / 104 / 112 / 120 / 128 / 144 / 160 -> 0.1052 / 0.1056 / 0.1055 / 0.1066 / 0.1063 /
                                // 0.1072 / 0.1067 on config 3, but config 5 (20 transcripts per read) 0.954 ms at 112 against 0.940 at 128: stays 128
-    if (const char *e = getenv("EMSAR_HIP_TILE_BLOCK")) { int v = atoi(e); if (v >= 16 && v <= 900) block = v; }
-    int short_ecnt = 0; int32_t short_block = 512;      // rows of <= short_ecnt entries: sort block short_block (0 = no such class)
-    if (const char *e = getenv("EMSAR_HIP_SHORT_ECNT")) { int v = atoi(e); if (v >= 0 && v <= 32) short_ecnt = v; }
-    if (const char *e = getenv("EMSAR_HIP_SHORT_BLOCK")) { int v = atoi(e); if (v >= block && v <= (1 << 20)) short_block = v; }
-    if (short_block < block) short_block = block;
-    int64_t tile_rows = kTileRows;
-    int unit_tiles = 2;                 // tiles that may share one dictionary (a unit: one workgroup, one dictionary load, one flush)
-    if (const char *e = getenv("EMSAR_HIP_UNIT_TILES")) { int v = atoi(e); if (v >= 1 && v <= kUnitMaxTiles) unit_tiles = v; }
-    if (const char *e = getenv("EMSAR_HIP_TILE_ROWS")) { int v = atoi(e); if (v >= kTileSliceRows && v <= kTileRows) tile_rows = v / kTileSliceRows * kTileSliceRows; }
+    int short_ecnt = 0;        // SHORT_ECNT, SHORT_BLOCK.  Rows of <= short_ecnt entries: sort block short_block (0 = no such class); never narrower than block
+    int32_t short_block = 512;
+    int64_t tile_rows = kTileRows;   // TILE_ROWS: rows per tile, whole slices
+    int unit_tiles = 2;        // UNIT_TILES: tiles that may share one dictionary (a unit: one workgroup, one dictionary load, one flush)
     // A unit may grow beyond unit_tiles tiles' worth of rows (up to unit_tiles_max) as long as that does not fill its dictionary with far
     // entries: rows of many neighbouring transcripts (config 5: 20 per read) pack three tiles under one dictionary with ~150 far slots,
     // rows of gene families (config 3) would pay 2.6 x the far entries for the third tile.  Measured with a fixed 3: config 5 x 0.25
     // 0.2121 -> 0.1896 ms, config 3 family law 0.1054 -> 0.1106, window law 0.0966 -> 0.1068 (gpurun_out/sweep4).
-    int unit_tiles_max = 3, far_soft = 160;
-    if (const char *e = getenv("EMSAR_HIP_UNIT_TILES_MAX")) { int v = atoi(e); if (v >= 1 && v <= kUnitMaxTiles) unit_tiles_max = v; }
-    if (const char *e = getenv("EMSAR_HIP_UNIT_FAR_SOFT")) { int v = atoi(e); if (v >= 0 && v <= kFarMax) far_soft = v; }
-    if (unit_tiles_max < unit_tiles) unit_tiles_max = unit_tiles;
-    const int64_t base_rows = tile_rows * unit_tiles;
-    const int64_t unit_rows = tile_rows * unit_tiles_max;
-    int dense_min = kDenseMin;
-    if (const char *e = getenv("EMSAR_HIP_TILE_DENSE")) { int v = atoi(e); if (v >= 1 && v <= 64) dense_min = v; }
-    bool unit_sort = true;
-    if (const char *e = getenv("EMSAR_HIP_UNIT_SORT")) unit_sort = atoi(e) != 0;
-    bool unit_lpt = true;               // slices dealt to the waves by work (0: in order, alternate tiles mirrored)
-    if (const char *e = getenv("EMSAR_HIP_UNIT_LPT")) unit_lpt = atoi(e) != 0;
-    bool cut_at_slices = true;
-    if (const char *e = getenv("EMSAR_HIP_TILE_CUT")) cut_at_slices = atoi(e) != 0;
-    const auto tp1 = t_now();
-    // ---- sort: pass A by anchor tid, pass B by (block, length class); both stable ----
-    // A stable counting sort over chunks of the input: one histogram per chunk, offsets ordered (key, chunk), then every
-    // chunk scatters its own rows in order -- the permutation of the sequential sort.
-    auto counting_sort = [&](const std::vector<uint32_t> &in, std::vector<uint32_t> &dst, size_t n_keys, auto key) {
-        const int64_t n = (int64_t)in.size();
-        dst.resize((size_t)n);
-        const int nc = (int)std::min<int64_t>(n_host, std::max<int64_t>(1, n / min_chunk));
-        std::vector<std::vector<uint64_t>> hist((size_t)nc);
-        auto chunk = [&](int c) { return std::make_pair(n * c / nc, n * (c + 1) / nc); };
-        auto count = [&](int c) {
-            hist[(size_t)c].assign(n_keys, 0);
-            auto [lo, hi] = chunk(c);
-            for (int64_t i = lo; i < hi; i++) hist[(size_t)c][key(in[(size_t)i])]++;
-        };
-        run_on_threads(nc, count);
-        uint64_t run = 0;
-        for (size_t k = 0; k < n_keys; k++)
-            for (int c = 0; c < nc; c++) { const uint64_t h = hist[(size_t)c][k]; hist[(size_t)c][k] = run; run += h; }
-        auto scatter = [&](int c) {
-            auto [lo, hi] = chunk(c);
-            uint64_t *off = hist[(size_t)c].data();
-            for (int64_t i = lo; i < hi; i++) { const uint32_t r = in[(size_t)i]; dst[(size_t)off[key(r)]++] = r; }
-        };
-        run_on_threads(nc, scatter);
-    };
-    std::vector<uint32_t> pa, perm;
-    {
-        counting_sort(act, pa, (size_t)n_tx, [&](uint32_t r) { return (size_t)mintid[r]; });
-        std::vector<uint32_t>().swap(act);
-        const int64_t n_blocks = ((int64_t)n_tx + block - 1) / block;
-        // Rows of few entries touch few transcripts: they are sorted in WIDER blocks (their (block, count) buckets then hold several
-        // slices of equal rows -- no padding -- and a unit of them still spans a narrow range of anchors); they come after the others.
-        counting_sort(pa, perm, (size_t)(2 * n_blocks * kLenClasses), [&](uint32_t r) {
-            const int e = (int)ecnt[r];
-            if (e <= short_ecnt) return (size_t)(n_blocks + mintid[r] / short_block) * kLenClasses + (size_t)len_class((int64_t)e);
-            return (size_t)(mintid[r] / block) * kLenClasses + (size_t)len_class((int64_t)e);
-        });
-    }
-    std::vector<uint32_t>().swap(pa);
-    const auto tp2 = t_now();
+    int unit_tiles_max = 3, far_soft = 160;   // UNIT_TILES_MAX (never below unit_tiles), UNIT_FAR_SOFT
+    int dense_min = kDenseMin; // TILE_DENSE: see kDenseMin; anything but 1 builds COO lists, which check_tiled_extents refuses
+    bool unit_sort = true;     // UNIT_SORT: the rows of a unit in descending order of their entry count
+    bool unit_lpt = true;      // UNIT_LPT: slices dealt to the waves by work (0: in order, alternate tiles mirrored)
+    bool cut_at_slices = true; // TILE_CUT: a unit closed by a cap in the middle of a slice hands the rows of that slice to the next unit
+    int64_t frag_rows = kFragRows;   // FRAG_ROWS: sorted rows per independently tiled fragment (tests: many fragments on small inputs)
+    // TAIL_SPLIT.  The tail: with ~3.4 k units for 1024 workgroup slots the last workgroups run on a half-empty chip (timeline of config 3: 14 of
+    // 114 us below 75 % occupancy).  The lightest units are therefore cut into their tiles -- every tile carries the dictionary
+    // descriptor, so a tile that stops following is a unit of its own -- and the small pieces fill the tail.  Measured (EMSAR_HIP_TAIL_SPLIT =
+    // share of the units cut, config 3): 0 / 10 / 20 / 35 / 50 % -> family law 0.1071 / 0.1055 / 0.1075 / 0.1077 / 0.1108 ms, window law
+    // 0.0967 / 0.0976 / 0.0986 / 0.1000: what the tail gains the extra per-unit overhead takes back.  Off.
+    int tail_pct = 0;
+    bool debug = false;        // EMSAR_HIP_DEBUG: timings and statistics on stderr
+    int64_t base_rows = 0, unit_rows = 0;     // derived: rows of a unit of unit_tiles / unit_tiles_max tiles
+};
+inline TiledKnobs read_tiled_knobs() {
+    TiledKnobs K;
+    env_flag("EMSAR_HIP_TILE_ANCHOR", K.anchor_median);
+    env_int("EMSAR_HIP_TILE_BLOCK", 16, 900, K.block);
+    env_int("EMSAR_HIP_SHORT_ECNT", 0, 32, K.short_ecnt);
+    env_int("EMSAR_HIP_SHORT_BLOCK", K.block, 1 << 20, K.short_block);
+    K.short_block = std::max(K.short_block, K.block);
+    env_int("EMSAR_HIP_UNIT_TILES", 1, kUnitMaxTiles, K.unit_tiles);
+    env_int("EMSAR_HIP_TILE_ROWS", kTileSliceRows, kTileRows, K.tile_rows);
+    K.tile_rows = K.tile_rows / kTileSliceRows * kTileSliceRows;
+    env_int("EMSAR_HIP_UNIT_TILES_MAX", 1, kUnitMaxTiles, K.unit_tiles_max);
+    K.unit_tiles_max = std::max(K.unit_tiles_max, K.unit_tiles);
+    env_int("EMSAR_HIP_UNIT_FAR_SOFT", 0, kFarMax, K.far_soft);
+    env_int("EMSAR_HIP_TILE_DENSE", 1, 64, K.dense_min);
+    env_flag("EMSAR_HIP_UNIT_SORT", K.unit_sort);
+    env_flag("EMSAR_HIP_UNIT_LPT", K.unit_lpt);
+    env_flag("EMSAR_HIP_TILE_CUT", K.cut_at_slices);
+    if (const char *e = getenv("EMSAR_HIP_FRAG_ROWS")) { const long long v = atoll(e); if (v >= kTileRows) K.frag_rows = v; }   // the one 64-bit knob
+    env_int("EMSAR_HIP_TAIL_SPLIT", 0, 100, K.tail_pct);
+    K.debug = getenv("EMSAR_HIP_DEBUG") != nullptr;
+    K.base_rows = K.tile_rows * K.unit_tiles;
+    K.unit_rows = K.tile_rows * K.unit_tiles_max;
+    return K;
+}
 
-    // ---- tiles ----
-    // The sorted rows are cut into fragments of kFragRows rows; every fragment is tiled on its own (into a private
-    // TiledLayout) and the fragments are concatenated.  The cut points depend on the data only, so the layout is the same
-    // whatever the number of host threads that happen to build it.
-    auto form_tiles = [&](int64_t range_begin, int64_t range_end, TiledLayout &out) -> int {
-    std::vector<int32_t> stamp((size_t)n_tx, -1), loc((size_t)n_tx, 0);
-        std::vector<int32_t> distinct;
-        std::vector<uint32_t> pairs, sorted;   // (col_local << 16) | row_in_slice
-        std::vector<uint32_t> ccount, fill;
-        std::vector<uint32_t> segs;            // 4 dwords per segment
-        std::vector<uint32_t> uord;            // the unit's rows in the order they are laid out
-        std::vector<uint32_t> rslots, rents, rent, rent_ptr;   // one row's slots / entries; all rows' entries of the tile
-        int64_t i0 = range_begin;
-        int32_t tile_id = 0;
-        const int64_t n_act = range_end;      // rows beyond the range belong to another fragment
-        while (i0 < n_act) {
-            // 1. how many rows fit: row cap, entry cap, distinct-tid cap
-            distinct.clear();
-            int64_t ents = 0, i1 = i0;
-            while (i1 < n_act && i1 - i0 < unit_rows) {
-                uint32_t r = perm[(size_t)i1];
-                uint64_t b = row_ptr[r], e = row_ptr[r + 1];
-                if (i1 > i0 && ents + (int64_t)(e - b) > (int64_t)unit_tiles_max * kTileEntries) break;
-                size_t before = distinct.size();
-                for (uint64_t k = b; k < e; k++) {
-                    int32_t t = tid_at(k);
-                    if (stamp[(size_t)t] != tile_id) { stamp[(size_t)t] = tile_id; distinct.push_back(t); }
-                }
-                if (i1 > i0 && (int64_t)distinct.size() > kTileDistinct) {   // undo this row, close the tile
-                    for (size_t q = before; q < distinct.size(); q++) stamp[(size_t)distinct[q]] = -1;
-                    distinct.resize(before);
-                    break;
-                }
-                ents += (int64_t)(e - b);
-                i1++;
+// Host threads of the builder.  Every parallel step gives the result of the sequential one, so the layout does not depend on
+// these counts.  The chunked stages (classification, counting sorts) take up to 16 threads with at least 65536 rows each; the
+// fragment pool takes up to 16.  EMSAR_HOST_THREADS (tests: threads on small inputs) sets both, with chunks of 16 rows.
+struct HostThreads {
+    int chunked = 1, pool = 1;
+    int64_t min_chunk = (int64_t)1 << 16;
+    int for_rows(int64_t n) const { return (int)std::min<int64_t>(chunked, std::max<int64_t>(1, n / min_chunk)); }
+    int for_fragments(int64_t n_frag) const { return (int)std::min<int64_t>(n_frag, pool); }
+};
+inline HostThreads host_threads(int64_t n_rows) {
+    HostThreads H;
+    const unsigned hw = std::thread::hardware_concurrency();
+    H.pool = (int)(hw ? std::min(hw, 16u) : 1u);
+    H.chunked = n_rows < H.min_chunk ? 1 : H.pool;
+    int v = 0;
+    env_int("EMSAR_HOST_THREADS", 1, INT32_MAX, v);
+    if (v >= 1) { H.chunked = std::min(v, 64); H.min_chunk = 16; H.pool = v; }
+    return H;
+}
+// fn(t, lo, hi) over [0, n) cut into one contiguous range per thread; returns the number of ranges
+template <class F>
+inline int par_ranges(const HostThreads &H, int64_t n, F fn) {
+    const int nt = H.for_rows(n);
+    run_on_threads(nt, [&](int t) { fn(t, n * t / nt, n * (t + 1) / nt); });
+    return nt;
+}
+
+// the matrix as the builder reads it: the caller's CSR seen through the library's numbering, or the merged rows (numbered already)
+struct RowView {
+    const uint64_t *row_ptr;
+    const int32_t *col_idx;
+    const int32_t *tid_map;                // the id under which the caller's transcript is stored; nullptr = as given
+    int32_t tid_at(uint64_t k) const { return tid_map ? tid_map[col_idx[k]] : col_idx[k]; }
+    uint64_t len(int64_t r) const { return row_ptr[r + 1] - row_ptr[r]; }
+};
+
+// With merge_rows, rows with the same tid multiset (2..kMaxRowLen tids) are stored once and weighted by the sum of
+// their members' weights -- what the reference's update_ReadCounts does when it counts reads per segment
+// (emsar_functions.c:838-943).  Every quantity the library computes is a sum over rows of a function of the row's tid
+// set times a per-row weight, so the merge is exact up to summation order.
+struct MergedRows {
+    std::vector<uint64_t> ptr;             // unique rows with sorted tids, in the library's numbering
+    std::vector<int32_t> col;
+    std::vector<uint32_t> orig;            // first member, for rows that are not merged (singles, long rows)
+};
+inline void merge_identical_rows(int64_t n_rows, const RowView &V, MergedRows &M, TiledLayout &out) {
+    const int64_t nnz_in = (int64_t)V.row_ptr[n_rows];
+    std::vector<int32_t> scol((size_t)nnz_in);
+    std::vector<uint64_t> hash((size_t)n_rows, 0);
+    for (int64_t r = 0; r < n_rows; r++) {
+        uint64_t b = V.row_ptr[r], e = V.row_ptr[r + 1];
+        for (uint64_t k = b; k < e; k++) scol[(size_t)k] = V.tid_at(k);
+        std::sort(scol.begin() + (int64_t)b, scol.begin() + (int64_t)e);
+        uint64_t h = 1469598103934665603ull ^ (e - b);
+        for (uint64_t k = b; k < e; k++) { h ^= (uint64_t)(uint32_t)scol[(size_t)k]; h *= 1099511628211ull; }
+        hash[(size_t)r] = h;
+    }
+    uint64_t cap = 16;
+    while (cap < (uint64_t)n_rows * 2 + 2) cap <<= 1;
+    std::vector<int64_t> table((size_t)cap, -1);       // -> merged id
+    std::vector<int64_t> merged_of((size_t)n_rows, -1);
+    std::vector<uint32_t> cnt;                          // members per merged row
+    M.ptr.push_back(0);
+    for (int64_t r = 0; r < n_rows; r++) {
+        uint64_t b = V.row_ptr[r], e = V.row_ptr[r + 1], len = e - b;
+        bool mergeable = len >= 2 && len <= (uint64_t)kMaxRowLen;
+        int64_t id = -1;
+        if (mergeable) {
+            uint64_t h = hash[(size_t)r] & (cap - 1);
+            while (table[(size_t)h] >= 0) {
+                int64_t o = table[(size_t)h];
+                uint64_t ob = M.ptr[(size_t)o], oe = M.ptr[(size_t)o + 1];
+                if (oe - ob == len && std::memcmp(M.col.data() + ob, scol.data() + b, len * 4) == 0) { id = o; break; }
+                h = (h + 1) & (cap - 1);
             }
-            if ((int64_t)distinct.size() > kTileDistinct) return -3;   // a single row with too many tids: excluded by kMaxRowLen
-            // a tile closed by the dictionary or entry cap in the middle of a slice would pad that slice with empty rows
-            // (forward bytes and gathers for nothing): give the rows of the started slice to the next tile instead
-            if (cut_at_slices && i1 < n_act && i1 - i0 > kTileSliceRows && (i1 - i0) % kTileSliceRows != 0) {
-                const int64_t keep = (i1 - i0) / kTileSliceRows * kTileSliceRows;
-                for (int32_t t : distinct) stamp[(size_t)t] = -1;
-                distinct.clear();
-                i1 = i0 + keep;
-                for (int64_t i = i0; i < i1; i++) {
-                    uint32_t r = perm[(size_t)i];
-                    for (uint64_t k = row_ptr[r]; k < row_ptr[r + 1]; k++) {
-                        int32_t t = tid_at(k);
-                        if (stamp[(size_t)t] != tile_id) { stamp[(size_t)t] = tile_id; distinct.push_back(t); }
-                    }
-                }
+            if (id < 0) table[(size_t)h] = (int64_t)cnt.size();
+        }
+        if (id < 0) {
+            id = (int64_t)cnt.size();
+            M.col.insert(M.col.end(), scol.begin() + (int64_t)b, scol.begin() + (int64_t)e);
+            M.ptr.push_back((uint64_t)M.col.size());
+            cnt.push_back(0);
+            M.orig.push_back((uint32_t)r);
+        }
+        merged_of[(size_t)r] = id;
+        cnt[(size_t)id]++;
+    }
+    const int64_t n_m = (int64_t)cnt.size();
+    out.mem_ptr.assign((size_t)n_m + 1, 0);
+    for (int64_t i = 0; i < n_m; i++) out.mem_ptr[(size_t)i + 1] = out.mem_ptr[(size_t)i] + cnt[(size_t)i];
+    out.mem_row.resize((size_t)n_rows);
+    std::vector<uint64_t> fillp(out.mem_ptr.begin(), out.mem_ptr.end() - 1);
+    for (int64_t r = 0; r < n_rows; r++) out.mem_row[(size_t)fillp[(size_t)merged_of[(size_t)r]]++] = (uint32_t)r;
+    out.merged = true;
+}
+
+// What the sort and the tiler know of the rows: the tiled ones, and per row its anchor and its number of block entries.
+struct RowKeys {
+    std::vector<int32_t> anchor;           // the anchor tid of every tiled row (TiledKnobs::anchor_median), -1 otherwise
+    std::vector<uint16_t> ecnt;            // its number of block entries (dictionaries start at multiples of kBlk, so
+                                           // a near tid t lies in block t / kBlk whatever the tile): the sort's length
+    std::vector<uint32_t> act;             // the tiled rows, ascending
+};
+// Rows with one tid go to out.single_*, rows too long for a dictionary to out.left_*, the others get their keys.
+// `orig` (merged input only) names the caller's row of a view row: singles and long rows are never merged.
+inline void classify_rows(int64_t n_rows, const RowView &V, const std::vector<uint32_t> *orig, const TiledKnobs &K, const HostThreads &H,
+                          TiledLayout &out, RowKeys &keys) {
+    keys.anchor.assign((size_t)n_rows, -1);
+    keys.ecnt.assign((size_t)n_rows, 0);
+    par_ranges(H, n_rows, [&](int, int64_t lo, int64_t hi) {
+        std::vector<int32_t> tmp;
+        for (int64_t r = lo; r < hi; r++) {
+            const uint64_t b = V.row_ptr[r], len = V.len(r);
+            if (len < 2 || len > (uint64_t)kMaxRowLen) continue;
+            tmp.resize((size_t)len);
+            for (uint64_t k = 0; k < len; k++) tmp[(size_t)k] = V.tid_at(b + k);
+            std::sort(tmp.begin(), tmp.end());
+            keys.anchor[(size_t)r] = K.anchor_median ? tmp[(size_t)(len / 2)] : tmp[0];
+            EntryRun run;
+            int n_ent = 0;
+            for (int32_t t : tmp) n_ent += run.opens(t / kBlk, 1u << (t % kBlk));
+            keys.ecnt[(size_t)r] = (uint16_t)n_ent;
+        }
+    });
+    // every thread classifies a contiguous range of rows into lists of its own; the lists are joined in range order
+    struct Part { std::vector<uint32_t> single_row, left_row, act; std::vector<int32_t> single_tid, left_col; std::vector<uint64_t> left_len; };
+    std::vector<Part> part((size_t)std::max(1, H.chunked));
+    const int np = par_ranges(H, n_rows, [&](int t, int64_t lo, int64_t hi) {
+        Part &P = part[(size_t)t];
+        for (int64_t r = lo; r < hi; r++) {
+            const uint64_t b = V.row_ptr[r], e = V.row_ptr[r + 1], len = e - b;
+            if (len == 0) continue;
+            const uint32_t r_orig = orig ? (*orig)[(size_t)r] : (uint32_t)r;
+            if (len == 1) { P.single_row.push_back(r_orig); P.single_tid.push_back(V.tid_at(b)); continue; }
+            if (len > (uint64_t)kMaxRowLen) {
+                P.left_row.push_back(r_orig);
+                for (uint64_t k = b; k < e; k++) P.left_col.push_back(V.tid_at(k));
+                P.left_len.push_back(len);
+                continue;
             }
-            // 2. dictionary: the contiguous tid range [distinct[a], distinct[c]] that covers the MOST of the tile's tids while the
-            //    near blocks (8 table entries per 3 slots of the range, tids present or not) plus one entry per tid outside the range
-            //    (cross-family hits on either side: the far list) still fit the table.  The cost falls as a grows and rises as c grows,
-            //    so the smallest feasible a for every c gives the widest cover.  If not even the best window fits, the unit gives
-            //    back its last slice of rows and tries again.
-            size_t best_a = 0, best_c = 0;
-            for (;;) {
-                std::sort(distinct.begin(), distinct.end());
-                const size_t n = distinct.size();
-                size_t a = 0;
-                bool any = false;
-                for (size_t c = 0; c < n; c++) {
-                    auto fits = [&](size_t aa) {
-                        const int64_t lo_a = distinct[aa] - distinct[aa] % kBlk;
-                        return dict_fits((int64_t)distinct[c] - lo_a + 1, (int64_t)n - (int64_t)(c - aa + 1));
-                    };
-                    while (a < c && !fits(a)) a++;
-                    if (!fits(a)) continue;
-                    if (!any || c - a > best_c - best_a) { best_a = a; best_c = c; any = true; }
-                }
-                // a unit larger than the base size keeps its extra rows only if they did not flood the dictionary with far entries
-                const bool too_far = any && i1 - i0 > base_rows && (int64_t)n - (int64_t)(best_c - best_a + 1) > (int64_t)far_soft;
-                if (any && !too_far) break;
-                if (i1 - i0 <= 1) return -3;
-                const int64_t keep = too_far ? base_rows : i1 - i0 > kTileSliceRows ? (i1 - i0 - 1) / kTileSliceRows * kTileSliceRows : (i1 - i0) / 2;
-                for (int32_t t : distinct) stamp[(size_t)t] = -1;
-                distinct.clear();
-                i1 = i0 + std::max<int64_t>(keep, 1);
-                for (int64_t i = i0; i < i1; i++) {
-                    uint32_t r = perm[(size_t)i];
-                    for (uint64_t k = row_ptr[r]; k < row_ptr[r + 1]; k++) {
-                        int32_t t = tid_at(k);
-                        if (stamp[(size_t)t] != tile_id) { stamp[(size_t)t] = tile_id; distinct.push_back(t); }
-                    }
-                }
+            P.act.push_back((uint32_t)r);
+        }
+    });
+    size_t ns = 0, nl = 0, nlc = 0, na = 0;
+    for (int t = 0; t < np; t++) { ns += part[(size_t)t].single_row.size(); nl += part[(size_t)t].left_row.size(); nlc += part[(size_t)t].left_col.size(); na += part[(size_t)t].act.size(); }
+    out.single_row.reserve(ns); out.single_tid.reserve(ns); out.left_row.reserve(nl); out.left_col.reserve(nlc); out.left_ptr.reserve(nl + 1); keys.act.reserve(na);
+    out.left_ptr.push_back(0);
+    for (int t = 0; t < np; t++) {
+        Part &P = part[(size_t)t];
+        out.single_row.insert(out.single_row.end(), P.single_row.begin(), P.single_row.end());
+        out.single_tid.insert(out.single_tid.end(), P.single_tid.begin(), P.single_tid.end());
+        out.left_row.insert(out.left_row.end(), P.left_row.begin(), P.left_row.end());
+        out.left_col.insert(out.left_col.end(), P.left_col.begin(), P.left_col.end());
+        for (uint64_t len : P.left_len) out.left_ptr.push_back(out.left_ptr.back() + len);
+        keys.act.insert(keys.act.end(), P.act.begin(), P.act.end());
+        P = Part();
+    }
+}
+
+// A stable counting sort over chunks of the input: one histogram per chunk, offsets ordered (key, chunk), then every
+// chunk scatters its own rows in order -- the permutation of the sequential sort.
+template <class Key>
+inline void counting_sort(const HostThreads &H, const std::vector<uint32_t> &in, std::vector<uint32_t> &dst, size_t n_keys, Key key) {
+    const int64_t n = (int64_t)in.size();
+    dst.resize((size_t)n);
+    const int nc = H.for_rows(n);
+    std::vector<std::vector<uint64_t>> hist((size_t)nc);
+    auto chunk = [&](int c) { return std::make_pair(n * c / nc, n * (c + 1) / nc); };
+    run_on_threads(nc, [&](int c) {
+        hist[(size_t)c].assign(n_keys, 0);
+        auto [lo, hi] = chunk(c);
+        for (int64_t i = lo; i < hi; i++) hist[(size_t)c][key(in[(size_t)i])]++;
+    });
+    uint64_t run = 0;
+    for (size_t k = 0; k < n_keys; k++)
+        for (int c = 0; c < nc; c++) { const uint64_t h = hist[(size_t)c][k]; hist[(size_t)c][k] = run; run += h; }
+    run_on_threads(nc, [&](int c) {
+        auto [lo, hi] = chunk(c);
+        uint64_t *off = hist[(size_t)c].data();
+        for (int64_t i = lo; i < hi; i++) { const uint32_t r = in[(size_t)i]; dst[(size_t)off[key(r)]++] = r; }
+    });
+}
+// The tiled rows by (block(anchor), class of the entry count, anchor): pass A by anchor tid, pass B by (block, length class); both
+// stable.  Consumes keys.act.
+inline void sort_rows(int32_t n_tx, const TiledKnobs &K, const HostThreads &H, RowKeys &keys, std::vector<uint32_t> &perm) {
+    std::vector<uint32_t> pa;
+    counting_sort(H, keys.act, pa, (size_t)n_tx, [&](uint32_t r) { return (size_t)keys.anchor[r]; });
+    std::vector<uint32_t>().swap(keys.act);
+    const int64_t n_blocks = ((int64_t)n_tx + K.block - 1) / K.block;
+    // Rows of few entries touch few transcripts: they are sorted in WIDER blocks (their (block, count) buckets then hold several
+    // slices of equal rows -- no padding -- and a unit of them still spans a narrow range of anchors); they come after the others.
+    counting_sort(H, pa, perm, (size_t)(2 * n_blocks * kLenClasses), [&](uint32_t r) {
+        const int e = (int)keys.ecnt[r];
+        if (e <= K.short_ecnt) return (size_t)(n_blocks + keys.anchor[r] / K.short_block) * kLenClasses + (size_t)len_class((int64_t)e);
+        return (size_t)(keys.anchor[r] / K.block) * kLenClasses + (size_t)len_class((int64_t)e);
+    });
+}
+
+// Tiles one fragment of the sorted rows, perm[begin, end), into a private TiledLayout.  One unit at a time: gather rows (1), choose
+// the dictionary window (2), compute every row's entries, deal the slices to the waves, emit each tile's forward (3) and backward (4)
+// slices.  The scratch vectors live as long as the tiler, so a unit allocates nothing once they have grown.
+struct FragmentTiler {
+    const RowView &V;
+    const TiledKnobs &K;
+    const std::vector<uint32_t> &perm;
+    const std::vector<uint16_t> &ecnt;
+    TiledLayout out;
+    std::vector<int32_t> stamp, loc;       // per tid: the unit that has it in `distinct`; its dictionary slot
+    std::vector<int32_t> distinct;         // the distinct tids of the unit's rows
+    std::vector<uint32_t> pairs, sorted;   // (entry << 16) | row_in_slice
+    std::vector<uint32_t> ccount, fill;
+    std::vector<uint32_t> segs;            // 4 dwords per segment
+    std::vector<uint32_t> uord;            // the unit's rows in the order they are laid out
+    std::vector<uint32_t> rslots, rents, rent, rent_ptr;   // one row's slots / entries; all rows' entries of the unit
+    int32_t tile_id = 0;
+    int64_t i0 = 0, i1 = 0, end = 0;       // the unit is perm[i0, i1); rows from `end` on belong to another fragment
+    struct Extent { int64_t a0, bnd, k; }; // a slice: positions [a0, bnd) of uord, its widest row
+    std::vector<Extent> extents;
+    static constexpr uint32_t pad_row = (uint32_t)kTileSliceRows;          // w_r[768] of every slice = 0
+
+    FragmentTiler(const RowView &v, const TiledKnobs &k, const std::vector<uint32_t> &p, const std::vector<uint16_t> &e, int32_t n_tx)
+        : V(v), K(k), perm(p), ecnt(e), stamp((size_t)n_tx, -1), loc((size_t)n_tx, 0) {}
+
+    // add the tids of rows perm[a, b) that the unit does not have yet to `distinct`
+    void stamp_rows(int64_t a, int64_t b) {
+        for (int64_t i = a; i < b; i++) {
+            const uint32_t r = perm[(size_t)i];
+            for (uint64_t k = V.row_ptr[r]; k < V.row_ptr[r + 1]; k++) {
+                const int32_t t = V.tid_at(k);
+                if (stamp[(size_t)t] != tile_id) { stamp[(size_t)t] = tile_id; distinct.push_back(t); }
             }
-            const int32_t lo = distinct[best_a] - distinct[best_a] % kBlk;       // blocks of the near range = tid / kBlk (see ecnt)
-            const int32_t near_n = distinct[best_c] - lo + 1;
-            Tile T;
-            std::memset(&T, 0, sizeof T);
-            T.lo = lo; T.near_n = (uint16_t)near_n;
-            T.far_off = (uint32_t)out.far_tid.size();
-            for (size_t q = 0; q < distinct.size(); q++) {
-                int32_t t = distinct[q];
-                if (t >= lo && t - lo < near_n) loc[(size_t)t] = t - lo;
-                else { loc[(size_t)t] = near_n + (int32_t)(out.far_tid.size() - T.far_off); out.far_tid.push_back(t); }
+        }
+    }
+    void unstamp() {
+        for (int32_t t : distinct) stamp[(size_t)t] = -1;
+        distinct.clear();
+    }
+    // the unit keeps its first `keep` rows only
+    void restamp(int64_t keep) {
+        unstamp();
+        i1 = i0 + keep;
+        stamp_rows(i0, i1);
+    }
+
+    // 1. how many rows fit: row cap, entry cap, distinct-tid cap
+    int gather_rows() {
+        distinct.clear();
+        int64_t ents = 0;
+        i1 = i0;
+        while (i1 < end && i1 - i0 < K.unit_rows) {
+            const int64_t len = (int64_t)V.len(perm[(size_t)i1]);
+            if (i1 > i0 && ents + len > (int64_t)K.unit_tiles_max * kTileEntries) break;
+            const size_t before = distinct.size();
+            stamp_rows(i1, i1 + 1);
+            if (i1 > i0 && (int64_t)distinct.size() > kTileDistinct) {   // undo this row, close the unit
+                for (size_t q = before; q < distinct.size(); q++) stamp[(size_t)distinct[q]] = -1;
+                distinct.resize(before);
+                break;
             }
-            const int32_t far_n = (int32_t)(out.far_tid.size() - T.far_off);     // (rounding lo down may have taken in a tid or two)
-            T.far_n = (uint16_t)far_n;
-            const int nd = near_n + far_n;
-            const uint32_t pad_row = (uint32_t)kTileSliceRows;             // w_r[768] of every slice = 0
-            const Tile Tdict = T;                                          // what the tiles of the unit share: the dictionary
-            // The rows of the unit in descending order of their entry count (stable: rows of one count keep the order of the
-            // sort above).  A slice's forward width is its longest row, so slices of equal rows carry the least padding, and
-            // the slices come out in descending order of work -- what the unit kernel's wave assignment expects.
-            uord.assign(perm.begin() + i0, perm.begin() + i1);
-            if (unit_sort) std::stable_sort(uord.begin(), uord.end(), [&](uint32_t a, uint32_t b) { return ecnt[a] > ecnt[b]; });
-            // the entries of every row of the tile, once (used by the forward and by the backward index)
-            rent_ptr.assign(1, 0u); rent.clear();
-            for (int64_t i = i0; i < i1; i++) {
-                const uint32_t r = uord[(size_t)(i - i0)];
-                rslots.clear();
-                for (uint64_t q = row_ptr[r]; q < row_ptr[r + 1]; q++) {
-                    const int32_t d = loc[(size_t)tid_at(q)];
-                    rslots.push_back((uint32_t)d);
-                    if (d >= near_n) out.far_entries++;
-                }
-                slots_to_entries(rslots, rents, (uint32_t)near_n);
-                rent.insert(rent.end(), rents.begin(), rents.end());
-                rent_ptr.push_back((uint32_t)rent.size());
-                out.tiled_entries += (int64_t)rents.size();
-                out.tiled_ids += (int64_t)rslots.size();
+            ents += len;
+            i1++;
+        }
+        if ((int64_t)distinct.size() > kTileDistinct) return -3;   // a single row with too many tids: excluded by kMaxRowLen
+        // a unit closed by the dictionary or entry cap in the middle of a slice would pad that slice with empty rows
+        // (forward bytes and gathers for nothing): give the rows of the started slice to the next unit instead
+        if (K.cut_at_slices && i1 < end && i1 - i0 > kTileSliceRows && (i1 - i0) % kTileSliceRows != 0)
+            restamp((i1 - i0) / kTileSliceRows * kTileSliceRows);
+        return 0;
+    }
+
+    // 2. dictionary: the contiguous tid range [distinct[a], distinct[c]] that covers the MOST of the unit's tids while the
+    //    near blocks (8 table entries per 3 slots of the range, tids present or not) plus one entry per tid outside the range
+    //    (cross-family hits on either side: the far list) still fit the table.  The cost falls as a grows and rises as c grows,
+    //    so the smallest feasible a for every c gives the widest cover.  If not even the best window fits, the unit gives
+    //    back its last slice of rows and tries again.
+    int choose_window(int32_t &lo, int32_t &near_n) {
+        size_t best_a = 0, best_c = 0;
+        for (;;) {
+            std::sort(distinct.begin(), distinct.end());
+            const size_t n = distinct.size();
+            size_t a = 0;
+            bool any = false;
+            for (size_t c = 0; c < n; c++) {
+                auto fits = [&](size_t aa) {
+                    const int64_t lo_a = distinct[aa] - distinct[aa] % kBlk;
+                    return dict_fits((int64_t)distinct[c] - lo_a + 1, (int64_t)n - (int64_t)(c - aa + 1));
+                };
+                while (a < c && !fits(a)) a++;
+                if (!fits(a)) continue;
+                if (!any || c - a > best_c - best_a) { best_a = a; best_c = c; any = true; }
             }
-            // The rows of the unit (longest first) are cut into slices of 768; the slices are dealt to the four waves of the workgroup,
-            // heaviest first, each to the wave with the least work so far (work = forward columns + entries: the first slice of a unit
-            // holds its long-row tail -- 18 columns on config 3 where the others have 2-7 -- and used to share a wave with the last one).
-            // Tile t of the unit holds the t-th slice of every wave that has one; Tile::follows says which wave takes which slice.
-            const int64_t n_chunks_u = (i1 - i0 + kTileSliceRows - 1) / kTileSliceRows;
+            // a unit larger than the base size keeps its extra rows only if they did not flood the dictionary with far entries
+            const bool too_far = any && i1 - i0 > K.base_rows && (int64_t)n - (int64_t)(best_c - best_a + 1) > (int64_t)K.far_soft;
+            if (any && !too_far) break;
+            if (i1 - i0 <= 1) return -3;
+            const int64_t keep = too_far ? K.base_rows : i1 - i0 > kTileSliceRows ? (i1 - i0 - 1) / kTileSliceRows * kTileSliceRows : (i1 - i0) / 2;
+            restamp(std::max<int64_t>(keep, 1));
+        }
+        lo = distinct[best_a] - distinct[best_a] % kBlk;       // blocks of the near range = tid / kBlk (see RowKeys::ecnt)
+        near_n = distinct[best_c] - lo + 1;
+        return 0;
+    }
+
+    // the dictionary slot of every tid of the unit (loc), its far list, and the part of the descriptor that the unit's tiles share
+    Tile lay_dictionary(int32_t lo, int32_t near_n) {
+        Tile T;
+        std::memset(&T, 0, sizeof T);
+        T.lo = lo; T.near_n = (uint16_t)near_n;
+        T.far_off = (uint32_t)out.far_tid.size();
+        for (int32_t t : distinct) {
+            if (t >= lo && t - lo < near_n) loc[(size_t)t] = t - lo;
+            else { loc[(size_t)t] = near_n + (int32_t)(out.far_tid.size() - T.far_off); out.far_tid.push_back(t); }
+        }
+        T.far_n = (uint16_t)(out.far_tid.size() - T.far_off);     // (rounding lo down may have taken in a tid or two)
+        return T;
+    }
+
+    // The rows of the unit in descending order of their entry count (stable: rows of one count keep the order of the
+    // sort).  A slice's forward width is its longest row, so slices of equal rows carry the least padding, and
+    // the slices come out in descending order of work -- what the unit kernel's wave assignment expects.
+    // Then the entries of every row of the unit, once (used by the forward and by the backward index).
+    void row_entries(int32_t near_n) {
+        uord.assign(perm.begin() + i0, perm.begin() + i1);
+        if (K.unit_sort) std::stable_sort(uord.begin(), uord.end(), [&](uint32_t a, uint32_t b) { return ecnt[a] > ecnt[b]; });
+        rent_ptr.assign(1, 0u); rent.clear();
+        for (const uint32_t r : uord) {
+            rslots.clear();
+            for (uint64_t q = V.row_ptr[r]; q < V.row_ptr[r + 1]; q++) {
+                const int32_t d = loc[(size_t)V.tid_at(q)];
+                rslots.push_back((uint32_t)d);
+                if (d >= near_n) out.far_entries++;
+            }
+            slots_to_entries(rslots, rents, (uint32_t)near_n);
+            rent.insert(rent.end(), rents.begin(), rents.end());
+            rent_ptr.push_back((uint32_t)rent.size());
+            out.tiled_entries += (int64_t)rents.size();
+            out.tiled_ids += (int64_t)rslots.size();
+        }
+    }
+
+    // bounds and widest row of slice `chunk` of the unit's rows
+    Extent slice_extent(int64_t chunk) const {
+        const int64_t a0 = chunk * kTileSliceRows, bnd = std::min(i1 - i0, a0 + kTileSliceRows);
+        int64_t k = 0;
+        for (int64_t p = a0; p < bnd; p++) k = std::max<int64_t>(k, (int64_t)(rent_ptr[(size_t)p + 1] - rent_ptr[(size_t)p]));
+        return Extent{a0, bnd, k};
+    }
+
+    // The rows of the unit (longest first) are cut into slices of 768; the slices are dealt to the four waves of the workgroup,
+    // heaviest first, each to the wave with the least work so far (work = forward columns + entries: the first slice of a unit
+    // holds its long-row tail -- 18 columns on config 3 where the others have 2-7 -- and used to share a wave with the last one).
+    // Tile t of the unit holds the t-th slice of every wave that has one; Tile::wave_of says which wave takes which slice.
+    void deal_slices(std::vector<int> (&wave_slices)[kTileSlices]) {
+        const int64_t n_chunks = (i1 - i0 + kTileSliceRows - 1) / kTileSliceRows;
+        extents.resize((size_t)n_chunks);
+        for (int64_t c = 0; c < n_chunks; c++) extents[(size_t)c] = slice_extent(c);
+        if (K.unit_lpt) {
+            std::vector<std::pair<int64_t, int>> cost((size_t)n_chunks);
+            for (int64_t c = 0; c < n_chunks; c++) {
+                const Extent &E = extents[(size_t)c];
+                cost[(size_t)c] = {E.k * kTileSliceRows + (int64_t)(rent_ptr[(size_t)E.bnd] - rent_ptr[(size_t)E.a0]), (int)c};
+            }
+            std::stable_sort(cost.begin(), cost.end(), [](const std::pair<int64_t, int> &a, const std::pair<int64_t, int> &b) { return a.first > b.first; });
+            int64_t load[kTileSlices] = {0, 0, 0, 0};
+            for (const auto &cc : cost) {
+                int w = -1;
+                for (int q = 0; q < kTileSlices; q++)
+                    if ((int)wave_slices[q].size() < kUnitMaxTiles && (w < 0 || load[q] < load[w])) w = q;
+                wave_slices[w].push_back(cc.second); load[w] += cc.first;
+            }
+        } else {                                      // in order, alternate tiles mirrored (the scheme before)
+            for (int64_t c = 0; c < n_chunks; c++) {
+                const int64_t per = K.tile_rows / kTileSliceRows, t = c / per, s = c % per;
+                wave_slices[(t & 1) ? (int)(kTileSlices - 1 - s) : (int)s].push_back((int)c);
+            }
+        }
+    }
+
+    // 3. forward slice s of tile T.  Column j of a slice is 256 dwords; row p of the slice (p = position in sorted order) is
+    //    field p/64 of the int4 of lane p%64: the 64 lanes of one E-step gather read 64 CONSECUTIVE sorted rows, i.e. mostly
+    //    one family -- the same few table entries (LDS broadcast) or neighbouring ones (distinct banks) instead of a random spread
+    void emit_forward_slice(Tile &T, int s, const Extent &E) {
+        T.k[s] = (uint16_t)E.k;
+        const size_t base = out.fwd.size();
+        out.fwd.resize(base + (size_t)E.k * kSliceDwords, 0u);            // entry 0 = the empty subset: padding
+        out.padded_slots += E.k * kTileSliceRows;
+        for (int64_t p = E.a0; p < E.bnd; p++) {
+            const uint32_t in_slice = (uint32_t)(p - E.a0);
+            out.slot_row[(size_t)T.row_base + (size_t)s * kTileSliceRows + in_slice] = (int64_t)uord[(size_t)p];
+            const uint32_t b = rent_ptr[(size_t)p], e = rent_ptr[(size_t)p + 1];
+            for (uint32_t q = b; q < e; q++) {
+                const uint32_t d = rent[q];
+                const uint32_t fl = in_slice & 63u, fi = in_slice >> 6;      // lane, field: see slot numbering above
+                uint32_t *dw = &out.fwd[base + (size_t)(q - b) * kSliceDwords + fl * 4 + fi / 3];
+                const int sh = 10 * (int)(fi % 3);
+                *dw = (*dw & ~(0x3FFu << sh)) | (d << sh);
+            }
+        }
+    }
+
+    // 4. backward index of slice s: its (entry value, row) pairs sorted by entry value, cut into segments
+    void emit_backward_slice(Tile &T, int s, const Extent &E) {
+        pairs.clear();
+        for (int64_t p = E.a0; p < E.bnd; p++) {
+            const uint32_t in_slice = (uint32_t)(p - E.a0);
+            for (uint32_t q = rent_ptr[(size_t)p]; q < rent_ptr[(size_t)p + 1]; q++) pairs.push_back((rent[q] << 16) | in_slice);
+        }
+        ccount.assign((size_t)kDictEntries + 1, 0);
+        for (uint32_t p : pairs) ccount[(p >> 16) + 1]++;
+        for (int d = 0; d < kDictEntries; d++) ccount[(size_t)d + 1] += ccount[(size_t)d];
+        sorted.resize(pairs.size());
+        fill.assign(ccount.begin(), ccount.end() - 1);
+        for (uint32_t p : pairs) sorted[fill[p >> 16]++] = p;
+        segs.clear();
+        const size_t coo_before = out.coo.size();
+        for (int d = 0; d < kDictEntries; d++) {
+            const uint32_t b = ccount[(size_t)d], e = ccount[(size_t)d + 1];
+            if (e - b < (uint32_t)K.dense_min) {
+                for (uint32_t q = b; q < e; q++) out.coo.push_back(((uint32_t)d << 16) | (sorted[q] & 0xFFFF));
+                continue;
+            }
+            for (uint32_t q = b; q < e; q += kSegRows) {
+                uint32_t seg[4] = {0, 0, 0, 0};
+                pack10(seg, 0, (uint32_t)d);
+                for (uint32_t j = 0; j < (uint32_t)kSegRows; j++) pack10(seg, 1 + (int)j, q + j < e ? (sorted[q + j] & 0xFFFF) : pad_row);
+                segs.insert(segs.end(), seg, seg + 4);
+            }
+        }
+        T.coo_n[s] = (uint16_t)(out.coo.size() - coo_before);
+        out.coo_entries += T.coo_n[s];
+        const int64_t nseg = (int64_t)segs.size() / 4;
+        const int m = (int)((nseg + 63) / 64);
+        T.m[s] = (uint16_t)m;
+        const size_t base = out.bwd.size();
+        uint32_t empty[4] = {0, 0, 0, 0};                          // unused segment: entry 0 (never flushed), padding rows
+        for (int j = 1; j < 12; j++) pack10(empty, j, pad_row);
+        out.bwd.resize(base + (size_t)m * 64 * 4, 0u);
+        for (int64_t g = 0; g < (int64_t)m * 64; g++) {
+            // logical segment g -> lane g / m, unit g % m ; physical int4 index (unit*64 + lane)
+            const int64_t lane = g / m, unit = g % m;
+            const size_t u0 = base + (size_t)((unit * 64 + lane) * 4);
+            const uint32_t *src = g < nseg ? &segs[(size_t)g * 4] : empty;
+            for (int w = 0; w < 4; w++) out.bwd[u0 + (size_t)w] = src[w];
+        }
+    }
+
+    // tile `tu` of the unit: the tu-th slice of every wave that has one (all forward slices first: the tile's forward block is contiguous)
+    void emit_tile(const Tile &Tdict, size_t tu, const std::vector<int> (&wave_slices)[kTileSlices]) {
+        int chunk_of[kTileSlices]; unsigned wave_map = 0; int ns = 0;
+        for (int q = 0; q < kTileSlices; q++)
+            if (wave_slices[q].size() > tu) { chunk_of[ns] = wave_slices[q][tu]; wave_map |= (unsigned)q << (2 * ns); ns++; }
+        Tile T = Tdict;
+        T.follows = tu > 0 ? 1 : 0;
+        T.wave_of = (uint8_t)wave_map;
+        T.n_slices = (uint16_t)ns;
+        T.row_base = (uint32_t)out.slot_row.size();
+        out.slot_row.resize(out.slot_row.size() + (size_t)T.n_slices * kTileSliceRows, -1);
+        T.fwd_off = (uint64_t)out.fwd.size() * 4;
+        T.bwd_off = (uint64_t)out.bwd.size() * 4;
+        T.coo_off = (uint32_t)out.coo.size();
+        out.n_fslices += T.n_slices;
+        for (int s = 0; s < ns; s++) emit_forward_slice(T, s, extents[(size_t)chunk_of[s]]);
+        for (int s = 0; s < ns; s++) emit_backward_slice(T, s, extents[(size_t)chunk_of[s]]);
+        out.tiles.push_back(T);
+    }
+
+    int run(int64_t range_begin, int64_t range_end) {
+        i0 = range_begin; end = range_end;
+        while (i0 < end) {
+            int32_t lo = 0, near_n = 0;
+            if (const int rc = gather_rows()) return rc;
+            if (const int rc = choose_window(lo, near_n)) return rc;
+            const Tile Tdict = lay_dictionary(lo, near_n);
+            row_entries(near_n);
             std::vector<int> wave_slices[kTileSlices];
-            if (unit_lpt) {
-                std::vector<std::pair<int64_t, int>> cost((size_t)n_chunks_u);
-                for (int64_t c = 0; c < n_chunks_u; c++) {
-                    const int64_t a0 = i0 + c * kTileSliceRows, bnd = std::min(i1, a0 + kTileSliceRows);
-                    int64_t k = 0;
-                    for (int64_t i = a0; i < bnd; i++) k = std::max<int64_t>(k, (int64_t)(rent_ptr[(size_t)(i - i0) + 1] - rent_ptr[(size_t)(i - i0)]));
-                    cost[(size_t)c] = {k * kTileSliceRows + (int64_t)(rent_ptr[(size_t)(bnd - i0)] - rent_ptr[(size_t)(a0 - i0)]), (int)c};
-                }
-                std::stable_sort(cost.begin(), cost.end(), [](const std::pair<int64_t, int> &a, const std::pair<int64_t, int> &b) { return a.first > b.first; });
-                int64_t load[kTileSlices] = {0, 0, 0, 0};
-                for (const auto &cc : cost) {
-                    int w = -1;
-                    for (int q = 0; q < kTileSlices; q++)
-                        if ((int)wave_slices[q].size() < kUnitMaxTiles && (w < 0 || load[q] < load[w])) w = q;
-                    wave_slices[w].push_back(cc.second); load[w] += cc.first;
-                }
-            } else {                                      // in order, alternate tiles mirrored (the scheme before)
-                for (int64_t c = 0; c < n_chunks_u; c++) {
-                    const int64_t per = tile_rows / kTileSliceRows, t = c / per, s = c % per;
-                    wave_slices[(t & 1) ? (int)(kTileSlices - 1 - s) : (int)s].push_back((int)c);
-                }
-            }
+            deal_slices(wave_slices);
             size_t n_tiles_u = 0;
             for (int q = 0; q < kTileSlices; q++) n_tiles_u = std::max(n_tiles_u, wave_slices[q].size());
-            for (size_t tu = 0; tu < n_tiles_u; tu++) {
-            int chunk_of[kTileSlices]; unsigned wave_map = 0; int ns = 0;
-            for (int q = 0; q < kTileSlices; q++)
-                if (wave_slices[q].size() > tu) { chunk_of[ns] = wave_slices[q][tu]; wave_map |= (unsigned)q << (2 * ns); ns++; }
-            T = Tdict;
-            T.follows = tu > 0 ? 1 : 0;
-            T.wave_of = (uint8_t)wave_map;
-            T.n_slices = (uint16_t)ns;
-            T.row_base = (uint32_t)out.slot_row.size();
-            out.slot_row.resize(out.slot_row.size() + (size_t)T.n_slices * kTileSliceRows, -1);
-            T.fwd_off = (uint64_t)out.fwd.size() * 4;
-            T.bwd_off = (uint64_t)out.bwd.size() * 4;
-            T.coo_off = (uint32_t)out.coo.size();
-            out.n_fslices += T.n_slices;
-            // 3. forward slices (all of them first: the tile's forward block is contiguous).  Column j of a slice is 256
-            //    dwords; row p of the slice (p = position in sorted order) is field p/64 of the int4 of lane p%64: the 64
-            //    lanes of one E-step gather read 64 CONSECUTIVE sorted rows, i.e. mostly one family -- the same few
-            //    table entries (LDS broadcast) or neighbouring ones (distinct banks) instead of a random spread
-            for (int s = 0; s < T.n_slices; s++) {
-                int64_t a0 = i0 + (int64_t)chunk_of[s] * kTileSliceRows, bnd = std::min(i1, a0 + kTileSliceRows);
-                int64_t k = 0;
-                for (int64_t i = a0; i < bnd; i++) k = std::max<int64_t>(k, (int64_t)(rent_ptr[(size_t)(i - i0) + 1] - rent_ptr[(size_t)(i - i0)]));
-                T.k[s] = (uint16_t)k;
-                size_t base = out.fwd.size();
-                out.fwd.resize(base + (size_t)k * kSliceDwords, 0u);            // entry 0 = the empty subset: padding
-                out.padded_slots += k * kTileSliceRows;
-                for (int64_t i = a0; i < bnd; i++) {
-                    uint32_t r = uord[(size_t)(i - i0)];
-                    uint32_t in_slice = (uint32_t)(i - a0);
-                    out.slot_row[(size_t)T.row_base + (size_t)s * kTileSliceRows + in_slice] = (int64_t)r;
-                    const uint32_t b = rent_ptr[(size_t)(i - i0)], e = rent_ptr[(size_t)(i - i0) + 1];
-                    for (uint32_t q = b; q < e; q++) {
-                        const uint32_t d = rent[q];
-                        const uint32_t fl = in_slice & 63u, fi = in_slice >> 6;      // lane, field: see slot numbering above
-                        uint32_t *dw = &out.fwd[base + (size_t)(q - b) * kSliceDwords + fl * 4 + fi / 3];
-                        const int sh = 10 * (int)(fi % 3);
-                        *dw = (*dw & ~(0x3FFu << sh)) | (d << sh);
-                    }
-                }
-            }
-            // 4. backward index of each slice: its (entry value, row) pairs sorted by entry value
-            for (int s = 0; s < T.n_slices; s++) {
-                int64_t a0 = i0 + (int64_t)chunk_of[s] * kTileSliceRows, bnd = std::min(i1, a0 + kTileSliceRows);
-                pairs.clear();
-                for (int64_t i = a0; i < bnd; i++) {
-                    uint32_t in_slice = (uint32_t)(i - a0);
-                    for (uint32_t q = rent_ptr[(size_t)(i - i0)]; q < rent_ptr[(size_t)(i - i0) + 1]; q++) pairs.push_back((rent[q] << 16) | in_slice);
-                }
-                ccount.assign((size_t)kDictEntries + 1, 0);
-                for (uint32_t p : pairs) ccount[(p >> 16) + 1]++;
-                for (int d = 0; d < kDictEntries; d++) ccount[(size_t)d + 1] += ccount[(size_t)d];
-                sorted.resize(pairs.size());
-                fill.assign(ccount.begin(), ccount.end() - 1);
-                for (uint32_t p : pairs) sorted[fill[p >> 16]++] = p;
-                segs.clear();
-                size_t coo_before = out.coo.size();
-                for (int d = 0; d < kDictEntries; d++) {
-                    uint32_t b = ccount[(size_t)d], e = ccount[(size_t)d + 1];
-                    if (e - b < (uint32_t)dense_min) {
-                        for (uint32_t q = b; q < e; q++) out.coo.push_back(((uint32_t)d << 16) | (sorted[q] & 0xFFFF));
-                        continue;
-                    }
-                    for (uint32_t q = b; q < e; q += kSegRows) {
-                        uint32_t seg[4] = {0, 0, 0, 0};
-                        pack10(seg, 0, (uint32_t)d);
-                        for (uint32_t j = 0; j < (uint32_t)kSegRows; j++) pack10(seg, 1 + (int)j, q + j < e ? (sorted[q + j] & 0xFFFF) : pad_row);
-                        segs.insert(segs.end(), seg, seg + 4);
-                    }
-                }
-                T.coo_n[s] = (uint16_t)(out.coo.size() - coo_before);
-                out.coo_entries += T.coo_n[s];
-                const int64_t nseg = (int64_t)segs.size() / 4;
-                const int m = (int)((nseg + 63) / 64);
-                T.m[s] = (uint16_t)m;
-                size_t base = out.bwd.size();
-                uint32_t empty[4] = {0, 0, 0, 0};                          // unused segment: entry 0 (never flushed), padding rows
-                for (int j = 1; j < 12; j++) pack10(empty, j, pad_row);
-                out.bwd.resize(base + (size_t)m * 64 * 4, 0u);
-                for (int64_t g = 0; g < (int64_t)m * 64; g++) {
-                    // logical segment g -> lane g / m, unit g % m ; physical int4 index (unit*64 + lane)
-                    int64_t lane = g / m, unit = g % m;
-                    size_t u0 = base + (size_t)((unit * 64 + lane) * 4);
-                    const uint32_t *src = g < nseg ? &segs[(size_t)g * 4] : empty;
-                    for (int w = 0; w < 4; w++) out.bwd[u0 + (size_t)w] = src[w];
-                }
-            }
-            (void)nd;
-            out.tiles.push_back(T);
-            }
-            for (int32_t t : distinct) stamp[(size_t)t] = -1;
+            for (size_t tu = 0; tu < n_tiles_u; tu++) emit_tile(Tdict, tu, wave_slices);
+            unstamp();
             tile_id++;
             i0 = i1;
         }
         return 0;
-    };
-    {
-        int64_t frag_rows = kFragRows;
-        if (const char *e = getenv("EMSAR_HIP_FRAG_ROWS")) { long long v = atoll(e); if (v >= kTileRows) frag_rows = v; }   // tests: many fragments on small inputs
-        const int64_t n_frag = std::max<int64_t>(1, (n_act + frag_rows - 1) / frag_rows);
-        std::vector<TiledLayout> frag((size_t)n_frag);
-        std::vector<int> frc((size_t)n_frag, 0);
-        unsigned hw = std::thread::hardware_concurrency();
-        int nthr = (int)std::min<int64_t>(n_frag, hw ? std::min(hw, 16u) : 1u);
-        if (const char *e = getenv("EMSAR_HOST_THREADS")) { int v = atoi(e); if (v >= 1) nthr = (int)std::min<int64_t>(n_frag, v); }
-        std::atomic<int64_t> next{0};
-        auto worker = [&]() {
-            for (;;) {
-                const int64_t g = next.fetch_add(1);
-                if (g >= n_frag) break;
-                frc[(size_t)g] = form_tiles(g * frag_rows, std::min(n_act, (g + 1) * frag_rows), frag[(size_t)g]);
-            }
-        };
-        run_on_threads(nthr, [&](int) { worker(); });
-        for (int64_t g = 0; g < n_frag; g++) if (frc[(size_t)g] != 0) return frc[(size_t)g];
-        const auto tp3 = t_now();
-        if (dbg_t) fprintf(stderr, "build_tiled: classify %.0f ms, sort %.0f ms, tiles %.0f ms on %d thread(s)\n", t_ms(tp0, tp1), t_ms(tp1, tp2), t_ms(tp2, tp3), nthr);
-        // concatenate: descriptors, COO pairs and far lists here (small), the three big arrays by the pool, each fragment
-        // into its own range of the final arrays
-        std::vector<size_t> slot_b((size_t)n_frag + 1, 0), fwd_b((size_t)n_frag + 1, 0), bwd_b((size_t)n_frag + 1, 0);
-        {
-            size_t nt_ = 0, nc_ = 0, nfar_ = 0;
-            for (int64_t g = 0; g < n_frag; g++) {
-                const TiledLayout &F = frag[(size_t)g];
-                nt_ += F.tiles.size(); nc_ += F.coo.size(); nfar_ += F.far_tid.size();
-                slot_b[(size_t)g + 1] = slot_b[(size_t)g] + F.slot_row.size();
-                fwd_b[(size_t)g + 1] = fwd_b[(size_t)g] + F.fwd.size();
-                bwd_b[(size_t)g + 1] = bwd_b[(size_t)g] + F.bwd.size();
-            }
-            if (slot_b[(size_t)n_frag] >= ((size_t)1 << 32)) return -1;
-            out.tiles.reserve(nt_); out.coo.reserve(nc_); out.far_tid.reserve(nfar_);
-            out.slot_row.resize(slot_b[(size_t)n_frag]); out.fwd.resize(fwd_b[(size_t)n_frag]); out.bwd.resize(bwd_b[(size_t)n_frag]);
-        }
-        for (int64_t g = 0; g < n_frag; g++) {
-            TiledLayout &F = frag[(size_t)g];
-            const uint32_t far_b = (uint32_t)out.far_tid.size(), coo_b = (uint32_t)out.coo.size();
-            for (Tile t : F.tiles) {
-                t.fwd_off += (uint64_t)fwd_b[(size_t)g] * 4; t.bwd_off += (uint64_t)bwd_b[(size_t)g] * 4;
-                t.row_base += (uint32_t)slot_b[(size_t)g]; t.far_off += far_b; t.coo_off += coo_b;
-                out.tiles.push_back(t);
-            }
-            out.coo.insert(out.coo.end(), F.coo.begin(), F.coo.end());
-            out.far_tid.insert(out.far_tid.end(), F.far_tid.begin(), F.far_tid.end());
-            out.tiled_entries += F.tiled_entries; out.tiled_ids += F.tiled_ids; out.far_entries += F.far_entries; out.coo_entries += F.coo_entries;
-            out.n_fslices += F.n_fslices; out.padded_slots += F.padded_slots;
-        }
-        next.store(0);
-        auto copier = [&]() {
-            for (;;) {
-                const int64_t g = next.fetch_add(1);
-                if (g >= n_frag) break;
-                TiledLayout &F = frag[(size_t)g];
-                if (!F.slot_row.empty()) memcpy(out.slot_row.data() + slot_b[(size_t)g], F.slot_row.data(), F.slot_row.size() * sizeof(int64_t));
-                if (!F.fwd.empty()) memcpy(out.fwd.data() + fwd_b[(size_t)g], F.fwd.data(), F.fwd.size() * 4);
-                if (!F.bwd.empty()) memcpy(out.bwd.data() + bwd_b[(size_t)g], F.bwd.data(), F.bwd.size() * 4);
-                F = TiledLayout();
-            }
-        };
-        run_on_threads(nthr, [&](int) { copier(); });
     }
-    // Largest tiles first: they start while the grid is full, the small ones fill the tail.
-    auto work = [](const Tile &t) {
-        int64_t w = 0;
-        for (int s = 0; s < t.n_slices; s++) w += (int64_t)t.k[s] * kTileSliceRows + (int64_t)t.m[s] * 64 * 12 + t.coo_n[s] * 2;
-        return w;
-    };
-    {   // the sort moves whole units (a tile and the one that follows it)
-        struct Unit { uint32_t first, n; int64_t w; };
-        std::vector<Unit> units;
-        for (size_t i = 0; i < out.tiles.size(); i++) {
-            if (out.tiles[i].follows && !units.empty()) { units.back().n++; units.back().w += work(out.tiles[i]); }
-            else { out.tiles[i].follows = 0; units.push_back(Unit{(uint32_t)i, 1u, work(out.tiles[i])}); }
+};
+
+// The fragments into `out`: descriptors, COO pairs and far lists on this thread (small), the three big arrays by the pool, each
+// fragment into its own range of the final arrays.  -1: more row slots than a descriptor can address.
+inline int concat_fragments(std::vector<TiledLayout> &frag, int nthr, TiledLayout &out) {
+    const size_t n_frag = frag.size();
+    std::vector<size_t> slot_b(n_frag + 1, 0), fwd_b(n_frag + 1, 0), bwd_b(n_frag + 1, 0);
+    size_t n_tiles = 0, n_coo = 0, n_far = 0;
+    for (size_t g = 0; g < n_frag; g++) {
+        const TiledLayout &F = frag[g];
+        n_tiles += F.tiles.size(); n_coo += F.coo.size(); n_far += F.far_tid.size();
+        slot_b[g + 1] = slot_b[g] + F.slot_row.size();
+        fwd_b[g + 1] = fwd_b[g] + F.fwd.size();
+        bwd_b[g + 1] = bwd_b[g] + F.bwd.size();
+    }
+    if (slot_b[n_frag] >= ((size_t)1 << 32)) return -1;
+    out.tiles.reserve(n_tiles); out.coo.reserve(n_coo); out.far_tid.reserve(n_far);
+    out.slot_row.resize(slot_b[n_frag]); out.fwd.resize(fwd_b[n_frag]); out.bwd.resize(bwd_b[n_frag]);
+    for (size_t g = 0; g < n_frag; g++) {
+        const TiledLayout &F = frag[g];
+        const uint32_t far_b = (uint32_t)out.far_tid.size(), coo_b = (uint32_t)out.coo.size();
+        for (Tile t : F.tiles) {
+            t.fwd_off += (uint64_t)fwd_b[g] * 4; t.bwd_off += (uint64_t)bwd_b[g] * 4;
+            t.row_base += (uint32_t)slot_b[g]; t.far_off += far_b; t.coo_off += coo_b;
+            out.tiles.push_back(t);
         }
-        std::stable_sort(units.begin(), units.end(), [](const Unit &a, const Unit &b) { return a.w > b.w; });
-        // The tail: with ~3.4 k units for 1024 workgroup slots the last workgroups run on a half-empty chip (timeline of config 3: 14 of
-        // 114 us below 75 % occupancy).  The lightest units are therefore cut into their tiles -- every tile carries the dictionary
-        // descriptor, so a tile that stops following is a unit of its own -- and the small pieces fill the tail.  Measured (EMSAR_HIP_TAIL_SPLIT =
-        // share of the units cut, config 3): 0 / 10 / 20 / 35 / 50 % -> family law 0.1071 / 0.1055 / 0.1075 / 0.1077 / 0.1108 ms, window law
-        // 0.0967 / 0.0976 / 0.0986 / 0.1000: what the tail gains the extra per-unit overhead takes back.  Off.
-        int tail_pct = 0;
-        if (const char *e = getenv("EMSAR_HIP_TAIL_SPLIT")) { int v = atoi(e); if (v >= 0 && v <= 100) tail_pct = v; }
-        if (tail_pct > 0 && units.size() > 2048) {
-            const size_t keep = units.size() - units.size() * (size_t)tail_pct / 100;
-            std::vector<Unit> cut(units.begin(), units.begin() + (std::ptrdiff_t)keep);
-            for (size_t q = keep; q < units.size(); q++)
-                for (uint32_t j = 0; j < units[q].n; j++) {
-                    out.tiles[units[q].first + j].follows = 0;
-                    cut.push_back(Unit{units[q].first + j, 1u, work(out.tiles[units[q].first + j])});
-                }
-            std::stable_sort(cut.begin() + (std::ptrdiff_t)keep, cut.end(), [](const Unit &a, const Unit &b) { return a.w > b.w; });
-            units.swap(cut);
+        out.coo.insert(out.coo.end(), F.coo.begin(), F.coo.end());
+        out.far_tid.insert(out.far_tid.end(), F.far_tid.begin(), F.far_tid.end());
+        out.tiled_entries += F.tiled_entries; out.tiled_ids += F.tiled_ids; out.far_entries += F.far_entries; out.coo_entries += F.coo_entries;
+        out.n_fslices += F.n_fslices; out.padded_slots += F.padded_slots;
+    }
+    std::atomic<size_t> next{0};
+    run_on_threads(nthr, [&](int) {
+        for (;;) {
+            const size_t g = next.fetch_add(1);
+            if (g >= n_frag) break;
+            TiledLayout &F = frag[g];
+            if (!F.slot_row.empty()) memcpy(out.slot_row.data() + slot_b[g], F.slot_row.data(), F.slot_row.size() * sizeof(int64_t));
+            if (!F.fwd.empty()) memcpy(out.fwd.data() + fwd_b[g], F.fwd.data(), F.fwd.size() * 4);
+            if (!F.bwd.empty()) memcpy(out.bwd.data() + bwd_b[g], F.bwd.data(), F.bwd.size() * 4);
+            F = TiledLayout();
         }
-        if (dbg_t && !units.empty()) {     // how well the units fill 1024 workgroup slots in this (longest-first) order: greedy makespan over the mean load
-            for (int64_t c : {(int64_t)0, (int64_t)20000}) {     // c: a fixed cost per unit (descriptor, dictionary, flush) in the units of `work`
-                std::vector<int64_t> slot(1024, 0);
-                int64_t tot = 0;
-                for (const Unit &u : units) { auto it = std::min_element(slot.begin(), slot.end()); *it += u.w + c; tot += u.w; }
-                const int64_t mk = *std::max_element(slot.begin(), slot.end());
-                fprintf(stderr, "build_tiled: %zu units, work max %lld, median %lld, min %lld; with %lld per unit on top: greedy makespan on 1024 slots %.0f = %.3f of the mean load\n",
-                        units.size(), (long long)units.front().w, (long long)units[units.size() / 2].w, (long long)units.back().w, (long long)c, (double)mk, (double)mk * 1024.0 / (double)tot);
+    });
+    return 0;
+}
+
+// what a tile costs the pass, in operands: forward columns, backward segments, COO pairs
+inline int64_t tile_work(const Tile &t) {
+    int64_t w = 0;
+    for (int s = 0; s < t.n_slices; s++) w += (int64_t)t.k[s] * kTileSliceRows + (int64_t)t.m[s] * 64 * 12 + t.coo_n[s] * 2;
+    return w;
+}
+// Largest units first: they start while the grid is full, the small ones fill the tail.  The sort moves whole units (a tile and
+// the ones that follow it); TiledKnobs::tail_pct cuts the lightest units into their tiles.  Fills out.unit_first.
+inline void order_units(TiledLayout &out, const TiledKnobs &K) {
+    struct Unit { uint32_t first, n; int64_t w; };
+    auto heavier = [](const Unit &a, const Unit &b) { return a.w > b.w; };
+    std::vector<Unit> units;
+    for (size_t i = 0; i < out.tiles.size(); i++) {
+        if (out.tiles[i].follows && !units.empty()) { units.back().n++; units.back().w += tile_work(out.tiles[i]); }
+        else { out.tiles[i].follows = 0; units.push_back(Unit{(uint32_t)i, 1u, tile_work(out.tiles[i])}); }
+    }
+    std::stable_sort(units.begin(), units.end(), heavier);
+    if (K.tail_pct > 0 && units.size() > 2048) {
+        const size_t keep = units.size() - units.size() * (size_t)K.tail_pct / 100;
+        std::vector<Unit> cut(units.begin(), units.begin() + (std::ptrdiff_t)keep);
+        for (size_t q = keep; q < units.size(); q++)
+            for (uint32_t j = 0; j < units[q].n; j++) {
+                out.tiles[units[q].first + j].follows = 0;
+                cut.push_back(Unit{units[q].first + j, 1u, tile_work(out.tiles[units[q].first + j])});
             }
-        }
-        std::vector<Tile> sorted_tiles;
-        sorted_tiles.reserve(out.tiles.size());
-        out.unit_first.clear();
-        for (const Unit &u : units) {
-            out.unit_first.push_back((uint32_t)sorted_tiles.size());
-            for (uint32_t j = 0; j < u.n; j++) sorted_tiles.push_back(out.tiles[u.first + j]);
-        }
+        std::stable_sort(cut.begin() + (std::ptrdiff_t)keep, cut.end(), heavier);
+        units.swap(cut);
+    }
+    std::vector<Tile> sorted_tiles;
+    sorted_tiles.reserve(out.tiles.size());
+    out.unit_first.clear();
+    for (const Unit &u : units) {
         out.unit_first.push_back((uint32_t)sorted_tiles.size());
-        out.tiles.swap(sorted_tiles);
+        for (uint32_t j = 0; j < u.n; j++) sorted_tiles.push_back(out.tiles[u.first + j]);
     }
-    if (dbg_t) fprintf(stderr, "build_tiled: total %.0f ms; %zu tiles in %zu units, %lld slices, %lld entries in %lld padded operands, %lld far\n", t_ms(tp0, t_now()),
-                       out.tiles.size(), out.unit_first.empty() ? (size_t)0 : out.unit_first.size() - 1, (long long)out.n_fslices,
-                       (long long)out.tiled_entries, (long long)out.padded_slots, (long long)out.far_entries);
-    if (dbg_t) {        // batches of 8 columns / segments per slice: what the E- and M-steps request after their first batch
+    out.unit_first.push_back((uint32_t)sorted_tiles.size());
+    out.tiles.swap(sorted_tiles);
+}
+
+// EMSAR_HIP_DEBUG: what the finished layout will cost the pass kernels (tools/ and profiles/ quote these lines)
+inline void print_layout_stats(const TiledLayout &out, std::chrono::steady_clock::time_point build_begin) {
+    const size_t nu = out.unit_first.empty() ? 0 : out.unit_first.size() - 1;
+    if (nu > 0) {     // how well the units fill 1024 workgroup slots in this (longest-first) order: greedy makespan over the mean load
+        std::vector<int64_t> uw(nu, 0);
+        for (size_t u = 0; u < nu; u++) for (uint32_t t = out.unit_first[u]; t < out.unit_first[u + 1]; t++) uw[u] += tile_work(out.tiles[t]);
+        for (int64_t c : {(int64_t)0, (int64_t)20000}) {     // c: a fixed cost per unit (descriptor, dictionary, flush) in the units of tile_work
+            std::vector<int64_t> slot(1024, 0);
+            int64_t tot = 0;
+            for (const int64_t w : uw) { auto it = std::min_element(slot.begin(), slot.end()); *it += w + c; tot += w; }
+            const int64_t mk = *std::max_element(slot.begin(), slot.end());
+            fprintf(stderr, "build_tiled: %zu units, work max %lld, median %lld, min %lld; with %lld per unit on top: greedy makespan on 1024 slots %.0f = %.3f of the mean load\n",
+                    nu, (long long)uw.front(), (long long)uw[nu / 2], (long long)uw.back(), (long long)c, (double)mk, (double)mk * 1024.0 / (double)tot);
+        }
+    }
+    const double total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - build_begin).count();   // the build ends here
+    fprintf(stderr, "build_tiled: total %.0f ms; %zu tiles in %zu units, %lld slices, %lld entries in %lld padded operands, %lld far\n", total_ms,
+            out.tiles.size(), nu, (long long)out.n_fslices, (long long)out.tiled_entries, (long long)out.padded_slots, (long long)out.far_entries);
+    {        // batches of 8 columns / segments per slice: what the E- and M-steps request after their first batch
         double n = 0, sk = 0, sm = 0, k8 = 0, k16 = 0, m8 = 0, m16 = 0, m24 = 0;
-        for (const Tile &T : out.tiles) for (int s2 = 0; s2 < (int)T.n_slices; s2++) {
-            n += 1; sk += T.k[s2]; sm += T.m[s2]; k8 += T.k[s2] > 8; k16 += T.k[s2] > 16; m8 += T.m[s2] > 8; m16 += T.m[s2] > 16; m24 += T.m[s2] > 24;
+        for (const Tile &T : out.tiles) for (int s = 0; s < (int)T.n_slices; s++) {
+            n += 1; sk += T.k[s]; sm += T.m[s]; k8 += T.k[s] > 8; k16 += T.k[s] > 16; m8 += T.m[s] > 8; m16 += T.m[s] > 16; m24 += T.m[s] > 24;
         }
         if (n > 0) fprintf(stderr, "build_tiled: per slice %.2f forward columns (%.0f %% > 8, %.0f %% > 16), %.2f backward segments per lane (%.0f %% > 8, %.0f %% > 16, %.0f %% > 24)\n",
                            sk / n, 100 * k8 / n, 100 * k16 / n, sm / n, 100 * m8 / n, 100 * m16 / n, 100 * m24 / n);
     }
-    if (dbg_t && !out.unit_first.empty()) {         // how evenly a unit's slices load the four waves of its workgroup: sum of the loads / (4 x the largest)
+    if (!out.unit_first.empty()) {         // how evenly a unit's slices load the four waves of its workgroup: sum of the loads / (4 x the largest)
         double eff = 0, wsum = 0, hist[13] = {0};
-        const size_t nu = out.unit_first.size() - 1;
         for (size_t u = 0; u < nu; u++) {
             int64_t load[kTileSlices] = {0, 0, 0, 0}, tot = 0; int ns = 0;
             for (uint32_t t = out.unit_first[u]; t < out.unit_first[u + 1]; t++) {
                 const Tile &T = out.tiles[t];
-                for (int s2 = 0; s2 < (int)T.n_slices; s2++) {
-                    const int64_t w = (int64_t)T.k[s2] * kTileSliceRows + (int64_t)T.m[s2] * 64 * 12;
-                    load[(T.wave_of >> (2 * s2)) & 3] += w; tot += w; ns++;
+                for (int s = 0; s < (int)T.n_slices; s++) {
+                    const int64_t w = (int64_t)T.k[s] * kTileSliceRows + (int64_t)T.m[s] * 64 * 12;
+                    load[(T.wave_of >> (2 * s)) & 3] += w; tot += w; ns++;
                 }
             }
             const int64_t mx = std::max(std::max(load[0], load[1]), std::max(load[2], load[3]));
@@ -918,8 +986,61 @@ inline int build_tiled(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr_in,
         for (int i = 1; i <= 12; i++) fprintf(stderr, " %.0f", hist[i]);
         fprintf(stderr, "\n");
     }
-    const int ext = check_tiled_extents(out);       // nothing reaches the device unless every descriptor stays inside its arrays
-    return ext == 0 ? 0 : ext;
+}
+
+// The TILED layout of a CSR matrix.  0 = built and checked; -1 = too many rows or row slots for 32-bit descriptors; -3 = a row that
+// fits no dictionary (excluded by kMaxRowLen); -20 .. -32 = check_tiled_extents refused the result.
+inline int build_tiled(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr_in, const int32_t *col_idx_in, TiledLayout &out,
+                       bool merge_rows = false, bool renumber = true) {
+    if (n_rows >= (int64_t)1 << 32) return -1;
+    out = TiledLayout();
+    const TiledKnobs K = read_tiled_knobs();
+    auto t_now = [] { return std::chrono::steady_clock::now(); };
+    auto t_ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    if (renumber) cooccurrence_order(n_rows, n_tx, row_ptr_in, col_idx_in, kMaxRowLen, kBlk, out.new_of_old, out.renum);
+    RowView V{row_ptr_in, col_idx_in, out.new_of_old.empty() ? nullptr : out.new_of_old.data()};
+    out.n_rows = n_rows; out.n_tx = n_tx; out.nnz = (int64_t)row_ptr_in[n_rows];
+    MergedRows M;                            // merged view of the matrix (only built when asked for)
+    if (merge_rows) {
+        merge_identical_rows(n_rows, V, M, out);
+        V = RowView{M.ptr.data(), M.col.data(), nullptr};
+        n_rows = (int64_t)M.orig.size();
+    }
+    const HostThreads H = host_threads(n_rows);
+
+    const auto tp0 = t_now();
+    RowKeys keys;
+    classify_rows(n_rows, V, merge_rows ? &M.orig : nullptr, K, H, out, keys);
+    const int64_t n_act = (int64_t)keys.act.size();
+    const auto tp1 = t_now();
+    std::vector<uint32_t> perm;
+    sort_rows(n_tx, K, H, keys, perm);
+    const auto tp2 = t_now();
+
+    // The sorted rows are cut into fragments of frag_rows rows; every fragment is tiled on its own (into a private
+    // TiledLayout) and the fragments are concatenated.  The cut points depend on the data only, so the layout is the same
+    // whatever the number of host threads that happen to build it.
+    const int64_t n_frag = std::max<int64_t>(1, (n_act + K.frag_rows - 1) / K.frag_rows);
+    const int nthr = H.for_fragments(n_frag);
+    std::vector<TiledLayout> frag((size_t)n_frag);
+    std::vector<int> frc((size_t)n_frag, 0);
+    std::atomic<int64_t> next{0};
+    run_on_threads(nthr, [&](int) {
+        FragmentTiler tiler(V, K, perm, keys.ecnt, n_tx);
+        for (;;) {
+            const int64_t g = next.fetch_add(1);
+            if (g >= n_frag) break;
+            tiler.out = TiledLayout();
+            frc[(size_t)g] = tiler.run(g * K.frag_rows, std::min(n_act, (g + 1) * K.frag_rows));
+            frag[(size_t)g] = std::move(tiler.out);
+        }
+    });
+    for (const int rc : frc) if (rc != 0) return rc;
+    if (K.debug) fprintf(stderr, "build_tiled: classify %.0f ms, sort %.0f ms, tiles %.0f ms on %d thread(s)\n", t_ms(tp0, tp1), t_ms(tp1, tp2), t_ms(tp2, t_now()), nthr);
+    if (const int rc = concat_fragments(frag, nthr, out)) return rc;
+    order_units(out, K);
+    if (K.debug) print_layout_stats(out, tp0);
+    return check_tiled_extents(out);       // nothing reaches the device unless every descriptor stays inside its arrays
 }
 
 // What k_pass_tiled_unit reads first, at an address that depends on the workgroup index alone (no unit -> tile index to chase):

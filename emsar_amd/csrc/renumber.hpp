@@ -19,6 +19,7 @@
 //      already good -- consecutive windows -- is left alone).
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -93,7 +94,7 @@ inline void cooccurrence_order(int64_t n_rows, int32_t n_tx, const uint64_t *row
     auto hash = [](uint64_t k) { k ^= k >> 31; k *= 0x9E3779B97F4A7C15ull; k ^= k >> 29; k *= 0xBF58476D1CE4E5B9ull; k ^= k >> 32; return k; };
     auto on_threads = [&](auto fn) {
         std::vector<std::thread> pool;
-        bool failed = false;
+        std::atomic<bool> failed{false};
         for (int t = 1; t < nt; t++) {
             try { pool.emplace_back([&, t] { try { fn(t); } catch (const std::bad_alloc &) { failed = true; } }); }
             catch (const std::system_error &) { try { fn(t); } catch (const std::bad_alloc &) { failed = true; } }
