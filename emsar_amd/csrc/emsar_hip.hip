@@ -24,6 +24,8 @@
 //                         k_sub_draw, k_sub_scale                the depth subsampling: binomial draws, every replicate to its own depth
 //   kernels_genes.hpp     k_gene_sums, k_gene_finish             per-gene sums in a fixed order (gene_sums, the bootstrap's gene sd)
 //   kernels_quant.hpp     k_boot_quantiles                       quantiles over the held replicates (bootstrap_quantiles)
+//   kernels_isoforms.hpp  k_iso_usage, k_iso_dominant, k_iso_accum, k_iso_quantiles   each transcript's share of its gene, the dominant
+//                         isoform, and their statistics over the replicates (isoform_usage, bootstrap_isoforms)
 //   collapse.hip          read-level rows -> weighted segments (own translation unit)
 #include <hip/hip_runtime.h>
 
@@ -55,6 +57,7 @@
 #include "kernels_boot.hpp"
 #include "kernels_genes.hpp"
 #include "kernels_quant.hpp"
+#include "kernels_isoforms.hpp"
 
 // ==================================================================================================
 // context
@@ -88,13 +91,14 @@ struct SetsDev {
 
 // gene map (emsar_hip_set_gene_map), dropped by upload_structure.  One int32 block: per gene in gene order its transcripts' library
 // indices by ascending caller tid (gene_tx), the chunks' begin offsets into gene_tx (chunk_beg, n_gene_chunks + 1), each chunk's
-// gene when that gene has one chunk, else -1 (chunk_out), and the genes of more than one chunk (gene_multi: gene, first chunk, end)
+// gene when that gene has one chunk, else -1 (chunk_out), the genes of more than one chunk (gene_multi: gene, first chunk, end), and
+// the gene of every library index, -1 = none (gene_of_lib, n_tx)
 struct GeneMap {
     bool have_genes = false;
     int32_t n_genes = 0;
     int64_t n_gene_chunks = 0, n_gene_multi = 0;
     DevBuf<int32_t> d_gene_blk;
-    int32_t *d_gene_tx = nullptr, *d_chunk_beg = nullptr, *d_chunk_out = nullptr, *d_gene_multi = nullptr;   // views into d_gene_blk
+    int32_t *d_gene_tx = nullptr, *d_chunk_beg = nullptr, *d_chunk_out = nullptr, *d_gene_multi = nullptr, *d_gene_of_lib = nullptr;   // views into d_gene_blk
 };
 
 // compute_adjEUMA on the device (emsar_hip_upload_euma), dropped by upload_structure
@@ -212,10 +216,10 @@ inline const double *to_lib(const emsar_hip_ctx *ctx, const double *caller, std:
     for (size_t t = 0; t < m.size(); t++) tmp[(size_t)m[t]] = caller[t];
     return tmp.data();
 }
-inline void from_lib(const emsar_hip_ctx *ctx, double *v /* in place: library order -> caller order */) {
+template <class V> inline void from_lib(const emsar_hip_ctx *ctx, V *v /* in place: library order -> caller order */) {
     const auto &m = tid_map(ctx);
     if (m.empty() || ctx->layout != EMSAR_LAYOUT_TILED) return;
-    std::vector<double> tmp(v, v + m.size());
+    std::vector<V> tmp(v, v + m.size());
     for (size_t t = 0; t < m.size(); t++) v[t] = tmp[(size_t)m[t]];
 }
 

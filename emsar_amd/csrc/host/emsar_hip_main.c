@@ -24,6 +24,10 @@
  * --bootstrap-quantiles q1,q2,.. (needs --bootstrap B, B <= 4096) adds percentile intervals: <prefix>.<i>.bootq holds, per transcript, the
  * q-quantiles of FPKM and then of TPM over the same B replicates (emsar_hip_bootstrap_quantiles: q = 0.025,0.5,0.975 gives the 95 %
  * percentile interval and the median), with --g2t also <prefix>.<i>.gbootq per gene.  The other files are the same bytes with and without it.
+ * --isoforms (needs --g2t) adds the isoform usage: <prefix>.<i>.isoforms holds, per transcript that is in a gene, its gene, its FPKM, its share
+ * of the gene's FPKM and whether it is the gene's dominant isoform (emsar_hip_isoform_usage on the .fpkm column); with --bootstrap B also the
+ * mean and sd of that share and how often the transcript dominates over the same B replicates, with --bootstrap-quantiles also the share's
+ * quantiles (emsar_hip_bootstrap_isoforms, which gives the other bootstrap files the same bytes).  The other files do not change with it.
  * --subsample f1,f2,.. answers "was the sample sequenced deep enough": <prefix>.<i>.saturation holds, per transcript and fraction,
  * the mean and sd of FPKM (at the thinned depth) and TPM over --subsample-reps replicates in which every read is kept with
  * probability f (emsar_hip_subsample; seed --subsample-seed + i), with --g2t also <prefix>.<i>.gsaturation per gene.  The other
@@ -59,6 +63,7 @@ typedef struct {
     int bq_n; double bq[64];          /* --bootstrap-quantiles q1,.. (0 = off) */
     int sub_nf, sub_reps; double sub_f[64]; uint64_t sub_seed;   /* --subsample f1,.. (0 = off), --subsample-reps, --subsample-seed: sample i uses seed + i */
     const char *g2t;                  /* --g2t FILE (NULL = off) */
+    int isoforms;                     /* --isoforms (needs --g2t) */
     const emsar_genes *genes;         /* its gene map, read once by main() and shared read-only by the workers */
 } config;
 
@@ -119,6 +124,7 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
     emsar_counts *cnt = parsed->cnt; emsar_model *m = NULL;
     double *theta = NULL, *rounds = NULL, *mean = NULL, *sd = NULL, *ieuma = NULL, *tpm = NULL, *ir = NULL, *den = NULL; int32_t *iri = NULL;
     double *gcols = NULL, *gsums = NULL;     /* --g2t: [3][n_tx] FPKM, iReadcount, TPM and their [3][n_genes] gene sums */
+    double *iso_u = NULL; int32_t *dom = NULL;   /* --isoforms: [n_tx] usage and [n_genes] dominant isoform of the .fpkm column */
     int rc = parsed->rc;
     parsed->cnt = NULL;
     snprintf(err, sizeof err, "%s", parsed->err);
@@ -225,16 +231,38 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         snprintf(path, sizeof path, "%s/%s.%d.gfpkm", cfg->outdir, cfg->prefix, i);
         if ((rc = emsar_write_gfpkm(path, G, gsums, gsums + NG, gsums + 2 * NG))) { fprintf(stderr, "can't write %s\n", path); goto done; }
     }
+    /* ---- isoform usage (--isoforms): each transcript's share of its gene's FPKM and the gene's dominant isoform, on the device ---- */
+    const int ISO = G && cfg->isoforms;
+    if (ISO) {
+        iso_u = (double *)malloc((T > 0 ? T : 1) * 8); dom = (int32_t *)malloc((NG > 0 ? NG : 1) * 4);
+        if (!iso_u || !dom) { rc = EMSAR_HOST_ERR_OOM; goto done; }
+        if ((rc = emsar_hip_isoform_usage(ctx, 1, mean, iso_u, dom))) {
+            fprintf(stderr, "alnfile[%d]: isoform usage: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+            goto done;
+        }
+        if (cfg->boot_n <= 0) {
+            snprintf(path, sizeof path, "%s/%s.%d.isoforms", cfg->outdir, cfg->prefix, i);
+            if ((rc = emsar_write_isoforms(path, r, G, mean, iso_u, dom, 0, NULL, NULL, NULL, 0, NULL, NULL))) { fprintf(stderr, "can't write %s\n", path); goto done; }
+        }
+    }
     /* ---- Poisson bootstrap (--bootstrap B): its own file; .fpkm keeps the reference's column 3.  With --g2t the same replicates
-     *      give the genes' sd as well (bootstrap_genes: the transcript outputs are the same bits as bootstrap's) ---- */
+     *      give the genes' sd as well (bootstrap_genes: the transcript outputs are the same bits as bootstrap's), and with --isoforms
+     *      the usage statistics (bootstrap_isoforms: every other output is the same bits) ---- */
     if (cfg->boot_n > 0) {
         double *bm = (double *)malloc(T * 8), *bs = (double *)malloc(T * 8), *bt = (double *)malloc(T * 8);
         double *gb = G ? (double *)malloc(NG * 8 * 3) : NULL;
         /* --bootstrap-quantiles: [2][n_q][n_tx] FPKM then TPM quantiles, with --g2t also [2][n_q][n_genes] */
         const size_t NQ = (size_t)cfg->bq_n;
         double *bq = NQ ? (double *)malloc((T > 0 ? T : 1) * 8 * 2 * NQ) : NULL, *gq = NQ && G ? (double *)malloc((NG > 0 ? NG : 1) * 8 * 2 * NQ) : NULL;
-        if (!bm || !bs || !bt || (G && !gb) || (NQ && !bq) || (NQ && G && !gq)) rc = EMSAR_HOST_ERR_OOM;
-        else if ((rc = NQ ? emsar_hip_bootstrap_quantiles(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, cfg->bq_n, cfg->bq, bm, bs, bt, NULL, NULL,
+        /* --isoforms: [2][n_tx] mean and sd of the usage, [n_tx] dominance counts, [n_q][n_tx] usage quantiles */
+        double *ub = ISO ? (double *)malloc((T > 0 ? T : 1) * 8 * (2 + NQ)) : NULL;
+        int32_t *uc = ISO ? (int32_t *)malloc((T > 0 ? T : 1) * 4) : NULL;
+        const emsar_isoform_outputs iso = {ub, ub ? ub + T : NULL, uc, ub && NQ ? ub + 2 * T : NULL};
+        if (!bm || !bs || !bt || (G && !gb) || (NQ && !bq) || (NQ && G && !gq) || (ISO && (!ub || !uc))) rc = EMSAR_HOST_ERR_OOM;
+        else if ((rc = ISO ? emsar_hip_bootstrap_isoforms(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, cfg->bq_n, cfg->bq, bm, bs, bt, NULL, NULL,
+                                                          bq, NQ ? bq + NQ * T : NULL, gb, gb + NG, gb + 2 * NG, gq, NQ ? gq + NQ * NG : NULL,
+                                                          &w->bstats[i], &w->qstats[i], &iso)
+                         : NQ ? emsar_hip_bootstrap_quantiles(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, cfg->bq_n, cfg->bq, bm, bs, bt, NULL, NULL,
                                                           bq, bq + NQ * T, gb, G ? gb + NG : NULL, G ? gb + 2 * NG : NULL, gq, G ? gq + NQ * NG : NULL,
                                                           &w->bstats[i], &w->qstats[i])
                          : G ? emsar_hip_bootstrap_genes(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, bm, bs, bt, NULL, gb, gb + NG, gb + 2 * NG,
@@ -256,8 +284,14 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
                     if ((rc = emsar_write_gbootq(path, G, cfg->bq_n, cfg->bq, gq, gq + NQ * NG))) fprintf(stderr, "can't write %s\n", path);
                 }
             }
+            if (!rc && ISO) {
+                snprintf(path, sizeof path, "%s/%s.%d.isoforms", cfg->outdir, cfg->prefix, i);
+                if ((rc = emsar_write_isoforms(path, r, G, mean, iso_u, dom, cfg->boot_n, iso.usage_mean, iso.usage_sd, iso.dominant_count, cfg->bq_n, cfg->bq,
+                                               iso.usage_q)))
+                    fprintf(stderr, "can't write %s\n", path);
+            }
         }
-        free(bm); free(bs); free(bt); free(gb); free(bq); free(gq);
+        free(bm); free(bs); free(bt); free(gb); free(bq); free(gq); free(ub); free(uc);
         if (rc) goto done;
     }
     /* ---- depth subsampling (--subsample f1,f2,..): its own files ---- */
@@ -289,7 +323,7 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         fprintf(stdout, "Complete: %s/%s.%d.fpkm  (EM passes %d, converged %d, solve %.1f ms, logL %.6f)\n", cfg->outdir, cfg->prefix, i,
                 w->stats[i].iters, w->stats[i].converged, w->stats[i].solve_ms, w->stats[i].loglik);
 done:
-    free(theta); free(rounds); free(mean); free(sd); free(ieuma); free(tpm); free(ir); free(iri); free(den); free(gcols); free(gsums);
+    free(theta); free(rounds); free(mean); free(sd); free(ieuma); free(tpm); free(ir); free(iri); free(den); free(gcols); free(gsums); free(iso_u); free(dom);
     emsar_counts_free(cnt); emsar_model_free(m);
     return rc;
 }
@@ -375,6 +409,9 @@ static void usage(const char *a0) {
             "      --subsample-seed <n>  seed of their draws (default 1; sample i of -M uses n + i)\n"
             "      --g2t <file>          gene map (gene<TAB>transcript per line, plain or gzipped): also write <prefix>.<i>.gfpkm, the\n"
             "                            per-gene sums of util/FPKM2gFPKM.pl, and with --bootstrap <prefix>.<i>.gbootstrap (gene sd)\n"
+            "      --isoforms            with --g2t: also write <prefix>.<i>.isoforms, per transcript its share of its gene's FPKM (usage) and whether\n"
+            "                            it is the gene's dominant isoform; with --bootstrap the mean and sd of the usage and the frequency of\n"
+            "                            dominance over the replicates, with --bootstrap-quantiles the usage's quantiles as well\n"
             "      --gpus <n> / --devices <a,b,..> (-M: one worker per entry, ids may repeat) / --device <d> / --plain /\n"
             "      --stats-json <file> / -q / -v\n", a0);
 }
@@ -398,7 +435,7 @@ int main(int argc, char **argv) {
         {"count-floor", required_argument, 0, 1004}, {"streaming-only", no_argument, 0, 1005}, {"rsh-cache", optional_argument, 0, 1006}, {"zero-cut", required_argument, 0, 1007}, {"abs-step", required_argument, 0, 1008}, {"devices", required_argument, 0, 1009}, {"device-collapse", no_argument, 0, 1010}, {"no-deterministic", no_argument, 0, 1011},
         {"bootstrap", required_argument, 0, 1012}, {"bootstrap-seed", required_argument, 0, 1013}, {"g2t", required_argument, 0, 1014},
         {"subsample", required_argument, 0, 1015}, {"subsample-reps", required_argument, 0, 1016}, {"subsample-seed", required_argument, 0, 1017},
-        {"bootstrap-quantiles", required_argument, 0, 1018},
+        {"bootstrap-quantiles", required_argument, 0, 1018}, {"isoforms", no_argument, 0, 1019},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
@@ -489,6 +526,7 @@ int main(int argc, char **argv) {
                 }
                 break;
             }
+            case 1019: cfg.isoforms = 1; break;
             case 1009: {
                 const char *q = optarg;
                 while (*q && n_dev_map < 64) {
@@ -507,6 +545,7 @@ int main(int argc, char **argv) {
     if (cfg.bq_n > 0 && (cfg.boot_n < 1 || cfg.boot_n > 4096)) {
         fprintf(stderr, "--bootstrap-quantiles needs --bootstrap B with 1 <= B <= 4096 replicates.\n"); return 1;
     }
+    if (cfg.isoforms && !cfg.g2t) { fprintf(stderr, "--isoforms needs --g2t FILE.\n"); return 1; }
     if (!cfg.rsh_path || optind + 2 >= argc) { usage(argv[0]); return 1; }
     if (emsar_set_strand(strand, cfg.ao.pe, &cfg.ao.strand)) { fprintf(stderr, "error: invalid strand type.\n"); return 1; }
     cfg.outdir = argv[optind]; cfg.prefix = argv[optind + 1];

@@ -160,6 +160,14 @@ int emsar_write_gbootstrap(const char *path, const emsar_genes *g, const double 
  * q over the bootstrap replicates ([n_q][n_tx] / [n_q][n_genes] each), "%lf"; the header names the probabilities */
 int emsar_write_bootq(const char *path, const emsar_rsh *r, int n_q, const double *q, const double *fpkm_q, const double *tpm_q);
 int emsar_write_gbootq(const char *path, const emsar_genes *g, int n_q, const double *q, const double *fpkm_q, const double *tpm_q);
+/* .isoforms (emsar-hip --g2t --isoforms): one line per transcript that is in a gene (gene_of_tx >= 0), in the order of .fpkm:
+ * transcript_ID gene_ID FPKM usage dominant, "%s\t%s\t%lf\t%lf\t%d"; usage [n_tx] and dominant [n_genes] (tid of the gene's dominant
+ * isoform or -1) as emsar_hip_isoform_usage returns them for fpkm.  n_boot > 0 (--bootstrap B) adds usage_mean usage_sd dominant_freq
+ * (= dominant_count / n_boot), n_q > 0 as well (--bootstrap-quantiles) one usage_q<q> column per probability (usage_q [n_q][n_tx]),
+ * all "%lf".  With n_boot == 0 the bootstrap arguments are not read. */
+int emsar_write_isoforms(const char *path, const emsar_rsh *r, const emsar_genes *g, const double *fpkm, const double *usage,
+                         const int32_t *dominant, int n_boot, const double *usage_mean, const double *usage_sd,
+                         const int32_t *dominant_count, int n_q, const double *q, const double *usage_q);
 /* .saturation (emsar-hip --subsample): a "#" line (fractions, replicates, seed, depth_mean per fraction), a header, then per
  * transcript its name, FPKM and TPM as in .fpkm and per fraction mean_FPKM sd_FPKM mean_TPM sd_TPM ([n_fractions][n_tx] each) */
 int emsar_write_saturation(const char *path, const emsar_rsh *r, const double *fpkm, const double *tpm, int n_fractions,

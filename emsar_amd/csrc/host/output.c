@@ -12,6 +12,10 @@
  *   .bootq              a header naming the probabilities (FPKM@q.. then TPM@q.., q as "%.17g"), then per transcript the quantiles of
  *                       FPKM at each q and of TPM at each q over the bootstrap replicates, all "%lf"
  *   .gbootq             the same per gene, in the order of .gfpkm
+ * and the isoform usage's file (--g2t --isoforms):
+ *   .isoforms           per transcript that is in a gene, in the order of .fpkm: transcript_ID gene_ID FPKM usage dominant
+ *                       ("%s\t%s\t%lf\t%lf\t%d"), with --bootstrap also usage_mean usage_sd dominant_freq, with --bootstrap-quantiles
+ *                       also usage_q<q> per probability (q as "%.17g"), all "%lf"
  * and the depth subsampling's files (--subsample):
  *   .saturation         "# fractions=.. replicates=.. seed=.. depth_mean=..", a header, then per transcript FPKM and TPM as in .fpkm and
  *                       per fraction mean_FPKM sd_FPKM mean_TPM sd_TPM, all "%lf"
@@ -96,6 +100,27 @@ int emsar_write_bootq(const char *path, const emsar_rsh *r, int n_q, const doubl
 
 int emsar_write_gbootq(const char *path, const emsar_genes *g, int n_q, const double *q, const double *fpkm_q, const double *tpm_q) {
     return write_bootq(path, "geneID", g->names, g->n_genes, n_q, q, fpkm_q, tpm_q);
+}
+
+int emsar_write_isoforms(const char *path, const emsar_rsh *r, const emsar_genes *g, const double *fpkm, const double *usage,
+                         const int32_t *dominant, int n_boot, const double *usage_mean, const double *usage_sd,
+                         const int32_t *dominant_count, int n_q, const double *q, const double *usage_q) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    if (n_boot <= 0) n_q = 0;
+    fprintf(f, "transcript_ID\tgene_ID\tFPKM\tusage\tdominant");
+    if (n_boot > 0) fprintf(f, "\tusage_mean\tusage_sd\tdominant_freq");
+    for (int k = 0; k < n_q; k++) fprintf(f, "\tusage_q%.17g", q[k]);
+    fprintf(f, "\n");
+    for (int32_t t = 0; t < r->n_tx; t++) {
+        const int32_t k = g->gene_of_tx[t];
+        if (k < 0) continue;
+        fprintf(f, "%s\t%s\t%lf\t%lf\t%d", r->names[t], g->names[k], fpkm[t], usage[t], dominant[k] == t ? 1 : 0);
+        if (n_boot > 0) fprintf(f, "\t%lf\t%lf\t%lf", usage_mean[t], usage_sd[t], (double)dominant_count[t] / (double)n_boot);
+        for (int j = 0; j < n_q; j++) fprintf(f, "\t%lf", usage_q[(int64_t)j * r->n_tx + t]);
+        fprintf(f, "\n");
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
 
 /* the rows of .saturation / .gsaturation: n names, per fraction ncol columns col[j] = [n_fractions][n] */

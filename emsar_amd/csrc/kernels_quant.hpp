@@ -63,6 +63,22 @@ __global__ __launch_bounds__(1024) void k_quant_sums(int n, const int32_t *__res
     if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 
+// The bitonic network over a tile [Bp][1 << cs] in LDS, all columns in lockstep, ascending down every column; called by all 256
+// lanes of the workgroup after the barrier that follows the tile's stores, ends behind a barrier.  (k_boot_quantiles, k_iso_quantiles)
+__device__ __forceinline__ void quant_sort_tile(double *smem, int Bp, int cs) {
+    const int cmask = (1 << cs) - 1;
+    for (int size = 2; size <= Bp; size <<= 1)
+        for (int j = size >> 1; j > 0; j >>= 1) {
+            for (int k = threadIdx.x; k < ((Bp >> 1) << cs); k += 256) {
+                const int p = k >> cs, c = k & cmask;
+                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
+                const double a = smem[(i << cs) + c], b = smem[(l << cs) + c];
+                if ((a > b) == ((i & size) == 0)) { smem[(i << cs) + c] = b; smem[(l << cs) + c] = a; }
+            }
+            __syncthreads();
+        }
+}
+
 //   x [B][n] the held replicates, sums [B] their TPM denominators, q [n_q]; out_f, out_t [n_q][n]
 //   Bp = B rounded up to a power of two, cs = log2 of the tile's columns; dynamic LDS: (Bp << cs) doubles
 __global__ __launch_bounds__(256) void k_boot_quantiles(int64_t n, int B, int Bp, int cs, const double *__restrict__ x,
@@ -83,16 +99,7 @@ __global__ __launch_bounds__(256) void k_boot_quantiles(int64_t n, int B, int Bp
             smem[k] = v;
         }
         __syncthreads();
-        for (int size = 2; size <= Bp; size <<= 1)
-            for (int j = size >> 1; j > 0; j >>= 1) {
-                for (int k = threadIdx.x; k < ((Bp >> 1) << cs); k += 256) {
-                    const int p = k >> cs, c = k & cmask;
-                    const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
-                    const double a = smem[(i << cs) + c], b = smem[(l << cs) + c];
-                    if ((a > b) == ((i & size) == 0)) { smem[(i << cs) + c] = b; smem[(l << cs) + c] = a; }
-                }
-                __syncthreads();
-            }
+        quant_sort_tile(smem, Bp, cs);
         double *out = pass ? out_t : out_f;
         for (int64_t k = threadIdx.x; k < ((int64_t)n_q << cs); k += 256) {
             const int qi = (int)(k >> cs), c = (int)(k & cmask);

@@ -1,11 +1,13 @@
 // resample.hpp -- the resampling driver behind include/emsar_hip.h: the Poisson bootstrap, its gene-level statistics and quantiles, the
 // binomial depth subsampling, and the gene map with its sums.  Part of emsar_hip.hip's translation unit, included at its end: it uses
-// the context, ensure_sets, layout_weights, solve_impl and the kernels (kernels_boot.hpp, kernels_genes.hpp, kernels_quant.hpp).
+// the context, ensure_sets, layout_weights, solve_impl and the kernels (kernels_boot.hpp, kernels_genes.hpp, kernels_quant.hpp,
+// kernels_isoforms.hpp).
 // One call = one BootRun:  plan memory (held replicates first, then the batch size) -> allocate
 //                          for each fraction:  zero the accumulators
 //                              for each batch:  draw -> solve_sets -> solve_streamed -> reduce -> copy_out
 //                              finish_round (means / sd, gene outputs, depth_mean);  quantiles (if the replicates are held)
 //                          fill the statistics; put the context back (BootRestore)
+// The isoform usage (emsar_hip_isoform_usage, emsar_hip_bootstrap_isoforms) rides on the same stages: reduce and quantiles.
 
 namespace {
 
@@ -88,6 +90,21 @@ int launch_gene_sums(emsar_hip_ctx *ctx, const double *x, int64_t ncol, double *
     return EMSAR_HIP_OK;
 }
 
+// The dominant isoform of every gene in ncol (<= 65535) rows x[ncol][n_tx] with their gene sums gsum[ncol][n_genes] (launch_gene_sums
+// before, same stream) into dom[ncol][n_genes], library indices or -1; part_v / part_i hold ncol * n_gene_chunks partials (may be
+// null when no gene has more than one chunk).
+int launch_iso_dominant(emsar_hip_ctx *ctx, const double *x, int64_t ncol, const double *gsum, int32_t *dom, double *part_v, int32_t *part_i) {
+    if (ctx->genes.n_gene_chunks > 0)
+        hipLaunchKernelGGL(k_iso_dominant, dim3((unsigned)grid_for(ctx->genes.n_gene_chunks, 256), (unsigned)ncol), dim3(256), 0, ctx->stream,
+                           ctx->genes.n_gene_chunks, ctx->genes.d_chunk_beg, ctx->genes.d_chunk_out, ctx->genes.d_gene_tx, x, (int64_t)ctx->n_tx, gsum, dom,
+                           (int64_t)ctx->genes.n_genes, part_v, part_i);
+    if (ctx->genes.n_gene_multi > 0)
+        hipLaunchKernelGGL(k_iso_dominant_finish, dim3((unsigned)grid_for(ctx->genes.n_gene_multi, 256), (unsigned)ncol), dim3(256), 0, ctx->stream,
+                           ctx->genes.n_gene_multi, ctx->genes.d_gene_multi, part_v, part_i, ctx->genes.n_gene_chunks, gsum, dom, (int64_t)ctx->genes.n_genes);
+    HIPCHK(hipGetLastError());
+    return EMSAR_HIP_OK;
+}
+
 // What a call draws and where its results go.  fractions null: the Poisson bootstrap, one round.  Else the depth subsampling: one round
 // per fraction f_k with w_c ~ Binomial(R_c, f_k), every replicate scaled to its own depth, the outputs of round k at [k][...].
 // Outputs that are null are not returned; gene_mean non-null asks for the gene statistics (all null = none).
@@ -102,6 +119,9 @@ struct BootPlan {
     const double *q = nullptr;
     double *fpkm_q = nullptr, *tpm_q = nullptr, *gene_fpkm_q = nullptr, *gene_tpm_q = nullptr;     // [n_q][n_tx], [n_q][n_genes]
     double *replicate_sums = nullptr;    // [n_rep] S_b
+    // isoform usage (bootstrap only, needs the gene map): non-null asks for the replicates' gene sums, usage and dominant isoforms;
+    // its usage_q needs n_q > 0
+    const emsar_isoform_outputs *iso = nullptr;
 };
 struct BootTimes {
     int32_t batch = 0, unconverged = 0, passes_max = 0;
@@ -120,12 +140,13 @@ struct BootRun {
     const int32_t first, n_rep;
     const BootPlan &plan;
     // switches
-    const bool genes, binomial, hold;    // gene statistics; binomial draws (subsampling); all replicates held on the device (quantiles)
+    const bool genes, iso, gene_sums;    // gene statistics wanted; isoform usage wanted; either: the replicates' gene sums are needed
+    const bool binomial, hold;           // binomial draws (subsampling); all replicates held on the device (quantiles)
     bool use_sets = false;               // the closed form and the resident sets, all replicates of a batch in one launch per class
     bool need_stream = false;            // a streaming solve per replicate for what the set solver does not cover
     // sizes
     const int n;                         // transcripts
-    const int64_t n_rows, ng;            // rows; genes (0 without gene statistics)
+    const int64_t n_rows, ng;            // rows; genes (0 when no gene sums are needed)
     const unsigned gn;                   // workgroups of a 256-thread kernel over the transcripts
     int64_t n_rw = 0, slot_stride = 0;   // row_w entries of the resident sets; one replicate's [row_w | usum] block
     int64_t n_sets = 0, n_gu = 0;        // resident sets; their transcripts, all sets together
@@ -142,6 +163,10 @@ struct BootRun {
     DevBuf<double> d_q, d_qsums;                    // quantiles: [n_q] the probabilities, [n_rep] S_b added in the caller's order
     DevBuf<double> d_qout;                          // [2][n_q][n] then [2][n_q][ng]: FPKM and TPM quantiles of transcripts, then of genes
     DevBuf<int32_t> d_libof;                        // [n] caller tid -> library index, null = the same
+    DevBuf<int32_t> d_dom, d_dpart_i;               // isoforms: [batch][ng] dominant isoform of the replicates' genes, [batch][n_gchunk] chunk partials
+    DevBuf<double> d_dpart_v;                       // [batch][n_gchunk]
+    DevBuf<double> d_uacc, d_uq;                    // [2][n] Welford accumulators of the usage; [n_q][n] its quantiles
+    DevBuf<int32_t> d_ucnt;                         // [n] replicates in which the transcript is its gene's dominant isoform
     std::vector<int32_t> h_wb;           // host staging: [batch][n_rows]
     std::vector<double> h_th;            // [n] a streaming solve's result
     std::vector<SetStat> h_bstat;        // [batch][n_sets]
@@ -156,14 +181,14 @@ struct BootRun {
 
     BootRun(emsar_hip_ctx *c, const emsar_em_params &par, uint64_t seed_, int32_t first_, int32_t n_rep_, const BootPlan &plan_)
         : ctx(c), p(par), seed(seed_), first(first_), n_rep(n_rep_), plan(plan_),
-          genes(plan_.gene_mean != nullptr), binomial(plan_.fractions != nullptr), hold(plan_.n_q > 0), n(c->n_tx), n_rows(c->n_rows),
-          ng(genes ? c->genes.n_genes : 0), gn((unsigned)grid_for(c->n_tx, 256)), guard(c) {}
+          genes(plan_.gene_mean != nullptr), iso(plan_.iso != nullptr), gene_sums(genes || iso), binomial(plan_.fractions != nullptr),
+          hold(plan_.n_q > 0), n(c->n_tx), n_rows(c->n_rows), ng(gene_sums ? c->genes.n_genes : 0), gn((unsigned)grid_for(c->n_tx, 256)), guard(c) {}
     ~BootRun() { for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev); }
 
     // the batch's theta, S_b and gene sums: the batch buffers, or the batch's rows of the held ones
     double *th_rows(int64_t done) const { return d_thb + (hold ? done * n : 0); }
     double *sum_rows(int64_t done) const { return d_sums + (hold ? done : 0); }
-    double *gene_rows(int64_t done) const { return genes ? d_gsum + (hold ? done * ng : 0) : nullptr; }
+    double *gene_rows(int64_t done) const { return gene_sums ? d_gsum + (hold ? done * ng : 0) : nullptr; }
     int numeric(const char *sub, const char *boot) { ctx->err = binomial ? sub : boot; return EMSAR_HIP_ERR_NUMERIC; }
     // device time since e[0] was recorded, added to acc (the host waits for the stream)
     int lap(double &acc) {
@@ -176,13 +201,14 @@ struct BootRun {
     // half of the free device memory; they are allocated here, before anything is launched
     int alloc_held() {
         t.held_bytes = 8 * (int64_t)n_rep * ((int64_t)n + 1 + ng);
-        const int64_t T = n, G = ng, nq = plan.n_q;
+        const int64_t T = n, G = genes ? ng : 0, nq = plan.n_q;      // G: genes with quantile outputs
+        const bool uq = iso && plan.iso->usage_q;
         const auto &m = tid_map(ctx);
         const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !m.empty();
-        const int64_t need = t.held_bytes + 8 * (int64_t)n_rep + 8 * nq + 16 * nq * (T + G) + (remap ? 4 * T : 0);
+        const int64_t need = t.held_bytes + 8 * (int64_t)n_rep + 8 * nq + 16 * nq * (T + G) + (remap ? 4 * T : 0) + (uq ? 8 * nq * T : 0);
         if ((uint64_t)need > (uint64_t)(free_device_bytes() / 2)) { ctx->err = "bootstrap quantiles: the replicates do not fit half of the free device memory"; return EMSAR_HIP_ERR_OOM; }
-        if (d_thb.alloc((size_t)(n_rep * T)) != hipSuccess || d_sums.alloc((size_t)n_rep) != hipSuccess || (genes && d_gsum.alloc((size_t)(n_rep * G)) != hipSuccess) || d_q.alloc((size_t)nq) != hipSuccess ||
-            d_qout.alloc((size_t)(2 * nq * (T + G))) != hipSuccess || d_qsums.alloc((size_t)n_rep) != hipSuccess || (remap && d_libof.alloc((size_t)T) != hipSuccess)) {
+        if (d_thb.alloc((size_t)(n_rep * T)) != hipSuccess || d_sums.alloc((size_t)n_rep) != hipSuccess || (gene_sums && d_gsum.alloc((size_t)(n_rep * ng)) != hipSuccess) || d_q.alloc((size_t)nq) != hipSuccess ||
+            d_qout.alloc((size_t)(2 * nq * (T + G))) != hipSuccess || (uq && d_uq.alloc((size_t)(nq * T)) != hipSuccess) || d_qsums.alloc((size_t)n_rep) != hipSuccess || (remap && d_libof.alloc((size_t)T) != hipSuccess)) {
             (void)hipGetLastError();
             ctx->err = "bootstrap quantiles: device allocation of the held replicates failed";
             return EMSAR_HIP_ERR_OOM;
@@ -205,9 +231,10 @@ struct BootRun {
         slot_stride = n_rw + n;
         n_sets = use_sets ? ctx->sets.RS.n_resident() : 0;
         if (use_sets) for (int c = 0; c < emsar::kSetClasses; c++) for (const auto &d : ctx->sets.RS.desc[c]) n_gu += d.n_t;
-        n_gchunk = genes && ctx->genes.n_gene_multi > 0 ? ctx->genes.n_gene_chunks : 0;
+        n_gchunk = gene_sums && ctx->genes.n_gene_multi > 0 ? ctx->genes.n_gene_chunks : 0;
         // (a quantile call's theta, S_b and gene sums live in the held buffers, allocated before: not part of a batch, and what is free is what they left)
-        const int64_t per_rep = 8 * (slot_stride + n_gu + (hold ? 0 : n + 1 + ng) + n_gchunk) + (need_stream ? 4 * n_rows : 0) + (int64_t)sizeof(SetStat) * n_sets;
+        const int64_t per_rep = 8 * (slot_stride + n_gu + (hold ? 0 : n + 1 + ng) + n_gchunk) + (need_stream ? 4 * n_rows : 0) + (int64_t)sizeof(SetStat) * n_sets +
+                                (iso ? 4 * ng + 12 * n_gchunk : 0);
         const int64_t budget = std::min<int64_t>((int64_t)(free_device_bytes() / 4), (int64_t)2 << 30);
         batch = std::max<int64_t>(1, budget / std::max<int64_t>(per_rep, 1));
         if (const char *env = getenv("EMSAR_HIP_BOOT_BATCH")) { if (atoi(env) >= 1) batch = atoi(env); }
@@ -220,8 +247,13 @@ struct BootRun {
         HIPCHK(d_slots.alloc((size_t)(batch * slot_stride))); HIPCHK(d_gu.alloc((size_t)(batch * n_gu)));
         if (!hold) { HIPCHK(d_thb.alloc((size_t)(batch * n))); HIPCHK(d_sums.alloc((size_t)batch)); }
         HIPCHK(d_acc4.alloc((size_t)(4 * (int64_t)n)));
-        if (genes && !hold) HIPCHK(d_gsum.alloc((size_t)(batch * ng)));
+        if (gene_sums && !hold) HIPCHK(d_gsum.alloc((size_t)(batch * ng)));
         if (n_gchunk) HIPCHK(d_gpart.alloc((size_t)(batch * n_gchunk)));
+        if (iso) {
+            HIPCHK(d_dom.alloc((size_t)(batch * ng)));
+            if (n_gchunk) { HIPCHK(d_dpart_v.alloc((size_t)(batch * n_gchunk))); HIPCHK(d_dpart_i.alloc((size_t)(batch * n_gchunk))); }
+            HIPCHK(d_uacc.alloc((size_t)(2 * (int64_t)n))); HIPCHK(d_ucnt.alloc((size_t)n));
+        }
         if (genes) HIPCHK(d_gacc4.alloc((size_t)(4 * ng)));
         if (binomial) {
             HIPCHK(d_ndrawn.alloc((size_t)batch));
@@ -320,9 +352,15 @@ struct BootRun {
         hipLaunchKernelGGL(k_boot_sums, dim3((unsigned)nb), dim3(1024), 0, ctx->stream, n, thb, sums);
         hipLaunchKernelGGL(k_boot_accum, dim3(gn), dim3(256), 0, ctx->stream, n, (int)nb, done, thb, sums, d_acc4);
         HIPCHK(hipGetLastError());
-        if (genes) {   // the replicates' gene sums, then the same Welford step on them (gene TPM_b = G_b * 1e6 / S_b)
-            if ((rc = launch_gene_sums(ctx, thb, nb, gene_rows(done), d_gpart))) return rc;
+        if (gene_sums && (rc = launch_gene_sums(ctx, thb, nb, gene_rows(done), d_gpart))) return rc;
+        if (genes) {   // the same Welford step on the replicates' gene sums (gene TPM_b = G_b * 1e6 / S_b)
             hipLaunchKernelGGL(k_boot_accum, dim3((unsigned)grid_for(ng, 256)), dim3(256), 0, ctx->stream, (int)ng, (int)nb, done, gene_rows(done), sums, d_gacc4);
+            HIPCHK(hipGetLastError());
+        }
+        if (iso && n > 0) {   // the replicates' dominant isoforms, then usage and dominance reduced per transcript
+            if ((rc = launch_iso_dominant(ctx, thb, nb, gene_rows(done), d_dom, d_dpart_v, d_dpart_i))) return rc;
+            hipLaunchKernelGGL(k_iso_accum, dim3(gn), dim3(256), 0, ctx->stream, n, (int)nb, done, ctx->genes.d_gene_of_lib, thb, gene_rows(done), d_dom, ng,
+                               d_uacc, d_ucnt);
             HIPCHK(hipGetLastError());
         }
         // (after the launches: a copy into pageable memory makes the host wait for the stream)
@@ -365,6 +403,17 @@ struct BootRun {
             put(plan.gene_mean, 0, ng, false); put(plan.gene_sd, 1, ng, true); put(plan.gene_tpm_mean, 2, ng, false); put(plan.gene_tpm_sd, 3, ng, true);
         }
         if (plan.depth_mean) plan.depth_mean[fk] = (double)depth_sum / (double)n_rep;
+        if (iso) {   // usage is in [0, 1] whenever theta is finite, which the check above has settled
+            const emsar_isoform_outputs &o = *plan.iso;
+            acc.resize((size_t)(2 * (int64_t)n));
+            HIPCHK(hipMemcpyAsync(acc.data(), d_uacc, acc.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+            if (o.dominant_count) HIPCHK(hipMemcpyAsync(o.dominant_count, d_ucnt, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            put(o.usage_mean, 0, n, false); put(o.usage_sd, 1, n, true);
+            if (o.usage_mean) from_lib(ctx, o.usage_mean);
+            if (o.usage_sd) from_lib(ctx, o.usage_sd);
+            if (o.dominant_count) from_lib(ctx, o.dominant_count);
+        }
         return EMSAR_HIP_OK;
     }
     // quantiles over the held replicates: transcripts, then genes
@@ -384,8 +433,16 @@ struct BootRun {
         if (genes && ng > 0)
             hipLaunchKernelGGL(k_boot_quantiles, dim3((unsigned)((ng + (1 << cs) - 1) >> cs)), dim3(256), lds, ctx->stream, ng, (int)n_rep, Bp, cs,
                                d_gsum, d_qsums, (int)nq, d_q, d_gq, d_gq + nq * ng);
+        const bool uq = iso && plan.iso->usage_q;
+        if (uq && n > 0)
+            hipLaunchKernelGGL(k_iso_quantiles, dim3((unsigned)(((int64_t)n + (1 << cs) - 1) >> cs)), dim3(256), lds, ctx->stream, (int64_t)n, (int)n_rep,
+                               Bp, cs, ctx->genes.d_gene_of_lib, d_thb, d_gsum, ng, (int)nq, d_q, d_uq);
         HIPCHK(hipGetLastError());
         if ((rc = lap(t.quantile_ms))) return rc;
+        if (uq) {
+            HIPCHK(hipMemcpy(plan.iso->usage_q, d_uq, (size_t)(nq * n) * 8, hipMemcpyDeviceToHost));
+            for (int64_t k = 0; k < nq; k++) from_lib(ctx, plan.iso->usage_q + k * n);
+        }
         HIPCHK(hipMemcpy(plan.fpkm_q, d_qout, (size_t)(nq * n) * 8, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(plan.tpm_q, d_qout + nq * n, (size_t)(nq * n) * 8, hipMemcpyDeviceToHost));
         for (int64_t k = 0; k < nq; k++) { from_lib(ctx, plan.fpkm_q + k * n); from_lib(ctx, plan.tpm_q + k * n); }
@@ -403,6 +460,7 @@ struct BootRun {
             depth_sum = 0;
             HIPCHK(hipMemsetAsync(d_acc4, 0, (size_t)4 * n * 8, ctx->stream));
             if (genes) HIPCHK(hipMemsetAsync(d_gacc4, 0, (size_t)4 * ng * 8, ctx->stream));
+            if (iso) { HIPCHK(hipMemsetAsync(d_uacc, 0, (size_t)2 * n * 8, ctx->stream)); HIPCHK(hipMemsetAsync(d_ucnt, 0, (size_t)n * 4, ctx->stream)); }
             for (int64_t done = 0; done < n_rep; ) {
                 const int64_t nb = std::min<int64_t>(batch, n_rep - done);
                 unconv.assign((size_t)nb, 0);
@@ -436,6 +494,8 @@ int run_plan(emsar_hip_ctx *ctx, const emsar_em_params *pp, uint64_t seed, int32
 
 bool replicate_range_ok(int32_t first, int32_t n) { return n >= 1 && first >= 0 && (int64_t)first + (int64_t)n <= (int64_t)INT32_MAX + 1; }
 bool sub_fraction_ok(double f) { return std::isfinite(f) && f > 0.0 && f <= 1.0; }
+// isoform usage is defined on non-negative finite values
+bool iso_values_ok(const double *x, int64_t cnt) { return std::all_of(x, x + cnt, [](double v) { return std::isfinite(v) && v >= 0.0; }); }
 bool quantile_args_ok(int32_t n_q, const double *q) {
     return n_q >= 1 && q && std::all_of(q, q + n_q, [](double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; });
 }
@@ -562,12 +622,13 @@ int emsar_hip_set_gene_map(emsar_hip_ctx *ctx, int32_t n_genes, const int32_t *g
         for (int32_t t = 0; t < n; t++) if (gene_of_tx[t] >= 0) gp[(size_t)gene_of_tx[t] + 1]++;
         for (int32_t g = 0; g < n_genes; g++) gp[(size_t)g + 1] += gp[(size_t)g];
         const int64_t m = gp[(size_t)n_genes];
-        std::vector<int32_t> tx((size_t)m), chunk_beg, chunk_out, multi;
+        std::vector<int32_t> tx((size_t)m), chunk_beg, chunk_out, multi, of_lib((size_t)n);
         std::vector<int64_t> fill(gp.begin(), gp.end() - 1);
         const auto &map = tid_map(ctx);
         const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !map.empty();
         for (int32_t t = 0; t < n; t++)
             if (gene_of_tx[t] >= 0) tx[(size_t)fill[(size_t)gene_of_tx[t]]++] = remap ? map[(size_t)t] : t;
+        for (int32_t t = 0; t < n; t++) of_lib[(size_t)(remap ? map[(size_t)t] : t)] = gene_of_tx[t];
         for (int32_t g = 0; g < n_genes; g++) {
             const int64_t len = gp[(size_t)g + 1] - gp[(size_t)g];
             const int64_t nch = std::max<int64_t>(1, (len + kGeneChunk - 1) / kGeneChunk);     // an empty gene: one empty chunk, sum 0
@@ -581,17 +642,19 @@ int emsar_hip_set_gene_map(emsar_hip_ctx *ctx, int32_t n_genes, const int32_t *g
         chunk_beg.push_back((int32_t)m);
         const size_t nc = chunk_out.size();
         std::vector<int32_t> blk;
-        blk.reserve((size_t)m + 2 * nc + 1 + multi.size());
+        blk.reserve((size_t)m + 2 * nc + 1 + multi.size() + (size_t)n);
         blk.insert(blk.end(), tx.begin(), tx.end());
         blk.insert(blk.end(), chunk_beg.begin(), chunk_beg.end());
         blk.insert(blk.end(), chunk_out.begin(), chunk_out.end());
         blk.insert(blk.end(), multi.begin(), multi.end());
+        blk.insert(blk.end(), of_lib.begin(), of_lib.end());
         GeneMap G;                   // moved into the context when it is complete
         HIPCHK(G.d_gene_blk.upload(blk.data(), blk.size()));
         G.d_gene_tx = G.d_gene_blk;
         G.d_chunk_beg = G.d_gene_tx + m;
         G.d_chunk_out = G.d_chunk_beg + nc + 1;
         G.d_gene_multi = G.d_chunk_out + nc;
+        G.d_gene_of_lib = G.d_gene_multi + multi.size();
         G.n_genes = n_genes; G.n_gene_chunks = (int64_t)nc; G.n_gene_multi = (int64_t)multi.size() / 3;
         G.have_genes = true;
         ctx->genes = std::move(G);
@@ -625,6 +688,120 @@ int emsar_hip_gene_sums(emsar_hip_ctx *ctx, int32_t n_cols, const double *tx_val
         }
     } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
     return EMSAR_HIP_OK;
+}
+
+// ---- isoform usage --------------------------------------------------------------------------------------------------------------
+int emsar_hip_isoform_usage(emsar_hip_ctx *ctx, int32_t n_cols, const double *tx_values, double *usage_out, int32_t *dominant_out) {
+    if (!ctx) return EMSAR_HIP_ERR_ARG;
+    if (!ctx->have_structure || !ctx->genes.have_genes) return EMSAR_HIP_ERR_STATE;
+    if (n_cols < 1 || !tx_values || !usage_out) return EMSAR_HIP_ERR_ARG;
+    const int64_t n = ctx->n_tx, ng = ctx->genes.n_genes, nc = ctx->genes.n_gene_multi > 0 ? ctx->genes.n_gene_chunks : 0;
+    if (!iso_values_ok(tx_values, (int64_t)n_cols * n)) return EMSAR_HIP_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t cb = std::min<int64_t>(n_cols, 65535);        // columns per launch (grid y)
+    DevBuf<double> d_x, d_gs, d_part, d_u, d_pv;
+    DevBuf<int32_t> d_dom, d_pi;
+    HIPCHK(d_x.alloc((size_t)(cb * n)));
+    HIPCHK(d_gs.alloc((size_t)(cb * ng)));
+    HIPCHK(d_u.alloc((size_t)(cb * n)));
+    if (nc) HIPCHK(d_part.alloc((size_t)(cb * nc)));
+    if (dominant_out) {
+        HIPCHK(d_dom.alloc((size_t)(cb * ng)));
+        if (nc) { HIPCHK(d_pv.alloc((size_t)(cb * nc))); HIPCHK(d_pi.alloc((size_t)(cb * nc))); }
+    }
+    try {
+        std::vector<double> tmp;
+        std::vector<int32_t> caller_of;                         // library index -> caller tid, empty = the same
+        const auto &m = tid_map(ctx);
+        if (dominant_out && ctx->layout == EMSAR_LAYOUT_TILED && !m.empty()) {
+            caller_of.resize(m.size());
+            for (size_t t = 0; t < m.size(); t++) caller_of[(size_t)m[t]] = (int32_t)t;
+        }
+        for (int64_t c0 = 0; c0 < n_cols; c0 += cb) {
+            const int64_t k = std::min<int64_t>(cb, n_cols - c0);
+            for (int64_t j = 0; j < k; j++) {
+                const double *col = to_lib(ctx, tx_values + (c0 + j) * n, tmp);
+                HIPCHK(hipMemcpy(d_x + j * n, col, (size_t)n * 8, hipMemcpyHostToDevice));
+            }
+            int rc = launch_gene_sums(ctx, d_x, k, d_gs, d_part);
+            if (rc) return rc;
+            if (n > 0)
+                hipLaunchKernelGGL(k_iso_usage, dim3((unsigned)grid_for(n, 256), (unsigned)k), dim3(256), 0, ctx->stream, (int)n, ctx->genes.d_gene_of_lib,
+                                   d_x, d_gs, ng, d_u);
+            HIPCHK(hipGetLastError());
+            if (dominant_out && (rc = launch_iso_dominant(ctx, d_x, k, d_gs, d_dom, d_pv, d_pi))) return rc;
+            HIPCHK(hipMemcpyAsync(usage_out + c0 * n, d_u, (size_t)(k * n) * 8, hipMemcpyDeviceToHost, ctx->stream));
+            if (dominant_out) HIPCHK(hipMemcpyAsync(dominant_out + c0 * ng, d_dom, (size_t)(k * ng) * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            for (int64_t j = 0; j < k; j++) from_lib(ctx, usage_out + (c0 + j) * n);
+            if (!caller_of.empty())
+                for (int64_t i = c0 * ng; i < (c0 + k) * ng; i++) if (dominant_out[i] >= 0) dominant_out[i] = caller_of[(size_t)dominant_out[i]];
+        }
+    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+    return EMSAR_HIP_OK;
+}
+
+int emsar_hip_isoform_usage_host(int32_t n_tx, int32_t n_genes, const int32_t *gene_of_tx, int32_t n_cols, const double *tx_values,
+                                 double *usage_out, int32_t *dominant_out) {
+    if (n_tx < 0 || n_genes < 1 || (!gene_of_tx && n_tx > 0) || n_cols < 1 || (n_tx > 0 && (!tx_values || !usage_out))) return EMSAR_HIP_ERR_ARG;
+    for (int32_t t = 0; t < n_tx; t++) if (gene_of_tx[t] < -1 || gene_of_tx[t] >= n_genes) return EMSAR_HIP_ERR_ARG;
+    if (!iso_values_ok(tx_values, (int64_t)n_cols * n_tx)) return EMSAR_HIP_ERR_ARG;
+    try {
+        // gene CSR by ascending tid, as set_gene_map builds it
+        std::vector<int64_t> gp((size_t)n_genes + 1, 0);
+        for (int32_t t = 0; t < n_tx; t++) if (gene_of_tx[t] >= 0) gp[(size_t)gene_of_tx[t] + 1]++;
+        for (int32_t g = 0; g < n_genes; g++) gp[(size_t)g + 1] += gp[(size_t)g];
+        std::vector<int32_t> tx((size_t)gp[(size_t)n_genes]);
+        std::vector<int64_t> fill(gp.begin(), gp.end() - 1);
+        for (int32_t t = 0; t < n_tx; t++) if (gene_of_tx[t] >= 0) tx[(size_t)fill[(size_t)gene_of_tx[t]]++] = t;
+        std::vector<double> gs((size_t)n_genes);
+        for (int32_t c = 0; c < n_cols; c++) {
+            const double *x = tx_values + (int64_t)c * n_tx;
+            for (int32_t g = 0; g < n_genes; g++) {
+                // chunks of kGeneChunk added left to right, then the chunk sums left to right; the first maximum by a strict >
+                double sum = 0.0, best = 0.0;
+                int32_t at = -1;
+                for (int64_t b = gp[(size_t)g]; b < gp[(size_t)g + 1]; b += kGeneChunk) {
+                    const int64_t e = std::min<int64_t>(b + kGeneChunk, gp[(size_t)g + 1]);
+                    double s = x[tx[(size_t)b]];
+                    for (int64_t i = b + 1; i < e; i++) s += x[tx[(size_t)i]];
+                    sum = b == gp[(size_t)g] ? s : sum + s;
+                    for (int64_t i = b; i < e; i++) if (at < 0 || x[tx[(size_t)i]] > best) { best = x[tx[(size_t)i]]; at = tx[(size_t)i]; }
+                }
+                gs[(size_t)g] = sum;
+                if (dominant_out) dominant_out[(int64_t)c * n_genes + g] = sum > 0.0 ? at : -1;
+            }
+            for (int32_t t = 0; t < n_tx; t++)
+                usage_out[(int64_t)c * n_tx + t] = gene_of_tx[t] >= 0 ? emsar::iso_usage(x[t], gs[(size_t)gene_of_tx[t]]) : 0.0;
+        }
+    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+    return EMSAR_HIP_OK;
+}
+
+int emsar_hip_bootstrap_isoforms(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t first_replicate, int32_t n_replicates,
+                                 int32_t n_q, const double *q, double *fpkm_mean, double *fpkm_sd, double *tpm_sd, double *replicates,
+                                 double *replicate_sums, double *fpkm_q, double *tpm_q, double *gene_fpkm_mean, double *gene_fpkm_sd,
+                                 double *gene_tpm_sd, double *gene_fpkm_q, double *gene_tpm_q, emsar_boot_stats *stats,
+                                 emsar_quantile_stats *qstats, const emsar_isoform_outputs *iso) {
+    if (!ctx) return EMSAR_HIP_ERR_ARG;
+    if (!ctx->have_sample || !ctx->genes.have_genes) return EMSAR_HIP_ERR_STATE;
+    if (!iso || n_q < 0 || !fpkm_mean || !fpkm_sd || !tpm_sd || !replicate_range_ok(first_replicate, n_replicates)) return EMSAR_HIP_ERR_ARG;
+    const int n_gene_stat = (gene_fpkm_mean != nullptr) + (gene_fpkm_sd != nullptr) + (gene_tpm_sd != nullptr);
+    BootPlan plan;
+    if (n_q == 0) {      // no quantiles: nothing is held, q and the quantile outputs are not looked at
+        if (iso->usage_q || (n_gene_stat != 0 && n_gene_stat != 3)) return EMSAR_HIP_ERR_ARG;
+    } else {
+        const int n_gene_out = n_gene_stat + (gene_fpkm_q != nullptr) + (gene_tpm_q != nullptr);
+        if (!fpkm_q || !tpm_q || n_replicates > emsar::kQuantMaxRep || !quantile_args_ok(n_q, q) || (n_gene_out != 0 && n_gene_out != 5)) return EMSAR_HIP_ERR_ARG;
+        plan.n_q = n_q; plan.q = q; plan.fpkm_q = fpkm_q; plan.tpm_q = tpm_q; plan.gene_fpkm_q = gene_fpkm_q; plan.gene_tpm_q = gene_tpm_q; plan.replicate_sums = replicate_sums;
+    }
+    plan.fpkm_mean = fpkm_mean; plan.fpkm_sd = fpkm_sd; plan.tpm_sd = tpm_sd; plan.replicates = replicates;
+    plan.gene_mean = gene_fpkm_mean; plan.gene_sd = gene_fpkm_sd; plan.gene_tpm_sd = gene_tpm_sd;
+    plan.iso = iso;
+    BootTimes t;
+    const int rc = run_bootstrap(ctx, p, seed, first_replicate, n_replicates, plan, stats, &t);
+    if (rc == EMSAR_HIP_OK && qstats) { memset(qstats, 0, sizeof(*qstats)); qstats->n_quantiles = n_q; qstats->held_bytes = t.held_bytes; qstats->quantile_ms = t.quantile_ms; }
+    return rc;
 }
 
 int emsar_hip_bootstrap_weights(emsar_hip_ctx *ctx, uint64_t seed, int32_t replicate, int32_t *w_out) { return draw_one(ctx, seed, replicate, nullptr, w_out); }

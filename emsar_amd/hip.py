@@ -24,6 +24,7 @@ SYMBOLS = [
     "emsar_hip_set_gene_map", "emsar_hip_gene_sums", "emsar_hip_bootstrap_genes",
     "emsar_hip_subsample", "emsar_hip_subsample_weights", "emsar_hip_subsample_draw_host",
     "emsar_hip_bootstrap_quantiles", "emsar_hip_quantiles_host",
+    "emsar_hip_isoform_usage", "emsar_hip_isoform_usage_host", "emsar_hip_bootstrap_isoforms",
 ]
 
 
@@ -76,6 +77,11 @@ class QuantileStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class IsoformOutputs(C.Structure):
+    _fields_ = [("usage_mean", C.POINTER(C.c_double)), ("usage_sd", C.POINTER(C.c_double)), ("dominant_count", C.POINTER(C.c_int32)),
+                ("usage_q", C.POINTER(C.c_double))]
 
 
 class SetsInfo(C.Structure):
@@ -144,6 +150,9 @@ def load_library():
     L.emsar_hip_bootstrap_quantiles.argtypes = [vp, C.POINTER(EmParams), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, f64p] + [f64p] * 12 + [
         C.POINTER(BootStats), C.POINTER(QuantileStats)]
     L.emsar_hip_quantiles_host.argtypes = [C.c_int32, C.c_int64, f64p, C.c_int32, f64p, f64p]
+    L.emsar_hip_isoform_usage.argtypes = [vp, C.c_int32, f64p, f64p, i32p]
+    L.emsar_hip_isoform_usage_host.argtypes = [C.c_int32, C.c_int32, i32p, C.c_int32, f64p, f64p, i32p]
+    L.emsar_hip_bootstrap_isoforms.argtypes = L.emsar_hip_bootstrap_quantiles.argtypes + [C.POINTER(IsoformOutputs)]
     _lib = L
     return L
 
@@ -218,6 +227,29 @@ def quantiles_host(values, q):
     if rc != 0:
         raise EmsarHipError(rc, "quantiles_host")
     return out[:, 0] if one else out
+
+
+def isoform_usage_host(gene_of_tx, n_genes, cols, want_dominant=False):
+    """Host-only: the library's isoform usage (include/emsar_hip.h "isoform usage") of cols [n_cols][n_tx] (or [n_tx]) under the gene map
+    gene_of_tx (-1 = no gene) -> usage of the same shape; with want_dominant (usage, dominant [n_cols][n_genes] or [n_genes]: the
+    tid of every gene's dominant isoform, -1 for a gene whose sum is 0).  No GPU needed, the same function the device evaluates."""
+    L = load_library()
+    g = _arr(gene_of_tx, np.int32)
+    x = _arr(cols, np.float64)
+    one = x.ndim == 1
+    x = np.ascontiguousarray(np.atleast_2d(x))
+    if x.shape[1] != len(g):
+        raise ValueError("columns of n_tx values expected")
+    usage = np.zeros(x.shape)
+    dom = np.zeros((x.shape[0], max(int(n_genes), 1)), dtype=np.int32) if want_dominant else None
+    rc = L.emsar_hip_isoform_usage_host(len(g), int(n_genes), _p(g, C.c_int32), x.shape[0], _p(x, C.c_double), _p(usage, C.c_double),
+                                        _p(dom, C.c_int32))
+    if rc != 0:
+        raise EmsarHipError(rc, "isoform_usage_host")
+    if not want_dominant:
+        return usage[0] if one else usage
+    dom = dom[:, :max(int(n_genes), 0)]
+    return (usage[0], dom[0]) if one else (usage, dom)
 
 
 def layout_selfcheck_tiled(n_tx, row_ptr, col_idx, merge_rows=False):
@@ -382,6 +414,58 @@ class EmsarHip:
         k = self.n_genes
         out.update({key: (v[:, :k] if v.ndim == 2 else v[:k]) for key, v in gene.items()})
         out.update(replicates=reps, stats=st, qstats=qs)
+        return out
+
+    def isoform_usage(self, cols, want_dominant=False):
+        """Each transcript's share of its gene's sum (include/emsar_hip.h "isoform usage"): cols [n_cols][n_tx] -> usage [n_cols][n_tx],
+        a single vector [n_tx] -> [n_tx]; with want_dominant (usage, dominant [n_cols][n_genes] or [n_genes]: the tid of every
+        gene's dominant isoform, -1 for a gene whose sum is 0).  After set_gene_map."""
+        x = _arr(cols, np.float64)
+        one = x.ndim == 1
+        x = np.ascontiguousarray(np.atleast_2d(x))
+        if x.shape[1] != self.n_tx:
+            raise ValueError("columns of n_tx values expected")
+        usage = np.zeros(x.shape)
+        dom = np.zeros((x.shape[0], max(self.n_genes, 1)), dtype=np.int32) if want_dominant else None
+        self._chk(self._L.emsar_hip_isoform_usage(self._h, x.shape[0], _p(x, C.c_double), _p(usage, C.c_double), _p(dom, C.c_int32)),
+                  "isoform_usage")
+        if not want_dominant:
+            return usage[0] if one else usage
+        dom = dom[:, :self.n_genes]
+        return (usage[0], dom[0]) if one else (usage, dom)
+
+    def bootstrap_isoforms(self, n, seed, q=None, first=0, want_replicates=False, want_genes=False, max_iter=100000, accel=1, tol=1e-10,
+                           abs_floor=1e-6, check_every=8, count_floor=0.0, set_mode=0, zero_cut=0.0, abs_step=0.0, newton_after=0):
+        """bootstrap_quantiles() (q given) or bootstrap() / bootstrap_genes() (q None) plus the isoform statistics over the same
+        replicates: usage_mean, usage_sd ([n_tx]: mean and sample sd of each transcript's share of its gene), dominant_count ([n_tx] int32:
+        replicates in which it is its gene's dominant isoform) and, with q, usage_q ([n_q][n_tx]).  The other keys are those of
+        bootstrap_quantiles; without q there are no *_q, replicate_sums and qstats.  After set_gene_map."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        qa = None if q is None else np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        K, T, G = (0 if qa is None else len(qa)), self.n_tx, max(self.n_genes, 1)
+        Ka, na = max(K, 1), max(int(n), 1)
+        out = {k: np.zeros(T) for k in ("fpkm_mean", "fpkm_sd", "tpm_sd", "usage_mean", "usage_sd")}
+        out["dominant_count"] = np.zeros(max(T, 1), dtype=np.int32)
+        gene = {k: np.zeros(G) for k in ("gene_fpkm_mean", "gene_fpkm_sd", "gene_tpm_sd")} if want_genes else {}
+        if qa is not None:
+            out.update(fpkm_q=np.zeros((Ka, T)), tpm_q=np.zeros((Ka, T)), replicate_sums=np.zeros(na), usage_q=np.zeros((Ka, T)))
+            if want_genes:
+                gene.update(gene_fpkm_q=np.zeros((Ka, G)), gene_tpm_q=np.zeros((Ka, G)))
+        reps = np.zeros((n, T)) if (want_replicates and n > 0) else None
+        st, qs = BootStats(), QuantileStats()
+        d = lambda a: _p(a, C.c_double)
+        iso = IsoformOutputs(d(out["usage_mean"]), d(out["usage_sd"]), _p(out["dominant_count"], C.c_int32), d(out.get("usage_q")))
+        self._chk(self._L.emsar_hip_bootstrap_isoforms(
+            self._h, C.byref(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(n), K, d(qa), d(out["fpkm_mean"]), d(out["fpkm_sd"]),
+            d(out["tpm_sd"]), d(reps), d(out.get("replicate_sums")), d(out.get("fpkm_q")), d(out.get("tpm_q")), d(gene.get("gene_fpkm_mean")),
+            d(gene.get("gene_fpkm_sd")), d(gene.get("gene_tpm_sd")), d(gene.get("gene_fpkm_q")), d(gene.get("gene_tpm_q")),
+            C.byref(st), C.byref(qs), C.byref(iso)), "bootstrap_isoforms")
+        k = self.n_genes
+        out["dominant_count"] = out["dominant_count"][:T]
+        out.update({key: (v[:, :k] if v.ndim == 2 else v[:k]) for key, v in gene.items()})
+        out.update(replicates=reps, stats=st)
+        if qa is not None:
+            out["qstats"] = qs
         return out
 
     def bootstrap_weights(self, seed, replicate):

@@ -89,6 +89,8 @@ def lib():
         L.emsar_write_gfpkm.argtypes = [C.c_char_p, C.POINTER(Genes), f64p, f64p, f64p]
         L.emsar_write_gbootstrap.argtypes = [C.c_char_p, C.POINTER(Genes), f64p, f64p, f64p, f64p, f64p]
         L.emsar_write_segments.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Counts), C.POINTER(Model), f64p]
+        L.emsar_write_isoforms.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Genes), f64p, f64p, i32p, C.c_int, f64p, f64p, i32p,
+                                           C.c_int, f64p, f64p]
         _lib = L
     return _lib
 
@@ -101,6 +103,28 @@ def _np(ptr, n, dtype):
 
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def write_isoforms(path, tx_names, gene_names, gene_of_tx, fpkm, usage, dominant, n_boot=0, usage_mean=None, usage_sd=None,
+                   dominant_count=None, q=None, usage_q=None):
+    """.isoforms (emsar_write_isoforms): transcripts tx_names in genes gene_names through gene_of_tx (-1 = no gene, no line); fpkm, usage
+    [n_tx] and dominant [n_genes] as isoform_usage returns them; with n_boot > 0 also usage_mean, usage_sd, dominant_count [n_tx], with q
+    also usage_q [n_q][n_tx]."""
+    n_tx = len(tx_names)
+    names = (C.c_char_p * max(n_tx, 1))(*[s.encode() for s in tx_names])
+    r = Rsh(n_tx=n_tx, names=C.cast(names, C.POINTER(C.c_char_p)))
+    gmap = np.ascontiguousarray(gene_of_tx, dtype=np.int32)
+    g = HostRsh._genes_struct(gene_names)
+    g.n_tx, g.gene_of_tx = n_tx, gmap.ctypes.data_as(C.POINTER(C.c_int32))
+    f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+    i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+    dp = lambda a: None if a is None else _dp(a)
+    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    a = [f64(fpkm), f64(usage), i32(dominant), f64(usage_mean), f64(usage_sd), i32(dominant_count), f64(q), f64(usage_q)]
+    rc = lib().emsar_write_isoforms(path.encode(), C.byref(r), C.byref(g), dp(a[0]), dp(a[1]), ip(a[2]), int(n_boot), dp(a[3]), dp(a[4]), ip(a[5]),
+                                    0 if q is None else len(a[6]), dp(a[6]), dp(a[7]))
+    if rc != 0:
+        raise HostError("write_isoforms rc=%d" % rc)
 
 
 class HostRsh:

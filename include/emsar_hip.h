@@ -281,6 +281,56 @@ int emsar_hip_bootstrap_quantiles(emsar_hip_ctx *ctx, const emsar_em_params *p, 
 int emsar_hip_quantiles_host(int32_t n_rep, int64_t n, const double *values /* [n_rep][n] */,
                              int32_t n_q, const double *q, double *out /* [n_q][n] */);
 
+/* ---- isoform usage: each transcript's share of its gene, the dominant isoform, and their bootstrap -------------------------------
+ * Definitions (fixed, so that host and device agree bit for bit), for one column x[0 .. n_tx) of non-negative transcript values in
+ * caller numbering and the gene map of set_gene_map:
+ *     G_g     the gene sum of x in the order documented for gene_sums (chunks of 256 by ascending caller tid, left to right);
+ *     usage   u_t = G_g(t) > 0 ? x_t / G_g(t) : 0.0, one IEEE division; 0.0 for a transcript in no gene.  0 <= u_t <= 1 holds exactly
+ *             (a rounded sum of non-negative addends is never below an addend), and a gene's only transcript with x_t > 0 has
+ *             u_t == 1.0.  Usage is the same for FPKM and TPM -- the replicate's scale cancels -- so it is defined on theta and
+ *             reported once;
+ *     dominant  dom_g = the transcript of gene g with the largest x_t, the smallest caller tid among equal maxima; -1 when G_g == 0
+ *             (a gene without transcripts included).  Values are compared, not usages, so nothing is rounded.
+ * Over B bootstrap replicates, per transcript and reduced in replicate order (the results do not depend on the batch size, the layout
+ * or the library's own transcript numbering): usage_mean / usage_sd = the Welford recurrence of bootstrap's mean and sd on u_b,t
+ * (sample sd with n - 1, 0 for B = 1; subtract, divide, multiply and add rounded separately); dominant_count[t] = the number of
+ * replicates b with dom_b,g(t) == t; with n_q > 0, usage_q[k][t] = the q[k]-quantile of u_.,t by the definition of bootstrap_quantiles.
+ *   isoform_usage        n_cols >= 1 columns of n_tx values in caller order -> usage_out [n_cols][n_tx] and, unless NULL, dominant_out
+ *                        [n_cols][n_genes] (caller tid or -1).  ERR_STATE without a map; ERR_ARG for n_cols < 1, a NULL tx_values or
+ *                        usage_out, and for a negative or non-finite value (checked on the host before anything is uploaded).
+ *   isoform_usage_host   the same definition on the host, no HIP call, no context; the same checks plus those of set_gene_map
+ *                        (n_genes < 1, an id < -1 or >= n_genes: ERR_ARG).
+ *   bootstrap_isoforms   bootstrap_quantiles' arguments and outputs (the same bits; with gene outputs the same bits as bootstrap_genes
+ *                        too) plus the isoform statistics, so that one run of the replicates feeds every file of emsar-hip.  n_q == 0:
+ *                        q, the quantile outputs and qstats may be NULL, nothing is held on the device and n_replicates is not limited
+ *                        to 4096; the gene outputs are then the three statistics, all NULL or all given.  n_q > 0: the limits of
+ *                        bootstrap_quantiles apply, the held replicates always include the gene sums (held_bytes = 8 * n_replicates *
+ *                        (n_tx + 1 + n_genes)), and a call with usage_q adds 8 * n_q * n_tx bytes for it to what must fit half of
+ *                        the free device memory.  The replicates' gene sums are computed whether or not gene outputs are asked for.
+ *                        ERR_NUMERIC is decided on theta, as in bootstrap: a gene sum of finite values that itself overflows to +inf
+ *                        is not an error -- every isoform of that gene then has usage 0 in that replicate (x / inf) and the
+ *                        largest value is still its dominant isoform; gene outputs, when asked for, report it as bootstrap_genes does.
+ *                        ERR_STATE without a gene map or before upload_sample; ERR_ARG for iso == NULL, n_q < 0, usage_q given with
+ *                        n_q == 0, and for everything bootstrap_quantiles rejects; ERR_NUMERIC as solve.  The context is left as it was.
+ *                        The device time of the usage and dominance kernels is part of reduce_ms, that of the usage quantiles of
+ *                        quantile_ms. */
+typedef struct {
+    double  *usage_mean, *usage_sd;  /* [n_tx], may each be NULL */
+    int32_t *dominant_count;         /* [n_tx], may be NULL */
+    double  *usage_q;                /* [n_q][n_tx]; NULL iff not wanted; needs n_q > 0 */
+} emsar_isoform_outputs;
+int emsar_hip_isoform_usage(emsar_hip_ctx *ctx, int32_t n_cols, const double *tx_values /* n_cols * n_tx */,
+                            double *usage_out /* n_cols * n_tx */, int32_t *dominant_out /* n_cols * n_genes, or NULL */);
+int emsar_hip_isoform_usage_host(int32_t n_tx, int32_t n_genes, const int32_t *gene_of_tx /* n_tx, -1 = no gene */, int32_t n_cols,
+                                 const double *tx_values, double *usage_out, int32_t *dominant_out /* or NULL */);
+int emsar_hip_bootstrap_isoforms(emsar_hip_ctx *ctx, const emsar_em_params *p, uint64_t seed, int32_t first_replicate, int32_t n_replicates,
+                                 int32_t n_q, const double *q,
+                                 double *fpkm_mean, double *fpkm_sd, double *tpm_sd, double *replicates /* or NULL */,
+                                 double *replicate_sums /* or NULL */, double *fpkm_q, double *tpm_q,
+                                 double *gene_fpkm_mean, double *gene_fpkm_sd, double *gene_tpm_sd,
+                                 double *gene_fpkm_q, double *gene_tpm_q,
+                                 emsar_boot_stats *stats, emsar_quantile_stats *qstats, const emsar_isoform_outputs *iso);
+
 /* ---- binomial depth subsampling: the estimates at a fraction of the reads ---------------------------------------------------
  * "Did we sequence deep enough": keeping every read of the sample with probability f, independently (what samtools view -s does),
  * gives row c the weight w_c ~ Binomial(R_c, f) (a read-level row has R = 1, a segment the sum of its reads: the same law).  For

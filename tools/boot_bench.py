@@ -1,6 +1,6 @@
 """Cost of the Poisson bootstrap (emsar_hip_bootstrap) on two workloads; prints one JSON object.
 
-    python tools/boot_bench.py [--reps 100] [--cfg3-scale 0.1] [--cfg3-reps 10] [--genes | --subsample | --quantiles] [--out FILE]
+    python tools/boot_bench.py [--reps 100] [--cfg3-scale 0.1] [--cfg3-reps 10] [--genes | --subsample | --quantiles | --isoforms] [--out FILE]
 
   segment   bench.py's time_to_mle problem (same seeds): one solve, then B replicates in one call -- device time per stage (HIP events),
             wall time, ms per replicate against one solve, the batch size and the slowest set's passes
@@ -15,6 +15,9 @@
   --quantiles  instead: emsar_hip_bootstrap_genes against emsar_hip_bootstrap_quantiles (q = 0.025, 0.5, 0.975, gene outputs included) on both
             workloads, the generator's families as genes, same context and B, the calls alternated (two rounds) -- total_ms of both,
             quantile_ms (device time of the quantile stage) and held_bytes
+  --isoforms   instead: emsar_hip_bootstrap_quantiles against emsar_hip_bootstrap_isoforms (the same q and gene outputs, plus usage_mean,
+            usage_sd, dominant_count and usage_q) on both workloads, the generator's families as genes, same context and B, the calls
+            alternated (two rounds) -- reduce_ms, quantile_ms and total_ms of both
 Kernel-level times come from a separate `rocprofv3 --kernel-trace --stats` run of this script."""
 import argparse
 import json
@@ -98,6 +101,23 @@ def run_quantiles(dev, B, solve_kw, gene_of_tx, n_genes, seed=1, rounds=2):
     return out
 
 
+def run_isoforms(dev, B, solve_kw, gene_of_tx, n_genes, seed=1, rounds=2):
+    """bootstrap_quantiles vs bootstrap_isoforms over QUANTILES, gene outputs in both, the same B, alternated"""
+    dev.set_gene_map(gene_of_tx, n_genes)
+    dev.solve(**solve_kw)
+    dev.bootstrap_quantiles(min(B, 2), QUANTILES, seed, want_genes=True, **solve_kw)      # first calls: draw map, kernels loaded
+    dev.bootstrap_isoforms(min(B, 2), seed, q=QUANTILES, want_genes=True, **solve_kw)
+    out = {"replicates": B, "n_genes": int(n_genes), "q": QUANTILES, "bootstrap_quantiles": [], "bootstrap_isoforms": []}
+    for _ in range(rounds):
+        for name, call in (("bootstrap_quantiles", lambda: dev.bootstrap_quantiles(B, QUANTILES, seed, want_genes=True, **solve_kw)),
+                           ("bootstrap_isoforms", lambda: dev.bootstrap_isoforms(B, seed, q=QUANTILES, want_genes=True, **solve_kw))):
+            r = call()
+            st, qs = r["stats"], r["qstats"]
+            out[name].append({"total_ms": st.total_ms, "reduce_ms": st.reduce_ms, "quantile_ms": qs.quantile_ms, "batch": st.batch,
+                              "held_bytes": qs.held_bytes})
+    return out
+
+
 SUB_FRACTIONS = [0.1, 0.25, 0.5, 0.75, 1.0]
 
 
@@ -152,6 +172,7 @@ def main():
     ap.add_argument("--genes", action="store_true")
     ap.add_argument("--subsample", action="store_true")
     ap.add_argument("--quantiles", action="store_true")
+    ap.add_argument("--isoforms", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
     from emsar_amd import EmsarHip, synth
@@ -163,10 +184,11 @@ def main():
         seg_kw = dict(max_iter=200000, tol=1e-10)
         if a.subsample:
             out["segment"] = {"n_tx": int(n_tx), "segments": int(len(R)), **run_subsample(dev, a.reps, seg_kw)}
-        elif a.quantiles:
+        elif a.quantiles or a.isoforms:
             sizes = family_sizes(n_tx)
             fam = np.repeat(np.arange(len(sizes)), sizes).astype(np.int32)
-            out["segment"] = {"n_tx": int(n_tx), "segments": int(len(R)), **run_quantiles(dev, a.reps, seg_kw, fam, int(fam.max()) + 1)}
+            out["segment"] = {"n_tx": int(n_tx), "segments": int(len(R)),
+                              **(run_isoforms if a.isoforms else run_quantiles)(dev, a.reps, seg_kw, fam, int(fam.max()) + 1)}
         elif a.genes:
             sizes = family_sizes(n_tx)
             fam = np.repeat(np.arange(len(sizes)), sizes).astype(np.int32)
@@ -187,9 +209,9 @@ def main():
             info = {"scale": a.cfg3_scale, "reads": int(s["n_reads"]), "n_tx": int(s["n_tx"]), "segments": int(len(cw))}
             if a.subsample:
                 out["cfg3"] = {**info, **run_subsample(dev, a.cfg3_reps, kw)}
-            elif a.quantiles:
+            elif a.quantiles or a.isoforms:
                 _, fam = synth.make_families(s["n_tx"], cfg["seed"])
-                out["cfg3"] = {**info, **run_quantiles(dev, a.cfg3_reps, kw, fam, int(fam.max()) + 1)}
+                out["cfg3"] = {**info, **(run_isoforms if a.isoforms else run_quantiles)(dev, a.cfg3_reps, kw, fam, int(fam.max()) + 1)}
             elif a.genes:
                 _, fam = synth.make_families(s["n_tx"], cfg["seed"])
                 out["cfg3"] = {**info, **run_genes(dev, a.cfg3_reps, kw, {"families": (fam, int(fam.max()) + 1)})}
