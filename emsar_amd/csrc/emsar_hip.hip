@@ -26,6 +26,8 @@
 //   kernels_quant.hpp     k_boot_quantiles                       quantiles over the held replicates (bootstrap_quantiles)
 //   kernels_isoforms.hpp  k_iso_usage, k_iso_dominant, k_iso_accum, k_iso_quantiles   each transcript's share of its gene, the dominant
 //                         isoform, and their statistics over the replicates (isoform_usage, bootstrap_isoforms)
+//   kernels_fit.hpp       k_fit_rows, k_fit_tx, k_fit_tx_finish, k_fit_totals   per-row residuals of a theta and their attribution to
+//                         the transcripts over a transposed index (model_fit; driver: fit.hpp, shared arithmetic: fit_index.hpp)
 //   collapse.hip          read-level rows -> weighted segments (own translation unit)
 #include <hip/hip_runtime.h>
 
@@ -47,6 +49,7 @@
 #include "boot_rng.hpp"
 #include "internal.hpp"
 #include "devmem.hpp"
+#include "fit_index.hpp"
 
 #include "kernels_common.hpp"
 #include "kernels_csr.hpp"
@@ -58,6 +61,7 @@
 #include "kernels_genes.hpp"
 #include "kernels_quant.hpp"
 #include "kernels_isoforms.hpp"
+#include "kernels_fit.hpp"
 
 // ==================================================================================================
 // context
@@ -154,6 +158,7 @@ struct emsar_hip_ctx {
     TxVectors vec;
     GeneMap genes;
     AdjEuma euma;
+    FitDev fit;                  // model fit (fit.hpp): caller-order CSR and transposed index, built on first use, dropped by upload_structure
     // sample
     bool weighted = false;
     RowWeights rw;
@@ -232,7 +237,7 @@ inline int64_t stored_bytes(const emsar_hip_ctx *ctx) {
 // the structure and all that hangs on it: the sample, its sets, the gene map, the adjEUMA arrays
 void free_structure(emsar_hip_ctx *ctx) {
     ctx->sets = SetsDev(); ctx->rw = RowWeights();
-    ctx->genes = GeneMap(); ctx->euma = AdjEuma();
+    ctx->genes = GeneMap(); ctx->euma = AdjEuma(); ctx->fit = FitDev();
     ctx->lay = LayoutDev(); ctx->vec = TxVectors();
     std::vector<uint64_t>().swap(ctx->h_row_ptr); std::vector<int32_t>().swap(ctx->h_col); std::vector<int32_t>().swap(ctx->h_wgt);
     ctx->have_structure = ctx->have_sample = false;
@@ -1321,3 +1326,4 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 }  // extern "C"
 
 #include "resample.hpp"   // the resampling driver and its entry points: bootstrap, genes, quantiles, subsampling
+#include "fit.hpp"        // the model fit and its entry points (after resample.hpp: the gene step is launch_gene_sums)

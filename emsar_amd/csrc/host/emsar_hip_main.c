@@ -28,6 +28,10 @@
  * of the gene's FPKM and whether it is the gene's dominant isoform (emsar_hip_isoform_usage on the .fpkm column); with --bootstrap B also the
  * mean and sd of that share and how often the transcript dominates over the same B replicates, with --bootstrap-quantiles also the share's
  * quantiles (emsar_hip_bootstrap_isoforms, which gives the other bootstrap files the same bytes).  The other files do not change with it.
+ * --fit answers "does the fitted model explain the reads": <prefix>.<i>.fit holds, per transcript, its FPKM, the effective number of segments
+ * attributed to it, the Pearson chi2, the Poisson deviance and the missed reads of those segments (each segment's residual shared out by
+ * theta_t / S_c), the missed share of its expected reads and the segment that misses most, by the id .segments uses (emsar_hip_model_fit on
+ * the .fpkm column and the E of the solve); with --g2t also <prefix>.<i>.gfit per gene.  The other files do not change with it.
  * --subsample f1,f2,.. answers "was the sample sequenced deep enough": <prefix>.<i>.saturation holds, per transcript and fraction,
  * the mean and sd of FPKM (at the thinned depth) and TPM over --subsample-reps replicates in which every read is kept with
  * probability f (emsar_hip_subsample; seed --subsample-seed + i), with --g2t also <prefix>.<i>.gsaturation per gene.  The other
@@ -64,6 +68,7 @@ typedef struct {
     int sub_nf, sub_reps; double sub_f[64]; uint64_t sub_seed;   /* --subsample f1,.. (0 = off), --subsample-reps, --subsample-seed: sample i uses seed + i */
     const char *g2t;                  /* --g2t FILE (NULL = off) */
     int isoforms;                     /* --isoforms (needs --g2t) */
+    int fit;                          /* --fit */
     const emsar_genes *genes;         /* its gene map, read once by main() and shared read-only by the workers */
 } config;
 
@@ -245,6 +250,27 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
             if ((rc = emsar_write_isoforms(path, r, G, mean, iso_u, dom, 0, NULL, NULL, NULL, 0, NULL, NULL))) { fprintf(stderr, "can't write %s\n", path); goto done; }
         }
     }
+    /* ---- model fit (--fit): the residuals of the printed FPKM against the sample's segments, per transcript and per gene, on the device ---- */
+    if (cfg->fit) {
+        const size_t Ta = T > 0 ? T : 1, Ga = NG > 0 ? NG : 1;
+        double *fv = (double *)malloc(Ta * 8 * 4), *gv = G ? (double *)malloc(Ga * 8 * 4) : NULL;
+        int32_t *fw = (int32_t *)malloc(Ta * 4);
+        const emsar_fit_outputs fo = {NULL, NULL, NULL, fv, fv ? fv + T : NULL, fv ? fv + 2 * T : NULL, fv ? fv + 3 * T : NULL, fw,
+                                      gv, gv ? gv + NG : NULL, gv ? gv + 2 * NG : NULL, gv ? gv + 3 * NG : NULL};
+        if (!fv || !fw || (G && !gv)) rc = EMSAR_HOST_ERR_OOM;
+        else if ((rc = emsar_hip_model_fit(ctx, mean, m->E_solver, &fo, NULL)))
+            fprintf(stderr, "alnfile[%d]: model fit: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+        else {
+            snprintf(path, sizeof path, "%s/%s.%d.fit", cfg->outdir, cfg->prefix, i);
+            if ((rc = emsar_write_fit(path, r, mean, den, fo.tx_df, fo.tx_chi2, fo.tx_dev, fo.tx_miss, fw))) fprintf(stderr, "can't write %s\n", path);
+            else if (G) {
+                snprintf(path, sizeof path, "%s/%s.%d.gfit", cfg->outdir, cfg->prefix, i);
+                if ((rc = emsar_write_gfit(path, r, G, mean, den, fo.gene_df, fo.gene_chi2, fo.gene_dev, fo.gene_miss))) fprintf(stderr, "can't write %s\n", path);
+            }
+        }
+        free(fv); free(gv); free(fw);
+        if (rc) goto done;
+    }
     /* ---- Poisson bootstrap (--bootstrap B): its own file; .fpkm keeps the reference's column 3.  With --g2t the same replicates
      *      give the genes' sd as well (bootstrap_genes: the transcript outputs are the same bits as bootstrap's), and with --isoforms
      *      the usage statistics (bootstrap_isoforms: every other output is the same bits) ---- */
@@ -412,6 +438,9 @@ static void usage(const char *a0) {
             "      --isoforms            with --g2t: also write <prefix>.<i>.isoforms, per transcript its share of its gene's FPKM (usage) and whether\n"
             "                            it is the gene's dominant isoform; with --bootstrap the mean and sd of the usage and the frequency of\n"
             "                            dominance over the replicates, with --bootstrap-quantiles the usage's quantiles as well\n"
+            "      --fit                 also write <prefix>.<i>.fit: per transcript the effective number of segments, Pearson chi2, Poisson deviance and\n"
+            "                            missed reads of the fitted model on its segments, the missed share of its expected reads and its worst\n"
+            "                            segment (the id of .segments); with --g2t also <prefix>.<i>.gfit per gene\n"
             "      --gpus <n> / --devices <a,b,..> (-M: one worker per entry, ids may repeat) / --device <d> / --plain /\n"
             "      --stats-json <file> / -q / -v\n", a0);
 }
@@ -435,7 +464,7 @@ int main(int argc, char **argv) {
         {"count-floor", required_argument, 0, 1004}, {"streaming-only", no_argument, 0, 1005}, {"rsh-cache", optional_argument, 0, 1006}, {"zero-cut", required_argument, 0, 1007}, {"abs-step", required_argument, 0, 1008}, {"devices", required_argument, 0, 1009}, {"device-collapse", no_argument, 0, 1010}, {"no-deterministic", no_argument, 0, 1011},
         {"bootstrap", required_argument, 0, 1012}, {"bootstrap-seed", required_argument, 0, 1013}, {"g2t", required_argument, 0, 1014},
         {"subsample", required_argument, 0, 1015}, {"subsample-reps", required_argument, 0, 1016}, {"subsample-seed", required_argument, 0, 1017},
-        {"bootstrap-quantiles", required_argument, 0, 1018}, {"isoforms", no_argument, 0, 1019},
+        {"bootstrap-quantiles", required_argument, 0, 1018}, {"isoforms", no_argument, 0, 1019}, {"fit", no_argument, 0, 1020},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
@@ -527,6 +556,7 @@ int main(int argc, char **argv) {
                 break;
             }
             case 1019: cfg.isoforms = 1; break;
+            case 1020: cfg.fit = 1; break;
             case 1009: {
                 const char *q = optarg;
                 while (*q && n_dev_map < 64) {

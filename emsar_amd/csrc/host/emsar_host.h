@@ -168,6 +168,16 @@ int emsar_write_gbootq(const char *path, const emsar_genes *g, int n_q, const do
 int emsar_write_isoforms(const char *path, const emsar_rsh *r, const emsar_genes *g, const double *fpkm, const double *usage,
                          const int32_t *dominant, int n_boot, const double *usage_mean, const double *usage_sd,
                          const int32_t *dominant_count, int n_q, const double *q, const double *usage_q);
+/* .fit (emsar-hip --fit): one line per transcript, in the order of .fpkm: transcriptID FPKM eff_segments chi2 deviance miss_reads
+ * miss_fraction worst_segment, "%s\t%lf\t%lf\t%lf\t%lf\t%lf\t%lf\t%s"; the four sums and worst_row [n_tx] as emsar_hip_model_fit returns them for
+ * fpkm; miss_fraction = miss / (fpkm * den), the missed share of the transcript's expected reads, 0 when that product is 0; worst_segment =
+ * "c<row>", the id .segments uses, or "-" */
+int emsar_write_fit(const char *path, const emsar_rsh *r, const double *fpkm, const double *den, const double *df, const double *chi2,
+                    const double *dev, const double *miss, const int32_t *worst_row);
+/* .gfit (with --g2t): per gene, in the order of .gfpkm: geneID eff_segments chi2 deviance miss_reads miss_fraction, the gene sums [n_genes] of
+ * the four columns; miss_fraction = miss / the sum of fpkm * den over the gene's transcripts in ascending tid, 0 when that sum is 0 */
+int emsar_write_gfit(const char *path, const emsar_rsh *r, const emsar_genes *g, const double *fpkm, const double *den, const double *df,
+                     const double *chi2, const double *dev, const double *miss);
 /* .saturation (emsar-hip --subsample): a "#" line (fractions, replicates, seed, depth_mean per fraction), a header, then per
  * transcript its name, FPKM and TPM as in .fpkm and per fraction mean_FPKM sd_FPKM mean_TPM sd_TPM ([n_fractions][n_tx] each) */
 int emsar_write_saturation(const char *path, const emsar_rsh *r, const double *fpkm, const double *tpm, int n_fractions,

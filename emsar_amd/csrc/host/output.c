@@ -16,6 +16,10 @@
  *   .isoforms           per transcript that is in a gene, in the order of .fpkm: transcript_ID gene_ID FPKM usage dominant
  *                       ("%s\t%s\t%lf\t%lf\t%d"), with --bootstrap also usage_mean usage_sd dominant_freq, with --bootstrap-quantiles
  *                       also usage_q<q> per probability (q as "%.17g"), all "%lf"
+ * and the model fit's files (--fit):
+ *   .fit                per transcript, in the order of .fpkm: transcriptID FPKM eff_segments chi2 deviance miss_reads miss_fraction
+ *                       worst_segment ("%s\t%lf\t%lf\t%lf\t%lf\t%lf\t%lf\t%s"; worst_segment is the c<row> id of .segments, or "-")
+ *   .gfit               per gene, in the order of .gfpkm: geneID eff_segments chi2 deviance miss_reads miss_fraction
  * and the depth subsampling's files (--subsample):
  *   .saturation         "# fractions=.. replicates=.. seed=.. depth_mean=..", a header, then per transcript FPKM and TPM as in .fpkm and
  *                       per fraction mean_FPKM sd_FPKM mean_TPM sd_TPM, all "%lf"
@@ -26,6 +30,7 @@
 
 #include <math.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 int emsar_write_fpkm(const char *path, const emsar_rsh *r, const double *mean, const double *sd, const double *ieuma,
                      const double *ireadcount, const int32_t *ireadcount_int, const double *tpm, int64_t *total_ir) {
@@ -120,6 +125,33 @@ int emsar_write_isoforms(const char *path, const emsar_rsh *r, const emsar_genes
         for (int j = 0; j < n_q; j++) fprintf(f, "\t%lf", usage_q[(int64_t)j * r->n_tx + t]);
         fprintf(f, "\n");
     }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+int emsar_write_fit(const char *path, const emsar_rsh *r, const double *fpkm, const double *den, const double *df, const double *chi2,
+                    const double *dev, const double *miss, const int32_t *worst_row) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "transcriptID\tFPKM\teff_segments\tchi2\tdeviance\tmiss_reads\tmiss_fraction\tworst_segment\n");
+    for (int32_t t = 0; t < r->n_tx; t++) {
+        const double expected = fpkm[t] * den[t];
+        fprintf(f, "%s\t%lf\t%lf\t%lf\t%lf\t%lf\t%lf\t", r->names[t], fpkm[t], df[t], chi2[t], dev[t], miss[t], expected != 0.0 ? miss[t] / expected : 0.0);
+        if (worst_row[t] >= 0) fprintf(f, "c%d\n", worst_row[t]); else fprintf(f, "-\n");
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+int emsar_write_gfit(const char *path, const emsar_rsh *r, const emsar_genes *g, const double *fpkm, const double *den, const double *df,
+                     const double *chi2, const double *dev, const double *miss) {
+    double *expected = (double *)calloc(g->n_genes > 0 ? (size_t)g->n_genes : 1, sizeof(double));
+    if (!expected) return EMSAR_HOST_ERR_OOM;
+    for (int32_t t = 0; t < r->n_tx; t++) if (g->gene_of_tx[t] >= 0) expected[g->gene_of_tx[t]] += fpkm[t] * den[t];
+    FILE *f = fopen(path, "w");
+    if (!f) { free(expected); return EMSAR_HOST_ERR_IO; }
+    fprintf(f, "geneID\teff_segments\tchi2\tdeviance\tmiss_reads\tmiss_fraction\n");
+    for (int32_t k = 0; k < g->n_genes; k++)
+        fprintf(f, "%s\t%lf\t%lf\t%lf\t%lf\t%lf\n", g->names[k], df[k], chi2[k], dev[k], miss[k], expected[k] != 0.0 ? miss[k] / expected[k] : 0.0);
+    free(expected);
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
 

@@ -25,6 +25,7 @@ SYMBOLS = [
     "emsar_hip_subsample", "emsar_hip_subsample_weights", "emsar_hip_subsample_draw_host",
     "emsar_hip_bootstrap_quantiles", "emsar_hip_quantiles_host",
     "emsar_hip_isoform_usage", "emsar_hip_isoform_usage_host", "emsar_hip_bootstrap_isoforms",
+    "emsar_hip_model_fit", "emsar_hip_model_fit_host",
 ]
 
 
@@ -82,6 +83,20 @@ class QuantileStats(C.Structure):
 class IsoformOutputs(C.Structure):
     _fields_ = [("usage_mean", C.POINTER(C.c_double)), ("usage_sd", C.POINTER(C.c_double)), ("dominant_count", C.POINTER(C.c_int32)),
                 ("usage_q", C.POINTER(C.c_double))]
+
+
+class FitOutputs(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in ("row_mu", "row_chi2", "row_dev", "tx_chi2", "tx_dev", "tx_miss", "tx_df")] + [
+        ("tx_worst_row", C.POINTER(C.c_int32))] + [(k, C.POINTER(C.c_double)) for k in ("gene_chi2", "gene_dev", "gene_miss", "gene_df")]
+
+
+class FitStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("total_ms", C.c_double), ("rows_inside", C.c_int64), ("rows_infeasible", C.c_int64),
+                ("index_slots", C.c_int64), ("index_bytes", C.c_int64), ("sum_chi2", C.c_double), ("sum_dev", C.c_double),
+                ("sum_miss", C.c_double), ("rows_ms", C.c_double), ("tx_ms", C.c_double), ("genes_ms", C.c_double), ("totals_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class SetsInfo(C.Structure):
@@ -153,6 +168,9 @@ def load_library():
     L.emsar_hip_isoform_usage.argtypes = [vp, C.c_int32, f64p, f64p, i32p]
     L.emsar_hip_isoform_usage_host.argtypes = [C.c_int32, C.c_int32, i32p, C.c_int32, f64p, f64p, i32p]
     L.emsar_hip_bootstrap_isoforms.argtypes = L.emsar_hip_bootstrap_quantiles.argtypes + [C.POINTER(IsoformOutputs)]
+    L.emsar_hip_model_fit.argtypes = [vp, f64p, f64p, C.POINTER(FitOutputs), C.POINTER(FitStats)]
+    L.emsar_hip_model_fit_host.argtypes = [C.c_int64, C.c_int32, u64p, i32p, i32p, f64p, f64p, C.c_int32, i32p, C.POINTER(FitOutputs),
+                                           C.POINTER(FitStats)]
     _lib = L
     return L
 
@@ -250,6 +268,48 @@ def isoform_usage_host(gene_of_tx, n_genes, cols, want_dominant=False):
         return usage[0] if one else usage
     dom = dom[:, :max(int(n_genes), 0)]
     return (usage[0], dom[0]) if one else (usage, dom)
+
+
+def _fit_buffers(n_rows, n_tx, n_genes, rows, genes):
+    """the output arrays of a model fit (never of length 0) and the struct that points at them"""
+    res = {k: np.zeros(max(n_tx, 1)) for k in ("tx_chi2", "tx_dev", "tx_miss", "tx_df")}
+    res["tx_worst_row"] = np.zeros(max(n_tx, 1), dtype=np.int32)
+    if rows:
+        res.update({k: np.zeros(max(n_rows, 1)) for k in ("row_mu", "row_chi2", "row_dev")})
+    if genes:
+        res.update({k: np.zeros(max(n_genes, 1)) for k in ("gene_chi2", "gene_dev", "gene_miss", "gene_df")})
+    o = FitOutputs()
+    for k, a in res.items():
+        setattr(o, k, _p(a, C.c_int32 if k == "tx_worst_row" else C.c_double))
+    return res, o
+
+
+def _fit_result(res, n_rows, n_tx, n_genes, st):
+    out = {k: v[:(n_rows if k.startswith("row_") else n_genes if k.startswith("gene_") else n_tx)] for k, v in res.items()}
+    out["stats"] = st
+    return out
+
+
+def model_fit_host(n_tx, row_ptr, col_idx, theta, row_weight=None, E=None, rows=False, gene_of_tx=None, n_genes=0, genes=None):
+    """Host-only: the library's model fit (include/emsar_hip.h "model fit") of theta against the rows' weights (None = 1 per row) and
+    E (None = 1.0), no GPU needed, the same functions the device evaluates.  Returns a dict: tx_chi2, tx_dev, tx_miss, tx_df, tx_worst_row
+    ([n_tx]), with rows also row_mu, row_chi2, row_dev ([n_rows]), with a gene map (gene_of_tx, n_genes; genes=False leaves them out)
+    also gene_chi2, gene_dev, gene_miss, gene_df ([n_genes]), and stats."""
+    L = load_library()
+    row_ptr, col_idx, th = _arr(row_ptr, np.uint64), _arr(col_idx, np.int32), _arr(theta, np.float64)
+    w, e, g = _arr(row_weight, np.int32), _arr(E, np.float64), _arr(gene_of_tx, np.int32)
+    n_rows = len(row_ptr) - 1
+    for a, n in ((th, n_tx), (w, n_rows), (e, n_rows), (g, n_tx)):
+        if a is not None and a.shape != (n,):
+            raise ValueError("array of length %d expected" % n)
+    want_genes = (g is not None) if genes is None else bool(genes)
+    res, o = _fit_buffers(n_rows, n_tx, int(n_genes), rows, want_genes)
+    st = FitStats()
+    rc = L.emsar_hip_model_fit_host(n_rows, int(n_tx), _p(row_ptr, C.c_uint64), _p(col_idx, C.c_int32), _p(w, C.c_int32), _p(e, C.c_double),
+                                    _p(th, C.c_double), int(n_genes), _p(g, C.c_int32), C.byref(o), C.byref(st))
+    if rc != 0:
+        raise EmsarHipError(rc, "model_fit_host")
+    return _fit_result(res, n_rows, int(n_tx), int(n_genes), st)
 
 
 def layout_selfcheck_tiled(n_tx, row_ptr, col_idx, merge_rows=False):
@@ -467,6 +527,20 @@ class EmsarHip:
         if qa is not None:
             out["qstats"] = qs
         return out
+
+    def model_fit(self, theta, E=None, rows=False, genes=False):
+        """Does theta explain the current sample's reads (include/emsar_hip.h "model fit")?  E None = 1.0 per row.  Returns a dict:
+        tx_chi2, tx_dev, tx_miss, tx_df, tx_worst_row ([n_tx]; the row whose miss weighs most on the transcript, -1 = none), with rows
+        also row_mu, row_chi2, row_dev ([n_rows]), with genes (after set_gene_map) also gene_chi2, gene_dev, gene_miss, gene_df
+        ([n_genes]), and stats.  After upload_sample; the context is left as it was."""
+        th, e = _arr(theta, np.float64), _arr(E, np.float64)
+        for a, n in ((th, self.n_tx), (e, self.n_rows)):
+            if a is not None and a.shape != (n,):
+                raise ValueError("array of length %d expected" % n)
+        res, o = _fit_buffers(self.n_rows, self.n_tx, self.n_genes, rows, genes)
+        st = FitStats()
+        self._chk(self._L.emsar_hip_model_fit(self._h, _p(th, C.c_double), _p(e, C.c_double), C.byref(o), C.byref(st)), "model_fit")
+        return _fit_result(res, self.n_rows, self.n_tx, self.n_genes, st)
 
     def bootstrap_weights(self, seed, replicate):
         """The drawn row weights of one bootstrap replicate (caller row order), drawn on the device."""

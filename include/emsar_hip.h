@@ -366,6 +366,62 @@ int emsar_hip_subsample_weights(emsar_hip_ctx *ctx, uint64_t seed, int32_t repli
 int emsar_hip_subsample_draw_host(uint64_t seed, int32_t replicate, double fraction, int64_t n_rows,
                                   const int32_t *row_weight /* NULL = 1 */, int32_t *w_out);
 
+/* ---- model fit: does the fitted model explain the reads? ------------------------------------------------------------------------
+ * Per-row residuals of one column theta against the sample, and a per-transcript and per-gene digest of them with a pointer to the
+ * worst row.  Everything is in caller numbering and caller row order, so no result depends on the layout, on merged rows, on the
+ * library's own transcript numbering or on the device.
+ * Inputs: the structure of upload_structure; R_c = the row weights of upload_sample (0 where E was 0 at that call); row_E of THIS call
+ * (NULL = 1.0; finite and >= 0); theta[n_tx] (finite and >= 0; both checked on the host before anything is uploaded).
+ * Per row c.  A row is OUTSIDE if it is empty or row_E[c] == 0: all its outputs are 0.  For the others
+ *     S_c  = sum of theta[col] over the row's entries, left to right (a repeated tid counts twice),   mu_c = row_E[c] * S_c,
+ *   mu_c > 0:            q_c = (R - mu) * (R - mu) / mu     the Pearson term
+ *                        a_c = |R - mu|                     the miss in reads
+ *                        d_c = max(0, 2 * ((R > 0 ? R * log(R / mu) : 0) - (R - mu)))     the Poisson deviance term
+ *   mu_c == 0, R_c == 0: all outputs 0
+ *   mu_c == 0, R_c > 0:  the likelihood is -inf there: q_c = d_c = +inf, a_c = R; the row is INFEASIBLE, counted in rows_infeasible
+ *                        and reaches no transcript (every share in it is 0).
+ * No fused multiply-add: every output except d is a pure function of IEEE +, -, *, / and the same bits on host and device; d goes
+ * through log (libm on the host, the device's log, both within 1 ulp).
+ * Per entry k = (c, t): the share p_k = theta_t / S_c, one division, for a row that is inside with mu_c > 0; other entries add nothing.
+ * Per transcript t: its entries ordered by (caller row ascending, position in the row ascending) are summed by the rule of gene_sums --
+ * consecutive chunks of 256, each added left to right from its first term, then the chunk sums left to right:
+ *     tx_chi2 = sum p_k q_c      tx_dev = sum p_k d_c      tx_miss = sum p_k a_c
+ *     tx_df   = sum p_k          the effective number of segments attributed to t
+ *     tx_worst_row = the caller row of the entry with the largest p_k * a_c, the smallest row among equal maxima, -1 when no entry
+ *                    has p_k * a_c > 0.  Products are compared, so nothing is rounded twice.
+ * Per gene (after set_gene_map): the gene sums of the four tx columns, in gene_sums' own order.  All four NULL, or all four given.
+ *   model_fit       ERR_STATE before upload_sample and for gene outputs without a map; ERR_ARG for a NULL theta, a negative or
+ *                   non-finite theta or E, a gene output group only partly given, and n_rows > INT32_MAX (the index holds int32 row
+ *                   ids); ERR_OOM if the index does not fit.  out may be NULL (statistics only).  The first call after
+ *                   upload_structure builds the transposed index (DESIGN.md "Model fit") and keeps it, with the caller-order CSR
+ *                   and 32 bytes per row, until the next upload_structure.  The context is left as it was: a following solve
+ *                   returns the same bits.
+ *   model_fit_host  the same definition with no HIP call and no context: the CSR, the weights (NULL = 1 per row; negative: ERR_ARG),
+ *                   E, theta and the gene map (gene_of_tx NULL = none: gene outputs then give ERR_STATE; else the checks of
+ *                   set_gene_map) are given directly.  kernel_ms and the stage times stay 0.
+ * The three totals are added over the rows that are not infeasible in a fixed order (one workgroup: lane l of 1024 takes the rows l,
+ * l + 1024, .. in order, a wave is folded by a butterfly, the 16 wave sums left to right); the host function restates that order. */
+typedef struct {
+    double  *row_mu, *row_chi2, *row_dev;               /* [n_rows] mu_c, q_c, d_c; may each be NULL */
+    double  *tx_chi2, *tx_dev, *tx_miss, *tx_df;        /* [n_tx]; may each be NULL */
+    int32_t *tx_worst_row;                              /* [n_tx]; may be NULL */
+    double  *gene_chi2, *gene_dev, *gene_miss, *gene_df; /* [n_genes]; all four NULL, or all four given after set_gene_map */
+} emsar_fit_outputs;
+typedef struct {
+    double  kernel_ms;                       /* device time of all stages (HIP events) */
+    double  total_ms;                        /* wall time of the call, the index build of a first call included */
+    int64_t rows_inside, rows_infeasible;    /* rows that are not outside; of these, rows with mu == 0 and R > 0 */
+    int64_t index_slots, index_bytes;        /* int32 row ids of the transposed index, padding included (<= nnz + 64 * 255); bytes of the index and its tables */
+    double  sum_chi2, sum_dev, sum_miss;     /* sum_c q_c, d_c, a_c over the inside rows that are not infeasible */
+    double  rows_ms, tx_ms, genes_ms, totals_ms;   /* device time per stage: rows, transcripts (both kernels), gene sums, totals */
+} emsar_fit_stats;
+int emsar_hip_model_fit(emsar_hip_ctx *ctx, const double *theta /* n_tx */, const double *row_E /* n_rows, or NULL */,
+                        const emsar_fit_outputs *out /* or NULL */, emsar_fit_stats *stats /* or NULL */);
+int emsar_hip_model_fit_host(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr, const int32_t *col_idx,
+                             const int32_t *row_weight /* NULL = 1 */, const double *row_E /* or NULL */, const double *theta,
+                             int32_t n_genes, const int32_t *gene_of_tx /* n_tx, or NULL = no gene map */,
+                             const emsar_fit_outputs *out /* or NULL */, emsar_fit_stats *stats /* or NULL */);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 typedef struct {
     int64_t n_rows, nnz;
