@@ -90,7 +90,7 @@ __device__ __forceinline__ double cl_estep_partial(const Cl &C) {
         }
         const double r = C.rw[j];
         const bool live = S > 0.0;
-        C.w[j - C.r0] = live ? r * fast_rcp(S) : 0.0;
+        C.w[j - C.r0] = (live && r > 0.0) ? r * fast_rcp(S) : 0.0;      // as in set_em_estep: no reads, no weight, whatever S is
         if (LL && live) ll += r * log(S);
     }
     __syncthreads();

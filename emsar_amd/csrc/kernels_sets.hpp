@@ -54,6 +54,10 @@ __device__ __forceinline__ double wave_max_dpp(double v) {      // v >= 0
 // Workgroup barrier of the set solver.  A one-wave workgroup needs none: the DS operations of a wave execute in order, so
 // only the compiler has to be kept from moving LDS accesses across the point (same hand-over as between the E- and the
 // M-step of the tiled pass kernel); s_barrier would cost its issue + wait on every one of the ~10 phases of a cycle.
+// The fences emit no instruction.  With today's hipcc taking them out changes no LDS access of the kernel either (checked on the ISA:
+// block layout and one address computation move, nothing crosses a phase) -- every LDS pointer here is computed at run time from the
+// one dynamic array, so the compiler must assume they alias and keeps the order by itself.  The fences are what still holds that
+// order once it learns more (a __restrict__, a static split of the array); no test can tell them from nothing until then.
 template <int THREADS>
 __device__ __forceinline__ void set_sync() {
     if (THREADS > 64) __syncthreads();
@@ -121,7 +125,9 @@ __device__ __forceinline__ double set_em_estep(const SetLds &L, const double *x)
         }
         const double r = L.rw[j];
         const bool live = S > 0.0;
-        L.w[j] = live ? r * fast_rcp(S) : 0.0;
+        // a row without reads contributes exactly 0 whatever S is: in a resampled replicate a row that drew 0 stays in its set, and
+        // while its transcripts decay towards 0 its S crosses the denormals, where fast_rcp is not finite (0 * NaN would reach acc)
+        L.w[j] = (live && r > 0.0) ? r * fast_rcp(S) : 0.0;
         if (LL && live) ll += r * log(S);
     }
     set_sync<THREADS>();
@@ -187,7 +193,7 @@ __device__ __forceinline__ bool set_newton_step(const SetLds &L, double *x, doub
     for (int j = threadIdx.x; j < nr; j += THREADS) {
         const double S = set_row_dot<THREADS>(L, x, j), rw = L.rw[j];
         const bool live = S > 0.0;
-        const double inv = live ? fast_rcp(S) : 0.0;
+        const double inv = (live && rw > 0.0) ? fast_rcp(S) : 0.0;      // as in set_em_estep: no reads, no weight, whatever S is
         L.w[j] = rw * inv; L.hrow[j] = rw * inv * inv;
         if (live) s3[0] += rw * log(S);
     }
