@@ -1,21 +1,28 @@
 // emsar_hip.hip -- MI355X (gfx950 / CDNA4) abundance-estimation core behind include/emsar_hip.h.
 //
-// Replaces run_MLE_threads() (/root/reference/src/emsar_main.c:446; MLE/Fp/lambdap,
+// Replaces the reference's run_MLE_threads() (src/emsar_main.c:446; MLE/Fp/lambdap,
 // emsar_functions.c:2946-3126) by an EM on the same segment Poisson likelihood:
 //     E-step  w_c = R_c / S_c ,  S_c = sum_t m_ct theta_t        (rows with E_c == 0 are outside F)
 //     M-step  theta_t <- theta_t * (sum_c m_ct w_c) / den_t ,    den_t = sum_c m_ct E_c
 // and compute_iEUMA / the TPM + iReadcount arithmetic of print_FPKMfinal (emsar_functions.c:3176-3232).
 //
 // One pass is HBM-bound integer streaming plus FP64 adds: ~2 flop per nonzero -- no MFMA.
-// This file: the context, the launch logic (launch_pass, enqueue_cycles, the set solver's driver) and the C ABI of uploads and solves.
+// This file: the context, its small helpers, and the C ABI of create / upload / theta / normalise / info / self-checks.
 //   context      its device and pinned memory lives in DevBuf / PinBuf owners (devmem.hpp), grouped by lifetime: LayoutDev, TxVectors, GeneMap
-//                and AdjEuma go with the structure, RowWeights and SetsDev with the sample; a group is dropped by assigning an empty one
-//   launch_pass  choose_pass_kernel says which TILED kernel runs (a pure function of weighted, mode, tile count and the two knobs;
-//                emsar_hip_debug_pass_kernel shows it to the tests), one launcher per kernel family launches it
-// resample.hpp (same translation unit, included at the end): the resampling driver and its C ABI -- bootstrap, quantiles, subsampling, genes.
+//                and AdjEuma go with the structure, RowWeights and SetsDev with the sample; a group is dropped by assigning an empty one.
+//                Nothing of a solve lives in it (solve.hpp: PassRules)
+// The drivers, same translation unit, included where their first user stands:
+//   pass_launch.hpp   choose_pass_kernel, one launcher per kernel family, launch_pass; the stamped diagnostic launches
+//   solve.hpp         the set solver's driver (ensure_sets, solve_resident_sets), em_pass / enqueue_cycles, SolveRun: one solve in stages;
+//                     emsar_hip_solve, emsar_hip_run_passes
+//   resample.hpp      the resampling driver and its C ABI -- bootstrap, quantiles, subsampling, genes
+//   fit.hpp           the model fit and its C ABI
 // Kernels (one translation unit, included below):
-//   kernels_tiled.hpp     k_pass_tiled / k_pass_tiled_multi<2>   the hot ones: one workgroup per tile (or pair of tiles) of the
-//                         TILED layout, dictionary of theta/acc in LDS, 10-bit ids, per-slice transposed index
+//   kernels_tiled.hpp     k_pass_tiled_unit                      the hot one (the default above 2048 tiles): one workgroup per UNIT of up to
+//                         two tiles of the TILED layout that share a dictionary of theta/acc in LDS (60 blocks x 16 subset sums),
+//                         10-bit ids, per-slice transposed index
+//                         k_pass_tiled / k_pass_tiled_multi<N>   one tile per workgroup (small problems, weighted likelihood passes,
+//                         scatter) / N tiles per workgroup, each with its own dictionary (opt-in: EMSAR_HIP_TILED_MULTI)
 //   kernels_csr.hpp       k_pass_csr                             the caller's CSR as it is (layout 1), leftover rows of TILED
 //   kernels_vector.hpp    k_update, k_update_p2/p3, k_sq_extrap_ll (SQUAREM extrapolation / acceptance on the device),
 //                         k_normalise, k_adj_euma, small reductions
@@ -168,19 +175,15 @@ struct emsar_hip_ctx {
     PinBuf<Scal> h_scal;
     int64_t bytes_formula = 0, bytes_stored = 0;
     int64_t tl_fwd_slots = 0, tl_n_fslices = 0;
-    double count_floor = 0.0;    // stopping-rule floor in reads for the current solve (emsar_em_params.count_floor)
-    double zero_cut = 0.0;       // emsar_em_params.zero_cut of the current solve
     bool use_graph = true;       // replay check_every cycles of the streaming solve from one hipGraph (EMSAR_HIP_GRAPH=0: launch each kernel)
-    int64_t graph_launches = 0;  // of the last solve (debug: EMSAR_HIP_DEBUG)
     bool det = false;            // deterministic mode (emsar_hip_set_deterministic / EMSAR_HIP_DETERMINISTIC): fixed-point sums, kernels_common.hpp
     double fx_mass = 0.0, fx_ll = 0.0;   // its scales for the current sample (upload_sample)
     DevBuf<double> d_sqpart;     // per-workgroup partial sums of the SQUAREM vector kernels [4][kSqPart]
     int update_grid = 1024;       // workgroups of k_update (EMSAR_HIP_UPDATE_GRID)
     int sq_grid = 256;           // workgroups of the SQUAREM vector kernels (EMSAR_HIP_SQ_GRID)
     int weighted_unit = 1;       // EMSAR_HIP_WEIGHTED_UNIT: weighted rows on k_pass_tiled_unit -- 1: the plain EM pass, 2: the likelihood passes too, 0: never
-    int tiled_multi = 1;         // EMSAR_HIP_TILED_MULTI 1: two tiles per workgroup (k_pass_tiled_multi) above kPairMinTiles tiles, else one
-                                 // (k_pass_tiled); 2: always two; 0: always one
-    const uint8_t *delta_mask = nullptr;   // sets.d_kind while the streaming solve runs next to resident sets
+    int tiled_multi = 1;         // EMSAR_HIP_TILED_MULTI 1: one unit of up to two tiles per workgroup (k_pass_tiled_unit) above kPairMinTiles tiles,
+                                 // else one tile (k_pass_tiled); 5: always units; 2 / 3 / 4: always that many tiles (k_pass_tiled_multi); 0: always one
     // set-resident solver (sets.hpp): host copy of the CSR and of the sample's row weights, built lazily by solve
     std::vector<uint64_t> h_row_ptr;
     std::vector<int32_t> h_col, h_wgt;
@@ -200,8 +203,6 @@ namespace {
 
 inline int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
 
-// per-solve state, cleared whatever the exit of a solve
-inline void clear_solve_state(emsar_hip_ctx *ctx) { ctx->count_floor = 0.0; ctx->zero_cut = 0.0; ctx->delta_mask = nullptr; }
 // deterministic mode's scales for a sample of `total` reads: no transcript is assigned more reads than the sample holds, |sum R log S| <= N * 745
 inline void set_fx_scales(emsar_hip_ctx *ctx, int64_t total) {
     int e_mass = 0, e_ll = 0;
@@ -246,127 +247,11 @@ void free_structure(emsar_hip_ctx *ctx) {
 // the fixed-point scales the EM kernels get (zeros = plain FP64 atomics; scatter passes always)
 inline Fx fx_of(const emsar_hip_ctx *ctx, int mode = MODE_EM) { return (ctx->det && mode != MODE_SCATTER) ? Fx{ctx->fx_mass, ctx->fx_ll} : Fx{0.0, 0.0}; }
 
-// ---- which TILED pass kernel runs: a pure function of the sample, the mode, the size and the two knobs ----
-constexpr int64_t kPairMinTiles = 2048;   // 256 CUs x 4 resident workgroups x 2 tiles
-enum PassFamily { FAMILY_TILE, FAMILY_MULTI, FAMILY_UNIT };      // k_pass_tiled, k_pass_tiled_multi, k_pass_tiled_unit
-struct PassKernel { PassFamily family; bool weighted; int mode; int n_multi; /* tiles per workgroup, FAMILY_MULTI only */ };
+}  // namespace
 
-PassKernel choose_pass_kernel(bool weighted, int mode, int64_t n_tiles, int tiled_multi, int weighted_unit) {
-    if (mode == MODE_SCATTER) return {FAMILY_TILE, false, MODE_SCATTER, 0};
-    const bool above = tiled_multi == 1 && n_tiles > kPairMinTiles;
-    if (!weighted && (tiled_multi >= 2 || above)) {
-        // more than one tile per workgroup.  Unweighted rows only: with the row weights in registers as well the body does not
-        // fit 128 VGPRs (round 1, two tiles: 0.218 vs 0.179 ms; round 2, the unit kernel on merged rows, 72-92 B of scratch:
-        // 0.124 vs 0.103 ms with one tile per workgroup; with the weights kept as integers its EM variant fits without
-        // scratch and runs config 3's merged rows in 0.0959 ms against 0.0956 ms for one tile per workgroup: no gain,
-        // and the likelihood variant -- twelve logs -- still spills).
-        // Only when the tiles outnumber the chip's workgroup slots: below that a pass is one workgroup's latency, and
-        // a pair takes twice as long as a tile (40 k reads: 47 -> 26 us per pass with one tile per workgroup)
-        if (tiled_multi == 1 || tiled_multi == 5) return {FAMILY_UNIT, false, mode, 0};      // units: one dictionary for up to two tiles
-        return {FAMILY_MULTI, false, mode, tiled_multi == 3 ? 3 : tiled_multi == 4 ? 4 : 2};
-    }
-    if (weighted && (weighted_unit == 2 || (weighted_unit == 1 && mode == MODE_EM)) && (tiled_multi == 5 || above)) {
-        // weighted rows (segments with read counts, merged rows) on the unit kernel: the weights are loaded as integers after the
-        // forward batch is consumed; both variants fit 128 VGPRs without scratch (round 3).  Measured on the collapsed form of
-        // config 3 (14.0 M segments of the family law / 5.4 M of the window law): plain pass 0.1273 -> 0.1221 / 0.0964 -> 0.0962 ms;
-        // the likelihood variant takes its twelve logs per lane in one rolled loop (tile_e_step) and is SLOWER than the one-tile
-        // kernel's unrolled logs (solve 0.161 against 0.150 ms per pass), so by default (1) only the plain EM pass of a SQUAREM
-        // cycle runs here and the two likelihood passes stay with k_pass_tiled; 2 = both, 0 = neither (EMSAR_HIP_WEIGHTED_UNIT)
-        return {FAMILY_UNIT, true, mode, 0};
-    }
-    return {FAMILY_TILE, weighted, mode, 0};
-}
+#include "pass_launch.hpp"   // choose_pass_kernel, the launchers, launch_pass; the stamped diagnostic launches
 
-// ---- launchers: one per kernel family, the template arguments as tag values ----
-template <bool B> using BoolC = std::integral_constant<bool, B>;
-template <int M> using ModeC = std::integral_constant<int, M>;
-// f(mode tag) / f(weighted tag, mode tag) for a pass of the E- and M-step, with or without the likelihood
-template <class F> void with_em_mode(int mode, const F &f) { if (mode == MODE_EM_LL) f(ModeC<MODE_EM_LL>()); else f(ModeC<MODE_EM>()); }
-template <class F> void with_em_variant(bool weighted, int mode, const F &f) {
-    if (weighted) with_em_mode(mode, [&](auto md) { f(BoolC<true>(), md); });
-    else with_em_mode(mode, [&](auto md) { f(BoolC<false>(), md); });
-}
-
-constexpr size_t kTiledLds = (size_t)kTiledLdsDoubles * sizeof(double);
-struct PassArgs { const double *theta; double *acc, *ll_out; Fx fx; };
-
-template <bool WT, int MD> void launch_tile(BoolC<WT>, ModeC<MD>, emsar_hip_ctx *ctx, const PassArgs &a) {
-    const LayoutDev &L = ctx->lay;
-    hipLaunchKernelGGL((k_pass_tiled<WT, MD>), dim3((unsigned)L.n_tiles), dim3(kTiledThreads), kTiledLds, ctx->stream, L.d_tiles, L.d_fwd, L.d_bwd,
-                       L.d_far, ctx->rw.d_wgt, L.d_rowval, a.theta, a.acc, a.ll_out, a.fx);
-}
-template <bool WT, int MD, int N> void launch_multi(BoolC<WT>, ModeC<MD>, std::integral_constant<int, N>, emsar_hip_ctx *ctx, const PassArgs &a) {
-    const LayoutDev &L = ctx->lay;
-    hipLaunchKernelGGL((k_pass_tiled_multi<WT, MD, N>), dim3((unsigned)((L.n_tiles + N - 1) / N)), dim3(kTiledThreads), kTiledLds, ctx->stream, L.d_tiles,
-                       (int)L.n_tiles, L.d_fwd, L.d_bwd, L.d_far, ctx->rw.d_wgt, a.theta, a.acc, a.ll_out, a.fx);
-}
-template <bool WT, int MD> void launch_unit(BoolC<WT>, ModeC<MD>, emsar_hip_ctx *ctx, const PassArgs &a) {
-    const LayoutDev &L = ctx->lay;
-    hipLaunchKernelGGL((k_pass_tiled_unit<WT, MD>), dim3((unsigned)L.n_units), dim3(kTiledThreads), kTiledLds, ctx->stream, L.d_utiles, L.unit_stride,
-                       L.d_far, L.d_fwd, L.d_bwd, ctx->rw.d_wgt, a.theta, a.acc, a.ll_out, a.fx);
-}
-// the CSR kernel: the caller's rows (32- or 64-bit row_ptr), or the leftover rows of TILED
-template <class PT, bool WT, int MD>
-void launch_csr_rows(emsar_hip_ctx *ctx, unsigned max_grid, int64_t n_rows, const PT *row_ptr, const int32_t *col, const int32_t *wgt, const double *val, const PassArgs &a) {
-    hipLaunchKernelGGL((k_pass_csr<PT, WT, MD>), dim3((unsigned)std::min<int64_t>((n_rows + 255) / 256, max_grid)), dim3(256), 0, ctx->stream, n_rows, row_ptr,
-                       col, wgt, val, a.theta, a.acc, a.ll_out, a.fx);
-}
-template <bool WT, int MD> void launch_left(BoolC<WT>, ModeC<MD>, emsar_hip_ctx *ctx, const PassArgs &a) {
-    const LayoutDev &L = ctx->lay;
-    launch_csr_rows<uint64_t, WT, MD>(ctx, 8192, L.n_left, L.d_left_ptr, L.d_left_col, ctx->rw.d_left_wgt, L.d_left_val, a);
-}
-template <bool WT, int MD> void launch_csr(BoolC<WT>, ModeC<MD>, emsar_hip_ctx *ctx, const PassArgs &a) {
-    const LayoutDev &L = ctx->lay;
-    if (ctx->ptr64) launch_csr_rows<uint64_t, WT, MD>(ctx, 256 * 32, ctx->n_rows, (const uint64_t *)L.d_row_ptr.get(), L.d_col, ctx->rw.d_wgt, L.d_rowval, a);
-    else launch_csr_rows<uint32_t, WT, MD>(ctx, 256 * 32, ctx->n_rows, (const uint32_t *)L.d_row_ptr.get(), L.d_col, ctx->rw.d_wgt, L.d_rowval, a);
-}
-
-// the dynamic LDS of the TILED kernels, for every instantiation choose_pass_kernel can return (once per upload_structure)
-hipError_t set_tiled_lds_attributes() {
-    hipError_t e = hipSuccess;
-    auto set = [&](auto *kernel) { if (e == hipSuccess) e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTiledLds); };
-    set(k_pass_tiled<false, MODE_SCATTER>);
-    for (const bool weighted : {false, true})
-        for (const int mode : {MODE_EM, MODE_EM_LL})
-            with_em_variant(weighted, mode, [&](auto wt, auto md) { set(k_pass_tiled<wt(), md()>); set(k_pass_tiled_unit<wt(), md()>); });
-    for (const int mode : {MODE_EM, MODE_EM_LL})
-        with_em_mode(mode, [&](auto md) { set(k_pass_tiled_multi<false, md(), 2>); set(k_pass_tiled_multi<false, md(), 3>); set(k_pass_tiled_multi<false, md(), 4>); });
-    return e;
-}
-
-// one pass of the chosen layout.  mode: MODE_EM / MODE_EM_LL / MODE_SCATTER
-int launch_pass(emsar_hip_ctx *ctx, int mode, const double *theta, double *acc, double *ll_out, bool rows_only = false /* the folded rows' likelihood terms are added by the caller */) {
-    const PassArgs a{theta, acc, ll_out, fx_of(ctx, mode)};
-    const bool scatter = mode == MODE_SCATTER;
-    if (ctx->layout == EMSAR_LAYOUT_TILED) {
-        if (ctx->lay.n_tiles > 0) {
-            const PassKernel k = choose_pass_kernel(ctx->weighted, mode, ctx->lay.n_tiles, ctx->tiled_multi, ctx->weighted_unit);
-            if (scatter) launch_tile(BoolC<false>(), ModeC<MODE_SCATTER>(), ctx, a);
-            else if (k.family == FAMILY_TILE) with_em_variant(k.weighted, k.mode, [&](auto wt, auto md) { launch_tile(wt, md, ctx, a); });
-            else if (k.family == FAMILY_UNIT) with_em_variant(k.weighted, k.mode, [&](auto wt, auto md) { launch_unit(wt, md, ctx, a); });
-            else with_em_mode(k.mode, [&](auto md) {
-                using std::integral_constant;
-                if (k.n_multi == 3) launch_multi(BoolC<false>(), md, integral_constant<int, 3>(), ctx, a);
-                else if (k.n_multi == 4) launch_multi(BoolC<false>(), md, integral_constant<int, 4>(), ctx, a);
-                else launch_multi(BoolC<false>(), md, integral_constant<int, 2>(), ctx, a);
-            });
-        }
-        if (ctx->lay.n_left > 0) {   // rows too long for a tile: generic CSR kernel on the leftover
-            if (scatter) launch_left(BoolC<false>(), ModeC<MODE_SCATTER>(), ctx, a);
-            else with_em_variant(ctx->weighted, mode, [&](auto wt, auto md) { launch_left(wt, md, ctx, a); });
-        }
-        if (mode == MODE_EM_LL && !rows_only)
-            hipLaunchKernelGGL(k_single_ll, dim3(std::min(grid_for(ctx->n_tx, 256), 256)), dim3(256), 0, ctx->stream, ctx->n_tx,
-                               ctx->lay.d_u, theta, ll_out, fx_of(ctx).ll);
-        HIPCHK(hipGetLastError());
-        return EMSAR_HIP_OK;
-    }
-    if (ctx->n_rows == 0) return EMSAR_HIP_OK;
-    if (scatter) launch_csr(BoolC<false>(), ModeC<MODE_SCATTER>(), ctx, a);
-    else with_em_variant(ctx->weighted, mode, [&](auto wt, auto md) { launch_csr(wt, md, ctx, a); });
-    HIPCHK(hipGetLastError());
-    return EMSAR_HIP_OK;
-}
+namespace {
 
 // a likelihood word of the host copy of the scalars (fixed point in deterministic mode)
 inline double host_ll(const emsar_hip_ctx *ctx, int i) {
@@ -376,54 +261,6 @@ inline double host_ll(const emsar_hip_ctx *ctx, int i) {
     for (int j = 0; j < kLlSlots; j++) { long long x; memcpy(&x, &L.s[j].v, 8); b += x; }
     return (double)b / ctx->fx_ll;
 }
-
-// th_out = EM(th_in); ll slot receives sum R log S at th_in when want_ll
-int em_pass(emsar_hip_ctx *ctx, const double *th_in, double *th_out, bool want_ll, int ll_slot, double abs_floor, int to_delta1 = 0) {
-    int rc = launch_pass(ctx, want_ll ? MODE_EM_LL : MODE_EM, th_in, ctx->vec.d_acc, &ctx->d_scal->ll[ll_slot].s[0].v);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_update, dim3(std::min(grid_for(ctx->n_tx, 256), ctx->update_grid)), dim3(256), 0, ctx->stream, ctx->n_tx, th_in, ctx->vec.d_acc,
-                       ctx->vec.d_den, ctx->layout == EMSAR_LAYOUT_TILED ? ctx->lay.d_u.get() : nullptr, th_out, abs_floor, ctx->count_floor, ctx->zero_cut, ctx->d_scal,
-                       ctx->delta_mask, to_delta1, fx_of(ctx).mass);
-    HIPCHK(hipGetLastError());
-    return EMSAR_HIP_OK;
-}
-
-// `cycles` cycles of the streaming solve on ctx->stream -- launched, or recorded when the stream is capturing.
-// One cycle = one plain EM pass, or one SQUAREM cycle of three passes (8 launches, see k_update_p2).  The current point is
-// ctx->vec.d_th[0] before and after (plain EM swaps d_th[0]/d_th[1] on the host: record an even count).
-int enqueue_cycles(emsar_hip_ctx *ctx, const emsar_em_params &p, double abs_step_base, int cycles) {
-    const int n = ctx->n_tx, g = grid_for(n, 256);
-    DevBuf<double> *th = ctx->vec.d_th;     // handles: plain EM swaps two of them
-    int rc;
-    for (int c = 0; c < cycles; c++) {
-        hipLaunchKernelGGL(k_cycle_begin, dim3(1), dim3(kLlSlots), 0, ctx->stream, ctx->d_scal, abs_step_base, p.accel ? 3 : 1);
-        if (!p.accel) {
-            if ((rc = em_pass(ctx, th[0], th[1], false, 0, p.abs_floor))) return rc;
-            std::swap(th[0], th[1]);
-            continue;
-        }
-        // the stopping rule is measured on the first (plain) step of the cycle only (delta1_bits)
-        const double *u = ctx->layout == EMSAR_LAYOUT_TILED ? ctx->lay.d_u.get() : nullptr;
-        const dim3 gv((unsigned)std::min(std::min(g, ctx->sq_grid), kSqPart)), bv(256);
-        if ((rc = em_pass(ctx, th[0], th[1], false, 0, p.abs_floor, 1))) return rc;
-        if ((rc = launch_pass(ctx, MODE_EM_LL, th[1], ctx->vec.d_acc, &ctx->d_scal->ll[1].s[0].v, true))) return rc;
-        hipLaunchKernelGGL(k_update_p2, gv, bv, 0, ctx->stream, n, th[0], th[1], ctx->vec.d_acc, ctx->vec.d_den, u, th[2], ctx->d_scal, ctx->d_sqpart, fx_of(ctx));
-        hipLaunchKernelGGL(k_sq_extrap_ll, gv, bv, 0, ctx->stream, n, th[0], th[1], th[2], ctx->vec.d_den, u, th[3], ctx->d_scal, ctx->d_sqpart, (int)gv.x, fx_of(ctx));
-        if ((rc = launch_pass(ctx, MODE_EM_LL, th[3], ctx->vec.d_acc, &ctx->d_scal->ll[2].s[0].v, true))) return rc;
-        hipLaunchKernelGGL(k_update_p3, gv, bv, 0, ctx->stream, n, th[3], th[2], ctx->vec.d_acc, ctx->vec.d_den, u, th[0], ctx->d_scal, ctx->d_sqpart, (int)gv.x, fx_of(ctx));
-        HIPCHK(hipGetLastError());
-    }
-    return EMSAR_HIP_OK;
-}
-
-struct CycleGraph {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    ~CycleGraph() {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-    }
-};
 
 // The streaming layout's row weights from per-row weights x(r) (caller order, 0 = outside the likelihood): TILED -- the slots (a merged
 // slot sums its member rows), the leftover rows and the per-transcript count of the folded single-transcript rows; CSR -- the rows as
@@ -531,139 +368,121 @@ int scatter_rows(emsar_hip_ctx *ctx, const double *val_host, double *d_out) {
     } catch (const std::bad_alloc &) { ctx->err = "out of host memory"; return EMSAR_HIP_ERR_OOM; }
 }
 
-// find and pack the connected sets of the current sample (sets.hpp) and move the records to the device
-int ensure_sets_impl(emsar_hip_ctx *ctx);
-int ensure_sets(emsar_hip_ctx *ctx) {
-    if (ctx->sets.sets_ready) return EMSAR_HIP_OK;
-    const int rc = ensure_sets_impl(ctx);
-    if (rc != EMSAR_HIP_OK) ctx->sets = SetsDev();       // a half-uploaded record set is freed, the next solve starts over
-    return rc;
+
+// ---- upload_structure in stages: layout choice, the TILED or the CSR upload, the T-sized vectors ----
+
+// the layout a call asks for: the merge flag taken off, AUTO resolved (EMSAR_HIP_LAYOUT may choose).  ERR_ARG: no such layout, or merged rows without TILED
+int choose_layout(int64_t n_rows, int &layout, bool &merge_rows) {
+    merge_rows = (layout & EMSAR_LAYOUT_FLAG_MERGE_ROWS) != 0;
+    layout &= ~EMSAR_LAYOUT_FLAG_MERGE_ROWS;
+    if (layout != EMSAR_LAYOUT_AUTO && layout != EMSAR_LAYOUT_CSR && layout != EMSAR_LAYOUT_TILED) return EMSAR_HIP_ERR_ARG;
+    if (layout == EMSAR_LAYOUT_AUTO) {
+        layout = (n_rows < ((int64_t)1 << 32)) ? EMSAR_LAYOUT_TILED : EMSAR_LAYOUT_CSR;
+        if (const char *e = getenv("EMSAR_HIP_LAYOUT")) { int v = atoi(e); if ((v == 1 || v == 3) && (v == 1 || n_rows < ((int64_t)1 << 32))) layout = v; }
+    }
+    return merge_rows && layout != EMSAR_LAYOUT_TILED ? EMSAR_HIP_ERR_ARG : EMSAR_HIP_OK;
 }
-int ensure_sets_impl(emsar_hip_ctx *ctx) {
-    auto t0 = std::chrono::steady_clock::now();
-    auto &S = ctx->sets.RS;
-    try {
-        emsar::build_sets(ctx->n_rows, ctx->n_tx, ctx->h_row_ptr.data(), ctx->h_col.data(), ctx->h_wgt.data(), S);
-    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    if (ctx->layout == EMSAR_LAYOUT_TILED && !tid_map(ctx).empty()) {
-        // the sets were found on the caller's CSR; theta / den on the device are in the library's numbering
-        const auto &m = tid_map(ctx);
+
+// EMSAR_HIP_DEBUG: where the time of an upload goes
+struct UploadTrace {
+    const bool on = getenv("EMSAR_HIP_DEBUG") != nullptr;
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void say(const char *what) const {
+        if (on) fprintf(stderr, "upload_structure: %s after %.0f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
+};
+
+// the TILED layout built and on the device; the four launch knobs are read here
+int upload_tiled(emsar_hip_ctx *ctx, const uint64_t *row_ptr, const int32_t *col_idx, bool merge_rows, const UploadTrace &trace) {
+    auto &L = ctx->lay.TL;
+    LayoutDev &D = ctx->lay;
+    const size_t T = (size_t)ctx->n_tx;
+    const int brc = emsar::build_tiled(ctx->n_rows, ctx->n_tx, row_ptr, col_idx, L, merge_rows);
+    if (brc != 0) { ctx->err = "TILED layout builder: code " + std::to_string(brc); return EMSAR_HIP_ERR_ARG; }
+    trace.say("layout built");
+    D.n_tiles = (int64_t)L.tiles.size(); D.n_slots = L.n_slots(); D.n_left = (int64_t)L.left_row.size();
+    HIPCHK(D.d_tiles.upload(L.tiles.data(), L.tiles.size()));
+    HIPCHK(D.d_units.upload(L.unit_first.data(), L.unit_first.size()));
+    D.n_units = L.unit_first.empty() ? 0 : (int64_t)L.unit_first.size() - 1;
+    {
+        emsar::UnitTables U;
+        emsar::build_unit_tables(L, U);
+        D.unit_stride = U.stride;
+        HIPCHK(D.d_utiles.upload(U.utiles.data(), U.utiles.size()));
+    }
+    HIPCHK(D.d_fwd.upload(L.fwd.data(), L.fwd.size()));
+    HIPCHK(D.d_bwd.upload(L.bwd.data(), L.bwd.size()));
+    HIPCHK(D.d_far.upload(L.far_tid.data(), L.far_tid.size()));
+    HIPCHK(D.d_left_ptr.upload(L.left_ptr.data(), L.left_ptr.size()));
+    HIPCHK(D.d_left_col.upload(L.left_col.data(), L.left_col.size()));
+    HIPCHK(D.d_u.alloc(T));
+    HIPCHK(hipMemset(D.d_u, 0, T * 8));
+    ctx->bytes_stored = (int64_t)L.fwd.size() * 4 + (int64_t)L.bwd.size() * 4 + (int64_t)L.far_tid.size() * 4 +
+                        (int64_t)L.tiles.size() * 64 + (int64_t)L.left_col.size() * 4 + (int64_t)L.left_ptr.size() * 8;
+    ctx->tl_fwd_slots = L.padded_slots; ctx->tl_n_fslices = L.n_fslices;
+    emsar::u32_vec().swap(L.fwd); emsar::u32_vec().swap(L.bwd);
+    std::vector<int32_t>().swap(L.left_col);
+    HIPCHK(set_tiled_lds_attributes());
+    { const char *pe = getenv("EMSAR_HIP_WEIGHTED_UNIT"); ctx->weighted_unit = pe ? atoi(pe) : 1; }
+    { const char *pe = getenv("EMSAR_HIP_TILED_MULTI"); ctx->tiled_multi = pe ? atoi(pe) : 1; }
+    { const char *pe = getenv("EMSAR_HIP_UPDATE_GRID"); if (pe && atoi(pe) >= 1) ctx->update_grid = atoi(pe); }
+    { const char *pe = getenv("EMSAR_HIP_SQ_GRID"); if (pe && atoi(pe) >= 1) ctx->sq_grid = atoi(pe); }
+    return EMSAR_HIP_OK;
+}
+
+// the caller's CSR as it is, row_ptr narrowed to 32 bits when nnz allows
+int upload_csr(emsar_hip_ctx *ctx, const uint64_t *row_ptr, const int32_t *col_idx) {
+    const int64_t n_rows = ctx->n_rows;
+    if (ctx->ptr64) {
+        HIPCHK(ctx->lay.d_row_ptr.upload(row_ptr, ((size_t)n_rows + 1) * 8));
+    } else {
+        std::vector<uint32_t> rp((size_t)n_rows + 1);
+        for (int64_t r = 0; r <= n_rows; r++) rp[(size_t)r] = (uint32_t)row_ptr[r];
+        HIPCHK(ctx->lay.d_row_ptr.upload(rp.data(), rp.size() * 4));
+    }
+    HIPCHK(ctx->lay.d_col.upload(col_idx, (size_t)ctx->nnz));
+    ctx->bytes_stored = ctx->nnz * 4 + (n_rows + 1) * (ctx->ptr64 ? 8 : 4);
+    return EMSAR_HIP_OK;
+}
+
+int alloc_tx_vectors(emsar_hip_ctx *ctx) {
+    const size_t T = (size_t)ctx->n_tx;
+    HIPCHK(ctx->vec.d_den.alloc(T));
+    HIPCHK(ctx->vec.d_acc.alloc(T));
+    for (auto &p : ctx->vec.d_th) HIPCHK(p.alloc(T));
+    for (auto &p : ctx->vec.d_tmp) HIPCHK(p.alloc(T));
+    HIPCHK(ctx->vec.d_itmp.alloc(T));
+    HIPCHK(hipMemset(ctx->vec.d_acc, 0, T * 8));
+    return EMSAR_HIP_OK;
+}
+
+// a new structure into an emptied context; the caller frees what a failing exit leaves half built
+int upload_structure_impl(emsar_hip_ctx *ctx, int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr, const int32_t *col_idx, int layout, bool merge_rows) {
+    ctx->n_rows = n_rows; ctx->n_tx = n_tx; ctx->nnz = (int64_t)row_ptr[n_rows];
+    ctx->ptr64 = (uint64_t)ctx->nnz >= (1ull << 32);
+    if (const char *e = getenv("EMSAR_HIP_FORCE_PTR64")) { if (atoi(e) != 0) ctx->ptr64 = true; }   // test hook: the 64-bit row_ptr kernels on small inputs
+    ctx->layout = layout;
+    const UploadTrace trace;
+    // the host copy of the CSR kept for the set-resident solver (built per sample: sets depend on which rows carry reads)
+    // is made by a second thread while this one builds the device layout from the same arrays
+    bool copy_failed = false;
+    std::thread csr_copy([&] {
         try {
-            std::vector<uint8_t> kind(S.kind.size());
-            std::vector<double> usum(S.usum.size());
-            for (size_t t = 0; t < m.size(); t++) { kind[(size_t)m[t]] = S.kind[t]; usum[(size_t)m[t]] = S.usum[t]; }
-            S.kind.swap(kind); S.usum.swap(usum);
-        } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-        for (int32_t &t : S.g_tid) t = m[(size_t)t];
-        for (int32_t &t : S.CL.g_tid) t = m[(size_t)t];
-    }
-    HIPCHK(ctx->sets.d_kind.upload(S.kind.data(), S.kind.size()));
-    HIPCHK(ctx->sets.d_usum.upload(S.usum.data(), S.usum.size()));
-    const int64_t n = S.n_resident();
-    if (n > 0) {
-        HIPCHK(ctx->sets.d_g_tid.upload(S.g_tid.data(), S.g_tid.size()));
-        HIPCHK(ctx->sets.d_g_u.upload(S.g_u.data(), S.g_u.size()));
-        HIPCHK(ctx->sets.d_row_w.upload(S.row_w.data(), S.row_w.size()));
-        HIPCHK(ctx->sets.d_srp.upload(S.rp.data(), S.rp.size()));
-        HIPCHK(ctx->sets.d_sent.upload(S.ent.data(), S.ent.size()));
-        HIPCHK(ctx->sets.d_scp.upload(S.cp.data(), S.cp.size()));
-        HIPCHK(ctx->sets.d_scrow.upload(S.crow.data(), S.crow.size()));
-        for (int c = 0; c < emsar::kSetClasses; c++)
-            if (!S.desc[c].empty()) HIPCHK(ctx->sets.d_sdesc[c].upload(S.desc[c].data(), S.desc[c].size()));
-        HIPCHK(ctx->sets.d_sstat.alloc((size_t)n));
-        HIPCHK(ctx->sets.h_sstat.alloc((size_t)n));
-        ctx->sets.n_sstat = n;
-        HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[0]));
-        HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[1]));
-        HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[2]));
-    }
-    const int64_t nc = S.n_cluster_sets();
-    if (nc > 0) {
-        auto &CL = S.CL;
-        HIPCHK(ctx->sets.d_cdesc.upload(CL.desc.data(), CL.desc.size()));
-        HIPCHK(ctx->sets.d_cblk.upload(CL.blk_set.data(), CL.blk_set.size()));
-        HIPCHK(ctx->sets.d_crp.upload(CL.rp.data(), CL.rp.size()));
-        HIPCHK(ctx->sets.d_ccp.upload(CL.cp.data(), CL.cp.size()));
-        HIPCHK(ctx->sets.d_cpart.upload(CL.part.data(), CL.part.size()));
-        HIPCHK(ctx->sets.d_cent.upload(CL.ent.data(), CL.ent.size()));
-        HIPCHK(ctx->sets.d_ccrow.upload(CL.crow.data(), CL.crow.size()));
-        HIPCHK(ctx->sets.d_cg_tid.upload(CL.g_tid.data(), CL.g_tid.size()));
-        HIPCHK(ctx->sets.d_cg_u.upload(CL.g_u.data(), CL.g_u.size()));
-        HIPCHK(ctx->sets.d_crow_w.upload(CL.row_w.data(), CL.row_w.size()));
-        HIPCHK(ctx->sets.d_cscratch.alloc((size_t)CL.scratch_doubles));
-        HIPCHK(ctx->sets.d_cbar.alloc((size_t)nc * 2));
-        HIPCHK(ctx->sets.d_cstat.alloc((size_t)nc));
-        HIPCHK(ctx->sets.h_cstat.alloc((size_t)nc));
-        ctx->sets.n_cstat = nc;
-        HIPCHK(hipFuncSetAttribute((const void *)k_solve_cluster, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kClusterLdsCap));
-        // only the sizes are needed from here on
-        std::vector<uint32_t>().swap(CL.rp); std::vector<uint32_t>().swap(CL.cp); std::vector<uint16_t>().swap(CL.ent); std::vector<uint16_t>().swap(CL.crow);
-        std::vector<int32_t>().swap(CL.g_tid); std::vector<double>().swap(CL.g_u); std::vector<double>().swap(CL.row_w);
-    }
-    // the device copies are the only ones needed from here on (desc sizes and counters stay)
-    std::vector<int32_t>().swap(S.g_tid); std::vector<double>().swap(S.g_u); std::vector<double>().swap(S.row_w);
-    std::vector<uint16_t>().swap(S.rp); std::vector<uint16_t>().swap(S.ent); std::vector<uint16_t>().swap(S.cp); std::vector<uint16_t>().swap(S.crow);
-    std::vector<double>().swap(S.usum);
-    ctx->sets_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    ctx->sets.sets_ready = true;
-    return EMSAR_HIP_OK;
-}
-
-// The three size classes of the set solver are independent (disjoint sets, disjoint theta entries): the larger two run on side streams next to
-// the 64-thread class.  fork_side_streams: the first n_side side streams wait for ctx->stream; launch_set_classes: launch(class, threads,
-// stream) for every class that has sets, the big ones first (the fewest, the longest per pass), then ctx->stream waits for those side streams.
-int fork_side_streams(emsar_hip_ctx *ctx, int n_side) {
-    HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
-    for (int i = 0; i < n_side; i++) HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0));
-    return EMSAR_HIP_OK;
-}
-template <class Launch>
-int launch_set_classes(emsar_hip_ctx *ctx, int n_side, const Launch &launch) {
-    const hipStream_t st[emsar::kSetClasses] = {ctx->stream, ctx->side[0], ctx->side[1]};
-    for (int c = emsar::kSetClasses - 1; c >= 0; c--) if (!ctx->sets.RS.desc[c].empty()) launch(c, emsar::kSetThreads[c], st[c]);
-    for (int i = 0; i < n_side; i++) {
-        HIPCHK(hipEventRecord(ctx->ev_join[i], ctx->side[i]));
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
-    }
-    HIPCHK(hipGetLastError());
-    return EMSAR_HIP_OK;
-}
-
-// closed-form transcripts and every LDS-resident set, written into theta (the streamed sets' entries are left alone)
-int solve_resident_sets(emsar_hip_ctx *ctx, const SetSolveParams &P, const SetSolveParams &Pcluster, double *theta) {
-    const auto &S = ctx->sets.RS;
-    hipLaunchKernelGGL(k_closed_form, dim3(grid_for(ctx->n_tx, 256)), dim3(256), 0, ctx->stream, ctx->n_tx, ctx->sets.d_kind, ctx->sets.d_usum,
-                       ctx->vec.d_den, theta);
-    const size_t off[3] = {0, S.desc[0].size(), S.desc[0].size() + S.desc[1].size()};      // per-set results in class order
-    if (const int rc = fork_side_streams(ctx, 3)) return rc;
-    if (ctx->sets.n_cstat > 0) {
-        // The clusters, on a stream of their own.  Every workgroup of a launch must be resident at once (they wait for each other at
-        // the cluster barriers): at most one workgroup per CU per launch -- each asks for most of a CU's LDS --, whole sets only.
-        const int n_cu = ctx->n_cu;
-        HIPCHK(hipMemsetAsync(ctx->sets.d_cbar, 0, (size_t)ctx->sets.n_cstat * 2 * sizeof(unsigned), ctx->side[2]));
-        HIPCHK(hipEventRecord(ctx->ev_c0, ctx->side[2]));
-        const auto &D = S.CL.desc;
-        size_t first = 0;
-        while (first < D.size()) {
-            size_t last = first, wgs = 0;
-            while (last < D.size() && (wgs == 0 || wgs + D[last].g <= (size_t)n_cu)) wgs += D[last++].g;
-            hipLaunchKernelGGL(k_solve_cluster, dim3((unsigned)wgs), dim3(emsar::kClusterThreads), S.CL.max_lds, ctx->side[2], ctx->sets.d_cdesc, ctx->sets.d_cblk,
-                               D[first].blk0, ctx->sets.d_cg_tid, ctx->sets.d_cg_u, ctx->sets.d_crow_w, ctx->sets.d_crp, ctx->sets.d_cent, ctx->sets.d_ccp, ctx->sets.d_ccrow, ctx->sets.d_cpart,
-                               ctx->sets.d_cscratch, ctx->sets.d_cbar, ctx->sets.d_cbar + ctx->sets.n_cstat, ctx->vec.d_den, theta, ctx->sets.d_cstat, Pcluster);
-            first = last;
-        }
-        HIPCHK(hipEventRecord(ctx->ev_c1, ctx->side[2]));
-        // The workgroups of a cluster wait for each other inside the launch, so all of them must get a CU: nothing else may hold CUs while
-        // the cluster batches run (k_solve_sets<512> asks for most of a CU's LDS too).  The size classes below start after the clusters.
-        HIPCHK(hipStreamWaitEvent(ctx->side[0], ctx->ev_c1, 0));
-        HIPCHK(hipStreamWaitEvent(ctx->side[1], ctx->ev_c1, 0));
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_c1, 0));
-    }
-    return launch_set_classes(ctx, 3, [&](int c, int threads, hipStream_t st) {
-        hipLaunchKernelGGL((c == 2 ? k_solve_sets<512> : c == 1 ? k_solve_sets<256> : k_solve_sets<64>), dim3((unsigned)S.desc[c].size()), dim3(threads),
-                           S.max_lds[c], st, ctx->sets.d_sdesc[c], ctx->sets.d_g_tid, ctx->sets.d_g_u, ctx->sets.d_row_w, ctx->sets.d_srp, ctx->sets.d_sent, ctx->sets.d_scp,
-                           ctx->sets.d_scrow, ctx->vec.d_den, theta, ctx->sets.d_sstat + off[c], P);
+            ctx->h_row_ptr.assign(row_ptr, row_ptr + n_rows + 1);
+            ctx->h_col.assign(col_idx, col_idx + ctx->nnz);
+        } catch (const std::bad_alloc &) { copy_failed = true; }
     });
+    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{csr_copy};
+    try {
+        if (const int rc = layout == EMSAR_LAYOUT_TILED ? upload_tiled(ctx, row_ptr, col_idx, merge_rows, trace) : upload_csr(ctx, row_ptr, col_idx)) return rc;
+    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
+    trace.say("device copies done");
+    csr_copy.join();
+    if (copy_failed) return EMSAR_HIP_ERR_OOM;
+    trace.say("host CSR copy joined");
+    if (const int rc = alloc_tx_vectors(ctx)) return rc;
+    ctx->have_structure = true;
+    return EMSAR_HIP_OK;
 }
 
 }  // namespace
@@ -749,98 +568,16 @@ void emsar_hip_destroy(emsar_hip_ctx *ctx) {
 int emsar_hip_upload_structure(emsar_hip_ctx *ctx, int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr,
                                const int32_t *col_idx, int layout) {
     if (!ctx) return EMSAR_HIP_ERR_ARG;
-    const bool merge_rows = (layout & EMSAR_LAYOUT_FLAG_MERGE_ROWS) != 0;
-    layout &= ~EMSAR_LAYOUT_FLAG_MERGE_ROWS;
-    if (layout != EMSAR_LAYOUT_AUTO && layout != EMSAR_LAYOUT_CSR && layout != EMSAR_LAYOUT_TILED) return EMSAR_HIP_ERR_ARG;
-    if (merge_rows && layout != EMSAR_LAYOUT_AUTO && layout != EMSAR_LAYOUT_TILED) return EMSAR_HIP_ERR_ARG;
+    // arguments first: a rejected call changes nothing
+    bool merge_rows = false;
+    if (choose_layout(n_rows, layout, merge_rows) != EMSAR_HIP_OK) return EMSAR_HIP_ERR_ARG;
     if (emsar::validate_csr(n_rows, n_tx, row_ptr, col_idx) != 0) return EMSAR_HIP_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     free_structure(ctx);
-    ctx->n_rows = n_rows; ctx->n_tx = n_tx; ctx->nnz = (int64_t)row_ptr[n_rows];
-    ctx->ptr64 = (uint64_t)ctx->nnz >= (1ull << 32);
-    if (const char *e = getenv("EMSAR_HIP_FORCE_PTR64")) { if (atoi(e) != 0) ctx->ptr64 = true; }   // test hook: the 64-bit row_ptr kernels on small inputs
-    if (layout == EMSAR_LAYOUT_AUTO) {
-        layout = (n_rows < ((int64_t)1 << 32)) ? EMSAR_LAYOUT_TILED : EMSAR_LAYOUT_CSR;
-        if (const char *e = getenv("EMSAR_HIP_LAYOUT")) { int v = atoi(e); if ((v == 1 || v == 3) && (v == 1 || n_rows < ((int64_t)1 << 32))) layout = v; }
-        if (merge_rows && layout != EMSAR_LAYOUT_TILED) return EMSAR_HIP_ERR_ARG;
-    }
-    ctx->layout = layout;
-    const size_t T = (size_t)n_tx;
-    const bool dbg = getenv("EMSAR_HIP_DEBUG") != nullptr;
-    const auto tu0 = std::chrono::steady_clock::now();
-    auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
-    // the host copy of the CSR kept for the set-resident solver (built per sample: sets depend on which rows carry reads)
-    // is made by a second thread while this one builds the device layout from the same arrays
-    bool copy_failed = false;
-    std::thread csr_copy([&] {
-        try {
-            ctx->h_row_ptr.assign(row_ptr, row_ptr + n_rows + 1);
-            ctx->h_col.assign(col_idx, col_idx + ctx->nnz);
-        } catch (const std::bad_alloc &) { copy_failed = true; }
-    });
-    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{csr_copy};
-    try {
-        if (layout == EMSAR_LAYOUT_TILED) {
-            auto &L = ctx->lay.TL;
-            const int brc = emsar::build_tiled(n_rows, n_tx, row_ptr, col_idx, L, merge_rows);
-            if (brc != 0) { ctx->err = "TILED layout builder: code " + std::to_string(brc); return EMSAR_HIP_ERR_ARG; }
-            if (dbg) fprintf(stderr, "upload_structure: layout built after %.0f ms\n", since(tu0));
-            ctx->lay.n_tiles = (int64_t)L.tiles.size(); ctx->lay.n_slots = L.n_slots(); ctx->lay.n_left = (int64_t)L.left_row.size();
-            HIPCHK(ctx->lay.d_tiles.upload(L.tiles.data(), L.tiles.size()));
-            HIPCHK(ctx->lay.d_units.upload(L.unit_first.data(), L.unit_first.size()));
-            ctx->lay.n_units = L.unit_first.empty() ? 0 : (int64_t)L.unit_first.size() - 1;
-            {
-                emsar::UnitTables U;
-                emsar::build_unit_tables(L, U);
-                ctx->lay.unit_stride = U.stride;
-                HIPCHK(ctx->lay.d_utiles.upload(U.utiles.data(), U.utiles.size()));
-            }
-            HIPCHK(ctx->lay.d_fwd.upload(L.fwd.data(), L.fwd.size()));
-            HIPCHK(ctx->lay.d_bwd.upload(L.bwd.data(), L.bwd.size()));
-            HIPCHK(ctx->lay.d_far.upload(L.far_tid.data(), L.far_tid.size()));
-            HIPCHK(ctx->lay.d_left_ptr.upload(L.left_ptr.data(), L.left_ptr.size()));
-            HIPCHK(ctx->lay.d_left_col.upload(L.left_col.data(), L.left_col.size()));
-            HIPCHK(ctx->lay.d_u.alloc(T));
-            HIPCHK(hipMemset(ctx->lay.d_u, 0, T * 8));
-            ctx->bytes_stored = (int64_t)L.fwd.size() * 4 + (int64_t)L.bwd.size() * 4 + (int64_t)L.far_tid.size() * 4 +
-                                (int64_t)L.tiles.size() * 64 + (int64_t)L.left_col.size() * 4 + (int64_t)L.left_ptr.size() * 8;
-            ctx->tl_fwd_slots = L.padded_slots; ctx->tl_n_fslices = L.n_fslices;
-            emsar::u32_vec().swap(L.fwd); emsar::u32_vec().swap(L.bwd);
-            std::vector<int32_t>().swap(L.left_col);
-            HIPCHK(set_tiled_lds_attributes());
-            { const char *pe = getenv("EMSAR_HIP_WEIGHTED_UNIT"); ctx->weighted_unit = pe ? atoi(pe) : 1; }
-            { const char *pe = getenv("EMSAR_HIP_TILED_MULTI"); ctx->tiled_multi = pe ? atoi(pe) : 1; }
-            { const char *pe = getenv("EMSAR_HIP_UPDATE_GRID"); if (pe && atoi(pe) >= 1) ctx->update_grid = atoi(pe); }
-            { const char *pe = getenv("EMSAR_HIP_SQ_GRID"); if (pe && atoi(pe) >= 1) ctx->sq_grid = atoi(pe); }
-        } else {
-            if (ctx->ptr64) {
-                HIPCHK(ctx->lay.d_row_ptr.upload(row_ptr, ((size_t)n_rows + 1) * 8));
-            } else {
-                std::vector<uint32_t> rp((size_t)n_rows + 1);
-                for (int64_t r = 0; r <= n_rows; r++) rp[(size_t)r] = (uint32_t)row_ptr[r];
-                HIPCHK(ctx->lay.d_row_ptr.upload(rp.data(), rp.size() * 4));
-            }
-            HIPCHK(ctx->lay.d_col.upload(col_idx, (size_t)ctx->nnz));
-            ctx->bytes_stored = ctx->nnz * 4 + (n_rows + 1) * (ctx->ptr64 ? 8 : 4);
-        }
-    } catch (const std::bad_alloc &) {
-        csr_copy.join();
-        free_structure(ctx);
-        return EMSAR_HIP_ERR_OOM;
-    }
-    if (dbg) fprintf(stderr, "upload_structure: device copies done after %.0f ms\n", since(tu0));
-    csr_copy.join();
-    if (copy_failed) { free_structure(ctx); return EMSAR_HIP_ERR_OOM; }
-    if (dbg) fprintf(stderr, "upload_structure: host CSR copy joined after %.0f ms\n", since(tu0));
-    HIPCHK(ctx->vec.d_den.alloc(T));
-    HIPCHK(ctx->vec.d_acc.alloc(T));
-    for (auto &p : ctx->vec.d_th) HIPCHK(p.alloc(T));
-    for (auto &p : ctx->vec.d_tmp) HIPCHK(p.alloc(T));
-    HIPCHK(ctx->vec.d_itmp.alloc(T));
-    HIPCHK(hipMemset(ctx->vec.d_acc, 0, T * 8));
-    ctx->have_structure = true;
-    return EMSAR_HIP_OK;
+    const int rc = upload_structure_impl(ctx, n_rows, n_tx, row_ptr, col_idx, layout, merge_rows);
+    if (rc != EMSAR_HIP_OK) free_structure(ctx);         // a half-built structure is freed, whatever the failing exit
+    return rc;
 }
 
 int emsar_hip_upload_sample(emsar_hip_ctx *ctx, const int32_t *row_weight, const double *row_E, const double *den) {
@@ -927,196 +664,6 @@ int emsar_hip_get_theta(emsar_hip_ctx *ctx, double *theta) {
     HIPCHK(hipMemcpyAsync(theta, ctx->vec.d_th[0], (size_t)ctx->n_tx * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     try { from_lib(ctx, theta); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    return EMSAR_HIP_OK;
-}
-
-int emsar_hip_run_passes(emsar_hip_ctx *ctx, int32_t n_passes, float *elapsed_ms, double *last_ll) {
-    if (!ctx || n_passes < 0) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->delta_mask = nullptr;
-    hipLaunchKernelGGL(k_cycle_begin, dim3(1), dim3(kLlSlots), 0, ctx->stream, ctx->d_scal, 0.0, 0);
-    HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-    int cur = 0;  // th[cur] holds the current point, th[cur^1] receives the next
-    for (int i = 0; i < n_passes; i++) {
-        bool ll = last_ll && i == n_passes - 1;
-        int rc = em_pass(ctx, ctx->vec.d_th[cur], ctx->vec.d_th[cur ^ 1], ll, 0, 1e-6);
-        if (rc) return rc;
-        cur ^= 1;
-    }
-    HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
-    if (cur == 1) HIPCHK(hipMemcpyAsync(ctx->vec.d_th[0], ctx->vec.d_th[1], (size_t)ctx->n_tx * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->h_scal, ctx->d_scal, sizeof(Scal), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (elapsed_ms) HIPCHK(hipEventElapsedTime(elapsed_ms, ctx->ev0, ctx->ev1));
-    if (last_ll) *last_ll = host_ll(ctx, 0);
-    return EMSAR_HIP_OK;
-}
-
-static int solve_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpkm_out, emsar_em_stats *stats);
-// the caller's parameters with the defaults filled in
-static emsar_em_params solve_params(const emsar_em_params *pp) {
-    emsar_em_params p = pp ? *pp : emsar_em_params{0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (p.max_iter <= 0) p.max_iter = 100000;
-    if (p.tol <= 0) p.tol = 1e-10;
-    if (p.abs_floor <= 0) p.abs_floor = 1e-6;
-    if (p.check_every <= 0) p.check_every = 8;
-    return p;
-}
-// what the resident sets get of them
-static SetSolveParams set_params(const emsar_em_params &p) {
-    // zero_cut / abs_step exist because a boundary optimum is approached like 1/k by the EM; the sets that get Newton steps reach it
-    // in a few steps and are held to the strict rule (same pass counts with and without the two rules on every problem measured,
-    // and then nothing is printed differently); the rules stay in force for the streamed part and with newton_after < 0
-    const bool strict_sets = p.newton_after >= 0;
-    return SetSolveParams{p.tol, p.abs_floor, p.count_floor, (!strict_sets && p.zero_cut > 0.0) ? p.zero_cut : 0.0,
-                          (!strict_sets && p.abs_step > 0.0) ? p.abs_step : 0.0, p.max_iter, p.accel, p.newton_after == 0 ? 60 : p.newton_after};
-}
-int emsar_hip_solve(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpkm_out, emsar_em_stats *stats) {
-    if (!ctx || !fpkm_out) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
-    const int rc = solve_impl(ctx, pp, fpkm_out, stats);
-    clear_solve_state(ctx);
-    return rc;
-}
-static int solve_impl(emsar_hip_ctx *ctx, const emsar_em_params *pp, double *fpkm_out, emsar_em_stats *stats) {
-    emsar_em_params p = solve_params(pp);
-    if (!(p.count_floor >= 0.0)) return EMSAR_HIP_ERR_ARG;
-    if (p.set_mode != 0 && p.set_mode != 1) return EMSAR_HIP_ERR_ARG;
-    ctx->count_floor = p.count_floor;
-    ctx->zero_cut = p.zero_cut > 0.0 ? p.zero_cut : 0.0;
-    const double abs_step_base = p.abs_step > 0.0 ? p.abs_step : 0.0;
-    ctx->delta_mask = nullptr;
-    HIPCHK(hipSetDevice(ctx->device));
-    int rc;
-    bool use_sets = p.set_mode == 0;
-    if (use_sets && (rc = ensure_sets(ctx))) return rc;
-    if (use_sets && ctx->sets.RS.giant) use_sets = false;      // one component holds most transcripts: plain streaming solve
-    // the streaming passes run when asked for, or for the sets that do not fit a workgroup
-    const bool need_stream = !use_sets || ctx->sets.RS.n_streamed_sets > 0;
-    if (use_sets && need_stream) ctx->delta_mask = ctx->sets.d_kind;
-    auto t0 = std::chrono::steady_clock::now();
-    if ((rc = emsar_hip_reset_theta(ctx))) return rc;
-    hipLaunchKernelGGL(k_scal_init, dim3(1), dim3(1), 0, ctx->stream, ctx->d_scal);
-    HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-    const int n = ctx->n_tx, g = grid_for(n, 256);
-    DevBuf<double> *th = ctx->vec.d_th;  // 0:th0 1:th1 2:th2 3:thx 4:thn (enqueue_cycles leaves the current point in th[0])
-    int iters = 0, converged = need_stream ? 0 : 1, cycles = 0;
-    double delta = need_stream ? INFINITY : 0.0;
-    // The first 4 x check_every cycles are launched kernel by kernel (a quick solve never pays for a graph); after that
-    // check_every cycles are recorded once into a hipGraph and replayed between the host's looks at the stopping rule.
-    // Measured gain: 1-5 % on problems of 40 k .. 2 M rows (tools/graph_bench.py) -- the launches were already asynchronous,
-    // and a pass of a small problem costs one workgroup's latency (12-26 us), not its launch.
-    const int per_cycle = p.accel ? 3 : 1;
-    const bool graph_ok = ctx->use_graph && (p.accel || p.check_every % 2 == 0);   // plain EM swaps th0/th1: an even count restores them
-    CycleGraph G;
-    ctx->graph_launches = 0;
-    while (need_stream && iters < p.max_iter) {
-        int todo = 1;
-        if (graph_ok && cycles >= 4 * p.check_every && cycles % p.check_every == 0 &&
-            (int64_t)iters + (int64_t)per_cycle * p.check_every <= (int64_t)p.max_iter) {
-            todo = p.check_every;
-            if (!G.exec) {
-                HIPCHK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-                rc = enqueue_cycles(ctx, p, abs_step_base, todo);
-                hipError_t e = hipStreamEndCapture(ctx->stream, &G.graph);      // always closes the capture
-                if (rc) return rc;
-                HIPCHK(e);
-                HIPCHK(hipGraphInstantiate(&G.exec, G.graph, nullptr, nullptr, 0));
-            }
-            HIPCHK(hipGraphLaunch(G.exec, ctx->stream));
-            ctx->graph_launches++;
-        } else if ((rc = enqueue_cycles(ctx, p, abs_step_base, 1))) return rc;
-        cycles += todo;
-        iters += todo * per_cycle;
-        if (cycles % p.check_every == 0 || iters >= p.max_iter) {
-            HIPCHK(hipMemcpyAsync(ctx->h_scal, ctx->d_scal, sizeof(Scal), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            unsigned long long bits = p.accel ? ctx->h_scal->delta1_bits : ctx->h_scal->delta_bits;
-            memcpy(&delta, &bits, 8);
-            if (!std::isfinite(delta) || ctx->h_scal->bad) { ctx->err = "non-finite theta"; return EMSAR_HIP_ERR_NUMERIC; }
-            if (delta < p.tol) { converged = 1; break; }
-        }
-    }
-    ctx->delta_mask = nullptr;
-    HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
-    if (use_sets) {
-        const SetSolveParams P = set_params(p);
-        // the cluster solver has no Newton step: its sets keep the two print-quantum rules whatever newton_after says (with the strict rule
-        // alone a boundary optimum keeps a cluster going for 10^5 passes at ~32 us each)
-        SetSolveParams Pc = P;
-        Pc.zero_cut = p.zero_cut > 0.0 ? p.zero_cut : 0.0;
-        Pc.abs_step = p.abs_step > 0.0 ? p.abs_step : 0.0;
-        if ((rc = solve_resident_sets(ctx, P, Pc, th[0]))) return rc;
-        if (ctx->sets.n_sstat > 0)
-            HIPCHK(hipMemcpyAsync(ctx->sets.h_sstat, ctx->sets.d_sstat, (size_t)ctx->sets.n_sstat * sizeof(SetStat), hipMemcpyDeviceToHost, ctx->stream));
-        if (ctx->sets.n_cstat > 0)
-            HIPCHK(hipMemcpyAsync(ctx->sets.h_cstat, ctx->sets.d_cstat, (size_t)ctx->sets.n_cstat * sizeof(ClusterStat), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(hipEventRecord(ctx->ev2, ctx->stream));
-    // F at the returned point: one likelihood-only pass (not counted in iters)
-    hipLaunchKernelGGL(k_cycle_begin, dim3(1), dim3(kLlSlots), 0, ctx->stream, ctx->d_scal, 0.0, 0);
-    if ((rc = launch_pass(ctx, MODE_EM_LL, th[0], ctx->vec.d_acc, &ctx->d_scal->ll[0].s[0].v))) return rc;
-    HIPCHK(hipMemsetAsync(ctx->vec.d_acc, 0, (size_t)n * 8, ctx->stream));
-    hipLaunchKernelGGL(k_dot, dim3(1), dim3(1024), 0, ctx->stream, n, th[0], ctx->vec.d_den, &ctx->d_scal->ll[3].s[0].v);
-    HIPCHK(hipMemcpyAsync(ctx->h_scal, ctx->d_scal, sizeof(Scal), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(fpkm_out, th[0], (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    try { from_lib(ctx, fpkm_out); } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    ctx->count_floor = 0.0; ctx->zero_cut = 0.0;
-    if (getenv("EMSAR_HIP_DEBUG"))
-        fprintf(stderr, "emsar_hip_solve: %d streaming passes, %lld graph replays of %d cycles\n", iters, (long long)ctx->graph_launches, p.check_every);
-    for (int32_t t = 0; t < n; t++)
-        if (!std::isfinite(fpkm_out[t])) { ctx->err = "non-finite theta"; return EMSAR_HIP_ERR_NUMERIC; }
-    int32_t set_max = 0, set_unconv = 0;
-    int64_t set_sum = 0;
-    if (use_sets)
-        for (int64_t i = 0; i < ctx->sets.n_sstat; i++) {
-            const SetStat &q = ctx->sets.h_sstat[i];
-            set_max = std::max(set_max, q.passes); set_sum += q.passes;
-            if (!q.converged) set_unconv++;
-            if (!std::isfinite(q.delta)) { ctx->err = "non-finite theta in a connected set"; return EMSAR_HIP_ERR_NUMERIC; }
-            if (q.delta > delta) delta = q.delta;
-        }
-    int32_t cl_max = 0;
-    if (use_sets)
-        for (int64_t i = 0; i < ctx->sets.n_cstat; i++) {
-            const ClusterStat &q = ctx->sets.h_cstat[i];
-            if (q.aborted) { ctx->err = "a workgroup cluster gave up waiting at its barrier"; return EMSAR_HIP_ERR_HIP; }
-            cl_max = std::max(cl_max, q.passes); set_sum += q.passes;
-            if (!q.converged) set_unconv++;
-            if (!std::isfinite(q.delta)) { ctx->err = "non-finite theta in a connected set"; return EMSAR_HIP_ERR_NUMERIC; }
-            if (q.delta > delta) delta = q.delta;
-        }
-    set_max = std::max(set_max, cl_max);
-    if (set_unconv) converged = 0;
-    if (stats) {
-        float ms = 0, ms_sets = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        HIPCHK(hipEventElapsedTime(&ms_sets, ctx->ev1, ctx->ev2));
-        memset(stats, 0, sizeof(*stats));
-        stats->iters = iters + set_max;
-        stats->converged = converged;
-        stats->final_delta = delta;
-        stats->loglik = host_ll(ctx, 0) + ctx->loglik_const - ctx->h_scal->ll[3].s[0].v;
-        stats->kernel_ms = ms + (use_sets ? ms_sets : 0.0f);
-        stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        stats->bytes_per_pass = ctx->bytes_formula;
-        stats->stored_bytes_per_pass = stored_bytes(ctx);
-        if (p.set_mode == 0 && ctx->sets.RS.giant) { stats->sets_streamed = 1; stats->sets_build_ms = ctx->sets_build_ms; }
-        if (use_sets) {
-            stats->sets_resident = (int32_t)ctx->sets.RS.n_resident();
-            stats->sets_streamed = (int32_t)ctx->sets.RS.n_streamed_sets;
-            stats->set_passes_max = set_max;
-            stats->sets_unconverged = set_unconv;
-            stats->set_passes_sum = set_sum;
-            stats->sets_build_ms = ctx->sets_build_ms;
-            stats->sets_kernel_ms = ms_sets;
-            stats->sets_cluster = (int32_t)ctx->sets.n_cstat;
-            stats->cluster_passes_max = cl_max;
-            if (ctx->sets.n_cstat > 0) { float mc = 0; HIPCHK(hipEventElapsedTime(&mc, ctx->ev_c0, ctx->ev_c1)); stats->cluster_kernel_ms = mc; }
-        }
-    }
     return EMSAR_HIP_OK;
 }
 
@@ -1209,72 +756,6 @@ int emsar_hip_get_info(const emsar_hip_ctx *ctx, emsar_hip_info *o) {
     return EMSAR_HIP_OK;
 }
 
-// Diagnostic only (not declared in the public header): one stamped pass of the TILED kernel on the current theta.
-// out[0..6] = mean cycles per wave spent in: loads issued + dictionary, barrier, E-step, barrier, M-step, barrier, flush;
-// out[7] = tiles.  The result vector theta is left untouched (acc is cleared again).
-int emsar_hip_debug_tiled_stamps(emsar_hip_ctx *ctx, double *out) {
-    if (!ctx || !out || ctx->layout != EMSAR_LAYOUT_TILED || !ctx->have_sample || ctx->weighted || ctx->lay.n_tiles == 0) return EMSAR_HIP_ERR_STATE;
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t nw = (size_t)ctx->lay.n_tiles * (kTiledThreads / 64), bytes = nw * 8 * sizeof(unsigned long long), lds = kTiledLds;
-    DevBuf<unsigned long long> d;
-    HIPCHK(d.alloc(nw * 8));
-    HIPCHK(hipMemsetAsync(d, 0, bytes, ctx->stream));
-    HIPCHK(hipFuncSetAttribute((const void *)k_pass_tiled<false, MODE_EM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_pass_tiled<false, MODE_EM, true>), dim3((unsigned)ctx->lay.n_tiles), dim3(kTiledThreads), lds, ctx->stream, ctx->lay.d_tiles,
-                       ctx->lay.d_fwd, ctx->lay.d_bwd, ctx->lay.d_far, ctx->rw.d_wgt, ctx->lay.d_rowval, ctx->vec.d_th[0], ctx->vec.d_acc, &ctx->d_scal->ll[3].s[0].v, Fx{0.0, 0.0}, d);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(ctx->vec.d_acc, 0, (size_t)ctx->n_tx * 8, ctx->stream));
-    std::vector<unsigned long long> h(nw * 8);
-    HIPCHK(hipMemcpyAsync(h.data(), d, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 7; i++) {
-        double sum = 0;
-        for (size_t w = 0; w < nw; w++) sum += (double)h[w * 8 + (size_t)i];
-        out[i] = sum / (double)nw;   // mean cycles per wave
-    }
-    out[7] = (double)ctx->lay.n_tiles;
-    return EMSAR_HIP_OK;
-}
-
-// The same for the unit kernel (the one config 3 runs): out[0..5] = mean cycles per wave in: descriptor + dictionary + first loads,
-// barrier, E-steps, M-steps, barrier, flush; out[6] = tiles per unit; out[7] = units.
-int emsar_hip_debug_unit_stamps(emsar_hip_ctx *ctx, double *out, unsigned long long *timeline /* NULL or 4 words per unit: start, end (100 MHz ticks), place, tiles */) {
-    if (!ctx || !out || ctx->layout != EMSAR_LAYOUT_TILED || !ctx->have_sample || ctx->weighted || ctx->lay.n_units == 0) return EMSAR_HIP_ERR_STATE;
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t nw = (size_t)ctx->lay.n_units * (kTiledThreads / 64), words = nw * 8 + (size_t)ctx->lay.n_units * 4, bytes = words * sizeof(unsigned long long), lds = kTiledLds;
-    DevBuf<unsigned long long> d;
-    HIPCHK(d.alloc(words));
-    HIPCHK(hipMemsetAsync(d, 0, bytes, ctx->stream));
-    HIPCHK(hipFuncSetAttribute((const void *)k_pass_tiled_unit<false, MODE_EM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_pass_tiled_unit<false, MODE_EM, true>), dim3((unsigned)ctx->lay.n_units), dim3(kTiledThreads), lds, ctx->stream, ctx->lay.d_utiles, ctx->lay.unit_stride,
-                       ctx->lay.d_far, ctx->lay.d_fwd, ctx->lay.d_bwd, ctx->rw.d_wgt, ctx->vec.d_th[0], ctx->vec.d_acc, &ctx->d_scal->ll[3].s[0].v, Fx{0.0, 0.0}, d);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(ctx->vec.d_acc, 0, (size_t)ctx->n_tx * 8, ctx->stream));
-    std::vector<unsigned long long> h(words);
-    HIPCHK(hipMemcpyAsync(h.data(), d, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (timeline) std::copy(h.begin() + (std::ptrdiff_t)(nw * 8), h.end(), timeline);
-    for (int i = 0; i < 7; i++) {
-        double sum = 0;
-        for (size_t w = 0; w < nw; w++) sum += (double)h[w * 8 + (size_t)i];
-        out[i] = sum / (double)nw;
-    }
-    out[7] = (double)ctx->lay.n_units;
-    return EMSAR_HIP_OK;
-}
-
-// Diagnostic only (not declared in the public header; needs no device): the name of the TILED pass kernel launch_pass picks for a sample
-// (weighted or not), a mode (0: EM, 1: EM with the likelihood, 2: scatter), a tile count and the two knobs' values.
-int emsar_hip_debug_pass_kernel(int weighted, int mode, int64_t n_tiles, int tiled_multi, int weighted_unit, char *out, size_t cap) {
-    if (!out || mode < MODE_EM || mode > MODE_SCATTER) return EMSAR_HIP_ERR_ARG;
-    const PassKernel k = choose_pass_kernel(weighted != 0, mode, n_tiles, tiled_multi, weighted_unit);
-    const char *const wt = k.weighted ? "true" : "false";
-    const int len = k.family == FAMILY_MULTI  ? snprintf(out, cap, "k_pass_tiled_multi<%s, %d, %d>", wt, k.mode, k.n_multi)
-                    : k.family == FAMILY_UNIT ? snprintf(out, cap, "k_pass_tiled_unit<%s, %d>", wt, k.mode)
-                                              : snprintf(out, cap, "k_pass_tiled<%s, %d>", wt, k.mode);
-    return len >= 0 && (size_t)len < cap ? EMSAR_HIP_OK : EMSAR_HIP_ERR_ARG;
-}
-
 int emsar_hip_layout_selfcheck_tiled(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr, const int32_t *col_idx,
                                      int merge_rows, emsar_hip_info *info_out) {
     try {
@@ -1325,5 +806,6 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 
 }  // extern "C"
 
+#include "solve.hpp"      // the set solver's driver and the solve driver: emsar_hip_solve, emsar_hip_run_passes
 #include "resample.hpp"   // the resampling driver and its entry points: bootstrap, genes, quantiles, subsampling
 #include "fit.hpp"        // the model fit and its entry points (after resample.hpp: the gene step is launch_gene_sums)

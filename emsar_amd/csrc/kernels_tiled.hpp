@@ -6,18 +6,22 @@ namespace {
 
 // ------------------------------------------------------------------------------------------------
 // k_pass_tiled: one EM pass over the TILED layout (layout_tiled.hpp).  One workgroup = 4 waves = the 4 slices of a tile.
-//   phase 0  every global load the wave needs first is issued at once (the three theta of the thread's dictionary block, 8
-//            forward columns, 8 backward segments); table: T[8b + m] = sum of the theta of block b's slots in subset m, the
-//            per-entry accumulators W[8b + m] = 0; barrier
+//   phase 0  every global load the wave needs first is issued at once (the tile's far list, 8 forward columns, 8 backward
+//            segments, then the four theta of the thread's dictionary block); table: T[16b + m] = sum of the theta of block b's
+//            slots in subset m, the per-entry accumulators W[16b + m] = 0; barrier
 //   phase E  the wave owns one slice (768 rows; lane l holds rows 64*i + l, i < 12): S_r = sum T[entry]  (LDS reads only, 10-bit
 //            entries = block and subset, padding is entry 0 = the empty subset: no branches), w_r = R_r / S_r -> the wave's own
 //            6 KiB of LDS
 //   phase M  the SAME wave walks the transposed index of its rows: a lane's segments (entry value + 11 row ids) are
 //            consecutive in entry order; it gathers w_r from LDS into a register sum and adds it to W[entry] when the
 //            entry changes.  No barrier between E and M.
-//   phase F  barrier; thread b folds the 8 accumulators of block b into its 3 transcripts (transcript i collects the subsets
-//            that hold it) and flushes them with one global FP64 atomic each
-// k_pass_tiled_unit (the default above 2048 tiles): the same for a UNIT of up to two tiles that share one dictionary.
+//   phase F  barrier; the near part is folded BY SLOT: thread s adds up the accumulators of the subsets of its block that hold
+//            slot s (8 of the block's 16) and flushes the sum to the slot's transcript with one global FP64 atomic; a far entry
+//            is flushed by the thread that fetched it
+// (kBlk = 4 slots per block: 60 blocks x 16 subset sums, 240 transcripts per dictionary)
+// k_pass_tiled_unit (the default above 2048 tiles, the kernel bench.py times): the same for a UNIT of up to two tiles that share one
+// dictionary, the E- and M-steps as tile_e_step / tile_m_step.  k_pass_tiled_multi<N> (opt-in): N tiles per workgroup, each with
+// its own dictionary.
 // HBM traffic: 10 bits per forward slot + 128 bits per 11 backward entries -- no row_ptr, no 32-bit tids.
 // ------------------------------------------------------------------------------------------------
 #ifndef EMSAR_UE_BATCH          // LDS gathers in flight per step of the E / M loops of the unit and multi kernels (tile_e_step,
@@ -29,7 +33,7 @@ namespace {
 constexpr int kTiledThreads = 256;                       // 4 wavefronts = 4 slices
 constexpr int kRPL = emsar::kRowsPerLane;                 // 12 rows per lane = twelve 10-bit ids per int4
 constexpr int kTiledWr = emsar::kTileSliceRows + 8;       // w_r of one slice (768) + the zero padding row
-constexpr int kTiledDictPad = emsar::kDictEntries;        // 960 table entries: 120 blocks x 8 subset sums (entry 0 = the empty subset = 0)
+constexpr int kTiledDictPad = emsar::kDictEntries;        // 960 table entries: 60 blocks x 16 subset sums (entry 0 = the empty subset = 0)
 constexpr int kBlk = emsar::kBlk;
 constexpr int kTiledLdsDoubles = 2 * kTiledDictPad + emsar::kTileSlices * kTiledWr;   // 40,192 B: 4 workgroups per CU
 
@@ -167,19 +171,20 @@ __device__ __forceinline__ DTile tile_load(const Tile *p /* wave-uniform */) {
     return T;
 }
 
-// ---- the dictionary of a tile (layout_tiled.hpp): near blocks of three transcripts with eight subset sums each, then one entry
-// per far transcript ----
-// Thread b < nb (the tile's near blocks, <= 120) fetches the three theta of block b and writes the eight subset sums T[8b + m];
-// the other threads fetch three far transcripts each (far entry i lives at T[8 nb + i] = its theta).  Everybody clears the
-// accumulators of what it wrote.  At the end of the tile the near part is folded BY SLOT: thread s (and s + 256) adds up the
-// subsets of its block that hold slot s and sends the sum to its transcript -- consecutive lanes add to consecutive transcripts,
-// 512 contiguous bytes per wave instruction (device-scope float atomics run at full rate only on contiguous addresses); a far
-// entry is flushed by the thread that fetched it.
+// ---- the dictionary of a tile (layout_tiled.hpp): near blocks of kBlk = 4 transcripts with NE = 16 subset sums each, then one
+// entry per far transcript ----
+// Thread b < nb (the tile's near blocks, <= 60) fetches the four theta of block b and writes the sixteen subset sums T[16b + m];
+// the threads that own no block (60 .. 255) fetch the far transcripts, strided (far entry i lives at T[16 nb + i] = its theta;
+// kFarMax makes that three each at most).  Everybody clears the accumulators of what it wrote.  At the end of the tile the near
+// part is folded BY SLOT: thread s < 240 adds up the subsets of its block that hold slot s and sends the sum to its transcript --
+// consecutive lanes add to consecutive transcripts, 512 contiguous bytes per wave instruction (device-scope float atomics run at
+// full rate only on contiguous addresses); a far entry is flushed by the thread that fetched it.
 struct BlockDict { double th[kBlk]; int tid[kBlk]; int stid[2]; };     // stid: the transcripts of near SLOTS threadIdx.x and threadIdx.x + 256
 constexpr int kSlotsPerThread = (emsar::kTileDict + kTiledThreads - 1) / kTiledThreads;
 static_assert(kSlotsPerThread <= 2, "BlockDict::stid");
 static_assert(emsar::kFarMax <= kBlk * (kTiledThreads - emsar::kDictBlocks), "kBlk far entries per thread that owns no near block");
-// the far list of a unit (n transcripts at far), three per thread that owns no near block
+// the far list of a tile or unit (n transcripts at far) into D.tid, strided over the threads that own no near block.  Always
+// issued before block_dict_issue: one round trip for the whole list, then every theta in one more
 __device__ __forceinline__ void block_dict_far_issue(const int32_t *far, int n, BlockDict &D) {
 #pragma unroll
     for (int i = 0; i < kBlk; i++) {
@@ -188,20 +193,19 @@ __device__ __forceinline__ void block_dict_far_issue(const int32_t *far, int n, 
         if ((int)threadIdx.x >= emsar::kDictBlocks && f < n) D.tid[i] = __builtin_nontemporal_load(&far[f]);
     }
 }
-template <int MODE, bool FAR_ISSUED = false>
-__device__ __forceinline__ void block_dict_issue(const DTile &T, int nd, const int32_t *far_tid, const double *theta, BlockDict &D) {
-    const int near_n = (int)T.near_n, far_n = nd - near_n, nb = (near_n + kBlk - 1) / kBlk;
+// the theta of the thread's dictionary entries: the near block's transcripts are derived here, the far ones were fetched by
+// block_dict_far_issue; and the transcripts of the near slots this thread flushes
+template <int MODE>
+__device__ __forceinline__ void block_dict_issue(const DTile &T, const double *theta, BlockDict &D) {
+    const int near_n = (int)T.near_n, nb = (near_n + kBlk - 1) / kBlk;
     const bool near_thread = (int)threadIdx.x < emsar::kDictBlocks;
 #pragma unroll
     for (int i = 0; i < kBlk; i++) {
         D.th[i] = 0.0;
-        if (!FAR_ISSUED || near_thread) D.tid[i] = -1;
         if (near_thread) {
+            D.tid[i] = -1;
             const int d = (int)threadIdx.x * kBlk + i;
             if ((int)threadIdx.x < nb && d < near_n) D.tid[i] = T.lo + d;
-        } else if (!FAR_ISSUED) {
-            const int f = ((int)threadIdx.x - emsar::kDictBlocks) + i * (kTiledThreads - emsar::kDictBlocks);      // far entry: strided, coalesced
-            if (f < far_n) D.tid[i] = __builtin_nontemporal_load(&far_tid[T.far_off + f]);
         }
         if (MODE != MODE_SCATTER && D.tid[i] >= 0) D.th[i] = theta[D.tid[i]];
     }
@@ -392,7 +396,6 @@ __global__ __launch_bounds__(kTiledThreads, 4) void k_pass_tiled(const Tile *__r
     if (STAMP) ts[0] = stamp_now();
 
     const DTile T = tile_load(tiles + blockIdx.x);
-    const int nd = (int)T.near_n + (int)T.far_n;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool has_slice = wave < (int)T.n_slices;
@@ -424,7 +427,7 @@ __global__ __launch_bounds__(kTiledThreads, 4) void k_pass_tiled(const Tile *__r
     // vmcnt(16) on every path (hipcc merges paths with different numbers of requests into vmcnt(0))
     if (MODE != MODE_SCATTER) load8_clamped(A, e, k < 8 ? k : 8);
     load8_clamped(B, b, m < 8 ? m : 8);
-    block_dict_issue<MODE, true>(T, nd, nullptr, theta, D);
+    block_dict_issue<MODE>(T, theta, D);
     if (!has_slice) { k = 0; m = 0; }
     // ---- phase 0: the table of subset sums into LDS, the accumulators cleared ----
     block_dict_store(T, D, th_w, acc_w);
@@ -606,7 +609,7 @@ __device__ __forceinline__ void tile_e_step(const TileWave &W, int4 (&A)[8], siz
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-__device__ __forceinline__ void tile_m_step(const TileWave &W, int4 (&B)[8], const double *w_s, double *acc_w, int lane, double fx) {
+__device__ __forceinline__ void tile_m_step(const TileWave &W, int4 (&B)[8], const double *w_s, double *acc_w, double fx) {
     const unsigned ws_base = __builtin_amdgcn_readfirstlane(lds_byte_addr(w_s));
     unsigned cur = 0xFFFFFFFFu;
     double part = 0.0;
@@ -631,7 +634,6 @@ __device__ __forceinline__ void tile_m_step(const TileWave &W, int4 (&B)[8], con
         }
     } else bwd_sum_regs<EMSAR_UM_BATCH, 4, 8>(B, W.m, ws_base, acc_w, cur, part, fx);
     if (part != 0.0) tile_acc_add(acc_w, cur, part, fx);
-    (void)lane;
 }
 struct TileEnv {            // per-launch constants of the multi-tile kernel
     const Tile *tiles; int n_tiles, stride;
@@ -656,9 +658,9 @@ __device__ __forceinline__ void tiled_stage(const TileEnv &V, int it, const DTil
     if (has_next) {
         if (Wn.has_slice) load8_clamped(A, Wn.e, Wn.k < 8 ? Wn.k : 8);
         block_dict_far_issue(V.far_tid + Tn.far_off, (int)Tn.far_n, D);
-        block_dict_issue<MODE, true>(Tn, Wn.nd, nullptr, V.theta, D);
+        block_dict_issue<MODE>(Tn, V.theta, D);
     }
-    if (W.has_slice) tile_m_step(W, B, V.w_s, V.acc_w, V.lane, V.fx);
+    if (W.has_slice) tile_m_step(W, B, V.w_s, V.acc_w, V.fx);
     if (has_next && Wn.has_slice && Wn.m > 0) load8_clamped(B, Wn.b, Wn.m < 8 ? Wn.m : 8);
     __syncthreads();
     block_dict_flush(T, Dcur, V.th_w, V.acc_w, V.acc, V.fx);
@@ -687,7 +689,7 @@ __global__ __launch_bounds__(kTiledThreads, 4) void k_pass_tiled_multi(const Til
     BlockDict D;
     int4 A[8], B[8];
     block_dict_far_issue(far_tid + T.far_off, (int)T.far_n, D);
-    block_dict_issue<MODE, true>(T, W.nd, nullptr, theta, D);
+    block_dict_issue<MODE>(T, theta, D);
     if (W.has_slice) {
         load8_clamped(A, W.e, W.k < 8 ? W.k : 8);
         if (W.m > 0) load8_clamped(B, W.b, W.m < 8 ? W.m : 8);
@@ -735,7 +737,7 @@ __global__ __launch_bounds__(kTiledThreads, 4) void k_pass_tiled_unit(const Tile
     // the first forward columns go out BEFORE the dictionary's theta (whose addresses wait for the far list): unconditionally -- a wave without a
     // slice asks for one line eight times -- so that the wait for the far list is vmcnt(8) on every path, not vmcnt(0)
     load8_clamped(A, W.has_slice ? W.e : reinterpret_cast<const int4 *>(fwd), W.has_slice ? (W.k < 8 ? W.k : 8) : 1);
-    block_dict_issue<MODE, true>(T, W.nd, nullptr, theta, D);
+    block_dict_issue<MODE>(T, theta, D);
     if (lane < 8) w_s[emsar::kTileSliceRows + lane] = 0.0;
     block_dict_store(T, D, th_w, acc_w);
     vm_loads_landed();
@@ -764,7 +766,7 @@ __global__ __launch_bounds__(kTiledThreads, 4) void k_pass_tiled_unit(const Tile
         if (STAMP) tb = stamp_now();
         if (W.has_slice) {
             load8_clamped(A, Wn.has_slice ? Wn.e : reinterpret_cast<const int4 *>(fwd), Wn.has_slice ? (Wn.k < 8 ? Wn.k : 8) : 1);
-            tile_m_step(W, B, w_s, acc_w, lane, fx.mass);
+            tile_m_step(W, B, w_s, acc_w, fx.mass);
         } else if (Wn.has_slice) load8_clamped(A, Wn.e, Wn.k < 8 ? Wn.k : 8);
         if (STAMP) { const unsigned long long tc = stamp_now(); te += tb - ta; tm += tc - tb; }
         T = Tn; W = Wn;

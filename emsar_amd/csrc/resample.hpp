@@ -1,6 +1,6 @@
 // resample.hpp -- the resampling driver behind include/emsar_hip.h: the Poisson bootstrap, its gene-level statistics and quantiles, the
 // binomial depth subsampling, and the gene map with its sums.  Part of emsar_hip.hip's translation unit, included at its end: it uses
-// the context, ensure_sets, layout_weights, solve_impl and the kernels (kernels_boot.hpp, kernels_genes.hpp, kernels_quant.hpp,
+// the context, layout_weights, plan_solve and SolveRun (solve.hpp) and the kernels (kernels_boot.hpp, kernels_genes.hpp, kernels_quant.hpp,
 // kernels_isoforms.hpp).
 // One call = one BootRun:  plan memory (held replicates first, then the batch size) -> allocate
 //                          for each fraction:  zero the accumulators
@@ -69,7 +69,6 @@ struct BootRestore {
             ctx->weighted = weighted;
         }
         ctx->fx_mass = fx_mass; ctx->fx_ll = fx_ll;
-        clear_solve_state(ctx);
         if (d_th0) (void)hipMemcpy(ctx->vec.d_th[0], d_th0, (size_t)ctx->n_tx * 8, hipMemcpyDeviceToDevice);
         return rc;
     }
@@ -221,11 +220,11 @@ struct BootRun {
     // EMSAR_HIP_BOOT_BATCH overrides
     int plan_batch() {
         int rc;
-        use_sets = p.set_mode == 0;
-        if (use_sets && (rc = ensure_sets(ctx))) return rc;
-        if (use_sets && ctx->sets.RS.giant) use_sets = false;
-        // the streaming passes solve what the set solver does not cover: everything, the streamed sets, the cluster sets
-        need_stream = !use_sets || ctx->sets.RS.n_streamed_sets > 0 || ctx->sets.n_cstat > 0;
+        SolvePlan sp;
+        if ((rc = plan_solve(ctx, p.set_mode, sp))) return rc;
+        use_sets = sp.use_sets;
+        // the streaming passes solve what the set solver does not cover: everything, the streamed sets -- and here the cluster sets too
+        need_stream = sp.need_stream || ctx->sets.n_cstat > 0;
         if ((rc = boot_prepare(ctx, use_sets))) return rc;
         n_rw = use_sets ? ctx->sets.boot_n_rw : 0;
         slot_stride = n_rw + n;
@@ -265,11 +264,7 @@ struct BootRun {
         HIPCHK(guard.d_th0.alloc((size_t)n));
         HIPCHK(hipMemcpyAsync(guard.d_th0, ctx->vec.d_th[0], (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream));
         HIPCHK(hipEventCreate(&e[0])); HIPCHK(hipEventCreate(&e[1]));
-        if (n_sets) {
-            HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets_boot<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[0]));
-            HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets_boot<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[1]));
-            HIPCHK(hipFuncSetAttribute((const void *)k_solve_sets_boot<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[2]));
-        }
+        if (n_sets) HIPCHK(set_class_lds_attributes((const void *)k_solve_sets_boot<64>, (const void *)k_solve_sets_boot<256>, (const void *)k_solve_sets_boot<512>));
         h_wb.resize(need_stream ? (size_t)(batch * n_rows) : 0);
         h_th.resize((size_t)std::max(n, 1));
         h_bstat.resize((size_t)(batch * n_sets));
@@ -331,9 +326,7 @@ struct BootRun {
             guard.swapped = true;
             if ((rc = boot_stream_weights(ctx, h_wb.data() + y * n_rows))) return rc;
             emsar_em_stats st;
-            rc = solve_impl(ctx, &ps, h_th.data(), &st);
-            clear_solve_state(ctx);
-            if (rc) return rc;
+            if ((rc = SolveRun(ctx, &ps, h_th.data(), &st).run())) return rc;
             t.stream_ms += st.kernel_ms;
             if (!st.converged) unconv[(size_t)y] = 1;
             hipLaunchKernelGGL(k_boot_take_streamed, dim3(gn), dim3(256), 0, ctx->stream, n, use_sets ? ctx->sets.d_kind.get() : nullptr, ctx->vec.d_th[0],
