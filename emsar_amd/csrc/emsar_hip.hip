@@ -17,6 +17,7 @@
 //                     emsar_hip_solve, emsar_hip_run_passes
 //   resample.hpp      the resampling driver and its C ABI -- bootstrap, quantiles, subsampling, genes
 //   fit.hpp           the model fit and its C ABI
+//   presence.hpp      the presence test (a likelihood-ratio test per transcript on its resident set) and its C ABI
 // Kernels (one translation unit, included below):
 //   kernels_tiled.hpp     k_pass_tiled_unit                      the hot one (the default above 2048 tiles): one workgroup per UNIT of up to
 //                         two tiles of the TILED layout that share a dictionary of theta/acc in LDS (60 blocks x 16 subset sums),
@@ -27,6 +28,7 @@
 //   kernels_vector.hpp    k_update, k_update_p2/p3, k_sq_extrap_ll (SQUAREM extrapolation / acceptance on the device),
 //                         k_normalise, k_adj_euma, small reductions
 //   kernels_sets.hpp      k_solve_sets                           one workgroup solves one connected set out of LDS
+//   kernels_presence.hpp  k_solve_sets_drop                      a set solved without one of its transcripts, and F at the result out of the same LDS
 //   kernels_boot.hpp      k_boot_draw, k_boot_accum, ...         the Poisson bootstrap (draws: boot_rng.hpp; sets: k_solve_sets_boot)
 //                         k_sub_draw, k_sub_scale                the depth subsampling: binomial draws, every replicate to its own depth
 //   kernels_genes.hpp     k_gene_sums, k_gene_finish             per-gene sums in a fixed order (gene_sums, the bootstrap's gene sd)
@@ -63,6 +65,7 @@
 #include "kernels_tiled.hpp"
 #include "kernels_vector.hpp"
 #include "kernels_sets.hpp"
+#include "kernels_presence.hpp"
 #include "kernels_cluster.hpp"
 #include "kernels_boot.hpp"
 #include "kernels_genes.hpp"
@@ -809,3 +812,4 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 #include "solve.hpp"      // the set solver's driver and the solve driver: emsar_hip_solve, emsar_hip_run_passes
 #include "resample.hpp"   // the resampling driver and its entry points: bootstrap, genes, quantiles, subsampling
 #include "fit.hpp"        // the model fit and its entry points (after resample.hpp: the gene step is launch_gene_sums)
+#include "presence.hpp"   // the presence test and its entry points (after resample.hpp: free_device_bytes)

@@ -32,6 +32,9 @@
  * attributed to it, the Pearson chi2, the Poisson deviance and the missed reads of those segments (each segment's residual shared out by
  * theta_t / S_c), the missed share of its expected reads and the segment that misses most, by the id .segments uses (emsar_hip_model_fit on
  * the .fpkm column and the E of the solve); with --g2t also <prefix>.<i>.gfit per gene.  The other files do not change with it.
+ * --presence answers "is this isoform needed to explain the reads at all": <prefix>.<i>.presence holds, per transcript (or per transcript named in
+ * --presence-list FILE, one name per line), the likelihood-ratio statistic Lambda of dropping it from its connected set, its p-value, a status
+ * word and the sibling that would take over its reads (emsar_hip_presence with the solve's parameters).  The other files do not change with it.
  * --subsample f1,f2,.. answers "was the sample sequenced deep enough": <prefix>.<i>.saturation holds, per transcript and fraction,
  * the mean and sd of FPKM (at the thinned depth) and TPM over --subsample-reps replicates in which every read is kept with
  * probability f (emsar_hip_subsample; seed --subsample-seed + i), with --g2t also <prefix>.<i>.gsaturation per gene.  The other
@@ -69,6 +72,8 @@ typedef struct {
     const char *g2t;                  /* --g2t FILE (NULL = off) */
     int isoforms;                     /* --isoforms (needs --g2t) */
     int fit;                          /* --fit */
+    int presence;                     /* --presence */
+    int32_t *pres_q; int pres_nq;     /* --presence-list FILE: the tids it names, in file order (NULL = all transcripts) */
     const emsar_genes *genes;         /* its gene map, read once by main() and shared read-only by the workers */
 } config;
 
@@ -271,6 +276,23 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         free(fv); free(gv); free(fw);
         if (rc) goto done;
     }
+    /* ---- presence test (--presence): one likelihood-ratio test per transcript on its connected set, on the device ---- */
+    if (cfg->presence) {
+        const size_t Q = cfg->pres_q ? (size_t)cfg->pres_nq : T, Qa = Q > 0 ? Q : 1;
+        double *pv = (double *)malloc(Qa * 8 * 3);
+        int32_t *pi = (int32_t *)malloc(Qa * 4 * 2);
+        const emsar_presence_outputs po = {pv, pv ? pv + Q : NULL, pi, pv ? pv + 2 * Q : NULL, pi ? pi + Q : NULL, NULL};
+        if (!pv || !pi) rc = EMSAR_HOST_ERR_OOM;
+        else if ((rc = emsar_hip_presence(ctx, &p, (int32_t)Q, cfg->pres_q, &po, NULL)))
+            fprintf(stderr, "alnfile[%d]: presence: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+        else {
+            snprintf(path, sizeof path, "%s/%s.%d.presence", cfg->outdir, cfg->prefix, i);
+            if ((rc = emsar_write_presence(path, r, (int32_t)Q, cfg->pres_q, mean, po.lambda, po.pvalue, po.status, po.heir, po.heir_share)))
+                fprintf(stderr, "can't write %s\n", path);
+        }
+        free(pv); free(pi);
+        if (rc) goto done;
+    }
     /* ---- Poisson bootstrap (--bootstrap B): its own file; .fpkm keeps the reference's column 3.  With --g2t the same replicates
      *      give the genes' sd as well (bootstrap_genes: the transcript outputs are the same bits as bootstrap's), and with --isoforms
      *      the usage statistics (bootstrap_isoforms: every other output is the same bits) ---- */
@@ -441,6 +463,10 @@ static void usage(const char *a0) {
             "      --fit                 also write <prefix>.<i>.fit: per transcript the effective number of segments, Pearson chi2, Poisson deviance and\n"
             "                            missed reads of the fitted model on its segments, the missed share of its expected reads and its worst\n"
             "                            segment (the id of .segments); with --g2t also <prefix>.<i>.gfit per gene\n"
+            "      --presence            also write <prefix>.<i>.presence: per transcript the likelihood-ratio statistic Lambda of solving its connected\n"
+            "                            set without it, the p-value, a status word (TESTED, ABSENT, ESSENTIAL, OUTSIDE, NOT_RESIDENT, UNCONVERGED)\n"
+            "                            and the sibling that takes over most of its reads, with the share it takes\n"
+            "      --presence-list <file> with --presence: test only the transcripts named in the file, one name per line\n"
             "      --gpus <n> / --devices <a,b,..> (-M: one worker per entry, ids may repeat) / --device <d> / --plain /\n"
             "      --stats-json <file> / -q / -v\n", a0);
 }
@@ -454,6 +480,7 @@ int main(int argc, char **argv) {
     cfg.sub_reps = 10; cfg.sub_seed = 1;
     const char *strand = "ns"; int multisample = 0, gpus = 0, device = 0;
     int dev_map[64], n_dev_map = 0;
+    const char *presence_list = NULL;
     static struct option lo[] = {
         {"rsh", required_argument, 0, 'I'}, {"PE", no_argument, 0, 'P'}, {"strand_type", required_argument, 0, 's'},
         {"maxthread", required_argument, 0, 'p'}, {"max_repeat", required_argument, 0, 'k'}, {"nround", required_argument, 0, 'n'},
@@ -465,6 +492,7 @@ int main(int argc, char **argv) {
         {"bootstrap", required_argument, 0, 1012}, {"bootstrap-seed", required_argument, 0, 1013}, {"g2t", required_argument, 0, 1014},
         {"subsample", required_argument, 0, 1015}, {"subsample-reps", required_argument, 0, 1016}, {"subsample-seed", required_argument, 0, 1017},
         {"bootstrap-quantiles", required_argument, 0, 1018}, {"isoforms", no_argument, 0, 1019}, {"fit", no_argument, 0, 1020},
+        {"presence", no_argument, 0, 1021}, {"presence-list", required_argument, 0, 1022},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
@@ -557,6 +585,8 @@ int main(int argc, char **argv) {
             }
             case 1019: cfg.isoforms = 1; break;
             case 1020: cfg.fit = 1; break;
+            case 1021: cfg.presence = 1; break;
+            case 1022: presence_list = optarg; break;
             case 1009: {
                 const char *q = optarg;
                 while (*q && n_dev_map < 64) {
@@ -576,6 +606,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--bootstrap-quantiles needs --bootstrap B with 1 <= B <= 4096 replicates.\n"); return 1;
     }
     if (cfg.isoforms && !cfg.g2t) { fprintf(stderr, "--isoforms needs --g2t FILE.\n"); return 1; }
+    if (presence_list && !cfg.presence) { fprintf(stderr, "--presence-list needs --presence.\n"); return 1; }
     if (!cfg.rsh_path || optind + 2 >= argc) { usage(argv[0]); return 1; }
     if (emsar_set_strand(strand, cfg.ao.pe, &cfg.ao.strand)) { fprintf(stderr, "error: invalid strand type.\n"); return 1; }
     cfg.outdir = argv[optind]; cfg.prefix = argv[optind + 1];
@@ -635,6 +666,25 @@ int main(int argc, char **argv) {
     free(cache_path);
     if (cfg.verbose > 0) fprintf(stdout, "rsh: %d transcripts, %lld segments, fragment lengths %d-%d (%.2fs)\n", rsh->n_tx,
                                  (long long)rsh->n_rows, rsh->frag_min, rsh->frag_max, now_s() - t0);
+    if (presence_list) {                       /* before any sample: an unknown name ends the run here */
+        FILE *f = fopen(presence_list, "r");
+        if (!f) { fprintf(stderr, "Can't open the presence list %s.\n", presence_list); emsar_rsh_free(rsh); return 1; }
+        char line[4096];
+        cfg.pres_q = (int32_t *)malloc(sizeof(int32_t));
+        while (cfg.pres_q && fgets(line, sizeof line, f)) {
+            size_t n = strlen(line);
+            while (n && (line[n - 1] == '\n' || line[n - 1] == '\r' || line[n - 1] == ' ' || line[n - 1] == '\t')) line[--n] = 0;
+            if (!n) continue;
+            const int32_t t = emsar_rsh_tid_of(rsh, line);
+            if (t < 0) { fprintf(stderr, "--presence-list: no transcript %s in the index.\n", line); fclose(f); emsar_rsh_free(rsh); return 1; }
+            int32_t *grown = (int32_t *)realloc(cfg.pres_q, sizeof(int32_t) * (size_t)(cfg.pres_nq + 1));
+            if (!grown) { free(cfg.pres_q); cfg.pres_q = NULL; break; }
+            cfg.pres_q = grown;
+            cfg.pres_q[cfg.pres_nq++] = t;
+        }
+        fclose(f);
+        if (!cfg.pres_q) { fprintf(stderr, "out of memory\n"); emsar_rsh_free(rsh); return 1; }
+    }
     emsar_genes *genes = NULL;
     if (cfg.g2t) {                             /* before any sample: a bad gene map ends the run here */
         if (emsar_genes_read(rsh, cfg.g2t, &genes, err, sizeof err)) { fprintf(stderr, "%s\n", err); emsar_rsh_free(rsh); return 1; }
@@ -737,6 +787,7 @@ int main(int argc, char **argv) {
     }
     emsar_rsh_free(rsh);
     emsar_genes_free(genes);
+    free(cfg.pres_q);
     for (int i = 0; i < n_list; i++) free(list[i]);
     free(list); free(status); free(stats); free(bstats); free(sstats); free(qstats); free(parse_s); free(model_s); free(host_s); free(wa); free(th);
     return bad ? 1 : 0;

@@ -178,6 +178,12 @@ int emsar_write_fit(const char *path, const emsar_rsh *r, const double *fpkm, co
  * the four columns; miss_fraction = miss / the sum of fpkm * den over the gene's transcripts in ascending tid, 0 when that sum is 0 */
 int emsar_write_gfit(const char *path, const emsar_rsh *r, const emsar_genes *g, const double *fpkm, const double *den, const double *df,
                      const double *chi2, const double *dev, const double *miss);
+/* .presence (emsar-hip --presence): one line per queried transcript -- query [n_query] tids, NULL = all n_tx in order; the result arrays are
+ * [n_query] as emsar_hip_presence returns them, fpkm is [n_tx] --: tid transcriptID FPKM Lambda p status heir heir_share,
+ * "%d\t%s\t%lf\t%lf\t%.6g\t%s\t%s\t%lf"; status is the word of the header's enum (TESTED, ABSENT, ESSENTIAL, OUTSIDE, NOT_RESIDENT,
+ * UNCONVERGED), heir the heir's transcriptID or "-"; a value that is not finite is written as "inf" or "nan" */
+int emsar_write_presence(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, const double *fpkm, const double *lambda,
+                         const double *pvalue, const int32_t *status, const int32_t *heir, const double *heir_share);
 /* .saturation (emsar-hip --subsample): a "#" line (fractions, replicates, seed, depth_mean per fraction), a header, then per
  * transcript its name, FPKM and TPM as in .fpkm and per fraction mean_FPKM sd_FPKM mean_TPM sd_TPM ([n_fractions][n_tx] each) */
 int emsar_write_saturation(const char *path, const emsar_rsh *r, const double *fpkm, const double *tpm, int n_fractions,

@@ -155,6 +155,29 @@ int emsar_write_gfit(const char *path, const emsar_rsh *r, const emsar_genes *g,
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
 
+/* a value of .presence: "%lf" / "%.6g", or the words inf / nan (no sign: Lambda and the share are not negative) */
+static void put_value(FILE *f, const char *fmt, double v) {
+    if (isnan(v)) fputs("nan", f); else if (isinf(v)) fputs("inf", f); else fprintf(f, fmt, v);
+}
+
+int emsar_write_presence(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, const double *fpkm, const double *lambda,
+                         const double *pvalue, const int32_t *status, const int32_t *heir, const double *heir_share) {
+    static const char *const word[6] = {"TESTED", "ABSENT", "ESSENTIAL", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED"};
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "tid\ttranscriptID\tFPKM\tLambda\tp\tstatus\their\their_share\n");
+    if (!query) n_query = r->n_tx;
+    for (int32_t i = 0; i < n_query; i++) {
+        const int32_t t = query ? query[i] : i;
+        fprintf(f, "%d\t%s\t%lf\t", t, r->names[t], fpkm[t]);
+        put_value(f, "%lf", lambda[i]); fputc('\t', f);
+        put_value(f, "%.6g", pvalue[i]);
+        fprintf(f, "\t%s\t%s\t", status[i] >= 0 && status[i] < 6 ? word[status[i]] : "?", heir[i] >= 0 && heir[i] < r->n_tx ? r->names[heir[i]] : "-");
+        put_value(f, "%lf", heir_share[i]); fputc('\n', f);
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
 /* the rows of .saturation / .gsaturation: n names, per fraction ncol columns col[j] = [n_fractions][n] */
 static int write_saturation(const char *path, const char *id, char **names, int64_t n, const double *fpkm, const double *tpm, int n_fractions,
                             const double *fractions, int n_replicates, uint64_t seed, const double *depth_mean, int ncol,

@@ -290,14 +290,21 @@ __device__ __forceinline__ bool set_newton_step(const SetLds &L, double *x, doub
     return false;
 }
 
-// the solve of one set by the whole workgroup (k_solve_sets; k_solve_sets_boot runs it on a bootstrap replicate's weights)
-template <int THREADS>
+// What solve_one_set<THREADS, KEEP = true> hands to its caller instead of writing it out: the set as it lies in LDS, the vector that
+// holds the result, and the statistics (kernels_presence.hpp runs its epilogue on them)
+struct SetSolved { SetLds L; const double *res; int passes, converged; double delta; };
+
+// the solve of one set by the whole workgroup (k_solve_sets; k_solve_sets_boot runs it on a bootstrap replicate's weights).
+// KEEP (k_solve_sets_drop): local transcript `drop` (-1 = none) is taken out of the problem -- its den is 0 in LDS, so it starts at 0
+// and stays there, as a transcript outside F does --, the result stays in LDS and is described in *kept for the caller, theta_g is
+// written only when nothing is dropped and st is not written.  With the defaults none of this exists in the generated code.
+template <int THREADS, bool KEEP = false>
 __device__ __forceinline__ void solve_one_set(const emsar::SetDesc d, const int32_t *__restrict__ g_tid,
                                               const double *__restrict__ g_u, const double *__restrict__ row_w,
                                               const uint16_t *__restrict__ rp_g, const uint16_t *__restrict__ ent_g,
                                               const uint16_t *__restrict__ cp_g, const uint16_t *__restrict__ crow_g,
                                               const double *__restrict__ den_g, double *__restrict__ theta_g,
-                                              SetStat *__restrict__ st, SetSolveParams P) {
+                                              SetStat *__restrict__ st, SetSolveParams P, int drop = -1, SetSolved *kept = nullptr) {
     extern __shared__ double smem[];
     const int nt = (int)d.n_t, nr = (int)d.n_r, nnz = (int)d.nnz;
     double *A = smem, *B = A + nt, *Cc = B + nt;
@@ -307,7 +314,8 @@ __device__ __forceinline__ void solve_one_set(const emsar::SetDesc d, const int3
     uint16_t *rp = (uint16_t *)(L.red + emsar::kSetRedDoubles), *ent = rp + (nr + 1), *cp = ent + nnz, *crow = cp + (nt + 1);
     L.rp = rp; L.ent = ent; L.cp = cp; L.crow = crow; L.nt = nt; L.nr = nr;
     for (int i = threadIdx.x; i < nt; i += THREADS) {
-        const double dn = den_g[g_tid[d.tid_off + i]];
+        double dn = den_g[g_tid[d.tid_off + i]];
+        if (KEEP && i == drop) dn = 0.0;
         L.den[i] = dn; L.u[i] = g_u[d.tid_off + i];
         A[i] = dn > 0.0 ? 1.0 : 0.0;
     }
@@ -405,6 +413,11 @@ __device__ __forceinline__ void solve_one_set(const emsar::SetDesc d, const int3
             if (cooldown > 0) cooldown--;
             else if (!set_newton_step<THREADS>(L, A, B, Cc, passes)) cooldown = 8;
         }
+    }
+    if (KEEP) {
+        if (drop < 0) for (int i = threadIdx.x; i < nt; i += THREADS) theta_g[g_tid[d.tid_off + i]] = res[i];
+        kept->L = L; kept->res = res; kept->passes = passes; kept->converged = converged; kept->delta = delta;
+        return;
     }
     for (int i = threadIdx.x; i < nt; i += THREADS) theta_g[g_tid[d.tid_off + i]] = res[i];
     if (threadIdx.x == 0) { st->passes = passes; st->converged = converged; st->delta = delta; }

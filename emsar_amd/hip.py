@@ -26,7 +26,11 @@ SYMBOLS = [
     "emsar_hip_bootstrap_quantiles", "emsar_hip_quantiles_host",
     "emsar_hip_isoform_usage", "emsar_hip_isoform_usage_host", "emsar_hip_bootstrap_isoforms",
     "emsar_hip_model_fit", "emsar_hip_model_fit_host",
+    "emsar_hip_presence", "emsar_hip_presence_pvalue_host",
 ]
+
+# status of a transcript in the presence test (include/emsar_hip.h "presence test"), by value
+PRESENCE_STATUS = ("TESTED", "ABSENT", "ESSENTIAL", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED")
 
 
 class EmsarHipError(RuntimeError):
@@ -97,6 +101,22 @@ class FitStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PresenceOutputs(C.Structure):
+    _fields_ = [("lambda_", C.POINTER(C.c_double)), ("pvalue", C.POINTER(C.c_double)), ("heir", C.POINTER(C.c_int32)),
+                ("heir_share", C.POINTER(C.c_double)), ("status", C.POINTER(C.c_int32)), ("theta_hat", C.POINTER(C.c_double))]
+
+
+class PresenceStats(C.Structure):
+    _fields_ = [("n_status", C.c_int64 * 6), ("items_launched", C.c_int64), ("drop_passes_sum", C.c_int64), ("drop_passes_max", C.c_int32),
+                ("reserved0", C.c_int32), ("min_raw_lambda", C.c_double), ("baseline_ms", C.c_double), ("drop_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["n_status"] = dict(zip(PRESENCE_STATUS, d["n_status"]))
+        return d
 
 
 class SetsInfo(C.Structure):
@@ -171,6 +191,8 @@ def load_library():
     L.emsar_hip_model_fit.argtypes = [vp, f64p, f64p, C.POINTER(FitOutputs), C.POINTER(FitStats)]
     L.emsar_hip_model_fit_host.argtypes = [C.c_int64, C.c_int32, u64p, i32p, i32p, f64p, f64p, C.c_int32, i32p, C.POINTER(FitOutputs),
                                            C.POINTER(FitStats)]
+    L.emsar_hip_presence.argtypes = [vp, C.POINTER(EmParams), C.c_int32, i32p, C.POINTER(PresenceOutputs), C.POINTER(PresenceStats)]
+    L.emsar_hip_presence_pvalue_host.argtypes = [C.c_int64, f64p, f64p]
     _lib = L
     return L
 
@@ -310,6 +332,19 @@ def model_fit_host(n_tx, row_ptr, col_idx, theta, row_weight=None, E=None, rows=
     if rc != 0:
         raise EmsarHipError(rc, "model_fit_host")
     return _fit_result(res, n_rows, int(n_tx), int(n_genes), st)
+
+
+def presence_pvalue_host(lam):
+    """Host-only: the presence test's p-value of the statistic Lambda under the boundary mixture 1/2 chi2_0 + 1/2 chi2_1 (include/emsar_hip.h
+    "presence test"): 1 for Lambda <= 0, 0.5 erfc(sqrt(Lambda / 2)) above, 0 for +inf, NaN for NaN.  A scalar or an array; no GPU needed."""
+    L = load_library()
+    x = np.ascontiguousarray(np.atleast_1d(np.asarray(lam, dtype=np.float64)))
+    out = np.zeros(max(x.size, 1))
+    rc = L.emsar_hip_presence_pvalue_host(x.size, _p(x.reshape(-1), C.c_double), _p(out, C.c_double))
+    if rc != 0:
+        raise EmsarHipError(rc, "presence_pvalue_host")
+    out = out[:x.size].reshape(x.shape)
+    return float(out[0]) if np.ndim(lam) == 0 else out
 
 
 def layout_selfcheck_tiled(n_tx, row_ptr, col_idx, merge_rows=False):
@@ -541,6 +576,25 @@ class EmsarHip:
         st = FitStats()
         self._chk(self._L.emsar_hip_model_fit(self._h, _p(th, C.c_double), _p(e, C.c_double), C.byref(o), C.byref(st)), "model_fit")
         return _fit_result(res, self.n_rows, self.n_tx, self.n_genes, st)
+
+    def presence(self, query=None, max_iter=100000, accel=1, tol=1e-10, abs_floor=1e-6, check_every=8, count_floor=0.0, set_mode=0, zero_cut=0.0,
+                 abs_step=0.0, newton_after=0):
+        """Likelihood-ratio test of each queried transcript (include/emsar_hip.h "presence test"): is it needed to explain the reads, or
+        would the rest of its connected set do as well?  query: tids in any order, repeats allowed, None = all transcripts; the solver
+        parameters are those of solve().  Returns a dict of arrays in query order: lambda, pvalue, heir (tid, -1 = none), heir_share,
+        status (index into PRESENCE_STATUS), theta_hat, and stats.  After upload_sample; the context is left as it was."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        q = None if query is None else np.ascontiguousarray(np.asarray(query, dtype=np.int32).reshape(-1))
+        nq = self.n_tx if q is None else len(q)
+        res = {k: np.zeros(max(nq, 1)) for k in ("lambda", "pvalue", "heir_share", "theta_hat")}
+        res.update({k: np.zeros(max(nq, 1), dtype=np.int32) for k in ("heir", "status")})
+        o = PresenceOutputs(_p(res["lambda"], C.c_double), _p(res["pvalue"], C.c_double), _p(res["heir"], C.c_int32), _p(res["heir_share"], C.c_double),
+                            _p(res["status"], C.c_int32), _p(res["theta_hat"], C.c_double))
+        st = PresenceStats()
+        self._chk(self._L.emsar_hip_presence(self._h, C.byref(p), nq, _p(q, C.c_int32), C.byref(o), C.byref(st)), "presence")
+        out = {k: v[:nq] for k, v in res.items()}
+        out["stats"] = st
+        return out
 
     def bootstrap_weights(self, seed, replicate):
         """The drawn row weights of one bootstrap replicate (caller row order), drawn on the device."""

@@ -91,6 +91,7 @@ def lib():
         L.emsar_write_segments.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Counts), C.POINTER(Model), f64p]
         L.emsar_write_isoforms.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Genes), f64p, f64p, i32p, C.c_int, f64p, f64p, i32p,
                                            C.c_int, f64p, f64p]
+        L.emsar_write_presence.argtypes = [C.c_char_p, C.POINTER(Rsh), C.c_int32, i32p, f64p, f64p, f64p, i32p, i32p, f64p]
         _lib = L
     return _lib
 
@@ -125,6 +126,23 @@ def write_isoforms(path, tx_names, gene_names, gene_of_tx, fpkm, usage, dominant
                                     0 if q is None else len(a[6]), dp(a[6]), dp(a[7]))
     if rc != 0:
         raise HostError("write_isoforms rc=%d" % rc)
+
+
+def write_presence(path, tx_names, fpkm, lam, pvalue, status, heir, heir_share, query=None):
+    """.presence (emsar_write_presence): transcripts tx_names with fpkm [n_tx]; lam, pvalue, status, heir, heir_share as EmsarHip.presence
+    returns them for query (tids, None = all transcripts in order)."""
+    n_tx = len(tx_names)
+    names = (C.c_char_p * max(n_tx, 1))(*[s.encode() for s in tx_names])
+    r = Rsh(n_tx=n_tx, names=C.cast(names, C.POINTER(C.c_char_p)))
+    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    q, st, he = i32(query), i32(status), i32(heir)
+    a = [f64(fpkm), f64(lam), f64(pvalue), f64(heir_share)]
+    rc = lib().emsar_write_presence(path.encode(), C.byref(r), n_tx if q is None else len(q), ip(q), _dp(a[0]), _dp(a[1]), _dp(a[2]), ip(st), ip(he),
+                                    _dp(a[3]))
+    if rc != 0:
+        raise HostError("write_presence rc=%d" % rc)
 
 
 class HostRsh:

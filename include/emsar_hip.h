@@ -422,6 +422,61 @@ int emsar_hip_model_fit_host(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
                              int32_t n_genes, const int32_t *gene_of_tx /* n_tx, or NULL = no gene map */,
                              const emsar_fit_outputs *out /* or NULL */, emsar_fit_stats *stats /* or NULL */);
 
+/* ---- presence test: a likelihood-ratio test for each transcript ----------------------------------
+ * Is transcript t needed to explain the reads of the current sample, or would the other transcripts of its connected set explain them
+ * as well?  For the sample of upload_structure + upload_sample and solver parameters p, with s the packed connected set of t
+ * (set_mode 0; the sets are found on first use, as by solve):
+ *     F_s(theta) = sum_c R_c log S_c + sum_t u_t log theta_t - sum_t theta_t den_t     over the rows and transcripts of s, u_t = the
+ *                  reads of the rows whose only transcript is t -- the sums the set solver's Newton step forms
+ *     baseline     theta_hat = the set solver's result for s with p (the bits solve returns for these transcripts)
+ *     drop-t       the same set with den_t taken as 0: theta_t is then 0 and t's entries add nothing to any S_c.  Same solver, same
+ *                  start, same stopping rule; only t's own set changes when t is dropped, so one test is one workgroup's work
+ *     Lambda_t     = 2 * (F_s(theta_hat) - F_s(theta_hat_without_t)); both F from the same epilogue of the same kernel.  A value below 0
+ *                  (rounding, the stopping rule) is reported as 0; the most negative raw value goes into the statistics
+ *     p_t          of the boundary mixture (1/2) chi2_0 + (1/2) chi2_1:  1 for Lambda <= 0,  0.5 * erfc(sqrt(Lambda / 2)) for
+ *                  Lambda > 0,  0 for +inf,  NaN for NaN; computed on the host (presence_pvalue_host is the same function)
+ *     heir_t       the transcript s != t of the set with the largest gain in expected reads (theta_without_t,s - theta_hat_s) * den_s,
+ *                  the lowest position in the set among equal gains; heir_share_t = that gain / (theta_hat_t * den_t).  -1 / NaN
+ *                  when no transcript gains.  It names the sibling t cannot be told apart from.
+ * status, per transcript:
+ *     TESTED        Lambda, p, heir as above
+ *     ABSENT        theta_hat_t is exactly 0: Lambda = 0, p = 1, nothing is solved.  Also a one-transcript component without reads
+ *     ESSENTIAL     without t some row with reads has no transcript left to explain it: u_t > 0 (decided before anything is launched;
+ *                   a row {t,t} is such a row), or the drop solve's epilogue finds a row with R > 0 and S = 0 (its other
+ *                   members all have den = 0).  Lambda = +inf, p = 0.  Also a one-transcript component with reads
+ *     OUTSIDE       den_t = 0 (outside the likelihood).  Lambda, p, heir_share are NaN, heir -1, theta_hat 0
+ *     NOT_RESIDENT  t lies in a streamed or a cluster set, one component holds most transcripts, or set_mode = 1: testing it would
+ *                   cost one streaming solve of its set per transcript, which this call does not do.  All outputs NaN / -1
+ *     UNCONVERGED   values are given, but the baseline or the drop solve hit max_iter
+ * Outputs are indexed by query position (by tid when query_tids is NULL; n_query is then ignored); a tid may repeat and the order is
+ * free: a transcript's result depends on its set, itself and p alone, not on what else is asked.  Any output pointer may be NULL, as
+ * may out and stats.  ERR_STATE before upload_sample; ERR_ARG for a tid outside 0 .. n_tx-1, n_query < 0, and the parameters solve
+ * rejects.  The context's theta, weights and scales are not touched: a following solve returns the same bits. */
+enum {
+    EMSAR_PRESENCE_TESTED = 0, EMSAR_PRESENCE_ABSENT = 1, EMSAR_PRESENCE_ESSENTIAL = 2, EMSAR_PRESENCE_OUTSIDE = 3,
+    EMSAR_PRESENCE_NOT_RESIDENT = 4, EMSAR_PRESENCE_UNCONVERGED = 5
+};
+typedef struct {
+    double  *lambda, *pvalue;     /* [n_query] */
+    int32_t *heir;                /* [n_query] caller tid, -1 = none */
+    double  *heir_share;          /* [n_query] */
+    int32_t *status;              /* [n_query] EMSAR_PRESENCE_* */
+    double  *theta_hat;           /* [n_query] the baseline: solve's value for a resident or closed-form transcript */
+} emsar_presence_outputs;
+typedef struct {
+    int64_t n_status[6];          /* distinct queried transcripts per status */
+    int64_t items_launched;       /* set solves: baselines and drops */
+    int64_t drop_passes_sum;      /* passes summed over the drop solves */
+    int32_t drop_passes_max;      /* passes of the slowest drop solve */
+    int32_t reserved0;
+    double  min_raw_lambda;       /* the most negative Lambda before clamping, 0 if none was negative */
+    double  baseline_ms, drop_ms; /* device time of the two phases (HIP events) */
+    double  total_ms;             /* wall time of the call, a first call's set building included */
+} emsar_presence_stats;
+int emsar_hip_presence(emsar_hip_ctx *ctx, const emsar_em_params *p, int32_t n_query, const int32_t *query_tids /* NULL = all transcripts */,
+                       const emsar_presence_outputs *out /* or NULL */, emsar_presence_stats *stats /* or NULL */);
+int emsar_hip_presence_pvalue_host(int64_t n, const double *lambda, double *p_out);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 typedef struct {
     int64_t n_rows, nnz;
