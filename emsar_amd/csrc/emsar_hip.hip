@@ -59,6 +59,7 @@
 #include "internal.hpp"
 #include "devmem.hpp"
 #include "fit_index.hpp"
+#include "asym_plan.hpp"
 
 #include "kernels_common.hpp"
 #include "kernels_csr.hpp"
@@ -72,6 +73,7 @@
 #include "kernels_quant.hpp"
 #include "kernels_isoforms.hpp"
 #include "kernels_fit.hpp"
+#include "kernels_asym.hpp"
 
 // ==================================================================================================
 // context
@@ -113,6 +115,7 @@ struct GeneMap {
     int64_t n_gene_chunks = 0, n_gene_multi = 0;
     DevBuf<int32_t> d_gene_blk;
     int32_t *d_gene_tx = nullptr, *d_chunk_beg = nullptr, *d_chunk_out = nullptr, *d_gene_multi = nullptr, *d_gene_of_lib = nullptr;   // views into d_gene_blk
+    std::vector<int32_t> h_gene_of_tx;   // the map as given, caller numbering (asym.hpp: the host finish)
 };
 
 // compute_adjEUMA on the device (emsar_hip_upload_euma), dropped by upload_structure
@@ -813,3 +816,4 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 #include "resample.hpp"   // the resampling driver and its entry points: bootstrap, genes, quantiles, subsampling
 #include "fit.hpp"        // the model fit and its entry points (after resample.hpp: the gene step is launch_gene_sums)
 #include "presence.hpp"   // the presence test and its entry points (after resample.hpp: free_device_bytes)
+#include "asym.hpp"       // the asymptotic standard errors and their entry points (after fit.hpp: fit_ensure_csr, launch_gene_sums)

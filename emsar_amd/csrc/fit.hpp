@@ -23,6 +23,16 @@ int64_t fit_rows_inside(int64_t n_rows, const uint64_t *row_ptr, const double *r
     return n;
 }
 
+// the caller-order CSR of this structure on the device, once: the model fit and the asymptotic standard errors (asym.hpp) share it
+int fit_ensure_csr(emsar_hip_ctx *ctx) {
+    FitDev &F = ctx->fit;
+    if (F.csr_ready) return EMSAR_HIP_OK;
+    HIPCHK(F.d_row_ptr.upload(ctx->h_row_ptr.data(), (size_t)ctx->n_rows + 1));
+    HIPCHK(F.d_col.upload(ctx->h_col.data(), (size_t)ctx->nnz));
+    F.csr_ready = true;
+    return EMSAR_HIP_OK;
+}
+
 struct FitRun {
     emsar_hip_ctx *const ctx;
     const double *const theta, *const row_E;
@@ -42,6 +52,7 @@ struct FitRun {
     int ensure_index() {
         FitDev &F = ctx->fit;
         if (F.ready) return EMSAR_HIP_OK;
+        if (const int rc = fit_ensure_csr(ctx)) return rc;
         emsar::FitIndex X;
         const int brc = emsar::build_fit_index(n_rows, ctx->n_tx, ctx->h_row_ptr.data(), ctx->h_col.data(), X);
         if (brc == -1) return EMSAR_HIP_ERR_OOM;
@@ -52,9 +63,7 @@ struct FitRun {
             for (auto &o : X.chunk_out) if (o >= 0) o = m[(size_t)o];
             for (size_t i = 0; i < X.multi.size(); i += 3) X.multi[i] = m[(size_t)X.multi[i]];
         }
-        FitDev N;                    // moved into the context when it is complete
-        HIPCHK(N.d_row_ptr.upload(ctx->h_row_ptr.data(), (size_t)n_rows + 1));
-        HIPCHK(N.d_col.upload(ctx->h_col.data(), (size_t)ctx->nnz));
+        FitDev N;                    // the index: moved into the context, next to the CSR, when it is complete
         HIPCHK(N.d_idx.upload(X.idx.data(), X.idx.size()));
         HIPCHK(N.d_group_base.upload(X.group_base.data(), X.group_base.size()));
         HIPCHK(N.d_group_steps.upload(X.group_steps.data(), X.group_steps.size()));
@@ -65,7 +74,8 @@ struct FitRun {
         if (X.n_multi > 0) { HIPCHK(N.d_part.alloc((size_t)(5 * X.n_chunks))); HIPCHK(N.d_part_row.alloc((size_t)X.n_chunks)); }
         N.n_chunks = X.n_chunks; N.n_groups = X.n_groups; N.n_multi = X.n_multi;
         N.index_slots = X.index_slots(); N.index_bytes = X.index_bytes();
-        N.ready = true;
+        N.d_row_ptr = std::move(F.d_row_ptr); N.d_col = std::move(F.d_col);
+        N.csr_ready = true; N.ready = true;
         ctx->fit = std::move(N);
         return EMSAR_HIP_OK;
     }

@@ -35,6 +35,10 @@
  * --presence answers "is this isoform needed to explain the reads at all": <prefix>.<i>.presence holds, per transcript (or per transcript named in
  * --presence-list FILE, one name per line), the likelihood-ratio statistic Lambda of dropping it from its connected set, its p-value, a status
  * word and the sibling that would take over its reads (emsar_hip_presence with the solve's parameters).  The other files do not change with it.
+ * --asymptotic answers "how sure is this FPKM" without resampling: <prefix>.<i>.asym holds, per transcript, the standard errors of FPKM and
+ * TPM from the inverse of the observed information at the .fpkm column (emsar_hip_asymptotic), a status word and the sibling it is most
+ * confounded with; with --g2t also <prefix>.<i>.gasym per gene and a usage_sd column.  Transcripts with FPKM <= --boundary-cut (5e-7) are held
+ * fixed: the normal approximation does not hold there, --bootstrap is the tool.  The other files do not change with it.
  * --subsample f1,f2,.. answers "was the sample sequenced deep enough": <prefix>.<i>.saturation holds, per transcript and fraction,
  * the mean and sd of FPKM (at the thinned depth) and TPM over --subsample-reps replicates in which every read is kept with
  * probability f (emsar_hip_subsample; seed --subsample-seed + i), with --g2t also <prefix>.<i>.gsaturation per gene.  The other
@@ -73,6 +77,7 @@ typedef struct {
     int isoforms;                     /* --isoforms (needs --g2t) */
     int fit;                          /* --fit */
     int presence;                     /* --presence */
+    int asymptotic; double boundary_cut;   /* --asymptotic [--boundary-cut X] */
     int32_t *pres_q; int pres_nq;     /* --presence-list FILE: the tids it names, in file order (NULL = all transcripts) */
     const emsar_genes *genes;         /* its gene map, read once by main() and shared read-only by the workers */
 } config;
@@ -293,6 +298,29 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         free(pv); free(pi);
         if (rc) goto done;
     }
+    /* ---- asymptotic standard errors (--asymptotic): the inverse of the observed information at the printed FPKM, on the device ---- */
+    if (cfg->asymptotic) {
+        const size_t Ta = T > 0 ? T : 1, Ga = NG > 0 ? NG : 1;
+        double *av = (double *)malloc(Ta * 8 * 5), *gv = G ? (double *)malloc(Ga * 8) : NULL;
+        int32_t *ai = (int32_t *)malloc(Ta * 4 * 2), *gi = G ? (int32_t *)malloc(Ga * 4) : NULL;
+        const emsar_asym_params ap = {cfg->boundary_cut, 0.0, -1, 0};
+        const emsar_asym_outputs ao = {av, av ? av + T : NULL, av ? av + 2 * T : NULL, NULL, G && av ? av + 4 * T : NULL, ai, ai ? ai + T : NULL,
+                                       av ? av + 3 * T : NULL, NULL, gv, gi, NULL, NULL, NULL};
+        if (!av || !ai || (G && (!gv || !gi))) rc = EMSAR_HOST_ERR_OOM;
+        else if ((rc = emsar_hip_asymptotic(ctx, mean, &ap, &ao, NULL)))
+            fprintf(stderr, "alnfile[%d]: asymptotic: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+        else {
+            snprintf(path, sizeof path, "%s/%s.%d.asym", cfg->outdir, cfg->prefix, i);
+            if ((rc = emsar_write_asym(path, r, mean, tpm, ao.sd_fpkm, ao.sd_tpm, ao.var, ao.status, ao.partner, ao.partner_cov, ao.usage_sd)))
+                fprintf(stderr, "can't write %s\n", path);
+            else if (G) {
+                snprintf(path, sizeof path, "%s/%s.%d.gasym", cfg->outdir, cfg->prefix, i);
+                if ((rc = emsar_write_gasym(path, G, gsums, gv, gi))) fprintf(stderr, "can't write %s\n", path);
+            }
+        }
+        free(av); free(gv); free(ai); free(gi);
+        if (rc) goto done;
+    }
     /* ---- Poisson bootstrap (--bootstrap B): its own file; .fpkm keeps the reference's column 3.  With --g2t the same replicates
      *      give the genes' sd as well (bootstrap_genes: the transcript outputs are the same bits as bootstrap's), and with --isoforms
      *      the usage statistics (bootstrap_isoforms: every other output is the same bits) ---- */
@@ -467,6 +495,10 @@ static void usage(const char *a0) {
             "                            set without it, the p-value, a status word (TESTED, ABSENT, ESSENTIAL, OUTSIDE, NOT_RESIDENT, UNCONVERGED)\n"
             "                            and the sibling that takes over most of its reads, with the share it takes\n"
             "      --presence-list <file> with --presence: test only the transcripts named in the file, one name per line\n"
+            "      --asymptotic          also write <prefix>.<i>.asym: per transcript the asymptotic standard error of FPKM and TPM from the inverse of\n"
+            "                            the observed information, a status word and the sibling it is most confounded with; with --g2t also\n"
+            "                            <prefix>.<i>.gasym (per gene) and a usage_sd column.  Not valid at the boundary (FPKM about 0): use --bootstrap there\n"
+            "      --boundary-cut <x>    with --asymptotic: transcripts with FPKM <= x are held fixed (default 5e-7, the .fpkm print quantum)\n"
             "      --gpus <n> / --devices <a,b,..> (-M: one worker per entry, ids may repeat) / --device <d> / --plain /\n"
             "      --stats-json <file> / -q / -v\n", a0);
 }
@@ -481,6 +513,7 @@ int main(int argc, char **argv) {
     const char *strand = "ns"; int multisample = 0, gpus = 0, device = 0;
     int dev_map[64], n_dev_map = 0;
     const char *presence_list = NULL;
+    int boundary_cut_given = 0;
     static struct option lo[] = {
         {"rsh", required_argument, 0, 'I'}, {"PE", no_argument, 0, 'P'}, {"strand_type", required_argument, 0, 's'},
         {"maxthread", required_argument, 0, 'p'}, {"max_repeat", required_argument, 0, 'k'}, {"nround", required_argument, 0, 'n'},
@@ -493,6 +526,7 @@ int main(int argc, char **argv) {
         {"subsample", required_argument, 0, 1015}, {"subsample-reps", required_argument, 0, 1016}, {"subsample-seed", required_argument, 0, 1017},
         {"bootstrap-quantiles", required_argument, 0, 1018}, {"isoforms", no_argument, 0, 1019}, {"fit", no_argument, 0, 1020},
         {"presence", no_argument, 0, 1021}, {"presence-list", required_argument, 0, 1022},
+        {"asymptotic", no_argument, 0, 1023}, {"boundary-cut", required_argument, 0, 1024},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
@@ -587,6 +621,8 @@ int main(int argc, char **argv) {
             case 1020: cfg.fit = 1; break;
             case 1021: cfg.presence = 1; break;
             case 1022: presence_list = optarg; break;
+            case 1023: cfg.asymptotic = 1; break;
+            case 1024: cfg.boundary_cut = atof(optarg); boundary_cut_given = 1; break;
             case 1009: {
                 const char *q = optarg;
                 while (*q && n_dev_map < 64) {
@@ -606,6 +642,9 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--bootstrap-quantiles needs --bootstrap B with 1 <= B <= 4096 replicates.\n"); return 1;
     }
     if (cfg.isoforms && !cfg.g2t) { fprintf(stderr, "--isoforms needs --g2t FILE.\n"); return 1; }
+    if (boundary_cut_given && !cfg.asymptotic) { fprintf(stderr, "--boundary-cut needs --asymptotic.\n"); return 1; }
+    if (boundary_cut_given && !(cfg.boundary_cut >= 0.0)) { fprintf(stderr, "--boundary-cut must be >= 0.\n"); return 1; }
+    if (!boundary_cut_given) cfg.boundary_cut = EMSAR_ASYM_DEFAULT_CUT;
     if (presence_list && !cfg.presence) { fprintf(stderr, "--presence-list needs --presence.\n"); return 1; }
     if (!cfg.rsh_path || optind + 2 >= argc) { usage(argv[0]); return 1; }
     if (emsar_set_strand(strand, cfg.ao.pe, &cfg.ao.strand)) { fprintf(stderr, "error: invalid strand type.\n"); return 1; }

@@ -184,6 +184,15 @@ int emsar_write_gfit(const char *path, const emsar_rsh *r, const emsar_genes *g,
  * UNCONVERGED), heir the heir's transcriptID or "-"; a value that is not finite is written as "inf" or "nan" */
 int emsar_write_presence(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, const double *fpkm, const double *lambda,
                          const double *pvalue, const int32_t *status, const int32_t *heir, const double *heir_share);
+
+/* .asym (emsar-hip --asymptotic): one line per transcript -- tid transcriptID FPKM sd_FPKM TPM sd_TPM status partner partner_corr, and
+ * usage_sd when it is given (--g2t); the arrays are [n_tx] as emsar_hip_asymptotic returns them.  partner_corr = partner_cov /
+ * sqrt(var_t * var_partner); "-" and nan where there is no partner.  sd values are written "%.6g", or the words inf / nan.
+ * .gasym: one line per gene -- geneID gFPKM sd status. */
+int emsar_write_asym(const char *path, const emsar_rsh *r, const double *fpkm, const double *tpm, const double *sd_fpkm, const double *sd_tpm,
+                     const double *var, const int32_t *status, const int32_t *partner, const double *partner_cov, const double *usage_sd);
+int emsar_write_gasym(const char *path, const emsar_genes *g, const double *gfpkm, const double *gene_sd, const int32_t *gene_status);
+
 /* .saturation (emsar-hip --subsample): a "#" line (fractions, replicates, seed, depth_mean per fraction), a header, then per
  * transcript its name, FPKM and TPM as in .fpkm and per fraction mean_FPKM sd_FPKM mean_TPM sd_TPM ([n_fractions][n_tx] each) */
 int emsar_write_saturation(const char *path, const emsar_rsh *r, const double *fpkm, const double *tpm, int n_fractions,

@@ -178,6 +178,39 @@ int emsar_write_presence(const char *path, const emsar_rsh *r, int32_t n_query, 
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
 
+static const char *const asym_word[5] = {"ESTIMATED", "BOUNDARY", "UNIDENTIFIABLE", "TOO_LARGE", "INFEASIBLE"};
+
+int emsar_write_asym(const char *path, const emsar_rsh *r, const double *fpkm, const double *tpm, const double *sd_fpkm, const double *sd_tpm,
+                     const double *var, const int32_t *status, const int32_t *partner, const double *partner_cov, const double *usage_sd) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "tid\ttranscriptID\tFPKM\tsd_FPKM\tTPM\tsd_TPM\tstatus\tpartner\tpartner_corr%s\n", usage_sd ? "\tusage_sd" : "");
+    for (int32_t t = 0; t < r->n_tx; t++) {
+        const int32_t q = partner[t] >= 0 && partner[t] < r->n_tx ? partner[t] : -1;
+        fprintf(f, "%d\t%s\t%lf\t", t, r->names[t], fpkm[t]);
+        put_value(f, "%.6g", sd_fpkm[t]);
+        fprintf(f, "\t%lf\t", tpm[t]);
+        put_value(f, "%.6g", sd_tpm[t]);
+        fprintf(f, "\t%s\t%s\t", status[t] >= 0 && status[t] < 5 ? asym_word[status[t]] : "?", q >= 0 ? r->names[q] : "-");
+        put_value(f, "%.6g", q >= 0 ? partner_cov[t] / sqrt(var[t] * var[q]) : NAN);
+        if (usage_sd) { fputc('\t', f); put_value(f, "%.6g", usage_sd[t]); }
+        fputc('\n', f);
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+int emsar_write_gasym(const char *path, const emsar_genes *g, const double *gfpkm, const double *gene_sd, const int32_t *gene_status) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "geneID\tgFPKM\tsd\tstatus\n");
+    for (int32_t k = 0; k < g->n_genes; k++) {
+        fprintf(f, "%s\t%lf\t", g->names[k], gfpkm[k]);
+        put_value(f, "%.6g", gene_sd[k]);
+        fprintf(f, "\t%s\n", gene_status[k] >= 0 && gene_status[k] < 5 ? asym_word[gene_status[k]] : "?");
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
 /* the rows of .saturation / .gsaturation: n names, per fraction ncol columns col[j] = [n_fractions][n] */
 static int write_saturation(const char *path, const char *id, char **names, int64_t n, const double *fpkm, const double *tpm, int n_fractions,
                             const double *fractions, int n_replicates, uint64_t seed, const double *depth_mean, int ncol,

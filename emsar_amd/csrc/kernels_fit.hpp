@@ -100,7 +100,7 @@ __global__ __launch_bounds__(1024) void k_fit_totals(int64_t n_rows, const emsar
 // caller's order and numbering (the layout's own CSR may carry the library's tids), the transposed index, the rows' records and the
 // chunks' partials.
 struct FitDev {
-    bool ready = false;
+    bool ready = false, csr_ready = false;      // the index with its tables; the CSR alone (fit_ensure_csr: asym.hpp needs no index)
     int64_t n_chunks = 0, n_groups = 0, n_multi = 0, index_slots = 0, index_bytes = 0;
     emsar::DevBuf<uint64_t> d_row_ptr;
     emsar::DevBuf<int32_t> d_col;

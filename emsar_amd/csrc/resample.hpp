@@ -649,6 +649,7 @@ int emsar_hip_set_gene_map(emsar_hip_ctx *ctx, int32_t n_genes, const int32_t *g
         G.d_gene_multi = G.d_chunk_out + nc;
         G.d_gene_of_lib = G.d_gene_multi + multi.size();
         G.n_genes = n_genes; G.n_gene_chunks = (int64_t)nc; G.n_gene_multi = (int64_t)multi.size() / 3;
+        G.h_gene_of_tx.assign(gene_of_tx, gene_of_tx + n);
         G.have_genes = true;
         ctx->genes = std::move(G);
     } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }

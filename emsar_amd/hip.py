@@ -27,10 +27,16 @@ SYMBOLS = [
     "emsar_hip_isoform_usage", "emsar_hip_isoform_usage_host", "emsar_hip_bootstrap_isoforms",
     "emsar_hip_model_fit", "emsar_hip_model_fit_host",
     "emsar_hip_presence", "emsar_hip_presence_pvalue_host",
+    "emsar_hip_asymptotic", "emsar_hip_asymptotic_host",
 ]
 
 # status of a transcript in the presence test (include/emsar_hip.h "presence test"), by value
 PRESENCE_STATUS = ("TESTED", "ABSENT", "ESSENTIAL", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED")
+
+# status of a transcript in the asymptotic standard errors (include/emsar_hip.h "asymptotic standard errors"), by value
+ASYM_STATUS = ("ESTIMATED", "BOUNDARY", "UNIDENTIFIABLE", "TOO_LARGE", "INFEASIBLE")
+ASYM_MAX_N = 192
+ASYM_DEFAULT_CUT = 5e-7
 
 
 class EmsarHipError(RuntimeError):
@@ -119,6 +125,31 @@ class PresenceStats(C.Structure):
         return d
 
 
+class AsymParams(C.Structure):
+    _fields_ = [("boundary_cut", C.c_double), ("pivot_tol", C.c_double), ("block_tid", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class AsymOutputs(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in ("var", "sd_fpkm", "sd_tpm", "rowsum", "usage_sd")] + [
+        ("status", C.POINTER(C.c_int32)), ("partner", C.POINTER(C.c_int32)), ("partner_cov", C.POINTER(C.c_double)),
+        ("blocker", C.POINTER(C.c_int32)), ("gene_sd", C.POINTER(C.c_double)), ("gene_status", C.POINTER(C.c_int32)),
+        ("block_n", C.POINTER(C.c_int32)), ("block_tids", C.POINTER(C.c_int32)), ("block_cov", C.POINTER(C.c_double))]
+
+
+class AsymStats(C.Structure):
+    _fields_ = [("components", C.c_int64), ("components_too_large", C.c_int64), ("components_infeasible", C.c_int64),
+                ("components_class", C.c_int64 * 4), ("components_unidentifiable", C.c_int64), ("n_status", C.c_int64 * 5),
+                ("rows_infeasible", C.c_int64), ("max_n", C.c_int32), ("reserved0", C.c_int32), ("min_pivot_ratio", C.c_double),
+                ("theta_unestimated_share", C.c_double), ("plan_ms", C.c_double), ("rows_ms", C.c_double), ("sets_ms", C.c_double),
+                ("genes_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["n_status"] = dict(zip(ASYM_STATUS, d["n_status"]))
+        d["components_class"] = list(d["components_class"])
+        return d
+
+
 class SetsInfo(C.Structure):
     _fields_ = [("n_components", C.c_int64), ("sets_resident", C.c_int64 * 3), ("max_lds_bytes", C.c_int64 * 3),
                 ("sets_streamed", C.c_int64), ("tids_closed", C.c_int64), ("tids_resident", C.c_int64),
@@ -193,6 +224,9 @@ def load_library():
                                            C.POINTER(FitStats)]
     L.emsar_hip_presence.argtypes = [vp, C.POINTER(EmParams), C.c_int32, i32p, C.POINTER(PresenceOutputs), C.POINTER(PresenceStats)]
     L.emsar_hip_presence_pvalue_host.argtypes = [C.c_int64, f64p, f64p]
+    L.emsar_hip_asymptotic.argtypes = [vp, f64p, C.POINTER(AsymParams), C.POINTER(AsymOutputs), C.POINTER(AsymStats)]
+    L.emsar_hip_asymptotic_host.argtypes = [C.c_int64, C.c_int32, u64p, i32p, i32p, f64p, f64p, C.c_int32, i32p, C.POINTER(AsymParams),
+                                            C.POINTER(AsymOutputs), C.POINTER(AsymStats)]
     _lib = L
     return L
 
@@ -332,6 +366,54 @@ def model_fit_host(n_tx, row_ptr, col_idx, theta, row_weight=None, E=None, rows=
     if rc != 0:
         raise EmsarHipError(rc, "model_fit_host")
     return _fit_result(res, n_rows, int(n_tx), int(n_genes), st)
+
+
+def _asym_buffers(n_tx, n_genes, genes, block):
+    """the output arrays of the asymptotic standard errors (never of length 0) and the struct that points at them"""
+    T = max(n_tx, 1)
+    res = {k: np.zeros(T) for k in ("var", "sd_fpkm", "sd_tpm", "rowsum", "partner_cov")}
+    res.update({k: np.zeros(T, dtype=np.int32) for k in ("status", "partner", "blocker")})
+    if genes:
+        res.update(usage_sd=np.zeros(T), gene_sd=np.zeros(max(n_genes, 1)), gene_status=np.zeros(max(n_genes, 1), dtype=np.int32))
+    if block:
+        res.update(block_n=np.zeros(1, dtype=np.int32), block_tids=np.zeros(ASYM_MAX_N, dtype=np.int32), block_cov=np.zeros(ASYM_MAX_N * ASYM_MAX_N))
+    o = AsymOutputs()
+    for k, a in res.items():
+        setattr(o, k, _p(a, C.c_int32 if a.dtype == np.int32 else C.c_double))
+    return res, o
+
+
+def _asym_result(res, n_tx, n_genes, st):
+    out = {k: v[:(n_genes if k.startswith("gene_") else n_tx)] for k, v in res.items() if not k.startswith("block_")}
+    if "block_n" in res:
+        n = int(res["block_n"][0])
+        out["block_tids"] = res["block_tids"][:n]
+        out["block_cov"] = res["block_cov"][:n * n].reshape(n, n)
+    out["stats"] = st
+    return out
+
+
+def asymptotic_host(n_tx, row_ptr, col_idx, theta, row_weight=None, E=None, gene_of_tx=None, n_genes=0, boundary_cut=None, pivot_tol=0.0,
+                    block_tid=-1):
+    """Host-only: the asymptotic standard errors (include/emsar_hip.h "asymptotic standard errors") of theta from the inverse of the
+    observed information, no GPU needed, the same functions the device evaluates.  Rows with E == 0 count no reads; boundary_cut None =
+    ASYM_DEFAULT_CUT.  Returns a dict:
+    var, sd_fpkm, sd_tpm, rowsum, partner_cov, status (index into ASYM_STATUS), partner, blocker ([n_tx]); with a gene map also
+    usage_sd ([n_tx]), gene_sd, gene_status ([n_genes]); with block_tid >= 0 also block_tids [n] and block_cov [n][n]; stats."""
+    L = load_library()
+    row_ptr, col_idx, th = _arr(row_ptr, np.uint64), _arr(col_idx, np.int32), _arr(theta, np.float64)
+    w, e, g = _arr(row_weight, np.int32), _arr(E, np.float64), _arr(gene_of_tx, np.int32)
+    n_rows = len(row_ptr) - 1
+    for a, n in ((th, n_tx), (w, n_rows), (e, n_rows), (g, n_tx)):
+        if a is not None and a.shape != (n,):
+            raise ValueError("array of length %d expected" % n)
+    res, o = _asym_buffers(int(n_tx), int(n_genes), g is not None, block_tid >= 0)
+    p, st = AsymParams(ASYM_DEFAULT_CUT if boundary_cut is None else boundary_cut, pivot_tol, int(block_tid), 0), AsymStats()
+    rc = L.emsar_hip_asymptotic_host(n_rows, int(n_tx), _p(row_ptr, C.c_uint64), _p(col_idx, C.c_int32), _p(w, C.c_int32), _p(e, C.c_double),
+                                     _p(th, C.c_double), int(n_genes), _p(g, C.c_int32), C.byref(p), C.byref(o), C.byref(st))
+    if rc != 0:
+        raise EmsarHipError(rc, "asymptotic_host")
+    return _asym_result(res, int(n_tx), int(n_genes), st)
 
 
 def presence_pvalue_host(lam):
@@ -595,6 +677,18 @@ class EmsarHip:
         out = {k: v[:nq] for k, v in res.items()}
         out["stats"] = st
         return out
+
+    def asymptotic(self, theta, boundary_cut=None, pivot_tol=0.0, block_tid=-1, genes=False):
+        """Asymptotic standard errors of theta from the inverse of the observed information of the current sample (include/emsar_hip.h
+        "asymptotic standard errors"); asymptotic_host describes the result.  genes (after set_gene_map) adds usage_sd, gene_sd and
+        gene_status.  After upload_sample; the context is left as it was."""
+        th = _arr(theta, np.float64)
+        if th.shape != (self.n_tx,):
+            raise ValueError("array of length %d expected" % self.n_tx)
+        res, o = _asym_buffers(self.n_tx, self.n_genes, genes, block_tid >= 0)
+        p, st = AsymParams(ASYM_DEFAULT_CUT if boundary_cut is None else boundary_cut, pivot_tol, int(block_tid), 0), AsymStats()
+        self._chk(self._L.emsar_hip_asymptotic(self._h, _p(th, C.c_double), C.byref(p), C.byref(o), C.byref(st)), "asymptotic")
+        return _asym_result(res, self.n_tx, self.n_genes, st)
 
     def bootstrap_weights(self, seed, replicate):
         """The drawn row weights of one bootstrap replicate (caller row order), drawn on the device."""

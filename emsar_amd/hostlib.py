@@ -92,6 +92,8 @@ def lib():
         L.emsar_write_isoforms.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Genes), f64p, f64p, i32p, C.c_int, f64p, f64p, i32p,
                                            C.c_int, f64p, f64p]
         L.emsar_write_presence.argtypes = [C.c_char_p, C.POINTER(Rsh), C.c_int32, i32p, f64p, f64p, f64p, i32p, i32p, f64p]
+        L.emsar_write_asym.argtypes = [C.c_char_p, C.POINTER(Rsh)] + [f64p] * 5 + [i32p, i32p, f64p, f64p]
+        L.emsar_write_gasym.argtypes = [C.c_char_p, C.POINTER(Genes), f64p, f64p, i32p]
         _lib = L
     return _lib
 
@@ -143,6 +145,35 @@ def write_presence(path, tx_names, fpkm, lam, pvalue, status, heir, heir_share, 
                                     _dp(a[3]))
     if rc != 0:
         raise HostError("write_presence rc=%d" % rc)
+
+
+def write_asym(path, tx_names, fpkm, tpm, sd_fpkm, sd_tpm, var, status, partner, partner_cov, usage_sd=None):
+    """.asym (emsar_write_asym): transcripts tx_names with fpkm, tpm [n_tx] and sd_fpkm, sd_tpm, var, status, partner, partner_cov (and
+    usage_sd) as EmsarHip.asymptotic returns them."""
+    n_tx = len(tx_names)
+    names = (C.c_char_p * max(n_tx, 1))(*[s.encode() for s in tx_names])
+    r = Rsh(n_tx=n_tx, names=C.cast(names, C.POINTER(C.c_char_p)))
+    f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    a = [f64(x) for x in (fpkm, tpm, sd_fpkm, sd_tpm, var, partner_cov, usage_sd)]
+    st, pa = i32(status), i32(partner)
+    ip = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))
+    rc = lib().emsar_write_asym(path.encode(), C.byref(r), _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3]), _dp(a[4]), ip(st), ip(pa), _dp(a[5]),
+                                None if a[6] is None else _dp(a[6]))
+    if rc != 0:
+        raise HostError("write_asym rc=%d" % rc)
+
+
+def write_gasym(path, gene_names, gfpkm, gene_sd, gene_status):
+    """.gasym (emsar_write_gasym): genes gene_names with their FPKM sums, gene_sd and gene_status as EmsarHip.asymptotic returns them."""
+    n = len(gene_names)
+    names = (C.c_char_p * max(n, 1))(*[s.encode() for s in gene_names])
+    g = Genes(n_genes=n, names=C.cast(names, C.POINTER(C.c_char_p)))
+    a, b = (np.ascontiguousarray(x, dtype=np.float64) for x in (gfpkm, gene_sd))
+    st = np.ascontiguousarray(gene_status, dtype=np.int32)
+    rc = lib().emsar_write_gasym(path.encode(), C.byref(g), _dp(a), _dp(b), st.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise HostError("write_gasym rc=%d" % rc)
 
 
 class HostRsh:

@@ -477,6 +477,109 @@ int emsar_hip_presence(emsar_hip_ctx *ctx, const emsar_em_params *p, int32_t n_q
                        const emsar_presence_outputs *out /* or NULL */, emsar_presence_stats *stats /* or NULL */);
 int emsar_hip_presence_pvalue_host(int64_t n, const double *lambda, double *p_out);
 
+/* ---- asymptotic standard errors: the inverse of the observed information at the MLE ---------------
+ * How sure is theta_t, without resampling?  For a theta that maximises the likelihood of the current sample, the observed information
+ * of the ACTIVE transcripts is J_ij = sum_c m_ci m_cj R_c / S_c^2 (m_ci = how often i stands in row c); its inverse is the asymptotic
+ * covariance of the estimates.  J is block diagonal over the connected components of the active transcripts, so one dense
+ * factorisation per component replaces the B solves of the bootstrap.  The function does not check that theta is an MLE.
+ * ASYMPTOTIC NORMALITY DOES NOT HOLD AT THE BOUNDARY: a transcript whose estimate is (about) 0 has a one-sided, non-normal
+ * distribution.  Such transcripts are held fixed here and get variance 0; the bootstrap (emsar_hip_bootstrap*) is the tool there, and
+ * for transcripts that are nearly confounded with a sibling (a tiny pivot; see min_pivot_ratio and partner).
+ * Everything is in caller numbering and caller row order: no result depends on the layout, on MERGE_ROWS, on the library's own
+ * transcript numbering or on the device.  Every operation below is rounded on its own (no fused multiply-add).
+ * Inputs: the structure of upload_structure; R_c = the row weights of upload_sample (0 where E was 0 at that call); theta[n_tx],
+ * finite and >= 0, checked on the host; the parameters: boundary_cut (params NULL means EMSAR_ASYM_DEFAULT_CUT, 5e-7, the .fpkm
+ * print quantum; 0 is allowed; a negative cut is taken as it stands and makes every transcript active, theta_t = 0 included),
+ * pivot_tol (<= 0 means 1e-10), block_tid (-1 = none).
+ * Active set.  t is ACTIVE iff theta_t > boundary_cut.  Inactive transcripts are held fixed: they still count in every S_c, and get
+ *   status BOUNDARY, var 0, rowsum 0, partner -1, partner_cov NaN.
+ * Rows.  S_c = sum of theta over the row's entries, left to right (a repeated tid counts twice).  w_c = R_c / (S_c * S_c) when
+ *   R_c > 0 and S_c > 0, else 0.  A row with entries, R_c > 0 and S_c == 0 is INFEASIBLE (counted in rows_infeasible); only an infeasible row
+ *   that holds an ACTIVE transcript marks a component, which can only be when boundary_cut < 0 was given (theta_t = 0 > cut).  Its
+ *   component gets status INFEASIBLE (numeric outputs NaN).  An infeasible row without an active transcript belongs to no component.
+ * Components: the connected components of the ACTIVE transcripts, linked by the rows with w_c != 0 and by infeasible rows.  Local
+ *   indices 0 .. n-1 by ascending caller tid; components are ordered by their smallest tid.  A component of more than 192 active
+ *   transcripts is TOO_LARGE (numeric outputs NaN); TOO_LARGE wins over INFEASIBLE.
+ * Information matrix, n x n, lower triangle.  J_ij starts from 0.0; over the entries k of transcript i in (caller row ascending,
+ *   position ascending) order, and for each over the entries k' of transcript j in the same row in position order: J_ij = J_ij + w_c.
+ *   A tid that stands twice in a row adds w_c four times to its diagonal.
+ * LDL^T without square roots.  For j = 0 .. n-1 and i >= j:  acc = J_ij;  for k < j ascending  acc = acc - (L_ik * D_k) * L_jk;
+ *   i == j: D_j = acc;  i > j: L_ij = acc / D_j.  Pivot rule: D_j must be finite and D_j > pivot_tol * J_jj (the original diagonal);
+ *   otherwise the component is UNIDENTIFIABLE: var = rowsum = +inf, partner -1, partner_cov NaN, and blocker = the caller tid of
+ *   local j, the first failing pivot.  A one-transcript component with J_tt == 0 (no row with reads holds it) fails the same way.
+ * M = L^-1, row by row; for j < i:  acc = L_ij;  for k = j+1 .. i-1  acc = acc + L_ik * M_kj;  M_ij = -acc;  M_ii = 1.
+ * Covariance.  Sigma_ij = sum over k = max(i,j) .. n-1 ascending of (M_ki * M_kj) / D_k, starting from the first term.
+ * Per ESTIMATED transcript (local i):
+ *   var         = Sigma_ii
+ *   rowsum      = sum_j Sigma_ij, j ascending, starting from the first term
+ *   genesum     = the same sum over the j with gene(j) == gene(i) >= 0; 0 without a gene map or for gene -1 (internal: it feeds gene_sd)
+ *   partner     = the caller tid of the j != i that minimises Sigma_ij * |Sigma_ij| / Sigma_jj (the most negative correlation, signed
+ *                 and squared, times var: only *, / and comparisons), the lowest local index among equal values, the first j when
+ *                 no value compares below it; -1 when n == 1.  partner_cov = that Sigma_ij (NaN when none).  It names the sibling t
+ *                 is most confounded with.
+ * Block output: with block_tid >= 0 the component of that transcript whole: block_n = n, block_tids[0 .. n-1] and block_cov, the
+ *   first n * n entries row-major with rows of n, symmetric.  block_n = 0 when the transcript is not ESTIMATED or block_tid = -1.
+ *   All three pointers given, or none.
+ * Host finish: one function for the device path and the host path, evaluated as written, left to right.  "chunked sum" = gene_sums'
+ *   rule over ascending tid: consecutive chunks of 256 added left to right from their first term, then the chunk sums left to right.
+ *   sd_fpkm  = sqrt(var)
+ *   S        = the chunked sum of theta over all transcripts;  V_S = the chunked sum of rowsum over the ESTIMATED transcripts (the
+ *              others count 0.0).  V_S LEAVES OUT the variance of active transcripts that are not ESTIMATED; their share of S is
+ *              theta_unestimated_share = (chunked sum of theta over the active, not ESTIMATED transcripts) / S, 0 for S == 0.
+ *   a = theta_t / S;  var_tpm = ((1e6 / S) * (1e6 / S)) * max(0, var - 2 * a * rowsum + a * a * V_S);  sd_tpm = sqrt(var_tpm) for an
+ *              ESTIMATED or BOUNDARY transcript, +inf for UNIDENTIFIABLE, NaN for TOO_LARGE and INFEASIBLE; 0 for all when S == 0.
+ *              max(0, x) is x when x > 0, else 0.
+ *   per gene   V_G = gene_sums of genesum (its own order; on the device path the device's gene_sums), gene_sd = sqrt(V_G).
+ *              gene_status = TOO_LARGE if a transcript of the gene is, else INFEASIBLE, else UNIDENTIFIABLE, else ESTIMATED if one
+ *              is, else BOUNDARY; gene_sd = NaN for TOO_LARGE and INFEASIBLE, +inf for UNIDENTIFIABLE.
+ *   usage_sd   G = gene_sums of theta, u = theta_t / G:  sqrt(max(0, var - 2 * u * genesum + u * u * V_G)) / G; 0 for G == 0; NaN /
+ *              +inf where gene_sd is; NaN for a transcript without a gene.  Needs the gene map.
+ *   asymptotic       ERR_STATE before upload_sample and for gene outputs (gene_sd, gene_status, usage_sd) without a map; ERR_ARG for
+ *                    a NULL, negative or non-finite theta, a block_tid outside -1 .. n_tx-1, a gene group or a block group only
+ *                    partly given.  out, stats and params may be NULL.  The first call after upload_structure uploads the
+ *                    caller-order CSR model_fit shares.  The context is left as it was: a following solve returns the same bits.
+ *   asymptotic_host  the same definition with no HIP call and no context; row_E NULL or given: rows with E == 0 have R = 0.  The
+ *                    stage times of the device stay 0.  Device and host return the same bits in every output.
+ * Device: EMSAR_HIP_ASYM_CLASS = 1 | 2 runs every component in at least the 64-lane / the 256-thread kernel (a testing aid; the bits
+ * do not change). */
+enum {
+    EMSAR_ASYM_ESTIMATED = 0, EMSAR_ASYM_BOUNDARY = 1, EMSAR_ASYM_UNIDENTIFIABLE = 2, EMSAR_ASYM_TOO_LARGE = 3, EMSAR_ASYM_INFEASIBLE = 4
+};
+#define EMSAR_ASYM_MAX_N 192
+#define EMSAR_ASYM_DEFAULT_CUT 5e-7
+typedef struct { double boundary_cut, pivot_tol; int32_t block_tid, reserved0; } emsar_asym_params;
+typedef struct {
+    double  *var, *sd_fpkm, *sd_tpm, *rowsum, *usage_sd;    /* [n_tx]; may each be NULL; usage_sd needs the gene map */
+    int32_t *status, *partner;                              /* [n_tx] EMSAR_ASYM_*; caller tid or -1 */
+    double  *partner_cov;                                   /* [n_tx] */
+    int32_t *blocker;                                       /* [n_tx] caller tid of the first failing pivot of an UNIDENTIFIABLE component, else -1 */
+    double  *gene_sd;                                       /* [n_genes]; gene_sd and gene_status both NULL, or both given after set_gene_map */
+    int32_t *gene_status;                                   /* [n_genes] */
+    int32_t *block_n, *block_tids;                          /* [1], [192] */
+    double  *block_cov;                                     /* [192 * 192] */
+} emsar_asym_outputs;
+typedef struct {
+    int64_t components;                  /* all components of active transcripts, the next two included */
+    int64_t components_too_large, components_infeasible;
+    int64_t components_class[4];         /* factorised: by one lane (n == 1), 8 lanes, one wave, 256 threads (the host path counts by n) */
+    int64_t components_unidentifiable;
+    int64_t n_status[5];                 /* transcripts per status */
+    int64_t rows_infeasible;             /* rows with R_c > 0 and S_c == 0 */
+    int32_t max_n, reserved0;            /* the largest component, TOO_LARGE ones included */
+    double  min_pivot_ratio;             /* the smallest D_j / J_jj over every pivot up to a component's first failing one; +inf if none */
+    double  theta_unestimated_share;
+    double  plan_ms;                     /* host: active set, components, records */
+    double  rows_ms, sets_ms, genes_ms;  /* device time per stage (HIP events); 0 on the host path */
+    double  total_ms;                    /* wall time of the call */
+} emsar_asym_stats;
+int emsar_hip_asymptotic(emsar_hip_ctx *ctx, const double *theta /* n_tx */, const emsar_asym_params *params /* or NULL: defaults */,
+                         const emsar_asym_outputs *out /* or NULL */, emsar_asym_stats *stats /* or NULL */);
+int emsar_hip_asymptotic_host(int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr, const int32_t *col_idx,
+                              const int32_t *row_weight /* NULL = 1 */, const double *row_E /* or NULL */, const double *theta,
+                              int32_t n_genes, const int32_t *gene_of_tx /* n_tx, or NULL = no gene map */,
+                              const emsar_asym_params *params /* or NULL */, const emsar_asym_outputs *out /* or NULL */,
+                              emsar_asym_stats *stats /* or NULL */);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 typedef struct {
     int64_t n_rows, nnz;
