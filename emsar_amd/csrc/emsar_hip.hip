@@ -18,6 +18,7 @@
 //   resample.hpp      the resampling driver and its C ABI -- bootstrap, quantiles, subsampling, genes
 //   fit.hpp           the model fit and its C ABI
 //   presence.hpp      the presence test (a likelihood-ratio test per transcript on its resident set) and its C ABI
+//   profile.hpp       the profile-likelihood intervals (two confidence limits per transcript, each a root search over set solves) and their C ABI
 // Kernels (one translation unit, included below):
 //   kernels_tiled.hpp     k_pass_tiled_unit                      the hot one (the default above 2048 tiles): one workgroup per UNIT of up to
 //                         two tiles of the TILED layout that share a dictionary of theta/acc in LDS (60 blocks x 16 subset sums),
@@ -29,6 +30,7 @@
 //                         k_normalise, k_adj_euma, small reductions
 //   kernels_sets.hpp      k_solve_sets                           one workgroup solves one connected set out of LDS
 //   kernels_presence.hpp  k_solve_sets_drop                      a set solved without one of its transcripts, and F at the result out of the same LDS
+//   kernels_profile.hpp   k_profile_sets                         one workgroup searches one confidence limit: set solves with den_t scaled, F as above
 //   kernels_boot.hpp      k_boot_draw, k_boot_accum, ...         the Poisson bootstrap (draws: boot_rng.hpp; sets: k_solve_sets_boot)
 //                         k_sub_draw, k_sub_scale                the depth subsampling: binomial draws, every replicate to its own depth
 //   kernels_genes.hpp     k_gene_sums, k_gene_finish             per-gene sums in a fixed order (gene_sums, the bootstrap's gene sd)
@@ -67,6 +69,7 @@
 #include "kernels_vector.hpp"
 #include "kernels_sets.hpp"
 #include "kernels_presence.hpp"
+#include "kernels_profile.hpp"
 #include "kernels_cluster.hpp"
 #include "kernels_boot.hpp"
 #include "kernels_genes.hpp"
@@ -816,4 +819,5 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 #include "resample.hpp"   // the resampling driver and its entry points: bootstrap, genes, quantiles, subsampling
 #include "fit.hpp"        // the model fit and its entry points (after resample.hpp: the gene step is launch_gene_sums)
 #include "presence.hpp"   // the presence test and its entry points (after resample.hpp: free_device_bytes)
+#include "profile.hpp"    // the profile-likelihood intervals and their entry points (after presence.hpp: PresenceRun)
 #include "asym.hpp"       // the asymptotic standard errors and their entry points (after fit.hpp: fit_ensure_csr, launch_gene_sums)

@@ -35,6 +35,10 @@
  * --presence answers "is this isoform needed to explain the reads at all": <prefix>.<i>.presence holds, per transcript (or per transcript named in
  * --presence-list FILE, one name per line), the likelihood-ratio statistic Lambda of dropping it from its connected set, its p-value, a status
  * word and the sibling that would take over its reads (emsar_hip_presence with the solve's parameters).  The other files do not change with it.
+ * --profile answers "how much of this isoform could be present": <prefix>.<i>.profile holds, per transcript (or per transcript named in
+ * --profile-list FILE), the limits of its profile-likelihood interval at --profile-level (0.95) in the units of the FPKM column, the
+ * presence test's Lambda and a status word (emsar_hip_profile with the solve's parameters).  The interval is one-sided by itself where the
+ * transcript cannot be told from absent, FPKM 0 included.  The other files do not change with it.
  * --asymptotic answers "how sure is this FPKM" without resampling: <prefix>.<i>.asym holds, per transcript, the standard errors of FPKM and
  * TPM from the inverse of the observed information at the .fpkm column (emsar_hip_asymptotic), a status word and the sibling it is most
  * confounded with; with --g2t also <prefix>.<i>.gasym per gene and a usage_sd column.  Transcripts with FPKM <= --boundary-cut (5e-7) are held
@@ -79,6 +83,8 @@ typedef struct {
     int presence;                     /* --presence */
     int asymptotic; double boundary_cut;   /* --asymptotic [--boundary-cut X] */
     int32_t *pres_q; int pres_nq;     /* --presence-list FILE: the tids it names, in file order (NULL = all transcripts) */
+    int profile, profile_evals; double profile_level; /* --profile [--profile-level L] [--profile-evals N] */
+    int32_t *prof_q; int prof_nq;     /* --profile-list FILE, as --presence-list */
     const emsar_genes *genes;         /* its gene map, read once by main() and shared read-only by the workers */
 } config;
 
@@ -298,6 +304,24 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         free(pv); free(pi);
         if (rc) goto done;
     }
+    /* ---- profile-likelihood intervals (--profile): two confidence limits per transcript on its connected set, on the device ---- */
+    if (cfg->profile) {
+        const size_t Q = cfg->prof_q ? (size_t)cfg->prof_nq : T, Qa = Q > 0 ? Q : 1;
+        double *pv = (double *)malloc(Qa * 8 * 3);
+        int32_t *pi = (int32_t *)malloc(Qa * 4);
+        const emsar_profile_params pp = {cfg->profile_level, 0.0, cfg->profile_evals, 0};
+        const emsar_profile_outputs po = {pv, pv ? pv + Q : NULL, NULL, NULL, pv ? pv + 2 * Q : NULL, NULL, pi, NULL};
+        if (!pv || !pi) rc = EMSAR_HOST_ERR_OOM;
+        else if ((rc = emsar_hip_profile(ctx, &p, &pp, (int32_t)Q, cfg->prof_q, &po, NULL)))
+            fprintf(stderr, "alnfile[%d]: profile: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+        else {
+            snprintf(path, sizeof path, "%s/%s.%d.profile", cfg->outdir, cfg->prefix, i);
+            if ((rc = emsar_write_profile(path, r, (int32_t)Q, cfg->prof_q, mean, po.lower, po.upper, po.lambda, po.status)))
+                fprintf(stderr, "can't write %s\n", path);
+        }
+        free(pv); free(pi);
+        if (rc) goto done;
+    }
     /* ---- asymptotic standard errors (--asymptotic): the inverse of the observed information at the printed FPKM, on the device ---- */
     if (cfg->asymptotic) {
         const size_t Ta = T > 0 ? T : 1, Ga = NG > 0 ? NG : 1;
@@ -495,12 +519,41 @@ static void usage(const char *a0) {
             "                            set without it, the p-value, a status word (TESTED, ABSENT, ESSENTIAL, OUTSIDE, NOT_RESIDENT, UNCONVERGED)\n"
             "                            and the sibling that takes over most of its reads, with the share it takes\n"
             "      --presence-list <file> with --presence: test only the transcripts named in the file, one name per line\n"
+            "      --profile             also write <prefix>.<i>.profile: per transcript the lower and upper limit of its profile-likelihood interval, the\n"
+            "                            presence test's Lambda and a status word (TWO_SIDED, LOWER_ZERO, OUTSIDE, NOT_RESIDENT, UNCONVERGED); valid at FPKM 0\n"
+            "      --profile-level <l>   with --profile: the confidence level, 0 < l < 1 (default 0.95)\n"
+            "      --profile-evals <n>   with --profile: at most n set solves per limit (default 40); a search that needs more is UNCONVERGED\n"
+            "      --profile-list <file> with --profile: only the transcripts named in the file, one name per line\n"
             "      --asymptotic          also write <prefix>.<i>.asym: per transcript the asymptotic standard error of FPKM and TPM from the inverse of\n"
             "                            the observed information, a status word and the sibling it is most confounded with; with --g2t also\n"
             "                            <prefix>.<i>.gasym (per gene) and a usage_sd column.  Not valid at the boundary (FPKM about 0): use --bootstrap there\n"
             "      --boundary-cut <x>    with --asymptotic: transcripts with FPKM <= x are held fixed (default 5e-7, the .fpkm print quantum)\n"
             "      --gpus <n> / --devices <a,b,..> (-M: one worker per entry, ids may repeat) / --device <d> / --plain /\n"
             "      --stats-json <file> / -q / -v\n", a0);
+}
+
+/* --presence-list / --profile-list FILE: the tids of the transcripts it names, one name per line, in file order */
+static int read_name_list(const char *what, const char *file, const emsar_rsh *rsh, int32_t **q_out, int *nq_out) {
+    FILE *f = fopen(file, "r");
+    if (!f) { fprintf(stderr, "Can't open the %s list %s.\n", what, file); return 1; }
+    char line[4096];
+    int32_t *q = (int32_t *)malloc(sizeof(int32_t));
+    int nq = 0;
+    while (q && fgets(line, sizeof line, f)) {
+        size_t n = strlen(line);
+        while (n && (line[n - 1] == '\n' || line[n - 1] == '\r' || line[n - 1] == ' ' || line[n - 1] == '\t')) line[--n] = 0;
+        if (!n) continue;
+        const int32_t t = emsar_rsh_tid_of(rsh, line);
+        if (t < 0) { fprintf(stderr, "--%s-list: no transcript %s in the index.\n", what, line); fclose(f); free(q); return 1; }
+        int32_t *grown = (int32_t *)realloc(q, sizeof(int32_t) * (size_t)(nq + 1));
+        if (!grown) { free(q); q = NULL; break; }
+        q = grown;
+        q[nq++] = t;
+    }
+    fclose(f);
+    if (!q) { fprintf(stderr, "out of memory\n"); return 1; }
+    *q_out = q; *nq_out = nq;
+    return 0;
 }
 
 int main(int argc, char **argv) {
@@ -512,7 +565,8 @@ int main(int argc, char **argv) {
     cfg.sub_reps = 10; cfg.sub_seed = 1;
     const char *strand = "ns"; int multisample = 0, gpus = 0, device = 0;
     int dev_map[64], n_dev_map = 0;
-    const char *presence_list = NULL;
+    const char *presence_list = NULL, *profile_list = NULL;
+    int profile_level_given = 0;
     int boundary_cut_given = 0;
     static struct option lo[] = {
         {"rsh", required_argument, 0, 'I'}, {"PE", no_argument, 0, 'P'}, {"strand_type", required_argument, 0, 's'},
@@ -527,6 +581,8 @@ int main(int argc, char **argv) {
         {"bootstrap-quantiles", required_argument, 0, 1018}, {"isoforms", no_argument, 0, 1019}, {"fit", no_argument, 0, 1020},
         {"presence", no_argument, 0, 1021}, {"presence-list", required_argument, 0, 1022},
         {"asymptotic", no_argument, 0, 1023}, {"boundary-cut", required_argument, 0, 1024},
+        {"profile", no_argument, 0, 1025}, {"profile-level", required_argument, 0, 1026}, {"profile-list", required_argument, 0, 1027},
+        {"profile-evals", required_argument, 0, 1028},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
@@ -623,6 +679,10 @@ int main(int argc, char **argv) {
             case 1022: presence_list = optarg; break;
             case 1023: cfg.asymptotic = 1; break;
             case 1024: cfg.boundary_cut = atof(optarg); boundary_cut_given = 1; break;
+            case 1025: cfg.profile = 1; break;
+            case 1026: cfg.profile_level = atof(optarg); profile_level_given = 1; break;
+            case 1027: profile_list = optarg; break;
+            case 1028: cfg.profile_evals = atoi(optarg); if (cfg.profile_evals <= 0) { fprintf(stderr, "--profile-evals must be positive.\n"); return 1; } break;
             case 1009: {
                 const char *q = optarg;
                 while (*q && n_dev_map < 64) {
@@ -646,6 +706,11 @@ int main(int argc, char **argv) {
     if (boundary_cut_given && !(cfg.boundary_cut >= 0.0)) { fprintf(stderr, "--boundary-cut must be >= 0.\n"); return 1; }
     if (!boundary_cut_given) cfg.boundary_cut = EMSAR_ASYM_DEFAULT_CUT;
     if (presence_list && !cfg.presence) { fprintf(stderr, "--presence-list needs --presence.\n"); return 1; }
+    if ((profile_list || profile_level_given || cfg.profile_evals) && !cfg.profile) {
+        fprintf(stderr, "--profile-list, --profile-level and --profile-evals need --profile.\n"); return 1;
+    }
+    if (profile_level_given && !(cfg.profile_level > 0.0 && cfg.profile_level < 1.0)) { fprintf(stderr, "--profile-level must lie in (0, 1).\n"); return 1; }
+    if (!profile_level_given) cfg.profile_level = 0.95;
     if (!cfg.rsh_path || optind + 2 >= argc) { usage(argv[0]); return 1; }
     if (emsar_set_strand(strand, cfg.ao.pe, &cfg.ao.strand)) { fprintf(stderr, "error: invalid strand type.\n"); return 1; }
     cfg.outdir = argv[optind]; cfg.prefix = argv[optind + 1];
@@ -705,25 +770,9 @@ int main(int argc, char **argv) {
     free(cache_path);
     if (cfg.verbose > 0) fprintf(stdout, "rsh: %d transcripts, %lld segments, fragment lengths %d-%d (%.2fs)\n", rsh->n_tx,
                                  (long long)rsh->n_rows, rsh->frag_min, rsh->frag_max, now_s() - t0);
-    if (presence_list) {                       /* before any sample: an unknown name ends the run here */
-        FILE *f = fopen(presence_list, "r");
-        if (!f) { fprintf(stderr, "Can't open the presence list %s.\n", presence_list); emsar_rsh_free(rsh); return 1; }
-        char line[4096];
-        cfg.pres_q = (int32_t *)malloc(sizeof(int32_t));
-        while (cfg.pres_q && fgets(line, sizeof line, f)) {
-            size_t n = strlen(line);
-            while (n && (line[n - 1] == '\n' || line[n - 1] == '\r' || line[n - 1] == ' ' || line[n - 1] == '\t')) line[--n] = 0;
-            if (!n) continue;
-            const int32_t t = emsar_rsh_tid_of(rsh, line);
-            if (t < 0) { fprintf(stderr, "--presence-list: no transcript %s in the index.\n", line); fclose(f); emsar_rsh_free(rsh); return 1; }
-            int32_t *grown = (int32_t *)realloc(cfg.pres_q, sizeof(int32_t) * (size_t)(cfg.pres_nq + 1));
-            if (!grown) { free(cfg.pres_q); cfg.pres_q = NULL; break; }
-            cfg.pres_q = grown;
-            cfg.pres_q[cfg.pres_nq++] = t;
-        }
-        fclose(f);
-        if (!cfg.pres_q) { fprintf(stderr, "out of memory\n"); emsar_rsh_free(rsh); return 1; }
-    }
+    /* before any sample: an unknown name ends the run here */
+    if (presence_list && read_name_list("presence", presence_list, rsh, &cfg.pres_q, &cfg.pres_nq)) { emsar_rsh_free(rsh); return 1; }
+    if (profile_list && read_name_list("profile", profile_list, rsh, &cfg.prof_q, &cfg.prof_nq)) { emsar_rsh_free(rsh); return 1; }
     emsar_genes *genes = NULL;
     if (cfg.g2t) {                             /* before any sample: a bad gene map ends the run here */
         if (emsar_genes_read(rsh, cfg.g2t, &genes, err, sizeof err)) { fprintf(stderr, "%s\n", err); emsar_rsh_free(rsh); return 1; }
@@ -826,7 +875,7 @@ int main(int argc, char **argv) {
     }
     emsar_rsh_free(rsh);
     emsar_genes_free(genes);
-    free(cfg.pres_q);
+    free(cfg.pres_q); free(cfg.prof_q);
     for (int i = 0; i < n_list; i++) free(list[i]);
     free(list); free(status); free(stats); free(bstats); free(sstats); free(qstats); free(parse_s); free(model_s); free(host_s); free(wa); free(th);
     return bad ? 1 : 0;

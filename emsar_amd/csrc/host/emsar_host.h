@@ -185,6 +185,12 @@ int emsar_write_gfit(const char *path, const emsar_rsh *r, const emsar_genes *g,
 int emsar_write_presence(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, const double *fpkm, const double *lambda,
                          const double *pvalue, const int32_t *status, const int32_t *heir, const double *heir_share);
 
+/* .profile (emsar-hip --profile): one line per queried transcript, query and arrays as for .presence, the arrays as emsar_hip_profile returns
+ * them --: tid transcriptID FPKM lower upper Lambda status, "%d\t%s\t%lf\t%lf\t%lf\t%lf\t%s"; status is the word of the header's enum
+ * (TWO_SIDED, LOWER_ZERO, OUTSIDE, NOT_RESIDENT, UNCONVERGED); a value that is not finite is written as "inf" or "nan" */
+int emsar_write_profile(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, const double *fpkm, const double *lower,
+                        const double *upper, const double *lambda, const int32_t *status);
+
 /* .asym (emsar-hip --asymptotic): one line per transcript -- tid transcriptID FPKM sd_FPKM TPM sd_TPM status partner partner_corr, and
  * usage_sd when it is given (--g2t); the arrays are [n_tx] as emsar_hip_asymptotic returns them.  partner_corr = partner_cov /
  * sqrt(var_t * var_partner); "-" and nan where there is no partner.  sd values are written "%.6g", or the words inf / nan.

@@ -178,6 +178,24 @@ int emsar_write_presence(const char *path, const emsar_rsh *r, int32_t n_query, 
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
 
+int emsar_write_profile(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, const double *fpkm, const double *lower,
+                        const double *upper, const double *lambda, const int32_t *status) {
+    static const char *const word[5] = {"TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED"};
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "tid\ttranscriptID\tFPKM\tlower\tupper\tLambda\tstatus\n");
+    if (!query) n_query = r->n_tx;
+    for (int32_t i = 0; i < n_query; i++) {
+        const int32_t t = query ? query[i] : i;
+        fprintf(f, "%d\t%s\t%lf\t", t, r->names[t], fpkm[t]);
+        put_value(f, "%lf", lower[i]); fputc('\t', f);
+        put_value(f, "%lf", upper[i]); fputc('\t', f);
+        put_value(f, "%lf", lambda[i]);
+        fprintf(f, "\t%s\n", status[i] >= 0 && status[i] < 5 ? word[status[i]] : "?");
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
 static const char *const asym_word[5] = {"ESTIMATED", "BOUNDARY", "UNIDENTIFIABLE", "TOO_LARGE", "INFEASIBLE"};
 
 int emsar_write_asym(const char *path, const emsar_rsh *r, const double *fpkm, const double *tpm, const double *sd_fpkm, const double *sd_tpm,

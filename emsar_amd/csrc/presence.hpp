@@ -50,6 +50,7 @@ struct PresenceRun {
     DevBuf<PresenceRec> d_rec[emsar::kSetClasses];
     hipEvent_t e[2] = {nullptr, nullptr};
     emsar_presence_stats st{};
+    const char *batch_env = "EMSAR_HIP_PRESENCE_BATCH";      // the profile intervals run these stages under their own variable
 
     PresenceRun(emsar_hip_ctx *c, const emsar_em_params *pp, int32_t nq_, const int32_t *q, const emsar_presence_outputs *o)
         : ctx(c), p(solve_params(pp)), nq(nq_), query(q), out(o ? *o : emsar_presence_outputs{}), n(c->n_tx) {}
@@ -135,7 +136,7 @@ struct PresenceRun {
         // the bootstrap's bound on a batch: what fits a quarter of the free device memory (at most 2 GiB); EMSAR_HIP_PRESENCE_BATCH overrides
         const int64_t budget = std::min<int64_t>((int64_t)(free_device_bytes() / 4), (int64_t)2 << 30);
         int64_t batch = std::max<int64_t>(1, budget / (int64_t)(emsar::kSetClasses * (sizeof(PresenceItem) + sizeof(PresenceRec))));
-        if (const char *env = getenv("EMSAR_HIP_PRESENCE_BATCH")) { if (atoi(env) >= 1) batch = atoi(env); }
+        if (const char *env = getenv(batch_env)) { if (atoi(env) >= 1) batch = atoi(env); }
         batch = std::min<int64_t>(std::min<int64_t>(batch, (int64_t)most), (int64_t)1 << 20);
         for (int c = 0; c < emsar::kSetClasses; c++)
             if (!items[c].empty()) {

@@ -27,11 +27,15 @@ SYMBOLS = [
     "emsar_hip_isoform_usage", "emsar_hip_isoform_usage_host", "emsar_hip_bootstrap_isoforms",
     "emsar_hip_model_fit", "emsar_hip_model_fit_host",
     "emsar_hip_presence", "emsar_hip_presence_pvalue_host",
+    "emsar_hip_profile", "emsar_hip_profile_cut_host",
     "emsar_hip_asymptotic", "emsar_hip_asymptotic_host",
 ]
 
 # status of a transcript in the presence test (include/emsar_hip.h "presence test"), by value
 PRESENCE_STATUS = ("TESTED", "ABSENT", "ESSENTIAL", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED")
+
+# status of a transcript's profile-likelihood interval (include/emsar_hip.h "profile-likelihood intervals"), by value
+PROFILE_STATUS = ("TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED")
 
 # status of a transcript in the asymptotic standard errors (include/emsar_hip.h "asymptotic standard errors"), by value
 ASYM_STATUS = ("ESTIMATED", "BOUNDARY", "UNIDENTIFIABLE", "TOO_LARGE", "INFEASIBLE")
@@ -122,6 +126,26 @@ class PresenceStats(C.Structure):
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["n_status"] = dict(zip(PRESENCE_STATUS, d["n_status"]))
+        return d
+
+
+class ProfileParams(C.Structure):
+    _fields_ = [("level", C.c_double), ("dev_tol", C.c_double), ("max_evals", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class ProfileOutputs(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in ("lower", "upper", "dev_lower", "dev_upper", "lambda_", "theta_hat")] + [
+        ("status", C.POINTER(C.c_int32)), ("evals", C.POINTER(C.c_int32))]
+
+
+class ProfileStats(C.Structure):
+    _fields_ = [("n_status", C.c_int64 * 5), ("items_launched", C.c_int64), ("evals_sum", C.c_int64), ("passes_sum", C.c_int64),
+                ("evals_max", C.c_int32), ("passes_max", C.c_int32), ("cut", C.c_double), ("baseline_ms", C.c_double), ("drop_ms", C.c_double),
+                ("search_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["n_status"] = dict(zip(PROFILE_STATUS, d["n_status"]))
         return d
 
 
@@ -224,6 +248,9 @@ def load_library():
                                            C.POINTER(FitStats)]
     L.emsar_hip_presence.argtypes = [vp, C.POINTER(EmParams), C.c_int32, i32p, C.POINTER(PresenceOutputs), C.POINTER(PresenceStats)]
     L.emsar_hip_presence_pvalue_host.argtypes = [C.c_int64, f64p, f64p]
+    L.emsar_hip_profile.argtypes = [vp, C.POINTER(EmParams), C.POINTER(ProfileParams), C.c_int32, i32p, C.POINTER(ProfileOutputs),
+                                    C.POINTER(ProfileStats)]
+    L.emsar_hip_profile_cut_host.argtypes = [C.c_double, f64p]
     L.emsar_hip_asymptotic.argtypes = [vp, f64p, C.POINTER(AsymParams), C.POINTER(AsymOutputs), C.POINTER(AsymStats)]
     L.emsar_hip_asymptotic_host.argtypes = [C.c_int64, C.c_int32, u64p, i32p, i32p, f64p, f64p, C.c_int32, i32p, C.POINTER(AsymParams),
                                             C.POINTER(AsymOutputs), C.POINTER(AsymStats)]
@@ -427,6 +454,16 @@ def presence_pvalue_host(lam):
         raise EmsarHipError(rc, "presence_pvalue_host")
     out = out[:x.size].reshape(x.shape)
     return float(out[0]) if np.ndim(lam) == 0 else out
+
+
+def profile_cut_host(level):
+    """Host-only: the cut q of a profile-likelihood interval (include/emsar_hip.h "profile-likelihood intervals"): the `level` quantile
+    of chi2 with one degree of freedom, erf(sqrt(q / 2)) = level; 0 < level < 1.  No GPU needed."""
+    out = C.c_double(0.0)
+    rc = load_library().emsar_hip_profile_cut_host(float(level), C.byref(out))
+    if rc != 0:
+        raise EmsarHipError(rc, "profile_cut_host")
+    return out.value
 
 
 def layout_selfcheck_tiled(n_tx, row_ptr, col_idx, merge_rows=False):
@@ -674,6 +711,28 @@ class EmsarHip:
                             _p(res["status"], C.c_int32), _p(res["theta_hat"], C.c_double))
         st = PresenceStats()
         self._chk(self._L.emsar_hip_presence(self._h, C.byref(p), nq, _p(q, C.c_int32), C.byref(o), C.byref(st)), "presence")
+        out = {k: v[:nq] for k, v in res.items()}
+        out["stats"] = st
+        return out
+
+    def profile(self, query=None, level=0.95, dev_tol=0.0, max_evals=0, max_iter=100000, accel=1, tol=1e-10, abs_floor=1e-6, check_every=8,
+                count_floor=0.0, set_mode=0, zero_cut=0.0, abs_step=0.0, newton_after=0):
+        """Profile-likelihood interval of each queried transcript (include/emsar_hip.h "profile-likelihood intervals"): the values of
+        theta_t whose best achievable likelihood lies within the chi2_1 cut of `level` of the maximum; one-sided by itself where the
+        transcript cannot be told from absent.  query: tids in any order, repeats allowed, None = all transcripts; dev_tol, max_evals 0 =
+        the defaults (1e-4, 40); the solver parameters are those of solve().  Returns a dict of arrays in query order: lower, upper,
+        dev_lower, dev_upper, lambda, theta_hat, status (index into PROFILE_STATUS), evals, and stats.  After upload_sample; the context
+        is left as it was."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        pp = ProfileParams(float(level), float(dev_tol), int(max_evals), 0)
+        q = None if query is None else np.ascontiguousarray(np.asarray(query, dtype=np.int32).reshape(-1))
+        nq = self.n_tx if q is None else len(q)
+        res = {k: np.zeros(max(nq, 1)) for k in ("lower", "upper", "dev_lower", "dev_upper", "lambda", "theta_hat")}
+        res.update({k: np.zeros(max(nq, 1), dtype=np.int32) for k in ("status", "evals")})
+        o = ProfileOutputs(*[_p(res[k], C.c_double) for k in ("lower", "upper", "dev_lower", "dev_upper", "lambda", "theta_hat")],
+                           _p(res["status"], C.c_int32), _p(res["evals"], C.c_int32))
+        st = ProfileStats()
+        self._chk(self._L.emsar_hip_profile(self._h, C.byref(p), C.byref(pp), nq, _p(q, C.c_int32), C.byref(o), C.byref(st)), "profile")
         out = {k: v[:nq] for k, v in res.items()}
         out["stats"] = st
         return out

@@ -92,6 +92,7 @@ def lib():
         L.emsar_write_isoforms.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Genes), f64p, f64p, i32p, C.c_int, f64p, f64p, i32p,
                                            C.c_int, f64p, f64p]
         L.emsar_write_presence.argtypes = [C.c_char_p, C.POINTER(Rsh), C.c_int32, i32p, f64p, f64p, f64p, i32p, i32p, f64p]
+        L.emsar_write_profile.argtypes = [C.c_char_p, C.POINTER(Rsh), C.c_int32, i32p, f64p, f64p, f64p, f64p, i32p]
         L.emsar_write_asym.argtypes = [C.c_char_p, C.POINTER(Rsh)] + [f64p] * 5 + [i32p, i32p, f64p, f64p]
         L.emsar_write_gasym.argtypes = [C.c_char_p, C.POINTER(Genes), f64p, f64p, i32p]
         _lib = L
@@ -145,6 +146,22 @@ def write_presence(path, tx_names, fpkm, lam, pvalue, status, heir, heir_share, 
                                     _dp(a[3]))
     if rc != 0:
         raise HostError("write_presence rc=%d" % rc)
+
+
+def write_profile(path, tx_names, fpkm, lower, upper, lam, status, query=None):
+    """.profile (emsar_write_profile): transcripts tx_names with fpkm [n_tx]; lower, upper, lam, status as EmsarHip.profile returns them for
+    query (tids, None = all transcripts in order)."""
+    n_tx = len(tx_names)
+    names = (C.c_char_p * max(n_tx, 1))(*[s.encode() for s in tx_names])
+    r = Rsh(n_tx=n_tx, names=C.cast(names, C.POINTER(C.c_char_p)))
+    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    q, st = i32(query), i32(status)
+    a = [f64(fpkm), f64(lower), f64(upper), f64(lam)]
+    rc = lib().emsar_write_profile(path.encode(), C.byref(r), n_tx if q is None else len(q), ip(q), _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3]), ip(st))
+    if rc != 0:
+        raise HostError("write_profile rc=%d" % rc)
 
 
 def write_asym(path, tx_names, fpkm, tpm, sd_fpkm, sd_tpm, var, status, partner, partner_cov, usage_sd=None):

@@ -477,6 +477,64 @@ int emsar_hip_presence(emsar_hip_ctx *ctx, const emsar_em_params *p, int32_t n_q
                        const emsar_presence_outputs *out /* or NULL */, emsar_presence_stats *stats /* or NULL */);
 int emsar_hip_presence_pvalue_host(int64_t n, const double *lambda, double *p_out);
 
+/* ---- profile-likelihood intervals: limits that hold at the boundary --------------------------------
+ * How much of transcript t could be present without the reads contradicting it -- also where theta_hat_t is 0 or close to it, where the
+ * asymptotic standard errors do not hold and the bootstrap's percentile interval is [0, 0].  For the sample of upload_structure +
+ * upload_sample and solver parameters p, with s the packed connected set of t (set_mode 0) and F_s as the presence test defines it:
+ *     D_t(x)       = 2 * (F_s(theta_hat) - max{ F_s(theta) : theta_t = x }) for x >= 0, the deviance of the value x.  D_t(theta_hat_t) = 0;
+ *                  F is concave, so D_t does not rise towards theta_hat_t from either side; D_t(0) is the presence test's Lambda_t
+ *     cut          q with erf(sqrt(q / 2)) = level, the `level` quantile of chi2 with 1 degree of freedom (profile_cut_host: bisection on
+ *                  std::erf until the bracket cannot be halved, no HIP call; 0.95 -> 3.841458820694124; ERR_ARG unless 0 < level < 1)
+ *     lower, upper = inf / sup {x >= 0 : D_t(x) <= q}.  upper always exists (F -> -inf as theta_t -> inf)
+ *     path         the maximiser of F(theta) - lambda * theta_t is the same set problem with den_t replaced by m * den_t
+ *                  (lambda = (m - 1) den_t), and it is the constrained maximum of F at x = theta_t(m): m = 1 is the MLE, m -> inf the
+ *                  presence test's drop solve, 0 < m < 1 the upper side.  Every point of the path is one solve of the set with
+ *                  m * den_t in LDS -- same solver, same start, same stopping rule as solve; its F is summed with the ORIGINAL den_t
+ *     search       a limit is a root search over log m on sqrt(D) - sqrt(q): from m0 = 1 + sqrt(q / n_t) (lower) or its reciprocal
+ *                  (upper), n_t = theta_hat_t den_t, doubling log m until D >= q, then Illinois steps with a bisection safeguard;
+ *                  on the upper side with n_t < q (theta_hat_t = 0 included) from m = 1/2, quartering.  It stops when |D - q| <= dev_tol * q (dev_tol <= 0: 1e-4) or after
+ *                  max_evals solves (<= 0: 40; then UNCONVERGED).  The reported limit is the x = theta_t(m) of the search's last
+ *                  solve and dev_lower / dev_upper that solve's deviance: each pair lies on the profile curve.  One workgroup
+ *                  runs one search, at most max_evals * max_iter passes
+ *     lambda       the presence test's value for t, computed by the same drop solve: its bits; +inf for an essential, 0 for an absent t
+ *     closed form  a one-transcript component has F(x) = u log x - x den: the same search on the host; u = 0 gives lower = 0,
+ *                  upper = q / (2 den) with no search
+ * status, per transcript:
+ *     TWO_SIDED     both limits were found by search, lower > 0
+ *     LOWER_ZERO    Lambda_t <= q (theta_hat_t == 0 included): lower = 0.0 exactly and dev_lower = Lambda_t -- at this level t cannot be
+ *                   told from absent; upper is found by search
+ *     OUTSIDE, NOT_RESIDENT   as in the presence test; every output NaN (evals 0)
+ *     UNCONVERGED   values are given, but the baseline, the drop solve, a solve of a search or a search itself hit its cap
+ * Outputs are indexed by query position (by tid when query_tids is NULL; n_query is then ignored); repeats and any order are allowed.  A
+ * transcript's result depends on its set, itself, p and the profile parameters alone -- not on what else is asked, the batch, the
+ * layout or the library's numbering.  The context's theta, weights and scales are not touched: a following solve or presence returns
+ * the same bits.  ERR_STATE before upload_sample; ERR_ARG for a tid outside 0 .. n_tx-1, n_query < 0, a level outside (0, 1), a
+ * non-finite dev_tol and the parameters solve rejects; ERR_NUMERIC for a non-finite baseline F.  EMSAR_HIP_PROFILE_BATCH = items per
+ * launch and class (a testing aid; the bits do not change). */
+enum {
+    EMSAR_PROFILE_TWO_SIDED = 0, EMSAR_PROFILE_LOWER_ZERO = 1, EMSAR_PROFILE_OUTSIDE = 2, EMSAR_PROFILE_NOT_RESIDENT = 3,
+    EMSAR_PROFILE_UNCONVERGED = 4
+};
+typedef struct { double level, dev_tol; int32_t max_evals, reserved0; } emsar_profile_params;      /* NULL: 0.95 and the defaults */
+typedef struct {
+    double  *lower, *upper, *dev_lower, *dev_upper, *lambda, *theta_hat;    /* [n_query]; may each be NULL */
+    int32_t *status, *evals;                                                /* [n_query] EMSAR_PROFILE_*; solves spent on the two searches */
+} emsar_profile_outputs;
+typedef struct {
+    int64_t n_status[5];          /* distinct queried transcripts per status */
+    int64_t items_launched;       /* workgroups: baselines, drops and searches */
+    int64_t evals_sum;            /* solves summed over the searches on the device */
+    int64_t passes_sum;           /* passes summed over those solves */
+    int32_t evals_max, passes_max; /* the search with the most solves / the most passes */
+    double  cut;                  /* q */
+    double  baseline_ms, drop_ms, search_ms; /* device time of the three phases (HIP events) */
+    double  total_ms;             /* wall time of the call, a first call's set building included */
+} emsar_profile_stats;
+int emsar_hip_profile(emsar_hip_ctx *ctx, const emsar_em_params *p, const emsar_profile_params *pp /* or NULL */, int32_t n_query,
+                      const int32_t *query_tids /* NULL = all transcripts */, const emsar_profile_outputs *out /* or NULL */,
+                      emsar_profile_stats *stats /* or NULL */);
+int emsar_hip_profile_cut_host(double level, double *cut_out);
+
 /* ---- asymptotic standard errors: the inverse of the observed information at the MLE ---------------
  * How sure is theta_t, without resampling?  For a theta that maximises the likelihood of the current sample, the observed information
  * of the ACTIVE transcripts is J_ij = sum_c m_ci m_cj R_c / S_c^2 (m_ci = how often i stands in row c); its inverse is the asymptotic
