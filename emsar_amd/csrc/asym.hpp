@@ -111,7 +111,7 @@ struct AsymRun {
         }
         lds[1] = (size_t)8 * (36 + 16) * 8;
         const auto &m = tid_map(ctx);
-        const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !m.empty();
+        const bool remap = renumbered(ctx);
         h_lib.resize(P.slots()); h_gene.resize(P.slots());
         for (size_t s = 0; s < P.slots(); s++) {
             const int32_t t = P.g_tid[s];

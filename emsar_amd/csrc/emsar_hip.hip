@@ -15,10 +15,12 @@
 //   pass_launch.hpp   choose_pass_kernel, one launcher per kernel family, launch_pass; the stamped diagnostic launches
 //   solve.hpp         the set solver's driver (ensure_sets, solve_resident_sets), em_pass / enqueue_cycles, SolveRun: one solve in stages;
 //                     emsar_hip_solve, emsar_hip_run_passes
-//   resample.hpp      the resampling driver and its C ABI -- bootstrap, quantiles, subsampling, genes
+//   set_items.hpp     the batch rule (item_batch) and SetItemRunner: batches of items, one workgroup each, through a set-kernel family
+//   resample.hpp     the resampling driver and its C ABI -- bootstrap, quantiles, subsampling, genes
 //   fit.hpp           the model fit and its C ABI
 //   presence.hpp      the presence test (a likelihood-ratio test per transcript on its resident set) and its C ABI
 //   profile.hpp       the profile-likelihood intervals (two confidence limits per transcript, each a root search over set solves) and their C ABI
+//   asym.hpp          the asymptotic standard errors (the observed information of every component, factorised on the device) and their C ABI
 // Kernels (one translation unit, included below):
 //   kernels_tiled.hpp     k_pass_tiled_unit                      the hot one (the default above 2048 tiles): one workgroup per UNIT of up to
 //                         two tiles of the TILED layout that share a dictionary of theta/acc in LDS (60 blocks x 16 subset sums),
@@ -224,16 +226,24 @@ inline void set_fx_scales(emsar_hip_ctx *ctx, int64_t total) {
 // The TILED layout may number the transcripts itself (renumber.hpp); every T-sized device vector is then in the LIBRARY's numbering and
 // the ABI maps: lib[new_of_old[t]] = caller[t].  Empty map = the caller's numbering.
 inline const std::vector<int32_t> &tid_map(const emsar_hip_ctx *ctx) { return ctx->lay.TL.new_of_old; }
+inline bool renumbered(const emsar_hip_ctx *ctx) { return ctx->layout == EMSAR_LAYOUT_TILED && !tid_map(ctx).empty(); }
+// the inverse of tid_map: library index -> caller tid; empty = the caller's numbering
+inline std::vector<int32_t> caller_of_lib(const emsar_hip_ctx *ctx) {
+    const auto &m = tid_map(ctx);
+    std::vector<int32_t> inv(renumbered(ctx) ? m.size() : 0);
+    for (size_t t = 0; t < inv.size(); t++) inv[(size_t)m[t]] = (int32_t)t;
+    return inv;
+}
 inline const double *to_lib(const emsar_hip_ctx *ctx, const double *caller, std::vector<double> &tmp) {
     const auto &m = tid_map(ctx);
-    if (m.empty() || ctx->layout != EMSAR_LAYOUT_TILED) return caller;
+    if (!renumbered(ctx)) return caller;
     tmp.resize(m.size());
     for (size_t t = 0; t < m.size(); t++) tmp[(size_t)m[t]] = caller[t];
     return tmp.data();
 }
 template <class V> inline void from_lib(const emsar_hip_ctx *ctx, V *v /* in place: library order -> caller order */) {
     const auto &m = tid_map(ctx);
-    if (m.empty() || ctx->layout != EMSAR_LAYOUT_TILED) return;
+    if (!renumbered(ctx)) return;
     std::vector<V> tmp(v, v + m.size());
     for (size_t t = 0; t < m.size(); t++) v[t] = tmp[(size_t)m[t]];
 }
@@ -816,8 +826,9 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 }  // extern "C"
 
 #include "solve.hpp"      // the set solver's driver and the solve driver: emsar_hip_solve, emsar_hip_run_passes
+#include "set_items.hpp"  // the batch rule and the item runner of the set kernels (after solve.hpp: launch_set_classes, set_params)
 #include "resample.hpp"   // the resampling driver and its entry points: bootstrap, genes, quantiles, subsampling
 #include "fit.hpp"        // the model fit and its entry points (after resample.hpp: the gene step is launch_gene_sums)
-#include "presence.hpp"   // the presence test and its entry points (after resample.hpp: free_device_bytes)
+#include "presence.hpp"   // the presence test and its entry points (after set_items.hpp: SetItemRunner, query_ok)
 #include "profile.hpp"    // the profile-likelihood intervals and their entry points (after presence.hpp: PresenceRun)
 #include "asym.hpp"       // the asymptotic standard errors and their entry points (after fit.hpp: fit_ensure_csr, launch_gene_sums)

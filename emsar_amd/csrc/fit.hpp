@@ -59,7 +59,7 @@ struct FitRun {
         if (brc != 0) { ctx->err = "model_fit: index builder: code " + std::to_string(brc); return EMSAR_HIP_ERR_HIP; }
         // results go to the library's index of a transcript: the [4][n_tx] block is what k_gene_sums reads
         const auto &m = tid_map(ctx);
-        if (ctx->layout == EMSAR_LAYOUT_TILED && !m.empty()) {
+        if (renumbered(ctx)) {
             for (auto &o : X.chunk_out) if (o >= 0) o = m[(size_t)o];
             for (size_t i = 0; i < X.multi.size(); i += 3) X.multi[i] = m[(size_t)X.multi[i]];
         }
@@ -143,7 +143,7 @@ struct FitRun {
         HIPCHK(hipStreamSynchronize(s));
         // library order -> caller order
         const auto &m = tid_map(ctx);
-        const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !m.empty();
+        const bool remap = renumbered(ctx);
         double *const txo[4] = {out.tx_chi2, out.tx_dev, out.tx_miss, out.tx_df};
         for (int64_t t = 0; t < n; t++) {
             const size_t l = remap ? (size_t)m[(size_t)t] : (size_t)t;

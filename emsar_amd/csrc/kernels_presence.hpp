@@ -12,7 +12,7 @@ struct PresenceRec { double F, gain; int32_t infeasible, passes, converged, heir
 static_assert(sizeof(PresenceRec) == 32, "PresenceRec is read by the host as 32 bytes");
 
 // Workgroup x solves item x with solve_one_set, then evaluates the result where it lies, in LDS:
-//   F = sum_c R_c log S_c + sum_t u_t log x_t - sum_t x_t den_t and the infeasible count, as set_newton_step sums them (one E-step
+//   F = sum_c R_c log S_c + sum_t u_t log x_t - sum_t x_t den_t and the infeasible count, by set_objective_terms (one E-step
 //   with log; L.red carries the reduction, nothing else of LDS is written);
 //   for a drop item the arg-max over s != drop of (x_s - theta[s]) den_s, ties to the lowest local index, theta = the baseline
 //   written by an EARLIER launch of baseline items into the same vector (a drop item writes nothing to it).
@@ -34,20 +34,13 @@ __global__ __launch_bounds__(THREADS) void k_solve_sets_drop(const emsar::SetDes
     const double *x = K.res;
     set_sync<THREADS>();
     double s3[3] = {0.0, 0.0, 0.0};        // sum R log S + u log x, sum x den, infeasible
-    for (int j = threadIdx.x; j < L.nr; j += THREADS) {
-        const double S = set_row_dot<THREADS>(L, x, j), rw = L.rw[j];
-        if (S > 0.0) s3[0] += rw * log(S); else if (rw > 0.0) s3[2] += 1.0;
-    }
     double best = 0.0, at = 0.0;           // this thread's largest gain and 65536 - its local index (0: none)
-    for (int i = threadIdx.x; i < L.nt; i += THREADS) {
-        const double xi = x[i], ui = L.u[i], dn = L.den[i];
-        if (ui > 0.0) { if (xi > 0.0) s3[0] += ui * log(xi); else s3[2] += 1.0; }
-        s3[1] += xi * dn;
+    set_objective_terms<THREADS>(L, x, s3, [&](int i) { return L.den[i]; }, [&](int i, double xi, double dn) {
         if (drop >= 0 && i != drop) {
             const double gain = (xi - theta[g_tid[d.tid_off + i]]) * dn;
             if (gain > best) { best = gain; at = (double)(65536 - i); }      // i ascends: the first of equal gains stays
         }
-    }
+    });
     set_reduce_sum<THREADS, 3>(s3, L.red);
     const double top = set_reduce_max<THREADS>(best, L.red);
     const double who = set_reduce_max<THREADS>((top > 0.0 && best == top) ? at : 0.0, L.red);      // the lowest index among the holders of the maximum
@@ -59,5 +52,6 @@ __global__ __launch_bounds__(THREADS) void k_solve_sets_drop(const emsar::SetDes
         rec[blockIdx.x] = r;
     }
 }
+const auto kSolveSetsDrop = set_kernels(k_solve_sets_drop<64>, k_solve_sets_drop<256>, k_solve_sets_drop<512>);
 
 }  // namespace

@@ -96,15 +96,7 @@ __global__ __launch_bounds__(THREADS) void k_profile_sets(const emsar::SetDesc *
         const double *x = K.res;
         set_sync<THREADS>();
         double s3[3] = {0.0, 0.0, 0.0};        // sum R log S + u log x, sum x den (t at its original den), infeasible
-        for (int j = threadIdx.x; j < L.nr; j += THREADS) {
-            const double Sj = set_row_dot<THREADS>(L, x, j), rw = L.rw[j];
-            if (Sj > 0.0) s3[0] += rw * log(Sj); else if (rw > 0.0) s3[2] += 1.0;
-        }
-        for (int i = threadIdx.x; i < L.nt; i += THREADS) {
-            const double xi = x[i], ui = L.u[i], dn = i == t ? den_t : L.den[i];
-            if (ui > 0.0) { if (xi > 0.0) s3[0] += ui * log(xi); else s3[2] += 1.0; }
-            s3[1] += xi * dn;
-        }
+        set_objective_terms<THREADS>(L, x, s3, [&](int i) { return i == t ? den_t : L.den[i]; }, [](int, double, double) {});
         const double xt_now = x[t];
         set_reduce_sum<THREADS, 3>(s3, L.red);
         set_sync<THREADS>();                   // the next solve_one_set overwrites the LDS this epilogue read
@@ -129,5 +121,6 @@ __global__ __launch_bounds__(THREADS) void k_profile_sets(const emsar::SetDesc *
         rec[blockIdx.x] = r;
     }
 }
+const auto kProfileSets = set_kernels(k_profile_sets<64>, k_profile_sets<256>, k_profile_sets<512>);
 
 }  // namespace

@@ -176,6 +176,22 @@ __device__ __forceinline__ double set_row_dot(const SetLds &L, const double *v, 
     }
     return S;
 }
+// This thread's share of F at a point v in LDS, added into s: s[0] += sum R log S + sum u log v, s[1] += sum v den, s[2] += the rows and
+// folded counts with reads that nothing explains.  den_of(i) is transcript i's den; each(i, v_i, den_i) rides on the transcript loop.
+// The reduction and every barrier stay with the caller.
+template <int THREADS, class DenOf, class Each>
+__device__ __forceinline__ void set_objective_terms(const SetLds &L, const double *v, double (&s)[3], const DenOf &den_of, const Each &each) {
+    for (int j = threadIdx.x; j < L.nr; j += THREADS) {
+        const double S = set_row_dot<THREADS>(L, v, j), rw = L.rw[j];
+        if (S > 0.0) s[0] += rw * log(S); else if (rw > 0.0) s[2] += 1.0;
+    }
+    for (int i = threadIdx.x; i < L.nt; i += THREADS) {
+        const double vi = v[i], ui = L.u[i], dn = den_of(i);
+        if (ui > 0.0) { if (vi > 0.0) s[0] += ui * log(vi); else s[2] += 1.0; }
+        s[1] += vi * dn;
+        each(i, vi, dn);
+    }
+}
 __device__ __forceinline__ double set_col_sum(const SetLds &L, const double *rowv, int i) {
     double a = 0.0;
     const int b = L.cp[i], e = L.cp[i + 1];
@@ -267,7 +283,7 @@ __device__ __forceinline__ bool set_newton_step(const SetLds &L, double *x, doub
             L.hp[i] = xn;
         }
         set_sync<THREADS>();
-        double s4[3] = {0.0, 0.0, 0.0};    // sum R log S + u log x, sum x den, infeasible
+        double s4[3] = {0.0, 0.0, 0.0};    // sum R log S + u log x, sum x den, infeasible: set_objective_terms written out (through it k_solve_sets compiles to other code)
         for (int j = threadIdx.x; j < nr; j += THREADS) {
             const double S = set_row_dot<THREADS>(L, L.hp, j), rw = L.rw[j];
             if (S > 0.0) s4[0] += rw * log(S); else if (rw > 0.0) s4[2] += 1.0;
@@ -450,5 +466,11 @@ __global__ __launch_bounds__(THREADS) void k_solve_sets_boot(const emsar::SetDes
     solve_one_set<THREADS>(desc[blockIdx.x], g_tid, g_u + y * gu_stride, row_w + y * rw_stride, rp_g, ent_g, cp_g, crow_g, den_g,
                            theta_g + y * th_stride, stat + y * stat_stride + blockIdx.x, P);
 }
+
+// A family of set kernels for the host: its <64>, <256> and <512> instantiations, family[c] = the kernel of size class c
+template <class Kernel> struct SetKernels { Kernel *k[emsar::kSetClasses]; Kernel *operator[](int c) const { return k[c]; } };
+template <class Kernel> SetKernels<Kernel> set_kernels(Kernel *k64, Kernel *k256, Kernel *k512) { return {{k64, k256, k512}}; }
+const auto kSolveSets = set_kernels(k_solve_sets<64>, k_solve_sets<256>, k_solve_sets<512>);
+const auto kSolveSetsBoot = set_kernels(k_solve_sets_boot<64>, k_solve_sets_boot<256>, k_solve_sets_boot<512>);
 
 }  // namespace

@@ -1,6 +1,6 @@
 // presence.hpp -- the presence test behind include/emsar_hip.h: emsar_hip_presence (device) and emsar_hip_presence_pvalue_host (no HIP
-// call).  Part of emsar_hip.hip's translation unit, included at its end after fit.hpp: it uses the context, plan_solve, set_params and
-// the set driver's launches (solve.hpp) and k_solve_sets_drop (kernels_presence.hpp).
+// call).  Part of emsar_hip.hip's translation unit, included at its end after fit.hpp: it uses the context, plan_solve and set_params
+// (solve.hpp), the item runner (set_items.hpp) and k_solve_sets_drop (kernels_presence.hpp).
 // One call = one PresenceRun:  plan        which solvers a solve would run; the sets are found on first use (ensure_sets)
 //                              classify    every queried transcript: outside / not resident / closed form / candidate of a resident set
 //                              baseline    one item (set, -1) per set that holds a candidate -> theta_hat in a vector of the run, F per set
@@ -46,27 +46,22 @@ struct PresenceRun {
     std::vector<int32_t> base_of_set[emsar::kSetClasses];  // set of a class -> its baseline item, -1 = none
     std::vector<PresenceRec> base_rec[emsar::kSetClasses];
     DevBuf<double> d_theta;              // [n] theta_hat: closed form and the baselined sets, the rest 0
-    DevBuf<PresenceItem> d_items[emsar::kSetClasses];
-    DevBuf<PresenceRec> d_rec[emsar::kSetClasses];
-    hipEvent_t e[2] = {nullptr, nullptr};
+    SetItemRunner<PresenceItem, PresenceRec> runner;
     emsar_presence_stats st{};
-    const char *batch_env = "EMSAR_HIP_PRESENCE_BATCH";      // the profile intervals run these stages under their own variable
 
-    PresenceRun(emsar_hip_ctx *c, const emsar_em_params *pp, int32_t nq_, const int32_t *q, const emsar_presence_outputs *o)
-        : ctx(c), p(solve_params(pp)), nq(nq_), query(q), out(o ? *o : emsar_presence_outputs{}), n(c->n_tx) {}
-    ~PresenceRun() { for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev); }
+    // batch_env: the profile intervals run these stages under their own variable
+    PresenceRun(emsar_hip_ctx *c, const emsar_em_params *pp, int32_t nq_, const int32_t *q, const emsar_presence_outputs *o,
+                const char *batch_env = "EMSAR_HIP_PRESENCE_BATCH")
+        : ctx(c), p(solve_params(pp)), nq(nq_), query(q), out(o ? *o : emsar_presence_outputs{}), n(c->n_tx),
+          runner(c, batch_env, "presence: an item lies outside its class's sets") {}
 
-    int32_t lib_of(int32_t tid) const {
-        const auto &m = tid_map(ctx);
-        return (ctx->layout == EMSAR_LAYOUT_TILED && !m.empty()) ? m[(size_t)tid] : tid;
-    }
+    int32_t lib_of(int32_t tid) const { return renumbered(ctx) ? tid_map(ctx)[(size_t)tid] : tid; }
 
     int plan() {
         if (!(p.count_floor >= 0.0) || (p.set_mode != 0 && p.set_mode != 1)) return EMSAR_HIP_ERR_ARG;
         SolvePlan sp;
         if (const int rc = plan_solve(ctx, p.set_mode, sp)) return rc;
         use_sets = sp.use_sets;
-        for (auto &ev : e) HIPCHK(hipEventCreate(&ev));
         cand_of_lib.assign((size_t)n, -1);
         for (int32_t i = 0; i < nq; i++) {
             const int32_t l = lib_of(query ? query[i] : i);
@@ -117,60 +112,17 @@ struct PresenceRun {
         return EMSAR_HIP_OK;
     }
 
-    // Items of the three classes through k_solve_sets_drop, at most `batch` per class and launch, the classes next to each other on
-    // their streams; recs[c][i] answers items[c][i].  Every index is checked against the class's descriptors before anything is launched.
-    int launch_items(const std::vector<PresenceItem> (&items)[emsar::kSetClasses], std::vector<PresenceRec> (&recs)[emsar::kSetClasses], double &ms_acc) {
+    // items through k_solve_sets_drop (SetItemRunner); the baseline's and the drop stage's items differ in `drop` alone
+    int solve_items(const std::vector<PresenceItem> (&items)[emsar::kSetClasses], std::vector<PresenceRec> (&recs)[emsar::kSetClasses], double &ms_acc) {
         const SetsDev &D = ctx->sets;
-        const auto &S = D.RS;
-        size_t most = 0;
-        for (int c = 0; c < emsar::kSetClasses; c++) {
-            for (const PresenceItem &it : items[c])
-                if (it.set < 0 || (size_t)it.set >= S.desc[c].size() || it.drop < -1 || it.drop >= (int32_t)S.desc[c][(size_t)it.set].n_t) {
-                    ctx->err = "presence: an item lies outside its class's sets";
-                    return EMSAR_HIP_ERR_HIP;
-                }
-            recs[c].resize(items[c].size());
-            most = std::max(most, items[c].size());
-        }
-        if (most == 0) return EMSAR_HIP_OK;
-        // the bootstrap's bound on a batch: what fits a quarter of the free device memory (at most 2 GiB); EMSAR_HIP_PRESENCE_BATCH overrides
-        const int64_t budget = std::min<int64_t>((int64_t)(free_device_bytes() / 4), (int64_t)2 << 30);
-        int64_t batch = std::max<int64_t>(1, budget / (int64_t)(emsar::kSetClasses * (sizeof(PresenceItem) + sizeof(PresenceRec))));
-        if (const char *env = getenv(batch_env)) { if (atoi(env) >= 1) batch = atoi(env); }
-        batch = std::min<int64_t>(std::min<int64_t>(batch, (int64_t)most), (int64_t)1 << 20);
-        for (int c = 0; c < emsar::kSetClasses; c++)
-            if (!items[c].empty()) {
-                const size_t cnt = std::min<size_t>((size_t)batch, items[c].size());
-                HIPCHK(d_items[c].alloc(cnt)); HIPCHK(d_rec[c].alloc(cnt));
-            }
-        HIPCHK(set_class_lds_attributes((const void *)k_solve_sets_drop<64>, (const void *)k_solve_sets_drop<256>, (const void *)k_solve_sets_drop<512>));
         const SetSolveParams P = set_params(p);
-        for (size_t first = 0; first < most; first += (size_t)batch) {
-            int rc;
-            size_t cnt[emsar::kSetClasses];
-            for (int c = 0; c < emsar::kSetClasses; c++) {
-                cnt[c] = items[c].size() > first ? std::min<size_t>((size_t)batch, items[c].size() - first) : 0;
-                if (cnt[c]) HIPCHK(hipMemcpyAsync(d_items[c], items[c].data() + first, cnt[c] * sizeof(PresenceItem), hipMemcpyHostToDevice, ctx->stream));
-            }
-            HIPCHK(hipEventRecord(e[0], ctx->stream));
-            if ((rc = fork_side_streams(ctx, 2))) return rc;
-            rc = launch_set_classes(ctx, 2, [&](int c, int threads, hipStream_t s) {
-                if (cnt[c] == 0) return;
-                hipLaunchKernelGGL((c == 2 ? k_solve_sets_drop<512> : c == 1 ? k_solve_sets_drop<256> : k_solve_sets_drop<64>), dim3((unsigned)cnt[c]), dim3(threads),
-                                   S.max_lds[c], s, D.d_sdesc[c].get(), d_items[c].get(), D.d_g_tid.get(), D.d_g_u.get(), D.d_row_w.get(), D.d_srp.get(), D.d_sent.get(),
-                                   D.d_scp.get(), D.d_scrow.get(), ctx->vec.d_den.get(), d_theta.get(), d_rec[c].get(), P);
+        HIPCHK(set_class_lds_attributes(kSolveSetsDrop));
+        return runner.run(items, recs, ms_acc, st.items_launched,
+            [](const PresenceItem &it, const emsar::SetDesc &d) { return it.drop >= -1 && it.drop < (int32_t)d.n_t; },
+            [&](int c, int threads, hipStream_t s, size_t cnt, const PresenceItem *d_items, PresenceRec *d_rec) {
+                hipLaunchKernelGGL(kSolveSetsDrop[c], dim3((unsigned)cnt), dim3(threads), D.RS.max_lds[c], s, D.d_sdesc[c].get(), d_items, D.d_g_tid.get(),
+                                   D.d_g_u.get(), D.d_row_w.get(), D.d_srp.get(), D.d_sent.get(), D.d_scp.get(), D.d_scrow.get(), ctx->vec.d_den.get(), d_theta.get(), d_rec, P);
             });
-            if (rc) return rc;
-            HIPCHK(hipEventRecord(e[1], ctx->stream));
-            for (int c = 0; c < emsar::kSetClasses; c++)
-                if (cnt[c]) HIPCHK(hipMemcpyAsync(recs[c].data() + first, d_rec[c], cnt[c] * sizeof(PresenceRec), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, e[0], e[1]));
-            ms_acc += ms;
-            for (int c = 0; c < emsar::kSetClasses; c++) st.items_launched += (int64_t)cnt[c];
-        }
-        return EMSAR_HIP_OK;
     }
 
     // theta_hat: the closed form, and every set that holds a queried transcript solved with nothing dropped
@@ -187,7 +139,7 @@ struct PresenceRun {
                 base_of_set[c.cls][(size_t)c.set] = (int32_t)items[c.cls].size();
                 items[c.cls].push_back(PresenceItem{c.set, -1});
             }
-        if (const int rc = launch_items(items, base_rec, st.baseline_ms)) return rc;
+        if (const int rc = solve_items(items, base_rec, st.baseline_ms)) return rc;
         h_theta.resize((size_t)n);
         if (n > 0) HIPCHK(hipMemcpyAsync(h_theta.data(), d_theta, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -217,7 +169,7 @@ struct PresenceRun {
                 items[cand[k].cls].push_back(PresenceItem{cand[k].set, cand[k].loc});
                 who[cand[k].cls].push_back((int32_t)k);
             }
-        if (const int rc = launch_items(items, recs, st.drop_ms)) return rc;
+        if (const int rc = solve_items(items, recs, st.drop_ms)) return rc;
         for (int cls = 0; cls < emsar::kSetClasses; cls++)
             for (size_t i = 0; i < recs[cls].size(); i++) {
                 Cand &c = cand[(size_t)who[cls][i]];
@@ -240,10 +192,7 @@ struct PresenceRun {
     }
 
     int copy_out() {
-        const auto &m = tid_map(ctx);
-        const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !m.empty();
-        std::vector<int32_t> caller_of;
-        if (remap) { caller_of.resize(m.size()); for (size_t t = 0; t < m.size(); t++) caller_of[(size_t)m[t]] = (int32_t)t; }
+        const std::vector<int32_t> caller_of = caller_of_lib(ctx);
         for (auto &c : cand) {
             if (c.status == PRES_ABSENT) c.lambda = 0.0;
             if (c.status == PRES_ESSENTIAL) c.lambda = INFINITY;
@@ -253,7 +202,7 @@ struct PresenceRun {
             const Cand &c = cand[(size_t)cand_of_lib[(size_t)lib_of(query ? query[i] : i)]];
             if (out.lambda) out.lambda[i] = c.lambda;
             if (out.pvalue) out.pvalue[i] = presence_pvalue(c.lambda);
-            if (out.heir) out.heir[i] = c.heir < 0 ? -1 : remap ? caller_of[(size_t)c.heir] : c.heir;
+            if (out.heir) out.heir[i] = c.heir < 0 ? -1 : !caller_of.empty() ? caller_of[(size_t)c.heir] : c.heir;
             if (out.heir_share) out.heir_share[i] = c.share;
             if (out.status) out.status[i] = c.status;
             if (out.theta_hat) out.theta_hat[i] = c.theta_hat;
@@ -276,21 +225,8 @@ extern "C" {
 
 int emsar_hip_presence(emsar_hip_ctx *ctx, const emsar_em_params *p, int32_t n_query, const int32_t *query_tids, const emsar_presence_outputs *out,
                        emsar_presence_stats *stats) {
-    if (!ctx) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
-    if (!query_tids) n_query = ctx->n_tx;
-    if (n_query < 0) return EMSAR_HIP_ERR_ARG;
-    if (query_tids) for (int32_t i = 0; i < n_query; i++) if (query_tids[i] < 0 || query_tids[i] >= ctx->n_tx) return EMSAR_HIP_ERR_ARG;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    try {
-        PresenceRun run(ctx, p, n_query, query_tids, out);
-        if (const int rc = run.run()) return rc;
-        run.st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        if (stats) *stats = run.st;
-    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    return EMSAR_HIP_OK;
+    if (const int rc = query_ok(ctx, n_query, query_tids)) return rc;
+    return run_query_call<PresenceRun>(ctx, stats, p, n_query, query_tids, out);
 }
 
 int emsar_hip_presence_pvalue_host(int64_t n, const double *lambda, double *p_out) {

@@ -1,7 +1,7 @@
 // profile.hpp -- the profile-likelihood intervals behind include/emsar_hip.h: emsar_hip_profile (device) and emsar_hip_profile_cut_host (no
 // HIP call).  Part of emsar_hip.hip's translation unit, included after presence.hpp: the first stages ARE the presence test's
 // (PresenceRun: plan, classify, baseline, mark_absent, drop_and_reduce), so theta_hat and Lambda are its bits; k_profile_sets
-// (kernels_profile.hpp) runs the searches.
+// (kernels_profile.hpp) runs the searches, its items batched by the runner the presence test uses (set_items.hpp).
 // One call = one ProfileRun:  plan .. drop    PresenceRun's stages on the same query: status, theta_hat, F per set, Lambda per candidate
 //                             closed_form     one-transcript components: the same search on the host from F(x) = u log x - x den
 //                             search          one item (set, t, side) per limit to find -- upper for every candidate of a resident
@@ -43,13 +43,13 @@ struct ProfileRun {
     const emsar_profile_outputs out;     // a copy: all NULL when the caller gave none
     ProfileSearchParams Q;
     std::vector<Limits> lim;
-    DevBuf<ProfileItem> d_items[emsar::kSetClasses];
-    DevBuf<ProfileRec> d_rec[emsar::kSetClasses];
+    SetItemRunner<ProfileItem, ProfileRec> runner;
     emsar_profile_stats st{};
 
+    // the presence stages batch under the profile's variable too
     ProfileRun(emsar_hip_ctx *c, const emsar_em_params *p, const emsar_profile_params &pp, int32_t nq_, const int32_t *q, const emsar_profile_outputs *o)
-        : ctx(c), pres(c, p, nq_, q, nullptr), nq(nq_), query(q), out(o ? *o : emsar_profile_outputs{}) {
-        pres.batch_env = "EMSAR_HIP_PROFILE_BATCH";
+        : ctx(c), pres(c, p, nq_, q, nullptr, "EMSAR_HIP_PROFILE_BATCH"), nq(nq_), query(q), out(o ? *o : emsar_profile_outputs{}),
+          runner(c, "EMSAR_HIP_PROFILE_BATCH", "profile: an item lies outside its class's sets") {
         Q.q = profile_cut(pp.level);
         Q.dev_tol = pp.dev_tol > 0.0 ? pp.dev_tol : 1e-4;
         Q.max_evals = pp.max_evals > 0 ? pp.max_evals : 40;
@@ -98,63 +98,6 @@ struct ProfileRun {
         }
     }
 
-    // Items of the three classes through k_profile_sets, at most `batch` per class and launch, the classes next to each other on their
-    // streams; recs[c][i] answers items[c][i].  Every index is checked against the class's descriptors before anything is launched.
-    int launch_items(const std::vector<ProfileItem> (&items)[emsar::kSetClasses], std::vector<ProfileRec> (&recs)[emsar::kSetClasses]) {
-        const SetsDev &D = ctx->sets;
-        const auto &S = D.RS;
-        size_t most = 0;
-        for (int c = 0; c < emsar::kSetClasses; c++) {
-            for (const ProfileItem &it : items[c])
-                if (it.set < 0 || (size_t)it.set >= S.desc[c].size() || it.t < 0 || it.t >= (int32_t)S.desc[c][(size_t)it.set].n_t || (it.side != 0 && it.side != 1)) {
-                    ctx->err = "profile: an item lies outside its class's sets";
-                    return EMSAR_HIP_ERR_HIP;
-                }
-            recs[c].resize(items[c].size());
-            most = std::max(most, items[c].size());
-        }
-        if (most == 0) return EMSAR_HIP_OK;
-        // the presence test's bound on a batch: what fits a quarter of the free device memory (at most 2 GiB); EMSAR_HIP_PROFILE_BATCH overrides
-        const int64_t budget = std::min<int64_t>((int64_t)(free_device_bytes() / 4), (int64_t)2 << 30);
-        int64_t batch = std::max<int64_t>(1, budget / (int64_t)(emsar::kSetClasses * (sizeof(ProfileItem) + sizeof(ProfileRec))));
-        if (const char *env = getenv("EMSAR_HIP_PROFILE_BATCH")) { if (atoi(env) >= 1) batch = atoi(env); }
-        batch = std::min<int64_t>(std::min<int64_t>(batch, (int64_t)most), (int64_t)1 << 20);
-        for (int c = 0; c < emsar::kSetClasses; c++)
-            if (!items[c].empty()) {
-                const size_t cnt = std::min<size_t>((size_t)batch, items[c].size());
-                HIPCHK(d_items[c].alloc(cnt)); HIPCHK(d_rec[c].alloc(cnt));
-            }
-        HIPCHK(set_class_lds_attributes((const void *)k_profile_sets<64>, (const void *)k_profile_sets<256>, (const void *)k_profile_sets<512>));
-        const SetSolveParams P = set_params(pres.p);
-        hipEvent_t *e = pres.e;
-        for (size_t first = 0; first < most; first += (size_t)batch) {
-            int rc;
-            size_t cnt[emsar::kSetClasses];
-            for (int c = 0; c < emsar::kSetClasses; c++) {
-                cnt[c] = items[c].size() > first ? std::min<size_t>((size_t)batch, items[c].size() - first) : 0;
-                if (cnt[c]) HIPCHK(hipMemcpyAsync(d_items[c], items[c].data() + first, cnt[c] * sizeof(ProfileItem), hipMemcpyHostToDevice, ctx->stream));
-            }
-            HIPCHK(hipEventRecord(e[0], ctx->stream));
-            if ((rc = fork_side_streams(ctx, 2))) return rc;
-            rc = launch_set_classes(ctx, 2, [&](int c, int threads, hipStream_t s) {
-                if (cnt[c] == 0) return;
-                hipLaunchKernelGGL((c == 2 ? k_profile_sets<512> : c == 1 ? k_profile_sets<256> : k_profile_sets<64>), dim3((unsigned)cnt[c]), dim3(threads),
-                                   S.max_lds[c], s, D.d_sdesc[c].get(), d_items[c].get(), D.d_g_tid.get(), D.d_g_u.get(), D.d_row_w.get(), D.d_srp.get(), D.d_sent.get(),
-                                   D.d_scp.get(), D.d_scrow.get(), ctx->vec.d_den.get(), d_rec[c].get(), P, Q);
-            });
-            if (rc) return rc;
-            HIPCHK(hipEventRecord(e[1], ctx->stream));
-            for (int c = 0; c < emsar::kSetClasses; c++)
-                if (cnt[c]) HIPCHK(hipMemcpyAsync(recs[c].data() + first, d_rec[c], cnt[c] * sizeof(ProfileRec), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, e[0], e[1]));
-            st.search_ms += ms;
-            for (int c = 0; c < emsar::kSetClasses; c++) st.items_launched += (int64_t)cnt[c];
-        }
-        return EMSAR_HIP_OK;
-    }
-
     // the searches of the resident candidates and what their records say
     int search_and_reduce() {
         if (!pres.use_sets) return EMSAR_HIP_OK;
@@ -170,7 +113,16 @@ struct ProfileRun {
                 who[c.cls].push_back((int32_t)k);
             }
         }
-        if (const int rc = launch_items(items, recs)) return rc;
+        const SetsDev &D = ctx->sets;
+        const SetSolveParams P = set_params(pres.p);
+        HIPCHK(set_class_lds_attributes(kProfileSets));
+        const int rc = runner.run(items, recs, st.search_ms, st.items_launched,
+            [](const ProfileItem &it, const emsar::SetDesc &d) { return it.t >= 0 && it.t < (int32_t)d.n_t && (it.side == 0 || it.side == 1); },
+            [&](int c, int threads, hipStream_t s, size_t cnt, const ProfileItem *d_items, ProfileRec *d_rec) {
+                hipLaunchKernelGGL(kProfileSets[c], dim3((unsigned)cnt), dim3(threads), D.RS.max_lds[c], s, D.d_sdesc[c].get(), d_items, D.d_g_tid.get(),
+                                   D.d_g_u.get(), D.d_row_w.get(), D.d_srp.get(), D.d_sent.get(), D.d_scp.get(), D.d_scrow.get(), ctx->vec.d_den.get(), d_rec, P, Q);
+            });
+        if (rc) return rc;
         for (int cls = 0; cls < emsar::kSetClasses; cls++)
             for (size_t i = 0; i < recs[cls].size(); i++) {
                 Limits &l = lim[(size_t)who[cls][i]];
@@ -228,23 +180,10 @@ extern "C" {
 
 int emsar_hip_profile(emsar_hip_ctx *ctx, const emsar_em_params *p, const emsar_profile_params *pp, int32_t n_query, const int32_t *query_tids,
                       const emsar_profile_outputs *out, emsar_profile_stats *stats) {
-    if (!ctx) return EMSAR_HIP_ERR_ARG;
-    if (!ctx->have_sample) return EMSAR_HIP_ERR_STATE;
+    if (const int rc = query_ok(ctx, n_query, query_tids)) return rc;      // first: a context without a sample is a state error whatever pp says
     const emsar_profile_params prm = pp ? *pp : emsar_profile_params{0.95, 0.0, 0, 0};
     if (!(prm.level > 0.0 && prm.level < 1.0) || !std::isfinite(prm.dev_tol)) return EMSAR_HIP_ERR_ARG;
-    if (!query_tids) n_query = ctx->n_tx;
-    if (n_query < 0) return EMSAR_HIP_ERR_ARG;
-    if (query_tids) for (int32_t i = 0; i < n_query; i++) if (query_tids[i] < 0 || query_tids[i] >= ctx->n_tx) return EMSAR_HIP_ERR_ARG;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    try {
-        ProfileRun run(ctx, p, prm, n_query, query_tids, out);
-        if (const int rc = run.run()) return rc;
-        run.st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        if (stats) *stats = run.st;
-    } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
-    return EMSAR_HIP_OK;
+    return run_query_call<ProfileRun>(ctx, stats, p, prm, n_query, query_tids, out);
 }
 
 int emsar_hip_profile_cut_host(double level, double *cut_out) {

@@ -26,7 +26,7 @@ int boot_prepare(emsar_hip_ctx *ctx, bool want_slot) {
         for (int c = 0; c < emsar::kSetClasses; c++) for (const auto &d : S.desc[c]) rw_dev += d.n_r;
         if (rw_dev != (size_t)n_rw || S.n_resident() != ctx->sets.RS.n_resident()) { ctx->err = "bootstrap: draw map does not match the sets"; return EMSAR_HIP_ERR_HIP; }
         const auto &m = tid_map(ctx);
-        const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !m.empty();
+        const bool remap = renumbered(ctx);
         for (auto &v : slot)
             if (v <= -2) { const int64_t t = -2 - v; v = n_rw + (remap ? m[(size_t)t] : t); }   // usum entry, library numbering
         HIPCHK(ctx->sets.d_boot_slot.upload(slot.data(), (size_t)ctx->n_rows));
@@ -128,8 +128,6 @@ struct BootTimes {
     double draw_ms = 0, sets_ms = 0, stream_ms = 0, reduce_ms = 0, quantile_ms = 0, total_ms = 0;
 };
 
-inline size_t free_device_bytes() { size_t f = 0, t = 0; return hipMemGetInfo(&f, &t) == hipSuccess ? f : (size_t)1 << 30; }
-
 // One resampling call: parameters, switches, sizes, buffers and counters, and the stages as functions of the batch (replicates
 // done .. done + nb - 1 of the round in progress).
 struct BootRun {
@@ -203,7 +201,7 @@ struct BootRun {
         const int64_t T = n, G = genes ? ng : 0, nq = plan.n_q;      // G: genes with quantile outputs
         const bool uq = iso && plan.iso->usage_q;
         const auto &m = tid_map(ctx);
-        const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !m.empty();
+        const bool remap = renumbered(ctx);
         const int64_t need = t.held_bytes + 8 * (int64_t)n_rep + 8 * nq + 16 * nq * (T + G) + (remap ? 4 * T : 0) + (uq ? 8 * nq * T : 0);
         if ((uint64_t)need > (uint64_t)(free_device_bytes() / 2)) { ctx->err = "bootstrap quantiles: the replicates do not fit half of the free device memory"; return EMSAR_HIP_ERR_OOM; }
         if (d_thb.alloc((size_t)(n_rep * T)) != hipSuccess || d_sums.alloc((size_t)n_rep) != hipSuccess || (gene_sums && d_gsum.alloc((size_t)(n_rep * ng)) != hipSuccess) || d_q.alloc((size_t)nq) != hipSuccess ||
@@ -234,10 +232,7 @@ struct BootRun {
         // (a quantile call's theta, S_b and gene sums live in the held buffers, allocated before: not part of a batch, and what is free is what they left)
         const int64_t per_rep = 8 * (slot_stride + n_gu + (hold ? 0 : n + 1 + ng) + n_gchunk) + (need_stream ? 4 * n_rows : 0) + (int64_t)sizeof(SetStat) * n_sets +
                                 (iso ? 4 * ng + 12 * n_gchunk : 0);
-        const int64_t budget = std::min<int64_t>((int64_t)(free_device_bytes() / 4), (int64_t)2 << 30);
-        batch = std::max<int64_t>(1, budget / std::max<int64_t>(per_rep, 1));
-        if (const char *env = getenv("EMSAR_HIP_BOOT_BATCH")) { if (atoi(env) >= 1) batch = atoi(env); }
-        batch = std::min<int64_t>(std::min<int64_t>(batch, n_rep), 65535);
+        batch = item_batch(std::max<int64_t>(per_rep, 1), "EMSAR_HIP_BOOT_BATCH", n_rep, 65535);
         return EMSAR_HIP_OK;
     }
     // the batch's device buffers (a quantile call keeps all n_rep replicates: a batch then writes its rows of the held buffers instead
@@ -264,7 +259,7 @@ struct BootRun {
         HIPCHK(guard.d_th0.alloc((size_t)n));
         HIPCHK(hipMemcpyAsync(guard.d_th0, ctx->vec.d_th[0], (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream));
         HIPCHK(hipEventCreate(&e[0])); HIPCHK(hipEventCreate(&e[1]));
-        if (n_sets) HIPCHK(set_class_lds_attributes((const void *)k_solve_sets_boot<64>, (const void *)k_solve_sets_boot<256>, (const void *)k_solve_sets_boot<512>));
+        if (n_sets) HIPCHK(set_class_lds_attributes(kSolveSetsBoot));
         h_wb.resize(need_stream ? (size_t)(batch * n_rows) : 0);
         h_th.resize((size_t)std::max(n, 1));
         h_bstat.resize((size_t)(batch * n_sets));
@@ -299,7 +294,7 @@ struct BootRun {
         const size_t off[3] = {0, S.desc[0].size(), S.desc[0].size() + S.desc[1].size()};
         if ((rc = fork_side_streams(ctx, 2))) return rc;
         rc = launch_set_classes(ctx, 2, [&](int c, int threads, hipStream_t st) {
-            hipLaunchKernelGGL((c == 2 ? k_solve_sets_boot<512> : c == 1 ? k_solve_sets_boot<256> : k_solve_sets_boot<64>),
+            hipLaunchKernelGGL(kSolveSetsBoot[c],
                                dim3((unsigned)S.desc[c].size(), (unsigned)nb), dim3(threads), S.max_lds[c], st, ctx->sets.d_sdesc[c], ctx->sets.d_g_tid, d_gu,
                                d_slots, ctx->sets.d_srp, ctx->sets.d_sent, ctx->sets.d_scp, ctx->sets.d_scrow, ctx->vec.d_den, thb, d_bstat + off[c], set_params(p), n_gu, slot_stride,
                                (int64_t)n, n_sets);
@@ -618,7 +613,7 @@ int emsar_hip_set_gene_map(emsar_hip_ctx *ctx, int32_t n_genes, const int32_t *g
         std::vector<int32_t> tx((size_t)m), chunk_beg, chunk_out, multi, of_lib((size_t)n);
         std::vector<int64_t> fill(gp.begin(), gp.end() - 1);
         const auto &map = tid_map(ctx);
-        const bool remap = ctx->layout == EMSAR_LAYOUT_TILED && !map.empty();
+        const bool remap = renumbered(ctx);
         for (int32_t t = 0; t < n; t++)
             if (gene_of_tx[t] >= 0) tx[(size_t)fill[(size_t)gene_of_tx[t]]++] = remap ? map[(size_t)t] : t;
         for (int32_t t = 0; t < n; t++) of_lib[(size_t)(remap ? map[(size_t)t] : t)] = gene_of_tx[t];
@@ -705,12 +700,7 @@ int emsar_hip_isoform_usage(emsar_hip_ctx *ctx, int32_t n_cols, const double *tx
     }
     try {
         std::vector<double> tmp;
-        std::vector<int32_t> caller_of;                         // library index -> caller tid, empty = the same
-        const auto &m = tid_map(ctx);
-        if (dominant_out && ctx->layout == EMSAR_LAYOUT_TILED && !m.empty()) {
-            caller_of.resize(m.size());
-            for (size_t t = 0; t < m.size(); t++) caller_of[(size_t)m[t]] = (int32_t)t;
-        }
+        const std::vector<int32_t> caller_of = dominant_out ? caller_of_lib(ctx) : std::vector<int32_t>();      // library index -> caller tid, empty = the same
         for (int64_t c0 = 0; c0 < n_cols; c0 += cb) {
             const int64_t k = std::min<int64_t>(cb, n_cols - c0);
             for (int64_t j = 0; j < k; j++) {

@@ -12,17 +12,16 @@ namespace {
 
 // ---- the set driver: the sample's connected sets on the device, and their launches ------------------------------------------------
 
-// the dynamic LDS of the three size classes of a set kernel (k_solve_sets, k_solve_sets_boot)
-hipError_t set_class_lds_attributes(const void *k64, const void *k256, const void *k512) {
-    const void *const kernel[emsar::kSetClasses] = {k64, k256, k512};
+// the dynamic LDS that the three size classes of a set-kernel family may ask for (the families: SetKernels, kernels_sets.hpp)
+template <class Kernel> hipError_t set_class_lds_attributes(const SetKernels<Kernel> &family) {
     for (int c = 0; c < emsar::kSetClasses; c++)
-        if (const hipError_t e = hipFuncSetAttribute(kernel[c], hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[c])) return e;
+        if (const hipError_t e = hipFuncSetAttribute((const void *)family[c], hipFuncAttributeMaxDynamicSharedMemorySize, (int)emsar::kSetLdsCap[c])) return e;
     return hipSuccess;
 }
 
 // the sets were found on the caller's CSR; theta / den on the device are in the library's numbering
 int renumber_sets(const emsar_hip_ctx *ctx, emsar::ResidentSets &S) {
-    if (ctx->layout != EMSAR_LAYOUT_TILED || tid_map(ctx).empty()) return EMSAR_HIP_OK;
+    if (!renumbered(ctx)) return EMSAR_HIP_OK;
     const auto &m = tid_map(ctx);
     try {
         std::vector<uint8_t> kind(S.kind.size());
@@ -52,7 +51,7 @@ int upload_resident_records(emsar_hip_ctx *ctx, emsar::ResidentSets &S) {
         HIPCHK(D.d_sstat.alloc((size_t)n));
         HIPCHK(D.h_sstat.alloc((size_t)n));
         D.n_sstat = n;
-        HIPCHK(set_class_lds_attributes((const void *)k_solve_sets<64>, (const void *)k_solve_sets<256>, (const void *)k_solve_sets<512>));
+        HIPCHK(set_class_lds_attributes(kSolveSets));
     }
     std::vector<int32_t>().swap(S.g_tid); std::vector<double>().swap(S.g_u); std::vector<double>().swap(S.row_w);
     std::vector<uint16_t>().swap(S.rp); std::vector<uint16_t>().swap(S.ent); std::vector<uint16_t>().swap(S.cp); std::vector<uint16_t>().swap(S.crow);
@@ -165,7 +164,7 @@ int solve_resident_sets(emsar_hip_ctx *ctx, const SetSolveParams &P, const SetSo
     if ((rc = fork_side_streams(ctx, 3))) return rc;
     if (D.n_cstat > 0 && (rc = launch_clusters(ctx, Pcluster, theta))) return rc;
     return launch_set_classes(ctx, 3, [&](int c, int threads, hipStream_t st) {
-        hipLaunchKernelGGL((c == 2 ? k_solve_sets<512> : c == 1 ? k_solve_sets<256> : k_solve_sets<64>), dim3((unsigned)S.desc[c].size()), dim3(threads),
+        hipLaunchKernelGGL(kSolveSets[c], dim3((unsigned)S.desc[c].size()), dim3(threads),
                            S.max_lds[c], st, D.d_sdesc[c], D.d_g_tid, D.d_g_u, D.d_row_w, D.d_srp, D.d_sent, D.d_scp, D.d_scrow, ctx->vec.d_den, theta,
                            D.d_sstat + off[c], P);
     });
