@@ -15,6 +15,7 @@ import oracle as O
 from emsar_amd import EmsarHip, EmsarHipError
 from emsar_amd.hip import LAYOUT_TILED
 from tests import pass_problems as P
+from tests.cycle_reference import ld_pass as _ld_pass      # one EM pass in long double
 from tests.pass_problems import VARIANTS
 
 pytestmark = pytest.mark.gpu
@@ -194,23 +195,6 @@ def test_dense_coo_lists_are_refused_and_the_context_stays_usable(dev, monkeypat
     _knobs(monkeypatch, dict(TILED_MULTI="5", WEIGHTED_UNIT="2"))
     c.upload(dev, False)
     _passes(dev, c, "after a refused layout")
-
-
-def _ld_pass(p, w, den, th):
-    """One EM pass in long double: S by add.reduceat, w / S, acc by scattering; returns (theta', sum w log S)."""
-    n = np.diff(p.rp.astype(np.int64))
-    x = th.astype(np.longdouble)
-    S = np.add.reduceat(np.append(x[p.ci], np.longdouble(0)), p.rp[:-1].astype(np.int64))
-    S[n == 0] = 0
-    live = (w > 0) & (S > 0)
-    q = np.zeros(p.n_rows, dtype=np.longdouble)
-    q[live] = w[live].astype(np.longdouble) / S[live]
-    acc = np.zeros(p.n_tx, dtype=np.longdouble)
-    np.add.at(acc, p.ci, np.repeat(q, n))
-    d = den.astype(np.longdouble)
-    out = np.where(den > 0, x * acc / np.where(den > 0, d, 1), 0)
-    terms = w[live].astype(np.longdouble) * np.log(S[live])
-    return out, np.sum(terms), np.sum(np.abs(terms))
 
 
 @pytest.mark.parametrize("variant", ["tiled_RE", "unit_wu0", "unit_wu1", "unit_wu2", "merged_unit"])
