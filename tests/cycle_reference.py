@@ -1,6 +1,8 @@
 """A long-double restatement of one cycle of the streaming solve (solve.hpp: enqueue_cycles; kernels_vector.hpp: k_update,
 k_cycle_begin, k_update_p2, k_sq_extrap_ll, k_update_p3), CPU only.  test_squarem_cycle_cpu.py runs it alone, test_squarem_cycle_gpu.py
-starts it at the device's own points, test_pass_kernels_gpu.py uses its EM pass.
+starts it at the device's own points, test_pass_kernels_gpu.py uses its EM pass.  The set-resident solver (kernels_sets.hpp) runs the
+same cycle per connected set: the second half of this file holds one Model per set, the set solver's Newton step restated
+(newton_step) and the cases of test_set_cycle_cpu.py / test_set_cycle_gpu.py.
 
 One SQUAREM cycle from A with the step bound stepmax, as the comments above em_new_theta state it:
     th1 = EM(A), th2 = EM(th1), r = th1 - A, v = (th2 - th1) - r
@@ -299,6 +301,14 @@ def _fast_slow(K):
     64 pairs of abundant transcripts (about 1000 reads each of their own, 0.5 % of them shared: EM contracts by 0.005 per pass there,
     and den = 1e-5 puts their optimum at 1e8, far from the start) carry |r| and |v|; 64 pairs of rare ones (2-8 reads of their own,
     8-13 shared: contraction about 0.5) start within 30 % of their optimum and are what an extrapolation would move."""
+    n_tx, rp, ci, R, den = _fast_slow_rows(linked=False)
+    return Problem("fast_slow", K, n_tx, rp, ci, R=R, den=den)
+
+
+def _fast_slow_rows(linked):
+    """the rows of fast_slow -> (n_tx, rp, ci, R, den).  linked: one more row of one read {i + 1, i + 2} between every two neighbouring
+    pairs, which makes the 128 pairs ONE connected set of 256 transcripts and 255 rows (the set solver's 256-thread class) and
+    leaves the second cycle's step where it was (s = 1.0051)."""
     rng = np.random.default_rng(3)
     rows, w, den = [], [], np.zeros(256)
     for i in range(0, 128, 2):
@@ -312,9 +322,13 @@ def _fast_slow(K):
         w += [u1, u2, m]
         den[i] = (u1 + m / 2) * (1 + 0.3 * rng.uniform(-1, 1))
         den[i + 1] = (u2 + m / 2) * (1 + 0.3 * rng.uniform(-1, 1))
+    if linked:
+        for i in range(1, 255, 2):
+            rows.append([i, i + 1])
+            w.append(1)
     rp = np.zeros(len(rows) + 1, dtype=np.uint64)
     rp[1:] = np.cumsum([len(r) for r in rows])
-    return Problem("fast_slow", K, 256, rp, np.concatenate(rows).astype(np.int32), R=np.array(w, dtype=np.int32), den=den)
+    return 256, rp, np.concatenate(rows).astype(np.int32), np.array(w, dtype=np.int32), den
 
 
 # K: the longest run of cycles from the uniform start in which the reference meets every condition below (test_squarem_cycle_cpu.py).
@@ -360,3 +374,292 @@ def choose_rules(model, x, y, passes_done):
     step = float(np.sqrt(move[top] * b) * max(passes_done + 1, 1000) / LD(2e5))
     out["abs_step"] = (Rules(abs_step=step), float(b / move[top]), stop_measure(x, y, den, Rules(abs_step=step), passes_done)[0])
     return out
+
+
+# ---- the set-resident solver (kernels_sets.hpp: solve_one_set, set_newton_step) ----------------------------------------------------------
+# One workgroup runs the same cycle on one connected set, with a step s and a stepmax of its own.  A single-transcript row {t} with count
+# R is the folded u_t of the kernel: x (R / x) = u in the update, R log x in F -- so Model states the set's cycle as it stands, once it
+# holds the set's rows only.
+
+def set_model(rp, ci, R, E, den, tids, rows):
+    """The Model of one connected set of a sample: tids its transcripts in the caller's numbering (their order is the model's), rows the
+    caller's rows that hold them (single-transcript rows included, E = 0 rows count 0), den the whole sample's den."""
+    rp = np.asarray(rp).astype(np.int64)
+    local = np.full(len(den), -1, dtype=np.int64)
+    local[tids] = np.arange(len(tids))
+    n = np.diff(rp)[rows]
+    srp = np.zeros(len(rows) + 1, dtype=np.uint64)
+    srp[1:] = np.cumsum(n)
+    sci = local[np.concatenate([np.asarray(ci)[rp[r]:rp[r + 1]] for r in rows])]
+    assert (sci >= 0).all(), "a row of the set holds a transcript outside it"
+    return Model(len(tids), srp, sci, np.asarray(R)[rows], np.asarray(den)[tids], np.asarray(E)[rows])
+
+
+class SetCase:
+    """A sample for the set solver: what a test uploads (den is the E-scatter, computed once on the host), one Model per connected
+    set with the set's caller tids, the size class of the kernel that solves each set, and K, the cycles that are checked."""
+
+    def __init__(self, name, K, cls, composed, den=None):
+        self.name, self.K, self.cls = name, K, cls
+        self.n_tx, self.rp, self.ci, self.R, self.E = composed[:5]
+        self.whole = Model(self.n_tx, self.rp, self.ci, self.R, den, self.E)      # den given (then E is None): the caller's own
+        self.den = self.whole.den
+        if len(composed) > 5:
+            self.tids = [m[0] for m in composed[5]]
+            self.models = [set_model(self.rp, self.ci, self.R, self.E, self.den, t, r) for t, r in composed[5]]
+        else:                                   # one connected set: the whole sample's model is the set's
+            self.tids, self.models = [np.arange(self.n_tx)], [self.whole]
+        self.model = self.models[0]
+        for a in (self.rp, self.ci, self.R, self.E, self.den):
+            if a is not None:
+                a.setflags(write=False)
+
+
+def _shape_case(shape, seed):
+    from tests import set_problems as SP
+    return SP.compose([SP.edge_set(*shape, seed=seed)], seed=seed)
+
+
+def _ragged_case(seed):
+    from tests import set_problems as SP
+    return SP.compose([SP.ragged_set(seed)], seed=seed)
+
+
+def _edge_case(k):
+    from tests import set_problems as SP
+    return SP.edge_problem(k)
+
+
+# name -> (size class, K, the cap on K, builder).  K: the longest run of cycles from the uniform start, the cap at the most, in which the
+# reference meets comparable() and LEFT_OUT_MAX (test_set_cycle_cpu.py holds every K to that).  The cap is 12 for the problems of
+# set_problems.py as the edge tests solve them and 14 for the seeded ones, compose([set], seed) of a shape or of ragged_set(seed): these
+# were searched, 40 seeds a shape, for kinds of cycle with the reference alone.  Nothing the device computes entered a choice.
+# ragged_problem() stops at 3: cycle 4 leaves one component of its 60 out, 1.7 %.
+SET_EDGE_K = {0: 12, 1: 12, 2: 3, 3: 4, 4: 12, 5: 12, 6: 8, 7: 6, 8: 12}
+SET_RAGGED_K = 3
+SET_SEEDED = {((40, 80, 227), 307): (0, 14), ((40, 80, 227), 308): (0, 14),
+              ((40, 80, 228), 325): (1, 13), ((40, 80, 228), 302): (1, 9), ((250, 500, 4784), 308): (1, 14),
+              ((100, 513, 1100), 302): (2, 10), ((100, 513, 1100), 311): (2, 11)}
+# accepted cycles only, but the most components that keep th2 in the 512-thread class (2 .. 5 per cycle), up to 0.8 % left out
+SET_SEEDED.update({((250, 500, 4785), seed): (2, 14) for seed in range(300, 312)})
+SET_RAGGED_SEEDED = {2: 14, 4: 14, 7: 14}
+SET_CASES = {}
+
+
+def _add_set_cases():
+    from tests import set_problems as SP
+    for k, K in SET_EDGE_K.items():
+        SET_CASES["edge%d" % k] = (SP.EDGES[k][2], K, 12, lambda k=k: _edge_case(k))
+    SET_CASES["ragged"] = (0, SET_RAGGED_K, 12, lambda: SP.ragged_problem())
+    for (shape, seed), (cls, K) in SET_SEEDED.items():
+        SET_CASES["%dx%dx%d-s%d" % (shape + (seed,))] = (cls, K, 14, lambda shape=shape, seed=seed: _shape_case(shape, seed))
+    for seed, K in SET_RAGGED_SEEDED.items():
+        SET_CASES["ragged-s%d" % seed] = (0, K, 14, lambda seed=seed: _ragged_case(seed))
+    # cycle 2 has s = 1.0051: between 1 and the switch at 1.01; cycle 3 has an acceptance margin of 9.5e-10
+    SET_CASES["fast_slow_linked"] = (1, 2, 14, lambda: _fast_slow_rows(linked=True))
+
+
+_add_set_cases()
+_set_cases = {}
+
+
+def set_case(name):
+    if name not in _set_cases:
+        cls, K, _, make = SET_CASES[name]
+        made = make()
+        if name == "fast_slow_linked":                     # (n_tx, rp, ci, R, den): no E, a den of its own
+            _set_cases[name] = SetCase(name, K, cls, made[:4] + (None,), den=made[4])
+        else:
+            _set_cases[name] = SetCase(name, K, cls, made)
+    return _set_cases[name]
+
+
+def longest_run(model, limit=14):
+    """the cycles from the uniform start while each meets comparable() and LEFT_OUT_MAX, limit at the most"""
+    A, stepmax, out = model.start, 1.0, []
+    for k in range(limit):
+        c = model.cycle(A, stepmax, 3 * k)
+        if not comparable(c) or float((c.kappa > KAPPA_MAX).mean()) > LEFT_OUT_MAX:
+            break
+        out.append(c)
+        A, stepmax = c.A_next, c.stepmax_next
+    return out
+
+
+# ---- the projected Newton step of the set solver -------------------------------------------------------------------------------------------
+
+BOUND_READS = 1e-6          # kBoundReads of set_newton_step
+# the conditions under which a Newton step's choices can be compared between two implementations
+NEWTON_MASK_MARGIN, NEWTON_RQ_MARGIN, NEWTON_F_MARGIN, NEWTON_REOPEN_MARGIN = 1e-6, 1e-2, 1e-11, 1e-7
+NEWTON_FLOOR_READS = 1e-6   # the distance between two results is measured in reads against reads + this
+# Where the step is checked on the device: size class -> (case, early / late / refused, k's): the step from A_k, the point after k cycles.
+# The device is checked at the FIRST k, which has margins on the reference's own trajectory (test_set_cycle_cpu.py; the GPU test asserts
+# them again at the device's A_k, which is another point, the more so the later it is).  The other k's are neighbours at which the
+# distance between the two precisions is measured too.  The late points have bound components: transcripts without reads of their own on
+# their way to 0.  At the refused point all four trial steps lose F: the solver leaves the point alone and counts the passes.
+NEWTON_POINTS = {0: [("40x80x227-s307", "early", (2, 3, 4)), ("40x80x227-s307", "late", (20, 22)), ("40x80x227-s307", "refused", (18,))],
+                 1: [("40x80x228-s325", "early", (2, 3, 4)), ("edge4", "late", (50, 55, 60))],
+                 2: [("100x513x1100-s302", "early", (2, 3, 4)), ("edge8", "late", (60, 64, 56))]}
+# The largest distance between newton_step in float64 and in long double at those points: 1.39e-11 (edge4, k = 55; then 7.6e-12 at edge8,
+# k = 64).  The GPU test derives its bound from the measured figure; test_set_cycle_cpu.py holds every distance to the cap, which leaves
+# room for another libm or numpy.
+NEWTON_DIST, NEWTON_DIST_CAP = 1.4e-11, 2e-11
+
+
+class Newton:
+    """What one Newton step computed (attributes; see newton_step())."""
+
+
+def _rows_dot(p, v):
+    n = np.diff(p.rp.astype(np.int64))
+    S = np.add.reduceat(np.append(v[p.ci], v.dtype.type(0)), p.rp[:-1].astype(np.int64))
+    S[n == 0] = 0
+    return S
+
+
+def _cols_sum(p, rowv):
+    n = np.diff(p.rp.astype(np.int64))
+    out = np.zeros(p.n_tx, dtype=rowv.dtype)
+    order, starts, ids = _scatter_plan(p)
+    if len(starts):
+        out[ids] = np.add.reduceat(np.repeat(rowv, n)[order], starts)
+    return out
+
+
+def newton_step(model, x, T=LD):
+    """set_newton_step restated in the float type T, and the plain EM step that follows it in solve_one_set (with its re-opening of a
+    bound component whose gradient at 0 has turned positive).  Returns a Newton: x_new (x if refused), accepted, n_cg, n_trials, passes
+    (1 + n_cg + n_trials), bound (mask), y = EM(x_new), measure (of x_new -> y, abs_floor 1e-6, no other rule), and the margins of every
+    choice: mask_margin (g < 0 and x den < 1e-6 of the components without reads of their own), rq_margin (rq against rq_stop at every
+    look, relative to rq_stop), F_margin (Fn against Fx - 1e-13 |Fx| at every trial, relative to the sum of |terms| of both),
+    reopen_margin (acc against den (1 + 1e-9) at the components at 0)."""
+    o = Newton()
+    n = np.diff(model.rp.astype(np.int64))
+    single = n == 1
+    w = model.w.astype(T)
+    rw = np.where(single, T(0), w)                       # the rows of the set; a single-transcript row is folded into u
+    u = np.zeros(model.n_tx, dtype=T)
+    np.add.at(u, model.ci[model.rp[:-1].astype(np.int64)[single]], w[single])
+    den, x = model.den.astype(T), x.astype(T)
+    pos = x > 0
+    safe_x = np.where(pos, x, T(1))
+
+    def F(v):
+        S = _rows_dot(model, v)
+        live, vp = S > 0, (u > 0) & (v > 0)
+        terms = np.concatenate([rw[live] * np.log(S[live]), u[vp] * np.log(v[vp]), -(v * den)])
+        bad = int(((rw > 0) & ~live).sum() + ((u > 0) & ~(v > 0)).sum())
+        return np.sum(terms), np.sum(np.abs(terms)), bad
+
+    S = _rows_dot(model, x)
+    live = (S > 0) & (rw > 0)
+    inv = np.where(live, T(1) / np.where(live, S, T(1)), T(0))
+    acc = _cols_sum(model, rw * inv)
+    hrow = rw * inv * inv
+    up2 = np.where(pos, u / (safe_x * safe_x), T(0))
+    g = acc - den + np.where(pos, u / safe_x, T(0))
+    Fx, Fx_abs, _ = F(x)
+    inF = den > 0
+    o.bound = bound = inF & (g < 0) & (x * den < T(BOUND_READS)) & (u == 0)
+    free = inF & ~bound
+    cand = inF & (u == 0)                                # what could be bound: both conditions have a margin there
+    o.mask_margin = np.inf
+    if cand.any():
+        mg = np.abs(g[cand]) / (acc[cand] + den[cand])
+        mx = np.abs(x[cand] * den[cand] - T(BOUND_READS)) / T(BOUND_READS)
+        small, neg = (x * den < T(BOUND_READS))[cand], (g < 0)[cand]
+        # a condition matters only where the other one holds
+        o.mask_margin = float(min(np.min(np.where(small, mg, np.inf)), np.min(np.where(neg, mx, np.inf))))
+    diag = _cols_sum(model, hrow) + up2
+    mi = np.where(free, np.where(diag > 0, T(1) / np.where(diag > 0, diag, T(1)), T(1)), T(0))
+    r = np.where(free, g, T(0))
+    z = np.zeros(model.n_tx, dtype=T)
+    p = mi * r
+    rq = np.sum(r * p)
+    rq_stop = T(1e-8) * rq
+    o.n_cg, o.rq_margin = 0, np.inf
+    for it in range(model.n_tx):
+        if rq_stop > 0:
+            o.rq_margin = min(o.rq_margin, float(abs(rq - rq_stop) / rq_stop))
+        if not (rq > rq_stop and rq > 0):
+            break
+        hp = np.where(free, _cols_sum(model, hrow * _rows_dot(model, p)) + up2 * p, T(0))
+        s1 = np.sum(p * hp)
+        o.n_cg += 1
+        if not s1 > 0:
+            break
+        al = rq / s1
+        z = z + al * p
+        r = r - al * hp
+        s2 = np.sum(np.where(free, r * (mi * r), T(0)))
+        beta = s2 / rq
+        rq = s2
+        p = mi * r + beta * p
+    else:
+        o.rq_margin = min(o.rq_margin, float(abs(rq - rq_stop) / rq_stop)) if rq_stop > 0 else o.rq_margin
+    o.z = z
+    o.n_trials, o.accepted, o.F_margin, o.x_new, o.alpha = 0, False, np.inf, x, T(0)
+    alpha = T(1)
+    for tr in range(4):
+        xn = np.where(free, np.maximum(x + alpha * z, T(0)), np.where(bound, T(0) if alpha == 1 else x * (1 - alpha), T(0)))
+        Fn, Fn_abs, bad = F(xn)
+        o.n_trials += 1
+        if bad == 0:
+            o.F_margin = min(o.F_margin, float(abs(Fn - (Fx - T(1e-13) * abs(Fx))) / (Fx_abs + Fn_abs)))
+        if bad == 0 and Fn >= Fx - T(1e-13) * abs(Fx):
+            o.accepted, o.x_new, o.alpha = True, xn, alpha
+            break
+        alpha = alpha * T(0.25)
+    o.passes = 1 + o.n_cg + o.n_trials
+    # the plain step that follows: B = EM(x_new), a component at 0 whose gradient there is positive is re-opened just above 0
+    v = o.x_new
+    S = _rows_dot(model, v)
+    live = (S > 0) & (rw > 0)
+    acc = _cols_sum(model, rw * np.where(live, T(1) / np.where(live, S, T(1)), T(0)))
+    safe_den = np.where(inF, den, T(1))
+    y = np.where(inF & (v > 0), (v * acc + u) / safe_den, T(0))
+    at0 = inF & (v == 0)
+    reopen = at0 & (acc > den * (1 + T(1e-9)))
+    o.reopen_margin = float(np.min(np.abs(acc[at0] / den[at0] - (1 + T(1e-9))))) if at0.any() else np.inf
+    o.y = np.where(reopen, T(1e-9) / safe_den, y)
+    o.reopened = int(reopen.sum())
+    d = np.abs(o.y - v) / (np.abs(o.y) + T(1e-6))
+    o.measure = T(1) if reopen.any() else (d.max() if len(d) else T(0))
+    return o
+
+
+def newton_comparable(o):
+    return (o.mask_margin >= NEWTON_MASK_MARGIN and o.rq_margin >= NEWTON_RQ_MARGIN and o.F_margin >= NEWTON_F_MARGIN
+            and o.reopen_margin >= NEWTON_REOPEN_MARGIN)
+
+
+def newton_margins(o):
+    return "accepted %s alpha %g n_cg %d n_trials %d bound %d reopened %d | margins: mask %.3g rq %.3g F %.3g reopen %.3g" % (
+        o.accepted, float(o.alpha), o.n_cg, o.n_trials, int(o.bound.sum()), o.reopened, o.mask_margin, o.rq_margin, o.F_margin, o.reopen_margin)
+
+
+def newton_distance(a, b, den):
+    """the largest distance between two results in reads, against the reads of the component plus NEWTON_FLOOR_READS (below that many
+    reads the step itself takes a component for 0)"""
+    a, b, den = a.astype(LD), b.astype(LD), den.astype(LD)
+    return float(np.max(np.abs(a - b) * den / (np.abs(b) * den + LD(NEWTON_FLOOR_READS))))
+
+
+def choose_late_abs_step(model, x, y, passes_done):
+    """An abs_step for a step x -> y past 1000 passes that shows the pass count in its bound: the bound at this pass lies at the geometric
+    midpoint of a gap of at least GAP_MIN^2 between two components' moves, the measure under it is positive and differs by more than
+    1e-3 both from the plain one and from the measure under the bound of pass 1000, which is (passes_done + 1) / 1000 times larger.
+    Returns (Rules, gap, measure, measure under the bound of pass 1000) of the smallest such bound, or None."""
+    assert passes_done + 1 > 1000
+    x, y = x.astype(LD), y.astype(LD)
+    plain, _, _, move = stop_measure(x, y, model.den, Rules(), passes_done)
+    moves = np.unique(move[move > 0])
+    for a, b in zip(moves, moves[1:]):
+        if b / a < GAP_MIN * GAP_MIN:
+            continue
+        r = Rules(abs_step=float(np.sqrt(a * b) * (passes_done + 1) / LD(2e5)))
+        measure = stop_measure(x, y, model.den, r, passes_done)[0]
+        frozen = stop_measure(x, y, model.den, r, 0)[0]
+        if measure > 0 and abs(measure - plain) > 1e-3 * plain and abs(frozen - measure) > 1e-3 * measure:
+            return r, float(b / a), measure, frozen
+    return None

@@ -118,11 +118,19 @@ def compose(sets, seed=0):
     Added on top of the requested shapes, so that these stay exact: copies of about 5 % of the rows with E = 0 (outside the
     likelihood: no part of any set) and, for about 10 % of the transcripts, a single-transcript row (folded into the transcript's own
     count, no row of a set).  E is uniform in [0.5, 2] elsewhere."""
+    return compose_members(sets, seed)[:5]
+
+
+def compose_members(sets, seed=0):
+    """compose, and the membership: -> (n_tx, rp, ci, R, E, members), members[k] = (tids, rows) of sets[k] in the caller's numbering --
+    its transcripts in the order of the set's local ids, and every row that holds one of them (ascending): the rows of the shape, their
+    E = 0 copies and the single-transcript rows."""
     rng = np.random.default_rng(seed)
-    rows, R, base = [], [], 0
+    rows, R, base, bases = [], [], 0, []
     for s in sets:
         rows += [tuple(base + t for t in r) for r in s.rows]
         R += s.weights
+        bases.append(base)
         base += s.n_t
     n_tx, n_shape = base, len(rows)
     E = list(rng.uniform(0.5, 2.0, size=n_shape))
@@ -140,7 +148,9 @@ def compose(sets, seed=0):
     rp = np.zeros(len(rows) + 1, dtype=np.uint64)
     rp[1:] = np.cumsum([len(r) for r in rows])
     ci = shuffle[np.concatenate([np.array(r, dtype=np.int64) for r in rows])].astype(np.int32)
-    return n_tx, rp, ci, np.array(R, dtype=np.int32)[order], np.array(E)[order]
+    set_of_row = np.searchsorted(np.array(bases + [n_tx]), np.array([r[0] for r in rows]), side="right") - 1
+    members = [(shuffle[b:b + s.n_t].astype(np.int64), np.flatnonzero(set_of_row == k)) for k, (s, b) in enumerate(zip(sets, bases))]
+    return n_tx, rp, ci, np.array(R, dtype=np.int32)[order], np.array(E)[order], members
 
 
 _cache = {}
@@ -172,6 +182,13 @@ def all_resident_problem():
     if "resident" not in _cache:
         _cache["resident"] = compose(resident_sets(), seed=16)      # of seeds 11 .. 30 the quickest for the oracle solving it as one problem
     return _cache["resident"]
+
+
+def all_resident_members():
+    """all_resident_problem() with the membership of its sets (compose_members)"""
+    if "resident_members" not in _cache:
+        _cache["resident_members"] = compose_members(resident_sets(), seed=16)
+    return _cache["resident_members"]
 
 
 def everything_problem():
