@@ -20,6 +20,7 @@
 //   fit.hpp           the model fit and its C ABI
 //   presence.hpp      the presence test (a likelihood-ratio test per transcript on its resident set) and its C ABI
 //   profile.hpp       the profile-likelihood intervals (two confidence limits per transcript, each a root search over set solves) and their C ABI
+//   compare.hpp       the two-sample likelihood-ratio test (two contexts; per transcript a multiplier search over set solves of both samples) and its C ABI
 //   asym.hpp          the asymptotic standard errors (the observed information of every component, factorised on the device) and their C ABI
 // Kernels (one translation unit, included below):
 //   kernels_tiled.hpp     k_pass_tiled_unit                      the hot one (the default above 2048 tiles): one workgroup per UNIT of up to
@@ -33,6 +34,7 @@
 //   kernels_sets.hpp      k_solve_sets                           one workgroup solves one connected set out of LDS
 //   kernels_presence.hpp  k_solve_sets_drop                      a set solved without one of its transcripts, and F at the result out of the same LDS
 //   kernels_profile.hpp   k_profile_sets                         one workgroup searches one confidence limit: set solves with den_t scaled, F as above
+//   kernels_compare.hpp   k_compare_sets                         one workgroup searches one transcript's multiplier: per evaluation a set solve of each sample
 //   kernels_boot.hpp      k_boot_draw, k_boot_accum, ...         the Poisson bootstrap (draws: boot_rng.hpp; sets: k_solve_sets_boot)
 //                         k_sub_draw, k_sub_scale                the depth subsampling: binomial draws, every replicate to its own depth
 //   kernels_genes.hpp     k_gene_sums, k_gene_finish             per-gene sums in a fixed order (gene_sums, the bootstrap's gene sd)
@@ -72,6 +74,7 @@
 #include "kernels_sets.hpp"
 #include "kernels_presence.hpp"
 #include "kernels_profile.hpp"
+#include "kernels_compare.hpp"
 #include "kernels_cluster.hpp"
 #include "kernels_boot.hpp"
 #include "kernels_genes.hpp"
@@ -831,4 +834,5 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 #include "fit.hpp"        // the model fit and its entry points (after resample.hpp: the gene step is launch_gene_sums)
 #include "presence.hpp"   // the presence test and its entry points (after set_items.hpp: SetItemRunner, query_ok)
 #include "profile.hpp"    // the profile-likelihood intervals and their entry points (after presence.hpp: PresenceRun)
+#include "compare.hpp"    // the two-sample likelihood-ratio test and its entry points (after profile.hpp: PresenceRun, ProfileSearch's style)
 #include "asym.hpp"       // the asymptotic standard errors and their entry points (after fit.hpp: fit_ensure_csr, launch_gene_sums)

@@ -39,6 +39,12 @@
  * --profile-list FILE), the limits of its profile-likelihood interval at --profile-level (0.95) in the units of the FPKM column, the
  * presence test's Lambda and a status word (emsar_hip_profile with the solve's parameters).  The interval is one-sided by itself where the
  * transcript cannot be told from absent, FPKM 0 included.  The other files do not change with it.
+ * --compare (with -M and at least two samples) answers "does this isoform's abundance differ from sample 0": every sample i >= 1 writes
+ * <prefix>.<i>.compare with, per transcript (or per transcript named in --compare-list FILE), its FPKM in sample i and in sample 0, log2 of their
+ * ratio, the likelihood-ratio statistic Lambda of H0: theta_i = r * theta_0 (--compare-ratio r, default 1) with every sibling free in both samples,
+ * its chi2_1 p-value, a status word and the evaluations spent (emsar_hip_compare with the solve's parameters: sample i is A, sample 0 is B).
+ * Sample 0's solver inputs (R, E, den) are kept on the host and uploaded into a second context on each worker's device.  The other files do not
+ * change with it.
  * --asymptotic answers "how sure is this FPKM" without resampling: <prefix>.<i>.asym holds, per transcript, the standard errors of FPKM and
  * TPM from the inverse of the observed information at the .fpkm column (emsar_hip_asymptotic), a status word and the sibling it is most
  * confounded with; with --g2t also <prefix>.<i>.gasym per gene and a usage_sd column.  Transcripts with FPKM <= --boundary-cut (5e-7) are held
@@ -85,8 +91,15 @@ typedef struct {
     int32_t *pres_q; int pres_nq;     /* --presence-list FILE: the tids it names, in file order (NULL = all transcripts) */
     int profile, profile_evals; double profile_level; /* --profile [--profile-level L] [--profile-evals N] */
     int32_t *prof_q; int prof_nq;     /* --profile-list FILE, as --presence-list */
+    int compare; double compare_ratio; /* --compare [--compare-ratio r] */
+    int32_t *cmp_q; int cmp_nq;       /* --compare-list FILE, as --presence-list */
+    struct compare_ref *ref;          /* --compare: sample 0's solver inputs, shared by the workers */
     const emsar_genes *genes;         /* its gene map, read once by main() and shared read-only by the workers */
 } config;
+
+/* --compare: what sample 0 was solved from, published once by the worker that runs it (under the workers' mutex; ready: 0 = not yet,
+ * 1 = the arrays stand, -1 = sample 0 failed before it had them) and read by every other sample */
+typedef struct compare_ref { int ready; int32_t *R; double *E, *den; } compare_ref;
 
 typedef struct {
     config *cfg; const emsar_rsh *rsh;
@@ -103,7 +116,46 @@ typedef struct {
     int *go;              /* start gate: the workers wait until main() knows how many of them exist */
     emsar_aln_opts ao;    /* the job's alignment options, plus this worker's collapse device when --device-collapse */
     struct { emsar_hip_ctx *ctx; pthread_mutex_t mu; } cdev;
+    emsar_hip_ctx *ref_ctx; /* --compare: sample 0 in a second context on this worker's device, made on first use */
 } worker_arg;
+
+/* --compare: sample 0's inputs for the other samples (NULL arrays: it failed) */
+static void publish_ref(worker_arg *w, const emsar_rsh *r, const int32_t *R, const double *E, const double *den) {
+    compare_ref *ref = w->cfg->ref;
+    const size_t nr = (size_t)(r->n_rows > 0 ? r->n_rows : 1), nt = (size_t)(r->n_tx > 0 ? r->n_tx : 1);
+    int32_t *cR = R ? (int32_t *)malloc(nr * 4) : NULL;
+    double *cE = R ? (double *)malloc(nr * 8) : NULL, *cd = R ? (double *)malloc(nt * 8) : NULL;
+    const int ok = cR && cE && cd;
+    if (ok) { memcpy(cR, R, (size_t)r->n_rows * 4); memcpy(cE, E, (size_t)r->n_rows * 8); memcpy(cd, den, (size_t)r->n_tx * 8); }
+    else { free(cR); free(cE); free(cd); cR = NULL; cE = cd = NULL; }
+    pthread_mutex_lock(w->mu);
+    ref->R = cR; ref->E = cE; ref->den = cd; ref->ready = ok ? 1 : -1;
+    pthread_cond_broadcast(w->cv);
+    pthread_mutex_unlock(w->mu);
+}
+
+/* .compare: one line per queried transcript -- tid transcriptID FPKM FPKM_ref log2FC Lambda p status evals; a value that is not finite is
+ * written as "inf", "-inf" or "nan" */
+static void put_num(FILE *f, const char *fmt, double v) {
+    if (isnan(v)) fputs("nan", f); else if (isinf(v)) fputs(v > 0 ? "inf" : "-inf", f); else fprintf(f, fmt, v);
+}
+static int write_compare(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, const emsar_compare_outputs *o) {
+    static const char *const word[5] = {"TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED"};
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "tid\ttranscriptID\tFPKM\tFPKM_ref\tlog2FC\tLambda\tp\tstatus\tevals\n");
+    for (int32_t i = 0; i < n_query; i++) {
+        const int32_t t = query ? query[i] : i;
+        fprintf(f, "%d\t%s\t", t, r->names[t]);
+        put_num(f, "%lf", o->theta_a[i]); fputc('\t', f);
+        put_num(f, "%lf", o->theta_b[i]); fputc('\t', f);
+        put_num(f, "%lf", o->log2fc[i]); fputc('\t', f);
+        put_num(f, "%lf", o->lambda[i]); fputc('\t', f);
+        put_num(f, "%.6g", o->pvalue[i]);
+        fprintf(f, "\t%s\t%d\n", o->status[i] >= 0 && o->status[i] < 5 ? word[o->status[i]] : "?", o->evals[i]);
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
 
 /* emsar_aln_opts.collapse on the GPU (--device-collapse): the parse threads of a worker hand their read-level rows to a context
  * of their own on the worker's device (the solve context is busy with the sample before); one call at a time */
@@ -146,7 +198,7 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
     double *theta = NULL, *rounds = NULL, *mean = NULL, *sd = NULL, *ieuma = NULL, *tpm = NULL, *ir = NULL, *den = NULL; int32_t *iri = NULL;
     double *gcols = NULL, *gsums = NULL;     /* --g2t: [3][n_tx] FPKM, iReadcount, TPM and their [3][n_genes] gene sums */
     double *iso_u = NULL; int32_t *dom = NULL;   /* --isoforms: [n_tx] usage and [n_genes] dominant isoform of the .fpkm column */
-    int rc = parsed->rc;
+    int rc = parsed->rc, published = 0;
     parsed->cnt = NULL;
     snprintf(err, sizeof err, "%s", parsed->err);
     w->parse_s[i] = parsed->secs;
@@ -214,6 +266,7 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         if (l != 0.0) for (uint64_t k = r->row_ptr[c]; k < r->row_ptr[c + 1]; k++) ieuma[r->col_idx[k]] += l;
     }
     w->host_s[i] = w->model_s[i] + (now_s() - t_host);
+    if (cfg->compare && i == 0) { publish_ref(w, r, cnt->R, m->E_solver, den); published = 1; }
     if ((rc = emsar_hip_upload_sample(ctx, cnt->R, m->E_solver, den)) ||
         (rc = emsar_hip_solve(ctx, &p, theta, &w->stats[i]))) {
         fprintf(stderr, "alnfile[%d]: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
@@ -322,6 +375,41 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         free(pv); free(pi);
         if (rc) goto done;
     }
+    /* ---- two-sample test (--compare): this sample (A) against sample 0 (B, in a second context on this device), on the device ---- */
+    if (cfg->compare && i > 0) {
+        compare_ref *ref = cfg->ref;
+        pthread_mutex_lock(w->mu);
+        while (!ref->ready) pthread_cond_wait(w->cv, w->mu);
+        const int have_ref = ref->ready > 0;
+        pthread_mutex_unlock(w->mu);
+        if (!have_ref) { fprintf(stderr, "alnfile[%d]: compare: sample 0 gave no solver inputs\n", i); rc = EMSAR_HOST_ERR_IO; goto done; }
+        if (!w->ref_ctx) {
+            emsar_hip_ctx *rc_ctx = NULL;
+            if ((rc = emsar_hip_create(&rc_ctx, w->device)) || (rc = emsar_hip_set_deterministic(rc_ctx, !cfg->no_deterministic)) ||
+                (rc = emsar_hip_upload_structure(rc_ctx, r->n_rows, r->n_tx, r->row_ptr, r->col_idx, EMSAR_LAYOUT_AUTO)) ||
+                (rc = emsar_hip_upload_sample(rc_ctx, ref->R, ref->E, ref->den))) {
+                fprintf(stderr, "alnfile[%d]: compare: sample 0's context: %s (%s)\n", i, emsar_hip_strerror(rc), rc_ctx ? emsar_hip_last_error(rc_ctx) : "");
+                emsar_hip_destroy(rc_ctx);
+                goto done;
+            }
+            w->ref_ctx = rc_ctx;
+        }
+        const size_t Q = cfg->cmp_q ? (size_t)cfg->cmp_nq : T, Qa = Q > 0 ? Q : 1;
+        double *cv = (double *)malloc(Qa * 8 * 5);
+        int32_t *ci = (int32_t *)malloc(Qa * 4 * 2);
+        const emsar_compare_params cp = {cfg->compare_ratio, 0.0, 0, 0};
+        const emsar_compare_outputs co = {cv, cv ? cv + Q : NULL, cv ? cv + 2 * Q : NULL, cv ? cv + 3 * Q : NULL, cv ? cv + 4 * Q : NULL, NULL, NULL, NULL, NULL,
+                                          ci, ci ? ci + Q : NULL};
+        if (!cv || !ci) rc = EMSAR_HOST_ERR_OOM;
+        else if ((rc = emsar_hip_compare(ctx, w->ref_ctx, &p, &cp, (int32_t)Q, cfg->cmp_q, &co, NULL)))
+            fprintf(stderr, "alnfile[%d]: compare: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+        else {
+            snprintf(path, sizeof path, "%s/%s.%d.compare", cfg->outdir, cfg->prefix, i);
+            if ((rc = write_compare(path, r, (int32_t)Q, cfg->cmp_q, &co))) fprintf(stderr, "can't write %s\n", path);
+        }
+        free(cv); free(ci);
+        if (rc) goto done;
+    }
     /* ---- asymptotic standard errors (--asymptotic): the inverse of the observed information at the printed FPKM, on the device ---- */
     if (cfg->asymptotic) {
         const size_t Ta = T > 0 ? T : 1, Ga = NG > 0 ? NG : 1;
@@ -423,6 +511,7 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         fprintf(stdout, "Complete: %s/%s.%d.fpkm  (EM passes %d, converged %d, solve %.1f ms, logL %.6f)\n", cfg->outdir, cfg->prefix, i,
                 w->stats[i].iters, w->stats[i].converged, w->stats[i].solve_ms, w->stats[i].loglik);
 done:
+    if (cfg->compare && i == 0 && !published) publish_ref(w, r, NULL, NULL, NULL);     /* the other samples must not wait for it */
     free(theta); free(rounds); free(mean); free(sd); free(ieuma); free(tpm); free(ir); free(iri); free(den); free(gcols); free(gsums); free(iso_u); free(dom);
     emsar_counts_free(cnt); emsar_model_free(m);
     return rc;
@@ -464,11 +553,13 @@ static void *worker_main(void *a) {
             pthread_cond_broadcast(w->cv);
             pthread_mutex_unlock(w->mu);
             w->status[i] = rc;
+            if (w->cfg->compare && i == 0) publish_ref(w, w->rsh, NULL, NULL, NULL);
         } else {
             w->status[i] = run_sample(w, ctx, i, cur);
         }
         c ^= 1;
     }
+    emsar_hip_destroy(w->ref_ctx);
     emsar_hip_destroy(ctx);
     if (w->cfg->device_collapse) { emsar_hip_destroy(w->cdev.ctx); pthread_mutex_destroy(&w->cdev.mu); }
     return NULL;
@@ -524,6 +615,12 @@ static void usage(const char *a0) {
             "      --profile-level <l>   with --profile: the confidence level, 0 < l < 1 (default 0.95)\n"
             "      --profile-evals <n>   with --profile: at most n set solves per limit (default 40); a search that needs more is UNCONVERGED\n"
             "      --profile-list <file> with --profile: only the transcripts named in the file, one name per line\n"
+            "      --compare             with -M and at least two samples: every sample i >= 1 also writes <prefix>.<i>.compare: per transcript its FPKM\n"
+            "                            in sample i and in sample 0, log2 of the ratio, the likelihood-ratio statistic Lambda of equal abundance\n"
+            "                            (siblings free in both samples), its p-value, a status word (TESTED, BOTH_ABSENT, OUTSIDE, NOT_RESIDENT,\n"
+            "                            UNCONVERGED) and the evaluations spent\n"
+            "      --compare-ratio <r>   with --compare: test theta_i = r * theta_0 (default 1; a fold change or a size factor)\n"
+            "      --compare-list <file> with --compare: only the transcripts named in the file, one name per line\n"
             "      --asymptotic          also write <prefix>.<i>.asym: per transcript the asymptotic standard error of FPKM and TPM from the inverse of\n"
             "                            the observed information, a status word and the sibling it is most confounded with; with --g2t also\n"
             "                            <prefix>.<i>.gasym (per gene) and a usage_sd column.  Not valid at the boundary (FPKM about 0): use --bootstrap there\n"
@@ -565,7 +662,9 @@ int main(int argc, char **argv) {
     cfg.sub_reps = 10; cfg.sub_seed = 1;
     const char *strand = "ns"; int multisample = 0, gpus = 0, device = 0;
     int dev_map[64], n_dev_map = 0;
-    const char *presence_list = NULL, *profile_list = NULL;
+    const char *presence_list = NULL, *profile_list = NULL, *compare_list = NULL;
+    int compare_ratio_given = 0;
+    compare_ref ref; memset(&ref, 0, sizeof ref);
     int profile_level_given = 0;
     int boundary_cut_given = 0;
     static struct option lo[] = {
@@ -583,6 +682,7 @@ int main(int argc, char **argv) {
         {"asymptotic", no_argument, 0, 1023}, {"boundary-cut", required_argument, 0, 1024},
         {"profile", no_argument, 0, 1025}, {"profile-level", required_argument, 0, 1026}, {"profile-list", required_argument, 0, 1027},
         {"profile-evals", required_argument, 0, 1028},
+        {"compare", no_argument, 0, 1029}, {"compare-ratio", required_argument, 0, 1030}, {"compare-list", required_argument, 0, 1031},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
@@ -683,6 +783,9 @@ int main(int argc, char **argv) {
             case 1026: cfg.profile_level = atof(optarg); profile_level_given = 1; break;
             case 1027: profile_list = optarg; break;
             case 1028: cfg.profile_evals = atoi(optarg); if (cfg.profile_evals <= 0) { fprintf(stderr, "--profile-evals must be positive.\n"); return 1; } break;
+            case 1029: cfg.compare = 1; break;
+            case 1030: cfg.compare_ratio = atof(optarg); compare_ratio_given = 1; break;
+            case 1031: compare_list = optarg; break;
             case 1009: {
                 const char *q = optarg;
                 while (*q && n_dev_map < 64) {
@@ -711,6 +814,11 @@ int main(int argc, char **argv) {
     }
     if (profile_level_given && !(cfg.profile_level > 0.0 && cfg.profile_level < 1.0)) { fprintf(stderr, "--profile-level must lie in (0, 1).\n"); return 1; }
     if (!profile_level_given) cfg.profile_level = 0.95;
+    if ((compare_list || compare_ratio_given) && !cfg.compare) { fprintf(stderr, "--compare-list and --compare-ratio need --compare.\n"); return 1; }
+    if (compare_ratio_given && !(cfg.compare_ratio > 0.0 && isfinite(cfg.compare_ratio))) { fprintf(stderr, "--compare-ratio must be positive.\n"); return 1; }
+    if (!compare_ratio_given) cfg.compare_ratio = 1.0;
+    if (cfg.compare && !multisample) { fprintf(stderr, "--compare needs -M and at least two samples.\n"); usage(argv[0]); return 1; }
+    cfg.ref = &ref;
     if (!cfg.rsh_path || optind + 2 >= argc) { usage(argv[0]); return 1; }
     if (emsar_set_strand(strand, cfg.ao.pe, &cfg.ao.strand)) { fprintf(stderr, "error: invalid strand type.\n"); return 1; }
     cfg.outdir = argv[optind]; cfg.prefix = argv[optind + 1];
@@ -731,6 +839,7 @@ int main(int argc, char **argv) {
         fclose(f);
         if (!n_list) { fprintf(stderr, "No alignment files in the alignment list\n"); return 1; }
     }
+    if (cfg.compare && n_list < 2) { fprintf(stderr, "--compare needs -M and at least two samples.\n"); usage(argv[0]); return 1; }
     cfg.aln = list; cfg.n_aln = n_list;
     /* the reference runs `mkdir -p outdir` (emsar_main.c:284-285); find out now, not after the solve, that it cannot be written */
     {
@@ -773,6 +882,7 @@ int main(int argc, char **argv) {
     /* before any sample: an unknown name ends the run here */
     if (presence_list && read_name_list("presence", presence_list, rsh, &cfg.pres_q, &cfg.pres_nq)) { emsar_rsh_free(rsh); return 1; }
     if (profile_list && read_name_list("profile", profile_list, rsh, &cfg.prof_q, &cfg.prof_nq)) { emsar_rsh_free(rsh); return 1; }
+    if (compare_list && read_name_list("compare", compare_list, rsh, &cfg.cmp_q, &cfg.cmp_nq)) { emsar_rsh_free(rsh); return 1; }
     emsar_genes *genes = NULL;
     if (cfg.g2t) {                             /* before any sample: a bad gene map ends the run here */
         if (emsar_genes_read(rsh, cfg.g2t, &genes, err, sizeof err)) { fprintf(stderr, "%s\n", err); emsar_rsh_free(rsh); return 1; }
@@ -817,7 +927,7 @@ int main(int argc, char **argv) {
     int go = 0, n_started = 1;
     for (int g = 0; g < n_workers; g++)
         wa[g] = (worker_arg){&cfg, rsh, multisample ? dev_map[g] : device, n_workers, g, &mu, &cv, &next_model, &eumacut, status, stats, bstats, sstats, qstats, parse_s,
-                             model_s, host_s, &go, cfg.ao, {NULL, PTHREAD_MUTEX_INITIALIZER}};
+                             model_s, host_s, &go, cfg.ao, {NULL, PTHREAD_MUTEX_INITIALIZER}, NULL};
     for (int g = 1; g < n_workers; g++) {
         if (pthread_create(&th[g], NULL, worker_main, &wa[g]) != 0) { fprintf(stderr, "warning: worker %d could not be started, using %d\n", g, g); break; }
         n_started++;
@@ -875,7 +985,7 @@ int main(int argc, char **argv) {
     }
     emsar_rsh_free(rsh);
     emsar_genes_free(genes);
-    free(cfg.pres_q); free(cfg.prof_q);
+    free(cfg.pres_q); free(cfg.prof_q); free(cfg.cmp_q); free(ref.R); free(ref.E); free(ref.den);
     for (int i = 0; i < n_list; i++) free(list[i]);
     free(list); free(status); free(stats); free(bstats); free(sstats); free(qstats); free(parse_s); free(model_s); free(host_s); free(wa); free(th);
     return bad ? 1 : 0;

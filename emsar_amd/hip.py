@@ -28,6 +28,7 @@ SYMBOLS = [
     "emsar_hip_model_fit", "emsar_hip_model_fit_host",
     "emsar_hip_presence", "emsar_hip_presence_pvalue_host",
     "emsar_hip_profile", "emsar_hip_profile_cut_host",
+    "emsar_hip_compare", "emsar_hip_compare_pvalue_host",
     "emsar_hip_asymptotic", "emsar_hip_asymptotic_host",
 ]
 
@@ -36,6 +37,10 @@ PRESENCE_STATUS = ("TESTED", "ABSENT", "ESSENTIAL", "OUTSIDE", "NOT_RESIDENT", "
 
 # status of a transcript's profile-likelihood interval (include/emsar_hip.h "profile-likelihood intervals"), by value
 PROFILE_STATUS = ("TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED")
+
+# status of a transcript in the two-sample test (include/emsar_hip.h "two-sample test"), by value
+COMPARE_STATUS = ("TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED")
+COMPARE_OUTPUTS = ("lambda", "pvalue", "log2fc", "theta_a", "theta_b", "theta_null", "multiplier", "gap", "raw_lambda")
 
 # status of a transcript in the asymptotic standard errors (include/emsar_hip.h "asymptotic standard errors"), by value
 ASYM_STATUS = ("ESTIMATED", "BOUNDARY", "UNIDENTIFIABLE", "TOO_LARGE", "INFEASIBLE")
@@ -149,6 +154,26 @@ class ProfileStats(C.Structure):
         return d
 
 
+class CompareParams(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("dev_tol", C.c_double), ("max_evals", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class CompareOutputs(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in ("lambda_", "pvalue", "log2fc", "theta_a", "theta_b", "theta_null", "multiplier", "gap",
+                                                     "raw_lambda")] + [("status", C.POINTER(C.c_int32)), ("evals", C.POINTER(C.c_int32))]
+
+
+class CompareStats(C.Structure):
+    _fields_ = [("n_status", C.c_int64 * 5), ("items_launched", C.c_int64), ("evals_sum", C.c_int64), ("passes_sum", C.c_int64),
+                ("evals_max", C.c_int32), ("passes_max", C.c_int32), ("min_raw_lambda", C.c_double), ("device_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["n_status"] = dict(zip(COMPARE_STATUS, d["n_status"]))
+        return d
+
+
 class AsymParams(C.Structure):
     _fields_ = [("boundary_cut", C.c_double), ("pivot_tol", C.c_double), ("block_tid", C.c_int32), ("reserved0", C.c_int32)]
 
@@ -251,6 +276,9 @@ def load_library():
     L.emsar_hip_profile.argtypes = [vp, C.POINTER(EmParams), C.POINTER(ProfileParams), C.c_int32, i32p, C.POINTER(ProfileOutputs),
                                     C.POINTER(ProfileStats)]
     L.emsar_hip_profile_cut_host.argtypes = [C.c_double, f64p]
+    L.emsar_hip_compare.argtypes = [vp, vp, C.POINTER(EmParams), C.POINTER(CompareParams), C.c_int32, i32p, C.POINTER(CompareOutputs),
+                                    C.POINTER(CompareStats)]
+    L.emsar_hip_compare_pvalue_host.argtypes = [C.c_int64, f64p, f64p]
     L.emsar_hip_asymptotic.argtypes = [vp, f64p, C.POINTER(AsymParams), C.POINTER(AsymOutputs), C.POINTER(AsymStats)]
     L.emsar_hip_asymptotic_host.argtypes = [C.c_int64, C.c_int32, u64p, i32p, i32p, f64p, f64p, C.c_int32, i32p, C.POINTER(AsymParams),
                                             C.POINTER(AsymOutputs), C.POINTER(AsymStats)]
@@ -454,6 +482,33 @@ def presence_pvalue_host(lam):
         raise EmsarHipError(rc, "presence_pvalue_host")
     out = out[:x.size].reshape(x.shape)
     return float(out[0]) if np.ndim(lam) == 0 else out
+
+
+def compare_pvalue_host(lam):
+    """Host-only: the two-sample test's p-value of the statistic Lambda under chi2 with one degree of freedom (include/emsar_hip.h
+    "two-sample test"): 1 for Lambda <= 0, erfc(sqrt(Lambda / 2)) above, 0 for +inf, NaN for NaN.  A scalar or an array; no GPU needed."""
+    L = load_library()
+    x = np.ascontiguousarray(np.atleast_1d(np.asarray(lam, dtype=np.float64)))
+    out = np.zeros(max(x.size, 1))
+    rc = L.emsar_hip_compare_pvalue_host(x.size, _p(x.reshape(-1), C.c_double), _p(out, C.c_double))
+    if rc != 0:
+        raise EmsarHipError(rc, "compare_pvalue_host")
+    out = out[:x.size].reshape(x.shape)
+    return float(out[0]) if np.ndim(lam) == 0 else out
+
+
+def debug_compare_closed(u_a, den_a, u_b, den_b, ratio=1.0, dev_tol=0.0, max_evals=0):
+    """Host-only diagnostic: what compare() gives a transcript that is a one-transcript component in both samples (u reads, den each):
+    the multiplier search as the host runs it for such pairs (no GPU needed).  Returns a dict of scalars keyed like compare()'s arrays."""
+    f = load_library().emsar_hip_debug_compare_closed       # not declared in the header: bound here, not in load_library
+    f.argtypes = [C.c_double] * 4 + [C.POINTER(CompareParams), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    cp, vals, status, evals = CompareParams(float(ratio), float(dev_tol), int(max_evals), 0), (C.c_double * 9)(), C.c_int32(), C.c_int32()
+    rc = f(float(u_a), float(den_a), float(u_b), float(den_b), C.byref(cp), vals, C.byref(status), C.byref(evals))
+    if rc != 0:
+        raise EmsarHipError(rc, "debug_compare_closed")
+    out = dict(zip(COMPARE_OUTPUTS, list(vals)))
+    out.update(status=status.value, evals=evals.value)
+    return out
 
 
 def profile_cut_host(level):
@@ -733,6 +788,28 @@ class EmsarHip:
                            _p(res["status"], C.c_int32), _p(res["evals"], C.c_int32))
         st = ProfileStats()
         self._chk(self._L.emsar_hip_profile(self._h, C.byref(p), C.byref(pp), nq, _p(q, C.c_int32), C.byref(o), C.byref(st)), "profile")
+        out = {k: v[:nq] for k, v in res.items()}
+        out["stats"] = st
+        return out
+
+    def compare(self, other, query=None, ratio=1.0, dev_tol=0.0, max_evals=0, max_iter=100000, accel=1, tol=1e-10, abs_floor=1e-6, check_every=8,
+                count_floor=0.0, set_mode=0, zero_cut=0.0, abs_step=0.0, newton_after=0):
+        """Two-sample likelihood-ratio test of each queried transcript (include/emsar_hip.h "two-sample test"): this context holds sample
+        A, `other` -- a second context on the same device with the same structure -- sample B; H0: theta_t^A = ratio * theta_t^B with
+        every other transcript free in both samples.  query: tids in any order, repeats allowed, None = all transcripts; dev_tol,
+        max_evals 0 = the defaults (1e-4, 40); the solver parameters are those of solve().  Returns a dict of arrays in query order:
+        lambda, pvalue, log2fc, theta_a, theta_b, theta_null, multiplier, gap, raw_lambda, status (index into COMPARE_STATUS), evals, and
+        stats.  After upload_sample on both; both contexts are left as they were."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        cp = CompareParams(float(ratio), float(dev_tol), int(max_evals), 0)
+        q = None if query is None else np.ascontiguousarray(np.asarray(query, dtype=np.int32).reshape(-1))
+        nq = self.n_tx if q is None else len(q)
+        res = {k: np.zeros(max(nq, 1)) for k in COMPARE_OUTPUTS}
+        res.update({k: np.zeros(max(nq, 1), dtype=np.int32) for k in ("status", "evals")})
+        o = CompareOutputs(*[_p(res[k], C.c_double) for k in COMPARE_OUTPUTS], _p(res["status"], C.c_int32), _p(res["evals"], C.c_int32))
+        st = CompareStats()
+        self._chk(self._L.emsar_hip_compare(self._h, getattr(other, "_h", None), C.byref(p), C.byref(cp), nq, _p(q, C.c_int32), C.byref(o), C.byref(st)),
+                  "compare")
         out = {k: v[:nq] for k, v in res.items()}
         out["stats"] = st
         return out

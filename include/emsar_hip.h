@@ -535,6 +535,79 @@ int emsar_hip_profile(emsar_hip_ctx *ctx, const emsar_em_params *p, const emsar_
                       emsar_profile_stats *stats /* or NULL */);
 int emsar_hip_profile_cut_host(double level, double *cut_out);
 
+/* ---- two-sample test: does a transcript's abundance differ between two samples? -------------------
+ * Two contexts on the same device hold the same structure (n_rows, n_tx, nnz, row_ptr and col_idx equal; compared on the host copies the
+ * contexts keep, nothing is uploaded for the check) and each its own sample: A in ctx_a, B in ctx_b.  For transcript t, solver
+ * parameters p and ratio r (0 means 1), with s_A / s_B the packed connected sets of t in A / B (set_mode 0) -- they may differ and lie
+ * in different size classes, because sets depend on which rows carry reads -- and F_s as the presence test defines it:
+ *     H1           theta^A, theta^B free:                     F1 = F_sA(theta_hat^A) + F_sB(theta_hat^B)
+ *     H0           theta_t^A = r * theta_t^B, all else free:  F0 = the maximum of F_sA + F_sB under that constraint
+ *     Lambda_t     = 2 (F1 - F0) >= 0,  p_t = erfc(sqrt(Lambda_t / 2)), chi2 with 1 degree of freedom.  The siblings of t stay free in
+ *                  both samples, so reads that merely move to a sibling do not count as a difference.  THE P-VALUE IS CONSERVATIVE WHEN
+ *                  ONE ESTIMATE SITS ON THE BOUNDARY (theta_hat_t = 0 in one sample): the statistic is then stochastically smaller
+ *                  than chi2_1.  E carries each sample's read total, so theta is depth-normalised; r != 1 tests against a fold change
+ *                  or applies a size factor.
+ *     path         for a multiplier lambda the dual L(lambda) = max [F_sA - lambda theta_t^A] + max [F_sB + r lambda theta_t^B] is two
+ *                  independent set problems: den_tA replaced by den_tA + lambda (scale_A = 1 + lambda / den_tA), den_tB by
+ *                  den_tB - r lambda (scale_B = 1 - r lambda / den_tB), lambda in (-den_tA, den_tB / r).  Each is one solve of the set
+ *                  with the scaled den_t in LDS -- same solver, same start, same stopping rule as solve, F summed with the ORIGINAL
+ *                  den_t, as the profile intervals do.  With x_A, x_B the two values of t: g(lambda) = x_A - r x_B falls in lambda and has
+ *                  one root lambda*; L(lambda) = F_A + F_B - lambda g(lambda) >= F0 for every lambda, with equality at lambda*.
+ *     search       one workgroup runs it.  Evaluation 0 is lambda = 0 and gives theta_hat_tA, theta_hat_tB and F1 from the code path of
+ *                  every later evaluation; g(0) == 0 exactly ends it with Lambda = 0.0, evals = 1.  Otherwise the root lies on the side
+ *                  of sign g(0): lambda = v * lambda_end, v in [0, 1), lambda_end = den_tB / r or -den_tA; Illinois steps with a
+ *                  midpoint safeguard on h = (x_A - r x_B) / (x_A + r x_B), h(1) = -+1 known without a solve.  It stops when
+ *                  2 |lambda g(lambda)| <= dev_tol (<= 0: 1e-4, absolute, on the chi-square scale), or when
+ *                  2 |g(lambda)| * (the width of the bracket in lambda) <= dev_tol -- L is convex with slope -g and the root lies in
+ *                  the bracket, so the dual value cannot fall further than that; this is the rule that ends a search whose root is the
+ *                  end of the range itself (t has no read to its name in the sample that would have to grow: x stays 0 there) --, or
+ *                  after max_evals evaluations (<= 0: 40; then UNCONVERGED); an evaluation is one solve per sample.
+ *     lambda       the dual value max(0, 2 (F1 - L(lambda_last))): a lower bound of the statistic at every lambda, stationary at
+ *                  lambda*, so its error is of second order in the gap; the stopping quantity is the distance between the primal and
+ *                  the dual value.  raw_lambda is the value before clamping, gap = g(lambda_last), multiplier = lambda_last,
+ *                  theta_null = the last x_A (the common value under H0, on A's scale)
+ *     log2fc       log2(theta_hat_A / (r theta_hat_B)); +-inf when exactly one estimate is 0, NaN when both are
+ *     closed form  a one-transcript component of either sample has x = u / den', F = u log x - x den (u = 0: x = 0); the kernel takes
+ *                  it in place of a set.  When both samples' components are closed form the host runs the same search and nothing is
+ *                  launched.
+ * status, per transcript:
+ *     TESTED        outputs as above
+ *     BOTH_ABSENT   theta_hat_t is exactly 0 in both samples: Lambda 0, p 1, evals 1
+ *     OUTSIDE       den_t == 0 in either sample.  Every numeric output NaN (evals 0)
+ *     NOT_RESIDENT  t lies in a streamed or a cluster set in either sample, one component holds most transcripts, or set_mode = 1.
+ *                   Every numeric output NaN (evals 0)
+ *     UNCONVERGED   values are given, but a solve hit max_iter or the search hit max_evals
+ * Outputs are indexed by query position (by tid when query_tids is NULL; n_query is then ignored); repeats and any order are allowed.  A
+ * transcript's result depends on its two sets, itself, p and cp alone -- not on what else is asked, the batch, the layout, MERGE_ROWS
+ * or the library's numbering.  Both contexts are left as they were: a following solve, presence or profile on either returns the same
+ * bits.  ERR_STATE when either context is before upload_sample; ERR_ARG for a NULL context, the same context twice, different devices
+ * or structures, a tid outside 0 .. n_tx-1, n_query < 0, a ratio or dev_tol that is not finite, a negative ratio and the parameters
+ * solve rejects; ERR_NUMERIC for a non-finite F at lambda = 0.  EMSAR_HIP_COMPARE_BATCH = items per launch and class (a testing aid;
+ * the bits do not change).  compare_pvalue_host: 1 for Lambda <= 0, erfc(sqrt(Lambda / 2)) above, 0 for +inf, NaN for NaN; no HIP call. */
+enum {
+    EMSAR_COMPARE_TESTED = 0, EMSAR_COMPARE_BOTH_ABSENT = 1, EMSAR_COMPARE_OUTSIDE = 2, EMSAR_COMPARE_NOT_RESIDENT = 3,
+    EMSAR_COMPARE_UNCONVERGED = 4
+};
+typedef struct { double ratio, dev_tol; int32_t max_evals, reserved0; } emsar_compare_params;      /* NULL: ratio 1 and the defaults */
+typedef struct {
+    double  *lambda, *pvalue, *log2fc, *theta_a, *theta_b, *theta_null, *multiplier, *gap, *raw_lambda;    /* [n_query]; may each be NULL */
+    int32_t *status, *evals;                                                /* [n_query] EMSAR_COMPARE_*; evaluations of the search */
+} emsar_compare_outputs;
+typedef struct {
+    int64_t n_status[5];          /* distinct queried transcripts per status */
+    int64_t items_launched;       /* workgroups: one search each */
+    int64_t evals_sum;            /* evaluations summed over the searches on the device */
+    int64_t passes_sum;           /* passes summed over their solves, both samples */
+    int32_t evals_max, passes_max; /* the search with the most evaluations / the most passes */
+    double  min_raw_lambda;       /* the most negative Lambda before clamping, 0 if none was negative */
+    double  device_ms;            /* device time of the searches (HIP events) */
+    double  total_ms;             /* wall time of the call, a first call's set building included */
+} emsar_compare_stats;
+int emsar_hip_compare(emsar_hip_ctx *ctx_a, emsar_hip_ctx *ctx_b, const emsar_em_params *p, const emsar_compare_params *cp /* or NULL */,
+                      int32_t n_query, const int32_t *query_tids /* NULL = all transcripts */, const emsar_compare_outputs *out /* or NULL */,
+                      emsar_compare_stats *stats /* or NULL */);
+int emsar_hip_compare_pvalue_host(int64_t n, const double *lambda, double *p_out);
+
 /* ---- asymptotic standard errors: the inverse of the observed information at the MLE ---------------
  * How sure is theta_t, without resampling?  For a theta that maximises the likelihood of the current sample, the observed information
  * of the ACTIVE transcripts is J_ij = sum_c m_ci m_cj R_c / S_c^2 (m_ci = how often i stands in row c); its inverse is the asymptotic

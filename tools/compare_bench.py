@@ -1,0 +1,73 @@
+"""Cost of the two-sample test (emsar_hip_compare) on bench.py's time_to_mle segment problem against one solve; prints one JSON object.
+
+    python tools/compare_bench.py [--rounds 3] [--max-iter 20000] [--max-evals 40] [--seed 5] [--out FILE]
+
+Sample A is the problem as it stands (same seeds, 100 k transcripts in families); sample B is a Poisson redraw of A's row weights (a
+technical replicate: the null holds for every transcript).  Both are uploaded into contexts of their own and solved once (the first
+solve finds and packs the sets); then every transcript is compared, --rounds times.  Reported: wall and device ms of the best call (HIP
+events around the searches), transcripts per status, evaluations per search (mean, max), the wall time of one solve of A in the same
+process and the ratio, the share of TESTED transcripts with p < 0.05 (about 0.05 or less under the null), and whether a solve after
+the calls returns the bits it returned before."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--max-iter", type=int, default=20000)
+    ap.add_argument("--max-evals", type=int, default=40)
+    ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    from boot_bench import segment_problem
+    from emsar_amd import EmsarHip
+    n_tx, rp, ci, R, E = segment_problem()
+    RB = np.random.default_rng(a.seed).poisson(R).astype(np.int32)
+    solve = dict(max_iter=a.max_iter, tol=1e-10)
+    out = {"n_tx": int(n_tx), "rows": int(len(rp) - 1), "max_iter": a.max_iter, "max_evals": a.max_evals, "seed": a.seed}
+    with EmsarHip(0) as A, EmsarHip(0) as B:
+        for dev, w in ((A, R), (B, RB)):
+            dev.upload_structure(n_tx, rp, ci)
+            dev.upload_sample(w, E, None)
+        th, _ = A.solve(**solve)                             # finds and packs the sets, warms up
+        B.solve(**solve)
+        solves = []
+        for _ in range(a.rounds):
+            t0 = time.perf_counter()
+            A.solve(**solve)
+            solves.append(time.perf_counter() - t0)
+        runs = []
+        for _ in range(a.rounds):
+            t0 = time.perf_counter()
+            r = A.compare(B, max_evals=a.max_evals, **solve)
+            d = r["stats"].as_dict()
+            d["wall_s"] = time.perf_counter() - t0
+            runs.append(d)
+        best = min(runs, key=lambda d: d["wall_s"])
+        tested = r["status"] == 0
+        out.update(runs=runs, status=best["n_status"], items_launched=best["items_launched"], wall_ms=1e3 * best["wall_s"],
+                   device_ms=best["device_ms"], evals_per_item_mean=best["evals_sum"] / max(1, best["items_launched"]),
+                   evals_max=best["evals_max"], passes_max=best["passes_max"], min_raw_lambda=best["min_raw_lambda"],
+                   solve_wall_ms=1e3 * min(solves), wall_over_solve=best["wall_s"] / min(solves),
+                   share_p_below_0_05=float(np.mean(r["pvalue"][tested] < 0.05)) if tested.any() else None)
+        th2, _ = A.solve(**solve)
+        out["solve_unchanged"] = bool(th2.tobytes() == th.tobytes())
+    txt = json.dumps(out, indent=1)
+    print(txt)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(txt + "\n")
+
+
+if __name__ == "__main__":
+    main()
