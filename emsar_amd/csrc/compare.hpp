@@ -1,11 +1,12 @@
 // compare.hpp -- the two-sample likelihood-ratio test behind include/emsar_hip.h: emsar_hip_compare (device) and
-// emsar_hip_compare_pvalue_host (no HIP call).  Part of emsar_hip.hip's translation unit, included after profile.hpp: the first stages of
-// each sample ARE the presence test's (PresenceRun: plan, classify), k_compare_sets (kernels_compare.hpp) runs the searches.
-// One call = one CompareRun:  plan, classify   PresenceRun's stages on the same query, once per context: the sets of both samples are found
+// emsar_hip_compare_pvalue_host (no HIP call).  Part of emsar_hip.hip's translation unit, included after profile.hpp: each sample's
+// queried transcripts are located as the presence test's are (SetQuery, set_items.hpp), k_compare_sets (kernels_compare.hpp) runs the
+// searches.
+// One call = one CompareRun:  plan, classify   SetQuery's stages on the same query, once per context: the sets of both samples are found
 //                                              on first use, every queried transcript is located in each
 //                             pair             per transcript: outside / not resident / both closed form (searched on the host) / one item
 //                                              in the launch class of the larger of its two sets
-//                             search           the items in batches across the three launch classes (PairItemRunner)
+//                             search           the items in batches across the three launch classes (SetItemRunner)
 //                             reduce           records -> Lambda, p, log2fc, status;  copy_out in query order
 // One workgroup runs one search of at most max_evals evaluations of two solves of at most max_iter passes each.  Neither context's
 // theta, weights or scales are touched.  The launches run on ctx_a's streams; ctx_b's stream is drained before.
@@ -25,41 +26,16 @@ inline double compare_pvalue(double lambda) {
     return std::erfc(std::sqrt(lambda / 2.0));
 }
 
-// the search of k_compare_sets on a pair of one-transcript components: the same steps, the same stopping rule, the same record
+// the search of k_compare_sets (CompareStep) on a pair of one-transcript components, compare_closed_form as its evaluation
 inline CompareRec compare_closed_pair(double u_a, double den_a, double u_b, double den_b, const CompareSearchParams &Q) {
-    const double r = Q.ratio;
-    CompareSearch S;
-    ComparePoint pt;
-    pt.lambda = 0.0; pt.scale_a = 1.0; pt.scale_b = 1.0;
-    bool up = false;
-    int evals = 0, search_ok = 0;
-    double x0_a = 0.0, x0_b = 0.0, F0_a = 0.0, F0_b = 0.0, x_a = 0.0, x_b = 0.0, F_a = 0.0, F_b = 0.0;
-    for (;;) {
-        compare_closed_form(u_a, den_a, pt.scale_a, x_a, F_a);
-        compare_closed_form(u_b, den_b, pt.scale_b, x_b, F_b);
-        evals++;
-        const double g = x_a - r * x_b;
-        if (evals == 1) {
-            x0_a = x_a; x0_b = x_b; F0_a = F_a; F0_b = F_b;
-            if (!(F_a - F_a == 0.0) || !(F_b - F_b == 0.0)) break;
-            if (g == 0.0) { search_ok = 1; break; }
-            up = g > 0.0;
-        }
-        if (!(g - g == 0.0) || !(F_a - F_a == 0.0) || !(F_b - F_b == 0.0)) break;
-        if (evals > 1 && 2.0 * std::fabs(pt.lambda * g) <= Q.dev_tol) { search_ok = 1; break; }
-        const double h = g / (x_a + r * x_b);
-        if (evals == 1) S.start(h); else S.update(h);
-        // the root lies in the bracket and L is convex with slope -g: the dual value cannot fall further than |g| times the bracket
-        if (2.0 * std::fabs(g) * ((S.v_hi - S.v_lo) * ComparePoint::end(up, r, den_a, den_b)) <= Q.dev_tol) { search_ok = 1; break; }
-        if (evals >= Q.max_evals) break;
-        pt.at(S.v, up, r, den_a, den_b);
-    }
-    CompareRec o;
-    o.lambda_mult = pt.lambda; o.x_a = x_a; o.x_b = x_b; o.x0_a = x0_a; o.x0_b = x0_b;
-    o.FhatA = F0_a; o.FhatB = F0_b; o.FA = F_a; o.FB = F_b;
-    o.evals = evals; o.passes = 0; o.flags = (search_ok ? COMPARE_REC_SEARCH_OK : 0) | COMPARE_REC_SOLVES_OK;
-    o.infeasible = 0;
-    return o;
+    CompareStep T;
+    T.start();
+    double x_a, F_a, x_b, F_b;
+    do {
+        compare_closed_form(u_a, den_a, T.pt.scale_a, x_a, F_a);
+        compare_closed_form(u_b, den_b, T.pt.scale_b, x_b, F_b);
+    } while (T.step(x_a, F_a, x_b, F_b, den_a, den_b, Q));
+    return T.record(0, 1, 0);
 }
 
 // what one queried transcript is given
@@ -84,96 +60,21 @@ inline bool compare_reduce(const CompareRec &r, double ratio, CompareResult &o) 
     return true;
 }
 
-// SetItemRunner's sibling for items that name a set in each of two contexts: items[c] run in launch class c (the larger of the item's
-// two size classes) on the streams of `ctx`, at most a batch per class and launch; recs[c][i] answers items[c][i].  Every item's two
-// sets are checked against their own context's descriptors before anything is launched.
-struct PairItemRunner {
-    emsar_hip_ctx *const ctx;            // ctx_a: its streams and events carry the launches
-    const emsar_hip_ctx *const other;    // ctx_b
-    DevBuf<CompareItem> d_items[emsar::kSetClasses];
-    DevBuf<CompareRec> d_rec[emsar::kSetClasses];
-    hipEvent_t e[2] = {nullptr, nullptr};
-
-    PairItemRunner(emsar_hip_ctx *a, const emsar_hip_ctx *b) : ctx(a), other(b) {}
-    ~PairItemRunner() { for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev); }
-
-    // a side of an item: a one-transcript component (set -1), or transcript t of set `set` of class cls <= the launch class
-    static bool side_ok(const emsar_hip_ctx *c, int launch_cls, int32_t cls, int32_t set, int32_t t, double den) {
-        if (!(den > 0.0)) return false;
-        if (set == -1) return true;
-        if (cls < 0 || cls > launch_cls || set < 0) return false;
-        const auto &desc = c->sets.RS.desc[cls];
-        return (size_t)set < desc.size() && t >= 0 && t < (int32_t)desc[(size_t)set].n_t;
-    }
-
-    template <class Launch>
-    int run(const std::vector<CompareItem> (&items)[emsar::kSetClasses], std::vector<CompareRec> (&recs)[emsar::kSetClasses], double &ms_acc,
-            int64_t &launched, const Launch &launch) {
-        size_t most = 0;
-        for (int c = 0; c < emsar::kSetClasses; c++) {
-            for (const CompareItem &it : items[c])
-                if (!side_ok(ctx, c, it.cls_a, it.set_a, it.t_a, it.den_a) || !side_ok(other, c, it.cls_b, it.set_b, it.t_b, it.den_b) ||
-                    std::max(it.set_a < 0 ? -1 : it.cls_a, it.set_b < 0 ? -1 : it.cls_b) != c) {
-                    ctx->err = "compare: an item lies outside its class's sets";
-                    return EMSAR_HIP_ERR_HIP;
-                }
-            recs[c].resize(items[c].size());
-            most = std::max(most, items[c].size());
-        }
-        if (most == 0) return EMSAR_HIP_OK;
-        const size_t batch = (size_t)item_batch((int64_t)(emsar::kSetClasses * (sizeof(CompareItem) + sizeof(CompareRec))), "EMSAR_HIP_COMPARE_BATCH",
-                                                (int64_t)most, (int64_t)1 << 20);
-        for (int c = 0; c < emsar::kSetClasses; c++)
-            if (!items[c].empty()) {
-                const size_t cnt = std::min(batch, items[c].size());
-                HIPCHK(d_items[c].alloc(cnt)); HIPCHK(d_rec[c].alloc(cnt));
-            }
-        for (hipEvent_t &ev : e) if (!ev) HIPCHK(hipEventCreate(&ev));
-        const hipStream_t st[emsar::kSetClasses] = {ctx->stream, ctx->side[0], ctx->side[1]};
-        for (size_t first = 0; first < most; first += batch) {
-            size_t cnt[emsar::kSetClasses];
-            for (int c = 0; c < emsar::kSetClasses; c++) {
-                cnt[c] = items[c].size() > first ? std::min(batch, items[c].size() - first) : 0;
-                if (cnt[c]) HIPCHK(hipMemcpyAsync(d_items[c], items[c].data() + first, cnt[c] * sizeof(CompareItem), hipMemcpyHostToDevice, ctx->stream));
-            }
-            HIPCHK(hipEventRecord(e[0], ctx->stream));
-            if (const int rc = fork_side_streams(ctx, 2)) return rc;
-            for (int c = emsar::kSetClasses - 1; c >= 0; c--) if (cnt[c]) launch(c, emsar::kSetThreads[c], st[c], cnt[c], d_items[c].get(), d_rec[c].get());
-            for (int i = 0; i < 2; i++) {
-                HIPCHK(hipEventRecord(ctx->ev_join[i], ctx->side[i]));
-                HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
-            }
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(e[1], ctx->stream));
-            for (int c = 0; c < emsar::kSetClasses; c++)
-                if (cnt[c]) HIPCHK(hipMemcpyAsync(recs[c].data() + first, d_rec[c], cnt[c] * sizeof(CompareRec), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, e[0], e[1]));
-            ms_acc += ms;
-            for (int c = 0; c < emsar::kSetClasses; c++) launched += (int64_t)cnt[c];
-        }
-        return EMSAR_HIP_OK;
-    }
-};
-
 struct CompareRun {
-    using Result = CompareResult;        // per queried transcript (PresenceRun::cand of both samples, same index)
-    emsar_hip_ctx *const ctx;            // ctx_a
+    using Result = CompareResult;        // per queried transcript (SetQuery::cand of both samples, same index)
+    emsar_hip_ctx *const ctx;            // ctx_a: its streams and events carry the launches
     emsar_hip_ctx *const ctx_b;
-    PresenceRun pa, pb;
-    const int32_t nq;
-    const int32_t *const query;
+    SetQuery qa, qb;                     // where every queried transcript stands in each sample
     const emsar_compare_outputs out;     // a copy: all NULL when the caller gave none
     CompareSearchParams Q;
     std::vector<Result> res;
-    PairItemRunner runner;
+    SetItemRunner<CompareItem, CompareRec> runner;
     emsar_compare_stats st{};
 
-    CompareRun(emsar_hip_ctx *a, emsar_hip_ctx *b, const emsar_em_params *p, const emsar_compare_params &cp, int32_t nq_, const int32_t *q,
+    CompareRun(emsar_hip_ctx *a, emsar_hip_ctx *b, const emsar_em_params *p, const emsar_compare_params &cp, int32_t nq, const int32_t *query,
                const emsar_compare_outputs *o)
-        : ctx(a), ctx_b(b), pa(a, p, nq_, q, nullptr, "EMSAR_HIP_COMPARE_BATCH"), pb(b, p, nq_, q, nullptr, "EMSAR_HIP_COMPARE_BATCH"), nq(nq_), query(q),
-          out(o ? *o : emsar_compare_outputs{}), runner(a, b) {
+        : ctx(a), ctx_b(b), qa(a, p, nq, query), qb(b, p, nq, query), out(o ? *o : emsar_compare_outputs{}),
+          runner(a, "EMSAR_HIP_COMPARE_BATCH", "compare: an item lies outside its class's sets") {
         Q = CompareSearchParams{cp.ratio == 0.0 ? 1.0 : cp.ratio, cp.dev_tol > 0.0 ? cp.dev_tol : 1e-4, cp.max_evals > 0 ? cp.max_evals : 40, 0};
     }
 
@@ -183,6 +84,17 @@ struct CompareRun {
                            D.d_srp.get(), D.d_sent.get(), D.d_scp.get(), D.d_scrow.get(), c->vec.d_den.get()};
     }
 
+    // a side of an item: a one-transcript component (set -1), or transcript t of set `set` of class cls <= the launch class, checked
+    // against its own context's descriptors
+    static bool side_ok(const emsar_hip_ctx *c, int launch_cls, int32_t cls, int32_t set, int32_t t, double den) {
+        if (!(den > 0.0)) return false;
+        if (set == -1) return true;
+        const emsar::SetDesc *d = cls <= launch_cls ? set_desc(c, cls, set) : nullptr;
+        return d && t >= 0 && t < (int32_t)d->n_t;
+    }
+    // the launch class of a pair: the larger of its two size classes, a one-transcript component counting as none
+    static int launch_class(int32_t set_a, int32_t cls_a, int32_t set_b, int32_t cls_b) { return std::max(set_a < 0 ? -1 : cls_a, set_b < 0 ? -1 : cls_b); }
+
     int reduce(const CompareRec &r, CompareResult &o) {
         if (!compare_reduce(r, Q.ratio, o)) { ctx->err = "compare: non-finite likelihood at lambda = 0"; return EMSAR_HIP_ERR_NUMERIC; }
         if (o.raw < st.min_raw_lambda) st.min_raw_lambda = o.raw;
@@ -190,32 +102,35 @@ struct CompareRun {
     }
 
     int pair_search_reduce() {
-        res.resize(pa.cand.size());
+        res.resize(qa.cand.size());
         std::vector<CompareItem> items[emsar::kSetClasses];
         std::vector<CompareRec> recs[emsar::kSetClasses];
         std::vector<int32_t> who[emsar::kSetClasses];          // item -> cand
-        for (size_t k = 0; k < pa.cand.size(); k++) {
-            const PresenceRun::Cand &a = pa.cand[k], &b = pb.cand[k];
+        for (size_t k = 0; k < qa.cand.size(); k++) {
+            const SetQuery::Cand &a = qa.cand[k], &b = qb.cand[k];
             Result &o = res[k];
-            if (a.status == PRES_NOT_RESIDENT || b.status == PRES_NOT_RESIDENT) { o.status = CMP_NOT_RESIDENT; continue; }
-            if (a.status == PRES_OUTSIDE || b.status == PRES_OUTSIDE) { o.status = CMP_OUTSIDE; continue; }
-            const double den_a = pa.h_den[(size_t)a.lib], den_b = pb.h_den[(size_t)b.lib];
-            const double u_a = a.set < 0 ? pa.h_usum[(size_t)a.lib] : 0.0, u_b = b.set < 0 ? pb.h_usum[(size_t)b.lib] : 0.0;
+            if (a.standing == SetQuery::NOT_RESIDENT || b.standing == SetQuery::NOT_RESIDENT) { o.status = CMP_NOT_RESIDENT; continue; }
+            if (a.standing == SetQuery::OUTSIDE || b.standing == SetQuery::OUTSIDE) { o.status = CMP_OUTSIDE; continue; }
+            const double den_a = qa.h_den[(size_t)a.lib], den_b = qb.h_den[(size_t)b.lib];
             if (a.set < 0 && b.set < 0) {
-                if (const int rc = reduce(compare_closed_pair(u_a, den_a, u_b, den_b, Q), o)) return rc;
+                if (const int rc = reduce(compare_closed_pair(a.u, den_a, b.u, den_b, Q), o)) return rc;
                 continue;
             }
-            const int cls = std::max(a.set < 0 ? -1 : a.cls, b.set < 0 ? -1 : b.cls);
-            items[cls].push_back(CompareItem{a.set, a.loc, a.cls, b.set, b.loc, b.cls, u_a, den_a, u_b, den_b});
+            const int cls = launch_class(a.set, a.cls, b.set, b.cls);
+            items[cls].push_back(CompareItem{a.set, a.loc, a.cls, b.set, b.loc, b.cls, a.u, den_a, b.u, den_b});
             who[cls].push_back((int32_t)k);
         }
-        const SetSolveParams P = set_params(pa.p);
+        const SetSolveParams P = set_params(qa.p);
         const CompareSide GA = side_of(ctx), GB = side_of(ctx_b);
         const auto &SA = ctx->sets.RS, &SB = ctx_b->sets.RS;
         size_t lds[emsar::kSetClasses], most = 0;              // a launch class holds the sets of its own and of every smaller class
         for (int c = 0; c < emsar::kSetClasses; c++) lds[c] = most = std::max(most, std::max((size_t)SA.max_lds[c], (size_t)SB.max_lds[c]));
         HIPCHK(set_class_lds_attributes(kCompareSets));
         const int rc = runner.run(items, recs, st.device_ms, st.items_launched,
+            [&](int c, const CompareItem &it) {
+                return side_ok(ctx, c, it.cls_a, it.set_a, it.t_a, it.den_a) && side_ok(ctx_b, c, it.cls_b, it.set_b, it.t_b, it.den_b) &&
+                       launch_class(it.set_a, it.cls_a, it.set_b, it.cls_b) == c;
+            },
             [&](int c, int threads, hipStream_t s, size_t cnt, const CompareItem *d_items, CompareRec *d_rec) {
                 hipLaunchKernelGGL(kCompareSets[c], dim3((unsigned)cnt), dim3(threads), lds[c], s, d_items, GA, GB, d_rec, P, Q);
             });
@@ -232,8 +147,8 @@ struct CompareRun {
 
     int copy_out() {
         for (const Result &o : res) st.n_status[o.status]++;
-        for (int32_t i = 0; i < nq; i++) {
-            const Result &o = res[(size_t)pa.cand_of_lib[(size_t)pa.lib_of(query ? query[i] : i)]];
+        for (int32_t i = 0; i < qa.nq; i++) {
+            const Result &o = res[qa.cand_index(i)];
             if (out.lambda) out.lambda[i] = o.lambda;
             if (out.pvalue) out.pvalue[i] = compare_pvalue(o.lambda);
             if (out.log2fc) out.log2fc[i] = o.log2fc;
@@ -251,8 +166,8 @@ struct CompareRun {
 
     int run() {
         int rc;
-        if ((rc = pa.plan()) || (rc = pa.classify())) return rc;
-        if ((rc = pb.plan()) || (rc = pb.classify())) { ctx->err = ctx_b->err; return rc; }
+        if ((rc = qa.plan()) || (rc = qa.classify())) return rc;
+        if ((rc = qb.plan()) || (rc = qb.classify())) { ctx->err = ctx_b->err; return rc; }
         if ((rc = pair_search_reduce())) return rc;
         return copy_out();
     }

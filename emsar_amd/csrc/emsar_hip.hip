@@ -15,7 +15,8 @@
 //   pass_launch.hpp   choose_pass_kernel, one launcher per kernel family, launch_pass; the stamped diagnostic launches
 //   solve.hpp         the set solver's driver (ensure_sets, solve_resident_sets), em_pass / enqueue_cycles, SolveRun: one solve in stages;
 //                     emsar_hip_solve, emsar_hip_run_passes
-//   set_items.hpp     the batch rule (item_batch) and SetItemRunner: batches of items, one workgroup each, through a set-kernel family
+//   set_items.hpp     the batch rule (item_batch); SetItemRunner: batches of items, one workgroup each, through a set-kernel family
+//                     (presence, profile, compare); SetQuery: where a call's queried transcripts stand in a context before any solve
 //   resample.hpp     the resampling driver and its C ABI -- bootstrap, quantiles, subsampling, genes
 //   fit.hpp           the model fit and its C ABI
 //   presence.hpp      the presence test (a likelihood-ratio test per transcript on its resident set) and its C ABI
@@ -34,7 +35,9 @@
 //   kernels_sets.hpp      k_solve_sets                           one workgroup solves one connected set out of LDS
 //   kernels_presence.hpp  k_solve_sets_drop                      a set solved without one of its transcripts, and F at the result out of the same LDS
 //   kernels_profile.hpp   k_profile_sets                         one workgroup searches one confidence limit: set solves with den_t scaled, F as above
+//                         (solve_set_scaled); ProfileStep: the search step kernel and host share; IllinoisBracket
 //   kernels_compare.hpp   k_compare_sets                         one workgroup searches one transcript's multiplier: per evaluation a set solve of each sample
+//                         (solve_set_scaled); CompareStep: the search step kernel and host share
 //   kernels_boot.hpp      k_boot_draw, k_boot_accum, ...         the Poisson bootstrap (draws: boot_rng.hpp; sets: k_solve_sets_boot)
 //                         k_sub_draw, k_sub_scale                the depth subsampling: binomial draws, every replicate to its own depth
 //   kernels_genes.hpp     k_gene_sums, k_gene_finish             per-gene sums in a fixed order (gene_sums, the bootstrap's gene sd)
@@ -829,10 +832,10 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 }  // extern "C"
 
 #include "solve.hpp"      // the set solver's driver and the solve driver: emsar_hip_solve, emsar_hip_run_passes
-#include "set_items.hpp"  // the batch rule and the item runner of the set kernels (after solve.hpp: launch_set_classes, set_params)
+#include "set_items.hpp"  // the batch rule, the item runner of the set kernels and the locator (after solve.hpp: fork_side_streams, plan_solve, set_params)
 #include "resample.hpp"   // the resampling driver and its entry points: bootstrap, genes, quantiles, subsampling
 #include "fit.hpp"        // the model fit and its entry points (after resample.hpp: the gene step is launch_gene_sums)
-#include "presence.hpp"   // the presence test and its entry points (after set_items.hpp: SetItemRunner, query_ok)
+#include "presence.hpp"   // the presence test and its entry points (after set_items.hpp: SetItemRunner, SetQuery, query_ok)
 #include "profile.hpp"    // the profile-likelihood intervals and their entry points (after presence.hpp: PresenceRun)
-#include "compare.hpp"    // the two-sample likelihood-ratio test and its entry points (after profile.hpp: PresenceRun, ProfileSearch's style)
+#include "compare.hpp"    // the two-sample likelihood-ratio test and its entry points (after set_items.hpp: SetItemRunner, SetQuery)
 #include "asym.hpp"       // the asymptotic standard errors and their entry points (after fit.hpp: fit_ensure_csr, launch_gene_sums)

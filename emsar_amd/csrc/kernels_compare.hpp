@@ -29,36 +29,18 @@ struct CompareSide {
 
 // The root search of the multiplier lambda = v * lambda_end on v in [0, 1), on h(v) = (x_A - r x_B) / (x_A + r x_B): h(0) comes from the
 // evaluation at lambda = 0, h(1) = -sign h(0) is known without a solve (x_B -> inf or x_A -> inf at the end of the range).  Illinois
-// steps (regula falsi that halves the weight of an end it keeps twice), replaced by the midpoint when the point does not fall strictly
-// inside the bracket: the refine stage of ProfileSearch.  The root lies in (v_lo, v_hi) at all times -- at v_hi = 1 itself when t has no
-// read to its name on the side that would have to grow (x stays 0 there whatever its den): the search then closes in on the end.  The same code runs in the kernel (every value it sees is the same in all
-// threads of the workgroup) and on the host (pairs of one-transcript components).  v names the point of the evaluation under way.
+// steps on the bracket (IllinoisBracket, kernels_profile.hpp); an evaluation whose h has the sign of h_lo replaces the lo end.  The root
+// lies in (v_lo, v_hi) at all times -- at v_hi = 1 itself when t has no read to its name on the side that would have to grow (x stays 0
+// there whatever its den): the search then closes in on the end.  v names the point of the evaluation under way.
 struct CompareSearch {
-    double v_lo, h_lo, v_hi, h_hi;       // h_lo has the sign of h(0), h_hi the other; v_lo < v_hi
+    IllinoisBracket B;                   // in v: h_lo has the sign of h(0), h_hi the other; v_lo < v_hi
     double v;
-    int kept;                            // +1 / -1 = the hi / lo end survived the last update
 
     __host__ __device__ void start(double h0) {
-        v_lo = 0.0; h_lo = h0; v_hi = 1.0; h_hi = h0 > 0.0 ? -1.0 : 1.0; kept = 0;
-        next();
+        B.p_lo = 0.0; B.h_lo = h0; B.p_hi = 1.0; B.h_hi = h0 > 0.0 ? -1.0 : 1.0; B.kept = 0;
+        v = B.next();
     }
-    __host__ __device__ void next() {
-        const double w = v_hi - v_lo;
-        const double vn = v_lo - h_lo * w / (h_hi - h_lo);
-        v = (vn > v_lo && vn < v_hi) ? vn : v_lo + 0.5 * w;
-    }
-    __host__ __device__ void update(double h) {
-        if ((h > 0.0) == (h_lo > 0.0)) {
-            v_lo = v; h_lo = h;
-            if (kept == 1) h_hi *= 0.5;
-            kept = 1;
-        } else {
-            v_hi = v; h_hi = h;
-            if (kept == -1) h_lo *= 0.5;
-            kept = -1;
-        }
-        next();
-    }
+    __host__ __device__ void update(double h) { B.replace((h > 0.0) == (B.h_lo > 0.0), v, h); v = B.next(); }
 };
 
 // lambda_end and the two den scales of a point v of the search; up = the root lies at lambda > 0 (g(0) > 0)
@@ -77,81 +59,96 @@ __host__ __device__ inline void compare_closed_form(double u, double den, double
     F = u > 0.0 ? u * log(x) - x * den : 0.0;
 }
 
-// Workgroup x runs the whole search of item x.  One evaluation = the two samples one after the other in the same LDS: solve_one_set with
-// den_t taken as scale * den_t (the maximiser of F_A - lambda theta_t, of F_B + r lambda theta_t), then F by set_objective_terms with the
-// ORIGINAL den_t, exactly as k_profile_sets does; solve_one_set reloads the set and restarts from the uniform point each time, so a
-// record is a pure function of (item, P, Q).  Evaluation 0 is lambda = 0 (both scales exactly 1): theta_hat and F_hat of both samples
-// come from the code path of every later evaluation.  The launch has the thread count and the LDS of the larger of the two classes.
-// Every branch is taken by the whole workgroup: it is decided on the item's fields and on reduction results handed to the scalar unit
-// (profile_uniform); the strided loops and the reductions stand outside any branch that threads could take differently.
-// The worst case is 2 * Q.max_evals * P.max_iter passes.
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void k_compare_sets(const CompareItem *__restrict__ items, CompareSide GA, CompareSide GB,
-                                                          CompareRec *__restrict__ rec, SetSolveParams P, CompareSearchParams Q) {
-    const CompareItem it = items[blockIdx.x];
-    const double r = Q.ratio;
+// One search and what its record needs, driven by k_compare_sets and by the host (compare_closed_pair, compare.hpp): the caller
+// evaluates both samples at pt's scales and hands the two values of t and the two F there to step(), until step() says stop.  In the
+// kernel every argument of step() is the same in all threads (the item's fields, reduction results made uniform): what it returns is a
+// branch the whole workgroup takes.
+struct CompareStep {
     CompareSearch S;
-    ComparePoint pt;
-    pt.lambda = 0.0; pt.scale_a = 1.0; pt.scale_b = 1.0;
-    bool up = false;
-    int evals = 0, passes = 0, solves_ok = 1, search_ok = 0, infeasible = 0;
-    double x0_a = 0.0, x0_b = 0.0, F0_a = 0.0, F0_b = 0.0, x_a = 0.0, x_b = 0.0, F_a = 0.0, F_b = 0.0;
-    for (;;) {
-#pragma nounroll
-        for (int side = 0; side < 2; side++) {
-            const bool b = side != 0;
-            const int set = b ? it.set_b : it.set_a, t = b ? it.t_b : it.t_a, cls = b ? it.cls_b : it.cls_a;
-            const double den_t = b ? it.den_b : it.den_a, scale = b ? pt.scale_b : pt.scale_a;
-            double x_t, F;
-            if (set < 0) compare_closed_form(b ? it.u_b : it.u_a, den_t, scale, x_t, F);
-            else {
-                const emsar::SetDesc *dp = cls == 0 ? (b ? GB.desc0 : GA.desc0) : cls == 1 ? (b ? GB.desc1 : GA.desc1) : (b ? GB.desc2 : GA.desc2);
-                const emsar::SetDesc d = dp[set];
-                SetSolved K;
-                solve_one_set<THREADS, true>(d, b ? GB.g_tid : GA.g_tid, b ? GB.g_u : GA.g_u, b ? GB.row_w : GA.row_w, b ? GB.rp : GA.rp,
-                                             b ? GB.ent : GA.ent, b ? GB.cp : GA.cp, b ? GB.crow : GA.crow, b ? GB.den : GA.den, nullptr, nullptr,
-                                             P, t, &K, scale);
-                const SetLds &L = K.L;
-                const double *x = K.res;
-                set_sync<THREADS>();
-                double s3[3] = {0.0, 0.0, 0.0};        // sum R log S + u log x, sum x den (t at its original den), infeasible
-                set_objective_terms<THREADS>(L, x, s3, [&](int i) { return i == t ? den_t : L.den[i]; }, [](int, double, double) {});
-                const double xt_now = x[t];
-                set_reduce_sum<THREADS, 3>(s3, L.red);
-                set_sync<THREADS>();                   // the next solve_one_set overwrites the LDS this epilogue read
-                passes += K.passes;
-                solves_ok &= K.converged;
-                infeasible += (int)s3[2];
-                x_t = profile_uniform(xt_now);
-                F = profile_uniform(s3[0] - s3[1]);
-            }
-            if (b) { x_b = x_t; F_b = F; } else { x_a = x_t; F_a = F; }
-        }
+    ComparePoint pt;                     // the point of the evaluation under way; evaluation 0 is lambda = 0, both scales exactly 1
+    bool up;
+    int evals, search_ok;                // search_ok: a stopping rule was met; else a non-finite value or the cap ended it
+    double x0_a, x0_b, F0_a, F0_b;       // at lambda = 0
+    double x_a, x_b, F_a, F_b;           // the last evaluation
+
+    __host__ __device__ void start() {
+        pt.lambda = 0.0; pt.scale_a = 1.0; pt.scale_b = 1.0;
+        up = false; evals = 0; search_ok = 0;
+        x0_a = x0_b = F0_a = F0_b = x_a = x_b = F_a = F_b = 0.0;
+    }
+    // true = evaluate again, at the new pt
+    __host__ __device__ bool step(double xa, double Fa, double xb, double Fb, double den_a, double den_b, const CompareSearchParams &Q) {
+        const double r = Q.ratio;
+        x_a = xa; F_a = Fa; x_b = xb; F_b = Fb;
         evals++;
         const double g = x_a - r * x_b;
         if (evals == 1) {
             x0_a = x_a; x0_b = x_b; F0_a = F_a; F0_b = F_b;
-            if (!(F_a - F_a == 0.0) || !(F_b - F_b == 0.0)) break;              // a non-finite likelihood at lambda = 0: the host's error
-            if (g == 0.0) { search_ok = 1; break; }
+            if (!(F_a - F_a == 0.0) || !(F_b - F_b == 0.0)) return false;           // a non-finite likelihood at lambda = 0: the host's error
+            if (g == 0.0) { search_ok = 1; return false; }
             up = g > 0.0;
         }
-        if (!(g - g == 0.0) || !(F_a - F_a == 0.0) || !(F_b - F_b == 0.0)) break;   // a non-finite value: reported unconverged
-        if (evals > 1 && 2.0 * fabs(pt.lambda * g) <= Q.dev_tol) { search_ok = 1; break; }
+        if (!(g - g == 0.0) || !(F_a - F_a == 0.0) || !(F_b - F_b == 0.0)) return false;   // a non-finite value: reported unconverged
+        if (evals > 1 && 2.0 * fabs(pt.lambda * g) <= Q.dev_tol) { search_ok = 1; return false; }
         const double h = g / (x_a + r * x_b);
         if (evals == 1) S.start(h); else S.update(h);
         // the root lies in the bracket and L is convex with slope -g: the dual value cannot fall further than |g| times the bracket
-        if (2.0 * fabs(g) * ((S.v_hi - S.v_lo) * ComparePoint::end(up, r, it.den_a, it.den_b)) <= Q.dev_tol) { search_ok = 1; break; }
-        if (evals >= Q.max_evals) break;
-        pt.at(S.v, up, r, it.den_a, it.den_b);
+        if (2.0 * fabs(g) * ((S.B.p_hi - S.B.p_lo) * ComparePoint::end(up, r, den_a, den_b)) <= Q.dev_tol) { search_ok = 1; return false; }
+        if (evals >= Q.max_evals) return false;
+        pt.at(S.v, up, r, den_a, den_b);
+        return true;
     }
-    if (threadIdx.x == 0) {
+    // the record; the host's closed-form pairs have no passes, no solve that could fail and nothing infeasible: (0, 1, 0)
+    __host__ __device__ CompareRec record(int passes, int solves_ok, int infeasible) const {
         CompareRec o;
         o.lambda_mult = pt.lambda; o.x_a = x_a; o.x_b = x_b; o.x0_a = x0_a; o.x0_b = x0_b;
         o.FhatA = F0_a; o.FhatB = F0_b; o.FA = F_a; o.FB = F_b;
         o.evals = evals; o.passes = passes; o.flags = (search_ok ? COMPARE_REC_SEARCH_OK : 0) | (solves_ok ? COMPARE_REC_SOLVES_OK : 0);
         o.infeasible = infeasible;
-        rec[blockIdx.x] = o;
+        return o;
     }
+};
+
+// Workgroup x runs the whole search of item x (CompareStep).  One evaluation = the two samples one after the other in the same LDS:
+// solve_set_scaled (kernels_profile.hpp) with den_t taken as scale * den_t (the maximiser of F_A - lambda theta_t, of
+// F_B + r lambda theta_t) and F with the ORIGINAL den_t, exactly as k_profile_sets does; solve_one_set reloads the set and restarts
+// from the uniform point each time, so a record is a pure function of (item, P, Q).  Evaluation 0 is lambda = 0 (both scales exactly
+// 1): theta_hat and F_hat of both samples come from the code path of every later evaluation.  The launch has the thread count and the
+// LDS of the larger of the two classes.
+// Every branch is taken by the whole workgroup: it is decided on the item's fields and on reduction results handed to the scalar unit
+// (set_uniform); the strided loops and the reductions stand outside any branch that threads could take differently.
+// The worst case is 2 * Q.max_evals * P.max_iter passes.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_compare_sets(const CompareItem *__restrict__ items, CompareSide GA, CompareSide GB,
+                                                          CompareRec *__restrict__ rec, SetSolveParams P, CompareSearchParams Q) {
+    const CompareItem it = items[blockIdx.x];
+    CompareStep T;
+    T.start();
+    int passes = 0, solves_ok = 1, infeasible = 0;
+    for (;;) {
+        double x_a = 0.0, F_a = 0.0, x_b = 0.0, F_b = 0.0;
+#pragma nounroll
+        for (int side = 0; side < 2; side++) {
+            const bool b = side != 0;
+            const int set = b ? it.set_b : it.set_a, t = b ? it.t_b : it.t_a, cls = b ? it.cls_b : it.cls_a;
+            const double den_t = b ? it.den_b : it.den_a, scale = b ? T.pt.scale_b : T.pt.scale_a;
+            double x_t, F;
+            if (set < 0) compare_closed_form(b ? it.u_b : it.u_a, den_t, scale, x_t, F);
+            else {
+                const emsar::SetDesc *dp = cls == 0 ? (b ? GB.desc0 : GA.desc0) : cls == 1 ? (b ? GB.desc1 : GA.desc1) : (b ? GB.desc2 : GA.desc2);
+                const ScaledSolve e = solve_set_scaled<THREADS>(dp[set], b ? GB.g_tid : GA.g_tid, b ? GB.g_u : GA.g_u, b ? GB.row_w : GA.row_w,
+                                                                b ? GB.rp : GA.rp, b ? GB.ent : GA.ent, b ? GB.cp : GA.cp, b ? GB.crow : GA.crow,
+                                                                b ? GB.den : GA.den, P, t, den_t, scale);
+                passes += e.passes;
+                solves_ok &= e.converged;
+                infeasible += e.infeasible;
+                x_t = set_uniform(e.x_t); F = e.F;
+            }
+            if (b) { x_b = x_t; F_b = F; } else { x_a = x_t; F_a = F; }
+        }
+        if (!T.step(x_a, F_a, x_b, F_b, it.den_a, it.den_b, Q)) break;
+    }
+    if (threadIdx.x == 0) rec[blockIdx.x] = T.record(passes, solves_ok, infeasible);
 }
 const auto kCompareSets = set_kernels(k_compare_sets<64>, k_compare_sets<256>, k_compare_sets<512>);
 

@@ -101,6 +101,13 @@ __device__ __forceinline__ double set_reduce_max(double v, double *red) {
     }
     return v;
 }
+// a value every thread of the workgroup holds with the same bits (a reduction's result), moved to scalar registers: what is computed
+// from it, a branch condition above all, is the scalar unit's
+__device__ __forceinline__ double set_uniform(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
 
 struct SetLds {
     double *den, *u, *w, *rw, *red;

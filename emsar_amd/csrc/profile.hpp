@@ -1,9 +1,10 @@
 // profile.hpp -- the profile-likelihood intervals behind include/emsar_hip.h: emsar_hip_profile (device) and emsar_hip_profile_cut_host (no
 // HIP call).  Part of emsar_hip.hip's translation unit, included after presence.hpp: the first stages ARE the presence test's
-// (PresenceRun: plan, classify, baseline, mark_absent, drop_and_reduce), so theta_hat and Lambda are its bits; k_profile_sets
+// (PresenceRun::test: locate, baseline, mark_absent, drop_and_reduce), so theta_hat and Lambda are its bits; k_profile_sets
 // (kernels_profile.hpp) runs the searches, its items batched by the runner the presence test uses (set_items.hpp).
-// One call = one ProfileRun:  plan .. drop    PresenceRun's stages on the same query: status, theta_hat, F per set, Lambda per candidate
-//                             closed_form     one-transcript components: the same search on the host from F(x) = u log x - x den
+// One call = one ProfileRun:  test            PresenceRun's stages on the same query: status, theta_hat, F per set, Lambda per candidate
+//                             closed_form     one-transcript components: the kernel's search (ProfileStep) on the host from
+//                                             F(x) = u log x - x den
 //                             search          one item (set, t, side) per limit to find -- upper for every candidate of a resident
 //                                             set, lower where Lambda > q or t is essential --, in batches across the three classes
 //                             reduce          records -> limits, deviances, status;  copy_out in query order
@@ -30,26 +31,25 @@ inline double profile_cut(double level) {
 }
 
 struct ProfileRun {
-    // what the searches of one candidate (PresenceRun::cand, same index) left
+    // what one candidate (SetQuery::cand of the presence stages, same index) is given
     struct Limits {
         double lower = NAN, upper = NAN, dev_lower = NAN, dev_upper = NAN;
+        double lambda = NAN, theta_hat = NAN;           // the presence stages' values; NaN outside the likelihood and where not resident
         int32_t evals = 0, status = PROF_NOT_RESIDENT;
         bool capped = false;             // a search or one of its solves hit its cap
     };
     emsar_hip_ctx *const ctx;
     PresenceRun pres;
-    const int32_t nq;
-    const int32_t *const query;
     const emsar_profile_outputs out;     // a copy: all NULL when the caller gave none
     ProfileSearchParams Q;
     std::vector<Limits> lim;
     SetItemRunner<ProfileItem, ProfileRec> runner;
     emsar_profile_stats st{};
 
-    // the presence stages batch under the profile's variable too
-    ProfileRun(emsar_hip_ctx *c, const emsar_em_params *p, const emsar_profile_params &pp, int32_t nq_, const int32_t *q, const emsar_profile_outputs *o)
-        : ctx(c), pres(c, p, nq_, q, nullptr, "EMSAR_HIP_PROFILE_BATCH"), nq(nq_), query(q), out(o ? *o : emsar_profile_outputs{}),
+    ProfileRun(emsar_hip_ctx *c, const emsar_em_params *p, const emsar_profile_params &pp, int32_t nq, const int32_t *query, const emsar_profile_outputs *o)
+        : ctx(c), pres(c, p, nq, query, nullptr), out(o ? *o : emsar_profile_outputs{}),
           runner(c, "EMSAR_HIP_PROFILE_BATCH", "profile: an item lies outside its class's sets") {
+        pres.runner.batch_env = runner.batch_env;       // the presence stages batch under the profile's variable too
         Q.q = profile_cut(pp.level);
         Q.dev_tol = pp.dev_tol > 0.0 ? pp.dev_tol : 1e-4;
         Q.max_evals = pp.max_evals > 0 ? pp.max_evals : 40;
@@ -57,67 +57,62 @@ struct ProfileRun {
         st.cut = Q.q;
     }
 
-    bool found(double dev) const { return std::fabs(dev - Q.q) <= Q.dev_tol * Q.q; }
-
     // One limit of a one-transcript component with u > 0 reads: x(m) = u / (m den) maximises u log x - m den x; the search of the kernel
+    // (ProfileStep).  evals and capped gather both sides.
     void closed_limit(int side, double u, double den, double &x, double &dev, int32_t &evals, bool &capped) const {
-        const double th = u / den, F_hat = u * std::log(th) - th * den;
-        ProfileSearch S;
-        S.start(side, th * den, Q.q);
-        const double sqrt_q = std::sqrt(Q.q);
-        for (int n = 0;;) {
-            x = u / (std::exp(S.z) * den);
-            const double raw = 2.0 * (F_hat - (u * std::log(x) - x * den));
-            dev = raw > 0.0 ? raw : 0.0;
-            evals++; n++;
-            if (!(raw == raw)) { capped = true; return; }
-            if (found(dev)) return;
-            if (n >= Q.max_evals) { capped = true; return; }
-            S.update(std::sqrt(dev) - sqrt_q);
-        }
+        const double th = u / den, F_hat = u * std::log(th) - th * den, sqrt_q = std::sqrt(Q.q);
+        ProfileStep T;
+        T.start(side, th, den, F_hat, Q);
+        do x = u / (T.scale() * den);
+        while (T.step(x, u * std::log(x) - x * den, F_hat, sqrt_q, Q));
+        dev = T.dev;
+        evals += T.evals;
+        if (!T.search_ok) capped = true;
     }
 
     // the presence test's status of every candidate -> what the profile reports before any search; the closed form on the host
     void classify_and_closed_form() {
         lim.resize(pres.cand.size());
         for (size_t k = 0; k < pres.cand.size(); k++) {
-            PresenceRun::Cand &c = pres.cand[k];
+            const PresenceRun::Test &c = pres.cand[k];
+            const SetQuery::Cand &w = pres.q.cand[k];
             Limits &l = lim[k];
             if (c.status == PRES_OUTSIDE) { l.status = PROF_OUTSIDE; continue; }
             if (c.status == PRES_NOT_RESIDENT) { l.status = PROF_NOT_RESIDENT; continue; }
-            if (c.status == PRES_ABSENT) c.lambda = 0.0;
-            if (c.status == PRES_ESSENTIAL) c.lambda = INFINITY;
+            l.lambda = c.reported_lambda(); l.theta_hat = c.theta_hat;
             l.capped = c.status == PRES_UNCONVERGED;
-            l.status = c.lambda > Q.q ? PROF_TWO_SIDED : PROF_LOWER_ZERO;
-            if (l.status == PROF_LOWER_ZERO) { l.lower = 0.0; l.dev_lower = c.lambda; }
-            if (c.set >= 0) continue;            // a resident set: the searches run on the device
-            const double u = pres.h_usum[(size_t)c.lib], den = pres.h_den[(size_t)c.lib];
-            if (!(u > 0.0)) { l.upper = Q.q / (2.0 * den); l.dev_upper = Q.q; continue; }
-            closed_limit(0, u, den, l.lower, l.dev_lower, l.evals, l.capped);
-            closed_limit(1, u, den, l.upper, l.dev_upper, l.evals, l.capped);
+            l.status = l.lambda > Q.q ? PROF_TWO_SIDED : PROF_LOWER_ZERO;
+            if (l.status == PROF_LOWER_ZERO) { l.lower = 0.0; l.dev_lower = l.lambda; }
+            if (w.set >= 0) continue;            // a resident set: the searches run on the device
+            const double den = pres.q.h_den[(size_t)w.lib];
+            if (!(w.u > 0.0)) { l.upper = Q.q / (2.0 * den); l.dev_upper = Q.q; continue; }
+            closed_limit(0, w.u, den, l.lower, l.dev_lower, l.evals, l.capped);
+            closed_limit(1, w.u, den, l.upper, l.dev_upper, l.evals, l.capped);
         }
     }
 
     // the searches of the resident candidates and what their records say
     int search_and_reduce() {
-        if (!pres.use_sets) return EMSAR_HIP_OK;
+        if (!pres.q.use_sets) return EMSAR_HIP_OK;
         std::vector<ProfileItem> items[emsar::kSetClasses];
         std::vector<ProfileRec> recs[emsar::kSetClasses];
         std::vector<int32_t> who[emsar::kSetClasses];          // item -> cand
-        for (size_t k = 0; k < pres.cand.size(); k++) {
-            const PresenceRun::Cand &c = pres.cand[k];
-            if (c.set < 0 || lim[k].status == PROF_OUTSIDE || lim[k].status == PROF_NOT_RESIDENT) continue;
-            const double F_hat = pres.base_rec[c.cls][(size_t)pres.base_of_set[c.cls][(size_t)c.set]].F;
+        for (size_t k = 0; k < lim.size(); k++) {
+            const SetQuery::Cand &w = pres.q.cand[k];
+            if (w.set < 0 || lim[k].status == PROF_OUTSIDE || lim[k].status == PROF_NOT_RESIDENT) continue;
             for (int side = lim[k].status == PROF_TWO_SIDED ? 0 : 1; side < 2; side++) {
-                items[c.cls].push_back(ProfileItem{c.set, c.loc, side, 0, c.theta_hat, F_hat});
-                who[c.cls].push_back((int32_t)k);
+                items[w.cls].push_back(ProfileItem{w.set, w.loc, side, 0, lim[k].theta_hat, pres.base_of(w).F});
+                who[w.cls].push_back((int32_t)k);
             }
         }
         const SetsDev &D = ctx->sets;
-        const SetSolveParams P = set_params(pres.p);
+        const SetSolveParams P = set_params(pres.q.p);
         HIPCHK(set_class_lds_attributes(kProfileSets));
         const int rc = runner.run(items, recs, st.search_ms, st.items_launched,
-            [](const ProfileItem &it, const emsar::SetDesc &d) { return it.t >= 0 && it.t < (int32_t)d.n_t && (it.side == 0 || it.side == 1); },
+            [&](int c, const ProfileItem &it) {
+                const emsar::SetDesc *d = set_desc(ctx, c, it.set);
+                return d && it.t >= 0 && it.t < (int32_t)d->n_t && (it.side == 0 || it.side == 1);
+            },
             [&](int c, int threads, hipStream_t s, size_t cnt, const ProfileItem *d_items, ProfileRec *d_rec) {
                 hipLaunchKernelGGL(kProfileSets[c], dim3((unsigned)cnt), dim3(threads), D.RS.max_lds[c], s, D.d_sdesc[c].get(), d_items, D.d_g_tid.get(),
                                    D.d_g_u.get(), D.d_row_w.get(), D.d_srp.get(), D.d_sent.get(), D.d_scp.get(), D.d_scrow.get(), ctx->vec.d_den.get(), d_rec, P, Q);
@@ -127,7 +122,7 @@ struct ProfileRun {
             for (size_t i = 0; i < recs[cls].size(); i++) {
                 Limits &l = lim[(size_t)who[cls][i]];
                 const ProfileRec &r = recs[cls][i];
-                const bool base_ok = pres.base_rec[cls][(size_t)pres.base_of_set[cls][(size_t)items[cls][i].set]].converged != 0;
+                const bool base_ok = pres.base_of(pres.q.cand[(size_t)who[cls][i]]).converged != 0;
                 st.evals_sum += r.evals; st.passes_sum += r.passes;
                 st.evals_max = std::max(st.evals_max, r.evals); st.passes_max = std::max(st.passes_max, r.passes);
                 l.evals += r.evals;
@@ -139,22 +134,18 @@ struct ProfileRun {
     }
 
     int copy_out() {
-        for (size_t k = 0; k < lim.size(); k++) {
-            Limits &l = lim[k];
-            PresenceRun::Cand &c = pres.cand[k];
-            if (l.status == PROF_OUTSIDE || l.status == PROF_NOT_RESIDENT) c.lambda = c.theta_hat = NAN;
-            else if (l.capped) l.status = PROF_UNCONVERGED;
+        for (Limits &l : lim) {
+            if (l.capped) l.status = PROF_UNCONVERGED;       // never set outside the likelihood or where not resident
             st.n_status[l.status]++;
         }
-        for (int32_t i = 0; i < nq; i++) {
-            const size_t k = (size_t)pres.cand_of_lib[(size_t)pres.lib_of(query ? query[i] : i)];
-            const Limits &l = lim[k];
+        for (int32_t i = 0; i < pres.q.nq; i++) {
+            const Limits &l = lim[pres.q.cand_index(i)];
             if (out.lower) out.lower[i] = l.lower;
             if (out.upper) out.upper[i] = l.upper;
             if (out.dev_lower) out.dev_lower[i] = l.dev_lower;
             if (out.dev_upper) out.dev_upper[i] = l.dev_upper;
-            if (out.lambda) out.lambda[i] = pres.cand[k].lambda;
-            if (out.theta_hat) out.theta_hat[i] = pres.cand[k].theta_hat;
+            if (out.lambda) out.lambda[i] = l.lambda;
+            if (out.theta_hat) out.theta_hat[i] = l.theta_hat;
             if (out.status) out.status[i] = l.status;
             if (out.evals) out.evals[i] = l.evals;
         }
@@ -163,9 +154,7 @@ struct ProfileRun {
 
     int run() {
         int rc;
-        if ((rc = pres.plan()) || (rc = pres.classify()) || (rc = pres.baseline())) return rc;
-        pres.mark_absent();
-        if ((rc = pres.drop_and_reduce())) return rc;
+        if ((rc = pres.test())) return rc;
         classify_and_closed_form();
         if ((rc = search_and_reduce())) return rc;
         st.items_launched += pres.st.items_launched;

@@ -1,6 +1,7 @@
 // set_items.hpp -- what the drivers of the resident sets share beyond solve.hpp: the batch rule (item_batch), the item runner of a
-// set-kernel family whose workgroups each take one item and leave one record (SetItemRunner: presence.hpp, profile.hpp), and the
-// frame of a per-transcript call (query_ok, run_query_call).  Part of emsar_hip.hip's translation unit, included after solve.hpp.
+// set-kernel family whose workgroups each take one item and leave one record (SetItemRunner: presence.hpp, profile.hpp, compare.hpp),
+// the locator of a call's queried transcripts (SetQuery) and the frame of a per-transcript call (query_ok, run_query_call).  Part of
+// emsar_hip.hip's translation unit, included after solve.hpp.
 
 namespace {
 
@@ -15,12 +16,18 @@ inline int64_t item_batch(int64_t per_item_bytes, const char *env_name, int64_t 
     return std::min<int64_t>(std::min<int64_t>(batch, most), cap);
 }
 
-// Items of the three size classes through one family of set kernels, at most a batch per class and launch, the classes next to each
-// other on their streams; recs[c][i] answers items[c][i].  An Item names its set of the class in `set`.
+// the descriptor of set `set` of size class c of the context, null where there is none: the bounds check of an item's set
+inline const emsar::SetDesc *set_desc(const emsar_hip_ctx *ctx, int c, int32_t set) {
+    if (c < 0 || c >= emsar::kSetClasses || set < 0 || (size_t)set >= ctx->sets.RS.desc[c].size()) return nullptr;
+    return &ctx->sets.RS.desc[c][(size_t)set];
+}
+
+// Items of the three launch classes through one family of set kernels, at most a batch per class and launch, the classes next to each
+// other on the streams of `ctx`; recs[c][i] answers items[c][i].
 template <class Item, class Rec>
 struct SetItemRunner {
     emsar_hip_ctx *const ctx;
-    const char *const batch_env;         // the variable that overrides the batch
+    const char *batch_env;               // the variable that overrides the batch; the owner of a borrowed run may name its own
     const char *const bad_item;          // ctx->err of an item that fails the check
     DevBuf<Item> d_items[emsar::kSetClasses];
     DevBuf<Rec> d_rec[emsar::kSetClasses];
@@ -29,17 +36,18 @@ struct SetItemRunner {
     SetItemRunner(emsar_hip_ctx *c, const char *env, const char *bad) : ctx(c), batch_env(env), bad_item(bad) {}
     ~SetItemRunner() { for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev); }
 
-    // valid(item, descriptor of its set): the family's check, made on every item before anything is launched;
+    // valid(class, item): the family's whole check -- the item's sets against their descriptors (set_desc) and its own fields --, made on
+    // every item before anything is launched;
     // launch(class, threads, stream, count, d_items, d_rec): the family's kernel on `count` items, its LDS attributes set by the caller.
-    // The device time of the launches is added to ms_acc, the items to `launched`.
+    // A class is launched when it has items, the big classes first (launch_set_classes' order, which asks for sets in the class of `ctx`
+    // instead: an item of the compare family may run in a class in which ctx has none).  The device time of the launches is added to
+    // ms_acc, the items to `launched`.
     template <class Valid, class Launch>
     int run(const std::vector<Item> (&items)[emsar::kSetClasses], std::vector<Rec> (&recs)[emsar::kSetClasses], double &ms_acc, int64_t &launched,
             const Valid &valid, const Launch &launch) {
-        const auto &S = ctx->sets.RS;
         size_t most = 0;
         for (int c = 0; c < emsar::kSetClasses; c++) {
-            for (const Item &it : items[c])
-                if (it.set < 0 || (size_t)it.set >= S.desc[c].size() || !valid(it, S.desc[c][(size_t)it.set])) { ctx->err = bad_item; return EMSAR_HIP_ERR_HIP; }
+            for (const Item &it : items[c]) if (!valid(c, it)) { ctx->err = bad_item; return EMSAR_HIP_ERR_HIP; }
             recs[c].resize(items[c].size());
             most = std::max(most, items[c].size());
         }
@@ -51,17 +59,21 @@ struct SetItemRunner {
                 HIPCHK(d_items[c].alloc(cnt)); HIPCHK(d_rec[c].alloc(cnt));
             }
         for (hipEvent_t &ev : e) if (!ev) HIPCHK(hipEventCreate(&ev));
+        const hipStream_t st[emsar::kSetClasses] = {ctx->stream, ctx->side[0], ctx->side[1]};
         for (size_t first = 0; first < most; first += batch) {
-            int rc;
             size_t cnt[emsar::kSetClasses];
             for (int c = 0; c < emsar::kSetClasses; c++) {
                 cnt[c] = items[c].size() > first ? std::min(batch, items[c].size() - first) : 0;
                 if (cnt[c]) HIPCHK(hipMemcpyAsync(d_items[c], items[c].data() + first, cnt[c] * sizeof(Item), hipMemcpyHostToDevice, ctx->stream));
             }
             HIPCHK(hipEventRecord(e[0], ctx->stream));
-            if ((rc = fork_side_streams(ctx, 2))) return rc;
-            rc = launch_set_classes(ctx, 2, [&](int c, int threads, hipStream_t s) { if (cnt[c]) launch(c, threads, s, cnt[c], d_items[c].get(), d_rec[c].get()); });
-            if (rc) return rc;
+            if (const int rc = fork_side_streams(ctx, 2)) return rc;
+            for (int c = emsar::kSetClasses - 1; c >= 0; c--) if (cnt[c]) launch(c, emsar::kSetThreads[c], st[c], cnt[c], d_items[c].get(), d_rec[c].get());
+            for (int i = 0; i < 2; i++) {
+                HIPCHK(hipEventRecord(ctx->ev_join[i], ctx->side[i]));
+                HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
+            }
+            HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(e[1], ctx->stream));
             for (int c = 0; c < emsar::kSetClasses; c++)
                 if (cnt[c]) HIPCHK(hipMemcpyAsync(recs[c].data() + first, d_rec[c], cnt[c] * sizeof(Rec), hipMemcpyDeviceToHost, ctx->stream));
@@ -70,6 +82,94 @@ struct SetItemRunner {
             HIPCHK(hipEventElapsedTime(&ms, e[0], e[1]));
             ms_acc += ms;
             for (int c = 0; c < emsar::kSetClasses; c++) launched += (int64_t)cnt[c];
+        }
+        return EMSAR_HIP_OK;
+    }
+};
+
+// Where the queried transcripts of a per-transcript call stand in one context before anything is solved: what the presence test, the
+// profile intervals (through it) and the two-sample test (once per sample) need to know first.  plan, then classify.
+struct SetQuery {
+    enum Standing : int32_t {
+        OUTSIDE,                         // den is not > 0: outside the likelihood
+        NOT_RESIDENT,                    // in a streamed set or a cluster, or the solve would not use the sets at all
+        CLOSED,                          // a one-transcript component: `u` reads on the transcript alone
+        MEMBER                           // transcript `loc` of packed set `set` of size class `cls`
+    };
+    // one queried transcript (library index), once however often it is asked for
+    struct Cand {
+        int32_t lib, cls = -1, set = -1, loc = -1;
+        int32_t standing = NOT_RESIDENT;
+        bool own_reads = false;          // MEMBER: a single-transcript row of its own has reads
+        double u = 0.0;                  // CLOSED: its read count
+    };
+    emsar_hip_ctx *const ctx;
+    const emsar_em_params p;             // the caller's parameters with the defaults filled in
+    const int32_t nq;
+    const int32_t *const query;          // caller tids, null = all in order
+    const int n;
+    bool use_sets = false;
+    std::vector<Cand> cand;
+    std::vector<int32_t> cand_of_lib;    // [n] -> cand, -1 = not queried
+    std::vector<double> h_den, h_usum, h_gu;       // [n] [n] [resident tids]: den, closed-form counts, folded counts (use_sets only)
+    std::vector<int32_t> h_gtid;                   // [resident tids]
+
+    SetQuery(emsar_hip_ctx *c, const emsar_em_params *pp, int32_t nq_, const int32_t *q) : ctx(c), p(solve_params(pp)), nq(nq_), query(q), n(c->n_tx) {}
+
+    int32_t lib_of(int32_t tid) const { return renumbered(ctx) ? tid_map(ctx)[(size_t)tid] : tid; }
+    // the candidate of the i-th query
+    size_t cand_index(int32_t i) const { return (size_t)cand_of_lib[(size_t)lib_of(query ? query[i] : i)]; }
+
+    // which solvers a solve would run (the sets are found on first use: ensure_sets), and the query with its repeats removed
+    int plan() {
+        if (!(p.count_floor >= 0.0) || (p.set_mode != 0 && p.set_mode != 1)) return EMSAR_HIP_ERR_ARG;
+        SolvePlan sp;
+        if (const int rc = plan_solve(ctx, p.set_mode, sp)) return rc;
+        use_sets = sp.use_sets;
+        cand_of_lib.assign((size_t)n, -1);
+        for (int32_t i = 0; i < nq; i++) {
+            const int32_t l = lib_of(query ? query[i] : i);
+            if (cand_of_lib[(size_t)l] >= 0) continue;
+            cand_of_lib[(size_t)l] = (int32_t)cand.size();
+            Cand c; c.lib = l;
+            cand.push_back(c);
+        }
+        return EMSAR_HIP_OK;
+    }
+
+    // The packed sets' transcript lists and folded counts live on the device only (ensure_sets frees the host copies): they are read
+    // back here, with den and the closed-form counts.
+    int classify() {
+        if (!use_sets) return EMSAR_HIP_OK;          // every candidate NOT_RESIDENT
+        const SetsDev &D = ctx->sets;
+        const auto &S = D.RS;
+        size_t n_gu = 0;
+        for (int c = 0; c < emsar::kSetClasses; c++) for (const auto &d : S.desc[c]) n_gu = std::max<size_t>(n_gu, (size_t)d.tid_off + d.n_t);
+        h_den.resize((size_t)n); h_usum.resize((size_t)n); h_gtid.resize(n_gu); h_gu.resize(n_gu);
+        if (n > 0) {
+            HIPCHK(hipMemcpyAsync(h_den.data(), ctx->vec.d_den, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(h_usum.data(), D.d_usum, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if (n_gu > 0) {
+            HIPCHK(hipMemcpyAsync(h_gtid.data(), D.d_g_tid, n_gu * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(h_gu.data(), D.d_g_u, n_gu * 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        for (int c = 0; c < emsar::kSetClasses; c++)
+            for (size_t s = 0; s < S.desc[c].size(); s++) {
+                const emsar::SetDesc &d = S.desc[c][s];
+                for (uint32_t i = 0; i < d.n_t; i++) {
+                    const int32_t k = cand_of_lib[(size_t)h_gtid[d.tid_off + i]];
+                    if (k >= 0) { cand[(size_t)k].cls = c; cand[(size_t)k].set = (int32_t)s; cand[(size_t)k].loc = (int32_t)i; }
+                }
+            }
+        for (auto &c : cand) {
+            const uint8_t kind = S.kind[(size_t)c.lib];
+            if (!(h_den[(size_t)c.lib] > 0.0)) c.standing = OUTSIDE;
+            else if (kind == emsar::KIND_STREAMED || kind == emsar::KIND_CLUSTER) c.standing = NOT_RESIDENT;
+            else if (kind == emsar::KIND_CLOSED) { c.standing = CLOSED; c.u = h_usum[(size_t)c.lib]; }
+            else if (c.set < 0) { ctx->err = "presence: a resident transcript is in no packed set"; return EMSAR_HIP_ERR_HIP; }
+            else { c.standing = MEMBER; c.own_reads = h_gu[S.desc[c.cls][(size_t)c.set].tid_off + (size_t)c.loc] > 0.0; }
         }
         return EMSAR_HIP_OK;
     }

@@ -132,6 +132,21 @@ def test_closed_pair_special_cases():
     assert abs(a["lambda"] - b["lambda"]) <= 2 * DEV_TOL and abs(a["log2fc"] + b["log2fc"]) <= 1e-15
 
 
+def test_closed_pair_search_point_by_point():
+    """(40 reads, den 2) against (55, 2) capped after 1, 2 and 3 evaluations: the points of the search, which kernel and host take from
+    one step function.  Plain arithmetic, no libm call enters these three fields: the first point is v = (7.5 / 47.5) / (1 + 7.5 / 47.5)
+    = 3 / 22 of lambda_end = -den_A, multiplier -3 / 11; the values are those of the build before the step was shared."""
+    want = {1: ("0x0.0p+0", "0x1.4000000000000p+4", "-0x1.e000000000000p+2"),
+            2: ("-0x1.1745d1745d174p-2", "0x1.7286bca1af287p+4", "-0x1.0ac7691840ad0p+0"),
+            3: ("-0x1.3d5af9a723f79p-2", "0x1.7aae0140782d1p+4", "-0x1.24a59d21cb400p-3")}
+    for max_evals, bits in want.items():
+        r = H.debug_compare_closed(40, 2.0, 55, 2.0, max_evals=max_evals)
+        assert r["evals"] == max_evals and r["status"] == 4
+        assert tuple(float(r[k]).hex() for k in ("multiplier", "theta_null", "gap")) == bits, (max_evals, r)
+        assert r["theta_a"] == 20.0 and r["theta_b"] == 27.5
+    assert abs(float.fromhex(want[2][0]) + 3.0 / 11.0) <= 1e-16
+
+
 def test_the_numpy_reference_agrees_with_the_closed_form():
     """the stacked EM of tests/compare_problems.py on two singletons, and on the hand-made problem's closed-form pair"""
     prob, RA, RB, den_a, den_b = CP.small_problem()
