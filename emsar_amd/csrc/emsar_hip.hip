@@ -22,6 +22,7 @@
 //   presence.hpp      the presence test (a likelihood-ratio test per transcript on its resident set) and its C ABI
 //   profile.hpp       the profile-likelihood intervals (two confidence limits per transcript, each a root search over set solves) and their C ABI
 //   compare.hpp       the two-sample likelihood-ratio test (two contexts; per transcript a multiplier search over set solves of both samples) and its C ABI
+//   compare_genes.hpp the same test per gene (the null on the gene sum; per evaluation a loop over the gene's parts in both samples) and its C ABI
 //   asym.hpp          the asymptotic standard errors (the observed information of every component, factorised on the device) and their C ABI
 // Kernels (one translation unit, included below):
 //   kernels_tiled.hpp     k_pass_tiled_unit                      the hot one (the default above 2048 tiles): one workgroup per UNIT of up to
@@ -38,6 +39,8 @@
 //                         (solve_set_scaled); ProfileStep: the search step kernel and host share; IllinoisBracket
 //   kernels_compare.hpp   k_compare_sets                         one workgroup searches one transcript's multiplier: per evaluation a set solve of each sample
 //                         (solve_set_scaled); CompareStep: the search step kernel and host share
+//   kernels_compare_genes.hpp   k_compare_gene_sets              one workgroup searches one gene's multiplier: per evaluation every set part of
+//                         both samples solved with the members' den shifted (solve_gene_part; solve_one_set's DenEdit hook)
 //   kernels_boot.hpp      k_boot_draw, k_boot_accum, ...         the Poisson bootstrap (draws: boot_rng.hpp; sets: k_solve_sets_boot)
 //                         k_sub_draw, k_sub_scale                the depth subsampling: binomial draws, every replicate to its own depth
 //   kernels_genes.hpp     k_gene_sums, k_gene_finish             per-gene sums in a fixed order (gene_sums, the bootstrap's gene sd)
@@ -78,6 +81,7 @@
 #include "kernels_presence.hpp"
 #include "kernels_profile.hpp"
 #include "kernels_compare.hpp"
+#include "kernels_compare_genes.hpp"
 #include "kernels_cluster.hpp"
 #include "kernels_boot.hpp"
 #include "kernels_genes.hpp"
@@ -838,4 +842,5 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 #include "presence.hpp"   // the presence test and its entry points (after set_items.hpp: SetItemRunner, SetQuery, query_ok)
 #include "profile.hpp"    // the profile-likelihood intervals and their entry points (after presence.hpp: PresenceRun)
 #include "compare.hpp"    // the two-sample likelihood-ratio test and its entry points (after set_items.hpp: SetItemRunner, SetQuery)
-#include "asym.hpp"       // the asymptotic standard errors and their entry points (after fit.hpp: fit_ensure_csr, launch_gene_sums)
+#include "compare_genes.hpp"   // the gene-level two-sample test and its entry points (after compare.hpp: CompareRun, compare_reduce, same_structure)
+#include "asym.hpp"       //the asymptotic standard errors and their entry points (after fit.hpp: fit_ensure_csr, launch_gene_sums)

@@ -43,8 +43,10 @@
  * <prefix>.<i>.compare with, per transcript (or per transcript named in --compare-list FILE), its FPKM in sample i and in sample 0, log2 of their
  * ratio, the likelihood-ratio statistic Lambda of H0: theta_i = r * theta_0 (--compare-ratio r, default 1) with every sibling free in both samples,
  * its chi2_1 p-value, a status word and the evaluations spent (emsar_hip_compare with the solve's parameters: sample i is A, sample 0 is B).
- * Sample 0's solver inputs (R, E, den) are kept on the host and uploaded into a second context on each worker's device.  The other files do not
- * change with it.
+ * Sample 0's solver inputs (R, E, den) are kept on the host and uploaded into a second context on each worker's device.  With --g2t every
+ * sample i >= 1 also writes <prefix>.<i>.gcompare: per gene, in the order of .gfpkm, the gene sums of FPKM in sample i and in sample 0, log2 of
+ * their ratio, Lambda of H0: the gene's sum in i = r * its sum in 0 with the isoforms free in both samples, p, status, evaluations and parts
+ * (emsar_hip_compare_genes); --compare-list filters transcripts only.  The other files do not change with it.
  * --asymptotic answers "how sure is this FPKM" without resampling: <prefix>.<i>.asym holds, per transcript, the standard errors of FPKM and
  * TPM from the inverse of the observed information at the .fpkm column (emsar_hip_asymptotic), a status word and the sibling it is most
  * confounded with; with --g2t also <prefix>.<i>.gasym per gene and a usage_sd column.  Transcripts with FPKM <= --boundary-cut (5e-7) are held
@@ -153,6 +155,25 @@ static int write_compare(const char *path, const emsar_rsh *r, int32_t n_query, 
         put_num(f, "%lf", o->lambda[i]); fputc('\t', f);
         put_num(f, "%.6g", o->pvalue[i]);
         fprintf(f, "\t%s\t%d\n", o->status[i] >= 0 && o->status[i] < 5 ? word[o->status[i]] : "?", o->evals[i]);
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+/* .gcompare (--compare --g2t): one line per gene in the order of .gfpkm -- gene gFPKM gFPKM_ref log2FC Lambda p status evals parts; numbers
+ * as in .compare */
+static int write_gcompare(const char *path, const emsar_genes *g, const emsar_compare_gene_outputs *o) {
+    static const char *const word[6] = {"TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE"};
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "gene\tgFPKM\tgFPKM_ref\tlog2FC\tLambda\tp\tstatus\tevals\tparts\n");
+    for (int32_t k = 0; k < g->n_genes; k++) {
+        fprintf(f, "%s\t", g->names[k]);
+        put_num(f, "%lf", o->gene_a[k]); fputc('\t', f);
+        put_num(f, "%lf", o->gene_b[k]); fputc('\t', f);
+        put_num(f, "%lf", o->log2fc[k]); fputc('\t', f);
+        put_num(f, "%lf", o->lambda[k]); fputc('\t', f);
+        put_num(f, "%.6g", o->pvalue[k]);
+        fprintf(f, "\t%s\t%d\t%d\n", o->status[k] >= 0 && o->status[k] < 6 ? word[o->status[k]] : "?", o->evals[k], o->parts[k]);
     }
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
@@ -409,6 +430,23 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         }
         free(cv); free(ci);
         if (rc) goto done;
+        /* with --g2t the same question per gene (emsar_hip_compare_genes: this context's gene map serves both samples): .gcompare */
+        if (G) {
+            const size_t Ga = NG > 0 ? NG : 1;
+            double *gv = (double *)malloc(Ga * 8 * 5);
+            int32_t *gi = (int32_t *)malloc(Ga * 4 * 3);
+            const emsar_compare_gene_outputs go = {gv, gv ? gv + NG : NULL, gv ? gv + 2 * NG : NULL, gv ? gv + 3 * NG : NULL, gv ? gv + 4 * NG : NULL, NULL,
+                                                   NULL, NULL, NULL, gi, gi ? gi + NG : NULL, gi ? gi + 2 * NG : NULL};
+            if (!gv || !gi) rc = EMSAR_HOST_ERR_OOM;
+            else if ((rc = emsar_hip_compare_genes(ctx, w->ref_ctx, &p, &cp, (int32_t)NG, NULL, &go, NULL)))
+                fprintf(stderr, "alnfile[%d]: compare_genes: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+            else {
+                snprintf(path, sizeof path, "%s/%s.%d.gcompare", cfg->outdir, cfg->prefix, i);
+                if ((rc = write_gcompare(path, G, &go))) fprintf(stderr, "can't write %s\n", path);
+            }
+            free(gv); free(gi);
+            if (rc) goto done;
+        }
     }
     /* ---- asymptotic standard errors (--asymptotic): the inverse of the observed information at the printed FPKM, on the device ---- */
     if (cfg->asymptotic) {
@@ -618,7 +656,9 @@ static void usage(const char *a0) {
             "      --compare             with -M and at least two samples: every sample i >= 1 also writes <prefix>.<i>.compare: per transcript its FPKM\n"
             "                            in sample i and in sample 0, log2 of the ratio, the likelihood-ratio statistic Lambda of equal abundance\n"
             "                            (siblings free in both samples), its p-value, a status word (TESTED, BOTH_ABSENT, OUTSIDE, NOT_RESIDENT,\n"
-            "                            UNCONVERGED) and the evaluations spent\n"
+            "                            UNCONVERGED) and the evaluations spent; with --g2t also <prefix>.<i>.gcompare: per gene, in the order of\n"
+            "                            .gfpkm, the same test of the gene's summed FPKM with its isoforms free (status TOO_LARGE: more than 64\n"
+            "                            connected sets and lone transcripts in one sample), the evaluations and the parts searched over\n"
             "      --compare-ratio <r>   with --compare: test theta_i = r * theta_0 (default 1; a fold change or a size factor)\n"
             "      --compare-list <file> with --compare: only the transcripts named in the file, one name per line\n"
             "      --asymptotic          also write <prefix>.<i>.asym: per transcript the asymptotic standard error of FPKM and TPM from the inverse of\n"

@@ -321,15 +321,18 @@ struct SetSolved { SetLds L; const double *res; int passes, converged; double de
 // KEEP (k_solve_sets_drop): local transcript `drop` (-1 = none) is taken out of the problem -- its den is 0 in LDS, so it starts at 0
 // and stays there, as a transcript outside F does --, the result stays in LDS and is described in *kept for the caller, theta_g is
 // written only when nothing is dropped and st is not written.  scale != 0 (k_profile_sets): `drop` stays in the problem with its den
-// taken as scale * den in LDS.  With the defaults none of this exists in the generated code.
-template <int THREADS, bool KEEP = false>
+// taken as scale * den in LDS.  DenEdit (k_compare_gene_sets): edit(library tid, den) is the den of every local transcript as it goes
+// into LDS -- the hook that shifts den of several transcripts at once; it goes with KEEP, and theta_g is never written.  With the
+// defaults none of this exists in the generated code.
+struct NoDenEdit { static constexpr bool kActive = false; __device__ double operator()(int32_t, double dn) const { return dn; } };
+template <int THREADS, bool KEEP = false, class DenEdit = NoDenEdit>
 __device__ __forceinline__ void solve_one_set(const emsar::SetDesc d, const int32_t *__restrict__ g_tid,
                                               const double *__restrict__ g_u, const double *__restrict__ row_w,
                                               const uint16_t *__restrict__ rp_g, const uint16_t *__restrict__ ent_g,
                                               const uint16_t *__restrict__ cp_g, const uint16_t *__restrict__ crow_g,
                                               const double *__restrict__ den_g, double *__restrict__ theta_g,
                                               SetStat *__restrict__ st, SetSolveParams P, int drop = -1, SetSolved *kept = nullptr,
-                                              double scale = 0.0) {
+                                              double scale = 0.0, const DenEdit edit = DenEdit()) {
     extern __shared__ double smem[];
     const int nt = (int)d.n_t, nr = (int)d.n_r, nnz = (int)d.nnz;
     double *A = smem, *B = A + nt, *Cc = B + nt;
@@ -341,6 +344,7 @@ __device__ __forceinline__ void solve_one_set(const emsar::SetDesc d, const int3
     for (int i = threadIdx.x; i < nt; i += THREADS) {
         double dn = den_g[g_tid[d.tid_off + i]];
         if (KEEP && i == drop) dn = scale == 0.0 ? 0.0 : dn * scale;
+        if (DenEdit::kActive) dn = edit(g_tid[d.tid_off + i], dn);
         L.den[i] = dn; L.u[i] = g_u[d.tid_off + i];
         A[i] = dn > 0.0 ? 1.0 : 0.0;
     }
@@ -440,7 +444,7 @@ __device__ __forceinline__ void solve_one_set(const emsar::SetDesc d, const int3
         }
     }
     if (KEEP) {
-        if (drop < 0) for (int i = threadIdx.x; i < nt; i += THREADS) theta_g[g_tid[d.tid_off + i]] = res[i];
+        if (drop < 0 && !DenEdit::kActive) for (int i = threadIdx.x; i < nt; i += THREADS) theta_g[g_tid[d.tid_off + i]] = res[i];
         kept->L = L; kept->res = res; kept->passes = passes; kept->converged = converged; kept->delta = delta;
         return;
     }

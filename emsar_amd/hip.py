@@ -28,7 +28,7 @@ SYMBOLS = [
     "emsar_hip_model_fit", "emsar_hip_model_fit_host",
     "emsar_hip_presence", "emsar_hip_presence_pvalue_host",
     "emsar_hip_profile", "emsar_hip_profile_cut_host",
-    "emsar_hip_compare", "emsar_hip_compare_pvalue_host",
+    "emsar_hip_compare", "emsar_hip_compare_pvalue_host", "emsar_hip_compare_genes",
     "emsar_hip_asymptotic", "emsar_hip_asymptotic_host",
 ]
 
@@ -41,6 +41,10 @@ PROFILE_STATUS = ("TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVE
 # status of a transcript in the two-sample test (include/emsar_hip.h "two-sample test"), by value
 COMPARE_STATUS = ("TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED")
 COMPARE_OUTPUTS = ("lambda", "pvalue", "log2fc", "theta_a", "theta_b", "theta_null", "multiplier", "gap", "raw_lambda")
+
+# status of a gene in the gene-level two-sample test (include/emsar_hip.h "gene-level two-sample test"), by value
+COMPARE_GENE_STATUS = COMPARE_STATUS + ("TOO_LARGE",)
+COMPARE_GENE_OUTPUTS = ("lambda", "pvalue", "log2fc", "gene_a", "gene_b", "gene_null", "multiplier", "gap", "raw_lambda")
 
 # status of a transcript in the asymptotic standard errors (include/emsar_hip.h "asymptotic standard errors"), by value
 ASYM_STATUS = ("ESTIMATED", "BOUNDARY", "UNIDENTIFIABLE", "TOO_LARGE", "INFEASIBLE")
@@ -174,6 +178,22 @@ class CompareStats(C.Structure):
         return d
 
 
+class CompareGeneOutputs(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in ("lambda_", "pvalue", "log2fc", "gene_a", "gene_b", "gene_null", "multiplier", "gap",
+                                                     "raw_lambda")] + [(k, C.POINTER(C.c_int32)) for k in ("status", "evals", "parts")]
+
+
+class CompareGeneStats(C.Structure):
+    _fields_ = [("n_status", C.c_int64 * 6), ("items_launched", C.c_int64), ("evals_sum", C.c_int64), ("passes_sum", C.c_int64),
+                ("evals_max", C.c_int32), ("passes_max", C.c_int32), ("parts_max", C.c_int32), ("reserved0", C.c_int32),
+                ("min_raw_lambda", C.c_double), ("device_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["n_status"] = dict(zip(COMPARE_GENE_STATUS, d["n_status"]))
+        return d
+
+
 class AsymParams(C.Structure):
     _fields_ = [("boundary_cut", C.c_double), ("pivot_tol", C.c_double), ("block_tid", C.c_int32), ("reserved0", C.c_int32)]
 
@@ -279,6 +299,8 @@ def load_library():
     L.emsar_hip_compare.argtypes = [vp, vp, C.POINTER(EmParams), C.POINTER(CompareParams), C.c_int32, i32p, C.POINTER(CompareOutputs),
                                     C.POINTER(CompareStats)]
     L.emsar_hip_compare_pvalue_host.argtypes = [C.c_int64, f64p, f64p]
+    L.emsar_hip_compare_genes.argtypes = [vp, vp, C.POINTER(EmParams), C.POINTER(CompareParams), C.c_int32, i32p, C.POINTER(CompareGeneOutputs),
+                                          C.POINTER(CompareGeneStats)]
     L.emsar_hip_asymptotic.argtypes = [vp, f64p, C.POINTER(AsymParams), C.POINTER(AsymOutputs), C.POINTER(AsymStats)]
     L.emsar_hip_asymptotic_host.argtypes = [C.c_int64, C.c_int32, u64p, i32p, i32p, f64p, f64p, C.c_int32, i32p, C.POINTER(AsymParams),
                                             C.POINTER(AsymOutputs), C.POINTER(AsymStats)]
@@ -507,6 +529,27 @@ def debug_compare_closed(u_a, den_a, u_b, den_b, ratio=1.0, dev_tol=0.0, max_eva
     if rc != 0:
         raise EmsarHipError(rc, "debug_compare_closed")
     out = dict(zip(COMPARE_OUTPUTS, list(vals)))
+    out.update(status=status.value, evals=evals.value)
+    return out
+
+
+def debug_compare_genes_closed(u_a, den_a, u_b, den_b, ratio=1.0, dev_tol=0.0, max_evals=0):
+    """Host-only diagnostic: what compare_genes() gives a gene whose parts are all closed form -- one-transcript components with u_a[i]
+    reads and den_a[i] in sample A, u_b[j] and den_b[j] in B: the multiplier search as the host runs it for such genes (no GPU needed).
+    Returns a dict of scalars keyed like compare_genes()'s arrays."""
+    f = load_library().emsar_hip_debug_compare_genes_closed       # not declared in the header: bound here, not in load_library
+    f.restype = C.c_int
+    dp = C.POINTER(C.c_double)
+    f.argtypes = [C.c_int32, dp, dp, C.c_int32, dp, dp, C.POINTER(CompareParams), dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    ua, da, ub, db = (np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1)) for x in (u_a, den_a, u_b, den_b))
+    if ua.shape != da.shape or ub.shape != db.shape:
+        raise ValueError("u and den of a sample must have the same length")
+    cp, vals, status, evals = CompareParams(float(ratio), float(dev_tol), int(max_evals), 0), (C.c_double * 9)(), C.c_int32(), C.c_int32()
+    rc = f(len(ua), _p(ua, C.c_double), _p(da, C.c_double), len(ub), _p(ub, C.c_double), _p(db, C.c_double), C.byref(cp), vals,
+           C.byref(status), C.byref(evals))
+    if rc != 0:
+        raise EmsarHipError(rc, "debug_compare_genes_closed")
+    out = dict(zip(COMPARE_GENE_OUTPUTS, list(vals)))
     out.update(status=status.value, evals=evals.value)
     return out
 
@@ -810,6 +853,29 @@ class EmsarHip:
         st = CompareStats()
         self._chk(self._L.emsar_hip_compare(self._h, getattr(other, "_h", None), C.byref(p), C.byref(cp), nq, _p(q, C.c_int32), C.byref(o), C.byref(st)),
                   "compare")
+        out = {k: v[:nq] for k, v in res.items()}
+        out["stats"] = st
+        return out
+
+    def compare_genes(self, other, query=None, ratio=1.0, dev_tol=0.0, max_evals=0, max_iter=100000, accel=1, tol=1e-10, abs_floor=1e-6,
+                      check_every=8, count_floor=0.0, set_mode=0, zero_cut=0.0, abs_step=0.0, newton_after=0):
+        """Two-sample likelihood-ratio test of each queried gene (include/emsar_hip.h "gene-level two-sample test"): this context holds
+        sample A and the gene map (set_gene_map), `other` sample B; H0: the gene's sum of theta in A = ratio * its sum in B, with the
+        isoforms and every other transcript free in both samples.  query: gene ids in any order, repeats allowed, None = all genes; the
+        other parameters are compare()'s.  Returns a dict of arrays in query order: lambda, pvalue, log2fc, gene_a, gene_b, gene_null,
+        multiplier, gap, raw_lambda, status (index into COMPARE_GENE_STATUS), evals, parts, and stats.  After upload_sample on both; both
+        contexts are left as they were."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        cp = CompareParams(float(ratio), float(dev_tol), int(max_evals), 0)
+        q = None if query is None else np.ascontiguousarray(np.asarray(query, dtype=np.int32).reshape(-1))
+        nq = self.n_genes if q is None else len(q)
+        res = {k: np.zeros(max(nq, 1)) for k in COMPARE_GENE_OUTPUTS}
+        res.update({k: np.zeros(max(nq, 1), dtype=np.int32) for k in ("status", "evals", "parts")})
+        o = CompareGeneOutputs(*[_p(res[k], C.c_double) for k in COMPARE_GENE_OUTPUTS],
+                               *[_p(res[k], C.c_int32) for k in ("status", "evals", "parts")])
+        st = CompareGeneStats()
+        self._chk(self._L.emsar_hip_compare_genes(self._h, getattr(other, "_h", None), C.byref(p), C.byref(cp), nq, _p(q, C.c_int32), C.byref(o),
+                                                  C.byref(st)), "compare_genes")
         out = {k: v[:nq] for k, v in res.items()}
         out["stats"] = st
         return out

@@ -608,6 +608,69 @@ int emsar_hip_compare(emsar_hip_ctx *ctx_a, emsar_hip_ctx *ctx_b, const emsar_em
                       emsar_compare_stats *stats /* or NULL */);
 int emsar_hip_compare_pvalue_host(int64_t n, const double *lambda, double *p_out);
 
+/* ---- gene-level two-sample test: does a gene's total abundance differ between two samples? --------
+ * The per-transcript Lambdas above cannot be added up: a gene whose isoforms trade reads at an unchanged total gets several small
+ * p-values, a gene whose total moved but whose isoforms are confounded with each other gets none.  Here the null is imposed on the gene
+ * sum inside the likelihood, the isoforms staying free.  Contexts, structure check, p and cp (ratio r, dev_tol, max_evals) are those of
+ * emsar_hip_compare; the gene map is the one set on ctx_a (emsar_hip_set_gene_map) -- a map on ctx_b must be the same map -- and each
+ * context translates caller tids to its own library numbering.  For gene g:
+ *     members      in one sample the members of g that TAKE PART are those with den_t > 0 there; a member with den_t == 0 is held at 0
+ *                  in that sample.  They fall into PARTS: every packed connected set (set_mode 0) that holds at least one of them, and
+ *                  every member that is a one-transcript component (closed form: x = u / den', F = u log x - x den).  X = the sum of
+ *                  theta over the members, F = the sum of the parts' F (as the presence test defines it).
+ *     H1           everything free in both samples:                       F1 = F^A + F^B at lambda = 0
+ *     H0           X^A = r * X^B, all else (the isoforms too) free:        F0 = the maximum of F^A + F^B under that constraint
+ *     Lambda_g     = 2 (F1 - F0) >= 0,  p_g = erfc(sqrt(Lambda_g / 2)), chi2 with 1 degree of freedom.  THE P-VALUE IS CONSERVATIVE WHEN
+ *                  ONE GENE SUM SITS ON THE BOUNDARY (X = 0 in one sample): the statistic is then stochastically smaller than chi2_1.
+ *     path         the dual L(lambda) = max [F^A - lambda X^A] + max [F^B + r lambda X^B] falls apart into the parts: den_t of EVERY
+ *                  member becomes den_t + lambda in A and den_t - r lambda in B, lambda in (-min_A, min_B / r) with min_S the smallest
+ *                  den_t of the members taking part in S (beyond it the dual is unbounded).  On the side that shrinks the member(s) at
+ *                  the minimum take min_S * (1 - v), v in [0, 1) the point of the search, and the others den_t - v * min_S: both stay
+ *                  positive in floating point.  Each set part is one solve with the shifted den in LDS -- same solver, start and
+ *                  stopping rule as solve --, F summed with the ORIGINAL den.  g(lambda) = X^A - r X^B falls in lambda, L is convex
+ *                  with slope -g.
+ *     search       emsar_hip_compare's, unchanged, with den_tA := min_A, den_tB := min_B and the gene sums for the two values of t: one
+ *                  workgroup runs it, an evaluation loops over the set parts of A, then of B (each side by the smallest caller tid of a
+ *                  part's members), then the closed-form parts.  A gene whose parts are all closed form is searched on the host and
+ *                  nothing is launched for it.
+ *     outputs      lambda, raw_lambda, multiplier, gap as emsar_hip_compare defines them; gene_a, gene_b = X^A, X^B at lambda = 0;
+ *                  gene_null = the last X^A; log2fc = log2(gene_a / (r gene_b)), +-inf when exactly one sum is 0, NaN when both are;
+ *                  parts = the set and closed-form parts of both samples together
+ * status, per gene (EMSAR_COMPARE_* and EMSAR_GENE_COMPARE_TOO_LARGE):
+ *     TESTED        outputs as above
+ *     BOTH_ABSENT   both gene sums at lambda = 0 are exactly 0: Lambda 0, p 1, evals 1
+ *     OUTSIDE       in either sample no member has den > 0, or the gene has no transcript.  Every numeric output NaN (evals 0, parts 0)
+ *     NOT_RESIDENT  a member taking part lies in a streamed or a cluster set in either sample, one component holds most transcripts,
+ *                   or set_mode = 1.  Every numeric output NaN (evals 0, parts 0)
+ *     TOO_LARGE     more than 64 parts in either sample: one workgroup's work is bounded by 2 * 64 * max_evals * max_iter passes.
+ *                   Every numeric output NaN (evals 0, parts 0)
+ *     UNCONVERGED   values are given, but a solve hit max_iter or the search hit max_evals
+ * Outputs are indexed by query position (by gene id when query_genes is NULL; n_query is then ignored); repeats and any order are
+ * allowed.  A gene's result depends on its parts, p and cp alone -- not on what else is asked, the batch, the layout, MERGE_ROWS or the
+ * library's numbering.  Both contexts are left as they were: a following solve, presence, profile or compare on either returns the
+ * same bits.  ERR_STATE when either context is before upload_sample or ctx_a has no gene map; ERR_ARG for what emsar_hip_compare
+ * rejects, a different map on ctx_b and a gene id outside 0 .. n_genes-1; ERR_NUMERIC for a non-finite F at lambda = 0.
+ * EMSAR_HIP_COMPARE_GENES_BATCH = items per launch and class (a testing aid; the bits do not change). */
+enum { EMSAR_GENE_COMPARE_TOO_LARGE = 5 };                              /* the statuses above, and this one */
+typedef struct {
+    double  *lambda, *pvalue, *log2fc, *gene_a, *gene_b, *gene_null, *multiplier, *gap, *raw_lambda;       /* [n_query]; may each be NULL */
+    int32_t *status, *evals, *parts;                                        /* [n_query] EMSAR_COMPARE_*; evaluations; parts of both samples */
+} emsar_compare_gene_outputs;
+typedef struct {
+    int64_t n_status[6];          /* distinct queried genes per status */
+    int64_t items_launched;       /* workgroups: one search each */
+    int64_t evals_sum;            /* evaluations summed over the searches on the device */
+    int64_t passes_sum;           /* passes summed over their solves, every part of both samples */
+    int32_t evals_max, passes_max; /* the search with the most evaluations / the most passes */
+    int32_t parts_max, reserved0; /* the most parts of a gene that was searched */
+    double  min_raw_lambda;       /* the most negative Lambda before clamping, 0 if none was negative */
+    double  device_ms;            /* device time of the searches (HIP events) */
+    double  total_ms;             /* wall time of the call, a first call's set building included */
+} emsar_compare_gene_stats;
+int emsar_hip_compare_genes(emsar_hip_ctx *ctx_a, emsar_hip_ctx *ctx_b, const emsar_em_params *p, const emsar_compare_params *cp /* or NULL */,
+                            int32_t n_query, const int32_t *query_genes /* NULL = all genes */, const emsar_compare_gene_outputs *out /* or NULL */,
+                            emsar_compare_gene_stats *stats /* or NULL */);
+
 /* ---- asymptotic standard errors: the inverse of the observed information at the MLE ---------------
  * How sure is theta_t, without resampling?  For a theta that maximises the likelihood of the current sample, the observed information
  * of the ACTIVE transcripts is J_ij = sum_c m_ci m_cj R_c / S_c^2 (m_ci = how often i stands in row c); its inverse is the asymptotic

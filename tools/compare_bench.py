@@ -1,13 +1,15 @@
 """Cost of the two-sample test (emsar_hip_compare) on bench.py's time_to_mle segment problem against one solve; prints one JSON object.
 
-    python tools/compare_bench.py [--rounds 3] [--max-iter 20000] [--max-evals 40] [--seed 5] [--out FILE]
+    python tools/compare_bench.py [--genes] [--rounds 3] [--max-iter 20000] [--max-evals 40] [--seed 5] [--out FILE]
 
 Sample A is the problem as it stands (same seeds, 100 k transcripts in families); sample B is a Poisson redraw of A's row weights (a
 technical replicate: the null holds for every transcript).  Both are uploaded into contexts of their own and solved once (the first
 solve finds and packs the sets); then every transcript is compared, --rounds times.  Reported: wall and device ms of the best call (HIP
 events around the searches), transcripts per status, evaluations per search (mean, max), the wall time of one solve of A in the same
 process and the ratio, the share of TESTED transcripts with p < 0.05 (about 0.05 or less under the null), and whether a solve after
-the calls returns the bits it returned before."""
+the calls returns the bits it returned before.
+--genes: emsar_hip_compare_genes instead, the generator's families as genes (boot_bench.family_sizes): the same figures per gene, and
+the most parts a gene had.  A record, never a test threshold."""
 import argparse
 import json
 import os
@@ -27,9 +29,10 @@ def main():
     ap.add_argument("--max-iter", type=int, default=20000)
     ap.add_argument("--max-evals", type=int, default=40)
     ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--genes", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
-    from boot_bench import segment_problem
+    from boot_bench import family_sizes, segment_problem
     from emsar_amd import EmsarHip
     n_tx, rp, ci, R, E = segment_problem()
     RB = np.random.default_rng(a.seed).poisson(R).astype(np.int32)
@@ -39,6 +42,10 @@ def main():
         for dev, w in ((A, R), (B, RB)):
             dev.upload_structure(n_tx, rp, ci)
             dev.upload_sample(w, E, None)
+        if a.genes:
+            sizes = family_sizes(n_tx)
+            A.set_gene_map(np.repeat(np.arange(len(sizes), dtype=np.int32), sizes), len(sizes))
+            out.update(call="compare_genes", n_genes=int(len(sizes)))
         th, _ = A.solve(**solve)                             # finds and packs the sets, warms up
         B.solve(**solve)
         solves = []
@@ -49,7 +56,7 @@ def main():
         runs = []
         for _ in range(a.rounds):
             t0 = time.perf_counter()
-            r = A.compare(B, max_evals=a.max_evals, **solve)
+            r = (A.compare_genes if a.genes else A.compare)(B, max_evals=a.max_evals, **solve)
             d = r["stats"].as_dict()
             d["wall_s"] = time.perf_counter() - t0
             runs.append(d)
@@ -60,6 +67,8 @@ def main():
                    evals_max=best["evals_max"], passes_max=best["passes_max"], min_raw_lambda=best["min_raw_lambda"],
                    solve_wall_ms=1e3 * min(solves), wall_over_solve=best["wall_s"] / min(solves),
                    share_p_below_0_05=float(np.mean(r["pvalue"][tested] < 0.05)) if tested.any() else None)
+        if a.genes:
+            out["parts_max"] = best["parts_max"]
         th2, _ = A.solve(**solve)
         out["solve_unchanged"] = bool(th2.tobytes() == th.tobytes())
     txt = json.dumps(out, indent=1)
