@@ -35,16 +35,72 @@ inline CompareSearchParams compare_search_params(const emsar_compare_params &cp)
     return CompareSearchParams{cp.ratio == 0.0 ? 1.0 : cp.ratio, cp.dev_tol > 0.0 ? cp.dev_tol : 1e-4, cp.max_evals > 0 ? cp.max_evals : 40, 0};
 }
 
-struct CompareGenesRun {
+// The members taking part (den > 0) of one gene in one sample, by part.  min_den_live = the smallest den of those that are not
+// closed-form members without reads (the gene profile's end-of-range rule asks for it)
+struct GeneSideParts {
+    std::vector<CompareGenePart> sets;
+    std::vector<CompareGeneClosed> closed;
+    double min_den = INFINITY, min_den_live = INFINITY;
+    int members = 0;
+    bool not_resident = false, own_reads = false;      // own_reads: a member taking part has reads only it explains
+    int count() const { return (int)(sets.size() + closed.size()); }
+};
+
+// The queried genes of a gene-level call and their members, and the grouping of a gene's members into parts (compare_genes.hpp,
+// profile_genes.hpp)
+struct GeneQueryMembers {
+    std::vector<int32_t> genes;          // the queried genes, each once
+    std::vector<int32_t> slot_of_gene;   // [n_genes] -> genes / res, -1 = not queried
+    std::vector<int64_t> gp;             // genes[k]'s members: member_tids[gp[k] .. gp[k+1]), ascending caller tid
+    std::vector<int32_t> member_tids;
+
+    void list_members(const GeneMap &map, int32_t nq, const int32_t *query /* null = all in order */) {
+        const int32_t ng = map.n_genes;
+        const std::vector<int32_t> &of_tx = map.h_gene_of_tx;
+        slot_of_gene.assign((size_t)ng, -1);
+        for (int32_t i = 0; i < nq; i++) {
+            const int32_t g = query ? query[i] : i;
+            if (slot_of_gene[(size_t)g] < 0) { slot_of_gene[(size_t)g] = (int32_t)genes.size(); genes.push_back(g); }
+        }
+        gp.assign(genes.size() + 1, 0);
+        for (int32_t g : of_tx) if (g >= 0 && slot_of_gene[(size_t)g] >= 0) gp[(size_t)slot_of_gene[(size_t)g] + 1]++;
+        for (size_t k = 0; k < genes.size(); k++) gp[k + 1] += gp[k];
+        member_tids.resize((size_t)gp[genes.size()]);
+        std::vector<int64_t> fill(gp.begin(), gp.end() - 1);
+        for (int32_t t = 0; t < (int32_t)of_tx.size(); t++) {
+            const int32_t g = of_tx[(size_t)t];
+            if (g >= 0 && slot_of_gene[(size_t)g] >= 0) member_tids[(size_t)fill[(size_t)slot_of_gene[(size_t)g]]++] = t;
+        }
+    }
+
+    // gene slot k in the sample of q: the members with den > 0 there, ascending caller tid, so parts come by their smallest tid
+    GeneSideParts side_parts(const SetQuery &q, size_t k, int32_t side) const {
+        GeneSideParts s;
+        for (int64_t m = gp[k]; m < gp[k + 1]; m++) {
+            const SetQuery::Cand &c = q.cand[(size_t)q.cand_of_lib[(size_t)q.lib_of(member_tids[(size_t)m])]];
+            if (c.standing == SetQuery::OUTSIDE) continue;             // den == 0: held at 0 in this sample
+            if (c.standing == SetQuery::NOT_RESIDENT) { s.not_resident = true; continue; }
+            const double den = q.h_den[(size_t)c.lib];
+            s.min_den = std::min(s.min_den, den);
+            s.members++;
+            if (c.standing == SetQuery::CLOSED) {
+                s.closed.push_back(CompareGeneClosed{c.u, den});
+                if (c.u > 0.0) { s.min_den_live = std::min(s.min_den_live, den); s.own_reads = true; }
+                continue;
+            }
+            s.min_den_live = std::min(s.min_den_live, den);
+            s.own_reads |= c.own_reads;
+            bool seen = false;
+            for (const CompareGenePart &p : s.sets) seen |= p.set == c.set && p.cls == c.cls;
+            if (!seen) s.sets.push_back(CompareGenePart{side, c.set, c.cls, 0});
+        }
+        return s;
+    }
+};
+
+struct CompareGenesRun : GeneQueryMembers {
     struct Result : CompareResult { int32_t parts = 0; };      // per queried gene; theta_a / theta_b / theta_null hold the gene sums
-    // the members of one gene taking part in one sample, by part
-    struct SideParts {
-        std::vector<CompareGenePart> sets;
-        std::vector<CompareGeneClosed> closed;
-        double min_den = INFINITY;
-        bool not_resident = false;
-        int count() const { return (int)(sets.size() + closed.size()); }
-    };
+    using SideParts = GeneSideParts;
     emsar_hip_ctx *const ctx;            // ctx_a: its gene map, its streams and events
     emsar_hip_ctx *const ctx_b;
     const emsar_em_params *const p;      // the caller's solver parameters (SetQuery fills in the defaults)
@@ -52,10 +108,6 @@ struct CompareGenesRun {
     const int32_t *const query;          // gene ids, null = all in order
     const emsar_compare_gene_outputs out;
     CompareSearchParams Q;
-    std::vector<int32_t> genes;          // the queried genes, each once
-    std::vector<int32_t> slot_of_gene;   // [n_genes] -> genes / res, -1 = not queried
-    std::vector<int64_t> gp;             // genes[k]'s members: member_tids[gp[k] .. gp[k+1]), ascending caller tid
-    std::vector<int32_t> member_tids;
     std::vector<Result> res;
     std::vector<CompareGenePart> h_parts;
     std::vector<CompareGeneClosed> h_closed;
@@ -71,42 +123,6 @@ struct CompareGenesRun {
           runner(a, "EMSAR_HIP_COMPARE_GENES_BATCH", "compare_genes: an item lies outside its class's sets") {}
 
     int32_t gene_of_query(int32_t i) const { return query ? query[i] : i; }
-
-    void list_members() {
-        const int32_t ng = ctx->genes.n_genes;
-        const std::vector<int32_t> &of_tx = ctx->genes.h_gene_of_tx;
-        slot_of_gene.assign((size_t)ng, -1);
-        for (int32_t i = 0; i < nq; i++) {
-            const int32_t g = gene_of_query(i);
-            if (slot_of_gene[(size_t)g] < 0) { slot_of_gene[(size_t)g] = (int32_t)genes.size(); genes.push_back(g); }
-        }
-        gp.assign(genes.size() + 1, 0);
-        for (int32_t g : of_tx) if (g >= 0 && slot_of_gene[(size_t)g] >= 0) gp[(size_t)slot_of_gene[(size_t)g] + 1]++;
-        for (size_t k = 0; k < genes.size(); k++) gp[k + 1] += gp[k];
-        member_tids.resize((size_t)gp[genes.size()]);
-        std::vector<int64_t> fill(gp.begin(), gp.end() - 1);
-        for (int32_t t = 0; t < (int32_t)of_tx.size(); t++) {
-            const int32_t g = of_tx[(size_t)t];
-            if (g >= 0 && slot_of_gene[(size_t)g] >= 0) member_tids[(size_t)fill[(size_t)slot_of_gene[(size_t)g]]++] = t;
-        }
-    }
-
-    // gene slot k in the sample of q: the members with den > 0 there, ascending caller tid, so parts come by their smallest tid
-    SideParts side_parts(const SetQuery &q, size_t k, int32_t side) const {
-        SideParts s;
-        for (int64_t m = gp[k]; m < gp[k + 1]; m++) {
-            const SetQuery::Cand &c = q.cand[(size_t)q.cand_of_lib[(size_t)q.lib_of(member_tids[(size_t)m])]];
-            if (c.standing == SetQuery::OUTSIDE) continue;             // den == 0: held at 0 in this sample
-            if (c.standing == SetQuery::NOT_RESIDENT) { s.not_resident = true; continue; }
-            const double den = q.h_den[(size_t)c.lib];
-            s.min_den = std::min(s.min_den, den);
-            if (c.standing == SetQuery::CLOSED) { s.closed.push_back(CompareGeneClosed{c.u, den}); continue; }
-            bool seen = false;
-            for (const CompareGenePart &p : s.sets) seen |= p.set == c.set && p.cls == c.cls;
-            if (!seen) s.sets.push_back(CompareGenePart{side, c.set, c.cls, 0});
-        }
-        return s;
-    }
 
     static CompareSide side_of(const emsar_hip_ctx *c) { return CompareRun::side_of(c); }
 
@@ -222,7 +238,7 @@ struct CompareGenesRun {
     }
 
     int run() {
-        list_members();
+        list_members(ctx->genes, nq, query);
         SetQuery qa(ctx, p, (int32_t)member_tids.size(), member_tids.data()), qb(ctx_b, p, (int32_t)member_tids.size(), member_tids.data());
         int rc;
         if ((rc = qa.plan()) || (rc = qa.classify())) return rc;

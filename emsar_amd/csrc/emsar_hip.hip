@@ -82,6 +82,7 @@
 #include "kernels_profile.hpp"
 #include "kernels_compare.hpp"
 #include "kernels_compare_genes.hpp"
+#include "kernels_profile_genes.hpp"
 #include "kernels_cluster.hpp"
 #include "kernels_boot.hpp"
 #include "kernels_genes.hpp"
@@ -843,4 +844,5 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 #include "profile.hpp"    // the profile-likelihood intervals and their entry points (after presence.hpp: PresenceRun)
 #include "compare.hpp"    // the two-sample likelihood-ratio test and its entry points (after set_items.hpp: SetItemRunner, SetQuery)
 #include "compare_genes.hpp"   // the gene-level two-sample test and its entry points (after compare.hpp: CompareRun, compare_reduce, same_structure)
+#include "profile_genes.hpp"   // the gene-level profile intervals and the gene presence test (after compare_genes.hpp: GeneQueryMembers)
 #include "asym.hpp"       //the asymptotic standard errors and their entry points (after fit.hpp: fit_ensure_csr, launch_gene_sums)

@@ -38,7 +38,10 @@
  * --profile answers "how much of this isoform could be present": <prefix>.<i>.profile holds, per transcript (or per transcript named in
  * --profile-list FILE), the limits of its profile-likelihood interval at --profile-level (0.95) in the units of the FPKM column, the
  * presence test's Lambda and a status word (emsar_hip_profile with the solve's parameters).  The interval is one-sided by itself where the
- * transcript cannot be told from absent, FPKM 0 included.  The other files do not change with it.
+ * transcript cannot be told from absent, FPKM 0 included.  With --g2t also <prefix>.<i>.gprofile: per gene, in the order of .gfpkm, its gFPKM,
+ * the limits of the profile-likelihood interval of the gene's total (the isoforms free), the gene presence test's Lambda, the p-value bound
+ * P(chi2_members > Lambda), the members taking part and a status word (emsar_hip_profile_genes; --profile-list filters transcripts only).  The
+ * other files do not change with it.
  * --compare (with -M and at least two samples) answers "does this isoform's abundance differ from sample 0": every sample i >= 1 writes
  * <prefix>.<i>.compare with, per transcript (or per transcript named in --compare-list FILE), its FPKM in sample i and in sample 0, log2 of their
  * ratio, the likelihood-ratio statistic Lambda of H0: theta_i = r * theta_0 (--compare-ratio r, default 1) with every sibling free in both samples,
@@ -174,6 +177,24 @@ static int write_gcompare(const char *path, const emsar_genes *g, const emsar_co
         put_num(f, "%lf", o->lambda[k]); fputc('\t', f);
         put_num(f, "%.6g", o->pvalue[k]);
         fprintf(f, "\t%s\t%d\t%d\n", o->status[k] >= 0 && o->status[k] < 6 ? word[o->status[k]] : "?", o->evals[k], o->parts[k]);
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+/* .gprofile (--profile --g2t): one line per gene in the order of .gfpkm -- gene gFPKM lower upper Lambda p members status; numbers as in
+ * .profile, p as in .compare */
+static int write_gprofile(const char *path, const emsar_genes *g, const double *gfpkm, const emsar_profile_gene_outputs *o) {
+    static const char *const word[6] = {"TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE"};
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "gene\tgFPKM\tlower\tupper\tLambda\tp\tmembers\tstatus\n");
+    for (int32_t k = 0; k < g->n_genes; k++) {
+        fprintf(f, "%s\t%lf\t", g->names[k], gfpkm[k]);
+        put_num(f, "%lf", o->lower[k]); fputc('\t', f);
+        put_num(f, "%lf", o->upper[k]); fputc('\t', f);
+        put_num(f, "%lf", o->lambda[k]); fputc('\t', f);
+        put_num(f, "%.6g", o->pvalue[k]);
+        fprintf(f, "\t%d\t%s\n", o->members[k], o->status[k] >= 0 && o->status[k] < 6 ? word[o->status[k]] : "?");
     }
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
@@ -395,6 +416,24 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         }
         free(pv); free(pi);
         if (rc) goto done;
+        /* with --g2t the same question per gene, and whether the gene is needed at all (emsar_hip_profile_genes; --profile-list names
+         * transcripts and does not filter it): .gprofile */
+        if (G) {
+            const size_t Ga = NG > 0 ? NG : 1;
+            double *gv = (double *)malloc(Ga * 8 * 4);
+            int32_t *gi = (int32_t *)malloc(Ga * 4 * 2);
+            const emsar_profile_gene_outputs go = {gv, gv ? gv + NG : NULL, NULL, NULL, gv ? gv + 2 * NG : NULL, gv ? gv + 3 * NG : NULL, NULL,
+                                                   gi, NULL, NULL, gi ? gi + NG : NULL};
+            if (!gv || !gi) rc = EMSAR_HOST_ERR_OOM;
+            else if ((rc = emsar_hip_profile_genes(ctx, &p, &pp, (int32_t)NG, NULL, &go, NULL)))
+                fprintf(stderr, "alnfile[%d]: profile_genes: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+            else {
+                snprintf(path, sizeof path, "%s/%s.%d.gprofile", cfg->outdir, cfg->prefix, i);
+                if ((rc = write_gprofile(path, G, gsums, &go))) fprintf(stderr, "can't write %s\n", path);
+            }
+            free(gv); free(gi);
+            if (rc) goto done;
+        }
     }
     /* ---- two-sample test (--compare): this sample (A) against sample 0 (B, in a second context on this device), on the device ---- */
     if (cfg->compare && i > 0) {
@@ -649,10 +688,12 @@ static void usage(const char *a0) {
             "                            and the sibling that takes over most of its reads, with the share it takes\n"
             "      --presence-list <file> with --presence: test only the transcripts named in the file, one name per line\n"
             "      --profile             also write <prefix>.<i>.profile: per transcript the lower and upper limit of its profile-likelihood interval, the\n"
-            "                            presence test's Lambda and a status word (TWO_SIDED, LOWER_ZERO, OUTSIDE, NOT_RESIDENT, UNCONVERGED); valid at FPKM 0\n"
+            "                            presence test's Lambda and a status word (TWO_SIDED, LOWER_ZERO, OUTSIDE, NOT_RESIDENT, UNCONVERGED); valid at FPKM 0;\n"
+            "                            with --g2t also <prefix>.<i>.gprofile: per gene, in the order of .gfpkm, the limits of its total's interval, the gene\n"
+            "                            presence test's Lambda, its p-value bound, the members taking part and a status word (also TOO_LARGE)\n"
             "      --profile-level <l>   with --profile: the confidence level, 0 < l < 1 (default 0.95)\n"
             "      --profile-evals <n>   with --profile: at most n set solves per limit (default 40); a search that needs more is UNCONVERGED\n"
-            "      --profile-list <file> with --profile: only the transcripts named in the file, one name per line\n"
+            "      --profile-list <file> with --profile: only the transcripts named in the file, one name per line (.gprofile always holds every gene)\n"
             "      --compare             with -M and at least two samples: every sample i >= 1 also writes <prefix>.<i>.compare: per transcript its FPKM\n"
             "                            in sample i and in sample 0, log2 of the ratio, the likelihood-ratio statistic Lambda of equal abundance\n"
             "                            (siblings free in both samples), its p-value, a status word (TESTED, BOTH_ABSENT, OUTSIDE, NOT_RESIDENT,\n"

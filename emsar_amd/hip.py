@@ -29,6 +29,7 @@ SYMBOLS = [
     "emsar_hip_presence", "emsar_hip_presence_pvalue_host",
     "emsar_hip_profile", "emsar_hip_profile_cut_host",
     "emsar_hip_compare", "emsar_hip_compare_pvalue_host", "emsar_hip_compare_genes",
+    "emsar_hip_profile_genes", "emsar_hip_gene_presence_pvalue_host",
     "emsar_hip_asymptotic", "emsar_hip_asymptotic_host",
 ]
 
@@ -45,6 +46,10 @@ COMPARE_OUTPUTS = ("lambda", "pvalue", "log2fc", "theta_a", "theta_b", "theta_nu
 # status of a gene in the gene-level two-sample test (include/emsar_hip.h "gene-level two-sample test"), by value
 COMPARE_GENE_STATUS = COMPARE_STATUS + ("TOO_LARGE",)
 COMPARE_GENE_OUTPUTS = ("lambda", "pvalue", "log2fc", "gene_a", "gene_b", "gene_null", "multiplier", "gap", "raw_lambda")
+
+# status of a gene's profile-likelihood interval (include/emsar_hip.h "gene-level profile intervals"), by value
+PROFILE_GENE_STATUS = PROFILE_STATUS + ("TOO_LARGE",)
+PROFILE_GENE_OUTPUTS = ("lower", "upper", "dev_lower", "dev_upper", "lambda", "pvalue", "gene_hat")
 
 # status of a transcript in the asymptotic standard errors (include/emsar_hip.h "asymptotic standard errors"), by value
 ASYM_STATUS = ("ESTIMATED", "BOUNDARY", "UNIDENTIFIABLE", "TOO_LARGE", "INFEASIBLE")
@@ -194,6 +199,23 @@ class CompareGeneStats(C.Structure):
         return d
 
 
+class ProfileGeneOutputs(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in ("lower", "upper", "dev_lower", "dev_upper", "lambda_", "pvalue", "gene_hat")] + \
+               [(k, C.POINTER(C.c_int32)) for k in ("status", "evals", "parts", "members")]
+
+
+class ProfileGeneStats(C.Structure):
+    _fields_ = [("n_status", C.c_int64 * 6), ("items_launched", C.c_int64), ("evals_sum", C.c_int64), ("passes_sum", C.c_int64),
+                ("evals_max", C.c_int32), ("passes_max", C.c_int32), ("parts_max", C.c_int32), ("reserved0", C.c_int32),
+                ("min_raw_lambda", C.c_double), ("cut", C.c_double), ("baseline_ms", C.c_double), ("search_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["n_status"] = dict(zip(PROFILE_GENE_STATUS, d["n_status"]))
+        return d
+
+
 class AsymParams(C.Structure):
     _fields_ = [("boundary_cut", C.c_double), ("pivot_tol", C.c_double), ("block_tid", C.c_int32), ("reserved0", C.c_int32)]
 
@@ -301,6 +323,9 @@ def load_library():
     L.emsar_hip_compare_pvalue_host.argtypes = [C.c_int64, f64p, f64p]
     L.emsar_hip_compare_genes.argtypes = [vp, vp, C.POINTER(EmParams), C.POINTER(CompareParams), C.c_int32, i32p, C.POINTER(CompareGeneOutputs),
                                           C.POINTER(CompareGeneStats)]
+    L.emsar_hip_profile_genes.argtypes = [vp, C.POINTER(EmParams), C.POINTER(ProfileParams), C.c_int32, i32p, C.POINTER(ProfileGeneOutputs),
+                                          C.POINTER(ProfileGeneStats)]
+    L.emsar_hip_gene_presence_pvalue_host.argtypes = [C.c_int64, f64p, i32p, f64p]
     L.emsar_hip_asymptotic.argtypes = [vp, f64p, C.POINTER(AsymParams), C.POINTER(AsymOutputs), C.POINTER(AsymStats)]
     L.emsar_hip_asymptotic_host.argtypes = [C.c_int64, C.c_int32, u64p, i32p, i32p, f64p, f64p, C.c_int32, i32p, C.POINTER(AsymParams),
                                             C.POINTER(AsymOutputs), C.POINTER(AsymStats)]
@@ -552,6 +577,39 @@ def debug_compare_genes_closed(u_a, den_a, u_b, den_b, ratio=1.0, dev_tol=0.0, m
     out = dict(zip(COMPARE_GENE_OUTPUTS, list(vals)))
     out.update(status=status.value, evals=evals.value)
     return out
+
+
+def debug_profile_genes_closed(u, den, level=0.95, dev_tol=0.0, max_evals=0):
+    """Host-only diagnostic: what profile_genes() gives a gene whose parts are all closed form -- one-transcript components with u[i]
+    reads and den[i] each: the searches as the host runs them for such genes, the end-of-range rule included (no GPU needed).  Returns
+    a dict of scalars keyed like profile_genes()'s arrays, and evals_upper: the evaluations of the upper search alone."""
+    f = load_library().emsar_hip_debug_profile_genes_closed       # not declared in the header: bound here, not in load_library
+    f.restype = C.c_int
+    dp = C.POINTER(C.c_double)
+    f.argtypes = [C.c_int32, dp, dp, C.POINTER(ProfileParams), dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    uu, dd = (np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1)) for x in (u, den))
+    if uu.shape != dd.shape:
+        raise ValueError("u and den must have the same length")
+    pp, vals, status, evals = ProfileParams(float(level), float(dev_tol), int(max_evals), 0), (C.c_double * 8)(), C.c_int32(), C.c_int32()
+    rc = f(len(uu), _p(uu, C.c_double), _p(dd, C.c_double), C.byref(pp), vals, C.byref(status), C.byref(evals))
+    if rc != 0:
+        raise EmsarHipError(rc, "debug_profile_genes_closed")
+    out = dict(zip(PROFILE_GENE_OUTPUTS, list(vals)))
+    out.update(status=status.value, evals=evals.value, evals_upper=int(vals[7]))
+    return out
+
+
+def gene_presence_pvalue_host(lam, members):
+    """Host-only: the p-value bound of the gene presence test (include/emsar_hip.h "gene-level profile intervals"): P(chi2_k > Lambda)
+    with k = members, conservative whatever the weights of the chi-bar-square mixture are; 1 for Lambda <= 0, 0 for +inf, NaN for NaN
+    or k < 1.  No GPU needed."""
+    lam = np.ascontiguousarray(np.asarray(lam, dtype=np.float64).reshape(-1))
+    k = np.ascontiguousarray(np.broadcast_to(np.asarray(members, dtype=np.int32).reshape(-1), lam.shape))
+    out = np.zeros(max(len(lam), 1))
+    rc = load_library().emsar_hip_gene_presence_pvalue_host(len(lam), _p(lam, C.c_double), _p(k, C.c_int32), _p(out, C.c_double))
+    if rc != 0:
+        raise EmsarHipError(rc, "gene_presence_pvalue_host")
+    return out[:len(lam)]
 
 
 def profile_cut_host(level):
@@ -876,6 +934,28 @@ class EmsarHip:
         st = CompareGeneStats()
         self._chk(self._L.emsar_hip_compare_genes(self._h, getattr(other, "_h", None), C.byref(p), C.byref(cp), nq, _p(q, C.c_int32), C.byref(o),
                                                   C.byref(st)), "compare_genes")
+        out = {k: v[:nq] for k, v in res.items()}
+        out["stats"] = st
+        return out
+
+    def profile_genes(self, query=None, level=0.95, dev_tol=0.0, max_evals=0, max_iter=100000, accel=1, tol=1e-10, abs_floor=1e-6,
+                      check_every=8, count_floor=0.0, set_mode=0, zero_cut=0.0, abs_step=0.0, newton_after=0):
+        """Profile-likelihood interval of each queried gene's total and the gene presence test (include/emsar_hip.h "gene-level profile
+        intervals"): the values of the gene's sum of theta whose best achievable likelihood -- the isoforms and every other transcript
+        free -- lies within the chi2_1 cut of `level` of the maximum, and Lambda = the deviance of the sum 0.  query: gene ids in any
+        order, repeats allowed, None = all genes; the other parameters are profile()'s.  Returns a dict of arrays in query order: lower,
+        upper, dev_lower, dev_upper, lambda, pvalue, gene_hat, status (index into PROFILE_GENE_STATUS), evals, parts, members, and
+        stats.  After upload_sample and set_gene_map; the context is left as it was."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        pp = ProfileParams(float(level), float(dev_tol), int(max_evals), 0)
+        q = None if query is None else np.ascontiguousarray(np.asarray(query, dtype=np.int32).reshape(-1))
+        nq = self.n_genes if q is None else len(q)
+        ints = ("status", "evals", "parts", "members")
+        res = {k: np.zeros(max(nq, 1)) for k in PROFILE_GENE_OUTPUTS}
+        res.update({k: np.zeros(max(nq, 1), dtype=np.int32) for k in ints})
+        o = ProfileGeneOutputs(*[_p(res[k], C.c_double) for k in PROFILE_GENE_OUTPUTS], *[_p(res[k], C.c_int32) for k in ints])
+        st = ProfileGeneStats()
+        self._chk(self._L.emsar_hip_profile_genes(self._h, C.byref(p), C.byref(pp), nq, _p(q, C.c_int32), C.byref(o), C.byref(st)), "profile_genes")
         out = {k: v[:nq] for k, v in res.items()}
         out["stats"] = st
         return out

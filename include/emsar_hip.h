@@ -671,6 +671,84 @@ int emsar_hip_compare_genes(emsar_hip_ctx *ctx_a, emsar_hip_ctx *ctx_b, const em
                             int32_t n_query, const int32_t *query_genes /* NULL = all genes */, const emsar_compare_gene_outputs *out /* or NULL */,
                             emsar_compare_gene_stats *stats /* or NULL */);
 
+/* ---- gene-level profile intervals and the gene presence test --------------------------------------
+ * How much of gene g could be there, and is g needed to explain the reads at all?  Also where the gene sum is 0 or close to it, where
+ * the asymptotic errors do not hold and the bootstrap's percentile interval is [0, 0].  The per-transcript profile limits cannot be
+ * added up -- isoforms that are confounded with each other each get LOWER_ZERO and a wide upper while their sum may be pinned tightly
+ * by the reads --, and neither can the per-transcript presence Lambdas, for the reason given at the gene-level two-sample test.  For
+ * the sample of upload_structure + upload_sample, solver parameters p, the gene map of emsar_hip_set_gene_map, pp (level, dev_tol,
+ * max_evals and their defaults as in emsar_hip_profile) and q = the chi2_1 cut of emsar_hip_profile_cut_host, for gene g:
+ *     members, parts, X, F   exactly as emsar_hip_compare_genes defines them for one sample: the members with den_t > 0 take part; the
+ *                  parts are the packed sets that hold one and the one-transcript members in closed form, set parts by the smallest
+ *                  caller tid of their members, then closed-form parts by tid; mn = the smallest den of the members taking part;
+ *                  members (output) = how many take part
+ *     baseline     X_hat, F_hat = X and F with every den its own, computed through the code path of every later evaluation.
+ *                  gene_hat = X_hat agrees with gene_sums(solve) up to summation order
+ *     D_g(x)       = 2 (F_hat - max{F : X = x}), x >= 0
+ *     path         the maximiser of F - lambda X is the same problem with den_t + lambda on every member taking part, lambda in
+ *                  (-mn, inf); coordinate s = 1 + lambda / mn.  The member(s) at mn take mn * s in LDS, the others den_t + mn (s - 1):
+ *                  both stay positive in floating point.  Each set part is one solve -- same solver, start and stopping rule as solve
+ *                  --, F summed with the ORIGINAL den, X from the same reduction.  Each point (X(s), F(s)) lies on the profile curve;
+ *                  s > 1 is the lower side, 0 < s < 1 the upper side
+ *     search       emsar_hip_profile's, unchanged, with den_t := mn, theta_hat := X_hat and F_hat: the first guess uses n = X_hat mn,
+ *                  an upper bound of the gene's Poisson information, so the first step is short and the doubling takes over.  One
+ *                  workgroup runs one limit: at most max_evals evaluations of at most 64 set solves.  The reported limit is X of the
+ *                  last evaluation, dev_lower / dev_upper that evaluation's deviance
+ *     end of the range (upper side)   Z = the closed-form members with u = 0 reads, mn0 = their smallest den.  They add nothing to X for
+ *                  lambda > -mn0 and absorb any amount at lambda = -mn0 at a cost of mn0 per unit.  If mn0 is strictly below the den of
+ *                  every other member taking part, the first evaluation of the upper search is at s = 0 exactly (the others get
+ *                  den_t - mn0 > 0): if D_end < q then upper = X_end + (q - D_end) / (2 mn0), dev_upper = q, evals 1 -- beyond X_end the
+ *                  profile is linear --, otherwise the ordinary search runs with one evaluation less to spend.  A gene whose parts are
+ *                  all closed forms without reads gets upper = q / (2 mn), the transcript profile's rule.  Without this rule such
+ *                  genes never bracket
+ *     Lambda_g     = D_g(0): F_hat against the solve with den of EVERY member taken as 0 in LDS.  +inf (the gene is essential) when a
+ *                  member has reads only it explains (a folded single-transcript row, or a closed form with u > 0; decided before the
+ *                  launch) or when the drop leaves a row with reads that nothing explains; 0.0 when X_hat is exactly 0 (the baseline is
+ *                  then the maximum under X = 0).  Negative raw values are reported as 0, the most negative goes to the statistics
+ *     pvalue       the null X = 0 puts k = members parameters on the boundary: the statistic is a chi-bar-square mixture of
+ *                  chi2_0 .. chi2_k whose weights depend on the information matrix, NOT the transcript test's half/half mixture.
+ *                  Reported is the bound that is conservative whatever the weights, p = P(chi2_k > Lambda): with x = Lambda / 2,
+ *                  exp(-x) sum_{j < k/2} x^j / j! for even k, erfc(sqrt x) + exp(-x) sum_{j=1}^{(k-1)/2} x^(j-1/2) / Gamma(j+1/2) for odd
+ *                  k; 1 for Lambda <= 0, 0 for +inf, NaN for NaN or k < 1 (gene_presence_pvalue_host: the same function, no HIP call).
+ *                  THE DECISION lower = 0 IS MADE WITH THE chi2_1 CUT q AND IS THEREFORE ANTI-CONSERVATIVE FOR k > 1: lambda and members
+ *                  are reported so that a caller can apply a cut of their own
+ *     closed form  a gene whose parts are all closed form is finished on the host with the same search, nothing is launched for it
+ * status, per gene (EMSAR_PROFILE_* and EMSAR_GENE_PROFILE_TOO_LARGE):
+ *     TWO_SIDED     Lambda_g > q, both limits searched
+ *     LOWER_ZERO    Lambda_g <= q: lower = 0.0 exactly, dev_lower = Lambda_g; upper searched
+ *     OUTSIDE       no member with den > 0, or the gene has no transcript
+ *     NOT_RESIDENT  a member taking part lies in a streamed or a cluster set, one component holds most transcripts, or set_mode = 1
+ *     TOO_LARGE     more than 64 parts
+ *     UNCONVERGED   values are given, but a search or a solve hit its cap
+ *   For OUTSIDE, NOT_RESIDENT and TOO_LARGE every numeric output is NaN and evals, parts, members are 0.
+ * Outputs are indexed by query position (by gene id when query_genes is NULL; n_query is then ignored); repeats and any order are
+ * allowed.  A gene's result depends on its parts, p and pp alone -- not on what else is asked, the batch, the layout, MERGE_ROWS or the
+ * library's numbering.  The context is left as it was: a following solve or profile returns the same bits.  ERR_STATE before
+ * upload_sample and without a gene map; ERR_ARG for a gene id outside 0 .. n_genes-1, n_query < 0, a level outside (0, 1), a non-finite
+ * dev_tol and the parameters solve rejects; ERR_NUMERIC for a non-finite F_hat.  EMSAR_HIP_PROFILE_GENES_BATCH = items per launch and
+ * class (a testing aid; the bits do not change). */
+enum { EMSAR_GENE_PROFILE_TOO_LARGE = 5 };                              /* the EMSAR_PROFILE_* statuses, and this one */
+typedef struct {
+    double  *lower, *upper, *dev_lower, *dev_upper, *lambda, *pvalue, *gene_hat;       /* [n_query]; may each be NULL */
+    int32_t *status, *evals, *parts, *members;                              /* [n_query] status; evaluations of both searches; parts; k */
+} emsar_profile_gene_outputs;
+typedef struct {
+    int64_t n_status[6];          /* distinct queried genes per status */
+    int64_t items_launched;       /* workgroups: one per gene for baseline and drop, one per limit searched */
+    int64_t evals_sum;            /* evaluations summed over the searches on the device */
+    int64_t passes_sum;           /* passes summed over their solves, every part */
+    int32_t evals_max, passes_max; /* the search with the most evaluations / the most passes */
+    int32_t parts_max, reserved0; /* the most parts of a gene that was searched */
+    double  min_raw_lambda;       /* the most negative Lambda before clamping, 0 if none was negative */
+    double  cut;                  /* q */
+    double  baseline_ms, search_ms; /* device time of baseline + drop, and of the searches (HIP events) */
+    double  total_ms;             /* wall time of the call, a first call's set building included */
+} emsar_profile_gene_stats;
+int emsar_hip_profile_genes(emsar_hip_ctx *ctx, const emsar_em_params *p, const emsar_profile_params *pp /* or NULL */, int32_t n_query,
+                            const int32_t *query_genes /* NULL = all genes */, const emsar_profile_gene_outputs *out /* or NULL */,
+                            emsar_profile_gene_stats *stats /* or NULL */);
+int emsar_hip_gene_presence_pvalue_host(int64_t n, const double *lambda, const int32_t *members, double *p_out);
+
 /* ---- asymptotic standard errors: the inverse of the observed information at the MLE ---------------
  * How sure is theta_t, without resampling?  For a theta that maximises the likelihood of the current sample, the observed information
  * of the ACTIVE transcripts is J_ij = sum_c m_ci m_cj R_c / S_c^2 (m_ci = how often i stands in row c); its inverse is the asymptotic

@@ -1,13 +1,18 @@
 """Cost of the profile-likelihood intervals (emsar_hip_profile) on bench.py's time_to_mle segment problem; prints one JSON object.
 
-    python tools/profile_bench.py [--rounds 3] [--level 0.95] [--max-iter 20000] [--max-evals 40] [--out FILE]
+    python tools/profile_bench.py [--genes] [--rounds 3] [--level 0.95] [--max-iter 20000] [--max-evals 40] [--out FILE]
 
 The problem (same seeds, 100 k transcripts in families) is uploaded and solved (the first solve finds and packs the sets); then every
 transcript's interval is computed, --rounds times, and the presence test is run on the same input in the same process.  Reported: wall
 and device ms per call (baseline_ms + drop_ms + search_ms: HIP events), transcripts per status, set solves per search item (mean, max),
 the ratio of the wall time to emsar_hip_presence's, and -- for the transcripts the asymptotic standard errors call ESTIMATED with at
 least 50 expected reads -- the median and the 5 % and 95 % points of (upper - lower) / (2 sqrt(q) sd_fpkm): 1 where the likelihood is
-quadratic over the interval."""
+quadratic over the interval.
+--genes: after that, in the same process, emsar_hip_profile_genes with the generator's families as genes (boot_bench.family_sizes), all
+genes in one call: after one warm-up call, --rounds calls; wall and device ms (baseline_ms + search_ms: HIP events) as best / median /
+worst over the rounds, genes per status, the searches of the genes that converged (two for TWO_SIDED, one for LOWER_ZERO; device and
+host), evaluations per search, the most parts, and next to them the two yardsticks from this run: emsar_hip_profile over all transcripts (above) and one solve (wall, best
+of --rounds).  A record, never a test threshold."""
 import argparse
 import json
 import os
@@ -21,15 +26,45 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
+def genes_part(dev, a, solve, sizes, transcripts):
+    """emsar_hip_profile_genes over all family genes in one call (module docstring); `transcripts` = the best transcript-profile run"""
+    spread = lambda v: {"best": float(np.min(v)), "median": float(np.median(v)), "worst": float(np.max(v))}
+    dev.set_gene_map(np.repeat(np.arange(len(sizes), dtype=np.int32), sizes), len(sizes))
+    one = []
+    for _ in range(a.rounds):
+        t0 = time.perf_counter()
+        dev.solve(**solve)
+        one.append(1e3 * (time.perf_counter() - t0))
+    dev.profile_genes(level=a.level, max_evals=a.max_evals, **solve)          # warm-up: the kernels' first launch
+    runs = []
+    for _ in range(a.rounds):
+        t0 = time.perf_counter()
+        r = dev.profile_genes(level=a.level, max_evals=a.max_evals, **solve)
+        d = r["stats"].as_dict()
+        d["wall_ms"] = 1e3 * (time.perf_counter() - t0)
+        runs.append(d)
+    d = runs[0]
+    ok = np.isin(r["status"], (0, 1)) & (r["evals"] > 0)       # searched and converged, on the device or on the host
+    n_search = int(np.sum(np.where(r["status"][ok] == 0, 2, 1)))
+    return {"n_genes": int(len(sizes)), "status": d["n_status"], "wall_ms": spread([x["wall_ms"] for x in runs]),
+            "device_ms": spread([x["baseline_ms"] + x["search_ms"] for x in runs]), "baseline_ms": spread([x["baseline_ms"] for x in runs]),
+            "search_ms": spread([x["search_ms"] for x in runs]), "items_launched": d["items_launched"], "searches": n_search,
+            "evals_per_search": float(r["evals"][ok].sum()) / max(1, n_search), "device_evals_sum": d["evals_sum"], "evals_max": d["evals_max"],
+            "passes_max": d["passes_max"], "parts_max": d["parts_max"], "members_max": int(r["members"].max()),
+            "min_raw_lambda": d["min_raw_lambda"], "one_solve_wall_ms": spread(one), "transcript_profile_wall_ms": 1e3 * transcripts["wall_s"],
+            "transcript_profile_device_ms": transcripts["baseline_ms"] + transcripts["drop_ms"] + transcripts["search_ms"]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--level", type=float, default=0.95)
     ap.add_argument("--max-iter", type=int, default=20000)
     ap.add_argument("--max-evals", type=int, default=40)
+    ap.add_argument("--genes", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
-    from boot_bench import segment_problem
+    from boot_bench import family_sizes, segment_problem
     from emsar_amd import EmsarHip
     n_tx, rp, ci, R, E = segment_problem()
     solve = dict(max_iter=a.max_iter, tol=1e-10)
@@ -65,6 +100,8 @@ def main():
                    width_over_wald={"n": int(pick.sum()), "median": float(np.median(ratio)) if pick.any() else None,
                                     "p05": float(np.quantile(ratio, 0.05)) if pick.any() else None,
                                     "p95": float(np.quantile(ratio, 0.95)) if pick.any() else None})
+        if a.genes:
+            out["genes"] = genes_part(dev, a, solve, family_sizes(n_tx), best)
         th2, _ = dev.solve(**solve)
         out["solve_unchanged"] = bool(th2.tobytes() == th.tobytes())
     txt = json.dumps(out, indent=1)
