@@ -98,6 +98,19 @@ struct GeneQueryMembers {
     }
 };
 
+// ctx_b's gene_of_lib for a two-sample call whose map lives on ctx_a: ctx_b's own when it has the map, else ctx_a's map in ctx_b's
+// library numbering, uploaded into `hold` (compare_genes.hpp, compare_usage.hpp)
+inline int gene_of_lib_of_b(emsar_hip_ctx *ctx, emsar_hip_ctx *ctx_b, DevBuf<int32_t> &hold, const int32_t *&ptr) {
+    if (ctx_b->genes.have_genes) { ptr = ctx_b->genes.d_gene_of_lib; return EMSAR_HIP_OK; }
+    const std::vector<int32_t> &of_tx = ctx->genes.h_gene_of_tx;
+    std::vector<int32_t> of_lib(of_tx.size());
+    const bool remap = renumbered(ctx_b);
+    for (size_t t = 0; t < of_tx.size(); t++) of_lib[remap ? (size_t)tid_map(ctx_b)[t] : t] = of_tx[t];
+    HIPCHK(hold.upload(of_lib.data(), of_lib.size()));
+    ptr = hold;
+    return EMSAR_HIP_OK;
+}
+
 struct CompareGenesRun : GeneQueryMembers {
     struct Result : CompareResult { int32_t parts = 0; };      // per queried gene; theta_a / theta_b / theta_null hold the gene sums
     using SideParts = GeneSideParts;
@@ -129,18 +142,6 @@ struct CompareGenesRun : GeneQueryMembers {
     int reduce(const CompareRec &r, Result &o) {
         if (!compare_reduce(r, Q.ratio, o)) { ctx->err = "compare_genes: non-finite likelihood at lambda = 0"; return EMSAR_HIP_ERR_NUMERIC; }
         if (o.raw < st.min_raw_lambda) st.min_raw_lambda = o.raw;
-        return EMSAR_HIP_OK;
-    }
-
-    // ctx_b's gene_of_lib: its own when it has the map, else ctx_a's map in ctx_b's library numbering
-    int gene_of_b(const int32_t *&ptr) {
-        if (ctx_b->genes.have_genes) { ptr = ctx_b->genes.d_gene_of_lib; return EMSAR_HIP_OK; }
-        const std::vector<int32_t> &of_tx = ctx->genes.h_gene_of_tx;
-        std::vector<int32_t> of_lib(of_tx.size());
-        const bool remap = renumbered(ctx_b);
-        for (size_t t = 0; t < of_tx.size(); t++) of_lib[remap ? (size_t)tid_map(ctx_b)[t] : t] = of_tx[t];
-        HIPCHK(d_gene_of_b.upload(of_lib.data(), of_lib.size()));
-        ptr = d_gene_of_b;
         return EMSAR_HIP_OK;
     }
 
@@ -177,7 +178,7 @@ struct CompareGenesRun : GeneQueryMembers {
         }
         const int32_t *gene_of_lib_b = nullptr;
         if (!h_parts.empty()) {
-            if (const int rc = gene_of_b(gene_of_lib_b)) return rc;
+            if (const int rc = gene_of_lib_of_b(ctx, ctx_b, d_gene_of_b, gene_of_lib_b)) return rc;
             HIPCHK(d_parts.upload(h_parts.data(), h_parts.size()));
             HIPCHK(d_closed.upload(h_closed.data(), h_closed.size()));
         }

@@ -90,6 +90,7 @@
 #include "kernels_isoforms.hpp"
 #include "kernels_fit.hpp"
 #include "kernels_asym.hpp"
+#include "kernels_compare_usage.hpp"
 
 // ==================================================================================================
 // context
@@ -845,4 +846,5 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 #include "compare.hpp"    // the two-sample likelihood-ratio test and its entry points (after set_items.hpp: SetItemRunner, SetQuery)
 #include "compare_genes.hpp"   // the gene-level two-sample test and its entry points (after compare.hpp: CompareRun, compare_reduce, same_structure)
 #include "profile_genes.hpp"   // the gene-level profile intervals and the gene presence test (after compare_genes.hpp: GeneQueryMembers)
+#include "compare_usage.hpp"   // the two-sample test of isoform usage (after profile_genes.hpp; GeneQueryMembers, CompareRun::side_of, same_structure)
 #include "asym.hpp"       //the asymptotic standard errors and their entry points (after fit.hpp: fit_ensure_csr, launch_gene_sums)

@@ -50,6 +50,11 @@
  * sample i >= 1 also writes <prefix>.<i>.gcompare: per gene, in the order of .gfpkm, the gene sums of FPKM in sample i and in sample 0, log2 of
  * their ratio, Lambda of H0: the gene's sum in i = r * its sum in 0 with the isoforms free in both samples, p, status, evaluations and parts
  * (emsar_hip_compare_genes); --compare-list filters transcripts only.  The other files do not change with it.
+ * --compare-usage (with -M, at least two samples and --g2t) answers "did this isoform's share of its gene change against sample 0" (an
+ * isoform switch): every sample i >= 1 writes <prefix>.<i>.ucompare with, per transcript (or per transcript named in --compare-list FILE), its
+ * gene, its share of the gene in sample i and in sample 0, the difference of their logits, the likelihood-ratio statistic Lambda of H0: equal
+ * shares, its chi2_1 p-value, a status word, the outer points and the inner evaluations spent (emsar_hip_compare_usage with the solve's
+ * parameters: sample i is A, sample 0 is B).  The other files do not change with it.
  * --asymptotic answers "how sure is this FPKM" without resampling: <prefix>.<i>.asym holds, per transcript, the standard errors of FPKM and
  * TPM from the inverse of the observed information at the .fpkm column (emsar_hip_asymptotic), a status word and the sibling it is most
  * confounded with; with --g2t also <prefix>.<i>.gasym per gene and a usage_sd column.  Transcripts with FPKM <= --boundary-cut (5e-7) are held
@@ -97,6 +102,7 @@ typedef struct {
     int profile, profile_evals; double profile_level; /* --profile [--profile-level L] [--profile-evals N] */
     int32_t *prof_q; int prof_nq;     /* --profile-list FILE, as --presence-list */
     int compare; double compare_ratio; /* --compare [--compare-ratio r] */
+    int compare_usage;                /* --compare-usage (needs --g2t): also a two-sample run, shares sample 0 with --compare */
     int32_t *cmp_q; int cmp_nq;       /* --compare-list FILE, as --presence-list */
     struct compare_ref *ref;          /* --compare: sample 0's solver inputs, shared by the workers */
     const emsar_genes *genes;         /* its gene map, read once by main() and shared read-only by the workers */
@@ -177,6 +183,26 @@ static int write_gcompare(const char *path, const emsar_genes *g, const emsar_co
         put_num(f, "%lf", o->lambda[k]); fputc('\t', f);
         put_num(f, "%.6g", o->pvalue[k]);
         fprintf(f, "\t%s\t%d\t%d\n", o->status[k] >= 0 && o->status[k] < 6 ? word[o->status[k]] : "?", o->evals[k], o->parts[k]);
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+/* .ucompare (--compare-usage): one line per queried transcript -- transcript gene usage usage_ref dlogit Lambda p status outer evals; numbers
+ * as in .compare */
+static int write_ucompare(const char *path, const emsar_rsh *r, const emsar_genes *g, int32_t n_query, const int32_t *query, const emsar_usage_outputs *o) {
+    static const char *const word[8] = {"TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE", "UNDEFINED", "SINGLE"};
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "transcript\tgene\tusage\tusage_ref\tdlogit\tLambda\tp\tstatus\touter\tevals\n");
+    for (int32_t i = 0; i < n_query; i++) {
+        const int32_t t = query ? query[i] : i, k = g->gene_of_tx[t];
+        fprintf(f, "%s\t%s\t", r->names[t], k >= 0 ? g->names[k] : "");
+        put_num(f, "%lf", o->usage_a[i]); fputc('\t', f);
+        put_num(f, "%lf", o->usage_b[i]); fputc('\t', f);
+        put_num(f, "%lf", o->dlogit[i]); fputc('\t', f);
+        put_num(f, "%lf", o->lambda[i]); fputc('\t', f);
+        put_num(f, "%.6g", o->pvalue[i]);
+        fprintf(f, "\t%s\t%d\t%d\n", o->status[i] >= 0 && o->status[i] < 8 ? word[o->status[i]] : "?", o->outer_evals[i], o->evals[i]);
     }
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
@@ -308,7 +334,7 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         if (l != 0.0) for (uint64_t k = r->row_ptr[c]; k < r->row_ptr[c + 1]; k++) ieuma[r->col_idx[k]] += l;
     }
     w->host_s[i] = w->model_s[i] + (now_s() - t_host);
-    if (cfg->compare && i == 0) { publish_ref(w, r, cnt->R, m->E_solver, den); published = 1; }
+    if ((cfg->compare || cfg->compare_usage) && i == 0) { publish_ref(w, r, cnt->R, m->E_solver, den); published = 1; }
     if ((rc = emsar_hip_upload_sample(ctx, cnt->R, m->E_solver, den)) ||
         (rc = emsar_hip_solve(ctx, &p, theta, &w->stats[i]))) {
         fprintf(stderr, "alnfile[%d]: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
@@ -435,8 +461,8 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
             if (rc) goto done;
         }
     }
-    /* ---- two-sample test (--compare): this sample (A) against sample 0 (B, in a second context on this device), on the device ---- */
-    if (cfg->compare && i > 0) {
+    /* ---- two-sample tests (--compare, --compare-usage): this sample (A) against sample 0 (B, in a second context on this device), on the device ---- */
+    if ((cfg->compare || cfg->compare_usage) && i > 0) {
         compare_ref *ref = cfg->ref;
         pthread_mutex_lock(w->mu);
         while (!ref->ready) pthread_cond_wait(w->cv, w->mu);
@@ -455,36 +481,54 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
             w->ref_ctx = rc_ctx;
         }
         const size_t Q = cfg->cmp_q ? (size_t)cfg->cmp_nq : T, Qa = Q > 0 ? Q : 1;
-        double *cv = (double *)malloc(Qa * 8 * 5);
-        int32_t *ci = (int32_t *)malloc(Qa * 4 * 2);
-        const emsar_compare_params cp = {cfg->compare_ratio, 0.0, 0, 0};
-        const emsar_compare_outputs co = {cv, cv ? cv + Q : NULL, cv ? cv + 2 * Q : NULL, cv ? cv + 3 * Q : NULL, cv ? cv + 4 * Q : NULL, NULL, NULL, NULL, NULL,
-                                          ci, ci ? ci + Q : NULL};
-        if (!cv || !ci) rc = EMSAR_HOST_ERR_OOM;
-        else if ((rc = emsar_hip_compare(ctx, w->ref_ctx, &p, &cp, (int32_t)Q, cfg->cmp_q, &co, NULL)))
-            fprintf(stderr, "alnfile[%d]: compare: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-        else {
-            snprintf(path, sizeof path, "%s/%s.%d.compare", cfg->outdir, cfg->prefix, i);
-            if ((rc = write_compare(path, r, (int32_t)Q, cfg->cmp_q, &co))) fprintf(stderr, "can't write %s\n", path);
-        }
-        free(cv); free(ci);
-        if (rc) goto done;
-        /* with --g2t the same question per gene (emsar_hip_compare_genes: this context's gene map serves both samples): .gcompare */
-        if (G) {
-            const size_t Ga = NG > 0 ? NG : 1;
-            double *gv = (double *)malloc(Ga * 8 * 5);
-            int32_t *gi = (int32_t *)malloc(Ga * 4 * 3);
-            const emsar_compare_gene_outputs go = {gv, gv ? gv + NG : NULL, gv ? gv + 2 * NG : NULL, gv ? gv + 3 * NG : NULL, gv ? gv + 4 * NG : NULL, NULL,
-                                                   NULL, NULL, NULL, gi, gi ? gi + NG : NULL, gi ? gi + 2 * NG : NULL};
-            if (!gv || !gi) rc = EMSAR_HOST_ERR_OOM;
-            else if ((rc = emsar_hip_compare_genes(ctx, w->ref_ctx, &p, &cp, (int32_t)NG, NULL, &go, NULL)))
-                fprintf(stderr, "alnfile[%d]: compare_genes: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+        /* the share of its gene (emsar_hip_compare_usage: this context's gene map serves both samples): .ucompare */
+        if (cfg->compare_usage) {
+            double *uv = (double *)malloc(Qa * 8 * 5);
+            int32_t *ui = (int32_t *)malloc(Qa * 4 * 3);
+            const emsar_usage_outputs uo = {uv, NULL, uv ? uv + Q : NULL, uv ? uv + 2 * Q : NULL, uv ? uv + 3 * Q : NULL, NULL, uv ? uv + 4 * Q : NULL, NULL,
+                                            ui, ui ? ui + Q : NULL, ui ? ui + 2 * Q : NULL, NULL};
+            if (!uv || !ui) rc = EMSAR_HOST_ERR_OOM;
+            else if ((rc = emsar_hip_compare_usage(ctx, w->ref_ctx, &p, NULL, (int32_t)Q, cfg->cmp_q, &uo, NULL)))
+                fprintf(stderr, "alnfile[%d]: compare_usage: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
             else {
-                snprintf(path, sizeof path, "%s/%s.%d.gcompare", cfg->outdir, cfg->prefix, i);
-                if ((rc = write_gcompare(path, G, &go))) fprintf(stderr, "can't write %s\n", path);
+                snprintf(path, sizeof path, "%s/%s.%d.ucompare", cfg->outdir, cfg->prefix, i);
+                if ((rc = write_ucompare(path, r, G, (int32_t)Q, cfg->cmp_q, &uo))) fprintf(stderr, "can't write %s\n", path);
             }
-            free(gv); free(gi);
+            free(uv); free(ui);
             if (rc) goto done;
+        }
+        if (cfg->compare) {
+            double *cv = (double *)malloc(Qa * 8 * 5);
+            int32_t *ci = (int32_t *)malloc(Qa * 4 * 2);
+            const emsar_compare_params cp = {cfg->compare_ratio, 0.0, 0, 0};
+            const emsar_compare_outputs co = {cv, cv ? cv + Q : NULL, cv ? cv + 2 * Q : NULL, cv ? cv + 3 * Q : NULL, cv ? cv + 4 * Q : NULL, NULL, NULL, NULL, NULL,
+                                              ci, ci ? ci + Q : NULL};
+            if (!cv || !ci) rc = EMSAR_HOST_ERR_OOM;
+            else if ((rc = emsar_hip_compare(ctx, w->ref_ctx, &p, &cp, (int32_t)Q, cfg->cmp_q, &co, NULL)))
+                fprintf(stderr, "alnfile[%d]: compare: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+            else {
+                snprintf(path, sizeof path, "%s/%s.%d.compare", cfg->outdir, cfg->prefix, i);
+                if ((rc = write_compare(path, r, (int32_t)Q, cfg->cmp_q, &co))) fprintf(stderr, "can't write %s\n", path);
+            }
+            free(cv); free(ci);
+            if (rc) goto done;
+            /* with --g2t the same question per gene (emsar_hip_compare_genes: this context's gene map serves both samples): .gcompare */
+            if (G) {
+                const size_t Ga = NG > 0 ? NG : 1;
+                double *gv = (double *)malloc(Ga * 8 * 5);
+                int32_t *gi = (int32_t *)malloc(Ga * 4 * 3);
+                const emsar_compare_gene_outputs go = {gv, gv ? gv + NG : NULL, gv ? gv + 2 * NG : NULL, gv ? gv + 3 * NG : NULL, gv ? gv + 4 * NG : NULL, NULL,
+                                                       NULL, NULL, NULL, gi, gi ? gi + NG : NULL, gi ? gi + 2 * NG : NULL};
+                if (!gv || !gi) rc = EMSAR_HOST_ERR_OOM;
+                else if ((rc = emsar_hip_compare_genes(ctx, w->ref_ctx, &p, &cp, (int32_t)NG, NULL, &go, NULL)))
+                    fprintf(stderr, "alnfile[%d]: compare_genes: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
+                else {
+                    snprintf(path, sizeof path, "%s/%s.%d.gcompare", cfg->outdir, cfg->prefix, i);
+                    if ((rc = write_gcompare(path, G, &go))) fprintf(stderr, "can't write %s\n", path);
+                }
+                free(gv); free(gi);
+                if (rc) goto done;
+            }
         }
     }
     /* ---- asymptotic standard errors (--asymptotic): the inverse of the observed information at the printed FPKM, on the device ---- */
@@ -588,7 +632,7 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
         fprintf(stdout, "Complete: %s/%s.%d.fpkm  (EM passes %d, converged %d, solve %.1f ms, logL %.6f)\n", cfg->outdir, cfg->prefix, i,
                 w->stats[i].iters, w->stats[i].converged, w->stats[i].solve_ms, w->stats[i].loglik);
 done:
-    if (cfg->compare && i == 0 && !published) publish_ref(w, r, NULL, NULL, NULL);     /* the other samples must not wait for it */
+    if ((cfg->compare || cfg->compare_usage) && i == 0 && !published) publish_ref(w, r, NULL, NULL, NULL);     /* the other samples must not wait for it */
     free(theta); free(rounds); free(mean); free(sd); free(ieuma); free(tpm); free(ir); free(iri); free(den); free(gcols); free(gsums); free(iso_u); free(dom);
     emsar_counts_free(cnt); emsar_model_free(m);
     return rc;
@@ -630,7 +674,7 @@ static void *worker_main(void *a) {
             pthread_cond_broadcast(w->cv);
             pthread_mutex_unlock(w->mu);
             w->status[i] = rc;
-            if (w->cfg->compare && i == 0) publish_ref(w, w->rsh, NULL, NULL, NULL);
+            if ((w->cfg->compare || w->cfg->compare_usage) && i == 0) publish_ref(w, w->rsh, NULL, NULL, NULL);
         } else {
             w->status[i] = run_sample(w, ctx, i, cur);
         }
@@ -701,7 +745,10 @@ static void usage(const char *a0) {
             "                            .gfpkm, the same test of the gene's summed FPKM with its isoforms free (status TOO_LARGE: more than 64\n"
             "                            connected sets and lone transcripts in one sample), the evaluations and the parts searched over\n"
             "      --compare-ratio <r>   with --compare: test theta_i = r * theta_0 (default 1; a fold change or a size factor)\n"
-            "      --compare-list <file> with --compare: only the transcripts named in the file, one name per line\n"
+            "      --compare-list <file> with --compare or --compare-usage: only the transcripts named in the file, one name per line\n"
+            "      --compare-usage       with -M, at least two samples and --g2t: every sample i >= 1 also writes <prefix>.<i>.ucompare: per transcript its\n"
+            "                            gene, its share of the gene in sample i and in sample 0, the difference of their logits, Lambda of H0: equal\n"
+            "                            shares (an isoform switch otherwise), its chi2_1 p-value, a status word, outer points and evaluations\n"
             "      --asymptotic          also write <prefix>.<i>.asym: per transcript the asymptotic standard error of FPKM and TPM from the inverse of\n"
             "                            the observed information, a status word and the sibling it is most confounded with; with --g2t also\n"
             "                            <prefix>.<i>.gasym (per gene) and a usage_sd column.  Not valid at the boundary (FPKM about 0): use --bootstrap there\n"
@@ -763,7 +810,7 @@ int main(int argc, char **argv) {
         {"asymptotic", no_argument, 0, 1023}, {"boundary-cut", required_argument, 0, 1024},
         {"profile", no_argument, 0, 1025}, {"profile-level", required_argument, 0, 1026}, {"profile-list", required_argument, 0, 1027},
         {"profile-evals", required_argument, 0, 1028},
-        {"compare", no_argument, 0, 1029}, {"compare-ratio", required_argument, 0, 1030}, {"compare-list", required_argument, 0, 1031},
+        {"compare", no_argument, 0, 1029}, {"compare-ratio", required_argument, 0, 1030}, {"compare-list", required_argument, 0, 1031}, {"compare-usage", no_argument, 0, 1040},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
@@ -865,6 +912,7 @@ int main(int argc, char **argv) {
             case 1027: profile_list = optarg; break;
             case 1028: cfg.profile_evals = atoi(optarg); if (cfg.profile_evals <= 0) { fprintf(stderr, "--profile-evals must be positive.\n"); return 1; } break;
             case 1029: cfg.compare = 1; break;
+            case 1040: cfg.compare_usage = 1; break;
             case 1030: cfg.compare_ratio = atof(optarg); compare_ratio_given = 1; break;
             case 1031: compare_list = optarg; break;
             case 1009: {
@@ -895,10 +943,13 @@ int main(int argc, char **argv) {
     }
     if (profile_level_given && !(cfg.profile_level > 0.0 && cfg.profile_level < 1.0)) { fprintf(stderr, "--profile-level must lie in (0, 1).\n"); return 1; }
     if (!profile_level_given) cfg.profile_level = 0.95;
-    if ((compare_list || compare_ratio_given) && !cfg.compare) { fprintf(stderr, "--compare-list and --compare-ratio need --compare.\n"); return 1; }
+    if (compare_ratio_given && !cfg.compare) { fprintf(stderr, "--compare-ratio needs --compare.\n"); return 1; }
+    if (compare_list && !cfg.compare && !cfg.compare_usage) { fprintf(stderr, "--compare-list needs --compare or --compare-usage.\n"); return 1; }
+    if (cfg.compare_usage && !cfg.g2t) { fprintf(stderr, "--compare-usage needs --g2t FILE.\n"); usage(argv[0]); return 1; }
     if (compare_ratio_given && !(cfg.compare_ratio > 0.0 && isfinite(cfg.compare_ratio))) { fprintf(stderr, "--compare-ratio must be positive.\n"); return 1; }
     if (!compare_ratio_given) cfg.compare_ratio = 1.0;
     if (cfg.compare && !multisample) { fprintf(stderr, "--compare needs -M and at least two samples.\n"); usage(argv[0]); return 1; }
+    if (cfg.compare_usage && !multisample) { fprintf(stderr, "--compare-usage needs -M and at least two samples.\n"); usage(argv[0]); return 1; }
     cfg.ref = &ref;
     if (!cfg.rsh_path || optind + 2 >= argc) { usage(argv[0]); return 1; }
     if (emsar_set_strand(strand, cfg.ao.pe, &cfg.ao.strand)) { fprintf(stderr, "error: invalid strand type.\n"); return 1; }
@@ -921,6 +972,7 @@ int main(int argc, char **argv) {
         if (!n_list) { fprintf(stderr, "No alignment files in the alignment list\n"); return 1; }
     }
     if (cfg.compare && n_list < 2) { fprintf(stderr, "--compare needs -M and at least two samples.\n"); usage(argv[0]); return 1; }
+    if (cfg.compare_usage && n_list < 2) { fprintf(stderr, "--compare-usage needs -M and at least two samples.\n"); usage(argv[0]); return 1; }
     cfg.aln = list; cfg.n_aln = n_list;
     /* the reference runs `mkdir -p outdir` (emsar_main.c:284-285); find out now, not after the solve, that it cannot be written */
     {

@@ -30,6 +30,7 @@ SYMBOLS = [
     "emsar_hip_profile", "emsar_hip_profile_cut_host",
     "emsar_hip_compare", "emsar_hip_compare_pvalue_host", "emsar_hip_compare_genes",
     "emsar_hip_profile_genes", "emsar_hip_gene_presence_pvalue_host",
+    "emsar_hip_compare_usage",
     "emsar_hip_asymptotic", "emsar_hip_asymptotic_host",
 ]
 
@@ -46,6 +47,11 @@ COMPARE_OUTPUTS = ("lambda", "pvalue", "log2fc", "theta_a", "theta_b", "theta_nu
 # status of a gene in the gene-level two-sample test (include/emsar_hip.h "gene-level two-sample test"), by value
 COMPARE_GENE_STATUS = COMPARE_STATUS + ("TOO_LARGE",)
 COMPARE_GENE_OUTPUTS = ("lambda", "pvalue", "log2fc", "gene_a", "gene_b", "gene_null", "multiplier", "gap", "raw_lambda")
+
+# status of a transcript in the two-sample test of isoform usage (include/emsar_hip.h "two-sample test of isoform usage"), by value
+USAGE_STATUS = ("TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE", "UNDEFINED", "SINGLE")
+USAGE_OUTPUTS = ("lambda", "raw_lambda", "pvalue", "usage_a", "usage_b", "usage_null", "dlogit", "slope")
+USAGE_COUNTS = ("status", "outer_evals", "evals", "parts")
 
 # status of a gene's profile-likelihood interval (include/emsar_hip.h "gene-level profile intervals"), by value
 PROFILE_GENE_STATUS = PROFILE_STATUS + ("TOO_LARGE",)
@@ -199,6 +205,26 @@ class CompareGeneStats(C.Structure):
         return d
 
 
+class UsageParams(C.Structure):
+    _fields_ = [("dev_tol", C.c_double), ("max_evals", C.c_int32), ("max_outer", C.c_int32)]
+
+
+class UsageOutputs(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in ("lambda_", "raw_lambda", "pvalue", "usage_a", "usage_b", "usage_null", "dlogit", "slope")] + \
+               [(k, C.POINTER(C.c_int32)) for k in USAGE_COUNTS]
+
+
+class UsageStats(C.Structure):
+    _fields_ = [("n_status", C.c_int64 * 8), ("items_launched", C.c_int64), ("evals_sum", C.c_int64), ("passes_sum", C.c_int64),
+                ("outer_sum", C.c_int64), ("evals_max", C.c_int32), ("passes_max", C.c_int32), ("parts_max", C.c_int32),
+                ("outer_max", C.c_int32), ("min_raw_lambda", C.c_double), ("device_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["n_status"] = dict(zip(USAGE_STATUS, d["n_status"]))
+        return d
+
+
 class ProfileGeneOutputs(C.Structure):
     _fields_ = [(k, C.POINTER(C.c_double)) for k in ("lower", "upper", "dev_lower", "dev_upper", "lambda_", "pvalue", "gene_hat")] + \
                [(k, C.POINTER(C.c_int32)) for k in ("status", "evals", "parts", "members")]
@@ -323,6 +349,8 @@ def load_library():
     L.emsar_hip_compare_pvalue_host.argtypes = [C.c_int64, f64p, f64p]
     L.emsar_hip_compare_genes.argtypes = [vp, vp, C.POINTER(EmParams), C.POINTER(CompareParams), C.c_int32, i32p, C.POINTER(CompareGeneOutputs),
                                           C.POINTER(CompareGeneStats)]
+    L.emsar_hip_compare_usage.argtypes = [vp, vp, C.POINTER(EmParams), C.POINTER(UsageParams), C.c_int32, i32p, C.POINTER(UsageOutputs),
+                                          C.POINTER(UsageStats)]
     L.emsar_hip_profile_genes.argtypes = [vp, C.POINTER(EmParams), C.POINTER(ProfileParams), C.c_int32, i32p, C.POINTER(ProfileGeneOutputs),
                                           C.POINTER(ProfileGeneStats)]
     L.emsar_hip_gene_presence_pvalue_host.argtypes = [C.c_int64, f64p, i32p, f64p]
@@ -576,6 +604,28 @@ def debug_compare_genes_closed(u_a, den_a, u_b, den_b, ratio=1.0, dev_tol=0.0, m
         raise EmsarHipError(rc, "debug_compare_genes_closed")
     out = dict(zip(COMPARE_GENE_OUTPUTS, list(vals)))
     out.update(status=status.value, evals=evals.value)
+    return out
+
+
+def debug_compare_usage_closed(u_a, den_a, u_b, den_b, t=0, t_b=None, dev_tol=0.0, max_evals=0, max_outer=0):
+    """Host-only diagnostic: what compare_usage() gives member `t` of a gene whose members are all one-transcript components -- u_a[i]
+    reads and den_a[i] in sample A, u_b[j] and den_b[j] in B (den 0 = takes no part; t_b = the transcript's place in B's lists when it
+    differs): the host's statuses and the two-level search as the host runs it for such genes (no GPU needed).  Returns a dict of
+    scalars keyed like compare_usage()'s arrays."""
+    f = load_library().emsar_hip_debug_compare_usage_closed       # not declared in the header: bound here, not in load_library
+    f.restype = C.c_int
+    dp = C.POINTER(C.c_double)
+    f.argtypes = [C.c_int32, dp, dp, C.c_int32, C.c_int32, dp, dp, C.c_int32, C.POINTER(UsageParams), dp, C.POINTER(C.c_int32)]
+    ua, da, ub, db = (np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1)) for x in (u_a, den_a, u_b, den_b))
+    if ua.shape != da.shape or ub.shape != db.shape:
+        raise ValueError("u and den of a sample must have the same length")
+    up, vals, counts = UsageParams(float(dev_tol), int(max_evals), int(max_outer)), (C.c_double * 8)(), (C.c_int32 * 4)()
+    rc = f(len(ua), _p(ua, C.c_double), _p(da, C.c_double), int(t), len(ub), _p(ub, C.c_double), _p(db, C.c_double), int(t if t_b is None else t_b),
+           C.byref(up), vals, counts)
+    if rc != 0:
+        raise EmsarHipError(rc, "debug_compare_usage_closed")
+    out = dict(zip(USAGE_OUTPUTS, list(vals)))
+    out.update(zip(USAGE_COUNTS, list(counts)))
     return out
 
 
@@ -934,6 +984,29 @@ class EmsarHip:
         st = CompareGeneStats()
         self._chk(self._L.emsar_hip_compare_genes(self._h, getattr(other, "_h", None), C.byref(p), C.byref(cp), nq, _p(q, C.c_int32), C.byref(o),
                                                   C.byref(st)), "compare_genes")
+        out = {k: v[:nq] for k, v in res.items()}
+        out["stats"] = st
+        return out
+
+    def compare_usage(self, other, query=None, dev_tol=0.0, max_evals=0, max_outer=0, max_iter=100000, accel=1, tol=1e-10, abs_floor=1e-6,
+                      check_every=8, count_floor=0.0, set_mode=0, zero_cut=0.0, abs_step=0.0, newton_after=0):
+        """Two-sample test of isoform usage (include/emsar_hip.h "two-sample test of isoform usage"): did the share of each queried
+        transcript in its gene change between this context's sample A and `other`'s sample B?  H0: theta_t / (the gene sum) is the same
+        in both samples, everything else free.  This context holds the gene map (set_gene_map).  query: tids in any order, repeats
+        allowed, None = all transcripts; dev_tol, max_evals, max_outer 0 = the defaults (1e-4, 40, 12); the solver parameters are those
+        of solve().  Returns a dict of arrays in query order: lambda, raw_lambda, pvalue, usage_a, usage_b, usage_null, dlogit, slope,
+        status (index into USAGE_STATUS), outer_evals, evals, parts, and stats.  After upload_sample on both; both contexts are left as
+        they were."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        up = UsageParams(float(dev_tol), int(max_evals), int(max_outer))
+        q = None if query is None else np.ascontiguousarray(np.asarray(query, dtype=np.int32).reshape(-1))
+        nq = self.n_tx if q is None else len(q)
+        res = {k: np.zeros(max(nq, 1)) for k in USAGE_OUTPUTS}
+        res.update({k: np.zeros(max(nq, 1), dtype=np.int32) for k in USAGE_COUNTS})
+        o = UsageOutputs(*[_p(res[k], C.c_double) for k in USAGE_OUTPUTS], *[_p(res[k], C.c_int32) for k in USAGE_COUNTS])
+        st = UsageStats()
+        self._chk(self._L.emsar_hip_compare_usage(self._h, getattr(other, "_h", None), C.byref(p), C.byref(up), nq, _p(q, C.c_int32), C.byref(o),
+                                                  C.byref(st)), "compare_usage")
         out = {k: v[:nq] for k, v in res.items()}
         out["stats"] = st
         return out

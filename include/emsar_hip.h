@@ -671,6 +671,90 @@ int emsar_hip_compare_genes(emsar_hip_ctx *ctx_a, emsar_hip_ctx *ctx_b, const em
                             int32_t n_query, const int32_t *query_genes /* NULL = all genes */, const emsar_compare_gene_outputs *out /* or NULL */,
                             emsar_compare_gene_stats *stats /* or NULL */);
 
+/* ---- two-sample test of isoform usage: did a transcript's share of its gene change? ---------------
+ * An isoform switch (differential transcript usage).  emsar_hip_compare lights up every transcript of a gene whose total doubled at
+ * unchanged shares, emsar_hip_compare_genes does not see isoforms that swap at an unchanged total, and the bootstrap sd of the share
+ * (emsar_hip_isoform_usage) is per sample and fails where the share is 0 or 1 -- which is where switches live.  Here the null is imposed
+ * on the share inside the likelihood.  Contexts, structure check, p and the gene map rules are those of emsar_hip_compare_genes (the map
+ * is the one on ctx_a; a map on ctx_b must be the same one); members, parts, X and F are defined as there.  For transcript t of gene g,
+ * share = theta_t / X (FPKM is proportional to theta within a sample: this is the share emsar_hip_isoform_usage reports):
+ *     H1           everything free in both samples:                        F1 = F^A + F^B at lambda = 0
+ *     H0           theta_t^A / X^A = theta_t^B / X^B (= u, free):           F0 = max_u [P_A(u) + P_B(u)],
+ *                  P_k(u) = max {F^k : theta_t = u X} in sample k
+ *     Lambda       = 2 (F1 - F0) >= 0,  p = erfc(sqrt(Lambda / 2)), chi2 with 1 degree of freedom.  THE P-VALUE IS CONSERVATIVE WHEN A
+ *                  SHARE SITS AT 0 OR 1 IN ONE SAMPLE.  No ratio parameter: the share is scale-free, the samples' depths drop out.
+ *     inner level  u fixed: the samples decouple and theta_t - u X = 0 is linear.  Its Lagrangian is the ordinary problem with
+ *                  den_t + lambda (1 - u) on t and den_s - lambda u on every other member s taking part, lambda in
+ *                  (-den_t / (1 - u), mn / u), mn = the smallest den of the others (beyond it the dual is unbounded).  The gap
+ *                  g(lambda) = theta_t - u X falls in lambda, the dual D(lambda) = F - lambda g is convex with slope -g and
+ *                  D >= P_k(u), with equality at the root.  The search is emsar_hip_compare's on h = g / (theta_t + u X), in
+ *                  v in [0, 1) with lambda = v * (the end of the range on the side of sign g(0)); g(0) comes from evaluation 0 and
+ *                  costs no solve.  On the side that shrinks the member(s) at the limiting den take den * (1 - v), the others
+ *                  den - v * (their share of the limit); at lambda = 0 every den keeps its own bits.  It stops when
+ *                  2 |lambda g| <= dev_tol, when 2 |g| * (the width of the bracket in lambda) <= dev_tol, or after max_evals
+ *                  evaluations.  Its value is D at the last lambda: an upper bound of P_k(u) whose error is of second order in g.
+ *     outer level  P_k is quasi-concave in u with its maximum at the estimated share u_hat_k, so the maximum of P_A + P_B lies in
+ *                  [min u_hat, max u_hat].  dP_k / du = lambda_k Xc^k (envelope theorem), where Xc is the gene sum of the point ON
+ *                  the constraint: an inner search ends short of its root, so Xc is taken from the feasible point next to its last
+ *                  evaluation -- (X - theta_t) / (1 - u) when t is the member in deficit (t filled up to the share u), theta_t / u when
+ *                  the others are; both equal X at a root, and they differ from it where the root is the end of the multiplier's
+ *                  range (the member in deficit has no read to its name and stays 0 at every evaluated point, while at the end its
+ *                  value is free and the constraint sets it).  Illinois steps on s(u) = lambda_A Xc^A + lambda_B Xc^B, normalised by
+ *                  |lambda_A Xc^A| + |lambda_B Xc^B|, over that bracket; the signs at
+ *                  its ends are known without evaluation (at u = u_hat_k that sample's multiplier is 0).  Evaluation 0 is lambda = 0
+ *                  in both samples and gives u_hat_A, u_hat_B and F1 from the code path of every later evaluation;
+ *                  u_hat_A == u_hat_B ends the search with Lambda = 0.0 and outer_evals = 1.  It stops when
+ *                  2 |s| * (the width of the bracket in u) <= dev_tol or after max_outer outer points, evaluation 0 counted (at least
+ *                  one point of the null is evaluated whatever max_outer says).  F0 is the largest P_A + P_B among the points
+ *                  evaluated.  BETWEEN THE TWO ESTIMATED SHARES THE SUM OF A RISING AND A FALLING QUASI-CONCAVE FUNCTION NEED NOT BE
+ *                  CONCAVE: the search then finds a stationary point that need not be the maximum, which makes Lambda too large at
+ *                  worst (anti-conservative).
+ *     cost         one workgroup runs one (gene, t) search: at most max(max_outer, 2) * 2 * max_evals * parts * max_iter passes,
+ *                  parts <= 64 per sample.  A gene whose parts are all closed form in both samples is searched on the host with the
+ *                  same code and nothing is launched for it.
+ *     outputs      lambda, raw_lambda (before clamping at 0), pvalue; usage_a, usage_b = the shares at lambda = 0; usage_null = u of the
+ *                  best outer point; dlogit = logit(usage_a) - logit(usage_b), +-inf when exactly one share sits at an end or they sit
+ *                  at opposite ends, NaN when both sit at the same end; slope = the outer stopping quantity of the last point;
+ *                  outer_evals; evals = inner evaluations summed, evaluation 0's two included; parts = the parts of both samples
+ * status, per queried transcript:
+ *     TESTED        outputs as above
+ *     BOTH_ABSENT   theta_t is exactly 0 in both samples at lambda = 0, both gene sums positive: Lambda 0, p 1
+ *     UNDEFINED     a gene sum is exactly 0 at lambda = 0 in either sample: usage and Lambda NaN, the counters are given
+ *     SINGLE        fewer than two members take part in either sample: the share is 1 by construction
+ *     OUTSIDE       den_t == 0 in either sample, or t has no gene
+ *     NOT_RESIDENT  as in emsar_hip_compare_genes
+ *     TOO_LARGE     more than 64 parts in a sample
+ *     UNCONVERGED   values are given, but a solve, an inner search or the outer search hit its cap
+ *   For SINGLE, OUTSIDE, NOT_RESIDENT and TOO_LARGE every numeric output is NaN and the counters are 0.
+ * Outputs are indexed by query position (by tid when query_tids is NULL; n_query is then ignored); repeats and any order are allowed.  A
+ * result depends on the gene's parts, t, p and up alone -- not on what else is asked, the batch, the layout, MERGE_ROWS or the library's
+ * numbering.  Both contexts are left as they were.  Errors as emsar_hip_compare_genes, with tids for gene ids; ERR_ARG for a non-finite
+ * dev_tol.  EMSAR_HIP_COMPARE_USAGE_BATCH = items per launch and class (a testing aid; the bits do not change). */
+enum {
+    EMSAR_USAGE_TESTED = 0, EMSAR_USAGE_BOTH_ABSENT = 1, EMSAR_USAGE_OUTSIDE = 2, EMSAR_USAGE_NOT_RESIDENT = 3, EMSAR_USAGE_UNCONVERGED = 4,
+    EMSAR_USAGE_TOO_LARGE = 5, EMSAR_USAGE_UNDEFINED = 6, EMSAR_USAGE_SINGLE = 7
+};
+typedef struct { double dev_tol; int32_t max_evals, max_outer; } emsar_usage_params;    /* NULL or <= 0: 1e-4 (both levels), 40, 12 */
+typedef struct {
+    double  *lambda, *raw_lambda, *pvalue, *usage_a, *usage_b, *usage_null, *dlogit, *slope;               /* [n_query]; may each be NULL */
+    int32_t *status, *outer_evals, *evals, *parts;                          /* [n_query] EMSAR_USAGE_*; outer points; inner evaluations; parts */
+} emsar_usage_outputs;
+typedef struct {
+    int64_t n_status[8];          /* distinct queried transcripts per status */
+    int64_t items_launched;       /* workgroups: one search each */
+    int64_t evals_sum;            /* inner evaluations summed over the searches on the device */
+    int64_t passes_sum;           /* passes summed over their solves, every part of both samples */
+    int64_t outer_sum;            /* outer points summed over the searches on the device */
+    int32_t evals_max, passes_max; /* the search with the most inner evaluations / the most passes */
+    int32_t parts_max, outer_max; /* the most parts of a gene that was searched; the search with the most outer points */
+    double  min_raw_lambda;       /* the most negative Lambda before clamping, 0 if none was negative */
+    double  device_ms;            /* device time of the searches (HIP events) */
+    double  total_ms;             /* wall time of the call, a first call's set building included */
+} emsar_usage_stats;
+int emsar_hip_compare_usage(emsar_hip_ctx *ctx_a, emsar_hip_ctx *ctx_b, const emsar_em_params *p, const emsar_usage_params *up /* or NULL */,
+                            int32_t n_query, const int32_t *query_tids /* NULL = all transcripts */, const emsar_usage_outputs *out /* or NULL */,
+                            emsar_usage_stats *stats /* or NULL */);
+
 /* ---- gene-level profile intervals and the gene presence test --------------------------------------
  * How much of gene g could be there, and is g needed to explain the reads at all?  Also where the gene sum is 0 or close to it, where
  * the asymptotic errors do not hold and the bootstrap's percentile interval is [0, 0].  The per-transcript profile limits cannot be

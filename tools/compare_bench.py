@@ -1,6 +1,6 @@
 """Cost of the two-sample test (emsar_hip_compare) on bench.py's time_to_mle segment problem against one solve; prints one JSON object.
 
-    python tools/compare_bench.py [--genes] [--rounds 3] [--max-iter 20000] [--max-evals 40] [--seed 5] [--out FILE]
+    python tools/compare_bench.py [--genes | --usage] [--rounds 3] [--max-iter 20000] [--max-evals 40] [--seed 5] [--out FILE]
 
 Sample A is the problem as it stands (same seeds, 100 k transcripts in families); sample B is a Poisson redraw of A's row weights (a
 technical replicate: the null holds for every transcript).  Both are uploaded into contexts of their own and solved once (the first
@@ -9,7 +9,10 @@ events around the searches), transcripts per status, evaluations per search (mea
 process and the ratio, the share of TESTED transcripts with p < 0.05 (about 0.05 or less under the null), and whether a solve after
 the calls returns the bits it returned before.
 --genes: emsar_hip_compare_genes instead, the generator's families as genes (boot_bench.family_sizes): the same figures per gene, and
-the most parts a gene had.  A record, never a test threshold."""
+the most parts a gene had.
+--usage: emsar_hip_compare_usage over every transcript of a family of two or more (the families as genes): after one warm-up call the
+median wall and device ms of 5 calls, next to the median of 5 calls of emsar_hip_compare on the same transcripts and one solve, all
+from this run; outer points per search and inner evaluations per outer point.  A record, never a test threshold."""
 import argparse
 import json
 import os
@@ -30,6 +33,7 @@ def main():
     ap.add_argument("--max-evals", type=int, default=40)
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--genes", action="store_true")
+    ap.add_argument("--usage", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
     from boot_bench import family_sizes, segment_problem
@@ -48,6 +52,11 @@ def main():
             out.update(call="compare_genes", n_genes=int(len(sizes)))
         th, _ = A.solve(**solve)                             # finds and packs the sets, warms up
         B.solve(**solve)
+        if a.usage:
+            out.update(usage_record(A, B, n_tx, family_sizes(n_tx), solve))
+            th2, _ = A.solve(**solve)
+            out["solve_unchanged"] = bool(th2.tobytes() == th.tobytes())
+            return finish(out, a.out)
         solves = []
         for _ in range(a.rounds):
             t0 = time.perf_counter()
@@ -71,10 +80,43 @@ def main():
             out["parts_max"] = best["parts_max"]
         th2, _ = A.solve(**solve)
         out["solve_unchanged"] = bool(th2.tobytes() == th.tobytes())
+    finish(out, a.out)
+
+
+def usage_record(A, B, n_tx, sizes, solve, calls=5):
+    """--usage: the figures of emsar_hip_compare_usage, of emsar_hip_compare on the same transcripts and of one solve"""
+    gene_of = np.repeat(np.arange(len(sizes), dtype=np.int32), sizes)
+    A.set_gene_map(gene_of, len(sizes))
+    q = np.flatnonzero(np.asarray(sizes)[gene_of] >= 2).astype(np.int32)
+
+    def timed(f):
+        f()                                                    # warm-up
+        runs = []
+        for _ in range(calls):
+            t0 = time.perf_counter()
+            r = f()
+            runs.append((time.perf_counter() - t0, r))
+        runs.sort(key=lambda x: x[0])
+        return runs[len(runs) // 2]
+    wall_u, r = timed(lambda: A.compare_usage(B, q, **solve))
+    wall_c, c = timed(lambda: A.compare(B, q, **solve))
+    wall_s, _ = timed(lambda: A.solve(**solve))
+    d, dc = r["stats"].as_dict(), c["stats"].as_dict()
+    tested = r["status"] == 0
+    return dict(call="compare_usage", n_genes=int(len(sizes)), n_query=int(len(q)), calls=calls, status=d["n_status"], items_launched=d["items_launched"],
+                wall_ms=1e3 * wall_u, device_ms=d["device_ms"], outer_per_item_mean=d["outer_sum"] / max(1, d["items_launched"]), outer_max=d["outer_max"],
+                inner_evals_per_outer_point=d["evals_sum"] / max(1, d["outer_sum"]), evals_max=d["evals_max"], passes_sum=d["passes_sum"],
+                passes_max=d["passes_max"], parts_max=d["parts_max"], min_raw_lambda=d["min_raw_lambda"],
+                compare_wall_ms=1e3 * wall_c, compare_device_ms=dc["device_ms"], compare_passes_sum=dc["passes_sum"], solve_wall_ms=1e3 * wall_s,
+                wall_over_compare=wall_u / wall_c, wall_over_solve=wall_u / wall_s,
+                share_p_below_0_05=float(np.mean(r["pvalue"][tested] < 0.05)) if tested.any() else None)
+
+
+def finish(out, path):
     txt = json.dumps(out, indent=1)
     print(txt)
-    if a.out:
-        with open(a.out, "w") as f:
+    if path:
+        with open(path, "w") as f:
             f.write(txt + "\n")
 
 
