@@ -78,12 +78,6 @@ struct CompareRun {
         Q = CompareSearchParams{cp.ratio == 0.0 ? 1.0 : cp.ratio, cp.dev_tol > 0.0 ? cp.dev_tol : 1e-4, cp.max_evals > 0 ? cp.max_evals : 40, 0};
     }
 
-    static CompareSide side_of(const emsar_hip_ctx *c) {
-        const SetsDev &D = c->sets;
-        return CompareSide{D.d_sdesc[0].get(), D.d_sdesc[1].get(), D.d_sdesc[2].get(), D.d_g_tid.get(), D.d_g_u.get(), D.d_row_w.get(),
-                           D.d_srp.get(), D.d_sent.get(), D.d_scp.get(), D.d_scrow.get(), c->vec.d_den.get()};
-    }
-
     // a side of an item: a one-transcript component (set -1), or transcript t of set `set` of class cls <= the launch class, checked
     // against its own context's descriptors
     static bool side_ok(const emsar_hip_ctx *c, int launch_cls, int32_t cls, int32_t set, int32_t t, double den) {
@@ -122,9 +116,8 @@ struct CompareRun {
         }
         const SetSolveParams P = set_params(qa.p);
         const CompareSide GA = side_of(ctx), GB = side_of(ctx_b);
-        const auto &SA = ctx->sets.RS, &SB = ctx_b->sets.RS;
-        size_t lds[emsar::kSetClasses], most = 0;              // a launch class holds the sets of its own and of every smaller class
-        for (int c = 0; c < emsar::kSetClasses; c++) lds[c] = most = std::max(most, std::max((size_t)SA.max_lds[c], (size_t)SB.max_lds[c]));
+        size_t lds[emsar::kSetClasses];
+        launch_class_lds(lds, ctx, ctx_b);
         HIPCHK(set_class_lds_attributes(kCompareSets));
         const int rc = runner.run(items, recs, st.device_ms, st.items_launched,
             [&](int c, const CompareItem &it) {
@@ -138,8 +131,7 @@ struct CompareRun {
         for (int cls = 0; cls < emsar::kSetClasses; cls++)
             for (size_t i = 0; i < recs[cls].size(); i++) {
                 const CompareRec &r = recs[cls][i];
-                st.evals_sum += r.evals; st.passes_sum += r.passes;
-                st.evals_max = std::max(st.evals_max, r.evals); st.passes_max = std::max(st.passes_max, r.passes);
+                add_search_stats(st, r);
                 if (const int rc2 = reduce(r, res[(size_t)who[cls][i]])) return rc2;
             }
         return EMSAR_HIP_OK;
@@ -173,27 +165,17 @@ struct CompareRun {
     }
 };
 
-// the two contexts hold one structure: compared on what they keep on the host
-inline bool same_structure(const emsar_hip_ctx *a, const emsar_hip_ctx *b) {
-    return a->n_rows == b->n_rows && a->n_tx == b->n_tx && a->nnz == b->nnz && a->h_row_ptr == b->h_row_ptr && a->h_col == b->h_col;
-}
-
 }  // namespace
 
 extern "C" {
 
 int emsar_hip_compare(emsar_hip_ctx *ctx_a, emsar_hip_ctx *ctx_b, const emsar_em_params *p, const emsar_compare_params *cp, int32_t n_query,
                       const int32_t *query_tids, const emsar_compare_outputs *out, emsar_compare_stats *stats) {
-    if (!ctx_a || !ctx_b || ctx_a == ctx_b) return EMSAR_HIP_ERR_ARG;
-    if (!ctx_a->have_sample || !ctx_b->have_sample) return EMSAR_HIP_ERR_STATE;      // first: a state error whatever the other arguments say
-    if (ctx_a->device != ctx_b->device || !same_structure(ctx_a, ctx_b)) return EMSAR_HIP_ERR_ARG;
+    if (const int rc = two_samples_ok(ctx_a, ctx_b, false)) return rc;
     if (const int rc = query_ok(ctx_a, n_query, query_tids)) return rc;
     const emsar_compare_params prm = cp ? *cp : emsar_compare_params{1.0, 0.0, 0, 0};
     if (!std::isfinite(prm.ratio) || prm.ratio < 0.0 || !std::isfinite(prm.dev_tol)) return EMSAR_HIP_ERR_ARG;
-    emsar_hip_ctx *const ctx = ctx_b;
-    HIPCHK(hipSetDevice(ctx_b->device));
-    HIPCHK(hipStreamSynchronize(ctx_b->stream));
-    return run_query_call<CompareRun>(ctx_a, stats, ctx_b, p, prm, n_query, query_tids, out);
+    return run_two_sample_call<CompareRun>(ctx_a, ctx_b, stats, p, prm, n_query, query_tids, out);
 }
 
 // Diagnostic only (not declared in the public header; needs no device): what emsar_hip_compare gives a transcript whose component is a

@@ -1,7 +1,7 @@
 // compare_usage.hpp -- the two-sample test of isoform usage behind include/emsar_hip.h: emsar_hip_compare_usage.  Part of
-// emsar_hip.hip's translation unit, included after profile_genes.hpp: the members of the queried transcripts' genes are located and
-// grouped into parts as the gene-level two-sample test does (SetQuery, GeneQueryMembers), k_compare_usage_sets
-// (kernels_compare_usage.hpp) runs the searches.
+// emsar_hip.hip's translation unit, included after gene_parts.hpp: the members of the queried transcripts' genes are located and
+// grouped into parts as the gene-level two-sample test does (SetQuery; GeneQueryMembers, GenePartLists: gene_parts.hpp),
+// k_compare_usage_sets (kernels_compare_usage.hpp) runs the searches.
 // One call = one CompareUsageRun:  plan, classify   SetQuery's stages on the union of the members of the queried transcripts' genes, once
 //                                                   per context
 //                                  group            per gene and sample: its parts (GeneSideParts), once however many of its transcripts
@@ -20,38 +20,16 @@ enum UsageStatus : int32_t {
     USE_NOT_RESIDENT = EMSAR_USAGE_NOT_RESIDENT, USE_UNCONVERGED = EMSAR_USAGE_UNCONVERGED, USE_TOO_LARGE = EMSAR_USAGE_TOO_LARGE,
     USE_UNDEFINED = EMSAR_USAGE_UNDEFINED, USE_SINGLE = EMSAR_USAGE_SINGLE
 };
-enum { kUsageMaxParts = 64 };
-
 inline UsageSearchParams usage_search_params(const emsar_usage_params &up) {
     return UsageSearchParams{up.dev_tol > 0.0 ? up.dev_tol : 1e-4, up.max_evals > 0 ? up.max_evals : 40, up.max_outer > 0 ? up.max_outer : 12};
 }
 
 // the search of k_compare_usage_sets on a gene whose parts are all closed form (ca: A's, cb: B's; tc_a, tc_b: t's place in each),
-// usage_closed_sum as its evaluation
+// gene_closed_sum as its evaluation
 inline UsageRec compare_usage_closed_search(const CompareGeneClosed *ca, int na, int tc_a, const CompareGeneClosed *cb, int nb, int tc_b, double den_ta,
                                             double mn_a, double den_tb, double mn_b, const UsageSearchParams &Q) {
-    UsageOuter O;
-    O.start();
-    UsageLeft LA{0.0, 0.0, 0.0, 0.0, 0.0}, LB{0.0, 0.0, 0.0, 0.0, 0.0};
-    int evals = 0, inner_ok = 1;
-    do {
-        const bool first = O.outer == 0;
-        for (int side = 0; side < 2; side++) {
-            const bool b = side != 0;
-            const double den_t0 = b ? den_tb : den_ta, mn = b ? mn_b : mn_a;
-            UsageInner J;
-            bool more = J.start(first, O.u, b ? O.t0_b : O.t0_a, b ? O.X0_b : O.X0_a, b ? O.F0_b : O.F0_a, den_t0, mn);
-            while (more) {
-                double T = 0.0, X = 0.0, F = 0.0;
-                usage_closed_sum(b ? cb : ca, b ? nb : na, b ? tc_b : tc_a, J.pt, mn, T, X, F);
-                more = J.step(first, T, X, F, O.u, den_t0, mn, Q);
-            }
-            evals += J.evals;
-            inner_ok &= J.ok;
-            if (b) LB = J.left(O.u); else LA = J.left(O.u);
-        }
-    } while (O.step(LA, LB, Q));
-    return O.record(evals, 0, 1, inner_ok, 0);
+    const auto eval = [&](bool b, const GenePoint &pt, GeneSums &S) { gene_closed_sum(b ? cb : ca, b ? nb : na, pt, S); };
+    return usage_search(den_ta, mn_a, tc_a, den_tb, mn_b, tc_b, Q, eval).record(GeneSolveCount());
 }
 
 // what one queried transcript is given
@@ -89,10 +67,7 @@ struct CompareUsageRun : GeneQueryMembers {
     std::vector<int32_t> tids;           // the queried transcripts, each once
     std::vector<int32_t> slot_of_tid;    // [n_tx] -> tids / res, -1 = not queried
     std::vector<Result> res;
-    std::vector<CompareGenePart> h_parts;
-    std::vector<CompareGeneClosed> h_closed;
-    DevBuf<CompareGenePart> d_parts;
-    DevBuf<CompareGeneClosed> d_closed;
+    GenePartLists lists;
     DevBuf<int32_t> d_gene_of_b;         // ctx_b's gene_of_lib when it has no map of its own
     SetItemRunner<UsageItem, UsageRec> runner;
     emsar_usage_stats st{};
@@ -131,7 +106,7 @@ struct CompareUsageRun : GeneQueryMembers {
         std::vector<UsageRec> recs[emsar::kSetClasses];
         std::vector<int32_t> who[emsar::kSetClasses];          // item -> tids slot
         const std::vector<int32_t> &of_tx = ctx->genes.h_gene_of_tx;
-        struct GeneSides { GeneSideParts a, b; int32_t part_off = -1, closed_off = -1; bool made = false; };
+        struct GeneSides { GeneSideParts a, b; GenePartLists::Offsets at{-1, -1}; bool made = false; };
         std::vector<GeneSides> sides(genes.size());
         for (size_t i = 0; i < tids.size(); i++) {
             const int32_t t = tids[i], g = of_tx[(size_t)t];
@@ -145,7 +120,7 @@ struct CompareUsageRun : GeneQueryMembers {
             if (ta.standing == SetQuery::OUTSIDE || tb.standing == SetQuery::OUTSIDE) { o.status = USE_OUTSIDE; continue; }
             if (G.a.not_resident || G.b.not_resident) { o.status = USE_NOT_RESIDENT; continue; }
             if (G.a.members < 2 || G.b.members < 2) { o.status = USE_SINGLE; continue; }
-            if (G.a.count() > kUsageMaxParts || G.b.count() > kUsageMaxParts) { o.status = USE_TOO_LARGE; continue; }
+            if (G.a.count() > kGeneMaxParts || G.b.count() > kGeneMaxParts) { o.status = USE_TOO_LARGE; continue; }
             o.parts = G.a.count() + G.b.count();
             st.parts_max = std::max(st.parts_max, o.parts);
             int32_t tc_a, tc_b;
@@ -159,61 +134,40 @@ struct CompareUsageRun : GeneQueryMembers {
                 if (const int rc = reduce(r, o)) return rc;
                 continue;
             }
-            if (G.part_off < 0) {                              // the gene's slices, once for all its transcripts
-                G.part_off = (int32_t)h_parts.size(); G.closed_off = (int32_t)h_closed.size();
-                h_parts.insert(h_parts.end(), G.a.sets.begin(), G.a.sets.end());
-                h_parts.insert(h_parts.end(), G.b.sets.begin(), G.b.sets.end());
-                h_closed.insert(h_closed.end(), G.a.closed.begin(), G.a.closed.end());
-                h_closed.insert(h_closed.end(), G.b.closed.begin(), G.b.closed.end());
-            }
-            int cls = -1;
-            for (const CompareGenePart &pt : G.a.sets) cls = std::max(cls, (int)pt.cls);
-            for (const CompareGenePart &pt : G.b.sets) cls = std::max(cls, (int)pt.cls);
-            items[cls].push_back(UsageItem{G.part_off, (int32_t)G.a.sets.size(), (int32_t)G.b.sets.size(), G.closed_off, (int32_t)G.a.closed.size(),
+            if (G.at.part_off < 0) G.at = lists.append(G.a, &G.b);            // the gene's slices, once for all its transcripts
+            const int cls = lists.launch_class(G.at.part_off, (int32_t)(G.a.sets.size() + G.b.sets.size()));
+            items[cls].push_back(UsageItem{G.at.part_off, (int32_t)G.a.sets.size(), (int32_t)G.b.sets.size(), G.at.closed_off, (int32_t)G.a.closed.size(),
                                            (int32_t)G.b.closed.size(), g, ta.lib, tb.lib, tc_a, tc_b, 0, den_ta, den_tb, mn_a, mn_b});
             who[cls].push_back((int32_t)i);
         }
         const int32_t *gene_of_lib_b = nullptr;
-        if (!h_parts.empty()) {
+        if (!lists.empty()) {
             if (const int rc = gene_of_lib_of_b(ctx, ctx_b, d_gene_of_b, gene_of_lib_b)) return rc;
-            HIPCHK(d_parts.upload(h_parts.data(), h_parts.size()));
-            HIPCHK(d_closed.upload(h_closed.data(), h_closed.size()));
+            if (const int rc = lists.upload(ctx)) return rc;
         }
         const SetSolveParams P = set_params(qa.p);
-        const CompareSide GA = CompareRun::side_of(ctx), GB = CompareRun::side_of(ctx_b);
-        const auto &SA = ctx->sets.RS, &SB = ctx_b->sets.RS;
-        size_t lds[emsar::kSetClasses], most = 0;              // a launch class holds the sets of its own and of every smaller class
-        for (int c = 0; c < emsar::kSetClasses; c++) lds[c] = most = std::max(most, std::max((size_t)SA.max_lds[c], (size_t)SB.max_lds[c]));
+        const CompareSide GA = side_of(ctx), GB = side_of(ctx_b);
+        size_t lds[emsar::kSetClasses];
+        launch_class_lds(lds, ctx, ctx_b);
         HIPCHK(set_class_lds_attributes(kCompareUsageSets));
         const int32_t n_tx = ctx->n_tx;
         const int rc = runner.run(items, recs, st.device_ms, st.items_launched,
             [&](int c, const UsageItem &it) {
                 if (!(it.den_ta > 0.0) || !(it.den_tb > 0.0) || !(it.mn_a > 0.0) || !(it.mn_b > 0.0)) return false;
-                if (it.n_parts_a < 0 || it.n_parts_b < 0 || it.n_closed_a < 0 || it.n_closed_b < 0 || it.part_off < 0 || it.closed_off < 0) return false;
-                if (it.n_parts_a > kUsageMaxParts || it.n_parts_b > kUsageMaxParts) return false;
-                if ((size_t)it.part_off + (size_t)(it.n_parts_a + it.n_parts_b) > h_parts.size()) return false;
-                if ((size_t)it.closed_off + (size_t)(it.n_closed_a + it.n_closed_b) > h_closed.size()) return false;
-                if (it.gene < 0 || it.gene >= ctx->genes.n_genes || it.t_a < 0 || it.t_a >= n_tx || it.t_b < 0 || it.t_b >= n_tx) return false;
+                if (it.t_a < 0 || it.t_a >= n_tx || it.t_b < 0 || it.t_b >= n_tx) return false;
                 if (it.tc_a < -1 || it.tc_a >= it.n_closed_a || it.tc_b < -1 || it.tc_b >= it.n_closed_b) return false;
-                int top = -1;
-                for (int32_t k = 0; k < it.n_parts_a + it.n_parts_b; k++) {
-                    const CompareGenePart &pt = h_parts[(size_t)it.part_off + (size_t)k];
-                    if (pt.side != (k < it.n_parts_a ? 0 : 1) || pt.cls > c || !set_desc(pt.side ? ctx_b : ctx, pt.cls, pt.set)) return false;
-                    top = std::max(top, (int)pt.cls);
-                }
-                return top == c;
+                return lists.slice_ok(c, it.part_off, it.closed_off, it.gene, {{ctx, it.n_parts_a, it.n_closed_a}, {ctx_b, it.n_parts_b, it.n_closed_b}});
             },
             [&](int c, int threads, hipStream_t s, size_t cnt, const UsageItem *d_items, UsageRec *d_rec) {
-                hipLaunchKernelGGL(kCompareUsageSets[c], dim3((unsigned)cnt), dim3(threads), lds[c], s, d_items, d_parts.get(), d_closed.get(), GA, GB,
-                                   (const int32_t *)ctx->genes.d_gene_of_lib, gene_of_lib_b, d_rec, P, Q);
+                hipLaunchKernelGGL(kCompareUsageSets[c], dim3((unsigned)cnt), dim3(threads), lds[c], s, d_items, lists.d_parts.get(), lists.d_closed.get(),
+                                   GA, GB, (const int32_t *)ctx->genes.d_gene_of_lib, gene_of_lib_b, d_rec, P, Q);
             });
         if (rc) return rc;
         for (int cls = 0; cls < emsar::kSetClasses; cls++)
             for (size_t i = 0; i < recs[cls].size(); i++) {
                 const UsageRec &r = recs[cls][i];
-                st.evals_sum += r.evals; st.passes_sum += r.passes; st.outer_sum += r.outer;
-                st.evals_max = std::max(st.evals_max, r.evals); st.passes_max = std::max(st.passes_max, r.passes);
-                st.outer_max = std::max(st.outer_max, r.outer);
+                add_search_stats(st, r);
+                st.outer_sum += r.outer; st.outer_max = std::max(st.outer_max, r.outer);
                 if (const int rc2 = reduce(r, res[(size_t)who[cls][i]])) return rc2;
             }
         return EMSAR_HIP_OK;
@@ -266,19 +220,11 @@ extern "C" {
 
 int emsar_hip_compare_usage(emsar_hip_ctx *ctx_a, emsar_hip_ctx *ctx_b, const emsar_em_params *p, const emsar_usage_params *up, int32_t n_query,
                             const int32_t *query_tids, const emsar_usage_outputs *out, emsar_usage_stats *stats) {
-    if (!ctx_a || !ctx_b || ctx_a == ctx_b) return EMSAR_HIP_ERR_ARG;
-    if (!ctx_a->have_sample || !ctx_b->have_sample) return EMSAR_HIP_ERR_STATE;      // first: a state error whatever the other arguments say
-    if (ctx_a->device != ctx_b->device || !same_structure(ctx_a, ctx_b)) return EMSAR_HIP_ERR_ARG;
-    if (!ctx_a->genes.have_genes) return EMSAR_HIP_ERR_STATE;
-    const GeneMap &ga = ctx_a->genes, &gb = ctx_b->genes;
-    if (gb.have_genes && (gb.n_genes != ga.n_genes || gb.h_gene_of_tx != ga.h_gene_of_tx)) return EMSAR_HIP_ERR_ARG;
+    if (const int rc = two_samples_ok(ctx_a, ctx_b, true)) return rc;
     if (const int rc = query_ok(ctx_a, n_query, query_tids)) return rc;
     const emsar_usage_params prm = up ? *up : emsar_usage_params{0.0, 0, 0};
     if (!std::isfinite(prm.dev_tol)) return EMSAR_HIP_ERR_ARG;
-    emsar_hip_ctx *const ctx = ctx_b;
-    HIPCHK(hipSetDevice(ctx_b->device));
-    HIPCHK(hipStreamSynchronize(ctx_b->stream));
-    return run_query_call<CompareUsageRun>(ctx_a, stats, ctx_b, p, prm, n_query, query_tids, out);
+    return run_two_sample_call<CompareUsageRun>(ctx_a, ctx_b, stats, p, prm, n_query, query_tids, out);
 }
 
 // Diagnostic only (not declared in the public header; makes no HIP call): what emsar_hip_compare_usage gives member t_a of A's list /
@@ -308,7 +254,7 @@ int emsar_hip_debug_compare_usage_closed(int32_t n_a, const double *u_a, const d
         UsageResult o;
         if (tc[0] < 0 || tc[1] < 0) o.status = USE_OUTSIDE;
         else if (c[0].size() < 2 || c[1].size() < 2) o.status = USE_SINGLE;
-        else if (c[0].size() > kUsageMaxParts || c[1].size() > kUsageMaxParts) o.status = USE_TOO_LARGE;
+        else if (c[0].size() > kGeneMaxParts || c[1].size() > kGeneMaxParts) o.status = USE_TOO_LARGE;
         else {
             o.parts = (int32_t)(c[0].size() + c[1].size());
             const UsageRec r = compare_usage_closed_search(c[0].data(), (int)c[0].size(), tc[0], c[1].data(), (int)c[1].size(), tc[1], den_t[0], mn[0],

@@ -22,6 +22,7 @@
 //   presence.hpp      the presence test (a likelihood-ratio test per transcript on its resident set) and its C ABI
 //   profile.hpp       the profile-likelihood intervals (two confidence limits per transcript, each a root search over set solves) and their C ABI
 //   compare.hpp       the two-sample likelihood-ratio test (two contexts; per transcript a multiplier search over set solves of both samples) and its C ABI
+//   gene_parts.hpp    what the gene-level drivers share: the queried genes' members grouped into parts, the owner of a call's part lists
 //   compare_genes.hpp the same test per gene (the null on the gene sum; per evaluation a loop over the gene's parts in both samples) and its C ABI
 //   asym.hpp          the asymptotic standard errors (the observed information of every component, factorised on the device) and their C ABI
 // Kernels (one translation unit, included below):
@@ -39,8 +40,10 @@
 //                         (solve_set_scaled); ProfileStep: the search step kernel and host share; IllinoisBracket
 //   kernels_compare.hpp   k_compare_sets                         one workgroup searches one transcript's multiplier: per evaluation a set solve of each sample
 //                         (solve_set_scaled); CompareStep: the search step kernel and host share
-//   kernels_compare_genes.hpp   k_compare_gene_sets              one workgroup searches one gene's multiplier: per evaluation every set part of
-//                         both samples solved with the members' den shifted (solve_gene_part; solve_one_set's DenEdit hook)
+//   kernels_gene_parts.hpp      what the gene-level kernels share: the part lists, solve_gene_part (a set part solved with the members' den
+//                         edited; solve_one_set's DenEdit hook), eval_gene_side (one sample: its set parts, then its closed-form parts)
+//   kernels_compare_genes.hpp   k_compare_gene_sets              one workgroup searches one gene's multiplier: per evaluation every part of
+//                         both samples with the members' den shifted (compare_gene_search, shared with the host)
 //   kernels_boot.hpp      k_boot_draw, k_boot_accum, ...         the Poisson bootstrap (draws: boot_rng.hpp; sets: k_solve_sets_boot)
 //                         k_sub_draw, k_sub_scale                the depth subsampling: binomial draws, every replicate to its own depth
 //   kernels_genes.hpp     k_gene_sums, k_gene_finish             per-gene sums in a fixed order (gene_sums, the bootstrap's gene sd)
@@ -81,6 +84,7 @@
 #include "kernels_presence.hpp"
 #include "kernels_profile.hpp"
 #include "kernels_compare.hpp"
+#include "kernels_gene_parts.hpp"
 #include "kernels_compare_genes.hpp"
 #include "kernels_profile_genes.hpp"
 #include "kernels_cluster.hpp"
@@ -844,7 +848,8 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 #include "presence.hpp"   // the presence test and its entry points (after set_items.hpp: SetItemRunner, SetQuery, query_ok)
 #include "profile.hpp"    // the profile-likelihood intervals and their entry points (after presence.hpp: PresenceRun)
 #include "compare.hpp"    // the two-sample likelihood-ratio test and its entry points (after set_items.hpp: SetItemRunner, SetQuery)
-#include "compare_genes.hpp"   // the gene-level two-sample test and its entry points (after compare.hpp: CompareRun, compare_reduce, same_structure)
-#include "profile_genes.hpp"   // the gene-level profile intervals and the gene presence test (after compare_genes.hpp: GeneQueryMembers)
-#include "compare_usage.hpp"   // the two-sample test of isoform usage (after profile_genes.hpp; GeneQueryMembers, CompareRun::side_of, same_structure)
+#include "gene_parts.hpp"      // what the gene-level drivers share: GeneQueryMembers, GeneSideParts, GenePartLists (after compare.hpp)
+#include "compare_genes.hpp"   // the gene-level two-sample test and its entry points (after gene_parts.hpp; compare.hpp: compare_reduce)
+#include "profile_genes.hpp"   // the gene-level profile intervals and the gene presence test (after gene_parts.hpp; profile.hpp: profile_cut)
+#include "compare_usage.hpp"   // the two-sample test of isoform usage (after gene_parts.hpp; compare.hpp: compare_pvalue)
 #include "asym.hpp"       //the asymptotic standard errors and their entry points (after fit.hpp: fit_ensure_csr, launch_gene_sums)

@@ -26,6 +26,12 @@ struct CompareSide {
     const uint16_t *rp, *ent, *cp, *crow;
     const double *den;
 };
+// Its descriptors of size class cls.  The three pointers are read before the choice is made: G may be one of two kernel arguments picked
+// at run time, and a choice among loads would turn into a load from a computed address, which keeps a copy of the arguments in scratch.
+__device__ __forceinline__ const emsar::SetDesc *side_desc(const CompareSide &G, int cls) {
+    const emsar::SetDesc *const d0 = G.desc0, *const d1 = G.desc1, *const d2 = G.desc2;
+    return cls == 0 ? d0 : cls == 1 ? d1 : d2;
+}
 
 // The root search of the multiplier lambda = v * lambda_end on v in [0, 1), on h(v) = (x_A - r x_B) / (x_A + r x_B): h(0) comes from the
 // evaluation at lambda = 0, h(1) = -sign h(0) is known without a solve (x_B -> inf or x_A -> inf at the end of the range).  Illinois
@@ -135,10 +141,9 @@ __global__ __launch_bounds__(THREADS) void k_compare_sets(const CompareItem *__r
             double x_t, F;
             if (set < 0) compare_closed_form(b ? it.u_b : it.u_a, den_t, scale, x_t, F);
             else {
-                const emsar::SetDesc *dp = cls == 0 ? (b ? GB.desc0 : GA.desc0) : cls == 1 ? (b ? GB.desc1 : GA.desc1) : (b ? GB.desc2 : GA.desc2);
-                const ScaledSolve e = solve_set_scaled<THREADS>(dp[set], b ? GB.g_tid : GA.g_tid, b ? GB.g_u : GA.g_u, b ? GB.row_w : GA.row_w,
-                                                                b ? GB.rp : GA.rp, b ? GB.ent : GA.ent, b ? GB.cp : GA.cp, b ? GB.crow : GA.crow,
-                                                                b ? GB.den : GA.den, P, t, den_t, scale);
+                const CompareSide &G = b ? GB : GA;
+                const ScaledSolve e = solve_set_scaled<THREADS>(side_desc(G, cls)[set], G.g_tid, G.g_u, G.row_w, G.rp, G.ent, G.cp, G.crow, G.den, P, t,
+                                                                den_t, scale);
                 passes += e.passes;
                 solves_ok &= e.converged;
                 infeasible += e.infeasible;

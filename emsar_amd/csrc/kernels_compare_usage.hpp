@@ -1,11 +1,11 @@
 // kernels_compare_usage.hpp -- k_compare_usage_sets: the two-sample test of one transcript's share of its gene (emsar_hip_compare_usage;
 // driver: compare_usage.hpp)
 #pragma once
-// included by emsar_hip.hip only, after kernels_compare_genes.hpp
+// included by emsar_hip.hip only, after kernels_gene_parts.hpp
 
 namespace {
 
-// The null  theta_t^A / X^A = theta_t^B / X^B = u  (X = the gene sum, members and parts as k_compare_gene_sets defines them) is not linear
+// The null  theta_t^A / X^A = theta_t^B / X^B = u  (X = the gene sum, members and parts as kernels_gene_parts.hpp defines them) is not linear
 // in theta, so the search has two levels.
 //   inner   u fixed: the samples decouple, and in one sample the constraint theta_t - u X = 0 is linear.  Its dual
 //           D(lambda) = max [F - lambda (theta_t - u X)] is the ordinary problem with den_t + lambda (1 - u) on t and den_s - lambda u on
@@ -53,9 +53,8 @@ struct UsagePoint {
     }
 };
 
-// The multiplier search of one sample at one share u, driven by k_compare_usage_sets and by the host (compare_usage_closed_search):
-// the caller evaluates the sample at pt and hands theta_t, X and F there to step(), until step() says stop.  Every argument is the same
-// in all threads of the workgroup.
+// The multiplier search of one sample at one share u, driven by usage_search below: the caller evaluates the sample at pt and
+// hands theta_t, X and F there to step(), until step() says stop.  Every argument is the same in all threads of the workgroup.
 struct UsageInner {
     CompareSearch S;
     UsagePoint pt;
@@ -161,16 +160,40 @@ struct UsageOuter {
     }
 };
 
-// the closed-form parts of one side at pt, summed in list order: x = u / den', F = u log x - x den; member k_t of the list is t (-1: none)
-__host__ __device__ inline void usage_closed_sum(const CompareGeneClosed *c, int n, int k_t, const UsagePoint &pt, double mn, double &T, double &X,
-                                                 double &F) {
-    for (int k = 0; k < n; k++) {
-        const double u = c[k].u, den = c[k].den;
-        const double x = u > 0.0 ? u / (k == k_t ? pt.den_t : compare_gene_den(den, mn, pt.scale, pt.shift)) : 0.0;
-        X += x;
-        if (k == k_t) T += x;
-        F += u > 0.0 ? u * log(x) - x * den : 0.0;
-    }
+// The whole search of one transcript, both levels, driven by k_compare_usage_sets and by the host (genes whose parts are all closed
+// form): eval(b, pt, S) adds sample b (false = A) at pt into S.  tc_a, tc_b: t's place in each side's closed-form slice (-1: none).
+struct UsageSearched {
+    UsageOuter O;
+    int evals, inner_ok;                 // inner evaluations summed; every inner search met its stopping rule
+    __host__ __device__ UsageRec record(const GeneSolveCount &C) const { return O.record(evals, C.passes, C.solves_ok, inner_ok, C.infeasible); }
+};
+template <class Eval>
+__host__ __device__ __forceinline__ UsageSearched usage_search(double den_ta, double mn_a, int tc_a, double den_tb, double mn_b, int tc_b,
+                                                               const UsageSearchParams &Q, const Eval &eval) {
+    UsageSearched R;
+    UsageOuter &O = R.O;
+    O.start();
+    R.evals = 0; R.inner_ok = 1;
+    UsageLeft LA{0.0, 0.0, 0.0, 0.0, 0.0}, LB{0.0, 0.0, 0.0, 0.0, 0.0};
+    do {
+        const bool first = O.outer == 0;
+#pragma nounroll
+        for (int side = 0; side < 2; side++) {
+            const bool b = side != 0;
+            const double den_t0 = b ? den_tb : den_ta, mn = b ? mn_b : mn_a;
+            UsageInner J;
+            bool more = J.start(first, O.u, b ? O.t0_b : O.t0_a, b ? O.X0_b : O.X0_a, b ? O.F0_b : O.F0_a, den_t0, mn);
+            while (more) {
+                GeneSums S{0.0, 0.0, 0.0};
+                eval(b, GenePoint{mn, J.pt.scale, J.pt.shift, b ? tc_b : tc_a, J.pt.den_t}, S);
+                more = J.step(first, S.T, S.X, S.F, O.u, den_t0, mn, Q);
+            }
+            R.evals += J.evals;
+            R.inner_ok &= J.ok;
+            if (b) LB = J.left(O.u); else LA = J.left(O.u);
+        }
+    } while (O.step(LA, LB, Q));
+    return R;
 }
 
 // solve_one_set's den hook: t (by its library tid) takes den_t of the point, every other member of the gene that takes part its
@@ -186,43 +209,10 @@ struct UsageDenEdit {
     }
 };
 
-// One set part at one point, as solve_gene_part: the set solved with the members' den of the point in LDS, then F with the ORIGINAL den
-// and, from the same reduction, the part's share of theta_t and of the gene sum.  All three come back through set_uniform.
-struct UsagePartSolve { double T, X, F; int passes, converged, infeasible; };
-template <int THREADS>
-__device__ __forceinline__ UsagePartSolve solve_usage_part(const emsar::SetDesc d, const int32_t *__restrict__ g_tid, const double *__restrict__ g_u,
-                                                           const double *__restrict__ row_w, const uint16_t *__restrict__ rp_g,
-                                                           const uint16_t *__restrict__ ent_g, const uint16_t *__restrict__ cp_g,
-                                                           const uint16_t *__restrict__ crow_g, const double *__restrict__ den_g,
-                                                           SetSolveParams P, const int32_t *__restrict__ gene_of, int32_t gene, int32_t t,
-                                                           double den_t, double mn, double scale, double shift) {
-    SetSolved K;
-    solve_one_set<THREADS, true, UsageDenEdit>(d, g_tid, g_u, row_w, rp_g, ent_g, cp_g, crow_g, den_g, nullptr, nullptr, P, -1, &K, 0.0,
-                                               UsageDenEdit{gene_of, gene, t, den_t, mn, scale, shift});
-    const SetLds &L = K.L;
-    const double *x = K.res;
-    set_sync<THREADS>();
-    double s3[3] = {0.0, 0.0, 0.0};        // sum R log S + u log x, sum x den (original den), infeasible
-    double xs = 0.0, xt = 0.0;             // this thread's share of the members' sum and of theta_t
-    set_objective_terms<THREADS>(L, x, s3, [&](int i) { return den_g[g_tid[d.tid_off + i]]; },
-                                 [&](int i, double xi, double) {
-                                     const int32_t tid = g_tid[d.tid_off + i];
-                                     if (gene_of[tid] == gene) { xs += xi; if (tid == t) xt += xi; }
-                                 });
-    double s5[5] = {s3[0], s3[1], s3[2], xs, xt};
-    set_reduce_sum<THREADS, 5>(s5, L.red);
-    set_sync<THREADS>();                   // the next solve_one_set overwrites the LDS this epilogue read
-    return UsagePartSolve{set_uniform(s5[4]), set_uniform(s5[3]), set_uniform(s5[0] - s5[1]), K.passes, K.converged, (int)s5[2]};
-}
-
-// Workgroup x runs the whole search of item x, both levels (UsageOuter, UsageInner).  One evaluation of a sample = its set parts one
-// after the other in the same LDS (solve_usage_part), then its closed-form parts in registers, by every thread alike; theta_t, X and F
-// are summed over them in list order.  solve_one_set reloads the set and restarts from the uniform point each time, so a record is a
-// pure function of (item, its slices of the lists, P, Q).  The launch has the thread count of the largest class among the item's set
-// parts and the LDS of that class and every smaller one, of both samples.
-// Every branch is taken by the whole workgroup: the part fields come from the item list by scalar loads of an address no thread
-// differs in, theta_t, X and F go through set_uniform; the strided loops and the reductions stand outside any branch that threads
-// could take differently.
+// Workgroup x runs the whole search of item x, both levels (usage_search), one evaluation of a sample by eval_gene_side
+// (kernels_gene_parts.hpp: the uniformity of every branch, the worst case per evaluation) with theta_t riding on the reduction
+// (UsageTally), so a record is a pure function of (item, its slices of the lists, P, Q).  The launch has the thread count of the largest
+// class among the item's set parts and the LDS of that class and every smaller one, of both samples.
 // The worst case is max(Q.max_outer, 2) * 2 * Q.max_evals * parts * P.max_iter passes, parts <= 64 per sample (the driver's rule).
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void k_compare_usage_sets(const UsageItem *__restrict__ items, const CompareGenePart *__restrict__ parts,
@@ -230,45 +220,17 @@ __global__ __launch_bounds__(THREADS) void k_compare_usage_sets(const UsageItem 
                                                                 const int32_t *__restrict__ gene_of_a, const int32_t *__restrict__ gene_of_b,
                                                                 UsageRec *__restrict__ rec, SetSolveParams P, UsageSearchParams Q) {
     const UsageItem it = items[blockIdx.x];
-    UsageOuter O;
-    O.start();
-    UsageLeft LA{0.0, 0.0, 0.0, 0.0, 0.0}, LB{0.0, 0.0, 0.0, 0.0, 0.0};
-    int evals = 0, passes = 0, solves_ok = 1, inner_ok = 1, infeasible = 0;
-    do {
-        const bool first = O.outer == 0;
-#pragma nounroll
-        for (int side = 0; side < 2; side++) {
-            const bool b = side != 0;
-            const double den_t0 = b ? it.den_tb : it.den_ta, mn = b ? it.mn_b : it.mn_a;
-            const int p0 = it.part_off + (b ? it.n_parts_a : 0), np = b ? it.n_parts_b : it.n_parts_a;
-            UsageInner J;
-            bool more = J.start(first, O.u, b ? O.t0_b : O.t0_a, b ? O.X0_b : O.X0_a, b ? O.F0_b : O.F0_a, den_t0, mn);
-            while (more) {
-                double T = 0.0, X = 0.0, F = 0.0;
-#pragma nounroll
-                for (int k = 0; k < np; k++) {
-                    const CompareGenePart pt = parts[p0 + k];
-                    const emsar::SetDesc *dp = pt.cls == 0 ? (b ? GB.desc0 : GA.desc0) : pt.cls == 1 ? (b ? GB.desc1 : GA.desc1) : (b ? GB.desc2 : GA.desc2);
-                    const UsagePartSolve e = solve_usage_part<THREADS>(dp[pt.set], b ? GB.g_tid : GA.g_tid, b ? GB.g_u : GA.g_u, b ? GB.row_w : GA.row_w,
-                                                                       b ? GB.rp : GA.rp, b ? GB.ent : GA.ent, b ? GB.cp : GA.cp, b ? GB.crow : GA.crow,
-                                                                       b ? GB.den : GA.den, P, b ? gene_of_b : gene_of_a, it.gene, b ? it.t_b : it.t_a,
-                                                                       J.pt.den_t, mn, J.pt.scale, J.pt.shift);
-                    passes += e.passes;
-                    solves_ok &= e.converged;
-                    infeasible += e.infeasible;
-                    T += e.T; X += e.X; F += e.F;
-                }
-                usage_closed_sum(closed + it.closed_off + (b ? it.n_closed_a : 0), b ? it.n_closed_b : it.n_closed_a, b ? it.tc_b : it.tc_a, J.pt, mn,
-                                 T, X, F);
-                more = J.step(first, T, X, F, O.u, den_t0, mn, Q);
-            }
-            evals += J.evals;
-            inner_ok &= J.ok;
-            if (b) LB = J.left(O.u); else LA = J.left(O.u);
-        }
-    } while (O.step(LA, LB, Q));
-    if (threadIdx.x == 0) rec[blockIdx.x] = O.record(evals, passes, solves_ok, inner_ok, infeasible);
+    GeneSolveCount C;
+    const UsageSearched R = usage_search(it.den_ta, it.mn_a, it.tc_a, it.den_tb, it.mn_b, it.tc_b, Q, [&](bool b, const GenePoint &pt, GeneSums &S) {
+        const CompareSide &G = b ? GB : GA;
+        eval_gene_side<THREADS, true, UsageTally>(G, parts + it.part_off + (b ? it.n_parts_a : 0), b ? it.n_parts_b : it.n_parts_a,
+                                                  closed + it.closed_off + (b ? it.n_closed_a : 0), b ? it.n_closed_b : it.n_closed_a, pt, P,
+                                                  UsageDenEdit{b ? gene_of_b : gene_of_a, it.gene, b ? it.t_b : it.t_a, pt.den_t, pt.mn, pt.scale,
+                                                               pt.shift}, S, C);
+    });
+    if (threadIdx.x == 0) rec[blockIdx.x] = R.record(C);
 }
 const auto kCompareUsageSets = set_kernels(k_compare_usage_sets<64>, k_compare_usage_sets<256>, k_compare_usage_sets<512>);
 
 }  // namespace
+

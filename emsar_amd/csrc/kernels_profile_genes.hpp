@@ -1,12 +1,12 @@
 // kernels_profile_genes.hpp -- k_profile_gene_base, k_profile_gene_sets: the profile-likelihood interval of a gene's total and the gene
 // presence test (emsar_hip_profile_genes; driver: profile_genes.hpp)
 #pragma once
-// included by emsar_hip.hip only, after kernels_compare_genes.hpp
+// included by emsar_hip.hip only, after kernels_gene_parts.hpp
 
 namespace {
 
-// A gene's members taking part, its parts (CompareGenePart with side 0, CompareGeneClosed), X and F are k_compare_gene_sets' for one
-// sample.  The path: the maximiser of F - lambda X is the same problem with den_t + lambda on every member taking part, lambda in
+// A gene's members taking part, its parts (CompareGenePart with side 0, CompareGeneClosed), X and F are those of kernels_gene_parts.hpp
+// for one sample.  The path: the maximiser of F - lambda X is the same problem with den_t + lambda on every member taking part, lambda in
 // (-mn, inf), mn = the smallest such den; the coordinate is s = 1 + lambda / mn, a member's den in LDS compare_gene_den(dn, mn, s,
 // mn * (s - 1)).  s > 1 is the lower side, 0 < s < 1 the upper side, s = 1 every den exactly its own.
 //
@@ -70,73 +70,44 @@ struct GeneDropEdit {
     __device__ double operator()(int32_t tid, double dn) const { return gene_of[tid] == gene ? 0.0 : dn; }
 };
 
-// One set part without the gene: the presence epilogue's F (the members are at 0, anyone else's den lies in LDS with its own bits) and
-// the rows and folded counts with reads that nothing explains.  F comes back through set_uniform as solve_gene_part's does.
-struct GenePartDrop { double F; int passes, converged, infeasible; };
-template <int THREADS>
-__device__ __forceinline__ GenePartDrop solve_gene_part_dropped(const emsar::SetDesc d, const int32_t *__restrict__ g_tid, const double *__restrict__ g_u,
-                                                                const double *__restrict__ row_w, const uint16_t *__restrict__ rp_g,
-                                                                const uint16_t *__restrict__ ent_g, const uint16_t *__restrict__ cp_g,
-                                                                const uint16_t *__restrict__ crow_g, const double *__restrict__ den_g,
-                                                                SetSolveParams P, const int32_t *__restrict__ gene_of, int32_t gene) {
-    SetSolved K;
-    solve_one_set<THREADS, true, GeneDropEdit>(d, g_tid, g_u, row_w, rp_g, ent_g, cp_g, crow_g, den_g, nullptr, nullptr, P, -1, &K, 0.0,
-                                               GeneDropEdit{gene_of, gene});
-    const SetLds &L = K.L;
-    set_sync<THREADS>();
-    double s3[3] = {0.0, 0.0, 0.0};        // sum R log S + u log x, sum x den, infeasible
-    set_objective_terms<THREADS>(L, K.res, s3, [&](int i) { return L.den[i]; }, [](int, double, double) {});
-    set_reduce_sum<THREADS, 3>(s3, L.red);
-    set_sync<THREADS>();                   // the next solve_one_set overwrites the LDS this epilogue read
-    return GenePartDrop{set_uniform(s3[0] - s3[1]), K.passes, K.converged, (int)s3[2]};
+// the record of a search (k_profile_gene_sets; profile_gene_closed_limit, profile_genes.hpp); the host's closed-form genes have no
+// passes, no solve that could fail and nothing infeasible: GeneSolveCount()
+__host__ __device__ inline ProfileRec profile_gene_record(const ProfileGeneStep &T, const GeneSolveCount &C) {
+    ProfileRec r;
+    r.x = T.T.x; r.dev = T.T.dev; r.s = T.T.s; r.F = T.T.F;
+    r.evals = T.evals(); r.passes = C.passes; r.flags = (T.T.search_ok ? PROFILE_REC_SEARCH_OK : 0) | (C.solves_ok ? PROFILE_REC_SOLVES_OK : 0);
+    r.infeasible = C.infeasible;
+    return r;
 }
 
-__device__ __forceinline__ const emsar::SetDesc *gene_part_desc(const CompareSide &G, int cls) { return cls == 0 ? G.desc0 : cls == 1 ? G.desc1 : G.desc2; }
-
-// Workgroup x runs gene x: every set part at s = 1 (solve_gene_part: the code path of every evaluation of the searches, every den
-// exactly its own), the closed-form parts in registers, then -- unless the host has decided it -- every set part without the gene's
-// members.  A record is a pure function of (item, its slices of the lists, P).  The launch has the thread count of the largest class
-// among the item's set parts and the LDS of that class and every smaller one.
-// Every branch is taken by the whole workgroup, as the comment at k_compare_gene_sets requires: the item and part fields come from
-// scalar loads of an address no thread differs in, X and F go through set_uniform.
+// Workgroup x runs gene x: the sample at s = 1 (eval_gene_side with GeneDenEdit: the code path of every evaluation of the searches,
+// every den exactly its own), then -- unless the host has decided it -- every set part without the gene's members (GeneDropEdit; F
+// with the den that lies in LDS: the members are at 0, anyone else's has its own bits).  A record is a pure function of (item, its
+// slices of the lists, P).  The launch has the thread count of the largest class among the item's set parts and the LDS of that class
+// and every smaller one.  Every branch is taken by the whole workgroup, as the comment at eval_gene_side requires.
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void k_profile_gene_base(const ProfileGeneBaseItem *__restrict__ items, const CompareGenePart *__restrict__ parts,
                                                                const CompareGeneClosed *__restrict__ closed, CompareSide G,
                                                                const int32_t *__restrict__ gene_of, ProfileGeneBaseRec *__restrict__ rec,
                                                                SetSolveParams P) {
     const ProfileGeneBaseItem it = items[blockIdx.x];
-    double X = 0.0, F = 0.0, F_drop = 0.0;
-    int passes = 0, solves_ok = 1, infeasible = 0;
-#pragma nounroll
-    for (int k = 0; k < it.n_parts; k++) {
-        const CompareGenePart pt = parts[it.part_off + k];
-        const GenePartSolve e = solve_gene_part<THREADS>(gene_part_desc(G, pt.cls)[pt.set], G.g_tid, G.g_u, G.row_w, G.rp, G.ent, G.cp, G.crow, G.den, P,
-                                                         gene_of, it.gene, it.mn, 1.0, 0.0);
-        passes += e.passes;
-        solves_ok &= e.converged;
-        X += e.X; F += e.F;
-    }
-    compare_gene_closed_sum(closed + it.closed_off, it.n_closed, it.mn, 1.0, 0.0, X, F);
-    if (!it.skip_drop) {
-#pragma nounroll
-        for (int k = 0; k < it.n_parts; k++) {
-            const CompareGenePart pt = parts[it.part_off + k];
-            const GenePartDrop e = solve_gene_part_dropped<THREADS>(gene_part_desc(G, pt.cls)[pt.set], G.g_tid, G.g_u, G.row_w, G.rp, G.ent, G.cp, G.crow,
-                                                                    G.den, P, gene_of, it.gene);
-            passes += e.passes;
-            solves_ok &= e.converged;
-            infeasible += e.infeasible;
-            F_drop += e.F;
-        }
-    }
-    if (threadIdx.x == 0) rec[blockIdx.x] = ProfileGeneBaseRec{X, F, F_drop, infeasible, passes, solves_ok, 0};
+    const GenePoint own{it.mn, 1.0, 0.0, -1, 0.0};
+    GeneSums S{0.0, 0.0, 0.0}, D{0.0, 0.0, 0.0};
+    GeneSolveCount C, CD;
+    eval_gene_side<THREADS, true, GeneSumTally>(G, parts + it.part_off, it.n_parts, closed + it.closed_off, it.n_closed, own, P,
+                                                GeneDenEdit{gene_of, it.gene, it.mn, 1.0, 0.0}, S, C);
+    if (!it.skip_drop)
+        eval_gene_side<THREADS, false, NoTally>(G, parts + it.part_off, it.n_parts, closed, 0, own, P, GeneDropEdit{gene_of, it.gene}, D, CD);
+    if (threadIdx.x == 0)
+        rec[blockIdx.x] = ProfileGeneBaseRec{S.X, S.F, D.F, CD.infeasible, C.passes + CD.passes, C.solves_ok & CD.solves_ok, 0};
 }
 const auto kProfileGeneBase = set_kernels(k_profile_gene_base<64>, k_profile_gene_base<256>, k_profile_gene_base<512>);
 
-// Workgroup x runs the whole search of item x (ProfileGeneStep).  One evaluation = every set part of the item one after the other in
-// the same LDS (solve_gene_part at s), then the closed-form parts in registers, by every thread alike.  solve_one_set reloads the set
-// and restarts from the uniform point each time, so a record is a pure function of (item, its slices of the lists, P, Q).  Launch class
-// and uniformity as k_profile_gene_base.  The worst case is n_parts * Q.max_evals * P.max_iter passes; the driver admits 64 parts.
+// Workgroup x runs the whole search of item x (ProfileGeneStep), one evaluation by eval_gene_side at s, so a record is a pure function
+// of (item, its slices of the lists, P, Q).  Launch class and uniformity as k_profile_gene_base.  The worst case is
+// n_parts * Q.max_evals * P.max_iter passes; the driver admits 64 parts.  The loop is written out here and in profile_gene_closed_limit:
+// run through a driver shared with the host, as compare_gene_search is, it took ten more scalar spills at 256 and 512 threads and
+// emsar_hip_profile_genes ran 1.5 % longer.
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void k_profile_gene_sets(const ProfileGeneItem *__restrict__ items, const CompareGenePart *__restrict__ parts,
                                                                const CompareGeneClosed *__restrict__ closed, CompareSide G,
@@ -144,33 +115,20 @@ __global__ __launch_bounds__(THREADS) void k_profile_gene_sets(const ProfileGene
                                                                ProfileSearchParams Q) {
     const ProfileGeneItem it = items[blockIdx.x];
     const double sqrt_q = sqrt(Q.q);
+    GeneSolveCount C;
     ProfileGeneStep T;
     T.start(it.side, it.end, it.X_hat, it.mn, it.F_hat, Q);
-    int passes = 0, solves_ok = 1, infeasible = 0;
     for (;;) {
-        const double s = T.scale(), shift = it.mn * (s - 1.0);
-        double X = 0.0, F = 0.0;
-#pragma nounroll
-        for (int k = 0; k < it.n_parts; k++) {
-            const CompareGenePart pt = parts[it.part_off + k];
-            const GenePartSolve e = solve_gene_part<THREADS>(gene_part_desc(G, pt.cls)[pt.set], G.g_tid, G.g_u, G.row_w, G.rp, G.ent, G.cp, G.crow, G.den,
-                                                             P, gene_of, it.gene, it.mn, s, shift);
-            passes += e.passes;
-            solves_ok &= e.converged;
-            infeasible += e.infeasible;
-            X += e.X; F += e.F;
-        }
-        compare_gene_closed_sum(closed + it.closed_off, it.n_closed, it.mn, s, shift, X, F);
-        if (!T.step(X, F, it.F_hat, it.mn0, sqrt_q)) break;
+        const double s = T.scale();
+        const GenePoint pt{it.mn, s, it.mn * (s - 1.0), -1, 0.0};
+        GeneSums S{0.0, 0.0, 0.0};
+        eval_gene_side<THREADS, true, GeneSumTally>(G, parts + it.part_off, it.n_parts, closed + it.closed_off, it.n_closed, pt, P,
+                                                    GeneDenEdit{gene_of, it.gene, pt.mn, pt.scale, pt.shift}, S, C);
+        if (!T.step(S.X, S.F, it.F_hat, it.mn0, sqrt_q)) break;
     }
-    if (threadIdx.x == 0) {
-        ProfileRec r;
-        r.x = T.T.x; r.dev = T.T.dev; r.s = T.T.s; r.F = T.T.F;
-        r.evals = T.evals(); r.passes = passes; r.flags = (T.T.search_ok ? PROFILE_REC_SEARCH_OK : 0) | (solves_ok ? PROFILE_REC_SOLVES_OK : 0);
-        r.infeasible = infeasible;
-        rec[blockIdx.x] = r;
-    }
+    if (threadIdx.x == 0) rec[blockIdx.x] = profile_gene_record(T, C);
 }
 const auto kProfileGeneSets = set_kernels(k_profile_gene_sets<64>, k_profile_gene_sets<256>, k_profile_gene_sets<512>);
 
 }  // namespace
+

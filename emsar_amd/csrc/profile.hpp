@@ -123,8 +123,7 @@ struct ProfileRun {
                 Limits &l = lim[(size_t)who[cls][i]];
                 const ProfileRec &r = recs[cls][i];
                 const bool base_ok = pres.base_of(pres.q.cand[(size_t)who[cls][i]]).converged != 0;
-                st.evals_sum += r.evals; st.passes_sum += r.passes;
-                st.evals_max = std::max(st.evals_max, r.evals); st.passes_max = std::max(st.passes_max, r.passes);
+                add_search_stats(st, r);
                 l.evals += r.evals;
                 if (r.flags != (PROFILE_REC_SEARCH_OK | PROFILE_REC_SOLVES_OK) || !base_ok) l.capped = true;
                 if (items[cls][i].side == 0) { l.lower = r.x; l.dev_lower = r.dev; }

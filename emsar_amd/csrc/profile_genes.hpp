@@ -1,7 +1,8 @@
 // profile_genes.hpp -- the gene-level profile-likelihood intervals and the gene presence test behind include/emsar_hip.h:
 // emsar_hip_profile_genes (device) and emsar_hip_gene_presence_pvalue_host (no HIP call).  Part of emsar_hip.hip's translation unit,
-// included after compare_genes.hpp: the members of the queried genes are located and grouped into parts as the gene-level two-sample
-// test does (SetQuery, GeneQueryMembers), k_profile_gene_base and k_profile_gene_sets (kernels_profile_genes.hpp) do the solves.
+// included after gene_parts.hpp: the members of the queried genes are located and grouped into parts as the gene-level two-sample
+// test does (SetQuery; GeneQueryMembers, GenePartLists: gene_parts.hpp), k_profile_gene_base and k_profile_gene_sets
+// (kernels_profile_genes.hpp) do the solves.
 // One call = one ProfileGenesRun:  plan, classify   SetQuery's stages on the union of the queried genes' members
 //                                  group            per gene: its parts, mn, the end of the upper range; the host-only statuses; a gene
 //                                                   whose parts are all closed form is finished on the host (profile_gene_closed)
@@ -14,7 +15,7 @@
 
 namespace {
 
-enum { GPROF_TOO_LARGE = EMSAR_GENE_PROFILE_TOO_LARGE, kProfileGeneMaxParts = 64 };
+enum { GPROF_TOO_LARGE = EMSAR_GENE_PROFILE_TOO_LARGE };
 
 // P(chi2_k > lambda), x = lambda / 2: k even exp(-x) sum_{j < k/2} x^j / j!, k odd erfc(sqrt x) + exp(-x) sum_{j=1}^{(k-1)/2}
 // x^(j-1/2) / Gamma(j+1/2).  The terms are built by their ratios; beyond x = 700, where exp(-x) underflows against terms that
@@ -74,22 +75,19 @@ inline void profile_gene_take(const ProfileRec &r, int side, ProfileGeneResult &
     else { o.upper = r.x; o.dev_upper = r.dev; o.evals_upper = r.evals; }
 }
 
-// one limit of a gene whose parts are all closed form: k_profile_gene_sets' loop with compare_gene_closed_sum as its evaluation
+// one limit of a gene whose parts are all closed form: k_profile_gene_sets' loop with gene_closed_sum as its evaluation
 inline ProfileRec profile_gene_closed_limit(const CompareGeneClosed *c, int n, int side, int end, double mn, double mn0, double X_hat, double F_hat,
                                             const ProfileSearchParams &Q) {
     ProfileGeneStep T;
     T.start(side, end, X_hat, mn, F_hat, Q);
     const double sqrt_q = std::sqrt(Q.q);
-    double X, F;
+    GeneSums S;
     do {
         const double s = T.scale();
-        X = F = 0.0;
-        compare_gene_closed_sum(c, n, mn, s, mn * (s - 1.0), X, F);
-    } while (T.step(X, F, F_hat, mn0, sqrt_q));
-    ProfileRec r{};
-    r.x = T.T.x; r.dev = T.T.dev; r.s = T.T.s; r.F = T.T.F;
-    r.evals = T.evals(); r.flags = (T.T.search_ok ? PROFILE_REC_SEARCH_OK : 0) | PROFILE_REC_SOLVES_OK;
-    return r;
+        S = GeneSums{0.0, 0.0, 0.0};
+        gene_closed_sum(c, n, GenePoint{mn, s, mn * (s - 1.0), -1, 0.0}, S);
+    } while (T.step(S.X, S.F, F_hat, mn0, sqrt_q));
+    return profile_gene_record(T, GeneSolveCount());
 }
 
 // A gene whose parts are all closed form (s.sets empty, s.closed not): baseline, Lambda and both limits on the host.  A member with
@@ -98,8 +96,10 @@ inline ProfileRec profile_gene_closed_limit(const CompareGeneClosed *c, int n, i
 inline bool profile_gene_closed(const GeneSideParts &s, const ProfileSearchParams &Q, ProfileGeneResult &o) {
     const CompareGeneClosed *c = s.closed.data();
     const int n = (int)s.closed.size();
-    double X_hat = 0.0, F_hat = 0.0, mn0;
-    compare_gene_closed_sum(c, n, s.min_den, 1.0, 0.0, X_hat, F_hat);
+    GeneSums hat{0.0, 0.0, 0.0};
+    gene_closed_sum(c, n, GenePoint{s.min_den, 1.0, 0.0, -1, 0.0}, hat);
+    const double X_hat = hat.X, F_hat = hat.F;
+    double mn0;
     if (!std::isfinite(F_hat) || !std::isfinite(X_hat)) return false;
     o.gene_hat = X_hat;
     profile_gene_presence(s.own_reads ? INFINITY : 0.0, Q.q, o);
@@ -126,10 +126,7 @@ struct ProfileGenesRun : GeneQueryMembers {
     ProfileSearchParams Q;
     std::vector<ProfileGeneResult> res;
     std::vector<Pending> pending;
-    std::vector<CompareGenePart> h_parts;
-    std::vector<CompareGeneClosed> h_closed;
-    DevBuf<CompareGenePart> d_parts;
-    DevBuf<CompareGeneClosed> d_closed;
+    GenePartLists lists;
     SetItemRunner<ProfileGeneBaseItem, ProfileGeneBaseRec> base_runner;
     SetItemRunner<ProfileGeneItem, ProfileRec> runner;
     emsar_profile_gene_stats st{};
@@ -150,7 +147,7 @@ struct ProfileGenesRun : GeneQueryMembers {
             const GeneSideParts s = side_parts(q, k, 0);
             if (s.not_resident) { o.status = PROF_NOT_RESIDENT; continue; }
             if (s.count() == 0) { o.status = PROF_OUTSIDE; continue; }
-            if (s.count() > kProfileGeneMaxParts) { o.status = GPROF_TOO_LARGE; continue; }
+            if (s.count() > kGeneMaxParts) { o.status = GPROF_TOO_LARGE; continue; }
             o.parts = s.count(); o.members = s.members;
             st.parts_max = std::max(st.parts_max, o.parts);
             if (s.sets.empty()) {
@@ -158,43 +155,32 @@ struct ProfileGenesRun : GeneQueryMembers {
                 continue;
             }
             Pending g;
-            g.slot = (int32_t)k; g.cls = -1;
-            for (const CompareGenePart &pt : s.sets) g.cls = std::max(g.cls, pt.cls);
-            g.part_off = (int32_t)h_parts.size(); g.n_parts = (int32_t)s.sets.size();
-            g.closed_off = (int32_t)h_closed.size(); g.n_closed = (int32_t)s.closed.size();
+            const GenePartLists::Offsets at = lists.append(s);
+            g.slot = (int32_t)k;
+            g.part_off = at.part_off; g.n_parts = (int32_t)s.sets.size();
+            g.closed_off = at.closed_off; g.n_closed = (int32_t)s.closed.size();
+            g.cls = lists.launch_class(g.part_off, g.n_parts);
             g.end = profile_gene_end(s, g.mn0) ? 1 : 0;
             if (!g.end) g.mn0 = s.min_den;           // never used; keeps the item finite
             g.mn = s.min_den; g.own_reads = s.own_reads;
             pending.push_back(g);
-            h_parts.insert(h_parts.end(), s.sets.begin(), s.sets.end());
-            h_closed.insert(h_closed.end(), s.closed.begin(), s.closed.end());
         }
         return EMSAR_HIP_OK;
     }
 
-    // an item's slices against the lists, its parts against the descriptors, and its launch class: the class of its largest set part
+    // what the two item kinds share: mn and the slices (GenePartLists::slice_ok)
     bool slices_ok(int c, int32_t part_off, int32_t n_parts, int32_t closed_off, int32_t n_closed, int32_t gene, double mn) const {
-        if (!(mn > 0.0) || n_parts < 1 || n_parts > kProfileGeneMaxParts || n_closed < 0 || part_off < 0 || closed_off < 0) return false;
-        if ((size_t)part_off + (size_t)n_parts > h_parts.size() || (size_t)closed_off + (size_t)n_closed > h_closed.size()) return false;
-        if (n_parts + n_closed > kProfileGeneMaxParts || gene < 0 || gene >= ctx->genes.n_genes) return false;
-        int top = -1;
-        for (int32_t k = 0; k < n_parts; k++) {
-            const CompareGenePart &pt = h_parts[(size_t)part_off + (size_t)k];
-            if (pt.side != 0 || pt.cls > c || !set_desc(ctx, pt.cls, pt.set)) return false;
-            top = std::max(top, (int)pt.cls);
-        }
-        return top == c;
+        return mn > 0.0 && lists.slice_ok(c, part_off, closed_off, gene, {{ctx, n_parts, n_closed}});
     }
 
     int solve_search_reduce(const SetQuery &q) {
         if (pending.empty()) return EMSAR_HIP_OK;
-        HIPCHK(d_parts.upload(h_parts.data(), h_parts.size()));
-        if (!h_closed.empty()) HIPCHK(d_closed.upload(h_closed.data(), h_closed.size()));
+        if (const int urc = lists.upload(ctx)) return urc;
         const SetSolveParams P = set_params(q.p);
-        const CompareSide G = CompareRun::side_of(ctx);
+        const CompareSide G = side_of(ctx);
         const int32_t *gene_of = ctx->genes.d_gene_of_lib;
-        size_t lds[emsar::kSetClasses], most = 0;              // a launch class holds the sets of its own and of every smaller class
-        for (int c = 0; c < emsar::kSetClasses; c++) lds[c] = most = std::max(most, (size_t)ctx->sets.RS.max_lds[c]);
+        size_t lds[emsar::kSetClasses];
+        launch_class_lds(lds, ctx);
 
         // baseline and drop
         std::vector<ProfileGeneBaseItem> bitems[emsar::kSetClasses];
@@ -209,8 +195,8 @@ struct ProfileGenesRun : GeneQueryMembers {
         int rc = base_runner.run(bitems, brecs, st.baseline_ms, st.items_launched,
             [&](int c, const ProfileGeneBaseItem &it) { return slices_ok(c, it.part_off, it.n_parts, it.closed_off, it.n_closed, it.gene, it.mn); },
             [&](int c, int threads, hipStream_t s, size_t cnt, const ProfileGeneBaseItem *d_items, ProfileGeneBaseRec *d_rec) {
-                hipLaunchKernelGGL(kProfileGeneBase[c], dim3((unsigned)cnt), dim3(threads), lds[c], s, d_items, d_parts.get(), d_closed.get(), G, gene_of,
-                                   d_rec, P);
+                hipLaunchKernelGGL(kProfileGeneBase[c], dim3((unsigned)cnt), dim3(threads), lds[c], s, d_items, lists.d_parts.get(), lists.d_closed.get(),
+                                   G, gene_of, d_rec, P);
             });
         if (rc) return rc;
 
@@ -247,16 +233,14 @@ struct ProfileGenesRun : GeneQueryMembers {
                        (it.end == 0 || (it.side == 1 && it.mn0 > 0.0 && it.mn0 == it.mn));
             },
             [&](int c, int threads, hipStream_t s, size_t cnt, const ProfileGeneItem *d_items, ProfileRec *d_rec) {
-                hipLaunchKernelGGL(kProfileGeneSets[c], dim3((unsigned)cnt), dim3(threads), lds[c], s, d_items, d_parts.get(), d_closed.get(), G, gene_of,
-                                   d_rec, P, Q);
+                hipLaunchKernelGGL(kProfileGeneSets[c], dim3((unsigned)cnt), dim3(threads), lds[c], s, d_items, lists.d_parts.get(), lists.d_closed.get(),
+                                   G, gene_of, d_rec, P, Q);
             });
         if (rc) return rc;
         for (int cls = 0; cls < emsar::kSetClasses; cls++)
             for (size_t i = 0; i < recs[cls].size(); i++) {
-                const ProfileRec &r = recs[cls][i];
-                st.evals_sum += r.evals; st.passes_sum += r.passes;
-                st.evals_max = std::max(st.evals_max, r.evals); st.passes_max = std::max(st.passes_max, r.passes);
-                profile_gene_take(r, items[cls][i].side, res[(size_t)who[cls][i]]);
+                add_search_stats(st, recs[cls][i]);
+                profile_gene_take(recs[cls][i], items[cls][i].side, res[(size_t)who[cls][i]]);
             }
         return EMSAR_HIP_OK;
     }
@@ -300,9 +284,7 @@ int emsar_hip_profile_genes(emsar_hip_ctx *ctx, const emsar_em_params *p, const 
                             const emsar_profile_gene_outputs *out, emsar_profile_gene_stats *stats) {
     if (!ctx) return EMSAR_HIP_ERR_ARG;
     if (!ctx->have_sample || !ctx->genes.have_genes) return EMSAR_HIP_ERR_STATE;      // first: a state error whatever the other arguments say
-    if (!query_genes) n_query = ctx->genes.n_genes;
-    if (n_query < 0) return EMSAR_HIP_ERR_ARG;
-    if (query_genes) for (int32_t i = 0; i < n_query; i++) if (query_genes[i] < 0 || query_genes[i] >= ctx->genes.n_genes) return EMSAR_HIP_ERR_ARG;
+    if (const int rc = gene_query_ok(ctx, n_query, query_genes)) return rc;
     const emsar_profile_params prm = pp ? *pp : emsar_profile_params{0.95, 0.0, 0, 0};
     if (!profile_params_ok(prm)) return EMSAR_HIP_ERR_ARG;
     return run_query_call<ProfileGenesRun>(ctx, stats, p, prm, n_query, query_genes, out);

@@ -1,7 +1,8 @@
 // set_items.hpp -- what the drivers of the resident sets share beyond solve.hpp: the batch rule (item_batch), the item runner of a
 // set-kernel family whose workgroups each take one item and leave one record (SetItemRunner: presence.hpp, profile.hpp, compare.hpp),
-// the locator of a call's queried transcripts (SetQuery) and the frame of a per-transcript call (query_ok, run_query_call).  Part of
-// emsar_hip.hip's translation unit, included after solve.hpp.
+// the locator of a call's queried transcripts (SetQuery), what the two-sample and gene-level drivers ask of a context (side_of,
+// launch_class_lds, add_search_stats) and the frames of the calls (query_ok, gene_query_ok, two_samples_ok, run_query_call,
+// run_two_sample_call).  Part of emsar_hip.hip's translation unit, included after solve.hpp.
 
 namespace {
 
@@ -20,6 +21,27 @@ inline int64_t item_batch(int64_t per_item_bytes, const char *env_name, int64_t 
 inline const emsar::SetDesc *set_desc(const emsar_hip_ctx *ctx, int c, int32_t set) {
     if (c < 0 || c >= emsar::kSetClasses || set < 0 || (size_t)set >= ctx->sets.RS.desc[c].size()) return nullptr;
     return &ctx->sets.RS.desc[c][(size_t)set];
+}
+// the set records of the context's sample, as the two-sample and the gene-level kernels take them
+inline CompareSide side_of(const emsar_hip_ctx *c) {
+    const SetsDev &D = c->sets;
+    return CompareSide{D.d_sdesc[0].get(), D.d_sdesc[1].get(), D.d_sdesc[2].get(), D.d_g_tid.get(), D.d_g_u.get(), D.d_row_w.get(),
+                       D.d_srp.get(), D.d_sent.get(), D.d_scp.get(), D.d_scrow.get(), c->vec.d_den.get()};
+}
+// The LDS of a launch class whose items may hold sets of their own class and of every smaller one, of context a and (when given) b
+inline void launch_class_lds(size_t (&lds)[emsar::kSetClasses], const emsar_hip_ctx *a, const emsar_hip_ctx *b = nullptr) {
+    size_t most = 0;
+    for (int c = 0; c < emsar::kSetClasses; c++) {
+        most = std::max(most, (size_t)a->sets.RS.max_lds[c]);
+        if (b) most = std::max(most, (size_t)b->sets.RS.max_lds[c]);
+        lds[c] = most;
+    }
+}
+// a search record into the statistics of its call
+template <class Stats, class Rec>
+inline void add_search_stats(Stats &st, const Rec &r) {
+    st.evals_sum += r.evals; st.passes_sum += r.passes;
+    st.evals_max = std::max(st.evals_max, r.evals); st.passes_max = std::max(st.passes_max, r.passes);
 }
 
 // Items of the three launch classes through one family of set kernels, at most a batch per class and launch, the classes next to each
@@ -184,7 +206,30 @@ inline int query_ok(const emsar_hip_ctx *ctx, int32_t &n_query, const int32_t *q
     if (query_tids) for (int32_t i = 0; i < n_query; i++) if (query_tids[i] < 0 || query_tids[i] >= ctx->n_tx) return EMSAR_HIP_ERR_ARG;
     return EMSAR_HIP_OK;
 }
-// Its frame: the device, the stream drained, one Run(ctx, args...) built and run, total_ms taken, its statistics copied out
+// The query of a per-gene call of a context that holds a gene map: null = every gene in order, else n_query gene ids
+inline int gene_query_ok(const emsar_hip_ctx *ctx, int32_t &n_query, const int32_t *query_genes) {
+    if (!query_genes) n_query = ctx->genes.n_genes;
+    if (n_query < 0) return EMSAR_HIP_ERR_ARG;
+    if (query_genes) for (int32_t i = 0; i < n_query; i++) if (query_genes[i] < 0 || query_genes[i] >= ctx->genes.n_genes) return EMSAR_HIP_ERR_ARG;
+    return EMSAR_HIP_OK;
+}
+// the two contexts hold one structure: compared on what they keep on the host
+inline bool same_structure(const emsar_hip_ctx *a, const emsar_hip_ctx *b) {
+    return a->n_rows == b->n_rows && a->n_tx == b->n_tx && a->nnz == b->nnz && a->h_row_ptr == b->h_row_ptr && a->h_col == b->h_col;
+}
+// The two contexts of a two-sample call: distinct, each with a sample (a state error whatever the other arguments say), on one device,
+// of one structure; genes: ctx_a holds the gene map, and ctx_b's, if it has one, is the same
+inline int two_samples_ok(const emsar_hip_ctx *ctx_a, const emsar_hip_ctx *ctx_b, bool genes) {
+    if (!ctx_a || !ctx_b || ctx_a == ctx_b) return EMSAR_HIP_ERR_ARG;
+    if (!ctx_a->have_sample || !ctx_b->have_sample) return EMSAR_HIP_ERR_STATE;
+    if (ctx_a->device != ctx_b->device || !same_structure(ctx_a, ctx_b)) return EMSAR_HIP_ERR_ARG;
+    if (!genes) return EMSAR_HIP_OK;
+    if (!ctx_a->genes.have_genes) return EMSAR_HIP_ERR_STATE;
+    const GeneMap &ga = ctx_a->genes, &gb = ctx_b->genes;
+    if (gb.have_genes && (gb.n_genes != ga.n_genes || gb.h_gene_of_tx != ga.h_gene_of_tx)) return EMSAR_HIP_ERR_ARG;
+    return EMSAR_HIP_OK;
+}
+// The frame of a call: the device, the stream drained, one Run(ctx, args...) built and run, total_ms taken, its statistics copied out
 template <class Run, class Stats, class... Args>
 int run_query_call(emsar_hip_ctx *ctx, Stats *stats, const Args &...args) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -197,6 +242,15 @@ int run_query_call(emsar_hip_ctx *ctx, Stats *stats, const Args &...args) {
         if (stats) *stats = run.st;
     } catch (const std::bad_alloc &) { return EMSAR_HIP_ERR_OOM; }
     return EMSAR_HIP_OK;
+}
+// The frame of a two-sample call, its arguments checked: ctx_b's stream drained (the launches run on ctx_a's streams), then ctx_a's
+// frame with one Run(ctx_a, ctx_b, args...)
+template <class Run, class Stats, class... Args>
+int run_two_sample_call(emsar_hip_ctx *ctx_a, emsar_hip_ctx *ctx_b, Stats *stats, const Args &...args) {
+    emsar_hip_ctx *const ctx = ctx_b;
+    HIPCHK(hipSetDevice(ctx_b->device));
+    HIPCHK(hipStreamSynchronize(ctx_b->stream));
+    return run_query_call<Run>(ctx_a, stats, ctx_b, args...);
 }
 
 }  // namespace
