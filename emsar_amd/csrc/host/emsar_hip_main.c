@@ -1,5 +1,6 @@
 /* emsar_hip_main.c -- command-line driver: the per-sample loop of the reference's main()
- * (/root/reference/src/emsar_main.c:380-488) with run_MLE_threads() replaced by the HIP library.
+ * (the reference's src/emsar_main.c:380-488) with run_MLE_threads() replaced by the HIP library.  One function per analysis
+ * (stage_model .. stage_subsample, called in that order by run_sample()), every file format in output.c, the argument parsers in cli_parse.h.
  *
  *   emsar-hip [options] -I index.rsh outdir outprefix alignmentfile            (single sample)
  *   emsar-hip [options] -M -I index.rsh outdir outprefix alignmentfilelist     (one alignment file per line)
@@ -81,6 +82,7 @@
 
 #include "../../../include/emsar_hip.h"
 #include "emsar_host.h"
+#include "cli_parse.h"
 
 typedef struct {
     const char *rsh_path, *outdir, *prefix;
@@ -106,6 +108,11 @@ typedef struct {
     int32_t *cmp_q; int cmp_nq;       /* --compare-list FILE, as --presence-list */
     struct compare_ref *ref;          /* --compare: sample 0's solver inputs, shared by the workers */
     const emsar_genes *genes;         /* its gene map, read once by main() and shared read-only by the workers */
+    /* what only main() reads: the options as given, before the index, the lists and the devices they name have been looked at */
+    const char *strand; int multisample, gpus, device;
+    int dev_map[64], n_dev_map;       /* --devices */
+    const char *presence_list, *profile_list, *compare_list;
+    int boundary_cut_given, profile_level_given, compare_ratio_given;
 } config;
 
 /* --compare: what sample 0 was solved from, published once by the worker that runs it (under the workers' mutex; ready: 0 = not yet,
@@ -145,86 +152,6 @@ static void publish_ref(worker_arg *w, const emsar_rsh *r, const int32_t *R, con
     pthread_mutex_unlock(w->mu);
 }
 
-/* .compare: one line per queried transcript -- tid transcriptID FPKM FPKM_ref log2FC Lambda p status evals; a value that is not finite is
- * written as "inf", "-inf" or "nan" */
-static void put_num(FILE *f, const char *fmt, double v) {
-    if (isnan(v)) fputs("nan", f); else if (isinf(v)) fputs(v > 0 ? "inf" : "-inf", f); else fprintf(f, fmt, v);
-}
-static int write_compare(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, const emsar_compare_outputs *o) {
-    static const char *const word[5] = {"TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED"};
-    FILE *f = fopen(path, "w");
-    if (!f) return EMSAR_HOST_ERR_IO;
-    fprintf(f, "tid\ttranscriptID\tFPKM\tFPKM_ref\tlog2FC\tLambda\tp\tstatus\tevals\n");
-    for (int32_t i = 0; i < n_query; i++) {
-        const int32_t t = query ? query[i] : i;
-        fprintf(f, "%d\t%s\t", t, r->names[t]);
-        put_num(f, "%lf", o->theta_a[i]); fputc('\t', f);
-        put_num(f, "%lf", o->theta_b[i]); fputc('\t', f);
-        put_num(f, "%lf", o->log2fc[i]); fputc('\t', f);
-        put_num(f, "%lf", o->lambda[i]); fputc('\t', f);
-        put_num(f, "%.6g", o->pvalue[i]);
-        fprintf(f, "\t%s\t%d\n", o->status[i] >= 0 && o->status[i] < 5 ? word[o->status[i]] : "?", o->evals[i]);
-    }
-    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
-}
-
-/* .gcompare (--compare --g2t): one line per gene in the order of .gfpkm -- gene gFPKM gFPKM_ref log2FC Lambda p status evals parts; numbers
- * as in .compare */
-static int write_gcompare(const char *path, const emsar_genes *g, const emsar_compare_gene_outputs *o) {
-    static const char *const word[6] = {"TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE"};
-    FILE *f = fopen(path, "w");
-    if (!f) return EMSAR_HOST_ERR_IO;
-    fprintf(f, "gene\tgFPKM\tgFPKM_ref\tlog2FC\tLambda\tp\tstatus\tevals\tparts\n");
-    for (int32_t k = 0; k < g->n_genes; k++) {
-        fprintf(f, "%s\t", g->names[k]);
-        put_num(f, "%lf", o->gene_a[k]); fputc('\t', f);
-        put_num(f, "%lf", o->gene_b[k]); fputc('\t', f);
-        put_num(f, "%lf", o->log2fc[k]); fputc('\t', f);
-        put_num(f, "%lf", o->lambda[k]); fputc('\t', f);
-        put_num(f, "%.6g", o->pvalue[k]);
-        fprintf(f, "\t%s\t%d\t%d\n", o->status[k] >= 0 && o->status[k] < 6 ? word[o->status[k]] : "?", o->evals[k], o->parts[k]);
-    }
-    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
-}
-
-/* .ucompare (--compare-usage): one line per queried transcript -- transcript gene usage usage_ref dlogit Lambda p status outer evals; numbers
- * as in .compare */
-static int write_ucompare(const char *path, const emsar_rsh *r, const emsar_genes *g, int32_t n_query, const int32_t *query, const emsar_usage_outputs *o) {
-    static const char *const word[8] = {"TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE", "UNDEFINED", "SINGLE"};
-    FILE *f = fopen(path, "w");
-    if (!f) return EMSAR_HOST_ERR_IO;
-    fprintf(f, "transcript\tgene\tusage\tusage_ref\tdlogit\tLambda\tp\tstatus\touter\tevals\n");
-    for (int32_t i = 0; i < n_query; i++) {
-        const int32_t t = query ? query[i] : i, k = g->gene_of_tx[t];
-        fprintf(f, "%s\t%s\t", r->names[t], k >= 0 ? g->names[k] : "");
-        put_num(f, "%lf", o->usage_a[i]); fputc('\t', f);
-        put_num(f, "%lf", o->usage_b[i]); fputc('\t', f);
-        put_num(f, "%lf", o->dlogit[i]); fputc('\t', f);
-        put_num(f, "%lf", o->lambda[i]); fputc('\t', f);
-        put_num(f, "%.6g", o->pvalue[i]);
-        fprintf(f, "\t%s\t%d\t%d\n", o->status[i] >= 0 && o->status[i] < 8 ? word[o->status[i]] : "?", o->outer_evals[i], o->evals[i]);
-    }
-    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
-}
-
-/* .gprofile (--profile --g2t): one line per gene in the order of .gfpkm -- gene gFPKM lower upper Lambda p members status; numbers as in
- * .profile, p as in .compare */
-static int write_gprofile(const char *path, const emsar_genes *g, const double *gfpkm, const emsar_profile_gene_outputs *o) {
-    static const char *const word[6] = {"TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE"};
-    FILE *f = fopen(path, "w");
-    if (!f) return EMSAR_HOST_ERR_IO;
-    fprintf(f, "gene\tgFPKM\tlower\tupper\tLambda\tp\tmembers\tstatus\n");
-    for (int32_t k = 0; k < g->n_genes; k++) {
-        fprintf(f, "%s\t%lf\t", g->names[k], gfpkm[k]);
-        put_num(f, "%lf", o->lower[k]); fputc('\t', f);
-        put_num(f, "%lf", o->upper[k]); fputc('\t', f);
-        put_num(f, "%lf", o->lambda[k]); fputc('\t', f);
-        put_num(f, "%.6g", o->pvalue[k]);
-        fprintf(f, "\t%d\t%s\n", o->members[k], o->status[k] >= 0 && o->status[k] < 6 ? word[o->status[k]] : "?");
-    }
-    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
-}
-
 /* emsar_aln_opts.collapse on the GPU (--device-collapse): the parse threads of a worker hand their read-level rows to a context
  * of their own on the worker's device (the solve context is busy with the sample before); one call at a time */
 static int cli_collapse(void *user, int64_t n_rows, int32_t n_tx, const uint64_t *row_ptr, const int32_t *col_idx,
@@ -259,382 +186,419 @@ static void parse_wait(parse_job *j) {
     j->w = NULL;
 }
 
-static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parsed) {
-    config *cfg = w->cfg; const emsar_rsh *r = w->rsh;
-    char err[512] = "", path[4096];
-    emsar_counts *cnt = parsed->cnt; emsar_model *m = NULL;
-    double *theta = NULL, *rounds = NULL, *mean = NULL, *sd = NULL, *ieuma = NULL, *tpm = NULL, *ir = NULL, *den = NULL; int32_t *iri = NULL;
-    double *gcols = NULL, *gsums = NULL;     /* --g2t: [3][n_tx] FPKM, iReadcount, TPM and their [3][n_genes] gene sums */
-    double *iso_u = NULL; int32_t *dom = NULL;   /* --isoforms: [n_tx] usage and [n_genes] dominant isoform of the .fpkm column */
-    int rc = parsed->rc, published = 0;
-    parsed->cnt = NULL;
-    snprintf(err, sizeof err, "%s", parsed->err);
-    w->parse_s[i] = parsed->secs;
-    /* compute_adjEUMA (emsar_main.c:403): L = EUMA . Wf on the device, bit-identical to the host loop */
+/* One sample on its way through the stages below.  run_sample() calls them in a fixed order and stops at the first that fails; a stage owns
+ * and frees its own buffers and reads what an earlier stage left only through the fields here, which run_sample() alone frees. */
+typedef struct {
+    worker_arg *w; emsar_hip_ctx *ctx; int i;      /* sample i of the job on this worker's context */
+    const config *cfg; const emsar_rsh *r; const emsar_genes *G;   /* G = the gene map, NULL without --g2t */
+    size_t T, NG;                                  /* transcripts, genes (0 without --g2t) */
+    emsar_counts *cnt; emsar_model *m;             /* the counted alignments, taken over from the parse job; stage_model's model */
+    emsar_em_params p;                             /* the solve's parameters, which every test, interval and replicate solve reuses */
+    double *theta, *rounds, *mean, *sd, *ieuma, *tpm, *ir, *den; int32_t *iri;   /* stage_solve: the columns of .fpkm ([T]; rounds [n_round][T]) and den */
+    double *gcols, *gsums;                         /* stage_genes: [3][T] FPKM, iReadcount, TPM and their [3][NG] gene sums */
+    double *iso_u; int32_t *dom;                   /* stage_isoforms: [T] usage and [NG] dominant isoform of the .fpkm column */
+    int published;                                 /* sample 0 of a two-sample job has handed its solver inputs on */
+    char path[4096];                               /* the file being written */
+} sample;
+
+/* <outdir>/<prefix>.<i>.<ext> */
+static const char *out_path(sample *s, const char *ext) {
+    snprintf(s->path, sizeof s->path, "%s/%s.%d.%s", s->cfg->outdir, s->cfg->prefix, s->i, ext);
+    return s->path;
+}
+/* the status of a writer that was given out_path(): reported if it failed */
+static int wrote(const sample *s, int rc) {
+    if (rc) fprintf(stderr, "can't write %s\n", s->path);
+    return rc;
+}
+/* the status of a library call: reported if it failed, as "alnfile[i]: <what>: <status> (<the context's last error>)" */
+static int lib_call(const sample *s, const char *what, int rc) {
+    if (rc) fprintf(stderr, "alnfile[%d]: %s%s%s (%s)\n", s->i, what, *what ? ": " : "", emsar_hip_strerror(rc), emsar_hip_last_error(s->ctx));
+    return rc;
+}
+/* n elements of `size` bytes for a stage to carve its arrays from; never a request of length 0, whose NULL would read as out of memory */
+static void *slab(size_t n, size_t size) { return malloc((n ? n : 1) * size); }
+
+/* Model preparation: compute_adjEUMA (emsar_main.c:403: L = EUMA . Wf on the device, bit-identical to the host loop) and the model.
+ * EUMAcut carries over in sample order (emsar_main.c:95,418: never reset), but it only ever changes when a set exceeds 5000 transcripts
+ * (emsar_main.c:417-423).  So every worker builds its model at once, without the lock, from the value it sees now; at its turn in the
+ * sample order it checks that the samples before it have left that value in place and publishes its own (possibly raised) one.  Only if
+ * an earlier sample did raise the cut in the meantime is the model rebuilt, at the turn, from the value that sample left.
+ * Invariant: *w->next_model advances exactly once per sample whatever has failed -- run_sample() calls this stage unconditionally and the
+ * hand-over below is not skipped by any rc -- or the workers behind this sample would wait for ever. */
+static int stage_model(sample *s, int rc, const char *parse_err) {
+    worker_arg *w = s->w; const emsar_rsh *r = s->r;
+    char err[512];
     double *Ldev = NULL;
+    snprintf(err, sizeof err, "%s", parse_err);
     if (rc == 0) {
-        double *wf = (double *)malloc(sizeof(double) * (size_t)r->nfl);
-        Ldev = (double *)malloc(sizeof(double) * (size_t)(r->n_rows > 0 ? r->n_rows : 1));
+        double *wf = (double *)slab((size_t)r->nfl, 8);
+        Ldev = (double *)slab((size_t)r->n_rows, 8);
         if (!wf || !Ldev) rc = EMSAR_HOST_ERR_OOM;
-        else if (emsar_model_wf(r, cnt, wf) == EMSAR_HOST_OK) {
-            int hrc = emsar_hip_adj_euma(ctx, wf, Ldev);
-            if (hrc) { snprintf(err, sizeof err, "adj_euma: %s (%s)", emsar_hip_strerror(hrc), emsar_hip_last_error(ctx)); rc = EMSAR_HOST_ERR_IO; }
+        else if (emsar_model_wf(r, s->cnt, wf) == EMSAR_HOST_OK) {
+            int hrc = emsar_hip_adj_euma(s->ctx, wf, Ldev);
+            if (hrc) { snprintf(err, sizeof err, "adj_euma: %s (%s)", emsar_hip_strerror(hrc), emsar_hip_last_error(s->ctx)); rc = EMSAR_HOST_ERR_IO; }
         } else { free(Ldev); Ldev = NULL; }            /* model_build reports the empty fragment-length window */
         free(wf);
     }
-    /* Model preparation.  EUMAcut carries over in sample order (emsar_main.c:95,418: never reset), but it only ever changes
-     * when a set exceeds 5000 transcripts (emsar_main.c:417-423).  So every worker builds its model at once, without the
-     * lock, from the value it sees now; at its turn in the sample order it checks that the samples before it have left
-     * that value in place and publishes its own (possibly raised) one.  Only if an earlier sample did raise the cut in
-     * the meantime is the model rebuilt, at the turn, from the value that sample left. */
-    double t_model = now_s();
+    double t_model = now_s();                          /* model_s: from here to the end of the hand-over */
     pthread_mutex_lock(w->mu);
     const double cut_seen = *w->eumacut;
     pthread_mutex_unlock(w->mu);
     double cut_mine = cut_seen;
-    if (rc == 0) rc = emsar_model_build_L(r, cnt, cfg->delta, &cut_mine, Ldev, &m, err, sizeof err);
+    if (rc == 0) rc = emsar_model_build_L(r, s->cnt, s->cfg->delta, &cut_mine, Ldev, &s->m, err, sizeof err);
     pthread_mutex_lock(w->mu);
-    while (*w->next_model != i) pthread_cond_wait(w->cv, w->mu);
+    while (*w->next_model != s->i) pthread_cond_wait(w->cv, w->mu);
     if (rc == 0 && *w->eumacut != cut_seen) {
-        emsar_model_free(m); m = NULL;
+        emsar_model_free(s->m); s->m = NULL;
         cut_mine = *w->eumacut;
-        rc = emsar_model_build_L(r, cnt, cfg->delta, &cut_mine, Ldev, &m, err, sizeof err);
+        rc = emsar_model_build_L(r, s->cnt, s->cfg->delta, &cut_mine, Ldev, &s->m, err, sizeof err);
     }
     if (rc == 0) *w->eumacut = cut_mine;
     (*w->next_model)++;
     pthread_cond_broadcast(w->cv);
     pthread_mutex_unlock(w->mu);
     free(Ldev);
-    w->model_s[i] = now_s() - t_model;
-    if (rc) { fprintf(stderr, "alnfile[%d]=%s: %s\n", i, cfg->aln[i], err); goto done; }
-    if (cfg->verbose > 0)
+    w->model_s[s->i] = now_s() - t_model;
+    if (rc) fprintf(stderr, "alnfile[%d]=%s: %s\n", s->i, s->cfg->aln[s->i], err);
+    else if (s->cfg->verbose > 0)
         fprintf(stdout, "alnfile[%d]=%s  reads=%lld (seen %lld, >k %lld, bad fraglen %lld, discrepant %lld, no segment %lld)  sets=%d  gpu=%d\n",
-                i, cfg->aln[i], (long long)cnt->total_reads, (long long)cnt->reads_seen, (long long)cnt->reads_over_k,
-                (long long)cnt->reads_bad_fraglen, (long long)cnt->reads_discrepant, (long long)cnt->reads_no_segment, m->n_sets, w->device);
+                s->i, s->cfg->aln[s->i], (long long)s->cnt->total_reads, (long long)s->cnt->reads_seen, (long long)s->cnt->reads_over_k,
+                (long long)s->cnt->reads_bad_fraglen, (long long)s->cnt->reads_discrepant, (long long)s->cnt->reads_no_segment, s->m->n_sets, w->device);
+    return rc;
+}
 
-    const size_t T = (size_t)r->n_tx;
-    theta = (double *)malloc(T * 8); mean = (double *)malloc(T * 8); sd = (double *)malloc(T * 8);
-    ieuma = (double *)malloc(T * 8); tpm = (double *)malloc(T * 8); ir = (double *)malloc(T * 8); iri = (int32_t *)malloc(T * 4);
-    rounds = (double *)malloc(T * 8 * (size_t)cfg->n_round);
-    if (!theta || !mean || !sd || !ieuma || !tpm || !ir || !iri || !rounds) { rc = EMSAR_HOST_ERR_OOM; goto done; }
-
-    /* ---- the replaced call: run_MLE_threads() + construct_FPKMfinal, emsar_main.c:444-450 ---- */
-    emsar_em_params p = {cfg->max_iter, cfg->accel, cfg->tol, 0.0, 0, cfg->set_mode, cfg->count_floor, cfg->zero_cut, cfg->abs_step};
-    /* den_t = sum_c m_ct E_c in row order on the host: the device's own scatter adds with atomics, whose order (and with it
-     * the last bits of den, of theta and now and then the sixth printed decimal) changes from run to run */
-    double t_host = now_s();
-    den = (double *)calloc(T, sizeof(double));
-    if (!den) { rc = EMSAR_HOST_ERR_OOM; goto done; }
-    /* ... and compute_iEUMA (emsar_functions.c:3218: iEUMA_t = sum of adjEUMA over the segments that hold t) in the same sweep, for the
-     * same reason: the eff.length and iReadcount columns are then the same bytes in every run */
-    memset(ieuma, 0, T * 8);
+/* den_t = sum_c m_ct E_c in row order on the host: the device's own scatter adds with atomics, whose order (and with it the last bits of
+ * den, of theta and now and then the sixth printed decimal) changes from run to run; and compute_iEUMA (emsar_functions.c:3218: iEUMA_t =
+ * sum of adjEUMA over the segments that hold t) in the same sweep, for the same reason: the eff.length and iReadcount columns are then
+ * the same bytes in every run.  Both arrays arrive zeroed. */
+static void row_sums(const emsar_rsh *r, const emsar_model *m, double *den, double *ieuma) {
     for (int64_t c = 0; c < r->n_rows; c++) {
         const double e = m->E_solver[c], l = m->L[c];
         if (e != 0.0) for (uint64_t k = r->row_ptr[c]; k < r->row_ptr[c + 1]; k++) den[r->col_idx[k]] += e;
         if (l != 0.0) for (uint64_t k = r->row_ptr[c]; k < r->row_ptr[c + 1]; k++) ieuma[r->col_idx[k]] += l;
     }
+}
+
+/* The replaced call -- run_MLE_threads() + construct_FPKMfinal, emsar_main.c:444-450 -- then compute_iEUMA + print_FPKMfinal
+ * (emsar_main.c:454-460): .fpkm, .fraglength_effect and, with -g, .segments.  host_s = model_s + the row sums + the three writers. */
+static int stage_solve(sample *s) {
+    worker_arg *w = s->w; const config *cfg = s->cfg; const emsar_rsh *r = s->r;
+    const size_t T = s->T;
+    const int i = s->i;
+    int rc;
+    s->theta = (double *)slab(T, 8); s->mean = (double *)slab(T, 8); s->sd = (double *)slab(T, 8); s->tpm = (double *)slab(T, 8);
+    s->ir = (double *)slab(T, 8); s->iri = (int32_t *)slab(T, 4); s->rounds = (double *)slab(T * (size_t)cfg->n_round, 8);
+    if (!s->theta || !s->mean || !s->sd || !s->tpm || !s->ir || !s->iri || !s->rounds) return EMSAR_HOST_ERR_OOM;
+    double t_host = now_s();
+    s->den = (double *)calloc(T ? T : 1, sizeof(double)); s->ieuma = (double *)calloc(T ? T : 1, sizeof(double));
+    if (!s->den || !s->ieuma) return EMSAR_HOST_ERR_OOM;
+    row_sums(r, s->m, s->den, s->ieuma);
     w->host_s[i] = w->model_s[i] + (now_s() - t_host);
-    if ((cfg->compare || cfg->compare_usage) && i == 0) { publish_ref(w, r, cnt->R, m->E_solver, den); published = 1; }
-    if ((rc = emsar_hip_upload_sample(ctx, cnt->R, m->E_solver, den)) ||
-        (rc = emsar_hip_solve(ctx, &p, theta, &w->stats[i]))) {
-        fprintf(stderr, "alnfile[%d]: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-        goto done;
-    }
-    for (int k = 0; k < cfg->n_round; k++) memcpy(rounds + (size_t)k * T, theta, T * 8);   /* deterministic solver: rounds coincide */
-    emsar_mean_sd(r->n_tx, cfg->n_round, rounds, mean, sd);
-    /* ---- compute_iEUMA + print_FPKMfinal, emsar_main.c:454-460 ---- */
-    if ((rc = emsar_hip_normalise(ctx, mean, ieuma, cnt->total_reads, tpm, ir, iri))) {
-        fprintf(stderr, "alnfile[%d]: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-        goto done;
-    }
+    /* Invariant: with --compare or --compare-usage sample 0 publishes its inputs exactly once -- the arrays here, or, if it ends before
+     * this line, the failure marker in run_sample() -- so that no other sample waits for them in vain. */
+    if ((cfg->compare || cfg->compare_usage) && i == 0) { publish_ref(w, r, s->cnt->R, s->m->E_solver, s->den); s->published = 1; }
+    if ((rc = lib_call(s, "", emsar_hip_upload_sample(s->ctx, s->cnt->R, s->m->E_solver, s->den))) ||
+        (rc = lib_call(s, "", emsar_hip_solve(s->ctx, &s->p, s->theta, &w->stats[i])))) return rc;
+    for (int k = 0; k < cfg->n_round; k++) memcpy(s->rounds + (size_t)k * T, s->theta, T * 8);   /* deterministic solver: rounds coincide */
+    emsar_mean_sd(r->n_tx, cfg->n_round, s->rounds, s->mean, s->sd);
+    if ((rc = lib_call(s, "", emsar_hip_normalise(s->ctx, s->mean, s->ieuma, s->cnt->total_reads, s->tpm, s->ir, s->iri)))) return rc;
     int64_t tot = 0;
     t_host = now_s();
-    snprintf(path, sizeof path, "%s/%s.%d.fpkm", cfg->outdir, cfg->prefix, i);
-    if ((rc = emsar_write_fpkm(path, r, mean, sd, ieuma, ir, iri, tpm, &tot))) { fprintf(stderr, "can't write %s\n", path); goto done; }
+    if ((rc = wrote(s, emsar_write_fpkm(out_path(s, "fpkm"), r, s->mean, s->sd, s->ieuma, s->ir, s->iri, s->tpm, &tot)))) return rc;
     if (cfg->verbose > 0) fprintf(stdout, "Total inferred readcount=%lld\n", (long long)tot);
-    snprintf(path, sizeof path, "%s/%s.%d.fraglength_effect", cfg->outdir, cfg->prefix, i);
-    if ((rc = emsar_write_fraglength(path, r, cnt, m))) { fprintf(stderr, "can't write %s\n", path); goto done; }
-    if (cfg->print_segments) {
-        snprintf(path, sizeof path, "%s/%s.%d.segments", cfg->outdir, cfg->prefix, i);
-        if ((rc = emsar_write_segments(path, r, cnt, m, mean))) { fprintf(stderr, "can't write %s\n", path); goto done; }
-    }
+    if ((rc = wrote(s, emsar_write_fraglength(out_path(s, "fraglength_effect"), r, s->cnt, s->m)))) return rc;
+    if (cfg->print_segments && (rc = wrote(s, emsar_write_segments(out_path(s, "segments"), r, s->cnt, s->m, s->mean)))) return rc;
     w->host_s[i] += now_s() - t_host;
-    /* ---- gene level (--g2t): FPKM2gFPKM.pl's sums of columns FPKM, iReadcount and TPM per gene, on the device ---- */
-    const emsar_genes *G = cfg->genes;
-    const size_t NG = G ? (size_t)G->n_genes : 0;
-    if (G) {
-        gcols = (double *)malloc(T * 8 * 3); gsums = (double *)malloc(NG * 8 * 3);
-        if (!gcols || !gsums) { rc = EMSAR_HOST_ERR_OOM; goto done; }
-        memcpy(gcols, mean, T * 8); memcpy(gcols + T, ir, T * 8); memcpy(gcols + 2 * T, tpm, T * 8);
-        if ((rc = emsar_hip_gene_sums(ctx, 3, gcols, gsums))) {
-            fprintf(stderr, "alnfile[%d]: gene sums: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-            goto done;
-        }
-        snprintf(path, sizeof path, "%s/%s.%d.gfpkm", cfg->outdir, cfg->prefix, i);
-        if ((rc = emsar_write_gfpkm(path, G, gsums, gsums + NG, gsums + 2 * NG))) { fprintf(stderr, "can't write %s\n", path); goto done; }
+    return 0;
+}
+
+/* Gene level (--g2t): FPKM2gFPKM.pl's sums of columns FPKM, iReadcount and TPM per gene, on the device: .gfpkm */
+static int stage_genes(sample *s) {
+    const size_t T = s->T, NG = s->NG;
+    int rc;
+    s->gcols = (double *)slab(3 * T, 8); s->gsums = (double *)slab(3 * NG, 8);
+    if (!s->gcols || !s->gsums) return EMSAR_HOST_ERR_OOM;
+    memcpy(s->gcols, s->mean, T * 8); memcpy(s->gcols + T, s->ir, T * 8); memcpy(s->gcols + 2 * T, s->tpm, T * 8);
+    if ((rc = lib_call(s, "gene sums", emsar_hip_gene_sums(s->ctx, 3, s->gcols, s->gsums)))) return rc;
+    return wrote(s, emsar_write_gfpkm(out_path(s, "gfpkm"), s->G, s->gsums, s->gsums + NG, s->gsums + 2 * NG));
+}
+
+/* Isoform usage (--isoforms): each transcript's share of its gene's FPKM and the gene's dominant isoform, on the device.  .isoforms is
+ * written here unless a bootstrap follows: stage_bootstrap writes it then, with the replicates' columns next to these. */
+static int stage_isoforms(sample *s) {
+    int rc;
+    s->iso_u = (double *)slab(s->T, 8); s->dom = (int32_t *)slab(s->NG, 4);
+    if (!s->iso_u || !s->dom) return EMSAR_HOST_ERR_OOM;
+    if ((rc = lib_call(s, "isoform usage", emsar_hip_isoform_usage(s->ctx, 1, s->mean, s->iso_u, s->dom))) || s->cfg->boot_n > 0) return rc;
+    return wrote(s, emsar_write_isoforms(out_path(s, "isoforms"), s->r, s->G, s->mean, s->iso_u, s->dom, 0, NULL, NULL, NULL, 0, NULL, NULL));
+}
+
+/* Model fit (--fit): the residuals of the printed FPKM against the sample's segments, per transcript and per gene, on the device: .fit, .gfit */
+static int stage_fit(sample *s) {
+    const size_t T = s->T, NG = s->NG;
+    double *fv = (double *)slab(4 * T, 8), *gv = s->G ? (double *)slab(4 * NG, 8) : NULL;
+    int32_t *fw = (int32_t *)slab(T, 4);
+    int rc = fv && fw && (gv || !s->G) ? 0 : EMSAR_HOST_ERR_OOM;
+    if (!rc) {
+        const emsar_fit_outputs o = {.tx_chi2 = fv, .tx_dev = fv + T, .tx_miss = fv + 2 * T, .tx_df = fv + 3 * T, .tx_worst_row = fw,
+                                     .gene_chi2 = gv, .gene_dev = gv ? gv + NG : NULL, .gene_miss = gv ? gv + 2 * NG : NULL, .gene_df = gv ? gv + 3 * NG : NULL};
+        if (!(rc = lib_call(s, "model fit", emsar_hip_model_fit(s->ctx, s->mean, s->m->E_solver, &o, NULL))) &&
+            !(rc = wrote(s, emsar_write_fit(out_path(s, "fit"), s->r, s->mean, s->den, o.tx_df, o.tx_chi2, o.tx_dev, o.tx_miss, o.tx_worst_row))) && s->G)
+            rc = wrote(s, emsar_write_gfit(out_path(s, "gfit"), s->r, s->G, s->mean, s->den, o.gene_df, o.gene_chi2, o.gene_dev, o.gene_miss));
     }
-    /* ---- isoform usage (--isoforms): each transcript's share of its gene's FPKM and the gene's dominant isoform, on the device ---- */
-    const int ISO = G && cfg->isoforms;
-    if (ISO) {
-        iso_u = (double *)malloc((T > 0 ? T : 1) * 8); dom = (int32_t *)malloc((NG > 0 ? NG : 1) * 4);
-        if (!iso_u || !dom) { rc = EMSAR_HOST_ERR_OOM; goto done; }
-        if ((rc = emsar_hip_isoform_usage(ctx, 1, mean, iso_u, dom))) {
-            fprintf(stderr, "alnfile[%d]: isoform usage: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-            goto done;
-        }
-        if (cfg->boot_n <= 0) {
-            snprintf(path, sizeof path, "%s/%s.%d.isoforms", cfg->outdir, cfg->prefix, i);
-            if ((rc = emsar_write_isoforms(path, r, G, mean, iso_u, dom, 0, NULL, NULL, NULL, 0, NULL, NULL))) { fprintf(stderr, "can't write %s\n", path); goto done; }
-        }
+    free(fv); free(gv); free(fw);
+    return rc;
+}
+
+/* Presence test (--presence): one likelihood-ratio test per transcript on its connected set, on the device: .presence */
+static int stage_presence(sample *s) {
+    const int32_t *query = s->cfg->pres_q;
+    const size_t Q = query ? (size_t)s->cfg->pres_nq : s->T;
+    double *v = (double *)slab(3 * Q, 8);
+    int32_t *iv = (int32_t *)slab(2 * Q, 4);
+    int rc = v && iv ? 0 : EMSAR_HOST_ERR_OOM;
+    if (!rc) {
+        const emsar_presence_outputs o = {.lambda = v, .pvalue = v + Q, .heir_share = v + 2 * Q, .heir = iv, .status = iv + Q};
+        if (!(rc = lib_call(s, "presence", emsar_hip_presence(s->ctx, &s->p, (int32_t)Q, query, &o, NULL))))
+            rc = wrote(s, emsar_write_presence(out_path(s, "presence"), s->r, (int32_t)Q, query, s->mean, o.lambda, o.pvalue, o.status, o.heir, o.heir_share));
     }
-    /* ---- model fit (--fit): the residuals of the printed FPKM against the sample's segments, per transcript and per gene, on the device ---- */
-    if (cfg->fit) {
-        const size_t Ta = T > 0 ? T : 1, Ga = NG > 0 ? NG : 1;
-        double *fv = (double *)malloc(Ta * 8 * 4), *gv = G ? (double *)malloc(Ga * 8 * 4) : NULL;
-        int32_t *fw = (int32_t *)malloc(Ta * 4);
-        const emsar_fit_outputs fo = {NULL, NULL, NULL, fv, fv ? fv + T : NULL, fv ? fv + 2 * T : NULL, fv ? fv + 3 * T : NULL, fw,
-                                      gv, gv ? gv + NG : NULL, gv ? gv + 2 * NG : NULL, gv ? gv + 3 * NG : NULL};
-        if (!fv || !fw || (G && !gv)) rc = EMSAR_HOST_ERR_OOM;
-        else if ((rc = emsar_hip_model_fit(ctx, mean, m->E_solver, &fo, NULL)))
-            fprintf(stderr, "alnfile[%d]: model fit: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-        else {
-            snprintf(path, sizeof path, "%s/%s.%d.fit", cfg->outdir, cfg->prefix, i);
-            if ((rc = emsar_write_fit(path, r, mean, den, fo.tx_df, fo.tx_chi2, fo.tx_dev, fo.tx_miss, fw))) fprintf(stderr, "can't write %s\n", path);
-            else if (G) {
-                snprintf(path, sizeof path, "%s/%s.%d.gfit", cfg->outdir, cfg->prefix, i);
-                if ((rc = emsar_write_gfit(path, r, G, mean, den, fo.gene_df, fo.gene_chi2, fo.gene_dev, fo.gene_miss))) fprintf(stderr, "can't write %s\n", path);
-            }
-        }
-        free(fv); free(gv); free(fw);
-        if (rc) goto done;
+    free(v); free(iv);
+    return rc;
+}
+
+/* --profile with --g2t: the same question per gene, and whether the gene is needed at all (emsar_hip_profile_genes; --profile-list names
+ * transcripts and does not filter it): .gprofile */
+static int profile_genes(sample *s, const emsar_profile_params *pp) {
+    const size_t NG = s->NG;
+    double *v = (double *)slab(4 * NG, 8);
+    int32_t *iv = (int32_t *)slab(2 * NG, 4);
+    int rc = v && iv ? 0 : EMSAR_HOST_ERR_OOM;
+    if (!rc) {
+        const emsar_profile_gene_outputs o = {.lower = v, .upper = v + NG, .lambda = v + 2 * NG, .pvalue = v + 3 * NG, .status = iv, .members = iv + NG};
+        if (!(rc = lib_call(s, "profile_genes", emsar_hip_profile_genes(s->ctx, &s->p, pp, (int32_t)NG, NULL, &o, NULL))))
+            rc = wrote(s, emsar_write_gprofile(out_path(s, "gprofile"), s->G, s->gsums, o.lower, o.upper, o.lambda, o.pvalue, o.members, o.status));
     }
-    /* ---- presence test (--presence): one likelihood-ratio test per transcript on its connected set, on the device ---- */
-    if (cfg->presence) {
-        const size_t Q = cfg->pres_q ? (size_t)cfg->pres_nq : T, Qa = Q > 0 ? Q : 1;
-        double *pv = (double *)malloc(Qa * 8 * 3);
-        int32_t *pi = (int32_t *)malloc(Qa * 4 * 2);
-        const emsar_presence_outputs po = {pv, pv ? pv + Q : NULL, pi, pv ? pv + 2 * Q : NULL, pi ? pi + Q : NULL, NULL};
-        if (!pv || !pi) rc = EMSAR_HOST_ERR_OOM;
-        else if ((rc = emsar_hip_presence(ctx, &p, (int32_t)Q, cfg->pres_q, &po, NULL)))
-            fprintf(stderr, "alnfile[%d]: presence: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-        else {
-            snprintf(path, sizeof path, "%s/%s.%d.presence", cfg->outdir, cfg->prefix, i);
-            if ((rc = emsar_write_presence(path, r, (int32_t)Q, cfg->pres_q, mean, po.lambda, po.pvalue, po.status, po.heir, po.heir_share)))
-                fprintf(stderr, "can't write %s\n", path);
-        }
-        free(pv); free(pi);
-        if (rc) goto done;
+    free(v); free(iv);
+    return rc;
+}
+
+/* Profile-likelihood intervals (--profile): two confidence limits per transcript on its connected set, on the device: .profile, then .gprofile */
+static int stage_profile(sample *s) {
+    const int32_t *query = s->cfg->prof_q;
+    const size_t Q = query ? (size_t)s->cfg->prof_nq : s->T;
+    const emsar_profile_params pp = {.level = s->cfg->profile_level, .max_evals = s->cfg->profile_evals};
+    double *v = (double *)slab(3 * Q, 8);
+    int32_t *iv = (int32_t *)slab(Q, 4);
+    int rc = v && iv ? 0 : EMSAR_HOST_ERR_OOM;
+    if (!rc) {
+        const emsar_profile_outputs o = {.lower = v, .upper = v + Q, .lambda = v + 2 * Q, .status = iv};
+        if (!(rc = lib_call(s, "profile", emsar_hip_profile(s->ctx, &s->p, &pp, (int32_t)Q, query, &o, NULL))))
+            rc = wrote(s, emsar_write_profile(out_path(s, "profile"), s->r, (int32_t)Q, query, s->mean, o.lower, o.upper, o.lambda, o.status));
     }
-    /* ---- profile-likelihood intervals (--profile): two confidence limits per transcript on its connected set, on the device ---- */
-    if (cfg->profile) {
-        const size_t Q = cfg->prof_q ? (size_t)cfg->prof_nq : T, Qa = Q > 0 ? Q : 1;
-        double *pv = (double *)malloc(Qa * 8 * 3);
-        int32_t *pi = (int32_t *)malloc(Qa * 4);
-        const emsar_profile_params pp = {cfg->profile_level, 0.0, cfg->profile_evals, 0};
-        const emsar_profile_outputs po = {pv, pv ? pv + Q : NULL, NULL, NULL, pv ? pv + 2 * Q : NULL, NULL, pi, NULL};
-        if (!pv || !pi) rc = EMSAR_HOST_ERR_OOM;
-        else if ((rc = emsar_hip_profile(ctx, &p, &pp, (int32_t)Q, cfg->prof_q, &po, NULL)))
-            fprintf(stderr, "alnfile[%d]: profile: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-        else {
-            snprintf(path, sizeof path, "%s/%s.%d.profile", cfg->outdir, cfg->prefix, i);
-            if ((rc = emsar_write_profile(path, r, (int32_t)Q, cfg->prof_q, mean, po.lower, po.upper, po.lambda, po.status)))
-                fprintf(stderr, "can't write %s\n", path);
-        }
-        free(pv); free(pi);
-        if (rc) goto done;
-        /* with --g2t the same question per gene, and whether the gene is needed at all (emsar_hip_profile_genes; --profile-list names
-         * transcripts and does not filter it): .gprofile */
-        if (G) {
-            const size_t Ga = NG > 0 ? NG : 1;
-            double *gv = (double *)malloc(Ga * 8 * 4);
-            int32_t *gi = (int32_t *)malloc(Ga * 4 * 2);
-            const emsar_profile_gene_outputs go = {gv, gv ? gv + NG : NULL, NULL, NULL, gv ? gv + 2 * NG : NULL, gv ? gv + 3 * NG : NULL, NULL,
-                                                   gi, NULL, NULL, gi ? gi + NG : NULL};
-            if (!gv || !gi) rc = EMSAR_HOST_ERR_OOM;
-            else if ((rc = emsar_hip_profile_genes(ctx, &p, &pp, (int32_t)NG, NULL, &go, NULL)))
-                fprintf(stderr, "alnfile[%d]: profile_genes: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-            else {
-                snprintf(path, sizeof path, "%s/%s.%d.gprofile", cfg->outdir, cfg->prefix, i);
-                if ((rc = write_gprofile(path, G, gsums, &go))) fprintf(stderr, "can't write %s\n", path);
-            }
-            free(gv); free(gi);
-            if (rc) goto done;
-        }
+    free(v); free(iv);
+    return !rc && s->G ? profile_genes(s, &pp) : rc;
+}
+
+/* Two-sample tests: sample 0 in a second context on this worker's device, made on the first sample that needs it and kept by the worker */
+static int reference_context(sample *s) {
+    worker_arg *w = s->w; const emsar_rsh *r = s->r;
+    compare_ref *ref = s->cfg->ref;
+    emsar_hip_ctx *c = NULL;
+    int rc;
+    pthread_mutex_lock(w->mu);
+    while (!ref->ready) pthread_cond_wait(w->cv, w->mu);
+    const int have_ref = ref->ready > 0;
+    pthread_mutex_unlock(w->mu);
+    if (!have_ref) { fprintf(stderr, "alnfile[%d]: compare: sample 0 gave no solver inputs\n", s->i); return EMSAR_HOST_ERR_IO; }
+    if (w->ref_ctx) return 0;
+    if ((rc = emsar_hip_create(&c, w->device)) || (rc = emsar_hip_set_deterministic(c, !s->cfg->no_deterministic)) ||
+        (rc = emsar_hip_upload_structure(c, r->n_rows, r->n_tx, r->row_ptr, r->col_idx, EMSAR_LAYOUT_AUTO)) ||
+        (rc = emsar_hip_upload_sample(c, ref->R, ref->E, ref->den))) {
+        fprintf(stderr, "alnfile[%d]: compare: sample 0's context: %s (%s)\n", s->i, emsar_hip_strerror(rc), c ? emsar_hip_last_error(c) : "");
+        emsar_hip_destroy(c);
+        return rc;
     }
-    /* ---- two-sample tests (--compare, --compare-usage): this sample (A) against sample 0 (B, in a second context on this device), on the device ---- */
-    if ((cfg->compare || cfg->compare_usage) && i > 0) {
-        compare_ref *ref = cfg->ref;
-        pthread_mutex_lock(w->mu);
-        while (!ref->ready) pthread_cond_wait(w->cv, w->mu);
-        const int have_ref = ref->ready > 0;
-        pthread_mutex_unlock(w->mu);
-        if (!have_ref) { fprintf(stderr, "alnfile[%d]: compare: sample 0 gave no solver inputs\n", i); rc = EMSAR_HOST_ERR_IO; goto done; }
-        if (!w->ref_ctx) {
-            emsar_hip_ctx *rc_ctx = NULL;
-            if ((rc = emsar_hip_create(&rc_ctx, w->device)) || (rc = emsar_hip_set_deterministic(rc_ctx, !cfg->no_deterministic)) ||
-                (rc = emsar_hip_upload_structure(rc_ctx, r->n_rows, r->n_tx, r->row_ptr, r->col_idx, EMSAR_LAYOUT_AUTO)) ||
-                (rc = emsar_hip_upload_sample(rc_ctx, ref->R, ref->E, ref->den))) {
-                fprintf(stderr, "alnfile[%d]: compare: sample 0's context: %s (%s)\n", i, emsar_hip_strerror(rc), rc_ctx ? emsar_hip_last_error(rc_ctx) : "");
-                emsar_hip_destroy(rc_ctx);
-                goto done;
-            }
-            w->ref_ctx = rc_ctx;
-        }
-        const size_t Q = cfg->cmp_q ? (size_t)cfg->cmp_nq : T, Qa = Q > 0 ? Q : 1;
-        /* the share of its gene (emsar_hip_compare_usage: this context's gene map serves both samples): .ucompare */
-        if (cfg->compare_usage) {
-            double *uv = (double *)malloc(Qa * 8 * 5);
-            int32_t *ui = (int32_t *)malloc(Qa * 4 * 3);
-            const emsar_usage_outputs uo = {uv, NULL, uv ? uv + Q : NULL, uv ? uv + 2 * Q : NULL, uv ? uv + 3 * Q : NULL, NULL, uv ? uv + 4 * Q : NULL, NULL,
-                                            ui, ui ? ui + Q : NULL, ui ? ui + 2 * Q : NULL, NULL};
-            if (!uv || !ui) rc = EMSAR_HOST_ERR_OOM;
-            else if ((rc = emsar_hip_compare_usage(ctx, w->ref_ctx, &p, NULL, (int32_t)Q, cfg->cmp_q, &uo, NULL)))
-                fprintf(stderr, "alnfile[%d]: compare_usage: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-            else {
-                snprintf(path, sizeof path, "%s/%s.%d.ucompare", cfg->outdir, cfg->prefix, i);
-                if ((rc = write_ucompare(path, r, G, (int32_t)Q, cfg->cmp_q, &uo))) fprintf(stderr, "can't write %s\n", path);
-            }
-            free(uv); free(ui);
-            if (rc) goto done;
-        }
-        if (cfg->compare) {
-            double *cv = (double *)malloc(Qa * 8 * 5);
-            int32_t *ci = (int32_t *)malloc(Qa * 4 * 2);
-            const emsar_compare_params cp = {cfg->compare_ratio, 0.0, 0, 0};
-            const emsar_compare_outputs co = {cv, cv ? cv + Q : NULL, cv ? cv + 2 * Q : NULL, cv ? cv + 3 * Q : NULL, cv ? cv + 4 * Q : NULL, NULL, NULL, NULL, NULL,
-                                              ci, ci ? ci + Q : NULL};
-            if (!cv || !ci) rc = EMSAR_HOST_ERR_OOM;
-            else if ((rc = emsar_hip_compare(ctx, w->ref_ctx, &p, &cp, (int32_t)Q, cfg->cmp_q, &co, NULL)))
-                fprintf(stderr, "alnfile[%d]: compare: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-            else {
-                snprintf(path, sizeof path, "%s/%s.%d.compare", cfg->outdir, cfg->prefix, i);
-                if ((rc = write_compare(path, r, (int32_t)Q, cfg->cmp_q, &co))) fprintf(stderr, "can't write %s\n", path);
-            }
-            free(cv); free(ci);
-            if (rc) goto done;
-            /* with --g2t the same question per gene (emsar_hip_compare_genes: this context's gene map serves both samples): .gcompare */
-            if (G) {
-                const size_t Ga = NG > 0 ? NG : 1;
-                double *gv = (double *)malloc(Ga * 8 * 5);
-                int32_t *gi = (int32_t *)malloc(Ga * 4 * 3);
-                const emsar_compare_gene_outputs go = {gv, gv ? gv + NG : NULL, gv ? gv + 2 * NG : NULL, gv ? gv + 3 * NG : NULL, gv ? gv + 4 * NG : NULL, NULL,
-                                                       NULL, NULL, NULL, gi, gi ? gi + NG : NULL, gi ? gi + 2 * NG : NULL};
-                if (!gv || !gi) rc = EMSAR_HOST_ERR_OOM;
-                else if ((rc = emsar_hip_compare_genes(ctx, w->ref_ctx, &p, &cp, (int32_t)NG, NULL, &go, NULL)))
-                    fprintf(stderr, "alnfile[%d]: compare_genes: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-                else {
-                    snprintf(path, sizeof path, "%s/%s.%d.gcompare", cfg->outdir, cfg->prefix, i);
-                    if ((rc = write_gcompare(path, G, &go))) fprintf(stderr, "can't write %s\n", path);
-                }
-                free(gv); free(gi);
-                if (rc) goto done;
-            }
-        }
+    w->ref_ctx = c;
+    return 0;
+}
+
+/* --compare-usage: the share of its gene (emsar_hip_compare_usage: this context's gene map serves both samples): .ucompare */
+static int compare_usage(sample *s, size_t Q, const int32_t *query) {
+    double *v = (double *)slab(5 * Q, 8);
+    int32_t *iv = (int32_t *)slab(3 * Q, 4);
+    int rc = v && iv ? 0 : EMSAR_HOST_ERR_OOM;
+    if (!rc) {
+        const emsar_usage_outputs o = {.lambda = v, .pvalue = v + Q, .usage_a = v + 2 * Q, .usage_b = v + 3 * Q, .dlogit = v + 4 * Q,
+                                       .status = iv, .outer_evals = iv + Q, .evals = iv + 2 * Q};
+        if (!(rc = lib_call(s, "compare_usage", emsar_hip_compare_usage(s->ctx, s->w->ref_ctx, &s->p, NULL, (int32_t)Q, query, &o, NULL))))
+            rc = wrote(s, emsar_write_ucompare(out_path(s, "ucompare"), s->r, s->G, (int32_t)Q, query, o.usage_a, o.usage_b, o.dlogit, o.lambda, o.pvalue,
+                                               o.status, o.outer_evals, o.evals));
     }
-    /* ---- asymptotic standard errors (--asymptotic): the inverse of the observed information at the printed FPKM, on the device ---- */
-    if (cfg->asymptotic) {
-        const size_t Ta = T > 0 ? T : 1, Ga = NG > 0 ? NG : 1;
-        double *av = (double *)malloc(Ta * 8 * 5), *gv = G ? (double *)malloc(Ga * 8) : NULL;
-        int32_t *ai = (int32_t *)malloc(Ta * 4 * 2), *gi = G ? (int32_t *)malloc(Ga * 4) : NULL;
-        const emsar_asym_params ap = {cfg->boundary_cut, 0.0, -1, 0};
-        const emsar_asym_outputs ao = {av, av ? av + T : NULL, av ? av + 2 * T : NULL, NULL, G && av ? av + 4 * T : NULL, ai, ai ? ai + T : NULL,
-                                       av ? av + 3 * T : NULL, NULL, gv, gi, NULL, NULL, NULL};
-        if (!av || !ai || (G && (!gv || !gi))) rc = EMSAR_HOST_ERR_OOM;
-        else if ((rc = emsar_hip_asymptotic(ctx, mean, &ap, &ao, NULL)))
-            fprintf(stderr, "alnfile[%d]: asymptotic: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-        else {
-            snprintf(path, sizeof path, "%s/%s.%d.asym", cfg->outdir, cfg->prefix, i);
-            if ((rc = emsar_write_asym(path, r, mean, tpm, ao.sd_fpkm, ao.sd_tpm, ao.var, ao.status, ao.partner, ao.partner_cov, ao.usage_sd)))
-                fprintf(stderr, "can't write %s\n", path);
-            else if (G) {
-                snprintf(path, sizeof path, "%s/%s.%d.gasym", cfg->outdir, cfg->prefix, i);
-                if ((rc = emsar_write_gasym(path, G, gsums, gv, gi))) fprintf(stderr, "can't write %s\n", path);
-            }
-        }
-        free(av); free(gv); free(ai); free(gi);
-        if (rc) goto done;
+    free(v); free(iv);
+    return rc;
+}
+
+/* --compare: the abundance (emsar_hip_compare): .compare */
+static int compare_transcripts(sample *s, const emsar_compare_params *cp, size_t Q, const int32_t *query) {
+    double *v = (double *)slab(5 * Q, 8);
+    int32_t *iv = (int32_t *)slab(2 * Q, 4);
+    int rc = v && iv ? 0 : EMSAR_HOST_ERR_OOM;
+    if (!rc) {
+        const emsar_compare_outputs o = {.lambda = v, .pvalue = v + Q, .log2fc = v + 2 * Q, .theta_a = v + 3 * Q, .theta_b = v + 4 * Q, .status = iv, .evals = iv + Q};
+        if (!(rc = lib_call(s, "compare", emsar_hip_compare(s->ctx, s->w->ref_ctx, &s->p, cp, (int32_t)Q, query, &o, NULL))))
+            rc = wrote(s, emsar_write_compare(out_path(s, "compare"), s->r, (int32_t)Q, query, o.theta_a, o.theta_b, o.log2fc, o.lambda, o.pvalue, o.status, o.evals));
     }
-    /* ---- Poisson bootstrap (--bootstrap B): its own file; .fpkm keeps the reference's column 3.  With --g2t the same replicates
-     *      give the genes' sd as well (bootstrap_genes: the transcript outputs are the same bits as bootstrap's), and with --isoforms
-     *      the usage statistics (bootstrap_isoforms: every other output is the same bits) ---- */
-    if (cfg->boot_n > 0) {
-        double *bm = (double *)malloc(T * 8), *bs = (double *)malloc(T * 8), *bt = (double *)malloc(T * 8);
-        double *gb = G ? (double *)malloc(NG * 8 * 3) : NULL;
-        /* --bootstrap-quantiles: [2][n_q][n_tx] FPKM then TPM quantiles, with --g2t also [2][n_q][n_genes] */
-        const size_t NQ = (size_t)cfg->bq_n;
-        double *bq = NQ ? (double *)malloc((T > 0 ? T : 1) * 8 * 2 * NQ) : NULL, *gq = NQ && G ? (double *)malloc((NG > 0 ? NG : 1) * 8 * 2 * NQ) : NULL;
-        /* --isoforms: [2][n_tx] mean and sd of the usage, [n_tx] dominance counts, [n_q][n_tx] usage quantiles */
-        double *ub = ISO ? (double *)malloc((T > 0 ? T : 1) * 8 * (2 + NQ)) : NULL;
-        int32_t *uc = ISO ? (int32_t *)malloc((T > 0 ? T : 1) * 4) : NULL;
-        const emsar_isoform_outputs iso = {ub, ub ? ub + T : NULL, uc, ub && NQ ? ub + 2 * T : NULL};
-        if (!bm || !bs || !bt || (G && !gb) || (NQ && !bq) || (NQ && G && !gq) || (ISO && (!ub || !uc))) rc = EMSAR_HOST_ERR_OOM;
-        else if ((rc = ISO ? emsar_hip_bootstrap_isoforms(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, cfg->bq_n, cfg->bq, bm, bs, bt, NULL, NULL,
-                                                          bq, NQ ? bq + NQ * T : NULL, gb, gb + NG, gb + 2 * NG, gq, NQ ? gq + NQ * NG : NULL,
-                                                          &w->bstats[i], &w->qstats[i], &iso)
-                         : NQ ? emsar_hip_bootstrap_quantiles(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, cfg->bq_n, cfg->bq, bm, bs, bt, NULL, NULL,
-                                                          bq, bq + NQ * T, gb, G ? gb + NG : NULL, G ? gb + 2 * NG : NULL, gq, G ? gq + NQ * NG : NULL,
-                                                          &w->bstats[i], &w->qstats[i])
-                         : G ? emsar_hip_bootstrap_genes(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, bm, bs, bt, NULL, gb, gb + NG, gb + 2 * NG,
-                                                     &w->bstats[i])
-                         : emsar_hip_bootstrap(ctx, &p, cfg->boot_seed + (uint64_t)i, 0, cfg->boot_n, bm, bs, bt, NULL, &w->bstats[i])))
-            fprintf(stderr, "alnfile[%d]: bootstrap: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-        else {
-            snprintf(path, sizeof path, "%s/%s.%d.bootstrap", cfg->outdir, cfg->prefix, i);
-            if ((rc = emsar_write_bootstrap(path, r, mean, bm, bs, tpm, bt))) fprintf(stderr, "can't write %s\n", path);
-            else if (G) {
-                snprintf(path, sizeof path, "%s/%s.%d.gbootstrap", cfg->outdir, cfg->prefix, i);
-                if ((rc = emsar_write_gbootstrap(path, G, gsums, gb, gb + NG, gsums + 2 * NG, gb + 2 * NG))) fprintf(stderr, "can't write %s\n", path);
-            }
-            if (!rc && NQ) {
-                snprintf(path, sizeof path, "%s/%s.%d.bootq", cfg->outdir, cfg->prefix, i);
-                if ((rc = emsar_write_bootq(path, r, cfg->bq_n, cfg->bq, bq, bq + NQ * T))) fprintf(stderr, "can't write %s\n", path);
-                else if (G) {
-                    snprintf(path, sizeof path, "%s/%s.%d.gbootq", cfg->outdir, cfg->prefix, i);
-                    if ((rc = emsar_write_gbootq(path, G, cfg->bq_n, cfg->bq, gq, gq + NQ * NG))) fprintf(stderr, "can't write %s\n", path);
-                }
-            }
-            if (!rc && ISO) {
-                snprintf(path, sizeof path, "%s/%s.%d.isoforms", cfg->outdir, cfg->prefix, i);
-                if ((rc = emsar_write_isoforms(path, r, G, mean, iso_u, dom, cfg->boot_n, iso.usage_mean, iso.usage_sd, iso.dominant_count, cfg->bq_n, cfg->bq,
-                                               iso.usage_q)))
-                    fprintf(stderr, "can't write %s\n", path);
-            }
-        }
-        free(bm); free(bs); free(bt); free(gb); free(bq); free(gq); free(ub); free(uc);
-        if (rc) goto done;
+    free(v); free(iv);
+    return rc;
+}
+
+/* --compare with --g2t: the same question per gene (emsar_hip_compare_genes: this context's gene map serves both samples; --compare-list
+ * names transcripts and does not filter it): .gcompare */
+static int compare_genes(sample *s, const emsar_compare_params *cp) {
+    const size_t NG = s->NG;
+    double *v = (double *)slab(5 * NG, 8);
+    int32_t *iv = (int32_t *)slab(3 * NG, 4);
+    int rc = v && iv ? 0 : EMSAR_HOST_ERR_OOM;
+    if (!rc) {
+        const emsar_compare_gene_outputs o = {.lambda = v, .pvalue = v + NG, .log2fc = v + 2 * NG, .gene_a = v + 3 * NG, .gene_b = v + 4 * NG,
+                                              .status = iv, .evals = iv + NG, .parts = iv + 2 * NG};
+        if (!(rc = lib_call(s, "compare_genes", emsar_hip_compare_genes(s->ctx, s->w->ref_ctx, &s->p, cp, (int32_t)NG, NULL, &o, NULL))))
+            rc = wrote(s, emsar_write_gcompare(out_path(s, "gcompare"), s->G, o.gene_a, o.gene_b, o.log2fc, o.lambda, o.pvalue, o.status, o.evals, o.parts));
     }
-    /* ---- depth subsampling (--subsample f1,f2,..): its own files ---- */
-    if (cfg->sub_nf > 0) {
-        const size_t K = (size_t)cfg->sub_nf;
-        const uint64_t seed = cfg->sub_seed + (uint64_t)i;
-        double *sv = (double *)malloc((T > 0 ? T : 1) * 8 * 4 * K), *gv = G ? (double *)malloc(NG * 8 * 3 * K) : NULL;
-        double depth[64];
-        if (!sv || (G && !gv)) rc = EMSAR_HOST_ERR_OOM;
-        else if ((rc = emsar_hip_subsample(ctx, &p, seed, cfg->sub_nf, cfg->sub_f, cfg->sub_reps, sv, sv + K * T, sv + 2 * K * T, sv + 3 * K * T, depth, NULL,
-                                           gv, gv ? gv + K * NG : NULL, gv ? gv + 2 * K * NG : NULL, &w->sstats[i])))
-            fprintf(stderr, "alnfile[%d]: subsample: %s (%s)\n", i, emsar_hip_strerror(rc), emsar_hip_last_error(ctx));
-        else {
-            snprintf(path, sizeof path, "%s/%s.%d.saturation", cfg->outdir, cfg->prefix, i);
-            if ((rc = emsar_write_saturation(path, r, mean, tpm, cfg->sub_nf, cfg->sub_f, cfg->sub_reps, seed, depth, sv, sv + K * T, sv + 2 * K * T,
-                                             sv + 3 * K * T)))
-                fprintf(stderr, "can't write %s\n", path);
-            else if (G) {
-                snprintf(path, sizeof path, "%s/%s.%d.gsaturation", cfg->outdir, cfg->prefix, i);
-                if ((rc = emsar_write_gsaturation(path, G, gsums, gsums + 2 * NG, cfg->sub_nf, cfg->sub_f, cfg->sub_reps, seed, depth, gv, gv + K * NG,
-                                                  gv + 2 * K * NG)))
-                    fprintf(stderr, "can't write %s\n", path);
-            }
-        }
-        free(sv); free(gv);
-        if (rc) goto done;
+    free(v); free(iv);
+    return rc;
+}
+
+/* Two-sample tests (--compare, --compare-usage; every sample but the first): this sample (A) against sample 0 (B), on the device */
+static int stage_two_sample(sample *s) {
+    const config *cfg = s->cfg;
+    const int32_t *query = cfg->cmp_q;
+    const size_t Q = query ? (size_t)cfg->cmp_nq : s->T;
+    const emsar_compare_params cp = {.ratio = cfg->compare_ratio};
+    int rc = reference_context(s);
+    if (!rc && cfg->compare_usage) rc = compare_usage(s, Q, query);
+    if (!rc && cfg->compare) rc = compare_transcripts(s, &cp, Q, query);
+    if (!rc && cfg->compare && s->G) rc = compare_genes(s, &cp);
+    return rc;
+}
+
+/* Asymptotic standard errors (--asymptotic): the inverse of the observed information at the printed FPKM, on the device: .asym, .gasym */
+static int stage_asymptotic(sample *s) {
+    const size_t T = s->T, NG = s->NG;
+    double *v = (double *)slab(5 * T, 8), *gv = s->G ? (double *)slab(NG, 8) : NULL;
+    int32_t *iv = (int32_t *)slab(2 * T, 4), *gi = s->G ? (int32_t *)slab(NG, 4) : NULL;
+    int rc = v && iv && (!s->G || (gv && gi)) ? 0 : EMSAR_HOST_ERR_OOM;
+    if (!rc) {
+        const emsar_asym_params ap = {.boundary_cut = s->cfg->boundary_cut, .block_tid = -1};
+        const emsar_asym_outputs o = {.var = v, .sd_fpkm = v + T, .sd_tpm = v + 2 * T, .partner_cov = v + 3 * T, .usage_sd = s->G ? v + 4 * T : NULL,
+                                      .status = iv, .partner = iv + T, .gene_sd = gv, .gene_status = gi};
+        if (!(rc = lib_call(s, "asymptotic", emsar_hip_asymptotic(s->ctx, s->mean, &ap, &o, NULL))) &&
+            !(rc = wrote(s, emsar_write_asym(out_path(s, "asym"), s->r, s->mean, s->tpm, o.sd_fpkm, o.sd_tpm, o.var, o.status, o.partner, o.partner_cov,
+                                             o.usage_sd))) && s->G)
+            rc = wrote(s, emsar_write_gasym(out_path(s, "gasym"), s->G, s->gsums, gv, gi));
     }
-    if (cfg->verbose > 0)
+    free(v); free(gv); free(iv); free(gi);
+    return rc;
+}
+
+/* what stage_bootstrap asked the library for: mean and sd of FPKM and sd of TPM [T]; with --g2t the same per gene [NG]; with
+ * --bootstrap-quantiles the quantiles of FPKM and of TPM [n_q][T] and per gene [n_q][NG]; with --isoforms the usage statistics */
+typedef struct { double *mean, *sd, *tpm_sd, *g_mean, *g_sd, *g_tpm_sd, *q_fpkm, *q_tpm, *gq_fpkm, *gq_tpm; emsar_isoform_outputs iso; } boot_arrays;
+
+/* .bootstrap, and what the options add to it: .gbootstrap, .bootq, .gbootq, .isoforms */
+static int write_bootstrap_files(sample *s, const boot_arrays *b, int iso) {
+    const config *cfg = s->cfg;
+    int rc = wrote(s, emsar_write_bootstrap(out_path(s, "bootstrap"), s->r, s->mean, b->mean, b->sd, s->tpm, b->tpm_sd));
+    if (!rc && s->G)
+        rc = wrote(s, emsar_write_gbootstrap(out_path(s, "gbootstrap"), s->G, s->gsums, b->g_mean, b->g_sd, s->gsums + 2 * s->NG, b->g_tpm_sd));
+    if (!rc && cfg->bq_n) rc = wrote(s, emsar_write_bootq(out_path(s, "bootq"), s->r, cfg->bq_n, cfg->bq, b->q_fpkm, b->q_tpm));
+    if (!rc && cfg->bq_n && s->G) rc = wrote(s, emsar_write_gbootq(out_path(s, "gbootq"), s->G, cfg->bq_n, cfg->bq, b->gq_fpkm, b->gq_tpm));
+    if (!rc && iso)
+        rc = wrote(s, emsar_write_isoforms(out_path(s, "isoforms"), s->r, s->G, s->mean, s->iso_u, s->dom, cfg->boot_n, b->iso.usage_mean, b->iso.usage_sd,
+                                           b->iso.dominant_count, cfg->bq_n, cfg->bq, b->iso.usage_q));
+    return rc;
+}
+
+/* Poisson bootstrap (--bootstrap B): its own file; .fpkm keeps the reference's column 3.  With --g2t the same replicates give the genes' sd
+ * as well (bootstrap_genes: the transcript outputs are the same bits as bootstrap's), with --bootstrap-quantiles the percentiles
+ * (bootstrap_quantiles) and with --isoforms the usage statistics (bootstrap_isoforms: every other output is the same bits) */
+static int stage_bootstrap(sample *s) {
+    const config *cfg = s->cfg; worker_arg *w = s->w;
+    const size_t T = s->T, NG = s->NG, NQ = (size_t)cfg->bq_n;
+    const int i = s->i, iso = s->G && cfg->isoforms;
+    const uint64_t seed = cfg->boot_seed + (uint64_t)i;
+    double *tv = (double *)slab(3 * T, 8), *gv = s->G ? (double *)slab(3 * NG, 8) : NULL;
+    double *tq = NQ ? (double *)slab(2 * NQ * T, 8) : NULL, *gq = NQ && s->G ? (double *)slab(2 * NQ * NG, 8) : NULL;
+    double *uv = iso ? (double *)slab((2 + NQ) * T, 8) : NULL;
+    int32_t *uc = iso ? (int32_t *)slab(T, 4) : NULL;
+    int rc = tv && (gv || !s->G) && (tq || !NQ) && (gq || !NQ || !s->G) && (!iso || (uv && uc)) ? 0 : EMSAR_HOST_ERR_OOM;
+    if (!rc) {
+        const boot_arrays b = {.mean = tv, .sd = tv + T, .tpm_sd = tv + 2 * T, .g_mean = gv, .g_sd = gv ? gv + NG : NULL, .g_tpm_sd = gv ? gv + 2 * NG : NULL,
+                               .q_fpkm = tq, .q_tpm = tq ? tq + NQ * T : NULL, .gq_fpkm = gq, .gq_tpm = gq ? gq + NQ * NG : NULL,
+                               .iso = {.usage_mean = uv, .usage_sd = uv ? uv + T : NULL, .dominant_count = uc, .usage_q = uv && NQ ? uv + 2 * T : NULL}};
+        rc = iso ? emsar_hip_bootstrap_isoforms(s->ctx, &s->p, seed, 0, cfg->boot_n, cfg->bq_n, cfg->bq, b.mean, b.sd, b.tpm_sd, NULL, NULL, b.q_fpkm, b.q_tpm,
+                                                b.g_mean, b.g_sd, b.g_tpm_sd, b.gq_fpkm, b.gq_tpm, &w->bstats[i], &w->qstats[i], &b.iso)
+           : NQ ? emsar_hip_bootstrap_quantiles(s->ctx, &s->p, seed, 0, cfg->boot_n, cfg->bq_n, cfg->bq, b.mean, b.sd, b.tpm_sd, NULL, NULL, b.q_fpkm, b.q_tpm,
+                                                b.g_mean, b.g_sd, b.g_tpm_sd, b.gq_fpkm, b.gq_tpm, &w->bstats[i], &w->qstats[i])
+           : s->G ? emsar_hip_bootstrap_genes(s->ctx, &s->p, seed, 0, cfg->boot_n, b.mean, b.sd, b.tpm_sd, NULL, b.g_mean, b.g_sd, b.g_tpm_sd, &w->bstats[i])
+           : emsar_hip_bootstrap(s->ctx, &s->p, seed, 0, cfg->boot_n, b.mean, b.sd, b.tpm_sd, NULL, &w->bstats[i]);
+        if (!(rc = lib_call(s, "bootstrap", rc))) rc = write_bootstrap_files(s, &b, iso);
+    }
+    free(tv); free(gv); free(tq); free(gq); free(uv); free(uc);
+    return rc;
+}
+
+/* Depth subsampling (--subsample f1,f2,..): its own files, .saturation and .gsaturation */
+static int stage_subsample(sample *s) {
+    const config *cfg = s->cfg;
+    const size_t T = s->T, NG = s->NG, K = (size_t)cfg->sub_nf;
+    const uint64_t seed = cfg->sub_seed + (uint64_t)s->i;
+    double *v = (double *)slab(4 * K * T, 8), *gv = s->G ? (double *)slab(3 * K * NG, 8) : NULL;
+    double depth[64];
+    int rc = v && (gv || !s->G) ? 0 : EMSAR_HOST_ERR_OOM;
+    if (!rc) {
+        double *fpkm_mean = v, *fpkm_sd = v + K * T, *tpm_mean = v + 2 * K * T, *tpm_sd = v + 3 * K * T;
+        double *g_mean = gv, *g_sd = gv ? gv + K * NG : NULL, *g_tpm = gv ? gv + 2 * K * NG : NULL;
+        if (!(rc = lib_call(s, "subsample", emsar_hip_subsample(s->ctx, &s->p, seed, cfg->sub_nf, cfg->sub_f, cfg->sub_reps, fpkm_mean, fpkm_sd, tpm_mean, tpm_sd,
+                                                                depth, NULL, g_mean, g_sd, g_tpm, &s->w->sstats[s->i]))) &&
+            !(rc = wrote(s, emsar_write_saturation(out_path(s, "saturation"), s->r, s->mean, s->tpm, cfg->sub_nf, cfg->sub_f, cfg->sub_reps, seed, depth,
+                                                   fpkm_mean, fpkm_sd, tpm_mean, tpm_sd))) && s->G)
+            rc = wrote(s, emsar_write_gsaturation(out_path(s, "gsaturation"), s->G, s->gsums, s->gsums + 2 * NG, cfg->sub_nf, cfg->sub_f, cfg->sub_reps, seed,
+                                                  depth, g_mean, g_sd, g_tpm));
+    }
+    free(v); free(gv);
+    return rc;
+}
+
+/* One sample: the stages in the order of the files' dependencies.  Invariant: the first stage that fails ends the sample -- every later
+ * call is behind !rc -- and the files written before it stay.  The sample's arrays are freed here and nowhere else. */
+static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parsed) {
+    const config *cfg = w->cfg;
+    sample s = {.w = w, .ctx = ctx, .i = i, .cfg = cfg, .r = w->rsh, .G = cfg->genes, .T = (size_t)w->rsh->n_tx,
+                .NG = cfg->genes ? (size_t)cfg->genes->n_genes : 0, .cnt = parsed->cnt,
+                .p = {.max_iter = cfg->max_iter, .accel = cfg->accel, .tol = cfg->tol, .set_mode = cfg->set_mode, .count_floor = cfg->count_floor,
+                      .zero_cut = cfg->zero_cut, .abs_step = cfg->abs_step}};
+    parsed->cnt = NULL;
+    w->parse_s[i] = parsed->secs;
+    int rc = stage_model(&s, parsed->rc, parsed->err);
+    if (!rc) rc = stage_solve(&s);
+    if (!rc && s.G) rc = stage_genes(&s);
+    if (!rc && s.G && cfg->isoforms) rc = stage_isoforms(&s);
+    if (!rc && cfg->fit) rc = stage_fit(&s);
+    if (!rc && cfg->presence) rc = stage_presence(&s);
+    if (!rc && cfg->profile) rc = stage_profile(&s);
+    if (!rc && (cfg->compare || cfg->compare_usage) && i > 0) rc = stage_two_sample(&s);
+    if (!rc && cfg->asymptotic) rc = stage_asymptotic(&s);
+    if (!rc && cfg->boot_n > 0) rc = stage_bootstrap(&s);
+    if (!rc && cfg->sub_nf > 0) rc = stage_subsample(&s);
+    if (!rc && cfg->verbose > 0)
         fprintf(stdout, "Complete: %s/%s.%d.fpkm  (EM passes %d, converged %d, solve %.1f ms, logL %.6f)\n", cfg->outdir, cfg->prefix, i,
                 w->stats[i].iters, w->stats[i].converged, w->stats[i].solve_ms, w->stats[i].loglik);
-done:
-    if ((cfg->compare || cfg->compare_usage) && i == 0 && !published) publish_ref(w, r, NULL, NULL, NULL);     /* the other samples must not wait for it */
-    free(theta); free(rounds); free(mean); free(sd); free(ieuma); free(tpm); free(ir); free(iri); free(den); free(gcols); free(gsums); free(iso_u); free(dom);
-    emsar_counts_free(cnt); emsar_model_free(m);
+    if ((cfg->compare || cfg->compare_usage) && i == 0 && !s.published) publish_ref(w, s.r, NULL, NULL, NULL);     /* the other samples must not wait for it */
+    free(s.theta); free(s.rounds); free(s.mean); free(s.sd); free(s.ieuma); free(s.tpm); free(s.ir); free(s.iri); free(s.den);
+    free(s.gcols); free(s.gsums); free(s.iso_u); free(s.dom);
+    emsar_counts_free(s.cnt); emsar_model_free(s.m);
     return rc;
 }
 
@@ -781,20 +745,11 @@ static int read_name_list(const char *what, const char *file, const emsar_rsh *r
     return 0;
 }
 
-int main(int argc, char **argv) {
-    config cfg; memset(&cfg, 0, sizeof cfg);
-    cfg.ao.max_repeat = 100; cfg.n_round = 4; cfg.verbose = 1; cfg.accel = 1; cfg.tol = 1e-10; cfg.max_iter = 200000;
-    cfg.zero_cut = 2.5e-7;      /* a quarter of the "%lf" print quantum of the .fpkm file */
-    cfg.abs_step = 1e-13;       /* see emsar_em_params.abs_step */
-    cfg.boot_seed = 1;
-    cfg.sub_reps = 10; cfg.sub_seed = 1;
-    const char *strand = "ns"; int multisample = 0, gpus = 0, device = 0;
-    int dev_map[64], n_dev_map = 0;
-    const char *presence_list = NULL, *profile_list = NULL, *compare_list = NULL;
-    int compare_ratio_given = 0;
-    compare_ref ref; memset(&ref, 0, sizeof ref);
-    int profile_level_given = 0;
-    int boundary_cut_given = 0;
+static int bad(const char *msg) { fprintf(stderr, "%s\n", msg); return 1; }
+static int bad_usage(const char *msg, const char *a0) { bad(msg); usage(a0); return 1; }
+
+/* The option switch: 0, or 1 after the message of the first argument that is wrong (the usage text for an unknown option). */
+static int parse_options(int argc, char **argv, config *cfg) {
     static struct option lo[] = {
         {"rsh", required_argument, 0, 'I'}, {"PE", no_argument, 0, 'P'}, {"strand_type", required_argument, 0, 's'},
         {"maxthread", required_argument, 0, 'p'}, {"max_repeat", required_argument, 0, 'k'}, {"nround", required_argument, 0, 'n'},
@@ -802,7 +757,9 @@ int main(int argc, char **argv) {
         {"print_segments", no_argument, 0, 'g'}, {"multisample", no_argument, 0, 'M'}, {"SAM", no_argument, 0, 'S'}, {"BAM", no_argument, 0, 'B'},
         {"verbose", no_argument, 0, 'v'}, {"no_verbose", no_argument, 0, 'q'}, {"gpus", required_argument, 0, 1000},
         {"device", required_argument, 0, 1001}, {"plain", no_argument, 0, 1002}, {"stats-json", required_argument, 0, 1003},
-        {"count-floor", required_argument, 0, 1004}, {"streaming-only", no_argument, 0, 1005}, {"rsh-cache", optional_argument, 0, 1006}, {"zero-cut", required_argument, 0, 1007}, {"abs-step", required_argument, 0, 1008}, {"devices", required_argument, 0, 1009}, {"device-collapse", no_argument, 0, 1010}, {"no-deterministic", no_argument, 0, 1011},
+        {"count-floor", required_argument, 0, 1004}, {"streaming-only", no_argument, 0, 1005}, {"rsh-cache", optional_argument, 0, 1006},
+        {"zero-cut", required_argument, 0, 1007}, {"abs-step", required_argument, 0, 1008}, {"devices", required_argument, 0, 1009},
+        {"device-collapse", no_argument, 0, 1010}, {"no-deterministic", no_argument, 0, 1011},
         {"bootstrap", required_argument, 0, 1012}, {"bootstrap-seed", required_argument, 0, 1013}, {"g2t", required_argument, 0, 1014},
         {"subsample", required_argument, 0, 1015}, {"subsample-reps", required_argument, 0, 1016}, {"subsample-seed", required_argument, 0, 1017},
         {"bootstrap-quantiles", required_argument, 0, 1018}, {"isoforms", no_argument, 0, 1019}, {"fit", no_argument, 0, 1020},
@@ -810,268 +767,274 @@ int main(int argc, char **argv) {
         {"asymptotic", no_argument, 0, 1023}, {"boundary-cut", required_argument, 0, 1024},
         {"profile", no_argument, 0, 1025}, {"profile-level", required_argument, 0, 1026}, {"profile-list", required_argument, 0, 1027},
         {"profile-evals", required_argument, 0, 1028},
-        {"compare", no_argument, 0, 1029}, {"compare-ratio", required_argument, 0, 1030}, {"compare-list", required_argument, 0, 1031}, {"compare-usage", no_argument, 0, 1040},
+        {"compare", no_argument, 0, 1029}, {"compare-ratio", required_argument, 0, 1030}, {"compare-list", required_argument, 0, 1031},
+        {"compare-usage", no_argument, 0, 1040},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
         switch (c) {
-            case 'I': cfg.rsh_path = optarg; break;
-            case 'P': cfg.ao.pe = 1; break;
-            case 's': strand = optarg; break;
+            case 'I': cfg->rsh_path = optarg; break;
+            case 'P': cfg->ao.pe = 1; break;
+            case 's': cfg->strand = optarg; break;
             case 'p': break;                       /* CPU threads of the reference's solver: no meaning here */
             case 'F': case 'f': break;             /* overwritten by the rsh header in the reference too */
-            case 'k': cfg.ao.max_repeat = atoi(optarg); break;
-            case 'n': cfg.n_round = atoi(optarg); if (cfg.n_round <= 0) { fprintf(stderr, "option -n must be a natural number.\n"); return 1; } break;
-            case 'e': cfg.tol = atof(optarg); if (cfg.tol <= 0) { fprintf(stderr, "option -e must be positive.\n"); return 1; } break;
-            case 'i': cfg.max_iter = atoi(optarg); if (cfg.max_iter <= 0) { fprintf(stderr, "option -i must be positive.\n"); return 1; } break;
-            case 'd': cfg.delta = atoi(optarg); break;
-            case 'g': cfg.print_segments = 1; break;
-            case 'M': multisample = 1; break;
-            case 'S': cfg.ao.format = 1; break;
-            case 'B': cfg.ao.format = 2; break;
-            case 'v': cfg.verbose = 2; break;
-            case 'q': cfg.verbose = 0; break;
-            case 1000: gpus = atoi(optarg); break;
-            case 1001: device = atoi(optarg); break;
-            case 1002: cfg.accel = 0; break;
-            case 1003: cfg.stats_json = optarg; break;
-            case 1004: cfg.count_floor = atof(optarg); if (cfg.count_floor < 0) { fprintf(stderr, "--count-floor must be >= 0.\n"); return 1; } break;
-            case 1005: cfg.set_mode = 1; break;
-            case 1006: cfg.rsh_cache = optarg ? optarg : ""; break;
-            case 1007: cfg.zero_cut = atof(optarg); break;
-            case 1008: cfg.abs_step = atof(optarg); break;
-            case 1010: cfg.device_collapse = 1; break;
-            case 1011: cfg.no_deterministic = 1; break;
-            case 1012: {
-                char *end; errno = 0;
-                long v = strtol(optarg, &end, 10);
-                if (end == optarg || *end || errno || v < 0 || v > 1000000) { fprintf(stderr, "--bootstrap wants a number of replicates (0 .. 1000000).\n"); return 1; }
-                cfg.boot_n = (int)v;
+            case 'k': cfg->ao.max_repeat = atoi(optarg); break;
+            case 'n': if ((cfg->n_round = atoi(optarg)) <= 0) return bad("option -n must be a natural number."); break;
+            case 'e': if ((cfg->tol = atof(optarg)) <= 0) return bad("option -e must be positive."); break;
+            case 'i': if ((cfg->max_iter = atoi(optarg)) <= 0) return bad("option -i must be positive."); break;
+            case 'd': cfg->delta = atoi(optarg); break;
+            case 'g': cfg->print_segments = 1; break;
+            case 'M': cfg->multisample = 1; break;
+            case 'S': cfg->ao.format = 1; break;
+            case 'B': cfg->ao.format = 2; break;
+            case 'v': cfg->verbose = 2; break;
+            case 'q': cfg->verbose = 0; break;
+            case 1000: cfg->gpus = atoi(optarg); break;
+            case 1001: cfg->device = atoi(optarg); break;
+            case 1002: cfg->accel = 0; break;
+            case 1003: cfg->stats_json = optarg; break;
+            case 1004: if ((cfg->count_floor = atof(optarg)) < 0) return bad("--count-floor must be >= 0."); break;
+            case 1005: cfg->set_mode = 1; break;
+            case 1006: cfg->rsh_cache = optarg ? optarg : ""; break;
+            case 1007: cfg->zero_cut = atof(optarg); break;
+            case 1008: cfg->abs_step = atof(optarg); break;
+            case 1009: if (parse_device_list(optarg, cfg->dev_map, &cfg->n_dev_map)) return bad("--devices wants a comma-separated list of device ids."); break;
+            case 1010: cfg->device_collapse = 1; break;
+            case 1011: cfg->no_deterministic = 1; break;
+            case 1012: if (parse_count(optarg, 0, 1000000, &cfg->boot_n)) return bad("--bootstrap wants a number of replicates (0 .. 1000000)."); break;
+            case 1013: if (parse_seed(optarg, &cfg->boot_seed)) return bad("--bootstrap-seed wants a non-negative integer."); break;
+            case 1014: cfg->g2t = optarg; break;
+            case 1015:
+                if (parse_fraction_list(optarg, 0.0, 1, cfg->sub_f, &cfg->sub_nf)) return bad("--subsample wants a comma-separated list of 1 to 64 fractions in (0, 1].");
                 break;
-            }
-            case 1013: {
-                char *end; errno = 0;
-                unsigned long long v = strtoull(optarg, &end, 10);
-                if (end == optarg || *end || errno || optarg[0] == '-') { fprintf(stderr, "--bootstrap-seed wants a non-negative integer.\n"); return 1; }
-                cfg.boot_seed = (uint64_t)v;
+            case 1016: if (parse_count(optarg, 1, 1000000, &cfg->sub_reps)) return bad("--subsample-reps wants a number of replicates (1 .. 1000000)."); break;
+            case 1017: if (parse_seed(optarg, &cfg->sub_seed)) return bad("--subsample-seed wants a non-negative integer."); break;
+            case 1018:
+                if (parse_fraction_list(optarg, 0.0, 0, cfg->bq, &cfg->bq_n))
+                    return bad("--bootstrap-quantiles wants a comma-separated list of 1 to 64 probabilities in [0, 1].");
                 break;
-            }
-            case 1014: cfg.g2t = optarg; break;
-            case 1015: {
-                const char *q = optarg;
-                cfg.sub_nf = 0;
-                for (;;) {
-                    char *end; errno = 0;
-                    const double v = strtod(q, &end);
-                    if (end == q || (*end && *end != ',') || errno || !isfinite(v) || !(v > 0.0 && v <= 1.0) || cfg.sub_nf >= 64) {
-                        fprintf(stderr, "--subsample wants a comma-separated list of 1 to 64 fractions in (0, 1].\n"); return 1;
-                    }
-                    cfg.sub_f[cfg.sub_nf++] = v;
-                    if (!*end) break;
-                    q = end + 1;
-                }
-                break;
-            }
-            case 1016: {
-                char *end; errno = 0;
-                long v = strtol(optarg, &end, 10);
-                if (end == optarg || *end || errno || v < 1 || v > 1000000) { fprintf(stderr, "--subsample-reps wants a number of replicates (1 .. 1000000).\n"); return 1; }
-                cfg.sub_reps = (int)v;
-                break;
-            }
-            case 1017: {
-                char *end; errno = 0;
-                unsigned long long v = strtoull(optarg, &end, 10);
-                if (end == optarg || *end || errno || optarg[0] == '-') { fprintf(stderr, "--subsample-seed wants a non-negative integer.\n"); return 1; }
-                cfg.sub_seed = (uint64_t)v;
-                break;
-            }
-            case 1018: {
-                const char *q = optarg;
-                cfg.bq_n = 0;
-                for (;;) {
-                    char *end; errno = 0;
-                    const double v = strtod(q, &end);
-                    if (end == q || (*end && *end != ',') || errno || !isfinite(v) || !(v >= 0.0 && v <= 1.0) || cfg.bq_n >= 64) {
-                        fprintf(stderr, "--bootstrap-quantiles wants a comma-separated list of 1 to 64 probabilities in [0, 1].\n"); return 1;
-                    }
-                    cfg.bq[cfg.bq_n++] = v;
-                    if (!*end) break;
-                    q = end + 1;
-                }
-                break;
-            }
-            case 1019: cfg.isoforms = 1; break;
-            case 1020: cfg.fit = 1; break;
-            case 1021: cfg.presence = 1; break;
-            case 1022: presence_list = optarg; break;
-            case 1023: cfg.asymptotic = 1; break;
-            case 1024: cfg.boundary_cut = atof(optarg); boundary_cut_given = 1; break;
-            case 1025: cfg.profile = 1; break;
-            case 1026: cfg.profile_level = atof(optarg); profile_level_given = 1; break;
-            case 1027: profile_list = optarg; break;
-            case 1028: cfg.profile_evals = atoi(optarg); if (cfg.profile_evals <= 0) { fprintf(stderr, "--profile-evals must be positive.\n"); return 1; } break;
-            case 1029: cfg.compare = 1; break;
-            case 1040: cfg.compare_usage = 1; break;
-            case 1030: cfg.compare_ratio = atof(optarg); compare_ratio_given = 1; break;
-            case 1031: compare_list = optarg; break;
-            case 1009: {
-                const char *q = optarg;
-                while (*q && n_dev_map < 64) {
-                    char *end; long d = strtol(q, &end, 10);
-                    if (end == q || d < 0 || d > 1023) { fprintf(stderr, "--devices wants a comma-separated list of device ids.\n"); return 1; }
-                    dev_map[n_dev_map++] = (int)d;
-                    q = *end == ',' ? end + 1 : end;
-                    if (*end && *end != ',') { fprintf(stderr, "--devices wants a comma-separated list of device ids.\n"); return 1; }
-                }
-                if (!n_dev_map) { fprintf(stderr, "--devices wants a comma-separated list of device ids.\n"); return 1; }
-                break;
-            }
+            case 1019: cfg->isoforms = 1; break;
+            case 1020: cfg->fit = 1; break;
+            case 1021: cfg->presence = 1; break;
+            case 1022: cfg->presence_list = optarg; break;
+            case 1023: cfg->asymptotic = 1; break;
+            case 1024: cfg->boundary_cut = atof(optarg); cfg->boundary_cut_given = 1; break;
+            case 1025: cfg->profile = 1; break;
+            case 1026: cfg->profile_level = atof(optarg); cfg->profile_level_given = 1; break;
+            case 1027: cfg->profile_list = optarg; break;
+            case 1028: if ((cfg->profile_evals = atoi(optarg)) <= 0) return bad("--profile-evals must be positive."); break;
+            case 1029: cfg->compare = 1; break;
+            case 1040: cfg->compare_usage = 1; break;
+            case 1030: cfg->compare_ratio = atof(optarg); cfg->compare_ratio_given = 1; break;
+            case 1031: cfg->compare_list = optarg; break;
             default: usage(argv[0]); return 1;
         }
     }
-    if (cfg.bq_n > 0 && (cfg.boot_n < 1 || cfg.boot_n > 4096)) {
-        fprintf(stderr, "--bootstrap-quantiles needs --bootstrap B with 1 <= B <= 4096 replicates.\n"); return 1;
-    }
-    if (cfg.isoforms && !cfg.g2t) { fprintf(stderr, "--isoforms needs --g2t FILE.\n"); return 1; }
-    if (boundary_cut_given && !cfg.asymptotic) { fprintf(stderr, "--boundary-cut needs --asymptotic.\n"); return 1; }
-    if (boundary_cut_given && !(cfg.boundary_cut >= 0.0)) { fprintf(stderr, "--boundary-cut must be >= 0.\n"); return 1; }
-    if (!boundary_cut_given) cfg.boundary_cut = EMSAR_ASYM_DEFAULT_CUT;
-    if (presence_list && !cfg.presence) { fprintf(stderr, "--presence-list needs --presence.\n"); return 1; }
-    if ((profile_list || profile_level_given || cfg.profile_evals) && !cfg.profile) {
-        fprintf(stderr, "--profile-list, --profile-level and --profile-evals need --profile.\n"); return 1;
-    }
-    if (profile_level_given && !(cfg.profile_level > 0.0 && cfg.profile_level < 1.0)) { fprintf(stderr, "--profile-level must lie in (0, 1).\n"); return 1; }
-    if (!profile_level_given) cfg.profile_level = 0.95;
-    if (compare_ratio_given && !cfg.compare) { fprintf(stderr, "--compare-ratio needs --compare.\n"); return 1; }
-    if (compare_list && !cfg.compare && !cfg.compare_usage) { fprintf(stderr, "--compare-list needs --compare or --compare-usage.\n"); return 1; }
-    if (cfg.compare_usage && !cfg.g2t) { fprintf(stderr, "--compare-usage needs --g2t FILE.\n"); usage(argv[0]); return 1; }
-    if (compare_ratio_given && !(cfg.compare_ratio > 0.0 && isfinite(cfg.compare_ratio))) { fprintf(stderr, "--compare-ratio must be positive.\n"); return 1; }
-    if (!compare_ratio_given) cfg.compare_ratio = 1.0;
-    if (cfg.compare && !multisample) { fprintf(stderr, "--compare needs -M and at least two samples.\n"); usage(argv[0]); return 1; }
-    if (cfg.compare_usage && !multisample) { fprintf(stderr, "--compare-usage needs -M and at least two samples.\n"); usage(argv[0]); return 1; }
-    cfg.ref = &ref;
-    if (!cfg.rsh_path || optind + 2 >= argc) { usage(argv[0]); return 1; }
-    if (emsar_set_strand(strand, cfg.ao.pe, &cfg.ao.strand)) { fprintf(stderr, "error: invalid strand type.\n"); return 1; }
-    cfg.outdir = argv[optind]; cfg.prefix = argv[optind + 1];
-    const char *last = argv[optind + 2];
-    char **list = NULL; int n_list = 0;
-    if (!multisample) { list = (char **)malloc(sizeof(char *)); list[0] = strdup(last); n_list = 1; }
-    else {
-        FILE *f = fopen(last, "r");
-        if (!f) { fprintf(stderr, "Can't open alignment list file.\n"); return 1; }
-        char line[4096];
-        while (fgets(line, sizeof line, f)) {
-            size_t n = strlen(line);
-            while (n && (line[n - 1] == '\n' || line[n - 1] == '\r')) line[--n] = 0;
-            if (!n) continue;
-            list = (char **)realloc(list, sizeof(char *) * (size_t)(n_list + 1));
-            list[n_list++] = strdup(line);
-        }
-        fclose(f);
-        if (!n_list) { fprintf(stderr, "No alignment files in the alignment list\n"); return 1; }
-    }
-    if (cfg.compare && n_list < 2) { fprintf(stderr, "--compare needs -M and at least two samples.\n"); usage(argv[0]); return 1; }
-    if (cfg.compare_usage && n_list < 2) { fprintf(stderr, "--compare-usage needs -M and at least two samples.\n"); usage(argv[0]); return 1; }
-    cfg.aln = list; cfg.n_aln = n_list;
-    /* the reference runs `mkdir -p outdir` (emsar_main.c:284-285); find out now, not after the solve, that it cannot be written */
-    {
-        char tmp[4096];
-        size_t n = strlen(cfg.outdir);
-        if (n == 0 || n >= sizeof tmp) { fprintf(stderr, "can't create output directory %s\n", cfg.outdir); return 1; }
-        memcpy(tmp, cfg.outdir, n + 1);
-        for (size_t k = 1; k <= n; k++)
-            if (tmp[k] == '/' || tmp[k] == 0) {
-                const char keep = tmp[k];
-                tmp[k] = 0;
-                if (mkdir(tmp, 0777) != 0 && errno != EEXIST) { fprintf(stderr, "can't create output directory %s\n", tmp); return 1; }
-                tmp[k] = keep;
-            }
-        if (access(cfg.outdir, W_OK | X_OK) != 0) { fprintf(stderr, "can't write to output directory %s\n", cfg.outdir); return 1; }
-    }
+    return 0;
+}
 
+/* What the options ask of one another, and the defaults that depend on whether an option was given.  The order of the checks is the order of
+ * their messages: an argument list that trips two of them hears of the first. */
+static int check_options(config *cfg, const char *a0) {
+    if (cfg->bq_n > 0 && (cfg->boot_n < 1 || cfg->boot_n > 4096)) return bad("--bootstrap-quantiles needs --bootstrap B with 1 <= B <= 4096 replicates.");
+    if (cfg->isoforms && !cfg->g2t) return bad("--isoforms needs --g2t FILE.");
+    if (cfg->boundary_cut_given && !cfg->asymptotic) return bad("--boundary-cut needs --asymptotic.");
+    if (cfg->boundary_cut_given && !(cfg->boundary_cut >= 0.0)) return bad("--boundary-cut must be >= 0.");
+    if (!cfg->boundary_cut_given) cfg->boundary_cut = EMSAR_ASYM_DEFAULT_CUT;
+    if (cfg->presence_list && !cfg->presence) return bad("--presence-list needs --presence.");
+    if ((cfg->profile_list || cfg->profile_level_given || cfg->profile_evals) && !cfg->profile)
+        return bad("--profile-list, --profile-level and --profile-evals need --profile.");
+    if (cfg->profile_level_given && !(cfg->profile_level > 0.0 && cfg->profile_level < 1.0)) return bad("--profile-level must lie in (0, 1).");
+    if (!cfg->profile_level_given) cfg->profile_level = 0.95;
+    if (cfg->compare_ratio_given && !cfg->compare) return bad("--compare-ratio needs --compare.");
+    if (cfg->compare_list && !cfg->compare && !cfg->compare_usage) return bad("--compare-list needs --compare or --compare-usage.");
+    if (cfg->compare_usage && !cfg->g2t) return bad_usage("--compare-usage needs --g2t FILE.", a0);
+    if (cfg->compare_ratio_given && !(cfg->compare_ratio > 0.0 && isfinite(cfg->compare_ratio))) return bad("--compare-ratio must be positive.");
+    if (!cfg->compare_ratio_given) cfg->compare_ratio = 1.0;
+    if (cfg->compare && !cfg->multisample) return bad_usage("--compare needs -M and at least two samples.", a0);
+    if (cfg->compare_usage && !cfg->multisample) return bad_usage("--compare-usage needs -M and at least two samples.", a0);
+    return 0;
+}
+
+/* cfg->aln: the alignment file itself, or with -M the files its last argument lists, one per line */
+static int read_sample_list(config *cfg, const char *last) {
+    if (!cfg->multisample) {
+        cfg->aln = (char **)malloc(sizeof(char *)); cfg->aln[0] = strdup(last); cfg->n_aln = 1;
+        return 0;
+    }
+    FILE *f = fopen(last, "r");
+    if (!f) return bad("Can't open alignment list file.");
+    char line[4096];
+    while (fgets(line, sizeof line, f)) {
+        size_t n = strlen(line);
+        while (n && (line[n - 1] == '\n' || line[n - 1] == '\r')) line[--n] = 0;
+        if (!n) continue;
+        cfg->aln = (char **)realloc(cfg->aln, sizeof(char *) * (size_t)(cfg->n_aln + 1));
+        cfg->aln[cfg->n_aln++] = strdup(line);
+    }
+    fclose(f);
+    if (!cfg->n_aln) { fprintf(stderr, "No alignment files in the alignment list\n"); return 1; }
+    return 0;
+}
+
+/* the reference runs `mkdir -p outdir` (emsar_main.c:284-285); find out now, not after the solve, that it cannot be written */
+static int make_outdir(const char *outdir) {
+    char tmp[4096];
+    size_t n = strlen(outdir);
+    if (n == 0 || n >= sizeof tmp) { fprintf(stderr, "can't create output directory %s\n", outdir); return 1; }
+    memcpy(tmp, outdir, n + 1);
+    for (size_t k = 1; k <= n; k++)
+        if (tmp[k] == '/' || tmp[k] == 0) {
+            const char keep = tmp[k];
+            tmp[k] = 0;
+            if (mkdir(tmp, 0777) != 0 && errno != EEXIST) { fprintf(stderr, "can't create output directory %s\n", tmp); return 1; }
+            tmp[k] = keep;
+        }
+    if (access(outdir, W_OK | X_OK) != 0) { fprintf(stderr, "can't write to output directory %s\n", outdir); return 1; }
+    return 0;
+}
+
+/* the index: from its binary cache (--rsh-cache: <rsh>.bin next to the text unless a path was given) or from the text, which then writes the cache */
+static emsar_rsh *read_index(const config *cfg) {
     char err[512];
     emsar_rsh *rsh = NULL;
     double t0 = now_s();
     int rc = -1, from_cache = 0;
     char *cache_path = NULL;
-    if (cfg.rsh_cache) {                       /* <rsh>.bin next to the text unless a path was given */
-        size_t n = strlen(cfg.rsh_cache[0] ? cfg.rsh_cache : cfg.rsh_path) + 8;
+    if (cfg->rsh_cache) {
+        size_t n = strlen(cfg->rsh_cache[0] ? cfg->rsh_cache : cfg->rsh_path) + 8;
         cache_path = (char *)malloc(n);
-        if (!cache_path) { fprintf(stderr, "out of memory\n"); return 1; }
-        if (cfg.rsh_cache[0]) snprintf(cache_path, n, "%s", cfg.rsh_cache); else snprintf(cache_path, n, "%s.bin", cfg.rsh_path);
-        rc = emsar_rsh_read_cache(cfg.rsh_path, cache_path, &rsh, err, sizeof err);
+        if (!cache_path) { fprintf(stderr, "out of memory\n"); return NULL; }
+        if (cfg->rsh_cache[0]) snprintf(cache_path, n, "%s", cfg->rsh_cache); else snprintf(cache_path, n, "%s.bin", cfg->rsh_path);
+        rc = emsar_rsh_read_cache(cfg->rsh_path, cache_path, &rsh, err, sizeof err);
         if (rc == 0) from_cache = 1;
-        else if (cfg.verbose > 1) fprintf(stdout, "rsh cache not used (%s)\n", err);
+        else if (cfg->verbose > 1) fprintf(stdout, "rsh cache not used (%s)\n", err);
     }
-    if (rc) rc = emsar_rsh_read(cfg.rsh_path, &rsh, err, sizeof err);
-    if (rc) { fprintf(stderr, "%s\n", err); return 1; }
-    if (cache_path && !from_cache && emsar_rsh_write_cache(rsh, cfg.rsh_path, cache_path) != 0)
+    if (rc) rc = emsar_rsh_read(cfg->rsh_path, &rsh, err, sizeof err);
+    if (rc) { fprintf(stderr, "%s\n", err); return NULL; }
+    if (cache_path && !from_cache && emsar_rsh_write_cache(rsh, cfg->rsh_path, cache_path) != 0)
         fprintf(stderr, "warning: can't write the rsh cache %s\n", cache_path);
-    if (cfg.verbose > 0 && from_cache) fprintf(stdout, "rsh: binary cache %s\n", cache_path);
+    if (cfg->verbose > 0 && from_cache) fprintf(stdout, "rsh: binary cache %s\n", cache_path);
     free(cache_path);
-    if (cfg.verbose > 0) fprintf(stdout, "rsh: %d transcripts, %lld segments, fragment lengths %d-%d (%.2fs)\n", rsh->n_tx,
-                                 (long long)rsh->n_rows, rsh->frag_min, rsh->frag_max, now_s() - t0);
+    if (cfg->verbose > 0) fprintf(stdout, "rsh: %d transcripts, %lld segments, fragment lengths %d-%d (%.2fs)\n", rsh->n_tx,
+                                  (long long)rsh->n_rows, rsh->frag_min, rsh->frag_max, now_s() - t0);
+    return rsh;
+}
+
+/* -M: one worker per GPU, or per entry of --devices (cfg->dev_map holds their devices afterwards); 0 after a message if that cannot be had.
+ * A probe context tells how many devices exist without touching HIP here. */
+static int count_workers(config *cfg) {
+    int avail = 0, n_workers;
+    for (int d = 0; d < 64; d++) { emsar_hip_ctx *probe = NULL; if (emsar_hip_create(&probe, d) != 0) break; emsar_hip_destroy(probe); avail++; }
+    if (avail == 0) { fprintf(stderr, "%s\n", emsar_hip_strerror(EMSAR_HIP_ERR_NO_DEVICE)); return 0; }
+    if (cfg->n_dev_map) {
+        for (int g = 0; g < cfg->n_dev_map; g++)
+            if (cfg->dev_map[g] >= avail) { fprintf(stderr, "--devices: device %d does not exist (%d found)\n", cfg->dev_map[g], avail); return 0; }
+        n_workers = cfg->n_dev_map;
+    } else {
+        n_workers = cfg->gpus > 0 && cfg->gpus < avail ? cfg->gpus : avail;
+        for (int g = 0; g < n_workers && g < 64; g++) cfg->dev_map[g] = g;
+        if (n_workers > 64) n_workers = 64;
+    }
+    return n_workers > cfg->n_aln ? cfg->n_aln : n_workers;
+}
+
+/* --stats-json FILE: the job and, per sample, its status, its host times and the statistics of the library calls it made (w: any worker --
+ * the per-sample arrays are shared) */
+static void write_stats_json(const config *cfg, const worker_arg *w, int n_workers, double wall, int n_bad) {
+    FILE *f = fopen(cfg->stats_json, "w");
+    if (!f) return;
+    fprintf(f, "{\"samples\": %d, \"gpus\": %d, \"wall_s\": %.6f, \"failed\": %d, \"per_sample\": [", cfg->n_aln, n_workers, wall, n_bad);
+    for (int i = 0; i < cfg->n_aln; i++) {
+        const emsar_em_stats *e = &w->stats[i];
+        fprintf(f, "%s{\"status\": %d, \"parse_s\": %.6f, \"model_s\": %.6f, \"host_s\": %.6f, \"em_passes\": %d, \"converged\": %d, \"solve_ms\": %.4f, \"kernel_ms\": %.4f, \"loglik\": %.9g, \"bytes_per_pass\": %lld, "
+                   "\"sets_resident\": %d, \"sets_streamed\": %d, \"set_passes_max\": %d, \"set_passes_sum\": %lld, \"sets_build_ms\": %.4f, \"sets_kernel_ms\": %.4f",
+                i ? ", " : "", w->status[i], w->parse_s[i], w->model_s[i], w->host_s[i], e->iters, e->converged, e->solve_ms, e->kernel_ms, e->loglik,
+                (long long)e->bytes_per_pass, e->sets_resident, e->sets_streamed, e->set_passes_max, (long long)e->set_passes_sum, e->sets_build_ms,
+                e->sets_kernel_ms);
+        if (cfg->boot_n > 0) {
+            const emsar_boot_stats *b = &w->bstats[i];
+            fprintf(f, ", \"boot_replicates\": %d, \"boot_batch\": %d, \"boot_replicates_unconverged\": %d, \"boot_set_passes_max\": %d, "
+                       "\"boot_draws\": %lld, \"boot_draw_ms\": %.4f, \"boot_sets_ms\": %.4f, \"boot_stream_ms\": %.4f, \"boot_reduce_ms\": %.4f, \"boot_total_ms\": %.4f",
+                    b->n_replicates, b->batch, b->replicates_unconverged, b->set_passes_max, (long long)b->draws, b->draw_ms, b->sets_ms,
+                    b->stream_ms, b->reduce_ms, b->total_ms);
+        }
+        if (cfg->boot_n > 0 && cfg->bq_n > 0)
+            fprintf(f, ", \"bootq_quantiles\": %d, \"bootq_held_bytes\": %lld, \"bootq_ms\": %.4f", w->qstats[i].n_quantiles,
+                    (long long)w->qstats[i].held_bytes, w->qstats[i].quantile_ms);
+        if (cfg->sub_nf > 0) {
+            const emsar_subsample_stats *b = &w->sstats[i];
+            fprintf(f, ", \"sub_fractions\": %d, \"sub_replicates\": %d, \"sub_batch\": %d, \"sub_replicates_unconverged\": %d, "
+                       "\"sub_draws\": %lld, \"sub_draw_ms\": %.4f, \"sub_sets_ms\": %.4f, \"sub_stream_ms\": %.4f, \"sub_reduce_ms\": %.4f, \"sub_total_ms\": %.4f",
+                    b->n_fractions, b->n_replicates, b->batch, b->replicates_unconverged, (long long)b->draws, b->draw_ms, b->sets_ms,
+                    b->stream_ms, b->reduce_ms, b->total_ms);
+        }
+        fprintf(f, "}");
+    }
+    fprintf(f, "]}\n");
+    fclose(f);
+}
+
+int main(int argc, char **argv) {
+    config cfg = {.ao = {.max_repeat = 100}, .n_round = 4, .verbose = 1, .accel = 1, .tol = 1e-10, .max_iter = 200000,
+                  .zero_cut = 2.5e-7,      /* a quarter of the "%lf" print quantum of the .fpkm file */
+                  .abs_step = 1e-13,       /* see emsar_em_params.abs_step */
+                  .boot_seed = 1, .sub_reps = 10, .sub_seed = 1, .strand = "ns"};
+    compare_ref ref = {0};
+    if (parse_options(argc, argv, &cfg) || check_options(&cfg, argv[0])) return 1;
+    cfg.ref = &ref;
+    if (!cfg.rsh_path || optind + 2 >= argc) { usage(argv[0]); return 1; }
+    if (emsar_set_strand(cfg.strand, cfg.ao.pe, &cfg.ao.strand)) return bad("error: invalid strand type.");
+    cfg.outdir = argv[optind]; cfg.prefix = argv[optind + 1];
+    if (read_sample_list(&cfg, argv[optind + 2])) return 1;
+    if (cfg.compare && cfg.n_aln < 2) return bad_usage("--compare needs -M and at least two samples.", argv[0]);
+    if (cfg.compare_usage && cfg.n_aln < 2) return bad_usage("--compare-usage needs -M and at least two samples.", argv[0]);
+    if (make_outdir(cfg.outdir)) return 1;
+    emsar_rsh *rsh = read_index(&cfg);
+    if (!rsh) return 1;
     /* before any sample: an unknown name ends the run here */
-    if (presence_list && read_name_list("presence", presence_list, rsh, &cfg.pres_q, &cfg.pres_nq)) { emsar_rsh_free(rsh); return 1; }
-    if (profile_list && read_name_list("profile", profile_list, rsh, &cfg.prof_q, &cfg.prof_nq)) { emsar_rsh_free(rsh); return 1; }
-    if (compare_list && read_name_list("compare", compare_list, rsh, &cfg.cmp_q, &cfg.cmp_nq)) { emsar_rsh_free(rsh); return 1; }
+    if ((cfg.presence_list && read_name_list("presence", cfg.presence_list, rsh, &cfg.pres_q, &cfg.pres_nq)) ||
+        (cfg.profile_list && read_name_list("profile", cfg.profile_list, rsh, &cfg.prof_q, &cfg.prof_nq)) ||
+        (cfg.compare_list && read_name_list("compare", cfg.compare_list, rsh, &cfg.cmp_q, &cfg.cmp_nq))) { emsar_rsh_free(rsh); return 1; }
     emsar_genes *genes = NULL;
     if (cfg.g2t) {                             /* before any sample: a bad gene map ends the run here */
+        char err[512];
         if (emsar_genes_read(rsh, cfg.g2t, &genes, err, sizeof err)) { fprintf(stderr, "%s\n", err); emsar_rsh_free(rsh); return 1; }
         cfg.genes = genes;
         if (cfg.verbose > 1)
             fprintf(stdout, "g2t: %d genes; %lld g2t lines name a transcript not in the index (ignored); %d index transcripts in no gene%s\n",
                     genes->n_genes, (long long)genes->n_unknown, genes->n_unmapped, genes->n_unmapped ? " (empty geneID)" : "");
     }
-
-    int n_workers = 1;
-    if (multisample) {
-        /* one worker per GPU; a probe context tells us how many devices exist without touching HIP here */
-        int avail = 0;
-        for (int d = 0; d < 64; d++) { emsar_hip_ctx *probe = NULL; if (emsar_hip_create(&probe, d) != 0) break; emsar_hip_destroy(probe); avail++; }
-        if (avail == 0) { fprintf(stderr, "%s\n", emsar_hip_strerror(EMSAR_HIP_ERR_NO_DEVICE)); return 1; }
-        if (n_dev_map) {
-            for (int g = 0; g < n_dev_map; g++)
-                if (dev_map[g] >= avail) { fprintf(stderr, "--devices: device %d does not exist (%d found)\n", dev_map[g], avail); return 1; }
-            n_workers = n_dev_map;
-        } else {
-            n_workers = gpus > 0 && gpus < avail ? gpus : avail;
-            for (int g = 0; g < n_workers && g < 64; g++) dev_map[g] = g;
-            if (n_workers > 64) n_workers = 64;
-        }
-        if (n_workers > n_list) n_workers = n_list;
-    }
+    int n_workers = cfg.multisample ? count_workers(&cfg) : 1;
+    if (n_workers < 1) return 1;
+    const size_t n = (size_t)cfg.n_aln;
     pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER; pthread_cond_t cv = PTHREAD_COND_INITIALIZER;
-    int next_model = 0; double eumacut = 0.0;
-    int *status = (int *)calloc((size_t)n_list, sizeof(int));
-    emsar_em_stats *stats = (emsar_em_stats *)calloc((size_t)n_list, sizeof(emsar_em_stats));
-    emsar_boot_stats *bstats = (emsar_boot_stats *)calloc((size_t)n_list, sizeof(emsar_boot_stats));
-    emsar_subsample_stats *sstats = (emsar_subsample_stats *)calloc((size_t)n_list, sizeof(emsar_subsample_stats));
-    emsar_quantile_stats *qstats = (emsar_quantile_stats *)calloc((size_t)n_list, sizeof(emsar_quantile_stats));
-    double *parse_s = (double *)calloc((size_t)n_list, sizeof(double));
-    double *model_s = (double *)calloc((size_t)n_list, sizeof(double)), *host_s = (double *)calloc((size_t)n_list, sizeof(double));
+    int next_model = 0, go = 0, n_started = 1; double eumacut = 0.0;
+    /* what every worker shares: the hand-over's state and the per-sample results */
+    const worker_arg shared = {.cfg = &cfg, .rsh = rsh, .n_workers = n_workers, .mu = &mu, .cv = &cv, .next_model = &next_model, .eumacut = &eumacut, .go = &go,
+                               .status = (int *)calloc(n, sizeof(int)), .stats = (emsar_em_stats *)calloc(n, sizeof(emsar_em_stats)),
+                               .bstats = (emsar_boot_stats *)calloc(n, sizeof(emsar_boot_stats)),
+                               .sstats = (emsar_subsample_stats *)calloc(n, sizeof(emsar_subsample_stats)),
+                               .qstats = (emsar_quantile_stats *)calloc(n, sizeof(emsar_quantile_stats)), .parse_s = (double *)calloc(n, sizeof(double)),
+                               .model_s = (double *)calloc(n, sizeof(double)), .host_s = (double *)calloc(n, sizeof(double)), .ao = cfg.ao,
+                               .cdev = {.ctx = NULL, .mu = PTHREAD_MUTEX_INITIALIZER}};
     worker_arg *wa = (worker_arg *)calloc((size_t)n_workers, sizeof(worker_arg));
     pthread_t *th = (pthread_t *)calloc((size_t)n_workers, sizeof(pthread_t));
-    if (!status || !stats || !bstats || !sstats || !qstats || !parse_s || !model_s || !host_s || !wa || !th) { fprintf(stderr, "out of memory\n"); return 1; }
-    t0 = now_s();
+    if (!shared.status || !shared.stats || !shared.bstats || !shared.sstats || !shared.qstats || !shared.parse_s || !shared.model_s || !shared.host_s || !wa || !th)
+        return bad("out of memory");
+    double t0 = now_s();
     /* Workers wait at a gate until their number is final: a thread that cannot be started must not leave the others
      * waiting for samples nobody will take (the EUMAcut hand-over is in sample order). */
-    int go = 0, n_started = 1;
-    for (int g = 0; g < n_workers; g++)
-        wa[g] = (worker_arg){&cfg, rsh, multisample ? dev_map[g] : device, n_workers, g, &mu, &cv, &next_model, &eumacut, status, stats, bstats, sstats, qstats, parse_s,
-                             model_s, host_s, &go, cfg.ao, {NULL, PTHREAD_MUTEX_INITIALIZER}, NULL};
+    for (int g = 0; g < n_workers; g++) { wa[g] = shared; wa[g].worker = g; wa[g].device = cfg.multisample ? cfg.dev_map[g] : cfg.device; }
     for (int g = 1; g < n_workers; g++) {
         if (pthread_create(&th[g], NULL, worker_main, &wa[g]) != 0) { fprintf(stderr, "warning: worker %d could not be started, using %d\n", g, g); break; }
         n_started++;
     }
     /* every parallel host step of a worker gets its share of the cores: G workers x 16 reader threads each would
      * oversubscribe the host (parse and inflate pools, emsar_host_threads) */
-    {
-        long nc = sysconf(_SC_NPROCESSORS_ONLN);
-        int share = (int)((nc < 1 ? 1 : nc) / n_started);
-        emsar_host_set_thread_budget(share < 1 ? 1 : share > 16 ? 16 : share);
-    }
+    const long nc = sysconf(_SC_NPROCESSORS_ONLN);
+    const int share = (int)((nc < 1 ? 1 : nc) / n_started);
+    emsar_host_set_thread_budget(share < 1 ? 1 : share > 16 ? 16 : share);
     pthread_mutex_lock(&mu);
     n_workers = n_started;
     for (int g = 0; g < n_workers; g++) wa[g].n_workers = n_workers;
@@ -1080,46 +1043,15 @@ int main(int argc, char **argv) {
     pthread_mutex_unlock(&mu);
     worker_main(&wa[0]);
     for (int g = 1; g < n_workers; g++) pthread_join(th[g], NULL);
-    double wall = now_s() - t0;
-    int bad = 0;
-    for (int i = 0; i < n_list; i++) if (status[i]) bad++;
-    if (cfg.stats_json) {
-        FILE *f = fopen(cfg.stats_json, "w");
-        if (f) {
-            fprintf(f, "{\"samples\": %d, \"gpus\": %d, \"wall_s\": %.6f, \"failed\": %d, \"per_sample\": [", n_list, n_workers, wall, bad);
-            for (int i = 0; i < n_list; i++) {
-                fprintf(f, "%s{\"status\": %d, \"parse_s\": %.6f, \"model_s\": %.6f, \"host_s\": %.6f, \"em_passes\": %d, \"converged\": %d, \"solve_ms\": %.4f, \"kernel_ms\": %.4f, \"loglik\": %.9g, \"bytes_per_pass\": %lld, "
-                           "\"sets_resident\": %d, \"sets_streamed\": %d, \"set_passes_max\": %d, \"set_passes_sum\": %lld, \"sets_build_ms\": %.4f, \"sets_kernel_ms\": %.4f",
-                        i ? ", " : "", status[i], parse_s[i], model_s[i], host_s[i], stats[i].iters, stats[i].converged, stats[i].solve_ms, stats[i].kernel_ms, stats[i].loglik,
-                        (long long)stats[i].bytes_per_pass, stats[i].sets_resident, stats[i].sets_streamed, stats[i].set_passes_max,
-                        (long long)stats[i].set_passes_sum, stats[i].sets_build_ms, stats[i].sets_kernel_ms);
-                if (cfg.boot_n > 0) {
-                    const emsar_boot_stats *b = &bstats[i];
-                    fprintf(f, ", \"boot_replicates\": %d, \"boot_batch\": %d, \"boot_replicates_unconverged\": %d, \"boot_set_passes_max\": %d, "
-                               "\"boot_draws\": %lld, \"boot_draw_ms\": %.4f, \"boot_sets_ms\": %.4f, \"boot_stream_ms\": %.4f, \"boot_reduce_ms\": %.4f, \"boot_total_ms\": %.4f",
-                            b->n_replicates, b->batch, b->replicates_unconverged, b->set_passes_max, (long long)b->draws, b->draw_ms, b->sets_ms,
-                            b->stream_ms, b->reduce_ms, b->total_ms);
-                }
-                if (cfg.boot_n > 0 && cfg.bq_n > 0)
-                    fprintf(f, ", \"bootq_quantiles\": %d, \"bootq_held_bytes\": %lld, \"bootq_ms\": %.4f", qstats[i].n_quantiles,
-                            (long long)qstats[i].held_bytes, qstats[i].quantile_ms);
-                if (cfg.sub_nf > 0) {
-                    const emsar_subsample_stats *b = &sstats[i];
-                    fprintf(f, ", \"sub_fractions\": %d, \"sub_replicates\": %d, \"sub_batch\": %d, \"sub_replicates_unconverged\": %d, "
-                               "\"sub_draws\": %lld, \"sub_draw_ms\": %.4f, \"sub_sets_ms\": %.4f, \"sub_stream_ms\": %.4f, \"sub_reduce_ms\": %.4f, \"sub_total_ms\": %.4f",
-                            b->n_fractions, b->n_replicates, b->batch, b->replicates_unconverged, (long long)b->draws, b->draw_ms, b->sets_ms,
-                            b->stream_ms, b->reduce_ms, b->total_ms);
-                }
-                fprintf(f, "}");
-            }
-            fprintf(f, "]}\n");
-            fclose(f);
-        }
-    }
+    const double wall = now_s() - t0;
+    int n_bad = 0;
+    for (int i = 0; i < cfg.n_aln; i++) if (shared.status[i]) n_bad++;
+    if (cfg.stats_json) write_stats_json(&cfg, &shared, n_workers, wall, n_bad);
     emsar_rsh_free(rsh);
     emsar_genes_free(genes);
     free(cfg.pres_q); free(cfg.prof_q); free(cfg.cmp_q); free(ref.R); free(ref.E); free(ref.den);
-    for (int i = 0; i < n_list; i++) free(list[i]);
-    free(list); free(status); free(stats); free(bstats); free(sstats); free(qstats); free(parse_s); free(model_s); free(host_s); free(wa); free(th);
-    return bad ? 1 : 0;
+    for (int i = 0; i < cfg.n_aln; i++) free(cfg.aln[i]);
+    free(cfg.aln); free(shared.status); free(shared.stats); free(shared.bstats); free(shared.sstats); free(shared.qstats); free(shared.parse_s);
+    free(shared.model_s); free(shared.host_s); free(wa); free(th);
+    return n_bad ? 1 : 0;
 }

@@ -190,6 +190,26 @@ int emsar_write_presence(const char *path, const emsar_rsh *r, int32_t n_query, 
  * (TWO_SIDED, LOWER_ZERO, OUTSIDE, NOT_RESIDENT, UNCONVERGED); a value that is not finite is written as "inf" or "nan" */
 int emsar_write_profile(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, const double *fpkm, const double *lower,
                         const double *upper, const double *lambda, const int32_t *status);
+/* .gprofile (emsar-hip --profile --g2t): one line per gene in the order of .gfpkm -- gene gFPKM lower upper Lambda p members status; the
+ * arrays are [n_genes] as emsar_hip_profile_genes returns them for every gene, gfpkm the FPKM column of .gfpkm; the status words of .profile
+ * and TOO_LARGE; numbers "%lf", p "%.6g", a value that is not finite "nan", "inf" or "-inf" */
+int emsar_write_gprofile(const char *path, const emsar_genes *g, const double *gfpkm, const double *lower, const double *upper, const double *lambda,
+                         const double *pvalue, const int32_t *members, const int32_t *status);
+
+/* The two-sample files (emsar-hip -M --compare / --compare-usage, every sample i >= 1 against sample 0); numbers, p and values that are
+ * not finite as in .gprofile; the arrays as emsar_hip_compare, _compare_genes and _compare_usage return them.
+ * .compare: one line per queried transcript (query [n_query] tids, NULL = 0 .. n_query-1) -- tid transcriptID FPKM FPKM_ref log2FC Lambda p
+ * status evals; status TESTED, BOTH_ABSENT, OUTSIDE, NOT_RESIDENT or UNCONVERGED */
+int emsar_write_compare(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, const double *fpkm_a, const double *fpkm_b,
+                        const double *log2fc, const double *lambda, const double *pvalue, const int32_t *status, const int32_t *evals);
+/* .gcompare (with --g2t): one line per gene in the order of .gfpkm -- gene gFPKM gFPKM_ref log2FC Lambda p status evals parts; also TOO_LARGE */
+int emsar_write_gcompare(const char *path, const emsar_genes *g, const double *gene_a, const double *gene_b, const double *log2fc, const double *lambda,
+                         const double *pvalue, const int32_t *status, const int32_t *evals, const int32_t *parts);
+/* .ucompare: one line per queried transcript, query as for .compare -- transcript gene usage usage_ref dlogit Lambda p status outer evals; the
+ * gene field of a transcript in no gene (gene_of_tx < 0) is empty; also TOO_LARGE, UNDEFINED and SINGLE */
+int emsar_write_ucompare(const char *path, const emsar_rsh *r, const emsar_genes *g, int32_t n_query, const int32_t *query, const double *usage_a,
+                         const double *usage_b, const double *dlogit, const double *lambda, const double *pvalue, const int32_t *status,
+                         const int32_t *outer_evals, const int32_t *evals);
 
 /* .asym (emsar-hip --asymptotic): one line per transcript -- tid transcriptID FPKM sd_FPKM TPM sd_TPM status partner partner_corr, and
  * usage_sd when it is given (--g2t); the arrays are [n_tx] as emsar_hip_asymptotic returns them.  partner_corr = partner_cov /

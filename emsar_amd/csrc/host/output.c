@@ -24,6 +24,14 @@
  *   .saturation         "# fractions=.. replicates=.. seed=.. depth_mean=..", a header, then per transcript FPKM and TPM as in .fpkm and
  *                       per fraction mean_FPKM sd_FPKM mean_TPM sd_TPM, all "%lf"
  *   .gsaturation        the same per gene, per fraction mean_FPKM sd_FPKM mean_TPM
+ * and the files of the tests and intervals, each with a status word (one table per family below) and "nan" / "inf" for a value that is
+ * not finite:
+ *   .presence, .profile, .asym, .gasym     see emsar_host.h; an infinity is written without a sign
+ *   .gprofile           per gene, in the order of .gfpkm: gene gFPKM lower upper Lambda p members status
+ *   .compare            per queried transcript: tid transcriptID FPKM FPKM_ref log2FC Lambda p status evals
+ *   .gcompare           per gene, in the order of .gfpkm: gene gFPKM gFPKM_ref log2FC Lambda p status evals parts
+ *   .ucompare           per queried transcript: transcript gene usage usage_ref dlogit Lambda p status outer evals
+ *                       in these four the numbers are "%lf", p is "%.6g" and a negative infinity is written "-inf"
  * Column order of .fpkm is a contract: the reference's Perl utilities read columns 0,1,4,6 (util/FPKM2gFPKM.pl:19).
  */
 #include "emsar_host.h"
@@ -155,14 +163,29 @@ int emsar_write_gfit(const char *path, const emsar_rsh *r, const emsar_genes *g,
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
 
-/* a value of .presence: "%lf" / "%.6g", or the words inf / nan (no sign: Lambda and the share are not negative) */
-static void put_value(FILE *f, const char *fmt, double v) {
-    if (isnan(v)) fputs("nan", f); else if (isinf(v)) fputs("inf", f); else fprintf(f, fmt, v);
+/* The status words, one table per family of enums in include/emsar_hip.h; a file whose enum stops earlier uses the table's first words:
+ * .profile the first 5 of the intervals' (.gprofile all 6), .compare the first 5 and .gcompare the first 6 of the two-sample tests'
+ * (.ucompare all 8).  A number outside the file's range is written as "?". */
+static const char *const presence_word[6] = {"TESTED", "ABSENT", "ESSENTIAL", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED"};
+static const char *const interval_word[6] = {"TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE"};
+static const char *const two_sample_word[8] = {"TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE", "UNDEFINED", "SINGLE"};
+static const char *const asym_word[5] = {"ESTIMATED", "BOUNDARY", "UNIDENTIFIABLE", "TOO_LARGE", "INFEASIBLE"};
+
+static const char *status_word(const char *const *table, int n, int32_t v) { return v >= 0 && v < n ? table[v] : "?"; }
+
+/* a value that may not be finite: fmt ("%lf" / "%.6g"), or the words nan / inf.  signed_inf = 0 for .presence, .profile, .asym and .gasym
+ * (no sign: their Lambda, limits, shares and sd are not negative), 1 for .compare, .gcompare, .ucompare and .gprofile ("-inf") */
+static void put_value(FILE *f, const char *fmt, double v, int signed_inf) {
+    if (isnan(v)) fputs("nan", f); else if (isinf(v)) fputs(signed_inf && v < 0 ? "-inf" : "inf", f); else fprintf(f, fmt, v);
+}
+
+/* the number columns of a .compare, .gcompare, .ucompare or .gprofile line: n - 1 values "%lf" and the p-value "%.6g", tab-separated */
+static void put_test_columns(FILE *f, int n, const double *v) {
+    for (int k = 0; k < n; k++) { put_value(f, k + 1 < n ? "%lf" : "%.6g", v[k], 1); if (k + 1 < n) fputc('\t', f); }
 }
 
 int emsar_write_presence(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, const double *fpkm, const double *lambda,
                          const double *pvalue, const int32_t *status, const int32_t *heir, const double *heir_share) {
-    static const char *const word[6] = {"TESTED", "ABSENT", "ESSENTIAL", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED"};
     FILE *f = fopen(path, "w");
     if (!f) return EMSAR_HOST_ERR_IO;
     fprintf(f, "tid\ttranscriptID\tFPKM\tLambda\tp\tstatus\their\their_share\n");
@@ -170,17 +193,16 @@ int emsar_write_presence(const char *path, const emsar_rsh *r, int32_t n_query, 
     for (int32_t i = 0; i < n_query; i++) {
         const int32_t t = query ? query[i] : i;
         fprintf(f, "%d\t%s\t%lf\t", t, r->names[t], fpkm[t]);
-        put_value(f, "%lf", lambda[i]); fputc('\t', f);
-        put_value(f, "%.6g", pvalue[i]);
-        fprintf(f, "\t%s\t%s\t", status[i] >= 0 && status[i] < 6 ? word[status[i]] : "?", heir[i] >= 0 && heir[i] < r->n_tx ? r->names[heir[i]] : "-");
-        put_value(f, "%lf", heir_share[i]); fputc('\n', f);
+        put_value(f, "%lf", lambda[i], 0); fputc('\t', f);
+        put_value(f, "%.6g", pvalue[i], 0);
+        fprintf(f, "\t%s\t%s\t", status_word(presence_word, 6, status[i]), heir[i] >= 0 && heir[i] < r->n_tx ? r->names[heir[i]] : "-");
+        put_value(f, "%lf", heir_share[i], 0); fputc('\n', f);
     }
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
 
 int emsar_write_profile(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, const double *fpkm, const double *lower,
                         const double *upper, const double *lambda, const int32_t *status) {
-    static const char *const word[5] = {"TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED"};
     FILE *f = fopen(path, "w");
     if (!f) return EMSAR_HOST_ERR_IO;
     fprintf(f, "tid\ttranscriptID\tFPKM\tlower\tupper\tLambda\tstatus\n");
@@ -188,15 +210,72 @@ int emsar_write_profile(const char *path, const emsar_rsh *r, int32_t n_query, c
     for (int32_t i = 0; i < n_query; i++) {
         const int32_t t = query ? query[i] : i;
         fprintf(f, "%d\t%s\t%lf\t", t, r->names[t], fpkm[t]);
-        put_value(f, "%lf", lower[i]); fputc('\t', f);
-        put_value(f, "%lf", upper[i]); fputc('\t', f);
-        put_value(f, "%lf", lambda[i]);
-        fprintf(f, "\t%s\n", status[i] >= 0 && status[i] < 5 ? word[status[i]] : "?");
+        put_value(f, "%lf", lower[i], 0); fputc('\t', f);
+        put_value(f, "%lf", upper[i], 0); fputc('\t', f);
+        put_value(f, "%lf", lambda[i], 0);
+        fprintf(f, "\t%s\n", status_word(interval_word, 5, status[i]));
     }
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
 
-static const char *const asym_word[5] = {"ESTIMATED", "BOUNDARY", "UNIDENTIFIABLE", "TOO_LARGE", "INFEASIBLE"};
+int emsar_write_gprofile(const char *path, const emsar_genes *g, const double *gfpkm, const double *lower, const double *upper, const double *lambda,
+                         const double *pvalue, const int32_t *members, const int32_t *status) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "gene\tgFPKM\tlower\tupper\tLambda\tp\tmembers\tstatus\n");
+    for (int32_t k = 0; k < g->n_genes; k++) {
+        const double v[4] = {lower[k], upper[k], lambda[k], pvalue[k]};
+        fprintf(f, "%s\t%lf\t", g->names[k], gfpkm[k]);
+        put_test_columns(f, 4, v);
+        fprintf(f, "\t%d\t%s\n", members[k], status_word(interval_word, 6, status[k]));
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+int emsar_write_compare(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, const double *fpkm_a, const double *fpkm_b,
+                        const double *log2fc, const double *lambda, const double *pvalue, const int32_t *status, const int32_t *evals) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "tid\ttranscriptID\tFPKM\tFPKM_ref\tlog2FC\tLambda\tp\tstatus\tevals\n");
+    for (int32_t i = 0; i < n_query; i++) {
+        const int32_t t = query ? query[i] : i;
+        const double v[5] = {fpkm_a[i], fpkm_b[i], log2fc[i], lambda[i], pvalue[i]};
+        fprintf(f, "%d\t%s\t", t, r->names[t]);
+        put_test_columns(f, 5, v);
+        fprintf(f, "\t%s\t%d\n", status_word(two_sample_word, 5, status[i]), evals[i]);
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+int emsar_write_gcompare(const char *path, const emsar_genes *g, const double *gene_a, const double *gene_b, const double *log2fc, const double *lambda,
+                         const double *pvalue, const int32_t *status, const int32_t *evals, const int32_t *parts) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "gene\tgFPKM\tgFPKM_ref\tlog2FC\tLambda\tp\tstatus\tevals\tparts\n");
+    for (int32_t k = 0; k < g->n_genes; k++) {
+        const double v[5] = {gene_a[k], gene_b[k], log2fc[k], lambda[k], pvalue[k]};
+        fprintf(f, "%s\t", g->names[k]);
+        put_test_columns(f, 5, v);
+        fprintf(f, "\t%s\t%d\t%d\n", status_word(two_sample_word, 6, status[k]), evals[k], parts[k]);
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+int emsar_write_ucompare(const char *path, const emsar_rsh *r, const emsar_genes *g, int32_t n_query, const int32_t *query, const double *usage_a,
+                         const double *usage_b, const double *dlogit, const double *lambda, const double *pvalue, const int32_t *status,
+                         const int32_t *outer_evals, const int32_t *evals) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "transcript\tgene\tusage\tusage_ref\tdlogit\tLambda\tp\tstatus\touter\tevals\n");
+    for (int32_t i = 0; i < n_query; i++) {
+        const int32_t t = query ? query[i] : i, k = g->gene_of_tx[t];
+        const double v[5] = {usage_a[i], usage_b[i], dlogit[i], lambda[i], pvalue[i]};
+        fprintf(f, "%s\t%s\t", r->names[t], k >= 0 ? g->names[k] : "");
+        put_test_columns(f, 5, v);
+        fprintf(f, "\t%s\t%d\t%d\n", status_word(two_sample_word, 8, status[i]), outer_evals[i], evals[i]);
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
 
 int emsar_write_asym(const char *path, const emsar_rsh *r, const double *fpkm, const double *tpm, const double *sd_fpkm, const double *sd_tpm,
                      const double *var, const int32_t *status, const int32_t *partner, const double *partner_cov, const double *usage_sd) {
@@ -206,12 +285,12 @@ int emsar_write_asym(const char *path, const emsar_rsh *r, const double *fpkm, c
     for (int32_t t = 0; t < r->n_tx; t++) {
         const int32_t q = partner[t] >= 0 && partner[t] < r->n_tx ? partner[t] : -1;
         fprintf(f, "%d\t%s\t%lf\t", t, r->names[t], fpkm[t]);
-        put_value(f, "%.6g", sd_fpkm[t]);
+        put_value(f, "%.6g", sd_fpkm[t], 0);
         fprintf(f, "\t%lf\t", tpm[t]);
-        put_value(f, "%.6g", sd_tpm[t]);
-        fprintf(f, "\t%s\t%s\t", status[t] >= 0 && status[t] < 5 ? asym_word[status[t]] : "?", q >= 0 ? r->names[q] : "-");
-        put_value(f, "%.6g", q >= 0 ? partner_cov[t] / sqrt(var[t] * var[q]) : NAN);
-        if (usage_sd) { fputc('\t', f); put_value(f, "%.6g", usage_sd[t]); }
+        put_value(f, "%.6g", sd_tpm[t], 0);
+        fprintf(f, "\t%s\t%s\t", status_word(asym_word, 5, status[t]), q >= 0 ? r->names[q] : "-");
+        put_value(f, "%.6g", q >= 0 ? partner_cov[t] / sqrt(var[t] * var[q]) : NAN, 0);
+        if (usage_sd) { fputc('\t', f); put_value(f, "%.6g", usage_sd[t], 0); }
         fputc('\n', f);
     }
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
@@ -223,8 +302,8 @@ int emsar_write_gasym(const char *path, const emsar_genes *g, const double *gfpk
     fprintf(f, "geneID\tgFPKM\tsd\tstatus\n");
     for (int32_t k = 0; k < g->n_genes; k++) {
         fprintf(f, "%s\t%lf\t", g->names[k], gfpkm[k]);
-        put_value(f, "%.6g", gene_sd[k]);
-        fprintf(f, "\t%s\n", gene_status[k] >= 0 && gene_status[k] < 5 ? asym_word[gene_status[k]] : "?");
+        put_value(f, "%.6g", gene_sd[k], 0);
+        fprintf(f, "\t%s\n", status_word(asym_word, 5, gene_status[k]));
     }
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }

@@ -93,6 +93,10 @@ def lib():
                                            C.c_int, f64p, f64p]
         L.emsar_write_presence.argtypes = [C.c_char_p, C.POINTER(Rsh), C.c_int32, i32p, f64p, f64p, f64p, i32p, i32p, f64p]
         L.emsar_write_profile.argtypes = [C.c_char_p, C.POINTER(Rsh), C.c_int32, i32p, f64p, f64p, f64p, f64p, i32p]
+        L.emsar_write_gprofile.argtypes = [C.c_char_p, C.POINTER(Genes)] + [f64p] * 5 + [i32p, i32p]
+        L.emsar_write_compare.argtypes = [C.c_char_p, C.POINTER(Rsh), C.c_int32, i32p] + [f64p] * 5 + [i32p, i32p]
+        L.emsar_write_gcompare.argtypes = [C.c_char_p, C.POINTER(Genes)] + [f64p] * 5 + [i32p, i32p, i32p]
+        L.emsar_write_ucompare.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Genes), C.c_int32, i32p] + [f64p] * 5 + [i32p, i32p, i32p]
         L.emsar_write_asym.argtypes = [C.c_char_p, C.POINTER(Rsh)] + [f64p] * 5 + [i32p, i32p, f64p, f64p]
         L.emsar_write_gasym.argtypes = [C.c_char_p, C.POINTER(Genes), f64p, f64p, i32p]
         _lib = L
@@ -162,6 +166,66 @@ def write_profile(path, tx_names, fpkm, lower, upper, lam, status, query=None):
     rc = lib().emsar_write_profile(path.encode(), C.byref(r), n_tx if q is None else len(q), ip(q), _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3]), ip(st))
     if rc != 0:
         raise HostError("write_profile rc=%d" % rc)
+
+
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def write_gprofile(path, gene_names, gfpkm, lower, upper, lam, pvalue, members, status):
+    """.gprofile (emsar_write_gprofile): genes gene_names with their FPKM sums; lower, upper, lam, pvalue, members, status as
+    EmsarHip.profile_genes returns them for every gene."""
+    g = HostRsh._genes_struct(gene_names)
+    a = [np.ascontiguousarray(x, dtype=np.float64) for x in (gfpkm, lower, upper, lam, pvalue)]
+    i = [np.ascontiguousarray(x, dtype=np.int32) for x in (members, status)]
+    rc = lib().emsar_write_gprofile(path.encode(), C.byref(g), *([_dp(x) for x in a] + [_ip(x) for x in i]))
+    if rc != 0:
+        raise HostError("write_gprofile rc=%d" % rc)
+
+
+def write_compare(path, tx_names, theta_a, theta_b, log2fc, lam, pvalue, status, evals, query=None):
+    """.compare (emsar_write_compare): transcripts tx_names; theta_a, theta_b, log2fc, lam, pvalue, status, evals as EmsarHip.compare returns
+    them for query (tids, None = all transcripts in order)."""
+    n_tx = len(tx_names)
+    names = (C.c_char_p * max(n_tx, 1))(*[s.encode() for s in tx_names])
+    r = Rsh(n_tx=n_tx, names=C.cast(names, C.POINTER(C.c_char_p)))
+    q = None if query is None else np.ascontiguousarray(query, dtype=np.int32)
+    a = [np.ascontiguousarray(x, dtype=np.float64) for x in (theta_a, theta_b, log2fc, lam, pvalue)]
+    i = [np.ascontiguousarray(x, dtype=np.int32) for x in (status, evals)]
+    rc = lib().emsar_write_compare(path.encode(), C.byref(r), n_tx if q is None else len(q), None if q is None else _ip(q),
+                                   *([_dp(x) for x in a] + [_ip(x) for x in i]))
+    if rc != 0:
+        raise HostError("write_compare rc=%d" % rc)
+
+
+def write_gcompare(path, gene_names, gene_a, gene_b, log2fc, lam, pvalue, status, evals, parts):
+    """.gcompare (emsar_write_gcompare): genes gene_names; gene_a, gene_b, log2fc, lam, pvalue, status, evals, parts as EmsarHip.compare_genes
+    returns them for every gene."""
+    g = HostRsh._genes_struct(gene_names)
+    a = [np.ascontiguousarray(x, dtype=np.float64) for x in (gene_a, gene_b, log2fc, lam, pvalue)]
+    i = [np.ascontiguousarray(x, dtype=np.int32) for x in (status, evals, parts)]
+    rc = lib().emsar_write_gcompare(path.encode(), C.byref(g), *([_dp(x) for x in a] + [_ip(x) for x in i]))
+    if rc != 0:
+        raise HostError("write_gcompare rc=%d" % rc)
+
+
+def write_ucompare(path, tx_names, gene_names, gene_of_tx, usage_a, usage_b, dlogit, lam, pvalue, status, outer_evals, evals, query=None):
+    """.ucompare (emsar_write_ucompare): transcripts tx_names in genes gene_names through gene_of_tx (-1 = no gene, an empty gene field);
+    usage_a, usage_b, dlogit, lam, pvalue, status, outer_evals, evals as EmsarHip.compare_usage returns them for query (tids, None = all
+    transcripts in order)."""
+    n_tx = len(tx_names)
+    names = (C.c_char_p * max(n_tx, 1))(*[s.encode() for s in tx_names])
+    r = Rsh(n_tx=n_tx, names=C.cast(names, C.POINTER(C.c_char_p)))
+    gmap = np.ascontiguousarray(gene_of_tx, dtype=np.int32)
+    g = HostRsh._genes_struct(gene_names)
+    g.n_tx, g.gene_of_tx = n_tx, _ip(gmap)
+    q = None if query is None else np.ascontiguousarray(query, dtype=np.int32)
+    a = [np.ascontiguousarray(x, dtype=np.float64) for x in (usage_a, usage_b, dlogit, lam, pvalue)]
+    i = [np.ascontiguousarray(x, dtype=np.int32) for x in (status, outer_evals, evals)]
+    rc = lib().emsar_write_ucompare(path.encode(), C.byref(r), C.byref(g), n_tx if q is None else len(q), None if q is None else _ip(q),
+                                    *([_dp(x) for x in a] + [_ip(x) for x in i]))
+    if rc != 0:
+        raise HostError("write_ucompare rc=%d" % rc)
 
 
 def write_asym(path, tx_names, fpkm, tpm, sd_fpkm, sd_tpm, var, status, partner, partner_cov, usage_sd=None):

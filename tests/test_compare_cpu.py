@@ -178,3 +178,28 @@ def test_compare_kernels_use_no_scratch():
         assert len(names) == 1, (threads, names)
         print(names[0], meta[names[0]])
         assert meta[names[0]]["vgpr_spill_count"] == 0 and meta[names[0]]["private_segment_fixed_size"] == 0, (names[0], meta[names[0]])
+
+
+def test_writer_byte_for_byte(tmp_path):
+    """.compare (emsar_write_compare): a query list out of order with repeats, every status and two outside the range, and nan, +inf and -inf
+    in each of the five number columns -- the sign of an infinity is printed"""
+    from emsar_amd import hostlib
+    _build.build_all()
+    nan, inf = float("nan"), float("inf")
+    p = str(tmp_path / "a.compare")
+    hostlib.write_compare(p, ["tA", "tB", "tC", "tD", "tE"],
+                          [1.5, nan, inf, -inf, 0.0, 2.25, 1e-7], [0.75, nan, inf, -inf, 4.5, 0.0, 12345678.5], [1.0, nan, inf, -inf, -2.5, 0.5, -4e-7],
+                          [3.25, nan, inf, -inf, 0.0, 10.0, 0.125], [0.0714, nan, inf, -inf, 1.0, 1e-300, 0.123456789], [0, 1, 2, 3, 4, 5, -1],
+                          [12, 0, 1, 40, 7, 3, 2], query=[3, 0, 4, 0, 1, 2, 4])
+    assert open(p, "rb").read() == (b"tid\ttranscriptID\tFPKM\tFPKM_ref\tlog2FC\tLambda\tp\tstatus\tevals\n"
+                                    b"3\ttD\t1.500000\t0.750000\t1.000000\t3.250000\t0.0714\tTESTED\t12\n"
+                                    b"0\ttA\tnan\tnan\tnan\tnan\tnan\tBOTH_ABSENT\t0\n"
+                                    b"4\ttE\tinf\tinf\tinf\tinf\tinf\tOUTSIDE\t1\n"
+                                    b"0\ttA\t-inf\t-inf\t-inf\t-inf\t-inf\tNOT_RESIDENT\t40\n"
+                                    b"1\ttB\t0.000000\t4.500000\t-2.500000\t0.000000\t1\tUNCONVERGED\t7\n"
+                                    b"2\ttC\t2.250000\t0.000000\t0.500000\t10.000000\t1e-300\t?\t3\n"
+                                    b"4\ttE\t0.000000\t12345678.500000\t-0.000000\t0.125000\t0.123457\t?\t2\n")
+    hostlib.write_compare(p, ["tA", "tB"], [1.0, 2.0], [3.0, 4.0], [-1.5, -1.0], [0.5, 0.25], [0.5, 0.625], [0, 4], [9, 8])          # no query: all, in order
+    assert open(p, "rb").read() == (b"tid\ttranscriptID\tFPKM\tFPKM_ref\tlog2FC\tLambda\tp\tstatus\tevals\n"
+                                    b"0\ttA\t1.000000\t3.000000\t-1.500000\t0.500000\t0.5\tTESTED\t9\n"
+                                    b"1\ttB\t2.000000\t4.000000\t-1.000000\t0.250000\t0.625\tUNCONVERGED\t8\n")

@@ -161,3 +161,27 @@ def test_reference_two_member_gene_against_slsqp():
     print(lam_slsqp, ref["lam"], ref["w_ref"], res.message, abs(float(con @ res.x)))
     assert res.success and abs(float(con @ res.x)) <= 1e-9
     assert ref["w_ref"] <= W_REF_MAX and abs(ref["lam"] - lam_slsqp) <= ref["w_ref"] + 1e-7
+
+
+def test_writer_byte_for_byte(tmp_path):
+    """.gcompare (emsar_write_gcompare): three genes, one with an empty name, written three times -- every status and two outside the range,
+    and nan, +inf and -inf in each of the five number columns; the sign of an infinity is printed"""
+    from emsar_amd import _build, hostlib
+    _build.build_all()
+    nan, inf = float("nan"), float("inf")
+    genes = ["g1", "", "g3"]
+    head = b"gene\tgFPKM\tgFPKM_ref\tlog2FC\tLambda\tp\tstatus\tevals\tparts\n"
+    p = str(tmp_path / "a.gcompare")
+    hostlib.write_gcompare(p, genes, [1.5, nan, inf], [0.75, nan, inf], [1.0, nan, inf], [3.25, nan, inf], [0.0714, nan, inf], [0, 1, 2], [12, 0, 1], [2, 0, 64])
+    assert open(p, "rb").read() == head + (b"g1\t1.500000\t0.750000\t1.000000\t3.250000\t0.0714\tTESTED\t12\t2\n"
+                                           b"\tnan\tnan\tnan\tnan\tnan\tBOTH_ABSENT\t0\t0\n"
+                                           b"g3\tinf\tinf\tinf\tinf\tinf\tOUTSIDE\t1\t64\n")
+    hostlib.write_gcompare(p, genes, [-inf, 0.0, 2.25], [-inf, 4.5, 0.0], [-inf, -2.5, 0.5], [-inf, 0.0, 10.0], [-inf, 1.0, 1e-300], [3, 4, 5], [40, 7, 3], [1, 3, 65])
+    assert open(p, "rb").read() == head + (b"g1\t-inf\t-inf\t-inf\t-inf\t-inf\tNOT_RESIDENT\t40\t1\n"
+                                           b"\t0.000000\t4.500000\t-2.500000\t0.000000\t1\tUNCONVERGED\t7\t3\n"
+                                           b"g3\t2.250000\t0.000000\t0.500000\t10.000000\t1e-300\tTOO_LARGE\t3\t65\n")
+    hostlib.write_gcompare(p, genes, [1e-7, 1.0, 2.0], [12345678.5, 1.0, 2.0], [-4e-7, 0.0, 0.0], [0.125, 0.0, 0.0], [0.123456789, 1.0, 1.0], [6, -1, 7], [2, 1, 1],
+                           [2, 1, 1])
+    assert open(p, "rb").read() == head + (b"g1\t0.000000\t12345678.500000\t-0.000000\t0.125000\t0.123457\t?\t2\t2\n"
+                                           b"\t1.000000\t1.000000\t0.000000\t0.000000\t1\t?\t1\t1\n"
+                                           b"g3\t2.000000\t2.000000\t0.000000\t0.000000\t1\t?\t1\t1\n")

@@ -245,3 +245,28 @@ def test_recorded_references():
     for k in UP.KEPT:
         assert full[k] == rec["small-0-3-6:6"][k], (k, full[k], rec["small-0-3-6:6"][k])
     assert full["peaks"] == 1 and len(full["grid_u"]) == UP.GRID
+
+
+def test_writer_byte_for_byte(tmp_path):
+    """.ucompare (emsar_write_ucompare): five transcripts, one in no gene (an empty gene field, as for the gene with the empty name), a query list
+    out of order with repeats, every status and one outside the range, and nan, +inf and -inf in each of the five number columns -- the
+    sign of an infinity is printed"""
+    from emsar_amd import _build, hostlib
+    _build.build_all()
+    nan, inf = float("nan"), float("inf")
+    p = str(tmp_path / "a.ucompare")
+    hostlib.write_ucompare(p, ["tA", "tB", "tC", "tD", "tE"], ["g1", "", "g3"], [0, 2, -1, 0, 1],
+                           [0.25, nan, inf, -inf, 0.0, 1.0, 1e-7, 0.5, 0.5], [0.75, nan, inf, -inf, 1.0, 0.0, 0.999999, 0.5, 0.5],
+                           [-2.197225, nan, inf, -inf, -4e-7, 30.5, 0.0, 0.0, 0.0], [3.25, nan, inf, -inf, 0.0, 10.0, 0.125, 0.0, 0.0],
+                           [0.0714, nan, inf, -inf, 1.0, 1e-300, 0.123456789, 1.0, 1.0], [0, 1, 2, 3, 4, 5, 6, 7, 8], [5, 0, 1, 12, 3, 0, 0, 0, 2],
+                           [120, 0, 1, 480, 7, 3, 0, 0, 2], query=[3, 0, 4, 0, 1, 2, 4, 2, 1])
+    assert open(p, "rb").read() == (b"transcript\tgene\tusage\tusage_ref\tdlogit\tLambda\tp\tstatus\touter\tevals\n"
+                                    b"tD\tg1\t0.250000\t0.750000\t-2.197225\t3.250000\t0.0714\tTESTED\t5\t120\n"
+                                    b"tA\tg1\tnan\tnan\tnan\tnan\tnan\tBOTH_ABSENT\t0\t0\n"
+                                    b"tE\t\tinf\tinf\tinf\tinf\tinf\tOUTSIDE\t1\t1\n"
+                                    b"tA\tg1\t-inf\t-inf\t-inf\t-inf\t-inf\tNOT_RESIDENT\t12\t480\n"
+                                    b"tB\tg3\t0.000000\t1.000000\t-0.000000\t0.000000\t1\tUNCONVERGED\t3\t7\n"
+                                    b"tC\t\t1.000000\t0.000000\t30.500000\t10.000000\t1e-300\tTOO_LARGE\t0\t3\n"
+                                    b"tE\t\t0.000000\t0.999999\t0.000000\t0.125000\t0.123457\tUNDEFINED\t0\t0\n"
+                                    b"tC\t\t0.500000\t0.500000\t0.000000\t0.000000\t1\tSINGLE\t0\t0\n"
+                                    b"tB\tg3\t0.500000\t0.500000\t0.000000\t0.000000\t1\t?\t2\t2\n")

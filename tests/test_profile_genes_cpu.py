@@ -165,3 +165,28 @@ def test_abi_sizes():
     assert H.ProfileGeneStats.cut.offset == 96 and H.ProfileGeneStats.total_ms.offset == 120
     assert H.PROFILE_GENE_STATUS == ("TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE")
     assert "emsar_hip_profile_genes" in H.SYMBOLS and "emsar_hip_gene_presence_pvalue_host" in H.SYMBOLS
+
+
+# ---- the .gprofile file --------------------------------------------------------------------------------------------------------------
+def test_writer_byte_for_byte(tmp_path):
+    """.gprofile (emsar_write_gprofile): three genes, one with an empty name, written three times -- every status and two outside the range,
+    and nan, +inf and -inf in each of the four columns that can carry them (gFPKM is a sum of printed FPKM); the sign of an infinity is
+    printed"""
+    from emsar_amd import _build, hostlib
+    _build.build_all()
+    nan, inf = float("nan"), float("inf")
+    genes = ["g1", "", "g3"]
+    head = b"gene\tgFPKM\tlower\tupper\tLambda\tp\tmembers\tstatus\n"
+    p = str(tmp_path / "a.gprofile")
+    hostlib.write_gprofile(p, genes, [1.5, 0.0, 9.0], [0.75, nan, inf], [2.25, nan, inf], [3.25, nan, inf], [0.0714, nan, inf], [3, 0, 1], [0, 1, 2])
+    assert open(p, "rb").read() == head + (b"g1\t1.500000\t0.750000\t2.250000\t3.250000\t0.0714\t3\tTWO_SIDED\n"
+                                           b"\t0.000000\tnan\tnan\tnan\tnan\t0\tLOWER_ZERO\n"
+                                           b"g3\t9.000000\tinf\tinf\tinf\tinf\t1\tOUTSIDE\n")
+    hostlib.write_gprofile(p, genes, [1e-7, 4.5, 12345678.5], [-inf, 0.0, 1.0], [-inf, 6.5, 2.0], [-inf, 0.0, 10.0], [-inf, 1.0, 1e-300], [2, 64, 65], [3, 4, 5])
+    assert open(p, "rb").read() == head + (b"g1\t0.000000\t-inf\t-inf\t-inf\t-inf\t2\tNOT_RESIDENT\n"
+                                           b"\t4.500000\t0.000000\t6.500000\t0.000000\t1\t64\tUNCONVERGED\n"
+                                           b"g3\t12345678.500000\t1.000000\t2.000000\t10.000000\t1e-300\t65\tTOO_LARGE\n")
+    hostlib.write_gprofile(p, genes, [1.0, 1.0, 1.0], [0.5, 0.5, 0.5], [2.0, 2.0, 2.0], [0.125, 0.125, 0.125], [0.123456789, 1.0, 1.0], [1, 1, 1], [6, -1, 0])
+    assert open(p, "rb").read() == head + (b"g1\t1.000000\t0.500000\t2.000000\t0.125000\t0.123457\t1\t?\n"
+                                           b"\t1.000000\t0.500000\t2.000000\t0.125000\t1\t1\t?\n"
+                                           b"g3\t1.000000\t0.500000\t2.000000\t0.125000\t1\t1\tTWO_SIDED\n")
