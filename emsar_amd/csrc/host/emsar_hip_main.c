@@ -43,6 +43,10 @@
  * the limits of the profile-likelihood interval of the gene's total (the isoforms free), the gene presence test's Lambda, the p-value bound
  * P(chi2_members > Lambda), the members taking part and a status word (emsar_hip_profile_genes; --profile-list filters transcripts only).  The
  * other files do not change with it.
+ * --profile-usage (with --g2t) answers "what could this isoform's share of its gene be": <prefix>.<i>.uprofile holds, per transcript (or per
+ * transcript named in --profile-list FILE), its share, the limits of the share's profile-likelihood interval at --profile-level, the deviances
+ * of the shares 0 and 1, a status word, the outer points and the inner evaluations spent (emsar_hip_profile_usage with the solve's parameters
+ * and --profile-evals).  A switch of its own: --profile writes no .uprofile, and the other files do not change with it.
  * --compare (with -M and at least two samples) answers "does this isoform's abundance differ from sample 0": every sample i >= 1 writes
  * <prefix>.<i>.compare with, per transcript (or per transcript named in --compare-list FILE), its FPKM in sample i and in sample 0, log2 of their
  * ratio, the likelihood-ratio statistic Lambda of H0: theta_i = r * theta_0 (--compare-ratio r, default 1) with every sibling free in both samples,
@@ -103,6 +107,7 @@ typedef struct {
     int32_t *pres_q; int pres_nq;     /* --presence-list FILE: the tids it names, in file order (NULL = all transcripts) */
     int profile, profile_evals; double profile_level; /* --profile [--profile-level L] [--profile-evals N] */
     int32_t *prof_q; int prof_nq;     /* --profile-list FILE, as --presence-list */
+    int profile_usage;                /* --profile-usage (needs --g2t): .uprofile; takes --profile-level, --profile-evals and --profile-list */
     int compare; double compare_ratio; /* --compare [--compare-ratio r] */
     int compare_usage;                /* --compare-usage (needs --g2t): also a two-sample run, shares sample 0 with --compare */
     int32_t *cmp_q; int cmp_nq;       /* --compare-list FILE, as --presence-list */
@@ -400,6 +405,25 @@ static int stage_profile(sample *s) {
     return !rc && s->G ? profile_genes(s, &pp) : rc;
 }
 
+/* Profile-likelihood intervals of isoform usage (--profile-usage --g2t): two limits of each transcript's share of its gene: .uprofile */
+static int stage_profile_usage(sample *s) {
+    const int32_t *query = s->cfg->prof_q;
+    const size_t Q = query ? (size_t)s->cfg->prof_nq : s->T;
+    const emsar_profile_params pp = {.level = s->cfg->profile_level, .max_evals = s->cfg->profile_evals};
+    double *v = (double *)slab(5 * Q, 8);
+    int32_t *iv = (int32_t *)slab(3 * Q, 4);
+    int rc = v && iv ? 0 : EMSAR_HOST_ERR_OOM;
+    if (!rc) {
+        const emsar_profile_usage_outputs o = {.usage = v, .lower = v + Q, .upper = v + 2 * Q, .lambda_zero = v + 3 * Q, .lambda_one = v + 4 * Q,
+                                               .status = iv, .outer_evals = iv + Q, .evals = iv + 2 * Q};
+        if (!(rc = lib_call(s, "profile_usage", emsar_hip_profile_usage(s->ctx, &s->p, &pp, (int32_t)Q, query, &o, NULL))))
+            rc = wrote(s, emsar_write_uprofile(out_path(s, "uprofile"), s->r, s->G, (int32_t)Q, query, o.usage, o.lower, o.upper, o.lambda_zero,
+                                               o.lambda_one, o.status, o.outer_evals, o.evals));
+    }
+    free(v); free(iv);
+    return rc;
+}
+
 /* Two-sample tests: sample 0 in a second context on this worker's device, made on the first sample that needs it and kept by the worker */
 static int reference_context(sample *s) {
     worker_arg *w = s->w; const emsar_rsh *r = s->r;
@@ -588,6 +612,7 @@ static int run_sample(worker_arg *w, emsar_hip_ctx *ctx, int i, parse_job *parse
     if (!rc && cfg->fit) rc = stage_fit(&s);
     if (!rc && cfg->presence) rc = stage_presence(&s);
     if (!rc && cfg->profile) rc = stage_profile(&s);
+    if (!rc && cfg->profile_usage) rc = stage_profile_usage(&s);
     if (!rc && (cfg->compare || cfg->compare_usage) && i > 0) rc = stage_two_sample(&s);
     if (!rc && cfg->asymptotic) rc = stage_asymptotic(&s);
     if (!rc && cfg->boot_n > 0) rc = stage_bootstrap(&s);
@@ -702,6 +727,10 @@ static void usage(const char *a0) {
             "      --profile-level <l>   with --profile: the confidence level, 0 < l < 1 (default 0.95)\n"
             "      --profile-evals <n>   with --profile: at most n set solves per limit (default 40); a search that needs more is UNCONVERGED\n"
             "      --profile-list <file> with --profile: only the transcripts named in the file, one name per line (.gprofile always holds every gene)\n"
+            "      --profile-usage       with --g2t: also write <prefix>.<i>.uprofile: per transcript its share of its gene, the lower and upper limit of\n"
+            "                            the share's profile-likelihood interval, the deviances of the shares 0 and 1, a status word (TWO_SIDED, LOWER_ZERO,\n"
+            "                            UPPER_ONE, UNIT, UNDEFINED, SINGLE, OUTSIDE, NOT_RESIDENT, TOO_LARGE, UNCONVERGED), the outer points and the inner\n"
+            "                            evaluations spent; takes --profile-level, --profile-evals and --profile-list as --profile does\n"
             "      --compare             with -M and at least two samples: every sample i >= 1 also writes <prefix>.<i>.compare: per transcript its FPKM\n"
             "                            in sample i and in sample 0, log2 of the ratio, the likelihood-ratio statistic Lambda of equal abundance\n"
             "                            (siblings free in both samples), its p-value, a status word (TESTED, BOTH_ABSENT, OUTSIDE, NOT_RESIDENT,\n"
@@ -768,7 +797,7 @@ static int parse_options(int argc, char **argv, config *cfg) {
         {"profile", no_argument, 0, 1025}, {"profile-level", required_argument, 0, 1026}, {"profile-list", required_argument, 0, 1027},
         {"profile-evals", required_argument, 0, 1028},
         {"compare", no_argument, 0, 1029}, {"compare-ratio", required_argument, 0, 1030}, {"compare-list", required_argument, 0, 1031},
-        {"compare-usage", no_argument, 0, 1040},
+        {"compare-usage", no_argument, 0, 1040}, {"profile-usage", no_argument, 0, 1041},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
@@ -825,6 +854,7 @@ static int parse_options(int argc, char **argv, config *cfg) {
             case 1028: if ((cfg->profile_evals = atoi(optarg)) <= 0) return bad("--profile-evals must be positive."); break;
             case 1029: cfg->compare = 1; break;
             case 1040: cfg->compare_usage = 1; break;
+            case 1041: cfg->profile_usage = 1; break;
             case 1030: cfg->compare_ratio = atof(optarg); cfg->compare_ratio_given = 1; break;
             case 1031: cfg->compare_list = optarg; break;
             default: usage(argv[0]); return 1;
@@ -842,13 +872,14 @@ static int check_options(config *cfg, const char *a0) {
     if (cfg->boundary_cut_given && !(cfg->boundary_cut >= 0.0)) return bad("--boundary-cut must be >= 0.");
     if (!cfg->boundary_cut_given) cfg->boundary_cut = EMSAR_ASYM_DEFAULT_CUT;
     if (cfg->presence_list && !cfg->presence) return bad("--presence-list needs --presence.");
-    if ((cfg->profile_list || cfg->profile_level_given || cfg->profile_evals) && !cfg->profile)
+    if ((cfg->profile_list || cfg->profile_level_given || cfg->profile_evals) && !cfg->profile && !cfg->profile_usage)
         return bad("--profile-list, --profile-level and --profile-evals need --profile.");
     if (cfg->profile_level_given && !(cfg->profile_level > 0.0 && cfg->profile_level < 1.0)) return bad("--profile-level must lie in (0, 1).");
     if (!cfg->profile_level_given) cfg->profile_level = 0.95;
     if (cfg->compare_ratio_given && !cfg->compare) return bad("--compare-ratio needs --compare.");
     if (cfg->compare_list && !cfg->compare && !cfg->compare_usage) return bad("--compare-list needs --compare or --compare-usage.");
     if (cfg->compare_usage && !cfg->g2t) return bad_usage("--compare-usage needs --g2t FILE.", a0);
+    if (cfg->profile_usage && !cfg->g2t) return bad_usage("--profile-usage needs --g2t FILE.", a0);
     if (cfg->compare_ratio_given && !(cfg->compare_ratio > 0.0 && isfinite(cfg->compare_ratio))) return bad("--compare-ratio must be positive.");
     if (!cfg->compare_ratio_given) cfg->compare_ratio = 1.0;
     if (cfg->compare && !cfg->multisample) return bad_usage("--compare needs -M and at least two samples.", a0);

@@ -195,6 +195,12 @@ int emsar_write_profile(const char *path, const emsar_rsh *r, int32_t n_query, c
  * and TOO_LARGE; numbers "%lf", p "%.6g", a value that is not finite "nan", "inf" or "-inf" */
 int emsar_write_gprofile(const char *path, const emsar_genes *g, const double *gfpkm, const double *lower, const double *upper, const double *lambda,
                          const double *pvalue, const int32_t *members, const int32_t *status);
+/* .uprofile (emsar-hip --profile-usage --g2t): one line per queried transcript, query as for .profile -- transcript gene usage lower upper
+ * Lambda_zero Lambda_one status outer evals; the arrays as emsar_hip_profile_usage returns them; the gene field of a transcript in no gene is
+ * empty; the status words of .gprofile and UPPER_ONE, UNIT, UNDEFINED, SINGLE; numbers "%lf", a value that is not finite "nan" or "inf" */
+int emsar_write_uprofile(const char *path, const emsar_rsh *r, const emsar_genes *g, int32_t n_query, const int32_t *query, const double *usage,
+                         const double *lower, const double *upper, const double *lambda_zero, const double *lambda_one, const int32_t *status,
+                         const int32_t *outer_evals, const int32_t *evals);
 
 /* The two-sample files (emsar-hip -M --compare / --compare-usage, every sample i >= 1 against sample 0); numbers, p and values that are
  * not finite as in .gprofile; the arrays as emsar_hip_compare, _compare_genes and _compare_usage return them.

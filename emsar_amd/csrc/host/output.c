@@ -31,6 +31,7 @@
  *   .compare            per queried transcript: tid transcriptID FPKM FPKM_ref log2FC Lambda p status evals
  *   .gcompare           per gene, in the order of .gfpkm: gene gFPKM gFPKM_ref log2FC Lambda p status evals parts
  *   .ucompare           per queried transcript: transcript gene usage usage_ref dlogit Lambda p status outer evals
+ *   .uprofile           per queried transcript: transcript gene usage lower upper Lambda_zero Lambda_one status outer evals
  *                       in these four the numbers are "%lf", p is "%.6g" and a negative infinity is written "-inf"
  * Column order of .fpkm is a contract: the reference's Perl utilities read columns 0,1,4,6 (util/FPKM2gFPKM.pl:19).
  */
@@ -165,16 +166,18 @@ int emsar_write_gfit(const char *path, const emsar_rsh *r, const emsar_genes *g,
 
 /* The status words, one table per family of enums in include/emsar_hip.h; a file whose enum stops earlier uses the table's first words:
  * .profile the first 5 of the intervals' (.gprofile all 6), .compare the first 5 and .gcompare the first 6 of the two-sample tests'
- * (.ucompare all 8).  A number outside the file's range is written as "?". */
+ * (.ucompare all 8), .uprofile the 10 of the usage intervals'.  A number outside the file's range is written as "?". */
 static const char *const presence_word[6] = {"TESTED", "ABSENT", "ESSENTIAL", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED"};
 static const char *const interval_word[6] = {"TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE"};
+static const char *const usage_interval_word[10] = {"TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE", "UPPER_ONE", "UNIT",
+                                                    "UNDEFINED", "SINGLE"};
 static const char *const two_sample_word[8] = {"TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE", "UNDEFINED", "SINGLE"};
 static const char *const asym_word[5] = {"ESTIMATED", "BOUNDARY", "UNIDENTIFIABLE", "TOO_LARGE", "INFEASIBLE"};
 
 static const char *status_word(const char *const *table, int n, int32_t v) { return v >= 0 && v < n ? table[v] : "?"; }
 
 /* a value that may not be finite: fmt ("%lf" / "%.6g"), or the words nan / inf.  signed_inf = 0 for .presence, .profile, .asym and .gasym
- * (no sign: their Lambda, limits, shares and sd are not negative), 1 for .compare, .gcompare, .ucompare and .gprofile ("-inf") */
+ * and .uprofile (no sign: their Lambda, limits, shares and sd are not negative), 1 for .compare, .gcompare, .ucompare and .gprofile ("-inf") */
 static void put_value(FILE *f, const char *fmt, double v, int signed_inf) {
     if (isnan(v)) fputs("nan", f); else if (isinf(v)) fputs(signed_inf && v < 0 ? "-inf" : "inf", f); else fprintf(f, fmt, v);
 }
@@ -273,6 +276,23 @@ int emsar_write_ucompare(const char *path, const emsar_rsh *r, const emsar_genes
         fprintf(f, "%s\t%s\t", r->names[t], k >= 0 ? g->names[k] : "");
         put_test_columns(f, 5, v);
         fprintf(f, "\t%s\t%d\t%d\n", status_word(two_sample_word, 8, status[i]), outer_evals[i], evals[i]);
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+int emsar_write_uprofile(const char *path, const emsar_rsh *r, const emsar_genes *g, int32_t n_query, const int32_t *query, const double *usage,
+                         const double *lower, const double *upper, const double *lambda_zero, const double *lambda_one, const int32_t *status,
+                         const int32_t *outer_evals, const int32_t *evals) {
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "transcript\tgene\tusage\tlower\tupper\tLambda_zero\tLambda_one\tstatus\touter\tevals\n");
+    if (!query) n_query = r->n_tx;
+    for (int32_t i = 0; i < n_query; i++) {
+        const int32_t t = query ? query[i] : i, k = g->gene_of_tx[t];
+        const double v[5] = {usage[i], lower[i], upper[i], lambda_zero[i], lambda_one[i]};
+        fprintf(f, "%s\t%s", r->names[t], k >= 0 ? g->names[k] : "");
+        for (int c = 0; c < 5; c++) { fputc('\t', f); put_value(f, "%lf", v[c], 0); }
+        fprintf(f, "\t%s\t%d\t%d\n", status_word(usage_interval_word, 10, status[i]), outer_evals[i], evals[i]);
     }
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }

@@ -76,13 +76,17 @@ struct UsageInner {
         pt.at(S.v, up, u, den_t0, mn);
         return true;
     }
-    __host__ __device__ bool step(bool first, double th_, double X_, double F_, double u, double den_t0, double mn, const UsageSearchParams &Q) {
+    // product_rule: stop at 2 |lambda g| <= dev_tol as well as by the bracket.  The product bounds the error of the dual value only
+    // where lambda lies beyond the root; a search that must not stop short of it (the usage profile, whose first point lies next to
+    // lambda = 0 while the root may be the end of the range) turns it off and keeps the bracket rule, which always bounds it
+    __host__ __device__ bool step(bool first, double th_, double X_, double F_, double u, double den_t0, double mn, const UsageSearchParams &Q,
+                                  bool product_rule = true) {
         th = th_; X = X_; F = F_;
         evals++;
         if (first) { ok = 1; return false; }
         const double g = th - u * X;
         if (!(g - g == 0.0) || !(F - F == 0.0)) return false;                         // a non-finite value: reported unconverged
-        if (2.0 * fabs(pt.lambda * g) <= Q.dev_tol) { ok = 1; return false; }
+        if (product_rule && 2.0 * fabs(pt.lambda * g) <= Q.dev_tol) { ok = 1; return false; }
         S.update(g / (th + u * X));
         if (2.0 * fabs(g) * ((S.B.p_hi - S.B.p_lo) * UsagePoint::end(up, u, den_t0, mn)) <= Q.dev_tol) { ok = 1; return false; }
         if (evals >= Q.max_evals) return false;

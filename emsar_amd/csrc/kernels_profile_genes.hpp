@@ -69,6 +69,14 @@ struct GeneDropEdit {
     int32_t gene;
     __device__ double operator()(int32_t tid, double dn) const { return gene_of[tid] == gene ? 0.0 : dn; }
 };
+// The drops of the usage profile (kernels_profile_usage.hpp): member t of the gene alone (others = false), or every member but t
+struct UsageDropEdit {
+    static constexpr bool kActive = true;
+    const int32_t *gene_of;
+    int32_t gene, t;
+    bool others;
+    __device__ double operator()(int32_t tid, double dn) const { return (gene_of[tid] == gene && (tid == t) != others) ? 0.0 : dn; }
+};
 
 // the record of a search (k_profile_gene_sets; profile_gene_closed_limit, profile_genes.hpp); the host's closed-form genes have no
 // passes, no solve that could fail and nothing infeasible: GeneSolveCount()

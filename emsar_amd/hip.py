@@ -30,7 +30,7 @@ SYMBOLS = [
     "emsar_hip_profile", "emsar_hip_profile_cut_host",
     "emsar_hip_compare", "emsar_hip_compare_pvalue_host", "emsar_hip_compare_genes",
     "emsar_hip_profile_genes", "emsar_hip_gene_presence_pvalue_host",
-    "emsar_hip_compare_usage",
+    "emsar_hip_compare_usage", "emsar_hip_profile_usage",
     "emsar_hip_asymptotic", "emsar_hip_asymptotic_host",
 ]
 
@@ -56,6 +56,12 @@ USAGE_COUNTS = ("status", "outer_evals", "evals", "parts")
 # status of a gene's profile-likelihood interval (include/emsar_hip.h "gene-level profile intervals"), by value
 PROFILE_GENE_STATUS = PROFILE_STATUS + ("TOO_LARGE",)
 PROFILE_GENE_OUTPUTS = ("lower", "upper", "dev_lower", "dev_upper", "lambda", "pvalue", "gene_hat")
+
+# status of a transcript's profile-likelihood interval of isoform usage (include/emsar_hip.h "profile-likelihood intervals of isoform
+# usage"), by value
+PROFILE_USAGE_STATUS = PROFILE_GENE_STATUS + ("UPPER_ONE", "UNIT", "UNDEFINED", "SINGLE")
+PROFILE_USAGE_OUTPUTS = ("usage", "lower", "upper", "dev_lower", "dev_upper", "lambda_zero", "lambda_one")
+PROFILE_USAGE_COUNTS = ("status", "outer_evals", "evals", "parts", "members")
 
 # status of a transcript in the asymptotic standard errors (include/emsar_hip.h "asymptotic standard errors"), by value
 ASYM_STATUS = ("ESTIMATED", "BOUNDARY", "UNIDENTIFIABLE", "TOO_LARGE", "INFEASIBLE")
@@ -150,7 +156,7 @@ class PresenceStats(C.Structure):
 
 
 class ProfileParams(C.Structure):
-    _fields_ = [("level", C.c_double), ("dev_tol", C.c_double), ("max_evals", C.c_int32), ("reserved0", C.c_int32)]
+    _fields_ = [("level", C.c_double), ("dev_tol", C.c_double), ("max_evals", C.c_int32), ("max_outer", C.c_int32)]
 
 
 class ProfileOutputs(C.Structure):
@@ -239,6 +245,22 @@ class ProfileGeneStats(C.Structure):
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["n_status"] = dict(zip(PROFILE_GENE_STATUS, d["n_status"]))
+        return d
+
+
+class ProfileUsageOutputs(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in PROFILE_USAGE_OUTPUTS] + [(k, C.POINTER(C.c_int32)) for k in PROFILE_USAGE_COUNTS]
+
+
+class ProfileUsageStats(C.Structure):
+    _fields_ = [("n_status", C.c_int64 * 10), ("items_launched", C.c_int64), ("evals_sum", C.c_int64), ("passes_sum", C.c_int64),
+                ("outer_sum", C.c_int64), ("evals_max", C.c_int32), ("passes_max", C.c_int32), ("parts_max", C.c_int32),
+                ("outer_max", C.c_int32), ("min_raw_lambda", C.c_double), ("cut", C.c_double), ("baseline_ms", C.c_double),
+                ("search_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["n_status"] = dict(zip(PROFILE_USAGE_STATUS, d["n_status"]))
         return d
 
 
@@ -351,6 +373,8 @@ def load_library():
                                           C.POINTER(CompareGeneStats)]
     L.emsar_hip_compare_usage.argtypes = [vp, vp, C.POINTER(EmParams), C.POINTER(UsageParams), C.c_int32, i32p, C.POINTER(UsageOutputs),
                                           C.POINTER(UsageStats)]
+    L.emsar_hip_profile_usage.argtypes = [vp, C.POINTER(EmParams), C.POINTER(ProfileParams), C.c_int32, i32p, C.POINTER(ProfileUsageOutputs),
+                                          C.POINTER(ProfileUsageStats)]
     L.emsar_hip_profile_genes.argtypes = [vp, C.POINTER(EmParams), C.POINTER(ProfileParams), C.c_int32, i32p, C.POINTER(ProfileGeneOutputs),
                                           C.POINTER(ProfileGeneStats)]
     L.emsar_hip_gene_presence_pvalue_host.argtypes = [C.c_int64, f64p, i32p, f64p]
@@ -646,6 +670,26 @@ def debug_profile_genes_closed(u, den, level=0.95, dev_tol=0.0, max_evals=0):
         raise EmsarHipError(rc, "debug_profile_genes_closed")
     out = dict(zip(PROFILE_GENE_OUTPUTS, list(vals)))
     out.update(status=status.value, evals=evals.value, evals_upper=int(vals[7]))
+    return out
+
+
+def debug_profile_usage_closed(u, den, t=0, level=0.95, dev_tol=0.0, max_evals=0, max_outer=0):
+    """Host-only diagnostic: what profile_usage() gives member `t` of a gene whose members are all one-transcript components -- u[i]
+    reads and den[i] each (den 0 = takes no part): the host's statuses and the searches as the host runs them for such genes (no GPU
+    needed).  Returns a dict of scalars keyed like profile_usage()'s arrays."""
+    f = load_library().emsar_hip_debug_profile_usage_closed       # not declared in the header: bound here, not in load_library
+    f.restype = C.c_int
+    dp = C.POINTER(C.c_double)
+    f.argtypes = [C.c_int32, dp, dp, C.c_int32, C.POINTER(ProfileParams), dp, C.POINTER(C.c_int32)]
+    uu, dd = (np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1)) for x in (u, den))
+    if uu.shape != dd.shape:
+        raise ValueError("u and den must have the same length")
+    pp, vals, counts = ProfileParams(float(level), float(dev_tol), int(max_evals), int(max_outer)), (C.c_double * 7)(), (C.c_int32 * 5)()
+    rc = f(len(uu), _p(uu, C.c_double), _p(dd, C.c_double), int(t), C.byref(pp), vals, counts)
+    if rc != 0:
+        raise EmsarHipError(rc, "debug_profile_usage_closed")
+    out = dict(zip(PROFILE_USAGE_OUTPUTS, list(vals)))
+    out.update(zip(PROFILE_USAGE_COUNTS, list(counts)))
     return out
 
 
@@ -1029,6 +1073,28 @@ class EmsarHip:
         o = ProfileGeneOutputs(*[_p(res[k], C.c_double) for k in PROFILE_GENE_OUTPUTS], *[_p(res[k], C.c_int32) for k in ints])
         st = ProfileGeneStats()
         self._chk(self._L.emsar_hip_profile_genes(self._h, C.byref(p), C.byref(pp), nq, _p(q, C.c_int32), C.byref(o), C.byref(st)), "profile_genes")
+        out = {k: v[:nq] for k, v in res.items()}
+        out["stats"] = st
+        return out
+
+    def profile_usage(self, query=None, level=0.95, dev_tol=0.0, max_evals=0, max_outer=0, max_iter=100000, accel=1, tol=1e-10, abs_floor=1e-6,
+                      check_every=8, count_floor=0.0, set_mode=0, zero_cut=0.0, abs_step=0.0, newton_after=0):
+        """Profile-likelihood interval of each queried transcript's share of its gene (include/emsar_hip.h "profile-likelihood
+        intervals of isoform usage"): the shares theta_t / (the gene sum) whose best achievable likelihood -- everything else free --
+        lies within the chi2_1 cut of `level` of the maximum.  query: tids in any order, repeats allowed, None = all transcripts; level,
+        dev_tol, max_evals as in profile(), max_outer 0 = 24 outer points per limit; the solver parameters are those of solve().
+        Returns a dict of arrays in query order: usage, lower, upper, dev_lower, dev_upper, lambda_zero, lambda_one, status (index into
+        PROFILE_USAGE_STATUS), outer_evals, evals, parts, members, and stats.  After upload_sample and set_gene_map; the context is left
+        as it was."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        pp = ProfileParams(float(level), float(dev_tol), int(max_evals), int(max_outer))
+        q = None if query is None else np.ascontiguousarray(np.asarray(query, dtype=np.int32).reshape(-1))
+        nq = self.n_tx if q is None else len(q)
+        res = {k: np.zeros(max(nq, 1)) for k in PROFILE_USAGE_OUTPUTS}
+        res.update({k: np.zeros(max(nq, 1), dtype=np.int32) for k in PROFILE_USAGE_COUNTS})
+        o = ProfileUsageOutputs(*[_p(res[k], C.c_double) for k in PROFILE_USAGE_OUTPUTS], *[_p(res[k], C.c_int32) for k in PROFILE_USAGE_COUNTS])
+        st = ProfileUsageStats()
+        self._chk(self._L.emsar_hip_profile_usage(self._h, C.byref(p), C.byref(pp), nq, _p(q, C.c_int32), C.byref(o), C.byref(st)), "profile_usage")
         out = {k: v[:nq] for k, v in res.items()}
         out["stats"] = st
         return out

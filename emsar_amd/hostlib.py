@@ -97,6 +97,7 @@ def lib():
         L.emsar_write_compare.argtypes = [C.c_char_p, C.POINTER(Rsh), C.c_int32, i32p] + [f64p] * 5 + [i32p, i32p]
         L.emsar_write_gcompare.argtypes = [C.c_char_p, C.POINTER(Genes)] + [f64p] * 5 + [i32p, i32p, i32p]
         L.emsar_write_ucompare.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Genes), C.c_int32, i32p] + [f64p] * 5 + [i32p, i32p, i32p]
+        L.emsar_write_uprofile.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Genes), C.c_int32, i32p] + [f64p] * 5 + [i32p, i32p, i32p]
         L.emsar_write_asym.argtypes = [C.c_char_p, C.POINTER(Rsh)] + [f64p] * 5 + [i32p, i32p, f64p, f64p]
         L.emsar_write_gasym.argtypes = [C.c_char_p, C.POINTER(Genes), f64p, f64p, i32p]
         _lib = L
@@ -226,6 +227,25 @@ def write_ucompare(path, tx_names, gene_names, gene_of_tx, usage_a, usage_b, dlo
                                     *([_dp(x) for x in a] + [_ip(x) for x in i]))
     if rc != 0:
         raise HostError("write_ucompare rc=%d" % rc)
+
+
+def write_uprofile(path, tx_names, gene_names, gene_of_tx, usage, lower, upper, lambda_zero, lambda_one, status, outer_evals, evals, query=None):
+    """.uprofile (emsar_write_uprofile): transcripts tx_names in genes gene_names through gene_of_tx (-1 = no gene, an empty gene field);
+    usage, lower, upper, lambda_zero, lambda_one, status, outer_evals, evals as EmsarHip.profile_usage returns them for query (tids, None =
+    all transcripts in order)."""
+    n_tx = len(tx_names)
+    names = (C.c_char_p * max(n_tx, 1))(*[s.encode() for s in tx_names])
+    r = Rsh(n_tx=n_tx, names=C.cast(names, C.POINTER(C.c_char_p)))
+    gmap = np.ascontiguousarray(gene_of_tx, dtype=np.int32)
+    g = HostRsh._genes_struct(gene_names)
+    g.n_tx, g.gene_of_tx = n_tx, _ip(gmap)
+    q = None if query is None else np.ascontiguousarray(query, dtype=np.int32)
+    a = [np.ascontiguousarray(x, dtype=np.float64) for x in (usage, lower, upper, lambda_zero, lambda_one)]
+    i = [np.ascontiguousarray(x, dtype=np.int32) for x in (status, outer_evals, evals)]
+    rc = lib().emsar_write_uprofile(path.encode(), C.byref(r), C.byref(g), n_tx if q is None else len(q), None if q is None else _ip(q),
+                                    *([_dp(x) for x in a] + [_ip(x) for x in i]))
+    if rc != 0:
+        raise HostError("write_uprofile rc=%d" % rc)
 
 
 def write_asym(path, tx_names, fpkm, tpm, sd_fpkm, sd_tpm, var, status, partner, partner_cov, usage_sd=None):

@@ -515,7 +515,7 @@ enum {
     EMSAR_PROFILE_TWO_SIDED = 0, EMSAR_PROFILE_LOWER_ZERO = 1, EMSAR_PROFILE_OUTSIDE = 2, EMSAR_PROFILE_NOT_RESIDENT = 3,
     EMSAR_PROFILE_UNCONVERGED = 4
 };
-typedef struct { double level, dev_tol; int32_t max_evals, reserved0; } emsar_profile_params;      /* NULL: 0.95 and the defaults */
+typedef struct { double level, dev_tol; int32_t max_evals, max_outer; } emsar_profile_params;      /* NULL: 0.95 and the defaults; max_outer: read by emsar_hip_profile_usage alone, ignored by emsar_hip_profile and _profile_genes */
 typedef struct {
     double  *lower, *upper, *dev_lower, *dev_upper, *lambda, *theta_hat;    /* [n_query]; may each be NULL */
     int32_t *status, *evals;                                                /* [n_query] EMSAR_PROFILE_*; solves spent on the two searches */
@@ -832,6 +832,90 @@ int emsar_hip_profile_genes(emsar_hip_ctx *ctx, const emsar_em_params *p, const 
                             const int32_t *query_genes /* NULL = all genes */, const emsar_profile_gene_outputs *out /* or NULL */,
                             emsar_profile_gene_stats *stats /* or NULL */);
 int emsar_hip_gene_presence_pvalue_host(int64_t n, const double *lambda, const int32_t *members, double *p_out);
+
+/* ---- profile-likelihood intervals of isoform usage: what could a transcript's share of its gene be? ----
+ * The interval of the third quantity the library asks its questions of, next to emsar_hip_profile (a transcript's abundance) and
+ * emsar_hip_profile_genes (a gene's total).  The bootstrap's percentile interval of a share is [0, 0] where the estimate is 0, and
+ * usage_sd says nothing about how far the reads allow two confounded isoforms to move; the profile holds at the boundary.  One sample:
+ * the gene map of emsar_hip_set_gene_map, solver parameters p, pp (level, dev_tol, max_evals and their defaults as in emsar_hip_profile;
+ * max_outer <= 0: 24), q = the chi2_1 cut of emsar_hip_profile_cut_host.  Members, parts, X, F, mn (the smallest den of the OTHER members
+ * taking part) and the 64-part limit are exactly emsar_hip_compare_usage's definitions for one sample.  For transcript t of gene g:
+ *     baseline     theta_hat_t, X_hat, F_hat at lambda = 0, computed through the code path of every later evaluation, so every den keeps
+ *                  its own bits.  usage = theta_hat_t / X_hat, one IEEE division; it agrees with emsar_hip_isoform_usage up to
+ *                  summation order
+ *     D_t(u)       = 2 (F_hat - P(u)), P(u) = max {F : theta_t = u X} with everything else free, u in [0, 1].  On each side of usage
+ *                  the constraint set {theta_t <= u X} (>=) is a convex cone and F is concave: P is monotone on each side and each
+ *                  limit a unique root
+ *     ends         lambda_zero = D_t(0): F_hat against the solves with den_t taken as 0 in LDS (the transcript presence statistic,
+ *                  here summed over the gene's parts); lambda_one = D_t(1): F_hat against the solves with the den of every other
+ *                  member taking part taken as 0.  Each is +inf where a dropped member has reads only it explains (a folded
+ *                  single-transcript row, or a closed-form part with u > 0: decided on the host before the launch) or where the drop
+ *                  leaves a row with reads that nothing explains; 0.0 where the baseline already lies there (usage exactly 0,
+ *                  respectively 1).  Negative raw values are reported as 0, the most negative goes to the statistics
+ *     limits       lower = 0.0 exactly and dev_lower = lambda_zero where lambda_zero <= q; upper = 1.0 exactly and
+ *                  dev_upper = lambda_one where lambda_one <= q; otherwise the root of D_t(u) = q in (0, usage), respectively (usage, 1)
+ *     outer point  one point of a limit search is one inner multiplier search of emsar_hip_compare_usage at fixed u, run on this one
+ *                  sample by the same code (den_t + lambda (1 - u) on t, den_s - lambda u on the others; range, coordinate, h and the
+ *                  evaluation cap max_evals as there), stopped when 2 |g| * (the width of the bracket in lambda) <= dev_tol q / 4,
+ *                  a quarter of what the outer rule allows (the product rule 2 |lambda g| is not used: next to usage it would stop a
+ *                  search at its first, small multiplier while the root lies at the end of the range).  The point's value is the
+ *                  dual value F - lambda g >= P(u), so the reported D is a lower bound of the true one with an error of second
+ *                  order in g, and the interval errs wide.  Its slope is dD/du = -2 lambda Xc, Xc as emsar_hip_compare_usage
+ *                  defines it
+ *     outer search the coordinate is u itself, the function h(u) = sqrt(D) - sqrt(q): -sqrt(q) at usage, sqrt(D_end) - sqrt(q) > 0 or
+ *                  +inf at the end of the side (lambda_zero, lambda_one), both known without an evaluation, and the search never
+ *                  leaves the bracket they span.  First point: the Poisson guess for t's own expected reads, c = den_t X_hat
+ *                  (t alone with every read unambiguously its own: an upper bound of the information, so a short step):
+ *                  usage - sqrt(q usage / c) below, usage + sqrt(q usage / c) + q / (2 c) above; the midpoint of the bracket where
+ *                  that falls outside it.  Later points: a Newton step on h with the known slope (h' = D' / (2 sqrt D)) where
+ *                  D > 0, the slope has the sign of its side and the step falls strictly inside the bracket; else, while no point
+ *                  beyond the root has been seen, twice the distance from usage; else the Illinois step of the bracket (bisection
+ *                  while its far end is +inf).  It stops when |D - q| <= dev_tol q (dev_tol <= 0: 1e-4), when the larger |dD/du| of
+ *                  the bracket's ends times its width is <= dev_tol q (the end at usage has slope 0, an end not yet evaluated +inf),
+ *                  or after max_outer points (then UNCONVERGED).  The reported limit is u of the last outer point and dev_lower /
+ *                  dev_upper its D
+ *     cost         one workgroup per (gene, t) for the baseline and the two drops, one per limit searched: at most
+ *                  max_outer * max_evals * parts * max_iter passes.  A gene whose parts are all closed form is finished on the host
+ *                  by the same code and nothing is launched for it
+ *     outputs      usage, lower, upper, dev_lower, dev_upper, lambda_zero, lambda_one; outer_evals = outer points of both searches,
+ *                  evals = their inner evaluations summed, parts, members = how many take part
+ * status, per queried transcript (the first six are EMSAR_PROFILE_* and EMSAR_GENE_PROFILE_TOO_LARGE):
+ *     TWO_SIDED     both limits were found by search
+ *     LOWER_ZERO    lambda_zero <= q: lower = 0.0; upper searched
+ *     UPPER_ONE     lambda_one <= q: upper = 1.0; lower searched
+ *     UNIT          both: the interval is [0, 1] -- at this level the isoform cannot be told from its siblings
+ *     UNDEFINED     X_hat is exactly 0: usage, limits and Lambdas NaN, the counters are given
+ *     SINGLE        fewer than two members take part: the share is 1 by construction
+ *     OUTSIDE       den_t == 0, or t has no gene
+ *     NOT_RESIDENT  as in emsar_hip_profile_genes
+ *     TOO_LARGE     more than 64 parts
+ *     UNCONVERGED   values are given, but a solve, an inner search or an outer search hit its cap
+ *   For SINGLE, OUTSIDE, NOT_RESIDENT and TOO_LARGE every numeric output is NaN and the counters are 0.
+ * Outputs are indexed by query position (by tid when query_tids is NULL; n_query is then ignored); repeats and any order are allowed.  A
+ * result depends on the gene's parts, t, p and pp alone -- not on what else is asked, the batch, the layout, MERGE_ROWS or the library's
+ * numbering.  The context is left as it was.  Errors as emsar_hip_profile_genes, with tids for gene ids.
+ * EMSAR_HIP_PROFILE_USAGE_BATCH = items per launch and class (a testing aid; the bits do not change). */
+enum { EMSAR_UPROFILE_UPPER_ONE = 6, EMSAR_UPROFILE_UNIT = 7, EMSAR_UPROFILE_UNDEFINED = 8, EMSAR_UPROFILE_SINGLE = 9 };
+typedef struct {
+    double  *usage, *lower, *upper, *dev_lower, *dev_upper, *lambda_zero, *lambda_one;     /* [n_query]; may each be NULL */
+    int32_t *status, *outer_evals, *evals, *parts, *members;                /* [n_query] */
+} emsar_profile_usage_outputs;
+typedef struct {
+    int64_t n_status[10];         /* distinct queried transcripts per status */
+    int64_t items_launched;       /* workgroups: one per (gene, t) for baseline and drops, one per limit searched */
+    int64_t evals_sum;            /* inner evaluations summed over the searches on the device */
+    int64_t passes_sum;           /* passes summed over the searches' solves, every part (baseline and drops not counted) */
+    int64_t outer_sum;            /* outer points summed over the searches on the device */
+    int32_t evals_max, passes_max; /* the search with the most inner evaluations / the most passes */
+    int32_t parts_max, outer_max; /* the most parts of a gene that was searched; the search with the most outer points */
+    double  min_raw_lambda;       /* the most negative lambda_zero / lambda_one before clamping, 0 if none was negative */
+    double  cut;                  /* q */
+    double  baseline_ms, search_ms; /* device time of baseline + drops, and of the searches (HIP events) */
+    double  total_ms;             /* wall time of the call, a first call's set building included */
+} emsar_profile_usage_stats;
+int emsar_hip_profile_usage(emsar_hip_ctx *ctx, const emsar_em_params *p, const emsar_profile_params *pp /* or NULL */, int32_t n_query,
+                            const int32_t *query_tids /* NULL = all transcripts */, const emsar_profile_usage_outputs *out /* or NULL */,
+                            emsar_profile_usage_stats *stats /* or NULL */);
 
 /* ---- asymptotic standard errors: the inverse of the observed information at the MLE ---------------
  * How sure is theta_t, without resampling?  For a theta that maximises the likelihood of the current sample, the observed information

@@ -1,5 +1,5 @@
-/* host_writers.c -- the writers of the test and interval files (.compare, .gcompare, .ucompare, .gprofile and their neighbours .presence,
- * .profile, .asym, .gasym; output.c) and the driver's argument parsers (cli_parse.h) on the inputs of their CPU tests, as a plain program to
+/* host_writers.c -- the writers of the test and interval files (.compare, .gcompare, .ucompare, .gprofile, .uprofile and their neighbours
+ * .presence, .profile, .asym, .gasym; output.c) and the driver's argument parsers (cli_parse.h) on the inputs of their CPU tests, as a plain program to
  * put under the sanitizers:
  *   gcc -O1 -g -std=c11 -D_POSIX_C_SOURCE=200809L -fsanitize=address,undefined -fno-sanitize-recover=all -Iemsar_amd/csrc/host \
  *       tools/host_writers.c emsar_amd/csrc/host/output.c -lm -o host_writers && ./host_writers <scratch directory>
@@ -42,6 +42,8 @@ static void writers(const char *dir) {
         CHECK(emsar_write_compare(path, &r, NT, NULL, a, p, a, p, p, st, query) == EMSAR_HOST_OK);
         CHECK(emsar_write_ucompare(path, &r, &g, NQ, query, a, p, a, p, p, st, query, query) == EMSAR_HOST_OK);
         CHECK(emsar_write_ucompare(path, &r, &g, NT, NULL, a, p, a, p, p, st, query, query) == EMSAR_HOST_OK);
+        CHECK(emsar_write_uprofile(path, &r, &g, NQ, query, a, p, a, p, a, st, query, query) == EMSAR_HOST_OK);
+        CHECK(emsar_write_uprofile(path, &r, &g, NT, NULL, a, p, a, p, a, st, query, query) == EMSAR_HOST_OK);
         CHECK(emsar_write_presence(path, &r, NQ, query, fpkm, a, p, st, heir, a) == EMSAR_HOST_OK);
         CHECK(emsar_write_profile(path, &r, NQ, query, fpkm, a, p, a, st) == EMSAR_HOST_OK);
         for (int k = 0; k + NGENES <= NQ; k += NGENES) {           /* three genes at a time: the gene writers read n_genes entries */
@@ -59,6 +61,7 @@ static void writers(const char *dir) {
     CHECK(emsar_write_gcompare(path, &g, a, p, a, p, p, status, status, status) == EMSAR_HOST_ERR_IO);
     CHECK(emsar_write_ucompare(path, &r, &g, NQ, query, a, p, a, p, p, status, query, query) == EMSAR_HOST_ERR_IO);
     CHECK(emsar_write_gprofile(path, &g, a, p, a, p, p, status, status) == EMSAR_HOST_ERR_IO);
+    CHECK(emsar_write_uprofile(path, &r, &g, NQ, query, a, p, a, p, a, status, query, query) == EMSAR_HOST_ERR_IO);
     snprintf(path, sizeof path, "%s/host_writers.out", dir);
     remove(path);
     free(gmap); free(query); free(status); free(wild); free(heir); free(partner); free(a); free(p); free(fpkm); free(var);

@@ -1,6 +1,6 @@
 """Cost of the profile-likelihood intervals (emsar_hip_profile) on bench.py's time_to_mle segment problem; prints one JSON object.
 
-    python tools/profile_bench.py [--genes] [--rounds 3] [--level 0.95] [--max-iter 20000] [--max-evals 40] [--out FILE]
+    python tools/profile_bench.py [--genes | --usage] [--rounds 3] [--level 0.95] [--max-iter 20000] [--max-evals 40] [--out FILE]
 
 The problem (same seeds, 100 k transcripts in families) is uploaded and solved (the first solve finds and packs the sets); then every
 transcript's interval is computed, --rounds times, and the presence test is run on the same input in the same process.  Reported: wall
@@ -12,7 +12,13 @@ quadratic over the interval.
 genes in one call: after one warm-up call, --rounds calls; wall and device ms (baseline_ms + search_ms: HIP events) as best / median /
 worst over the rounds, genes per status, the searches of the genes that converged (two for TWO_SIDED, one for LOWER_ZERO; device and
 host), evaluations per search, the most parts, and next to them the two yardsticks from this run: emsar_hip_profile over all transcripts (above) and one solve (wall, best
-of --rounds).  A record, never a test threshold."""
+of --rounds).
+--usage: instead of all that, emsar_hip_profile_usage over every transcript of a family of two or more (the families as genes) in one call:
+the median of 5 calls after a warm-up call, wall and device ms (baseline_ms + search_ms: HIP events), transcripts per status, the limits
+searched, outer points per search, inner evaluations per outer point, and the yardsticks from the same run, each the median of 5 after a
+warm-up: emsar_hip_compare_usage on the same transcripts (against a Poisson redraw of the counts, seed 5, in a second context),
+emsar_hip_profile on the same transcripts and one solve.
+A record, never a test threshold."""
 import argparse
 import json
 import os
@@ -55,6 +61,50 @@ def genes_part(dev, a, solve, sizes, transcripts):
             "transcript_profile_device_ms": transcripts["baseline_ms"] + transcripts["drop_ms"] + transcripts["search_ms"]}
 
 
+def usage_part(a, solve, calls=5):
+    """--usage (module docstring)"""
+    from boot_bench import family_sizes, segment_problem
+    from emsar_amd import EmsarHip
+    n_tx, rp, ci, R, E = segment_problem()
+    sizes = family_sizes(n_tx)
+    gene_of = np.repeat(np.arange(len(sizes), dtype=np.int32), sizes)
+    q = np.flatnonzero(np.asarray(sizes)[gene_of] >= 2).astype(np.int32)
+
+    def timed(f):
+        f()                                                    # warm-up
+        runs = []
+        for _ in range(calls):
+            t0 = time.perf_counter()
+            r = f()
+            runs.append((time.perf_counter() - t0, r))
+        runs.sort(key=lambda x: x[0])
+        return runs[len(runs) // 2]
+    with EmsarHip(0) as dev, EmsarHip(0) as other:
+        for d, w in ((dev, R), (other, np.random.default_rng(5).poisson(R).astype(np.int32))):
+            d.upload_structure(n_tx, rp, ci)
+            d.upload_sample(w, E, None)
+            d.solve(**solve)                                   # finds and packs the sets, warms up
+        dev.set_gene_map(gene_of, len(sizes))
+        th, _ = dev.solve(**solve)
+        wall_u, r = timed(lambda: dev.profile_usage(q, level=a.level, max_evals=a.max_evals, **solve))
+        wall_c, c = timed(lambda: dev.compare_usage(other, q, **solve))
+        wall_p, p = timed(lambda: dev.profile(q, level=a.level, max_evals=a.max_evals, **solve))
+        wall_s, _ = timed(lambda: dev.solve(**solve))
+        unchanged = bool(dev.solve(**solve)[0].tobytes() == th.tobytes())
+    d, dc, dp = r["stats"].as_dict(), c["stats"].as_dict(), p["stats"].as_dict()
+    # the limits found by search, on the device or on the host: two for TWO_SIDED, one for LOWER_ZERO and UPPER_ONE; an UNCONVERGED
+    # transcript is counted with two, which is one too many where one of its limits lay at an end
+    limits = int(np.sum(np.isin(r["status"], (0, 4)) * 2 + np.isin(r["status"], (1, 6))))
+    return dict(call="profile_usage", n_genes=int(len(sizes)), n_query=int(len(q)), calls=calls, status=d["n_status"], items_launched=d["items_launched"],
+                wall_ms=1e3 * wall_u, device_ms=d["baseline_ms"] + d["search_ms"], baseline_ms=d["baseline_ms"], search_ms=d["search_ms"],
+                limits_searched=limits, unconverged=d["n_status"]["UNCONVERGED"], outer_per_search=float(r["outer_evals"].sum()) / max(1, limits),
+                outer_sum=d["outer_sum"], outer_max=d["outer_max"], inner_evals_per_outer_point=d["evals_sum"] / max(1, d["outer_sum"]),
+                evals_sum=d["evals_sum"], evals_max=d["evals_max"], passes_sum=d["passes_sum"], passes_max=d["passes_max"], parts_max=d["parts_max"],
+                min_raw_lambda=d["min_raw_lambda"], compare_usage_wall_ms=1e3 * wall_c, compare_usage_device_ms=dc["device_ms"],
+                profile_wall_ms=1e3 * wall_p, profile_device_ms=dp["baseline_ms"] + dp["drop_ms"] + dp["search_ms"], solve_wall_ms=1e3 * wall_s,
+                wall_over_compare_usage=wall_u / wall_c, wall_over_profile=wall_u / wall_p, solve_unchanged=unchanged)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
@@ -62,8 +112,18 @@ def main():
     ap.add_argument("--max-iter", type=int, default=20000)
     ap.add_argument("--max-evals", type=int, default=40)
     ap.add_argument("--genes", action="store_true")
+    ap.add_argument("--usage", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.usage:
+        out = usage_part(a, dict(max_iter=a.max_iter, tol=1e-10))
+        out.update(level=a.level, max_iter=a.max_iter, max_evals=a.max_evals)
+        txt = json.dumps(out, indent=1)
+        print(txt)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(txt + "\n")
+        return
     from boot_bench import family_sizes, segment_problem
     from emsar_amd import EmsarHip
     n_tx, rp, ci, R, E = segment_problem()
