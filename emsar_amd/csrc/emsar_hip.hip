@@ -40,6 +40,8 @@
 //                         (solve_set_scaled); ProfileStep: the search step kernel and host share; IllinoisBracket
 //   kernels_compare.hpp   k_compare_sets                         one workgroup searches one transcript's multiplier: per evaluation a set solve of each sample
 //                         (solve_set_scaled); CompareStep: the search step kernel and host share
+//   kernels_compare_groups.hpp  k_compare_groups_sets            one workgroup runs one common-value fit of a transcript across a subset
+//                         of K samples, two levels (groups_search, shared with the host)
 //   kernels_gene_parts.hpp      what the gene-level kernels share: the part lists, solve_gene_part (a set part solved with the members' den
 //                         edited; solve_one_set's DenEdit hook), eval_gene_side (one sample: its set parts, then its closed-form parts)
 //   kernels_compare_genes.hpp   k_compare_gene_sets              one workgroup searches one gene's multiplier: per evaluation every part of
@@ -61,6 +63,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <numeric>
 #include <string>
@@ -84,6 +87,7 @@
 #include "kernels_presence.hpp"
 #include "kernels_profile.hpp"
 #include "kernels_compare.hpp"
+#include "kernels_compare_groups.hpp"
 #include "kernels_gene_parts.hpp"
 #include "kernels_compare_genes.hpp"
 #include "kernels_profile_genes.hpp"
@@ -852,6 +856,7 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 #include "gene_parts.hpp"      // what the gene-level drivers share: GeneQueryMembers, GeneSideParts, GenePartLists (after compare.hpp)
 #include "compare_genes.hpp"   // the gene-level two-sample test and its entry points (after gene_parts.hpp; compare.hpp: compare_reduce)
 #include "profile_genes.hpp"   // the gene-level profile intervals and the gene presence test (after gene_parts.hpp; profile.hpp: profile_cut)
+#include "compare_groups.hpp"  // the K-sample test across replicate groups (after compare.hpp: side_ok; profile_genes.hpp: gene_presence_pvalue)
 #include "compare_usage.hpp"   // the two-sample test of isoform usage (after gene_parts.hpp; compare.hpp: compare_pvalue)
 #include "profile_usage.hpp"   // the profile intervals of isoform usage (after compare_usage.hpp; profile_genes.hpp: profile_params_ok)
 #include "asym.hpp"       //the asymptotic standard errors and their entry points (after fit.hpp: fit_ensure_csr, launch_gene_sums)

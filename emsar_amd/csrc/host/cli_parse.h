@@ -51,4 +51,45 @@ static int parse_device_list(const char *s, int *map, int *n) {
     }
     return *n == 0;
 }
+
+/* --compare-groups g0,g1,..: one group id per sample, whole numbers 0 .. 31, at most 33 are stored in out[33] (a 33rd tells the caller that
+ * there are too many); the list replaces what an earlier use of the option stored */
+static int parse_group_list(const char *s, int32_t *out, int *n) {
+    *n = 0;
+    for (;;) {
+        char *end; errno = 0;
+        const long v = strtol(s, &end, 10);
+        if (end == s || (*end && *end != ',') || errno || v < 0 || v > 31) return 1;
+        if (*n < 33) out[(*n)++] = (int32_t)v;
+        if (!*end) return 0;
+        s = end + 1;
+    }
+}
+
+/* --compare-sizes s0,s1,..: one size factor per sample, finite and positive, stored like the group ids */
+static int parse_size_list(const char *s, double *out, int *n) {
+    *n = 0;
+    for (;;) {
+        char *end; errno = 0;
+        const double v = strtod(s, &end);
+        if (end == s || (*end && *end != ',') || errno || !isfinite(v) || !(v > 0.0)) return 1;
+        if (*n < 33) out[(*n)++] = v;
+        if (!*end) return 0;
+        s = end + 1;
+    }
+}
+
+/* The groups of a K-sample job: n_groups ids for n_samples samples.  0, or the message of what is wrong: a length that is not the number
+ * of samples, fewer than two or more than 32 samples, an id that is not 0 .. G-1 without gaps (G = the largest id + 1: an empty group) */
+static const char *check_groups(int n_samples, int n_groups, const int32_t *group_of, int n_sizes) {
+    if (n_samples < 2) return "--compare-groups needs -M and at least two samples.";
+    if (n_samples > 32) return "--compare-groups takes at most 32 samples.";
+    if (n_groups != n_samples) return "--compare-groups wants one group id per sample.";
+    if (n_sizes && n_sizes != n_samples) return "--compare-sizes wants one size factor per sample.";
+    int32_t G = 0;
+    uint32_t seen = 0;
+    for (int k = 0; k < n_groups; k++) { seen |= 1u << group_of[k]; if (group_of[k] + 1 > G) G = group_of[k] + 1; }
+    if (seen != (G == 32 ? 0xffffffffu : (1u << G) - 1u)) return "--compare-groups: the group ids must be 0 .. G-1 with no group empty.";
+    return 0;
+}
 #endif

@@ -55,6 +55,13 @@
  * sample i >= 1 also writes <prefix>.<i>.gcompare: per gene, in the order of .gfpkm, the gene sums of FPKM in sample i and in sample 0, log2 of
  * their ratio, Lambda of H0: the gene's sum in i = r * its sum in 0 with the isoforms free in both samples, p, status, evaluations and parts
  * (emsar_hip_compare_genes); --compare-list filters transcripts only.  The other files do not change with it.
+ * --compare-groups g0,g1,.. (with -M; one group id per alignment file, 0 .. G-1, 2 to 32 samples) answers the question a run over many samples is
+ * made for, "did this isoform change between the conditions, and do the replicates of a condition agree": after every sample has been solved,
+ * ONE file <prefix>.groups holds, per transcript (or per transcript named in --compare-list FILE), the common FPKM of all samples and of each
+ * group, Lambda_between (the groups differ, replicates pooled inside the likelihood) and Lambda_within (the replicates of a group disagree)
+ * with their degrees of freedom and chi2 p-values, a status word, the outer points and the inner evaluations spent (emsar_hip_compare_groups
+ * with the solve's parameters on K contexts on the first worker's device).  --compare-sizes s0,s1,.. gives every sample a size factor.  The
+ * other files do not change with it.
  * --compare-usage (with -M, at least two samples and --g2t) answers "did this isoform's share of its gene change against sample 0" (an
  * isoform switch): every sample i >= 1 writes <prefix>.<i>.ucompare with, per transcript (or per transcript named in --compare-list FILE), its
  * gene, its share of the gene in sample i and in sample 0, the difference of their logits, the likelihood-ratio statistic Lambda of H0: equal
@@ -112,6 +119,9 @@ typedef struct {
     int compare_usage;                /* --compare-usage (needs --g2t): also a two-sample run, shares sample 0 with --compare */
     int32_t *cmp_q; int cmp_nq;       /* --compare-list FILE, as --presence-list */
     struct compare_ref *ref;          /* --compare: sample 0's solver inputs, shared by the workers */
+    int compare_groups, n_groups, n_sizes;   /* --compare-groups g0,.. [--compare-sizes s0,..]: the ids and factors as given (up to 33 are kept) */
+    int32_t group_of[33]; double group_size[33];
+    struct compare_ref *inputs;       /* --compare-groups: every sample's solver inputs [n_aln], each written by the worker that runs the sample */
     const emsar_genes *genes;         /* its gene map, read once by main() and shared read-only by the workers */
     /* what only main() reads: the options as given, before the index, the lists and the devices they name have been looked at */
     const char *strand; int multisample, gpus, device;
@@ -155,6 +165,16 @@ static void publish_ref(worker_arg *w, const emsar_rsh *r, const int32_t *R, con
     ref->R = cR; ref->E = cE; ref->den = cd; ref->ready = ok ? 1 : -1;
     pthread_cond_broadcast(w->cv);
     pthread_mutex_unlock(w->mu);
+}
+
+/* --compare-groups: sample i's inputs for the stage after the workers (ready stays 0 if it failed before it had them) */
+static void keep_inputs(const config *cfg, int i, const emsar_rsh *r, const int32_t *R, const double *E, const double *den) {
+    compare_ref *in = &cfg->inputs[i];
+    const size_t nr = (size_t)(r->n_rows > 0 ? r->n_rows : 1), nt = (size_t)(r->n_tx > 0 ? r->n_tx : 1);
+    in->R = (int32_t *)malloc(nr * 4); in->E = (double *)malloc(nr * 8); in->den = (double *)malloc(nt * 8);
+    if (!in->R || !in->E || !in->den) return;
+    memcpy(in->R, R, (size_t)r->n_rows * 4); memcpy(in->E, E, (size_t)r->n_rows * 8); memcpy(in->den, den, (size_t)r->n_tx * 8);
+    in->ready = 1;
 }
 
 /* emsar_aln_opts.collapse on the GPU (--device-collapse): the parse threads of a worker hand their read-level rows to a context
@@ -303,6 +323,7 @@ static int stage_solve(sample *s) {
     /* Invariant: with --compare or --compare-usage sample 0 publishes its inputs exactly once -- the arrays here, or, if it ends before
      * this line, the failure marker in run_sample() -- so that no other sample waits for them in vain. */
     if ((cfg->compare || cfg->compare_usage) && i == 0) { publish_ref(w, r, s->cnt->R, s->m->E_solver, s->den); s->published = 1; }
+    if (cfg->compare_groups) keep_inputs(cfg, i, r, s->cnt->R, s->m->E_solver, s->den);
     if ((rc = lib_call(s, "", emsar_hip_upload_sample(s->ctx, s->cnt->R, s->m->E_solver, s->den))) ||
         (rc = lib_call(s, "", emsar_hip_solve(s->ctx, &s->p, s->theta, &w->stats[i])))) return rc;
     for (int k = 0; k < cfg->n_round; k++) memcpy(s->rounds + (size_t)k * T, s->theta, T * 8);   /* deterministic solver: rounds coincide */
@@ -675,6 +696,46 @@ static void *worker_main(void *a) {
     return NULL;
 }
 
+/* K-sample test (--compare-groups), after every worker has joined: K contexts on `device` hold the samples' solver inputs, one call
+ * (emsar_hip_compare_groups with the solve's parameters) answers for all of them: <prefix>.groups */
+static int stage_groups(const config *cfg, const emsar_rsh *r, int device) {
+    const int K = cfg->n_aln;
+    const int32_t *query = cfg->cmp_q;
+    const size_t Q = query ? (size_t)cfg->cmp_nq : (size_t)r->n_tx;
+    int32_t G = 0;
+    for (int k = 0; k < K; k++) {
+        if (!cfg->inputs[k].ready) { fprintf(stderr, "compare-groups: sample %d gave no solver inputs\n", k); return EMSAR_HOST_ERR_IO; }
+        if (cfg->group_of[k] + 1 > G) G = cfg->group_of[k] + 1;
+    }
+    const emsar_em_params p = {.max_iter = cfg->max_iter, .accel = cfg->accel, .tol = cfg->tol, .set_mode = cfg->set_mode, .count_floor = cfg->count_floor,
+                               .zero_cut = cfg->zero_cut, .abs_step = cfg->abs_step};
+    emsar_hip_ctx *ctx[32] = {0};
+    double *v = (double *)slab((6 + (size_t)G) * Q, 8);
+    int32_t *iv = (int32_t *)slab(3 * Q, 4);
+    int rc = v && iv ? 0 : EMSAR_HOST_ERR_OOM;
+    for (int k = 0; k < K && !rc; k++) {
+        const compare_ref *in = &cfg->inputs[k];
+        if ((rc = emsar_hip_create(&ctx[k], device)) || (rc = emsar_hip_set_deterministic(ctx[k], !cfg->no_deterministic)) ||
+            (rc = emsar_hip_upload_structure(ctx[k], r->n_rows, r->n_tx, r->row_ptr, r->col_idx, EMSAR_LAYOUT_AUTO)) ||
+            (rc = emsar_hip_upload_sample(ctx[k], in->R, in->E, in->den)))
+            fprintf(stderr, "compare-groups: sample %d's context: %s (%s)\n", k, emsar_hip_strerror(rc), ctx[k] ? emsar_hip_last_error(ctx[k]) : "");
+    }
+    if (!rc) {
+        const emsar_groups_outputs o = {.theta_common = v, .lambda_between = v + Q, .p_between = v + 2 * Q, .lambda_within = v + 3 * Q, .p_within = v + 4 * Q,
+                                        .theta_group = v + 6 * Q, .status = iv, .outer = iv + Q, .evals = iv + 2 * Q};
+        char path[4096];
+        snprintf(path, sizeof path, "%s/%s.groups", cfg->outdir, cfg->prefix);
+        rc = emsar_hip_compare_groups(ctx, K, cfg->group_of, cfg->n_sizes ? cfg->group_size : NULL, &p, NULL, (int32_t)Q, query, &o, NULL);
+        if (rc) fprintf(stderr, "compare-groups: %s (%s)\n", emsar_hip_strerror(rc), emsar_hip_last_error(ctx[0]));
+        else if ((rc = emsar_write_groups(path, r, (int32_t)Q, query, K, cfg->group_of, cfg->n_sizes ? cfg->group_size : NULL, o.theta_common, o.theta_group,
+                                          o.lambda_between, o.p_between, o.lambda_within, o.p_within, o.status, o.outer, o.evals)))
+            fprintf(stderr, "can't write %s\n", path);
+    }
+    for (int k = 0; k < K; k++) emsar_hip_destroy(ctx[k]);
+    free(v); free(iv);
+    return rc;
+}
+
 static void usage(const char *a0) {
     fprintf(stderr,
             "Usage : %s <options> -I rshfile outdir outprefix alignmentfile|alignmentfilelist\n"
@@ -739,6 +800,12 @@ static void usage(const char *a0) {
             "                            connected sets and lone transcripts in one sample), the evaluations and the parts searched over\n"
             "      --compare-ratio <r>   with --compare: test theta_i = r * theta_0 (default 1; a fold change or a size factor)\n"
             "      --compare-list <file> with --compare or --compare-usage: only the transcripts named in the file, one name per line\n"
+            "      --compare-groups <g0,g1,..>  with -M and 2 to 32 samples: one group id (0 .. G-1) per alignment file; after all samples ONE file\n"
+            "                            <prefix>.groups: per transcript the common FPKM of all samples and of each group, Lambda_between (the groups\n"
+            "                            differ, replicates pooled inside the likelihood) and Lambda_within (the replicates of a group disagree), their\n"
+            "                            degrees of freedom and chi2 p-values, a status word (TESTED, ALL_ABSENT, OUTSIDE, NOT_RESIDENT, UNCONVERGED), outer\n"
+            "                            points and evaluations.  No over-dispersion is modelled: a large Lambda_within makes p_between anti-conservative\n"
+            "      --compare-sizes <s0,s1,..>   with --compare-groups: one positive size factor per sample (default 1); --compare-list filters it too\n"
             "      --compare-usage       with -M, at least two samples and --g2t: every sample i >= 1 also writes <prefix>.<i>.ucompare: per transcript its\n"
             "                            gene, its share of the gene in sample i and in sample 0, the difference of their logits, Lambda of H0: equal\n"
             "                            shares (an isoform switch otherwise), its chi2_1 p-value, a status word, outer points and evaluations\n"
@@ -798,6 +865,7 @@ static int parse_options(int argc, char **argv, config *cfg) {
         {"profile-evals", required_argument, 0, 1028},
         {"compare", no_argument, 0, 1029}, {"compare-ratio", required_argument, 0, 1030}, {"compare-list", required_argument, 0, 1031},
         {"compare-usage", no_argument, 0, 1040}, {"profile-usage", no_argument, 0, 1041},
+        {"compare-groups", required_argument, 0, 1042}, {"compare-sizes", required_argument, 0, 1043},
         {"maxfraglen", required_argument, 0, 'F'}, {"minfraglen", required_argument, 0, 'f'}, {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "vqPs:p:F:f:n:e:d:gMSBk:i:I:", lo, NULL)) != -1) {
@@ -857,6 +925,13 @@ static int parse_options(int argc, char **argv, config *cfg) {
             case 1041: cfg->profile_usage = 1; break;
             case 1030: cfg->compare_ratio = atof(optarg); cfg->compare_ratio_given = 1; break;
             case 1031: cfg->compare_list = optarg; break;
+            case 1042:
+                if (parse_group_list(optarg, cfg->group_of, &cfg->n_groups)) return bad("--compare-groups wants a comma-separated list of group ids (0 .. 31).");
+                cfg->compare_groups = 1;
+                break;
+            case 1043:
+                if (parse_size_list(optarg, cfg->group_size, &cfg->n_sizes)) return bad("--compare-sizes wants a comma-separated list of positive size factors.");
+                break;
             default: usage(argv[0]); return 1;
         }
     }
@@ -877,13 +952,16 @@ static int check_options(config *cfg, const char *a0) {
     if (cfg->profile_level_given && !(cfg->profile_level > 0.0 && cfg->profile_level < 1.0)) return bad("--profile-level must lie in (0, 1).");
     if (!cfg->profile_level_given) cfg->profile_level = 0.95;
     if (cfg->compare_ratio_given && !cfg->compare) return bad("--compare-ratio needs --compare.");
-    if (cfg->compare_list && !cfg->compare && !cfg->compare_usage) return bad("--compare-list needs --compare or --compare-usage.");
+    if (cfg->compare_list && !cfg->compare && !cfg->compare_usage && !cfg->compare_groups)
+        return bad("--compare-list needs --compare or --compare-usage.");
+    if (cfg->n_sizes && !cfg->compare_groups) return bad_usage("--compare-sizes needs --compare-groups.", a0);
     if (cfg->compare_usage && !cfg->g2t) return bad_usage("--compare-usage needs --g2t FILE.", a0);
     if (cfg->profile_usage && !cfg->g2t) return bad_usage("--profile-usage needs --g2t FILE.", a0);
     if (cfg->compare_ratio_given && !(cfg->compare_ratio > 0.0 && isfinite(cfg->compare_ratio))) return bad("--compare-ratio must be positive.");
     if (!cfg->compare_ratio_given) cfg->compare_ratio = 1.0;
     if (cfg->compare && !cfg->multisample) return bad_usage("--compare needs -M and at least two samples.", a0);
     if (cfg->compare_usage && !cfg->multisample) return bad_usage("--compare-usage needs -M and at least two samples.", a0);
+    if (cfg->compare_groups && !cfg->multisample) return bad_usage("--compare-groups needs -M and at least two samples.", a0);
     return 0;
 }
 
@@ -1020,6 +1098,11 @@ int main(int argc, char **argv) {
     if (read_sample_list(&cfg, argv[optind + 2])) return 1;
     if (cfg.compare && cfg.n_aln < 2) return bad_usage("--compare needs -M and at least two samples.", argv[0]);
     if (cfg.compare_usage && cfg.n_aln < 2) return bad_usage("--compare-usage needs -M and at least two samples.", argv[0]);
+    if (cfg.compare_groups) {
+        const char *wrong = check_groups(cfg.n_aln, cfg.n_groups, cfg.group_of, cfg.n_sizes);
+        if (wrong) return bad_usage(wrong, argv[0]);
+        if (!(cfg.inputs = (compare_ref *)calloc((size_t)cfg.n_aln, sizeof(compare_ref)))) return bad("out of memory");
+    }
     if (make_outdir(cfg.outdir)) return 1;
     emsar_rsh *rsh = read_index(&cfg);
     if (!rsh) return 1;
@@ -1074,13 +1157,16 @@ int main(int argc, char **argv) {
     pthread_mutex_unlock(&mu);
     worker_main(&wa[0]);
     for (int g = 1; g < n_workers; g++) pthread_join(th[g], NULL);
-    const double wall = now_s() - t0;
     int n_bad = 0;
     for (int i = 0; i < cfg.n_aln; i++) if (shared.status[i]) n_bad++;
+    if (cfg.compare_groups && !n_bad && stage_groups(&cfg, rsh, wa[0].device)) n_bad++;
+    const double wall = now_s() - t0;
     if (cfg.stats_json) write_stats_json(&cfg, &shared, n_workers, wall, n_bad);
     emsar_rsh_free(rsh);
     emsar_genes_free(genes);
     free(cfg.pres_q); free(cfg.prof_q); free(cfg.cmp_q); free(ref.R); free(ref.E); free(ref.den);
+    for (int i = 0; cfg.inputs && i < cfg.n_aln; i++) { free(cfg.inputs[i].R); free(cfg.inputs[i].E); free(cfg.inputs[i].den); }
+    free(cfg.inputs);
     for (int i = 0; i < cfg.n_aln; i++) free(cfg.aln[i]);
     free(cfg.aln); free(shared.status); free(shared.stats); free(shared.bstats); free(shared.sstats); free(shared.qstats); free(shared.parse_s);
     free(shared.model_s); free(shared.host_s); free(wa); free(th);

@@ -217,6 +217,15 @@ int emsar_write_ucompare(const char *path, const emsar_rsh *r, const emsar_genes
                          const double *usage_b, const double *dlogit, const double *lambda, const double *pvalue, const int32_t *status,
                          const int32_t *outer_evals, const int32_t *evals);
 
+/* .groups (emsar-hip -M --compare-groups; one file per job, <prefix>.groups): a "#" line (samples, the group of every sample, the size
+ * factors -- size NULL: all 1 --, the two degrees of freedom), a header, then one line per queried transcript, query as for .compare --
+ * transcript FPKM_common FPKM_g0 .. FPKM_g(G-1) Lambda_between df p_between Lambda_within df p_within status outer evals; G = the largest
+ * group id + 1, theta_group [n_query][G]; the arrays as emsar_hip_compare_groups returns them; numbers, p and values that are not finite
+ * as in .compare; status TESTED, ALL_ABSENT, OUTSIDE, NOT_RESIDENT or UNCONVERGED */
+int emsar_write_groups(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, int32_t n_samples, const int32_t *group_of,
+                       const double *size, const double *theta_common, const double *theta_group, const double *lambda_between, const double *p_between,
+                       const double *lambda_within, const double *p_within, const int32_t *status, const int32_t *outer, const int32_t *evals);
+
 /* .asym (emsar-hip --asymptotic): one line per transcript -- tid transcriptID FPKM sd_FPKM TPM sd_TPM status partner partner_corr, and
  * usage_sd when it is given (--g2t); the arrays are [n_tx] as emsar_hip_asymptotic returns them.  partner_corr = partner_cov /
  * sqrt(var_t * var_partner); "-" and nan where there is no partner.  sd values are written "%.6g", or the words inf / nan.

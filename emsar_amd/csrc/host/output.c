@@ -33,6 +33,9 @@
  *   .ucompare           per queried transcript: transcript gene usage usage_ref dlogit Lambda p status outer evals
  *   .uprofile           per queried transcript: transcript gene usage lower upper Lambda_zero Lambda_one status outer evals
  *                       in these four the numbers are "%lf", p is "%.6g" and a negative infinity is written "-inf"
+ *   .groups             "# samples=.. groups=g0,.. sizes=s0,.. df_between=.. df_within=..", a header, then per queried transcript:
+ *                       transcript FPKM_common FPKM_g0 .. Lambda_between df p_between Lambda_within df p_within status outer evals,
+ *                       numbers and p as in .compare
  * Column order of .fpkm is a contract: the reference's Perl utilities read columns 0,1,4,6 (util/FPKM2gFPKM.pl:19).
  */
 #include "emsar_host.h"
@@ -172,6 +175,7 @@ static const char *const interval_word[6] = {"TWO_SIDED", "LOWER_ZERO", "OUTSIDE
 static const char *const usage_interval_word[10] = {"TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE", "UPPER_ONE", "UNIT",
                                                     "UNDEFINED", "SINGLE"};
 static const char *const two_sample_word[8] = {"TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE", "UNDEFINED", "SINGLE"};
+static const char *const groups_word[5] = {"TESTED", "ALL_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED"};
 static const char *const asym_word[5] = {"ESTIMATED", "BOUNDARY", "UNIDENTIFIABLE", "TOO_LARGE", "INFEASIBLE"};
 
 static const char *status_word(const char *const *table, int n, int32_t v) { return v >= 0 && v < n ? table[v] : "?"; }
@@ -276,6 +280,34 @@ int emsar_write_ucompare(const char *path, const emsar_rsh *r, const emsar_genes
         fprintf(f, "%s\t%s\t", r->names[t], k >= 0 ? g->names[k] : "");
         put_test_columns(f, 5, v);
         fprintf(f, "\t%s\t%d\t%d\n", status_word(two_sample_word, 8, status[i]), outer_evals[i], evals[i]);
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+int emsar_write_groups(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, int32_t n_samples, const int32_t *group_of,
+                       const double *size, const double *theta_common, const double *theta_group, const double *lambda_between, const double *p_between,
+                       const double *lambda_within, const double *p_within, const int32_t *status, const int32_t *outer, const int32_t *evals) {
+    int32_t G = 0;
+    for (int32_t k = 0; k < n_samples; k++) if (group_of[k] + 1 > G) G = group_of[k] + 1;
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    fprintf(f, "# samples=%d groups=", n_samples);
+    for (int32_t k = 0; k < n_samples; k++) fprintf(f, "%s%d", k ? "," : "", group_of[k]);
+    fprintf(f, " sizes=");
+    for (int32_t k = 0; k < n_samples; k++) fprintf(f, "%s%g", k ? "," : "", size ? size[k] : 1.0);
+    fprintf(f, " df_between=%d df_within=%d\n", G - 1, n_samples - G);
+    fprintf(f, "transcript\tFPKM_common");
+    for (int32_t g = 0; g < G; g++) fprintf(f, "\tFPKM_g%d", g);
+    fprintf(f, "\tLambda_between\tdf\tp_between\tLambda_within\tdf\tp_within\tstatus\touter\tevals\n");
+    for (int32_t i = 0; i < n_query; i++) {
+        const int32_t t = query ? query[i] : i;
+        const double b[2] = {lambda_between[i], p_between[i]}, w[2] = {lambda_within[i], p_within[i]};
+        fprintf(f, "%s\t", r->names[t]);
+        put_value(f, "%lf", theta_common[i], 1);
+        for (int32_t g = 0; g < G; g++) { fputc('\t', f); put_value(f, "%lf", theta_group[(size_t)i * (size_t)G + (size_t)g], 1); }
+        fputc('\t', f); put_value(f, "%lf", b[0], 1); fprintf(f, "\t%d\t", G - 1); put_value(f, "%.6g", b[1], 1);
+        fputc('\t', f); put_value(f, "%lf", w[0], 1); fprintf(f, "\t%d\t", n_samples - G); put_value(f, "%.6g", w[1], 1);
+        fprintf(f, "\t%s\t%d\t%d\n", status_word(groups_word, 5, status[i]), outer[i], evals[i]);
     }
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }

@@ -31,6 +31,7 @@ SYMBOLS = [
     "emsar_hip_compare", "emsar_hip_compare_pvalue_host", "emsar_hip_compare_genes",
     "emsar_hip_profile_genes", "emsar_hip_gene_presence_pvalue_host",
     "emsar_hip_compare_usage", "emsar_hip_profile_usage",
+    "emsar_hip_compare_groups", "emsar_hip_compare_groups_pvalue_host",
     "emsar_hip_asymptotic", "emsar_hip_asymptotic_host",
 ]
 
@@ -52,6 +53,12 @@ COMPARE_GENE_OUTPUTS = ("lambda", "pvalue", "log2fc", "gene_a", "gene_b", "gene_
 USAGE_STATUS = ("TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE", "UNDEFINED", "SINGLE")
 USAGE_OUTPUTS = ("lambda", "raw_lambda", "pvalue", "usage_a", "usage_b", "usage_null", "dlogit", "slope")
 USAGE_COUNTS = ("status", "outer_evals", "evals", "parts")
+
+# status of a transcript in the K-sample test across replicate groups (include/emsar_hip.h "K-sample test"), by value
+GROUPS_STATUS = ("TESTED", "ALL_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED")
+GROUPS_OUTPUTS = ("lambda_between", "p_between", "lambda_within", "p_within", "raw_between", "raw_within", "theta_common", "slope")
+GROUPS_COUNTS = ("status", "outer", "evals")
+GROUPS_MAX = 32
 
 # status of a gene's profile-likelihood interval (include/emsar_hip.h "gene-level profile intervals"), by value
 PROFILE_GENE_STATUS = PROFILE_STATUS + ("TOO_LARGE",)
@@ -231,6 +238,27 @@ class UsageStats(C.Structure):
         return d
 
 
+class GroupsParams(C.Structure):
+    _fields_ = [("dev_tol", C.c_double), ("max_evals", C.c_int32), ("max_outer", C.c_int32)]
+
+
+class GroupsOutputs(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in GROUPS_OUTPUTS + ("theta_group", "theta_hat")] + \
+               [(k, C.POINTER(C.c_int32)) for k in GROUPS_COUNTS]
+
+
+class GroupsStats(C.Structure):
+    _fields_ = [("n_status", C.c_int64 * 5), ("items_launched", C.c_int64), ("evals_sum", C.c_int64), ("passes_sum", C.c_int64),
+                ("outer_sum", C.c_int64), ("evals_max", C.c_int32), ("passes_max", C.c_int32), ("outer_max", C.c_int32),
+                ("reserved0", C.c_int32), ("df_between", C.c_int32), ("df_within", C.c_int32), ("min_raw_lambda", C.c_double),
+                ("device_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["n_status"] = dict(zip(GROUPS_STATUS, d["n_status"]))
+        return d
+
+
 class ProfileGeneOutputs(C.Structure):
     _fields_ = [(k, C.POINTER(C.c_double)) for k in ("lower", "upper", "dev_lower", "dev_upper", "lambda_", "pvalue", "gene_hat")] + \
                [(k, C.POINTER(C.c_int32)) for k in ("status", "evals", "parts", "members")]
@@ -373,6 +401,9 @@ def load_library():
                                           C.POINTER(CompareGeneStats)]
     L.emsar_hip_compare_usage.argtypes = [vp, vp, C.POINTER(EmParams), C.POINTER(UsageParams), C.c_int32, i32p, C.POINTER(UsageOutputs),
                                           C.POINTER(UsageStats)]
+    L.emsar_hip_compare_groups.argtypes = [C.POINTER(vp), C.c_int32, i32p, f64p, C.POINTER(EmParams), C.POINTER(GroupsParams), C.c_int32, i32p,
+                                           C.POINTER(GroupsOutputs), C.POINTER(GroupsStats)]
+    L.emsar_hip_compare_groups_pvalue_host.argtypes = [C.c_int64, f64p, i32p, f64p]
     L.emsar_hip_profile_usage.argtypes = [vp, C.POINTER(EmParams), C.POINTER(ProfileParams), C.c_int32, i32p, C.POINTER(ProfileUsageOutputs),
                                           C.POINTER(ProfileUsageStats)]
     L.emsar_hip_profile_genes.argtypes = [vp, C.POINTER(EmParams), C.POINTER(ProfileParams), C.c_int32, i32p, C.POINTER(ProfileGeneOutputs),
@@ -628,6 +659,52 @@ def debug_compare_genes_closed(u_a, den_a, u_b, den_b, ratio=1.0, dev_tol=0.0, m
         raise EmsarHipError(rc, "debug_compare_genes_closed")
     out = dict(zip(COMPARE_GENE_OUTPUTS, list(vals)))
     out.update(status=status.value, evals=evals.value)
+    return out
+
+
+def _groups_layout(groups, sizes):
+    g = np.ascontiguousarray(np.asarray(groups, dtype=np.int32).reshape(-1))
+    s = None if sizes is None else np.ascontiguousarray(np.asarray(sizes, dtype=np.float64).reshape(-1))
+    if s is not None and len(s) != len(g):
+        raise ValueError("sizes must hold one factor per sample")
+    n_groups = int(g.max()) + 1 if len(g) and 0 <= int(g.max()) < GROUPS_MAX else 1
+    return g, s, n_groups
+
+
+def compare_groups_pvalue_host(lam, df):
+    """Host-only: P(chi2_df > Lambda), the K-sample test's p-value (include/emsar_hip.h "K-sample test"): 1 for Lambda <= 0, 0 for +inf,
+    NaN for NaN or df < 0; df 0 is the point mass at 0 (1 for Lambda <= 0, 0 above).  Arrays of equal length, or a scalar df for all;
+    no GPU needed."""
+    x = np.ascontiguousarray(np.atleast_1d(np.asarray(lam, dtype=np.float64)).reshape(-1))
+    k = np.ascontiguousarray(np.broadcast_to(np.asarray(df, dtype=np.int32), x.shape))
+    out = np.zeros(max(x.size, 1))
+    rc = load_library().emsar_hip_compare_groups_pvalue_host(x.size, _p(x, C.c_double), _p(k, C.c_int32), _p(out, C.c_double))
+    if rc != 0:
+        raise EmsarHipError(rc, "compare_groups_pvalue_host")
+    return out[:x.size]
+
+
+def debug_compare_groups_closed(u, den, groups, sizes=None, dev_tol=0.0, max_evals=0, max_outer=0):
+    """Host-only diagnostic: what compare_groups() gives a transcript that is a one-transcript component in each of the K samples
+    (u[k] reads, den[k]): the two-level searches as the host runs them for such transcripts (no GPU needed).  Returns a dict keyed like
+    compare_groups()'s arrays: scalars, theta_group [G] and theta_hat [K]."""
+    f = load_library().emsar_hip_debug_compare_groups_closed       # not declared in the header: bound here, not in load_library
+    f.restype = C.c_int
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    f.argtypes = [C.c_int32, dp, dp, ip, dp, C.POINTER(GroupsParams), dp, dp, dp, ip]
+    uu, dd = (np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1)) for x in (u, den))
+    g, s, n_groups = _groups_layout(groups, sizes)
+    if not (len(uu) == len(dd) == len(g)):
+        raise ValueError("u, den and groups must have the same length")
+    gp, vals, counts = GroupsParams(float(dev_tol), int(max_evals), int(max_outer)), (C.c_double * 8)(), (C.c_int32 * 3)()
+    tg, th = np.zeros(n_groups), np.zeros(max(len(uu), 1))
+    rc = f(len(uu), _p(uu, C.c_double), _p(dd, C.c_double), _p(g, C.c_int32), _p(s, C.c_double), C.byref(gp), vals, _p(tg, C.c_double),
+           _p(th, C.c_double), counts)
+    if rc != 0:
+        raise EmsarHipError(rc, "debug_compare_groups_closed")
+    out = dict(zip(GROUPS_OUTPUTS, list(vals)))
+    out.update(zip(GROUPS_COUNTS, list(counts)))
+    out.update(theta_group=tg, theta_hat=th[:len(uu)])
     return out
 
 
@@ -1051,6 +1128,38 @@ class EmsarHip:
         st = UsageStats()
         self._chk(self._L.emsar_hip_compare_usage(self._h, getattr(other, "_h", None), C.byref(p), C.byref(up), nq, _p(q, C.c_int32), C.byref(o),
                                                   C.byref(st)), "compare_usage")
+        out = {k: v[:nq] for k, v in res.items()}
+        out["stats"] = st
+        return out
+
+    def compare_groups(self, others, groups, sizes=None, query=None, dev_tol=0.0, max_evals=0, max_outer=0, max_iter=100000, accel=1, tol=1e-10,
+                       abs_floor=1e-6, check_every=8, count_floor=0.0, set_mode=0, zero_cut=0.0, abs_step=0.0, newton_after=0):
+        """K-sample test across replicate groups (include/emsar_hip.h "K-sample test"): this context holds sample 0, `others` -- a list of
+        contexts on the same device with the same structure -- samples 1 .. K-1; groups[k] in 0 .. G-1 names sample k's group, sizes[k] > 0
+        its size factor (None: all 1).  Lambda_between tests "the groups differ" with the replicates of a group pooled inside the
+        likelihood, Lambda_within "the replicates of a group disagree".  query: tids in any order, repeats allowed, None = all
+        transcripts; dev_tol, max_evals, max_outer 0 = the defaults (1e-4, 40, 12); the solver parameters are those of solve().  Returns
+        a dict of arrays in query order: lambda_between, p_between, lambda_within, p_within, raw_between, raw_within, theta_common, slope,
+        theta_group [n, G], theta_hat [n, K], status (index into GROUPS_STATUS), outer, evals, and stats.  After upload_sample on every
+        context; all are left as they were."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        gp = GroupsParams(float(dev_tol), int(max_evals), int(max_outer))
+        ctxs = [self] + list(others)
+        g, s, n_groups = _groups_layout(groups, sizes)
+        if len(g) != len(ctxs):
+            raise ValueError("groups must hold one id per sample")
+        handles = (C.c_void_p * len(ctxs))(*[getattr(c, "_h", None) for c in ctxs])
+        q = None if query is None else np.ascontiguousarray(np.asarray(query, dtype=np.int32).reshape(-1))
+        nq = self.n_tx if q is None else len(q)
+        res = {k: np.zeros(max(nq, 1)) for k in GROUPS_OUTPUTS}
+        res["theta_group"] = np.zeros((max(nq, 1), n_groups))
+        res["theta_hat"] = np.zeros((max(nq, 1), len(ctxs)))
+        res.update({k: np.zeros(max(nq, 1), dtype=np.int32) for k in GROUPS_COUNTS})
+        o = GroupsOutputs(*[_p(res[k], C.c_double) for k in GROUPS_OUTPUTS + ("theta_group", "theta_hat")],
+                          *[_p(res[k], C.c_int32) for k in GROUPS_COUNTS])
+        st = GroupsStats()
+        self._chk(self._L.emsar_hip_compare_groups(handles, len(ctxs), _p(g, C.c_int32), _p(s, C.c_double), C.byref(p), C.byref(gp), nq,
+                                                   _p(q, C.c_int32), C.byref(o), C.byref(st)), "compare_groups")
         out = {k: v[:nq] for k, v in res.items()}
         out["stats"] = st
         return out

@@ -97,6 +97,7 @@ def lib():
         L.emsar_write_compare.argtypes = [C.c_char_p, C.POINTER(Rsh), C.c_int32, i32p] + [f64p] * 5 + [i32p, i32p]
         L.emsar_write_gcompare.argtypes = [C.c_char_p, C.POINTER(Genes)] + [f64p] * 5 + [i32p, i32p, i32p]
         L.emsar_write_ucompare.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Genes), C.c_int32, i32p] + [f64p] * 5 + [i32p, i32p, i32p]
+        L.emsar_write_groups.argtypes = [C.c_char_p, C.POINTER(Rsh), C.c_int32, i32p, C.c_int32, i32p] + [f64p] * 7 + [i32p, i32p, i32p]
         L.emsar_write_uprofile.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Genes), C.c_int32, i32p] + [f64p] * 5 + [i32p, i32p, i32p]
         L.emsar_write_asym.argtypes = [C.c_char_p, C.POINTER(Rsh)] + [f64p] * 5 + [i32p, i32p, f64p, f64p]
         L.emsar_write_gasym.argtypes = [C.c_char_p, C.POINTER(Genes), f64p, f64p, i32p]
@@ -227,6 +228,24 @@ def write_ucompare(path, tx_names, gene_names, gene_of_tx, usage_a, usage_b, dlo
                                     *([_dp(x) for x in a] + [_ip(x) for x in i]))
     if rc != 0:
         raise HostError("write_ucompare rc=%d" % rc)
+
+
+def write_groups(path, tx_names, groups, sizes, theta_common, theta_group, lambda_between, p_between, lambda_within, p_within, status, outer, evals,
+                 query=None):
+    """.groups (emsar_write_groups): transcripts tx_names; groups (one id per sample), sizes (None = all 1) and the arrays as
+    EmsarHip.compare_groups takes and returns them for query (tids, None = all transcripts in order); theta_group [n, G]."""
+    n_tx = len(tx_names)
+    names = (C.c_char_p * max(n_tx, 1))(*[s.encode() for s in tx_names])
+    r = Rsh(n_tx=n_tx, names=C.cast(names, C.POINTER(C.c_char_p)))
+    q = None if query is None else np.ascontiguousarray(query, dtype=np.int32)
+    g = np.ascontiguousarray(groups, dtype=np.int32)
+    s = None if sizes is None else np.ascontiguousarray(sizes, dtype=np.float64)
+    a = [np.ascontiguousarray(x, dtype=np.float64) for x in (theta_common, theta_group, lambda_between, p_between, lambda_within, p_within)]
+    i = [np.ascontiguousarray(x, dtype=np.int32) for x in (status, outer, evals)]
+    rc = lib().emsar_write_groups(path.encode(), C.byref(r), n_tx if q is None else len(q), None if q is None else _ip(q), len(g), _ip(g),
+                                  None if s is None else _dp(s), *([_dp(x) for x in a] + [_ip(x) for x in i]))
+    if rc != 0:
+        raise HostError("write_groups rc=%d" % rc)
 
 
 def write_uprofile(path, tx_names, gene_names, gene_of_tx, usage, lower, upper, lambda_zero, lambda_one, status, outer_evals, evals, query=None):

@@ -917,6 +917,98 @@ int emsar_hip_profile_usage(emsar_hip_ctx *ctx, const emsar_em_params *p, const 
                             const int32_t *query_tids /* NULL = all transcripts */, const emsar_profile_usage_outputs *out /* or NULL */,
                             emsar_profile_usage_stats *stats /* or NULL */);
 
+/* ---- K-sample test across replicate groups: did a transcript change between conditions? -----------
+ * Many samples over one index are quantified to compare CONDITIONS, each with replicates, or the points of a time course.  Pairwise
+ * Lambdas of emsar_hip_compare cannot be put together for that: they share a sample and are not independent, and replicates cannot be
+ * pooled from outside the likelihood.  Here K contexts (2 <= K <= EMSAR_COMPARE_GROUPS_MAX) on one device hold one structure (checked
+ * as emsar_hip_compare checks it) and each its own sample; group_of[k] in 0 .. G-1 names sample k's group, every group non-empty; the
+ * size factors s_k > 0 (size NULL: all 1) play the role of emsar_hip_compare's ratio.  F^k is sample k's F_s as the presence test
+ * defines it; t's packed set may differ from sample to sample and lie in another size class.  For transcript t and a subset S of the
+ * samples, the COMMON-VALUE FIT is
+ *     C(S)         = the maximum of sum_{k in S} F^k under theta_t^k = s_k x for every k in S, over x >= 0 and everything else
+ *                  = max_x sum_{k in S} P_k(s_k x),  P_k(y) = max {F^k : theta_t^k = y};  C({k}) = F_hat^k, the free fit
+ *     Lambda_between = 2 (sum_g C(S_g) - C(all)),         df_between = G - 1: the conditions differ, replicates pooled inside the likelihood
+ *     Lambda_within  = 2 (sum_k F_hat^k - sum_g C(S_g)),  df_within = K - G:  the replicates of a condition disagree with each other
+ *     p_*          = P(chi2_df > Lambda_*), the tail of emsar_hip_gene_presence_pvalue_host; df 0: 1 for Lambda <= 0.  CONSERVATIVE WHERE
+ *                  AN ESTIMATE SITS ON THE BOUNDARY, as for emsar_hip_compare.  THE POISSON LIKELIHOOD HAS NO OVER-DISPERSION TERM: for
+ *                  biological replicates Lambda_within will often be large -- that is why it is reported next to Lambda_between --, AND
+ *                  p_between IS THEN ANTI-CONSERVATIVE.  No dispersion model is fitted.
+ *                  G = K tests "any difference among the K samples" (Lambda_within 0, df 0); G = 1 swaps the roles; K = 2, G = 2,
+ *                  s = (r, 1) is emsar_hip_compare's statistic at ratio r, reached by another search.
+ *     inner level  one sample k at a target y = s_k x > 0: the maximiser of F^k - lambda theta_t is the set problem with den_t + lambda
+ *                  in LDS, F summed with the ORIGINAL den_t (the path of emsar_hip_compare and of the profile intervals).  The gap
+ *                  g(lambda) = theta_t(lambda) - y falls in lambda in (-den_t, inf); the dual D(lambda) = F - lambda g >= P_k(y) is convex
+ *                  with slope -g, equal to P_k(y) at the root, and dP_k/dy = lambda there.  The side is the sign of theta_hat^k - y
+ *                  and needs no solve.  Where t must grow den' = den_t (1 - v); where it must shrink den' = den_t / (1 - v), unbounded
+ *                  above, v -> 1 the drop solve.  emsar_hip_compare's search runs on h = g / (theta_t + y) in v in [0, 1), h(1) = -+1
+ *                  known without a solve.  It stops when 2 |lambda g| <= dev_tol at an evaluation BEYOND the root (g has changed sign
+ *                  since lambda = 0: there |lambda - root| <= |lambda|), when 2 |g| * (the width of the bracket in lambda) <= dev_tol
+ *                  (the shrinking side has no finite end: the rule waits for a bracket whose upper end is an evaluation), or after
+ *                  max_evals evaluations; both rules bound D - P_k(y) by dev_tol / 2.  The search leaves D at its last evaluation and,
+ *                  as the slope dP_k/dy, the multiplier of the bracket's next Illinois point (an estimate of the root whose error is
+ *                  of second order in the bracket).  A one-transcript component is the closed form of emsar_hip_compare.
+ *     outer level  sum_k P_k(s_k x) is concave in x with slope Gs(x) = sum_k s_k lambda_k(x).  At x_lo = min_k theta_hat^k / s_k no
+ *                  sample has to rise above its estimate: every lambda_k >= 0 and Gs >= 0; at x_hi = max_k theta_hat^k / s_k every
+ *                  lambda_k <= 0.  So the signs at the two ends are known without an evaluation.  Illinois steps on
+ *                  h = Gs / sum_k |s_k lambda_k| over (x_lo, x_hi); every evaluated x lies strictly inside, so a target is never 0.
+ *                  Outer point 0 is lambda = 0 in every sample and gives theta_hat^k and F_hat^k from the code path of every later
+ *                  evaluation; if all theta_hat^k / s_k are equal the search ends there with C = sum F_hat and outer = 1.  It stops
+ *                  when 2 |Gs| (x_hi - x_lo) <= dev_tol or after max_outer points, point 0 counted (at least one point of the null is
+ *                  evaluated whatever max_outer says).  C(S) is the largest sum of the samples' dual values among the outer points,
+ *                  x_S that point.
+ *     cost         per transcript one search for all samples and one per group of two or more (a single group is the all-samples
+ *                  search itself); one workgroup runs one search, the samples in ascending index: at most
+ *                  max(max_outer, 2) * |S| * max_evals * max_iter passes.  A transcript that is a one-transcript component in every
+ *                  sample is searched on the host by the same code and nothing is launched for it.
+ *     outputs      lambda_between, lambda_within (clamped at 0), raw_between, raw_within (before clamping), p_between, p_within;
+ *                  theta_common = x of C(all), on the scale of size 1; theta_group[i][g] = x of C(S_g) (theta_hat^k / s_k for a group
+ *                  of one); theta_hat[i][k]; slope = the outer stopping quantity of the all-samples search, outer = its outer points;
+ *                  evals = the inner evaluations of all the transcript's searches.  Each Lambda is computed from the deficits
+ *                  sum_{k in S} F_hat^k - C(S), exactly 0 for a search that ended at outer point 0.
+ * status, per transcript:
+ *     TESTED        outputs as above
+ *     ALL_ABSENT    theta_hat_t is exactly 0 in every sample: both Lambdas 0, p 1
+ *     OUTSIDE       den_t == 0 in any sample.  Every numeric output NaN, the counters 0
+ *     NOT_RESIDENT  as in emsar_hip_compare, in any sample.  Every numeric output NaN, the counters 0
+ *     UNCONVERGED   values are given, but a solve, an inner search or an outer search hit its cap
+ * Outputs are indexed by query position (by tid when query_tids is NULL; n_query is then ignored); repeats and any order are allowed.  A
+ * transcript's result depends on its K sets, itself, the groups and sizes, p and gp alone -- not on what else is asked, the batch, the
+ * layout, MERGE_ROWS or the library's numbering.  All contexts are left as they were.  ERR_STATE when any context is before
+ * upload_sample; ERR_ARG for a NULL context, a context given twice, different devices or structures, K outside 2 .. 32, a group id
+ * outside 0 .. G-1 or an empty group (G = the largest id + 1), a size that is not finite and positive, a tid outside 0 .. n_tx-1,
+ * n_query < 0, a non-finite dev_tol and the parameters solve rejects; ERR_NUMERIC for a non-finite F at lambda = 0.
+ * EMSAR_HIP_GROUPS_BATCH = items per launch and class (a testing aid; the bits do not change).  compare_groups_pvalue_host:
+ * P(chi2_df > Lambda) per element, df 0: 1 for Lambda <= 0 and 0 above; NaN for NaN or df < 0; no HIP call. */
+#define EMSAR_COMPARE_GROUPS_MAX 32
+enum {
+    EMSAR_GROUPS_TESTED = 0, EMSAR_GROUPS_ALL_ABSENT = 1, EMSAR_GROUPS_OUTSIDE = 2, EMSAR_GROUPS_NOT_RESIDENT = 3, EMSAR_GROUPS_UNCONVERGED = 4
+};
+typedef struct { double dev_tol; int32_t max_evals, max_outer; } emsar_groups_params;  /* NULL or <= 0: 1e-4 (both levels), 40, 12 */
+typedef struct {
+    double  *lambda_between, *p_between, *lambda_within, *p_within, *raw_between, *raw_within, *theta_common, *slope;  /* [n_query]; may each be NULL */
+    double  *theta_group;         /* [n_query][G] */
+    double  *theta_hat;           /* [n_query][K] */
+    int32_t *status, *outer, *evals;                                        /* [n_query] EMSAR_GROUPS_*; outer points; inner evaluations */
+} emsar_groups_outputs;
+typedef struct {
+    int64_t n_status[5];          /* distinct queried transcripts per status */
+    int64_t items_launched;       /* workgroups: one search each */
+    int64_t evals_sum;            /* inner evaluations summed over the searches on the device */
+    int64_t passes_sum;           /* passes summed over their solves, every sample */
+    int64_t outer_sum;            /* outer points summed over the searches on the device */
+    int32_t evals_max, passes_max; /* the search with the most inner evaluations / the most passes */
+    int32_t outer_max, reserved0; /* the search with the most outer points */
+    int32_t df_between, df_within; /* G - 1, K - G */
+    double  min_raw_lambda;       /* the most negative of both Lambdas before clamping, 0 if none was negative */
+    double  device_ms;            /* device time of the searches (HIP events) */
+    double  total_ms;             /* wall time of the call, a first call's set building included */
+} emsar_groups_stats;
+int emsar_hip_compare_groups(emsar_hip_ctx *const *ctx /* [n_samples] */, int32_t n_samples, const int32_t *group_of /* [n_samples] */,
+                             const double *size /* [n_samples] or NULL */, const emsar_em_params *p, const emsar_groups_params *gp /* or NULL */,
+                             int32_t n_query, const int32_t *query_tids /* NULL = all transcripts */, const emsar_groups_outputs *out /* or NULL */,
+                             emsar_groups_stats *stats /* or NULL */);
+int emsar_hip_compare_groups_pvalue_host(int64_t n, const double *lambda, const int32_t *df, double *p_out);
+
 /* ---- asymptotic standard errors: the inverse of the observed information at the MLE ---------------
  * How sure is theta_t, without resampling?  For a theta that maximises the likelihood of the current sample, the observed information
  * of the ACTIVE transcripts is J_ij = sum_c m_ci m_cj R_c / S_c^2 (m_ci = how often i stands in row c); its inverse is the asymptotic

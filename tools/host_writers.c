@@ -1,4 +1,4 @@
-/* host_writers.c -- the writers of the test and interval files (.compare, .gcompare, .ucompare, .gprofile, .uprofile and their neighbours
+/* host_writers.c -- the writers of the test and interval files (.compare, .gcompare, .ucompare, .gprofile, .uprofile, .groups and their neighbours
  * .presence, .profile, .asym, .gasym; output.c) and the driver's argument parsers (cli_parse.h) on the inputs of their CPU tests, as a plain program to
  * put under the sanitizers:
  *   gcc -O1 -g -std=c11 -D_POSIX_C_SOURCE=200809L -fsanitize=address,undefined -fno-sanitize-recover=all -Iemsar_amd/csrc/host \
@@ -44,6 +44,16 @@ static void writers(const char *dir) {
         CHECK(emsar_write_ucompare(path, &r, &g, NT, NULL, a, p, a, p, p, st, query, query) == EMSAR_HOST_OK);
         CHECK(emsar_write_uprofile(path, &r, &g, NQ, query, a, p, a, p, a, st, query, query) == EMSAR_HOST_OK);
         CHECK(emsar_write_uprofile(path, &r, &g, NT, NULL, a, p, a, p, a, st, query, query) == EMSAR_HOST_OK);
+        {                                                           /* .groups: three samples in two groups, theta_group [NQ][2] */
+            const int32_t group_v[3] = {0, 1, 0};
+            const double size_v[3] = {1.0, 0.5, 2.0};
+            int32_t *group_of = ints(3, group_v);
+            double *size = doubles(3, size_v), *tg = (double *)malloc(sizeof(double) * 2 * NQ);
+            for (int k = 0; k < 2 * NQ; k++) tg[k] = a_v[k % NQ];
+            CHECK(emsar_write_groups(path, &r, NQ, query, 3, group_of, size, a, tg, a, p, a, p, st, query, query) == EMSAR_HOST_OK);
+            CHECK(emsar_write_groups(path, &r, NT, NULL, 3, group_of, NULL, a, tg, a, p, a, p, st, query, query) == EMSAR_HOST_OK);
+            free(group_of); free(size); free(tg);
+        }
         CHECK(emsar_write_presence(path, &r, NQ, query, fpkm, a, p, st, heir, a) == EMSAR_HOST_OK);
         CHECK(emsar_write_profile(path, &r, NQ, query, fpkm, a, p, a, st) == EMSAR_HOST_OK);
         for (int k = 0; k + NGENES <= NQ; k += NGENES) {           /* three genes at a time: the gene writers read n_genes entries */
@@ -101,6 +111,24 @@ static void parsers(void) {
     n = 0;
     CHECK(parse_device_list(d65, map, &n) == 0 && n == 64 && map[63] == 1023);
     free(l64); free(l65); free(d64); free(d65);
+    static const char *const bad_groups[] = {"", "x", "0,x", "0,", ",0", "0,,1", "-1", "0,-1", "32", "99999999999999999999", "0.5"};
+    static const char *const bad_sizes[] = {"", "x", "1,x", "1,", ",1", "0", "1,0", "-1", "nan", "inf", "1e999"};
+    int32_t ids[33];
+    double sizes[33];
+    for (size_t k = 0; k < sizeof bad_groups / sizeof *bad_groups; k++) CHECK(parse_group_list(bad_groups[k], ids, &n) == 1);
+    for (size_t k = 0; k < sizeof bad_sizes / sizeof *bad_sizes; k++) CHECK(parse_size_list(bad_sizes[k], sizes, &n) == 1);
+    char *g32 = repeated("0", 32), *g40 = repeated("31", 40), *s40 = repeated("0.5", 40);
+    CHECK(parse_group_list("0,0,1", ids, &n) == 0 && n == 3 && ids[2] == 1 && parse_group_list(g32, ids, &n) == 0 && n == 32);
+    CHECK(parse_group_list(g40, ids, &n) == 0 && n == 33 && ids[32] == 31);                   /* what follows the 33rd entry is not stored */
+    CHECK(parse_size_list("1,0.5,1e-300", sizes, &n) == 0 && n == 3 && sizes[1] == 0.5 && parse_size_list(s40, sizes, &n) == 0 && n == 33);
+    const int32_t g001[3] = {0, 0, 1}, g002[3] = {0, 0, 2}, g111[3] = {1, 1, 1};
+    CHECK(check_groups(3, 3, g001, 0) == 0 && check_groups(3, 3, g001, 3) == 0 && check_groups(3, 3, g001, 2) != 0);
+    CHECK(check_groups(3, 3, g002, 0) != 0 && check_groups(3, 3, g111, 0) != 0 && check_groups(2, 3, g001, 0) != 0 && check_groups(1, 1, g001, 0) != 0);
+    parse_group_list(g40, ids, &n);
+    CHECK(check_groups(33, n, ids, 0) != 0 && check_groups(40, n, ids, 0) != 0);
+    for (int k = 0; k < 32; k++) ids[k] = k;
+    CHECK(check_groups(32, 32, ids, 0) == 0);
+    free(g32); free(g40); free(s40);
 }
 
 int main(int argc, char **argv) {
