@@ -87,21 +87,12 @@ inline bool groups_reduce(const GroupsLayout &L, const GroupRec &all, const Grou
     return true;
 }
 
-// K one-transcript components as groups_search's samples: compare_closed_form as the evaluation
-struct GroupClosedSamples {
-    const double *u, *den_, *size_;
-    double th[kGroupsMax], Fh[kGroupsMax];
-    double size(int k) const { return size_[k]; }
-    double den(int k) const { return den_[k]; }
-    double hat(int k) const { return th[k]; }
-    void put_hat(int k, double x, double F) { th[k] = x; Fh[k] = F; }
-    void eval(int k, double scale, double &x, double &F) const { compare_closed_form(u[k], den_[k], scale, x, F); }
-};
-// The searches of k_compare_groups_sets on a transcript that is a one-transcript component in every sample (u[k] reads, den[k]), and
-// their reduction: what the host does for such transcripts
-inline bool groups_closed_transcript(const GroupsLayout &L, const double *u, const double *den, const GroupSearchParams &Q, GroupsResult &o,
-                                     double *theta_group, double *theta_hat) {
-    GroupClosedSamples E{u, den, L.size.data(), {}, {}};
+// Every search of one transcript or gene on the host, and their reduction: the all-samples search and one per group of two or more,
+// each on a copy of E0 -- samples that keep th[k], Fh[k] of point 0 (put_hat) and evaluate without the device
+template <class Samples>
+inline bool groups_host_searches(const GroupsLayout &L, const Samples &E0, const GroupSearchParams &Q, GroupsResult &o, double *theta_group,
+                                 double *theta_hat) {
+    Samples E = E0;
     const GroupRec all = groups_search(L.K, L.all, Q, E).record(0, 1, 0);
     double F_hat[kGroupsMax];
     for (int k = 0; k < L.K; k++) { theta_hat[k] = E.th[k]; F_hat[k] = E.Fh[k]; }
@@ -110,11 +101,28 @@ inline bool groups_closed_transcript(const GroupsLayout &L, const double *u, con
     for (int g = 0; g < L.G; g++) {
         if (L.mask[(size_t)g] == L.all) { group[(size_t)g] = &all; continue; }
         if (GroupsLayout::count(L.mask[(size_t)g]) < 2) continue;
-        GroupClosedSamples Eg{u, den, L.size.data(), {}, {}};
+        Samples Eg = E0;
         recs[(size_t)g] = groups_search(L.K, L.mask[(size_t)g], Q, Eg).record(0, 1, 0);
         group[(size_t)g] = &recs[(size_t)g];
     }
     return groups_reduce(L, all, group.data(), theta_hat, F_hat, o, theta_group);
+}
+
+// K one-transcript components as groups_search's samples: compare_closed_form as the evaluation
+struct GroupClosedSamples {
+    const double *u, *den_, *size_;
+    double th[kGroupsMax], Fh[kGroupsMax];
+    double size(int k) const { return size_[k]; }
+    double den(int k) const { return den_[k]; }
+    double hat(int k) const { return th[k]; }
+    void put_hat(int k, double x, double F) { th[k] = x; Fh[k] = F; }
+    void eval(int k, double scale, double /* lambda */, double &x, double &F) const { compare_closed_form(u[k], den_[k], scale, x, F); }
+};
+// The searches of k_compare_groups_sets on a transcript that is a one-transcript component in every sample (u[k] reads, den[k]), and
+// their reduction: what the host does for such transcripts
+inline bool groups_closed_transcript(const GroupsLayout &L, const double *u, const double *den, const GroupSearchParams &Q, GroupsResult &o,
+                                     double *theta_group, double *theta_hat) {
+    return groups_host_searches(L, GroupClosedSamples{u, den, L.size.data(), {}, {}}, Q, o, theta_group, theta_hat);
 }
 
 struct GroupsRun {

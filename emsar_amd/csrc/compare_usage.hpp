@@ -142,7 +142,7 @@ struct CompareUsageRun : GeneQueryMembers {
         }
         const int32_t *gene_of_lib_b = nullptr;
         if (!lists.empty()) {
-            if (const int rc = gene_of_lib_of_b(ctx, ctx_b, d_gene_of_b, gene_of_lib_b)) return rc;
+            if (const int rc = gene_of_lib_of(ctx, ctx_b, d_gene_of_b, gene_of_lib_b)) return rc;
             if (const int rc = lists.upload(ctx)) return rc;
         }
         const SetSolveParams P = set_params(qa.p);

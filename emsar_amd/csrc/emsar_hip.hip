@@ -100,6 +100,7 @@
 #include "kernels_asym.hpp"
 #include "kernels_compare_usage.hpp"
 #include "kernels_profile_usage.hpp"
+#include "kernels_compare_groups_genes.hpp"
 
 // ==================================================================================================
 // context
@@ -857,6 +858,7 @@ int emsar_hip_sets_selfcheck(int64_t n_rows, int32_t n_tx, const uint64_t *row_p
 #include "compare_genes.hpp"   // the gene-level two-sample test and its entry points (after gene_parts.hpp; compare.hpp: compare_reduce)
 #include "profile_genes.hpp"   // the gene-level profile intervals and the gene presence test (after gene_parts.hpp; profile.hpp: profile_cut)
 #include "compare_groups.hpp"  // the K-sample test across replicate groups (after compare.hpp: side_ok; profile_genes.hpp: gene_presence_pvalue)
+#include "compare_groups_genes.hpp"  // the gene-level K-sample test (after compare_groups.hpp: GroupsLayout, groups_reduce; gene_parts.hpp)
 #include "compare_usage.hpp"   // the two-sample test of isoform usage (after gene_parts.hpp; compare.hpp: compare_pvalue)
 #include "profile_usage.hpp"   // the profile intervals of isoform usage (after compare_usage.hpp; profile_genes.hpp: profile_params_ok)
 #include "asym.hpp"       //the asymptotic standard errors and their entry points (after fit.hpp: fit_ensure_csr, launch_gene_sums)

@@ -1,7 +1,7 @@
-// gene_parts.hpp -- what the gene-level drivers share (compare_genes.hpp, profile_genes.hpp, compare_usage.hpp; device half:
-// kernels_gene_parts.hpp): the queried genes' members and their grouping into parts (GeneQueryMembers, GeneSideParts), ctx_b's
-// gene_of_lib for a two-sample call, and the owner of a call's part lists (GenePartLists).  Part of emsar_hip.hip's translation unit,
-// included after compare.hpp.
+// gene_parts.hpp -- what the gene-level drivers share (compare_genes.hpp, profile_genes.hpp, compare_usage.hpp,
+// compare_groups_genes.hpp; device half: kernels_gene_parts.hpp): the queried genes' members and their grouping into parts
+// (GeneQueryMembers, GeneSideParts), another context's gene_of_lib for a call over several samples, and the owner of a call's part
+// lists (GenePartLists).  Part of emsar_hip.hip's translation unit, included after compare.hpp.
 
 namespace {
 
@@ -69,14 +69,14 @@ struct GeneQueryMembers {
     }
 };
 
-// ctx_b's gene_of_lib for a two-sample call whose map lives on ctx_a: ctx_b's own when it has the map, else ctx_a's map in ctx_b's
-// library numbering, uploaded into `hold`
-inline int gene_of_lib_of_b(emsar_hip_ctx *ctx, emsar_hip_ctx *ctx_b, DevBuf<int32_t> &hold, const int32_t *&ptr) {
-    if (ctx_b->genes.have_genes) { ptr = ctx_b->genes.d_gene_of_lib; return EMSAR_HIP_OK; }
+// Context k's gene_of_lib for a call over several contexts whose map lives on `ctx` (the first one): ctx_k's own when it has the map
+// (the callers have checked that it is the same map), else ctx's map in ctx_k's library numbering, uploaded into `hold`
+inline int gene_of_lib_of(emsar_hip_ctx *ctx, emsar_hip_ctx *ctx_k, DevBuf<int32_t> &hold, const int32_t *&ptr) {
+    if (ctx_k->genes.have_genes) { ptr = ctx_k->genes.d_gene_of_lib; return EMSAR_HIP_OK; }
     const std::vector<int32_t> &of_tx = ctx->genes.h_gene_of_tx;
     std::vector<int32_t> of_lib(of_tx.size());
-    const bool remap = renumbered(ctx_b);
-    for (size_t t = 0; t < of_tx.size(); t++) of_lib[remap ? (size_t)tid_map(ctx_b)[t] : t] = of_tx[t];
+    const bool remap = renumbered(ctx_k);
+    for (size_t t = 0; t < of_tx.size(); t++) of_lib[remap ? (size_t)tid_map(ctx_k)[t] : t] = of_tx[t];
     HIPCHK(hold.upload(of_lib.data(), of_lib.size()));
     ptr = hold;
     return EMSAR_HIP_OK;
@@ -95,15 +95,21 @@ struct GenePartLists {
 
     bool empty() const { return h_parts.empty(); }
 
-    // a's set parts, then b's; a's closed-form parts, then b's
-    Offsets append(const GeneSideParts &a, const GeneSideParts *b = nullptr) {
+    // the sides' set parts, side after side (a part's `side` says whose it is), and their closed-form parts in the same order
+    Offsets append(const GeneSideParts *const *sides, int n_sides) {
         const Offsets at{(int32_t)h_parts.size(), (int32_t)h_closed.size()};
-        for (const GeneSideParts *s : {&a, b}) {
+        for (int k = 0; k < n_sides; k++) {
+            const GeneSideParts *s = sides[k];
             if (!s) continue;
             h_parts.insert(h_parts.end(), s->sets.begin(), s->sets.end());
             h_closed.insert(h_closed.end(), s->closed.begin(), s->closed.end());
         }
         return at;
+    }
+    // one sample, or a then b
+    Offsets append(const GeneSideParts &a, const GeneSideParts *b = nullptr) {
+        const GeneSideParts *const sides[2] = {&a, b};
+        return append(sides, 2);
     }
     int upload(emsar_hip_ctx *ctx) {
         HIPCHK(d_parts.upload(h_parts.data(), h_parts.size()));
@@ -116,27 +122,34 @@ struct GenePartLists {
         for (int32_t k = 0; k < n_parts; k++) top = std::max(top, (int)h_parts[(size_t)part_off + (size_t)k].cls);
         return top;
     }
-    // An item's slices against the lists, side by side (the first side's context holds the gene map), its set parts against their own
-    // context's descriptors, and its launch class: c is the class of its largest set part
-    bool slice_ok(int c, int32_t part_off, int32_t closed_off, int32_t gene, std::initializer_list<Side> sides) const {
-        if (part_off < 0 || closed_off < 0 || gene < 0 || gene >= sides.begin()->ctx->genes.n_genes) return false;
+    // An item's slices against the lists, side by side (the first side's context holds the gene map), and its set parts against their
+    // own context's descriptors.  Gives the largest class among the set parts of the sides in `mask` (bit k = side k; -1 without any),
+    // -2 where anything is out of place
+    int slice_class(int32_t part_off, int32_t closed_off, int32_t gene, const Side *sides, int n_sides, uint32_t mask) const {
+        if (part_off < 0 || closed_off < 0 || n_sides < 1 || gene < 0 || gene >= sides[0].ctx->genes.n_genes) return -2;
         size_t n_parts = 0, n_closed = 0;
-        for (const Side &s : sides) {
-            if (s.n_parts < 0 || s.n_parts > kGeneMaxParts || s.n_closed < 0 || s.n_closed > kGeneMaxParts) return false;
-            if (s.n_parts + s.n_closed > kGeneMaxParts) return false;
+        for (int j = 0; j < n_sides; j++) {
+            const Side &s = sides[j];
+            if (s.n_parts < 0 || s.n_parts > kGeneMaxParts || s.n_closed < 0 || s.n_closed > kGeneMaxParts) return -2;
+            if (s.n_parts + s.n_closed > kGeneMaxParts) return -2;
             n_parts += (size_t)s.n_parts; n_closed += (size_t)s.n_closed;
         }
-        if ((size_t)part_off + n_parts > h_parts.size() || (size_t)closed_off + n_closed > h_closed.size()) return false;
+        if ((size_t)part_off + n_parts > h_parts.size() || (size_t)closed_off + n_closed > h_closed.size()) return -2;
         size_t k = (size_t)part_off;
-        int32_t side = 0;
-        for (const Side &s : sides) {
+        int top = -1;
+        for (int j = 0; j < n_sides; j++) {
+            const Side &s = sides[j];
             for (int32_t i = 0; i < s.n_parts; i++, k++) {
                 const CompareGenePart &p = h_parts[k];
-                if (p.side != side || p.cls > c || !set_desc(s.ctx, p.cls, p.set)) return false;
+                if (p.side != j || !set_desc(s.ctx, p.cls, p.set)) return -2;
+                if ((mask >> j) & 1u) top = std::max(top, (int)p.cls);
             }
-            side++;
         }
-        return launch_class(part_off, (int32_t)n_parts) == c;
+        return top;
+    }
+    // all sides count, and c is the class of the item's largest set part: the launch class of the one- and two-sample items
+    bool slice_ok(int c, int32_t part_off, int32_t closed_off, int32_t gene, std::initializer_list<Side> sides) const {
+        return c >= 0 && slice_class(part_off, closed_off, gene, sides.begin(), (int)sides.size(), ~0u) == c;
     }
 };
 

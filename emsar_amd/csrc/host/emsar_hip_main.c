@@ -60,8 +60,10 @@
  * ONE file <prefix>.groups holds, per transcript (or per transcript named in --compare-list FILE), the common FPKM of all samples and of each
  * group, Lambda_between (the groups differ, replicates pooled inside the likelihood) and Lambda_within (the replicates of a group disagree)
  * with their degrees of freedom and chi2 p-values, a status word, the outer points and the inner evaluations spent (emsar_hip_compare_groups
- * with the solve's parameters on K contexts on the first worker's device).  --compare-sizes s0,s1,.. gives every sample a size factor.  The
- * other files do not change with it.
+ * with the solve's parameters on K contexts on the first worker's device).  --compare-sizes s0,s1,.. gives every sample a size factor.  With
+ * --g2t also ONE file <prefix>.ggroups: the same "#" line, then per gene, in the order of .gfpkm, the common gFPKM of all samples and of each
+ * group and the same columns for the gene's SUM with the isoforms free in every sample, then the parts (emsar_hip_compare_groups_genes);
+ * --compare-list filters transcripts only.  The other files do not change with it.
  * --compare-usage (with -M, at least two samples and --g2t) answers "did this isoform's share of its gene change against sample 0" (an
  * isoform switch): every sample i >= 1 writes <prefix>.<i>.ucompare with, per transcript (or per transcript named in --compare-list FILE), its
  * gene, its share of the gene in sample i and in sample 0, the difference of their logits, the likelihood-ratio statistic Lambda of H0: equal
@@ -697,11 +699,15 @@ static void *worker_main(void *a) {
 }
 
 /* K-sample test (--compare-groups), after every worker has joined: K contexts on `device` hold the samples' solver inputs, one call
- * (emsar_hip_compare_groups with the solve's parameters) answers for all of them: <prefix>.groups */
+ * (emsar_hip_compare_groups with the solve's parameters) answers for all of them: <prefix>.groups.  With --g2t the first context takes the
+ * gene map and a second call (emsar_hip_compare_groups_genes, every gene; --compare-list names transcripts and does not filter it) answers
+ * per gene: <prefix>.ggroups */
 static int stage_groups(const config *cfg, const emsar_rsh *r, int device) {
     const int K = cfg->n_aln;
     const int32_t *query = cfg->cmp_q;
     const size_t Q = query ? (size_t)cfg->cmp_nq : (size_t)r->n_tx;
+    const size_t NG = cfg->genes ? (size_t)cfg->genes->n_genes : 0;
+    const double *size = cfg->n_sizes ? cfg->group_size : NULL;
     int32_t G = 0;
     for (int k = 0; k < K; k++) {
         if (!cfg->inputs[k].ready) { fprintf(stderr, "compare-groups: sample %d gave no solver inputs\n", k); return EMSAR_HOST_ERR_IO; }
@@ -710,9 +716,9 @@ static int stage_groups(const config *cfg, const emsar_rsh *r, int device) {
     const emsar_em_params p = {.max_iter = cfg->max_iter, .accel = cfg->accel, .tol = cfg->tol, .set_mode = cfg->set_mode, .count_floor = cfg->count_floor,
                                .zero_cut = cfg->zero_cut, .abs_step = cfg->abs_step};
     emsar_hip_ctx *ctx[32] = {0};
-    double *v = (double *)slab((6 + (size_t)G) * Q, 8);
-    int32_t *iv = (int32_t *)slab(3 * Q, 4);
-    int rc = v && iv ? 0 : EMSAR_HOST_ERR_OOM;
+    double *v = (double *)slab((6 + (size_t)G) * Q, 8), *gv = cfg->genes ? (double *)slab((5 + (size_t)G) * NG, 8) : NULL;
+    int32_t *iv = (int32_t *)slab(3 * Q, 4), *gi = cfg->genes ? (int32_t *)slab(4 * NG, 4) : NULL;
+    int rc = v && iv && (!cfg->genes || (gv && gi)) ? 0 : EMSAR_HOST_ERR_OOM;
     for (int k = 0; k < K && !rc; k++) {
         const compare_ref *in = &cfg->inputs[k];
         if ((rc = emsar_hip_create(&ctx[k], device)) || (rc = emsar_hip_set_deterministic(ctx[k], !cfg->no_deterministic)) ||
@@ -725,14 +731,27 @@ static int stage_groups(const config *cfg, const emsar_rsh *r, int device) {
                                         .theta_group = v + 6 * Q, .status = iv, .outer = iv + Q, .evals = iv + 2 * Q};
         char path[4096];
         snprintf(path, sizeof path, "%s/%s.groups", cfg->outdir, cfg->prefix);
-        rc = emsar_hip_compare_groups(ctx, K, cfg->group_of, cfg->n_sizes ? cfg->group_size : NULL, &p, NULL, (int32_t)Q, query, &o, NULL);
+        rc = emsar_hip_compare_groups(ctx, K, cfg->group_of, size, &p, NULL, (int32_t)Q, query, &o, NULL);
         if (rc) fprintf(stderr, "compare-groups: %s (%s)\n", emsar_hip_strerror(rc), emsar_hip_last_error(ctx[0]));
-        else if ((rc = emsar_write_groups(path, r, (int32_t)Q, query, K, cfg->group_of, cfg->n_sizes ? cfg->group_size : NULL, o.theta_common, o.theta_group,
+        else if ((rc = emsar_write_groups(path, r, (int32_t)Q, query, K, cfg->group_of, size, o.theta_common, o.theta_group,
                                           o.lambda_between, o.p_between, o.lambda_within, o.p_within, o.status, o.outer, o.evals)))
             fprintf(stderr, "can't write %s\n", path);
     }
+    if (!rc && cfg->genes) {
+        const emsar_groups_gene_outputs o = {.gene_common = gv, .lambda_between = gv + NG, .p_between = gv + 2 * NG, .lambda_within = gv + 3 * NG,
+                                             .p_within = gv + 4 * NG, .gene_group = gv + 5 * NG, .status = gi, .outer = gi + NG, .evals = gi + 2 * NG,
+                                             .parts = gi + 3 * NG};
+        char path[4096];
+        snprintf(path, sizeof path, "%s/%s.ggroups", cfg->outdir, cfg->prefix);
+        if ((rc = emsar_hip_set_gene_map(ctx[0], cfg->genes->n_genes, cfg->genes->gene_of_tx)) ||
+            (rc = emsar_hip_compare_groups_genes(ctx, K, cfg->group_of, size, &p, NULL, (int32_t)NG, NULL, &o, NULL)))
+            fprintf(stderr, "compare-groups (genes): %s (%s)\n", emsar_hip_strerror(rc), emsar_hip_last_error(ctx[0]));
+        else if ((rc = emsar_write_ggroups(path, cfg->genes, K, cfg->group_of, size, o.gene_common, o.gene_group, o.lambda_between, o.p_between,
+                                           o.lambda_within, o.p_within, o.status, o.outer, o.evals, o.parts)))
+            fprintf(stderr, "can't write %s\n", path);
+    }
     for (int k = 0; k < K; k++) emsar_hip_destroy(ctx[k]);
-    free(v); free(iv);
+    free(v); free(iv); free(gv); free(gi);
     return rc;
 }
 
@@ -804,7 +823,9 @@ static void usage(const char *a0) {
             "                            <prefix>.groups: per transcript the common FPKM of all samples and of each group, Lambda_between (the groups\n"
             "                            differ, replicates pooled inside the likelihood) and Lambda_within (the replicates of a group disagree), their\n"
             "                            degrees of freedom and chi2 p-values, a status word (TESTED, ALL_ABSENT, OUTSIDE, NOT_RESIDENT, UNCONVERGED), outer\n"
-            "                            points and evaluations.  No over-dispersion is modelled: a large Lambda_within makes p_between anti-conservative\n"
+            "                            points and evaluations.  No over-dispersion is modelled: a large Lambda_within makes p_between anti-conservative.\n"
+            "                            With --g2t also ONE file <prefix>.ggroups: per gene, in the order of .gfpkm, the same columns for the gene's summed\n"
+            "                            FPKM with its isoforms free in every sample (also TOO_LARGE), and the parts searched over\n"
             "      --compare-sizes <s0,s1,..>   with --compare-groups: one positive size factor per sample (default 1); --compare-list filters it too\n"
             "      --compare-usage       with -M, at least two samples and --g2t: every sample i >= 1 also writes <prefix>.<i>.ucompare: per transcript its\n"
             "                            gene, its share of the gene in sample i and in sample 0, the difference of their logits, Lambda of H0: equal\n"

@@ -225,6 +225,13 @@ int emsar_write_ucompare(const char *path, const emsar_rsh *r, const emsar_genes
 int emsar_write_groups(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, int32_t n_samples, const int32_t *group_of,
                        const double *size, const double *theta_common, const double *theta_group, const double *lambda_between, const double *p_between,
                        const double *lambda_within, const double *p_within, const int32_t *status, const int32_t *outer, const int32_t *evals);
+/* .ggroups (with --g2t; one file per job, <prefix>.ggroups): .groups' "#" line, then one line per gene in the order of .gfpkm -- gene
+ * gFPKM_common gFPKM_g0 .. gFPKM_g(G-1) Lambda_between df p_between Lambda_within df p_within status outer evals parts; gene_group [n_genes][G];
+ * the arrays as emsar_hip_compare_groups_genes returns them for every gene; number formats as in .groups; also TOO_LARGE */
+int emsar_write_ggroups(const char *path, const emsar_genes *g, int32_t n_samples, const int32_t *group_of, const double *size,
+                        const double *gene_common, const double *gene_group, const double *lambda_between, const double *p_between,
+                        const double *lambda_within, const double *p_within, const int32_t *status, const int32_t *outer, const int32_t *evals,
+                        const int32_t *parts);
 
 /* .asym (emsar-hip --asymptotic): one line per transcript -- tid transcriptID FPKM sd_FPKM TPM sd_TPM status partner partner_corr, and
  * usage_sd when it is given (--g2t); the arrays are [n_tx] as emsar_hip_asymptotic returns them.  partner_corr = partner_cov /

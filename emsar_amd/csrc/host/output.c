@@ -36,6 +36,7 @@
  *   .groups             "# samples=.. groups=g0,.. sizes=s0,.. df_between=.. df_within=..", a header, then per queried transcript:
  *                       transcript FPKM_common FPKM_g0 .. Lambda_between df p_between Lambda_within df p_within status outer evals,
  *                       numbers and p as in .compare
+ *   .ggroups            the same "#" line, then per gene, in the order of .gfpkm: gene gFPKM_common gFPKM_g0 .. and .groups' columns, then parts
  * Column order of .fpkm is a contract: the reference's Perl utilities read columns 0,1,4,6 (util/FPKM2gFPKM.pl:19).
  */
 #include "emsar_host.h"
@@ -169,13 +170,13 @@ int emsar_write_gfit(const char *path, const emsar_rsh *r, const emsar_genes *g,
 
 /* The status words, one table per family of enums in include/emsar_hip.h; a file whose enum stops earlier uses the table's first words:
  * .profile the first 5 of the intervals' (.gprofile all 6), .compare the first 5 and .gcompare the first 6 of the two-sample tests'
- * (.ucompare all 8), .uprofile the 10 of the usage intervals'.  A number outside the file's range is written as "?". */
+ * (.ucompare all 8), .uprofile the 10 of the usage intervals', .groups the first 5 of the K-sample tests' (.ggroups all 6).  A number outside the file's range is written as "?". */
 static const char *const presence_word[6] = {"TESTED", "ABSENT", "ESSENTIAL", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED"};
 static const char *const interval_word[6] = {"TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE"};
 static const char *const usage_interval_word[10] = {"TWO_SIDED", "LOWER_ZERO", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE", "UPPER_ONE", "UNIT",
                                                     "UNDEFINED", "SINGLE"};
 static const char *const two_sample_word[8] = {"TESTED", "BOTH_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE", "UNDEFINED", "SINGLE"};
-static const char *const groups_word[5] = {"TESTED", "ALL_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED"};
+static const char *const groups_word[6] = {"TESTED", "ALL_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED", "TOO_LARGE"};
 static const char *const asym_word[5] = {"ESTIMATED", "BOUNDARY", "UNIDENTIFIABLE", "TOO_LARGE", "INFEASIBLE"};
 
 static const char *status_word(const char *const *table, int n, int32_t v) { return v >= 0 && v < n ? table[v] : "?"; }
@@ -284,30 +285,61 @@ int emsar_write_ucompare(const char *path, const emsar_rsh *r, const emsar_genes
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }
 
-int emsar_write_groups(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, int32_t n_samples, const int32_t *group_of,
-                       const double *size, const double *theta_common, const double *theta_group, const double *lambda_between, const double *p_between,
-                       const double *lambda_within, const double *p_within, const int32_t *status, const int32_t *outer, const int32_t *evals) {
-    int32_t G = 0;
-    for (int32_t k = 0; k < n_samples; k++) if (group_of[k] + 1 > G) G = group_of[k] + 1;
-    FILE *f = fopen(path, "w");
-    if (!f) return EMSAR_HOST_ERR_IO;
+/* what .groups and .ggroups share: the "#" line, the header behind the name column (`value` = FPKM / gFPKM) and the number columns of a line */
+static void put_groups_head(FILE *f, const char *name, const char *value, int32_t n_samples, int32_t G, const int32_t *group_of, const double *size,
+                            const char *tail) {
     fprintf(f, "# samples=%d groups=", n_samples);
     for (int32_t k = 0; k < n_samples; k++) fprintf(f, "%s%d", k ? "," : "", group_of[k]);
     fprintf(f, " sizes=");
     for (int32_t k = 0; k < n_samples; k++) fprintf(f, "%s%g", k ? "," : "", size ? size[k] : 1.0);
     fprintf(f, " df_between=%d df_within=%d\n", G - 1, n_samples - G);
-    fprintf(f, "transcript\tFPKM_common");
-    for (int32_t g = 0; g < G; g++) fprintf(f, "\tFPKM_g%d", g);
-    fprintf(f, "\tLambda_between\tdf\tp_between\tLambda_within\tdf\tp_within\tstatus\touter\tevals\n");
+    fprintf(f, "%s\t%s_common", name, value);
+    for (int32_t g = 0; g < G; g++) fprintf(f, "\t%s_g%d", value, g);
+    fprintf(f, "\tLambda_between\tdf\tp_between\tLambda_within\tdf\tp_within\tstatus\touter\tevals%s\n", tail);
+}
+static void put_groups_columns(FILE *f, int32_t n_samples, int32_t G, double common, const double *group, double lambda_between, double p_between,
+                               double lambda_within, double p_within) {
+    put_value(f, "%lf", common, 1);
+    for (int32_t g = 0; g < G; g++) { fputc('\t', f); put_value(f, "%lf", group[g], 1); }
+    fputc('\t', f); put_value(f, "%lf", lambda_between, 1); fprintf(f, "\t%d\t", G - 1); put_value(f, "%.6g", p_between, 1);
+    fputc('\t', f); put_value(f, "%lf", lambda_within, 1); fprintf(f, "\t%d\t", n_samples - G); put_value(f, "%.6g", p_within, 1);
+}
+static int32_t groups_count(int32_t n_samples, const int32_t *group_of) {
+    int32_t G = 0;
+    for (int32_t k = 0; k < n_samples; k++) if (group_of[k] + 1 > G) G = group_of[k] + 1;
+    return G;
+}
+
+int emsar_write_groups(const char *path, const emsar_rsh *r, int32_t n_query, const int32_t *query, int32_t n_samples, const int32_t *group_of,
+                       const double *size, const double *theta_common, const double *theta_group, const double *lambda_between, const double *p_between,
+                       const double *lambda_within, const double *p_within, const int32_t *status, const int32_t *outer, const int32_t *evals) {
+    const int32_t G = groups_count(n_samples, group_of);
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    put_groups_head(f, "transcript", "FPKM", n_samples, G, group_of, size, "");
     for (int32_t i = 0; i < n_query; i++) {
         const int32_t t = query ? query[i] : i;
-        const double b[2] = {lambda_between[i], p_between[i]}, w[2] = {lambda_within[i], p_within[i]};
         fprintf(f, "%s\t", r->names[t]);
-        put_value(f, "%lf", theta_common[i], 1);
-        for (int32_t g = 0; g < G; g++) { fputc('\t', f); put_value(f, "%lf", theta_group[(size_t)i * (size_t)G + (size_t)g], 1); }
-        fputc('\t', f); put_value(f, "%lf", b[0], 1); fprintf(f, "\t%d\t", G - 1); put_value(f, "%.6g", b[1], 1);
-        fputc('\t', f); put_value(f, "%lf", w[0], 1); fprintf(f, "\t%d\t", n_samples - G); put_value(f, "%.6g", w[1], 1);
+        put_groups_columns(f, n_samples, G, theta_common[i], theta_group + (size_t)i * (size_t)G, lambda_between[i], p_between[i], lambda_within[i],
+                           p_within[i]);
         fprintf(f, "\t%s\t%d\t%d\n", status_word(groups_word, 5, status[i]), outer[i], evals[i]);
+    }
+    return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
+}
+
+int emsar_write_ggroups(const char *path, const emsar_genes *g, int32_t n_samples, const int32_t *group_of, const double *size,
+                        const double *gene_common, const double *gene_group, const double *lambda_between, const double *p_between,
+                        const double *lambda_within, const double *p_within, const int32_t *status, const int32_t *outer, const int32_t *evals,
+                        const int32_t *parts) {
+    const int32_t G = groups_count(n_samples, group_of);
+    FILE *f = fopen(path, "w");
+    if (!f) return EMSAR_HOST_ERR_IO;
+    put_groups_head(f, "gene", "gFPKM", n_samples, G, group_of, size, "\tparts");
+    for (int32_t k = 0; k < g->n_genes; k++) {
+        fprintf(f, "%s\t", g->names[k]);
+        put_groups_columns(f, n_samples, G, gene_common[k], gene_group + (size_t)k * (size_t)G, lambda_between[k], p_between[k], lambda_within[k],
+                           p_within[k]);
+        fprintf(f, "\t%s\t%d\t%d\t%d\n", status_word(groups_word, 6, status[k]), outer[k], evals[k], parts[k]);
     }
     return fclose(f) == 0 ? EMSAR_HOST_OK : EMSAR_HOST_ERR_IO;
 }

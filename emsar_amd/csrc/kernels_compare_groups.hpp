@@ -154,7 +154,8 @@ struct GroupSearched {
 // The whole search of one item, both levels, driven by k_compare_groups_sets and by the host (transcripts that are closed form in every
 // sample).  The samples of `mask` are visited in ascending index, so every sum has one order.  E gives the samples:
 //   E.size(k), E.den(k)          s_k and den_t^k
-//   E.eval(k, scale, x, F)       sample k with den_t taken as scale * den_t: theta_t and F there
+//   E.eval(k, scale, lambda, x, F)   sample k with den_t taken as scale * den_t = den_t + lambda: theta_t and F there.  A transcript needs
+//                                scale alone; the gene-level samples (kernels_compare_groups_genes.hpp) shift their other members by lambda
 //   E.put_hat(k, x, F)           keeps theta_hat^k (and F_hat^k for the record) after point 0;  E.hat(k) gives theta_hat^k back
 template <class Samples>
 __host__ __device__ __forceinline__ GroupSearched groups_search(int K, uint32_t mask, const GroupSearchParams &Q, Samples &E) {
@@ -174,7 +175,7 @@ __host__ __device__ __forceinline__ GroupSearched groups_search(int K, uint32_t 
             bool more = J.start(first, s * O.x, first ? 0.0 : E.hat(k), den);
             while (more) {
                 double x_t, F;
-                E.eval(k, J.scale, x_t, F);
+                E.eval(k, J.scale, J.lambda, x_t, F);
                 more = J.step(first, x_t, F, den, Q);
             }
             R.evals += J.evals;
@@ -209,7 +210,7 @@ struct GroupDeviceSamples {
         }
         __syncthreads();
     }
-    __device__ void eval(int k, double scale, double &x_t, double &F) {
+    __device__ void eval(int k, double scale, double /* lambda */, double &x_t, double &F) {
         const GroupLoc l = loc[k];
         if (l.set < 0) { compare_closed_form(l.u, l.den, scale, x_t, F); return; }
         const CompareSide G = samples[k].side;

@@ -10,8 +10,9 @@ namespace {
 // PARTS of the gene in that sample.  One evaluation of a sample is a loop over its parts; the gene sum X, F and whatever else a search
 // asks for are summed over them in the order of the lists below.
 
-// A set part: packed set `set` of size class `cls` of sample `side` (0 = A, 1 = B) holds at least one member that takes part.  A
-// gene's parts are A's then B's, each side by the smallest caller tid of the part's members.
+// A set part: packed set `set` of size class `cls` of sample `side` (0 = A, 1 = B; sample k of a K-sample call) holds at least one
+// member that takes part.  A gene's parts are A's then B's (sample 0's, then 1's, ..), each side by the smallest caller tid of the
+// part's members.
 struct CompareGenePart { int32_t side, set, cls, reserved0; };
 // A closed-form part: a member that is a one-transcript component, u reads and den (the bits of the sample's den)
 struct CompareGeneClosed { double u, den; };

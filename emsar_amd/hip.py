@@ -31,7 +31,7 @@ SYMBOLS = [
     "emsar_hip_compare", "emsar_hip_compare_pvalue_host", "emsar_hip_compare_genes",
     "emsar_hip_profile_genes", "emsar_hip_gene_presence_pvalue_host",
     "emsar_hip_compare_usage", "emsar_hip_profile_usage",
-    "emsar_hip_compare_groups", "emsar_hip_compare_groups_pvalue_host",
+    "emsar_hip_compare_groups", "emsar_hip_compare_groups_pvalue_host", "emsar_hip_compare_groups_genes",
     "emsar_hip_asymptotic", "emsar_hip_asymptotic_host",
 ]
 
@@ -59,6 +59,10 @@ GROUPS_STATUS = ("TESTED", "ALL_ABSENT", "OUTSIDE", "NOT_RESIDENT", "UNCONVERGED
 GROUPS_OUTPUTS = ("lambda_between", "p_between", "lambda_within", "p_within", "raw_between", "raw_within", "theta_common", "slope")
 GROUPS_COUNTS = ("status", "outer", "evals")
 GROUPS_MAX = 32
+# status of a gene in the gene-level K-sample test (include/emsar_hip.h "gene-level K-sample test"), by value
+GROUPS_GENE_STATUS = GROUPS_STATUS + ("TOO_LARGE",)
+GROUPS_GENE_OUTPUTS = ("lambda_between", "p_between", "lambda_within", "p_within", "raw_between", "raw_within", "gene_common", "slope")
+GROUPS_GENE_COUNTS = ("status", "outer", "evals", "parts")
 
 # status of a gene's profile-likelihood interval (include/emsar_hip.h "gene-level profile intervals"), by value
 PROFILE_GENE_STATUS = PROFILE_STATUS + ("TOO_LARGE",)
@@ -259,6 +263,23 @@ class GroupsStats(C.Structure):
         return d
 
 
+class GroupsGeneOutputs(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in GROUPS_GENE_OUTPUTS + ("gene_group", "gene_hat")] + \
+               [(k, C.POINTER(C.c_int32)) for k in GROUPS_GENE_COUNTS]
+
+
+class GroupsGeneStats(C.Structure):
+    _fields_ = [("n_status", C.c_int64 * 6), ("items_launched", C.c_int64), ("evals_sum", C.c_int64), ("passes_sum", C.c_int64),
+                ("outer_sum", C.c_int64), ("evals_max", C.c_int32), ("passes_max", C.c_int32), ("outer_max", C.c_int32),
+                ("parts_max", C.c_int32), ("df_between", C.c_int32), ("df_within", C.c_int32), ("min_raw_lambda", C.c_double),
+                ("device_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["n_status"] = dict(zip(GROUPS_GENE_STATUS, d["n_status"]))
+        return d
+
+
 class ProfileGeneOutputs(C.Structure):
     _fields_ = [(k, C.POINTER(C.c_double)) for k in ("lower", "upper", "dev_lower", "dev_upper", "lambda_", "pvalue", "gene_hat")] + \
                [(k, C.POINTER(C.c_int32)) for k in ("status", "evals", "parts", "members")]
@@ -404,6 +425,8 @@ def load_library():
     L.emsar_hip_compare_groups.argtypes = [C.POINTER(vp), C.c_int32, i32p, f64p, C.POINTER(EmParams), C.POINTER(GroupsParams), C.c_int32, i32p,
                                            C.POINTER(GroupsOutputs), C.POINTER(GroupsStats)]
     L.emsar_hip_compare_groups_pvalue_host.argtypes = [C.c_int64, f64p, i32p, f64p]
+    L.emsar_hip_compare_groups_genes.argtypes = [C.POINTER(vp), C.c_int32, i32p, f64p, C.POINTER(EmParams), C.POINTER(GroupsParams), C.c_int32,
+                                                 i32p, C.POINTER(GroupsGeneOutputs), C.POINTER(GroupsGeneStats)]
     L.emsar_hip_profile_usage.argtypes = [vp, C.POINTER(EmParams), C.POINTER(ProfileParams), C.c_int32, i32p, C.POINTER(ProfileUsageOutputs),
                                           C.POINTER(ProfileUsageStats)]
     L.emsar_hip_profile_genes.argtypes = [vp, C.POINTER(EmParams), C.POINTER(ProfileParams), C.c_int32, i32p, C.POINTER(ProfileGeneOutputs),
@@ -705,6 +728,34 @@ def debug_compare_groups_closed(u, den, groups, sizes=None, dev_tol=0.0, max_eva
     out = dict(zip(GROUPS_OUTPUTS, list(vals)))
     out.update(zip(GROUPS_COUNTS, list(counts)))
     out.update(theta_group=tg, theta_hat=th[:len(uu)])
+    return out
+
+
+def debug_compare_groups_genes_closed(members, groups, sizes=None, dev_tol=0.0, max_evals=0, max_outer=0):
+    """Host-only diagnostic: what compare_groups_genes() gives a gene whose parts are all closed form in each of the K samples --
+    members[k] = a list of (u, den) pairs, the gene's one-transcript components in sample k: the two-level searches as the host runs
+    them for such genes (no GPU needed).  Returns a dict keyed like compare_groups_genes()'s arrays: scalars, gene_group [G] and
+    gene_hat [K]."""
+    f = load_library().emsar_hip_debug_compare_groups_genes_closed  # not declared in the header: bound here, not in load_library
+    f.restype = C.c_int
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    f.argtypes = [C.c_int32, ip, dp, dp, ip, dp, C.POINTER(GroupsParams), dp, dp, dp, ip]
+    lists = [np.asarray(m, dtype=np.float64).reshape(-1, 2) for m in members]
+    n = np.ascontiguousarray([len(m) for m in lists], dtype=np.int32)
+    flat = np.concatenate(lists) if lists else np.zeros((0, 2))
+    uu, dd = np.ascontiguousarray(flat[:, 0]), np.ascontiguousarray(flat[:, 1])
+    g, s, n_groups = _groups_layout(groups, sizes)
+    if len(g) != len(lists):
+        raise ValueError("members and groups must have the same length")
+    gp, vals, counts = GroupsParams(float(dev_tol), int(max_evals), int(max_outer)), (C.c_double * 8)(), (C.c_int32 * 4)()
+    tg, th = np.zeros(n_groups), np.zeros(max(len(lists), 1))
+    rc = f(len(lists), _p(n, C.c_int32), _p(uu, C.c_double), _p(dd, C.c_double), _p(g, C.c_int32), _p(s, C.c_double), C.byref(gp), vals,
+           _p(tg, C.c_double), _p(th, C.c_double), counts)
+    if rc != 0:
+        raise EmsarHipError(rc, "debug_compare_groups_genes_closed")
+    out = dict(zip(GROUPS_GENE_OUTPUTS, list(vals)))
+    out.update(zip(GROUPS_GENE_COUNTS, list(counts)))
+    out.update(gene_group=tg, gene_hat=th[:len(lists)])
     return out
 
 
@@ -1160,6 +1211,36 @@ class EmsarHip:
         st = GroupsStats()
         self._chk(self._L.emsar_hip_compare_groups(handles, len(ctxs), _p(g, C.c_int32), _p(s, C.c_double), C.byref(p), C.byref(gp), nq,
                                                    _p(q, C.c_int32), C.byref(o), C.byref(st)), "compare_groups")
+        out = {k: v[:nq] for k, v in res.items()}
+        out["stats"] = st
+        return out
+
+    def compare_groups_genes(self, others, groups, sizes=None, genes=None, dev_tol=0.0, max_evals=0, max_outer=0, max_iter=100000, accel=1,
+                             tol=1e-10, abs_floor=1e-6, check_every=8, count_floor=0.0, set_mode=0, zero_cut=0.0, abs_step=0.0, newton_after=0):
+        """Gene-level K-sample test across replicate groups (include/emsar_hip.h "gene-level K-sample test"): compare_groups() asked of
+        each gene's SUM of theta, the isoforms and every other transcript free in every sample.  This context holds sample 0 and the gene
+        map (set_gene_map), `others` samples 1 .. K-1; groups, sizes and the parameters are compare_groups()'s.  genes: gene ids in any
+        order, repeats allowed, None = all genes.  Returns a dict of arrays in query order: lambda_between, p_between, lambda_within,
+        p_within, raw_between, raw_within, gene_common, slope, gene_group [n, G], gene_hat [n, K], status (index into
+        GROUPS_GENE_STATUS), outer, evals, parts, and stats.  After upload_sample on every context; all are left as they were."""
+        p = EmParams(max_iter, accel, tol, abs_floor, check_every, set_mode, count_floor, zero_cut, abs_step, newton_after, 0)
+        gp = GroupsParams(float(dev_tol), int(max_evals), int(max_outer))
+        ctxs = [self] + list(others)
+        g, s, n_groups = _groups_layout(groups, sizes)
+        if len(g) != len(ctxs):
+            raise ValueError("groups must hold one id per sample")
+        handles = (C.c_void_p * len(ctxs))(*[getattr(c, "_h", None) for c in ctxs])
+        q = None if genes is None else np.ascontiguousarray(np.asarray(genes, dtype=np.int32).reshape(-1))
+        nq = self.n_genes if q is None else len(q)
+        res = {k: np.zeros(max(nq, 1)) for k in GROUPS_GENE_OUTPUTS}
+        res["gene_group"] = np.zeros((max(nq, 1), n_groups))
+        res["gene_hat"] = np.zeros((max(nq, 1), len(ctxs)))
+        res.update({k: np.zeros(max(nq, 1), dtype=np.int32) for k in GROUPS_GENE_COUNTS})
+        o = GroupsGeneOutputs(*[_p(res[k], C.c_double) for k in GROUPS_GENE_OUTPUTS + ("gene_group", "gene_hat")],
+                              *[_p(res[k], C.c_int32) for k in GROUPS_GENE_COUNTS])
+        st = GroupsGeneStats()
+        self._chk(self._L.emsar_hip_compare_groups_genes(handles, len(ctxs), _p(g, C.c_int32), _p(s, C.c_double), C.byref(p), C.byref(gp), nq,
+                                                         _p(q, C.c_int32), C.byref(o), C.byref(st)), "compare_groups_genes")
         out = {k: v[:nq] for k, v in res.items()}
         out["stats"] = st
         return out

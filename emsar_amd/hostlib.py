@@ -98,6 +98,7 @@ def lib():
         L.emsar_write_gcompare.argtypes = [C.c_char_p, C.POINTER(Genes)] + [f64p] * 5 + [i32p, i32p, i32p]
         L.emsar_write_ucompare.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Genes), C.c_int32, i32p] + [f64p] * 5 + [i32p, i32p, i32p]
         L.emsar_write_groups.argtypes = [C.c_char_p, C.POINTER(Rsh), C.c_int32, i32p, C.c_int32, i32p] + [f64p] * 7 + [i32p, i32p, i32p]
+        L.emsar_write_ggroups.argtypes = [C.c_char_p, C.POINTER(Genes), C.c_int32, i32p] + [f64p] * 7 + [i32p, i32p, i32p, i32p]
         L.emsar_write_uprofile.argtypes = [C.c_char_p, C.POINTER(Rsh), C.POINTER(Genes), C.c_int32, i32p] + [f64p] * 5 + [i32p, i32p, i32p]
         L.emsar_write_asym.argtypes = [C.c_char_p, C.POINTER(Rsh)] + [f64p] * 5 + [i32p, i32p, f64p, f64p]
         L.emsar_write_gasym.argtypes = [C.c_char_p, C.POINTER(Genes), f64p, f64p, i32p]
@@ -246,6 +247,21 @@ def write_groups(path, tx_names, groups, sizes, theta_common, theta_group, lambd
                                   None if s is None else _dp(s), *([_dp(x) for x in a] + [_ip(x) for x in i]))
     if rc != 0:
         raise HostError("write_groups rc=%d" % rc)
+
+
+def write_ggroups(path, gene_names, groups, sizes, gene_common, gene_group, lambda_between, p_between, lambda_within, p_within, status, outer, evals,
+                  parts):
+    """.ggroups (emsar_write_ggroups): genes gene_names; groups (one id per sample), sizes (None = all 1) and the arrays as
+    EmsarHip.compare_groups_genes takes and returns them for every gene; gene_group [n_genes, G]."""
+    gs = HostRsh._genes_struct(gene_names)
+    g = np.ascontiguousarray(groups, dtype=np.int32)
+    s = None if sizes is None else np.ascontiguousarray(sizes, dtype=np.float64)
+    a = [np.ascontiguousarray(x, dtype=np.float64) for x in (gene_common, gene_group, lambda_between, p_between, lambda_within, p_within)]
+    i = [np.ascontiguousarray(x, dtype=np.int32) for x in (status, outer, evals, parts)]
+    rc = lib().emsar_write_ggroups(path.encode(), C.byref(gs), len(g), _ip(g), None if s is None else _dp(s),
+                                   *([_dp(x) for x in a] + [_ip(x) for x in i]))
+    if rc != 0:
+        raise HostError("write_ggroups rc=%d" % rc)
 
 
 def write_uprofile(path, tx_names, gene_names, gene_of_tx, usage, lower, upper, lambda_zero, lambda_one, status, outer_evals, evals, query=None):

@@ -1009,6 +1009,81 @@ int emsar_hip_compare_groups(emsar_hip_ctx *const *ctx /* [n_samples] */, int32_
                              emsar_groups_stats *stats /* or NULL */);
 int emsar_hip_compare_groups_pvalue_host(int64_t n, const double *lambda, const int32_t *df, double *p_out);
 
+/* ---- gene-level K-sample test across replicate groups: which genes changed between conditions? ----
+ * The per-transcript lines of emsar_hip_compare_groups cannot be added up, for the reasons given at the gene-level two-sample test
+ * (isoforms that trade reads at an unchanged total give several small p-values, a gene whose total moved but whose isoforms are
+ * confounded gives none), and the pairwise emsar_hip_compare_genes share a sample and cannot be combined.  The contexts, group_of, the
+ * size factors s_k, the degrees of freedom and gp are emsar_hip_compare_groups'; the gene map is that of the FIRST context
+ * (emsar_hip_set_gene_map; another context may hold the same map or none).  For gene g:
+ *     members, parts, X^k, F^k   exactly as emsar_hip_compare_genes defines them, per sample: the members with den_t > 0 in sample k take
+ *                  part there; the parts are the packed sets that hold one (by the smallest caller tid of their members), then the
+ *                  one-transcript members in closed form (by tid); X^k = the sum of theta over the members taking part, F^k = the sum
+ *                  of the parts' F; mn^k = the smallest den of the members taking part.  The parts of a gene may differ from sample to
+ *                  sample and lie in other size classes
+ *     C_g(S)       = max_x sum_{k in S} P_k(s_k x),  P_k(y) = max {F^k : X^k = y}: the isoforms and everything else stay free in every
+ *                  sample;  C_g({k}) = F_hat^k
+ *     Lambda_between = 2 (sum_g' C_g(S_g') - C_g(all)),         df_between = G - 1
+ *     Lambda_within  = 2 (sum_k F_hat^k - sum_g' C_g(S_g')),    df_within = K - G;   p_* as emsar_hip_compare_groups, WITH ITS CAVEATS: no
+ *                  over-dispersion term, conservative where an estimate sits on the boundary
+ *     path         emsar_hip_compare_groups' two-level search, the same code, with theta_t := X^k and den_t := mn^k.  The maximiser of
+ *                  F^k - lambda X^k is the problem with den_t + lambda on EVERY member taking part, lambda in (-mn^k, inf).  Where the
+ *                  gene must grow the member(s) at mn^k take mn^k (1 - v) in LDS and the others den_t - v mn^k; where it must shrink
+ *                  mn^k / (1 - v) and den_t + mn^k v / (1 - v): both stay positive in floating point (emsar_hip_compare_genes' rule).
+ *                  Each set part is one solve -- same solver, start and stopping rule as solve --, F summed with the ORIGINAL den, X
+ *                  from the same reduction; the dual value of a sample is F - lambda (X - y).  Outer point 0 is lambda = 0 in every
+ *                  sample and gives X_hat^k and F_hat^k from the code path of every later evaluation.  Stopping rules, caps and the
+ *                  choice of C_g(S) among the outer points are emsar_hip_compare_groups'.
+ *     end of the range   a sample in which the member(s) at mn^k have no reads cannot raise X^k by any lambda > -mn^k; the inner search
+ *                  then runs to v -> 1 and its dual value tends to the true P_k(y) = P_k(X_end) - mn^k (y - X_end), within dev_tol / 2
+ *                  by the bracket rule, as the transcript test treats a transcript without reads
+ *     cost         per gene one search for all samples and one per group of two or more (a single group is the all-samples search
+ *                  itself); one workgroup runs one search, the samples in ascending index: at most
+ *                  max(max_outer, 2) * |S| * max_evals * parts * max_iter passes, parts <= 64 per sample.  A gene whose parts are all
+ *                  closed form in every sample is searched on the host by the same code and nothing is launched for it.
+ *     outputs      lambda_between, lambda_within (clamped at 0), raw_between, raw_within, p_between, p_within; gene_common = x of
+ *                  C_g(all), on the scale of size 1; gene_group[i][g'] = x of C_g(S_g') (X_hat^k / s_k for a group of one);
+ *                  gene_hat[i][k] = X_hat^k, which agrees with gene_sums(solve) up to summation order; slope, outer = the all-samples
+ *                  search's; evals = the inner evaluations of all the gene's searches; parts = the parts summed over the samples
+ * status, per gene (EMSAR_GROUPS_* and EMSAR_GENE_GROUPS_TOO_LARGE), decided in this order:
+ *     NOT_RESIDENT  a member taking part lies in a streamed or a cluster set in any sample, one component holds most transcripts, or
+ *                   set_mode = 1
+ *     OUTSIDE       in some sample no member has den > 0, or the gene has no transcript
+ *     TOO_LARGE     more than 64 parts in a sample
+ *     TESTED        outputs as above
+ *     ALL_ABSENT    X_hat^k is exactly 0 in every sample: both Lambdas 0, p 1
+ *     UNCONVERGED   values are given, but a solve, an inner search or an outer search hit its cap
+ *   For NOT_RESIDENT, OUTSIDE and TOO_LARGE every numeric output is NaN and the counters are 0.
+ * Outputs are indexed by query position (by gene id when query_genes is NULL; n_query is then ignored); repeats and any order are
+ * allowed.  A gene's result depends on its parts, p, gp, the groups and the sizes alone -- not on what else is asked, the batch, the
+ * layout, MERGE_ROWS, the library's numbering or which of the other contexts hold the map.  All contexts are left as they were: a
+ * following solve, compare_groups or compare_genes returns the same bits.  Errors as emsar_hip_compare_groups, with gene ids for tids;
+ * in addition ERR_STATE when the first context has no gene map and ERR_ARG when another context holds a different one.
+ * EMSAR_HIP_GROUPS_GENES_BATCH = items per launch and class (a testing aid; the bits do not change). */
+enum { EMSAR_GENE_GROUPS_TOO_LARGE = 5 };                               /* the EMSAR_GROUPS_* statuses, and this one */
+typedef struct {
+    double  *lambda_between, *p_between, *lambda_within, *p_within, *raw_between, *raw_within, *gene_common, *slope;   /* [n_query]; may each be NULL */
+    double  *gene_group;          /* [n_query][G] */
+    double  *gene_hat;            /* [n_query][K] */
+    int32_t *status, *outer, *evals, *parts;                                /* [n_query] status; outer points; inner evaluations; parts */
+} emsar_groups_gene_outputs;
+typedef struct {
+    int64_t n_status[6];          /* distinct queried genes per status */
+    int64_t items_launched;       /* workgroups: one search each */
+    int64_t evals_sum;            /* inner evaluations summed over the searches on the device */
+    int64_t passes_sum;           /* passes summed over their solves, every part of every sample */
+    int64_t outer_sum;            /* outer points summed over the searches on the device */
+    int32_t evals_max, passes_max; /* the search with the most inner evaluations / the most passes */
+    int32_t outer_max, parts_max; /* the search with the most outer points; the most parts (all samples) of a gene that was searched */
+    int32_t df_between, df_within; /* G - 1, K - G */
+    double  min_raw_lambda;       /* the most negative of both Lambdas before clamping, 0 if none was negative */
+    double  device_ms;            /* device time of the searches (HIP events) */
+    double  total_ms;             /* wall time of the call, a first call's set building included */
+} emsar_groups_gene_stats;
+int emsar_hip_compare_groups_genes(emsar_hip_ctx *const *ctx /* [n_samples] */, int32_t n_samples, const int32_t *group_of /* [n_samples] */,
+                                   const double *size /* [n_samples] or NULL */, const emsar_em_params *p, const emsar_groups_params *gp /* or NULL */,
+                                   int32_t n_query, const int32_t *query_genes /* NULL = all genes */,
+                                   const emsar_groups_gene_outputs *out /* or NULL */, emsar_groups_gene_stats *stats /* or NULL */);
+
 /* ---- asymptotic standard errors: the inverse of the observed information at the MLE ---------------
  * How sure is theta_t, without resampling?  For a theta that maximises the likelihood of the current sample, the observed information
  * of the ACTIVE transcripts is J_ij = sum_c m_ci m_cj R_c / S_c^2 (m_ci = how often i stands in row c); its inverse is the asymptotic

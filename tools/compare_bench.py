@@ -1,6 +1,6 @@
 """Cost of the two-sample test (emsar_hip_compare) on bench.py's time_to_mle segment problem against one solve; prints one JSON object.
 
-    python tools/compare_bench.py [--genes | --usage | --groups] [--rounds 3] [--max-iter 20000] [--max-evals 40] [--seed 5] [--out FILE]
+    python tools/compare_bench.py [--genes | --usage | --groups [--genes]] [--rounds 3] [--max-iter 20000] [--max-evals 40] [--seed 5] [--out FILE]
 
 Sample A is the problem as it stands (same seeds, 100 k transcripts in families); sample B is a Poisson redraw of A's row weights (a
 technical replicate: the null holds for every transcript).  Both are uploaded into contexts of their own and solved once (the first
@@ -16,7 +16,10 @@ from this run; outer points per search and inner evaluations per outer point.
 --groups: emsar_hip_compare_groups over all transcripts in one call, K = 4 samples in two groups (0, 0, 1, 1): sample 0 is the problem as
 it stands, samples 1 to 3 are Poisson redraws of its row weights (seeds --seed, +1, +2): after one warm-up call the median wall and the
 device ms of 5 calls, the searches, outer points per search, inner evaluations per outer point and the UNCONVERGED count, next to the
-median of 5 calls of emsar_hip_compare on samples 0 and 2 and one solve, all from this run.  A record, never a test threshold."""
+median of 5 calls of emsar_hip_compare on samples 0 and 2 and one solve, all from this run.
+--groups --genes: emsar_hip_compare_groups_genes over all family genes in one call on the same four samples and groups: the same
+figures per gene search and the most parts a gene had, next to the medians of emsar_hip_compare_groups over all transcripts, of
+emsar_hip_compare_genes on samples 0 and 2 and of one solve, all from this run.  A record, never a test threshold."""
 import argparse
 import json
 import os
@@ -48,7 +51,7 @@ def main():
     solve = dict(max_iter=a.max_iter, tol=1e-10)
     out = {"n_tx": int(n_tx), "rows": int(len(rp) - 1), "max_iter": a.max_iter, "max_evals": a.max_evals, "seed": a.seed}
     if a.groups:
-        out.update(groups_record(n_tx, rp, ci, R, E, a.seed, solve))
+        out.update(groups_record(n_tx, rp, ci, R, E, a.seed, solve, family_sizes(n_tx) if a.genes else None))
         return finish(out, a.out)
     with EmsarHip(0) as A, EmsarHip(0) as B:
         for dev, w in ((A, R), (B, RB)):
@@ -103,8 +106,9 @@ def timed(f, calls):
     return runs[len(runs) // 2]
 
 
-def groups_record(n_tx, rp, ci, R, E, seed, solve, calls=5):
-    """--groups: the figures of emsar_hip_compare_groups at K = 4 in two groups, of emsar_hip_compare on samples 0 and 2 and of one solve"""
+def groups_record(n_tx, rp, ci, R, E, seed, solve, sizes=None, calls=5):
+    """--groups: the figures of emsar_hip_compare_groups at K = 4 in two groups, of emsar_hip_compare on samples 0 and 2 and of one solve;
+    sizes (the families as genes): those of emsar_hip_compare_groups_genes, next to compare_groups, compare_genes and one solve"""
     from emsar_amd import EmsarHip
     groups = (0, 0, 1, 1)
     weights = [R] + [np.random.default_rng(seed + k).poisson(R).astype(np.int32) for k in range(3)]
@@ -114,6 +118,8 @@ def groups_record(n_tx, rp, ci, R, E, seed, solve, calls=5):
             dev.upload_structure(n_tx, rp, ci)
             dev.upload_sample(w, E, None)
         th = [dev.solve(**solve)[0] for dev in devs]          # finds and packs the sets, warms up
+        if sizes is not None:
+            return groups_genes_record(devs, groups, sizes, th, solve, calls)
         wall_g, r = timed(lambda: d0.compare_groups(devs[1:], groups, **solve), calls)
         wall_c, c = timed(lambda: d0.compare(d2, **solve), calls)
         wall_s, _ = timed(lambda: d0.solve(**solve), calls)
@@ -126,6 +132,30 @@ def groups_record(n_tx, rp, ci, R, E, seed, solve, calls=5):
                 inner_evals_per_outer_point=d["evals_sum"] / max(1, d["outer_sum"]), evals_max=d["evals_max"], passes_sum=d["passes_sum"],
                 passes_max=d["passes_max"], min_raw_lambda=d["min_raw_lambda"], compare_wall_ms=1e3 * wall_c, compare_device_ms=dc["device_ms"],
                 compare_passes_sum=dc["passes_sum"], solve_wall_ms=1e3 * wall_s, wall_over_compare=wall_g / wall_c, wall_over_solve=wall_g / wall_s,
+                share_p_between_below_0_05=float(np.mean(r["p_between"][tested] < 0.05)) if tested.any() else None,
+                share_p_within_below_0_05=float(np.mean(r["p_within"][tested] < 0.05)) if tested.any() else None, solve_unchanged=bool(unchanged))
+
+
+def groups_genes_record(devs, groups, sizes, th, solve, calls):
+    """--groups --genes, on the loaded and solved contexts of groups_record"""
+    d0 = devs[0]
+    d0.set_gene_map(np.repeat(np.arange(len(sizes), dtype=np.int32), sizes), len(sizes))
+    wall_g, r = timed(lambda: d0.compare_groups_genes(devs[1:], groups, **solve), calls)
+    wall_t, t = timed(lambda: d0.compare_groups(devs[1:], groups, **solve), calls)
+    wall_c, c = timed(lambda: d0.compare_genes(devs[2], **solve), calls)
+    wall_s, _ = timed(lambda: d0.solve(**solve), calls)
+    d, dt, dc = r["stats"].as_dict(), t["stats"].as_dict(), c["stats"].as_dict()
+    tested = r["status"] == 0
+    unchanged = all(dev.solve(**solve)[0].tobytes() == x.tobytes() for dev, x in zip(devs, th))
+    return dict(call="compare_groups_genes", n_samples=len(devs), groups=list(groups), n_genes=int(len(sizes)), calls=calls, status=d["n_status"],
+                unconverged=d["n_status"]["UNCONVERGED"], searches=d["items_launched"], wall_ms=1e3 * wall_g, device_ms=d["device_ms"],
+                outer_per_search_mean=d["outer_sum"] / max(1, d["items_launched"]), outer_max=d["outer_max"],
+                inner_evals_per_outer_point=d["evals_sum"] / max(1, d["outer_sum"]), evals_max=d["evals_max"], passes_sum=d["passes_sum"],
+                passes_max=d["passes_max"], parts_max=d["parts_max"], min_raw_lambda=d["min_raw_lambda"],
+                compare_groups_wall_ms=1e3 * wall_t, compare_groups_device_ms=dt["device_ms"], compare_groups_searches=dt["items_launched"],
+                compare_genes_wall_ms=1e3 * wall_c, compare_genes_device_ms=dc["device_ms"], compare_genes_searches=dc["items_launched"],
+                solve_wall_ms=1e3 * wall_s, wall_over_compare_groups=wall_g / wall_t, wall_over_compare_genes=wall_g / wall_c,
+                wall_over_solve=wall_g / wall_s,
                 share_p_between_below_0_05=float(np.mean(r["p_between"][tested] < 0.05)) if tested.any() else None,
                 share_p_within_below_0_05=float(np.mean(r["p_within"][tested] < 0.05)) if tested.any() else None, solve_unchanged=bool(unchanged))
 
